@@ -25,6 +25,10 @@ value = megapixels decoded per second, whole job (all ranks).  Extra objects on 
                 (frames in that launch * (jxl bytes + W*H*4)) / the average HIP-event duration of one launch
   cpu_baseline  the CPU oracle (kind "port": libjxl is looked for with find_library and timed if present) built -O3 -march=native
                 on this box and run on its host cores, rank 0 at N = 1 only
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): the decoded pixels (4k: one row per image of the batch), or
+the encoded bytes (4k-encode), as float32 DIR/<name>.npy, at most 64 MB in all; a larger output is a fixed seeded sample of positions,
+listed in DIR/<name>_index.npy.  Inputs are the same from run to run, so two builds can be compared file by file.
 """
 import argparse
 import glob
@@ -164,6 +168,31 @@ def launch_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_BUDGET = 64 * 10**6   # bytes of .npy files that --dump-outputs may write in all (64 MB)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: writes {name: [uint8 tensors or arrays of one size]} as float32 DIR/<name>.npy, one flattened row per entry.  Rows
+    too long for the budget become a fixed, seeded sample of positions (the same for every row), written as DIR/<name>_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // len(outputs)
+    for name, flats in outputs.items():
+        flats = [f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in flats]
+        n = flats[0].numel()
+        keep = (share - 1024) // (4 * len(flats) + 8)   # float32 per row and position, float64 per index, .npy headers
+        if n * 4 * len(flats) + 1024 <= share:
+            rows = torch.stack([f.reshape(-1) for f in flats])
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            it = torch.from_numpy(idx).to(flats[0].device)
+            rows = torch.stack([f.reshape(-1)[it] for f in flats])
+        np.save(os.path.join(dirname, name + ".npy"), rows.cpu().numpy().astype(np.float32))
+
+
 def stage_kernels(B, chunk):
     nchunks = (B + chunk - 1) // chunk
     return {"lf_ans": ("lf_ans_kernel", 1, B), "hf_decode": ("hf_decode_kernel", 1, B), "alpha_ans": ("alpha_ans_kernel", 1, B),
@@ -206,9 +235,14 @@ def main():
                     "pictures are re-encoded by the product's own encoder before the timed region; a side measurement, not the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sync-steps", action="store_true", help="synchronise after every step (no cross-batch overlap)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB; "
+                         "larger outputs as a fixed seeded sample with DIR/<name>_index.npy)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = {"4k": 20, "16k-bands": 10, "4k-lossless": 5, "4k-encode": 10, "512-abi": 30}[args.workload]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
 
@@ -335,6 +369,9 @@ def run_4k(args, dec, rank, world, coll_dev, fence, max_over_ranks):
     stage_sum, nb = dec.stage_totals(reset=True)
     assert nb == args.steps, (nb, args.steps)
     elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        # the output set the last timed step wrote (the calls below reuse dev_out); one row per image of the batch
+        dump_outputs(args.dump_outputs, {"rgba8": outs if counter[0] & 1 else outs2})
 
     # host cost of submitting one batch into an idle pipeline (header parsing of B files, table blob, enqueue), outside the timed region:
     # it has to stay below the GPU time per step for the step to be GPU-bound
@@ -481,6 +518,8 @@ def run_side(args, dec, rank, world, fence, max_over_ranks):
             fence()
             ms = max_over_ranks((time.perf_counter() - t0) / k * 1e3)
             stages = dec.stage_times()
+            if key == main_key:
+                dumps = {"rgb8": [out]}
             api.load_image(data)
             t1 = time.perf_counter()
             api.load_image(data)
@@ -508,6 +547,7 @@ def run_side(args, dec, rank, world, fence, max_over_ranks):
             data = run()
         fence()
         ms = max_over_ranks((time.perf_counter() - t0) / args.steps * 1e3)
+        dumps = {"jxl_bytes": [np.frombuffer(data, dtype=np.uint8)]}
         stages = api.last_save_stage_times()
         back = api.load_image(data).pixels
         err = np.abs(back.astype(np.int32) - img.astype(np.int32))
@@ -531,9 +571,10 @@ def run_side(args, dec, rank, world, fence, max_over_ranks):
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run()
+            got = run()
         fence()
         ms = max_over_ranks((time.perf_counter() - t0) / args.steps * 1e3)
+        dumps = {"pixels": [got.pixels]}
         stages = api.last_load_stage_times()
         metric, workload = "megapixels/sec decode (512x512 lossy, LoadImage)", "512x512 RGBA8 lossy VarDCT (distance 1.0) through LoadImage: host buffers, callbacks, PCIe both ways"
         roof = _roof(stages, len(data) + W * H * 4, {"hf_decode": "hf_decode_kernel", "lf_ans": "lf_ans_kernel", "alpha_ans": "alpha_ans_kernel"})
@@ -547,6 +588,8 @@ def run_side(args, dec, rank, world, fence, max_over_ranks):
             extra["cpu_baseline"] = _cpu_side(lambda t: O.decode(data, num_threads=t), mp, "the CPU oracle decoding the same file (%s)" % build, seconds_budget=6.0)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumps)
     line = {"metric": metric, "value": round(world * mp / (ms * 1e-3), 2), "unit": "MP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "int32" if args.workload == "4k-lossless" else "f32", "data": "synthetic",
@@ -601,6 +644,8 @@ def run_bands(args, dec, rank, world, rehearsal, coll_dev, fence, max_over_ranks
     fence()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     stage_sum, nb = dec.stage_totals(reset=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rgba8": [bd.image()]})
     # where one band's time goes (rank 0, stage times of the last step), and the gather alone
     band_stages = dec.stage_times()
     tg = []
