@@ -163,7 +163,9 @@ JXLFILETYPEIO_API DecoderStatus jxlhip_finish(JxlHipDecoder* dec, DecoderStatus*
 
 /* Stage taps of the most recent (synchronised) batch, image `index`, for parity tests.  `name` as in
  * DESIGN.md ("lf", "qcoef", "xyb_idct", "xyb_filtered", "strategy", "raw_quant", "sharpness", "alpha", ...).
- * Copies up to `capacity` bytes device->host; returns the full byte size of the plane (0 = unknown name). */
+ * Copies up to `capacity` bytes device->host; returns the full byte size of the plane (0 = unknown name).
+ * `index` counts the batch's decoded images: a layered file contributes one per frame (in file order, in its place among the files),
+ * so in a batch with layered files it is not the file index. */
 JXLFILETYPEIO_API size_t jxlhip_read_plane(JxlHipDecoder* dec, int32_t index, const char* name, int32_t channel, void* dst,
                                            size_t capacity);
 

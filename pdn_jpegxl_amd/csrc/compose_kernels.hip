@@ -1,0 +1,179 @@
+// HIP kernel (gfx950) of layered images: the frames of an image, each decoded on its own into f32 scratch by the ordinary stages,
+// are blended onto the canvas in file order, and the displayed result leaves in the output sample type (DESIGN.md §2 has the rules,
+// §4 the measurements).
+//
+// One lane per canvas pixel.  The four reference slots of the pixel live in registers (4 slots x 4 channels), so no canvas-sized slot
+// buffers exist: every frame is read once, one 16-byte load per pixel for four channels, and the canvas is written once.  The frame descriptors are uniform across
+// a workgroup (scalar loads).  Un-premultiply, rounding to the output type and the orientation are fused into the store.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include "dev_types.h"
+#include "dev_util.h"
+#include "kernels.h"
+
+namespace jxlhip {
+namespace {
+
+__device__ __forceinline__ float Clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+
+// The four slots of a pixel as four named register quads, read and written through per-component selects: an array indexed by the
+// (uniform) slot number went to scratch memory (72-80 B per lane), even behind unrolled compares (the compiler folds them back into an
+// index); with selects the kernel has no scratch and 59 VGPRs.
+struct Slots { float4 s0, s1, s2, s3; };
+__device__ __forceinline__ float4 Sel(bool c, float4 a, float4 b) {
+  return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
+}
+__device__ __forceinline__ float4 ReadSlot(const Slots& sl, int s) {
+  return Sel(s == 0, sl.s0, Sel(s == 1, sl.s1, Sel(s == 2, sl.s2, sl.s3)));
+}
+__device__ __forceinline__ void WriteSlot(Slots& sl, int s, float4 v) {
+  sl.s0 = Sel(s == 0, v, sl.s0); sl.s1 = Sel(s == 1, v, sl.s1); sl.s2 = Sel(s == 2, v, sl.s2); sl.s3 = Sel(s == 3, v, sl.s3);
+}
+__device__ __forceinline__ float Lane(float4 v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
+
+// the frame's nch samples at (fx, fy): one 16-, 12-, 8- or 4-byte load
+__device__ __forceinline__ void LoadFrame(const ComposeFrame& fr, int nch, int fx, int fy, float (&v)[4]) {
+  const size_t i = (size_t)fy * fr.w + fx;
+  if (nch == 4) {
+    const float4 p = ((const float4*)fr.px)[i];
+    v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = p.w;
+  } else if (nch == 3) {
+    const float* p = fr.px + i * 3;
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = 0.f;
+  } else if (nch == 2) {
+    const float2 p = ((const float2*)fr.px)[i];
+    v[0] = p.x; v[1] = p.y; v[2] = 0.f; v[3] = 0.f;
+  } else {
+    v[0] = fr.px[i]; v[1] = 0.f; v[2] = 0.f; v[3] = 0.f;
+  }
+}
+
+// raw images (every frame replaces every channel): the frame's samples as its own decode wrote them in the output type, carried as bit
+// patterns - the composite then only selects, and a pixel leaves exactly as the standalone decode of its frame would write it
+__device__ __forceinline__ void LoadRaw(const ComposeFrame& fr, int nch, int out_bits, int fx, int fy, float (&v)[4]) {
+  const size_t i = ((size_t)fy * fr.w + fx) * nch;
+  const uint8_t* p = (const uint8_t*)fr.px;
+  if (out_bits == 8 && nch == 4) {
+    const uint32_t q = ((const uint32_t*)p)[i >> 2];
+#pragma unroll
+    for (int c = 0; c < 4; c++) v[c] = __uint_as_float((q >> (8 * c)) & 0xFF);
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    uint32_t q = 0;
+    if (c < nch) q = out_bits == 8 ? p[i + c] : (out_bits == 16 ? ((const uint16_t*)p)[i + c] : ((const uint32_t*)p)[i + c]);
+    v[c] = __uint_as_float(q);
+  }
+}
+
+// One channel: `old` from the channel's source slot, `ob` the alpha of the colour channels' source slot (for the alpha channel: its own
+// old value), `a` the frame's alpha sample.
+__device__ __forceinline__ float BlendSample(int mode, bool is_alpha, bool premul, bool clamp, float nw, float old, float a, float ob) {
+  if (clamp) a = Clamp01(a);
+  switch (mode) {
+    case 0: return nw;
+    case 1: return old + nw;
+    case 2: {
+      if (is_alpha) return a + ob * (1.f - a);
+      if (premul) return nw + old * (1.f - a);
+      const float A = a + ob * (1.f - a);
+      return A == 0.f ? 0.f : (nw * a + old * ob * (1.f - a)) / A;
+    }
+    case 3: return is_alpha ? old : old + nw * a;
+    default: return old * (clamp ? Clamp01(nw) : nw);
+  }
+}
+
+__global__ void compose_kernel(const ComposeImage* __restrict__ imgs, const ComposeFrame* __restrict__ frames) {
+  const ComposeImage& im = imgs[blockIdx.y];
+  const int w = im.w, h = im.h, nch = im.nch;
+  const int ai = im.has_alpha ? nch - 1 : -1;
+  // a workgroup per 256-pixel row segment, one pixel per lane: the segment's row and column come from one uniform (scalar) division per
+  // workgroup, none per pixel, and a wavefront's crop tests are on one row segment
+  const int xseg = (w + (int)blockDim.x - 1) / (int)blockDim.x;
+  for (int t = blockIdx.x; t < xseg * h; t += gridDim.x) {
+    const int y = t / xseg, x = (t - y * xseg) * (int)blockDim.x + (int)threadIdx.x;
+    if (x >= w) continue;
+    Slots sl;
+    sl.s0 = sl.s1 = sl.s2 = sl.s3 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float res[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < im.count; k++) {
+      const ComposeFrame& fr = frames[im.first + k];
+      const float4 oc = ReadSlot(sl, fr.source[0]), oa = ReadSlot(sl, fr.source[1]);
+      const float old_c[4] = {oc.x, oc.y, oc.z, oc.w}, old_a[4] = {oa.x, oa.y, oa.z, oa.w};
+      const int fx = x - fr.x0, fy = y - fr.y0;
+      if (fx >= 0 && fy >= 0 && fx < fr.w && fy < fr.h) {
+        float nw[4];
+        if (im.raw) LoadRaw(fr, nch, im.out_bits, fx, fy, nw);
+        else LoadFrame(fr, nch, fx, fy, nw);
+        const float a = ai >= 0 ? Lane(make_float4(nw[0], nw[1], nw[2], nw[3]), ai) : 1.f;
+        const float ob_c = Lane(oc, ai), ob_a = Lane(oa, ai);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          const bool is_alpha = c == ai;
+          const int g = is_alpha ? 1 : 0;
+          res[c] = c >= nch ? 0.f : BlendSample(fr.mode[g], is_alpha, im.premul != 0, fr.clamp[g] != 0, nw[c], is_alpha ? old_a[c] : old_c[c], a,
+                                                 is_alpha ? ob_a : ob_c);
+        }
+      } else {   // outside the crop: the source slot as it is
+#pragma unroll
+        for (int c = 0; c < 4; c++) res[c] = c == ai ? old_a[c] : old_c[c];
+      }
+      if (fr.save >= 0) WriteSlot(sl, fr.save, make_float4(res[0], res[1], res[2], res[3]));
+    }
+    // the displayed image: un-premultiply (as modular_out_kernel), round to the output type, store at the oriented position
+    if (im.premul && ai >= 0 && !im.raw) {
+      const float unmul = 1.0f / fmaxf(1.0f / 67108864.0f, Lane(make_float4(res[0], res[1], res[2], res[3]), ai));
+#pragma unroll
+      for (int c = 0; c < 4; c++) if (c < ai) res[c] *= unmul;
+    }
+    int ox = x, oy = y, ow = w;
+    switch (im.orientation) {
+      case 2: ox = w - 1 - x; break;
+      case 3: ox = w - 1 - x; oy = h - 1 - y; break;
+      case 4: oy = h - 1 - y; break;
+      case 5: ox = y; oy = x; ow = h; break;
+      case 6: ox = h - 1 - y; oy = x; ow = h; break;
+      case 7: ox = h - 1 - y; oy = w - 1 - x; ow = h; break;
+      case 8: ox = y; oy = w - 1 - x; ow = h; break;
+      default: break;
+    }
+    const size_t o = (size_t)oy * ow + ox;
+    if (im.raw) {
+      if (im.out_bits == 8 && nch == 4) {
+        uint32_t px = 0;
+#pragma unroll
+        for (int c = 0; c < 4; c++) px |= __float_as_uint(res[c]) << (8 * c);
+        ((uint32_t*)im.out)[o] = px;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+          if (c < nch) StoreOutSample(im.out, o * nch + c, __float_as_uint(res[c]), im.out_bits);
+      }
+      continue;
+    }
+    // rounding half up like modular_out_kernel (not v_cvt_pk_u8_f32, which rounds ties to even): a layered file whose frames replace
+    // decodes to the same bytes as its frames would alone
+    if (im.out_bits == 8 && nch == 4) {   // the common layout: one 4-byte store
+      uint32_t px = 0;
+#pragma unroll
+      for (int c = 0; c < 4; c++) px |= FloatToOutBits(res[c], 8, 0) << (8 * c);
+      ((uint32_t*)im.out)[o] = px;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; c++)
+        if (c < nch) StoreOutSample(im.out, o * nch + c, FloatToOutBits(res[c], im.out_bits, im.out_float), im.out_bits);
+    }
+  }
+}
+
+}  // namespace
+
+void LaunchCompose(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_segments, hipStream_t s) {
+  if (nimg <= 0) return;
+  const unsigned blocks = (unsigned)std::max(1, std::min(1 << 20, max_segments));
+  hipLaunchKernelGGL(compose_kernel, dim3(blocks, nimg), dim3(256), 0, s, imgs, frames);
+}
+
+}  // namespace jxlhip

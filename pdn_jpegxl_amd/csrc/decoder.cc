@@ -135,6 +135,11 @@ struct JxlHipDecoder {
     uint32_t* h_status = nullptr; size_t h_status_cap = 0;
     int n = 0;
     std::vector<ParsedFrame> frames;
+    // layered images: n counts images of the batch (a layered file has one per frame), nfiles the caller's files; file_of maps an image
+    // to its file (empty: one image per file); files keeps the parse of each layered file (the codestream its frames point into)
+    int nfiles = 0;
+    std::vector<int> file_of;
+    std::vector<ParsedFrame> files;
     std::vector<DevImage> imgs;          // host copies (device pointers inside)
     std::vector<int> parse_status;
     std::vector<std::string> parse_msg;
@@ -424,6 +429,57 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       for (auto& t : th) t.join();
     }
   }
+  // ---- layered images: every frame up to the displayed one becomes an image of the batch, decoded like any other into f32 scratch;
+  // compose_kernel blends them onto the canvas at the end.  Status words stay per image; Finish folds them per file.
+  S.nfiles = n;
+  S.file_of.clear();
+  S.files.clear();
+  struct Composite { int file, first, count; std::vector<int> save; uint8_t* out; };
+  std::vector<Composite> comps;
+  std::vector<const uint8_t*> x_dev_data;
+  std::vector<uint8_t*> x_dev_out;
+  for (int i = 0; i < n; i++)
+    if (parse_status[i] == DecoderStatus_Ok && frames[i].layers && band_rows > 0) {
+      parse_status[i] = DecoderStatus_DecodeError;
+      parse_msg[i] = "band decode of a layered image is not supported";
+    }
+  bool any_layered = false;
+  for (int i = 0; i < n; i++) any_layered |= parse_status[i] == DecoderStatus_Ok && frames[i].layers != nullptr;
+  if (any_layered) {
+    std::vector<ParsedFrame> xf;
+    std::vector<int> xst;
+    std::vector<std::string> xmsg;
+    S.files.reserve(n);
+    for (int i = 0; i < n; i++) {
+      if (parse_status[i] == DecoderStatus_Ok && frames[i].layers) {
+        std::shared_ptr<Layers> lay = frames[i].layers;
+        comps.push_back(Composite{i, (int)xf.size(), (int)lay->frames.size(), lay->save, dev_out[i]});
+        for (auto& fr : lay->frames) {
+          fr.orientation = 1;   // frames stay in codestream orientation; the compositor orients the displayed image
+          xf.push_back(std::move(fr));
+          xst.push_back(DecoderStatus_Ok);
+          xmsg.emplace_back();
+          S.file_of.push_back(i);
+          x_dev_data.push_back(dev_data ? dev_data[i] : nullptr);
+          x_dev_out.push_back(nullptr);
+        }
+        S.files.push_back(std::move(frames[i]));
+        continue;
+      }
+      xf.push_back(std::move(frames[i]));
+      xst.push_back(parse_status[i]);
+      xmsg.push_back(parse_msg[i]);
+      S.file_of.push_back(i);
+      x_dev_data.push_back(dev_data ? dev_data[i] : nullptr);
+      x_dev_out.push_back(dev_out[i]);
+    }
+    frames.swap(xf);
+    parse_status.swap(xst);
+    parse_msg.swap(xmsg);
+    n = (int)frames.size();
+    if (dev_data) dev_data = x_dev_data.data();
+    dev_out = x_dev_out.data();
+  }
   // frames that fit one group: their HfGlobal can only be located once the LF group has been decoded (one bit stream)
   for (int i = 0; i < n; i++) {
     if (parse_status[i] != DecoderStatus_Ok || !frames[i].single || frames[i].encoding != 0) continue;
@@ -465,8 +521,19 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     size_t mod_chan, mod_desc, wp_lf, wp_grp, lf_end, alpha32;
     size_t lf[3], lf_tmp[3], lfq[3], lf_extra, rawq, sharp, ytox, ytob, binfo, lf_desc, lf_count, alpha_desc, blk_list, blk_count, bitpos, tile_list, tmp[3], xyb[3], inv_sigma, alpha;
     size_t orient_tmp = 0;   // frames with an orientation other than 1 are decoded here, then laid out as displayed in the caller's buffer
+    size_t layer_px = 0;     // frames of a layered image: w*h*nch f32 samples for the compositor
   };
   std::vector<PerImg> L((size_t)n);
+  // blob space of a codestream uploaded from the host: once per file (every frame of a layered file points into the same bytes)
+  std::vector<size_t> file_cs((size_t)S.nfiles, 0);   // offset + 1
+  std::vector<uint8_t> cs_put((size_t)S.nfiles, 0);
+  auto take_cs = [&](int i) {
+    const ParsedFrame& f = frames[i];
+    if (!f.is_layer) return blob.Take(f.cs_size + 16);
+    size_t& o = file_cs[S.file_of[i]];
+    if (!o) o = blob.Take(f.cs_size + 16) + 1;
+    return o - 1;
+  };
   // the images' status words (64 B each) lie side by side: ONE copy brings them back (a copy per image was 384 five-microsecond copy
   // kernels at the end of the pixel stream - 2 ms of the step - and as many API calls)
   const size_t z_status_base = ws_zero.Take((size_t)std::max(1, n) * 64);
@@ -518,7 +585,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     if (f.encoding == 1) {
       // Modular (lossless) frame: whole-image int32 channel planes, no VarDCT workspace
       const bool resident_m = dev_data && dev_data[i] && f.cs_contiguous;
-      l.cs = resident_m ? 0 : blob.Take(f.cs_size + 16);
+      l.cs = resident_m ? 0 : take_cs(i);
       l.z_status = z_status_base + (size_t)i * 64;
       for (auto& pl : f.mod_planes) l.mod_planes.push_back(ws.Take(4 * (size_t)std::max(1, pl.w) * std::max(1, pl.h)));
       const size_t nsec = 1 + (size_t)f.nlf + f.ng;
@@ -527,6 +594,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       if (f.tree_uses_wp) l.wp_grp = ws.Take(nsec * 10 * (f.group_dim + 2) * 4);
       if (f.mcode.lz77) l.lz_mod = ws.Take(nsec * ((size_t)4 << 20)) + 1;
       n_mod_tasks += f.single ? 1 : ((int)nsec + mod_lanes - 1) / mod_lanes;
+      if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * (f.layer_f32 ? 4 : OutBytesPerSample(f)));
       continue;
     }
     l.a_cmap = blob.Take(f.acode.ctx_map.size());
@@ -544,7 +612,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       if (own_dq || !f.custom_order[o][0].empty() || !f.custom_order[o][1].empty() || !f.custom_order[o][2].empty()) l.scan[q] = blob.Take(8 * 3 * (size_t)dq_n[q], 256) + 1;
     }
     const bool resident = dev_data && dev_data[i] && f.cs_contiguous;
-    l.cs = resident ? 0 : blob.Take(f.cs_size + 16);
+    l.cs = resident ? 0 : take_cs(i);
     if (PlanColor(f).transfer == 5) l.trc_lut = blob.Take(4 * 3 * 4096, 256) + 1;
     l.z_cellinfo = ws_zero.Take(4 * cells);
     l.z_status = z_status_base + (size_t)i * 64;
@@ -591,6 +659,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     chunk_pix = std::max(chunk_pix, pix);
     l.inv_sigma = ws.Take(4 * cells);
     l.alpha = ws.Take((size_t)f.xsize * f.ysize * OutBytesPerSample(f));
+    if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));   // (never f32: checked on the host)
     l.lf_end = ws.Take(8);
     if (f.tree_uses_wp) { l.wp_lf = ws.Take((size_t)f.nlf * kWpLfInts * 4); l.wp_grp = ws.Take((size_t)f.ng * 10 * (kGroupDim + 2) * 4); }
     {
@@ -743,6 +812,11 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   const size_t off_lf_ans_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_lf_ans));
   const size_t off_mod_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_mod_tasks));
   const size_t off_alpha_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_alpha_wg));
+  size_t off_comp_imgs = 0, off_comp_frames = 0;
+  if (!comps.empty()) {
+    off_comp_imgs = blob.Take(sizeof(ComposeImage) * comps.size());
+    off_comp_frames = blob.Take(sizeof(ComposeFrame) * (size_t)n);
+  }
   const size_t zero_bytes = Align(ws_zero.off, 256);
   EnsureBlob(blob.off);
   EnsureWs(zero_bytes + ws.off);
@@ -868,7 +942,13 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     d.tree_size = (int32_t)f.tree.size();
     const bool resident = dev_data && dev_data[i] && f.cs_contiguous;
     if (resident) d.cs = dev_data[i] + f.cs_file_offset;
-    else { put(l.cs, f.cs, f.cs_size); d.cs = d_blob + l.cs; }
+    else {
+      // the frames of a layered file share one upload of its codestream
+      const int file = S.file_of.empty() ? i : S.file_of[i];
+      if (!f.is_layer || !cs_put[file]) put(l.cs, f.cs, f.cs_size);
+      if (f.is_layer) cs_put[file] = 1;
+      d.cs = d_blob + l.cs;
+    }
     d.cs_size = f.cs_size;
     if (f.encoding == 1) {
       d.is_modular = 1;
@@ -912,6 +992,10 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       d.status = (uint32_t*)(wz + l.z_status);
       status_off[i] = l.z_status;
       d.out = f.orientation == 1 ? dev_out[i] : wr + l.orient_tmp;
+      if (f.is_layer) d.out = wr + l.layer_px;
+      if (f.layer_f32) {   // unclamped f32 samples in the image's colour space; un-premultiply waits for the compositor
+        d.out_bits = 32; d.out_float = 1; d.unpremultiply = 0;
+      }
       auto code_lds_m = [](const HostCode& hc) { return 8 + 8 * hc.alias.size() + 4 * hc.cfg.size() + hc.ctx_map.size(); };
       // (one section per wavefront with row buffers: three rows and the leaf grid of modular_uniform.h instead of one row per lane)
       const size_t mod_rows = (mod_lanes == 1 && mod_rb) ? (size_t)3 * mod_rb * 4 + (size_t)kUniGridCells * 16 : (size_t)mod_lanes * mod_rb * 4;
@@ -1017,6 +1101,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     }
     if (f.tree_uses_wp) { d.wp_lf = (int32_t*)(wr + l.wp_lf); d.wp_grp = (int32_t*)(wr + l.wp_grp); d.wp_grp_ints = 10 * (kGroupDim + 2); }
     d.out = f.orientation == 1 ? dev_out[i] : wr + l.orient_tmp;
+    if (f.is_layer) d.out = wr + l.layer_px;   // a frame of a layered image whose frames all replace: output-type samples
     // Loop-filter routing.  Frames with EPF iterations run iteration 1 (+ Gaborish when no iteration 0 has to come between them) and
     // iteration 2 in the streaming kernels: fused_gab_epf1 = 1: one kernel -> output; 2: two kernels, f32 rows (stream_mid) between
     // them.  Three iterations (distance >= 4): Gaborish and iteration 0 first, as LDS-tiled stage kernels, then the two streaming
@@ -1156,6 +1241,42 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (Knob("JXLHIP_HF_GLOBAL")) lds_hf = kLdsMax + 1;
   if (Knob("JXLHIP_ALPHA_GLOBAL")) lds_alpha = kLdsMax + 1;
   if (Knob("JXLHIP_LF_GLOBAL")) lds_lf = kLdsMax + 1;
+  int max_segments = 1;
+  if (!comps.empty()) {
+    // the compositor's tables: one record per layered image, one per frame (frame records indexed like the batch's images)
+    ComposeImage* cimgs = (ComposeImage*)(h_blob + off_comp_imgs);
+    ComposeFrame* cframes = (ComposeFrame*)(h_blob + off_comp_frames);
+    for (size_t k = 0; k < comps.size(); k++) {
+      const Composite& c = comps[k];
+      const ParsedFrame& top = S.files[k];
+      ComposeImage& ci = cimgs[k];
+      memset(&ci, 0, sizeof(ci));
+      ci.w = (int32_t)top.xsize; ci.h = (int32_t)top.ysize;
+      ci.has_alpha = top.alpha_index >= 0 ? 1 : 0;
+      ci.nch = top.ncolor + ci.has_alpha;
+      ci.premul = (ci.has_alpha && top.ec[top.alpha_index].alpha_associated) ? 1 : 0;
+      ci.orientation = (int32_t)top.orientation;
+      ci.out_bits = 8 * (int32_t)OutBytesPerSample(top); ci.out_float = top.exp_bits ? 1 : 0;
+      ci.first = c.first; ci.count = c.count;
+      ci.raw = top.layers->raw ? 1 : 0;
+      ci.out = c.out;
+      max_segments = std::max(max_segments, (int)top.ysize * (int)((top.xsize + 255) / 256));   // compose_kernel: 256-pixel row segments
+      for (int j = 0; j < c.count; j++) {
+        const ParsedFrame& f = frames[c.first + j];
+        ComposeFrame& cf = cframes[c.first + j];
+        memset(&cf, 0, sizeof(cf));
+        cf.px = (const float*)imgs[c.first + j].out;
+        cf.x0 = f.have_crop ? f.crop_x0 : 0; cf.y0 = f.have_crop ? f.crop_y0 : 0;
+        cf.w = (int32_t)f.xsize; cf.h = (int32_t)f.ysize;
+        const BlendInfo& bc = f.blend[0];
+        const BlendInfo& ba = ci.has_alpha ? f.blend[1 + top.alpha_index] : bc;
+        cf.mode[0] = (int32_t)bc.mode; cf.mode[1] = (int32_t)ba.mode;
+        cf.source[0] = (int32_t)bc.source; cf.source[1] = (int32_t)ba.source;
+        cf.clamp[0] = (int32_t)bc.clamp; cf.clamp[1] = (int32_t)ba.clamp;
+        cf.save = c.save[j];
+      }
+    }
+  }
   memcpy(h_blob + off_imgs, imgs.data(), sizeof(DevImage) * imgs.size());
   d_imgs = (DevImage*)(d_blob + off_imgs);
   // ---- 4. enqueue: LF chain on s_lf, everything that needs the block layout on the main stream
@@ -1270,6 +1391,10 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     LaunchModularOut(d_imgs, n, max_mod_pixels, stream);
     Mark("modular", stream, 2);
   }
+  if (!comps.empty()) {
+    LaunchCompose((const ComposeImage*)(d_blob + off_comp_imgs), (const ComposeFrame*)(d_blob + off_comp_frames), (int)comps.size(), max_segments, stream);
+    Mark("compose", stream, 2);
+  }
   for (int i = 0; i < n; i++)
     if (parse_status[i] == DecoderStatus_Ok && frames[i].orientation != 1) {
       const ParsedFrame& f = frames[i];
@@ -1289,7 +1414,11 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     (void)st;
     if (debug_taps) CopyPlaneTap(2);
   } else if (statuses) {
-    for (int i = 0; i < n; i++) statuses[i] = parse_status[i];
+    for (int i = 0; i < S.nfiles; i++) statuses[i] = DecoderStatus_Ok;
+    for (int i = n - 1; i >= 0; i--) {   // a file's first failing image wins
+      const int file = S.file_of.empty() ? i : S.file_of[i];
+      if (parse_status[i] != DecoderStatus_Ok) statuses[file] = parse_status[i];
+    }
   }
 }
 
@@ -1430,7 +1559,10 @@ DecoderStatus JxlHipDecoder::Finish(DecoderStatus* statuses, ErrorInfo* err) {
   Slot& S = Last();
   WaitSlot(S);
   DecoderStatus worst = DecoderStatus_Ok;
+  // statuses and messages are per file: the frames of a layered file are images of their own here, and any failing one fails the file
+  std::vector<DecoderStatus> file_st((size_t)S.nfiles, DecoderStatus_Ok);
   for (int i = 0; i < S.n; i++) {
+    const int file = S.file_of.empty() ? i : S.file_of[i];
     DecoderStatus st = S.parse_status[i];
     if (st != DecoderStatus_Ok) {
       if (worst == DecoderStatus_Ok) SetErr(err, "%s", S.parse_msg[i].c_str());
@@ -1439,15 +1571,16 @@ DecoderStatus JxlHipDecoder::Finish(DecoderStatus* statuses, ErrorInfo* err) {
       st = DecoderStatus_DecodeError;
       if (worst == DecoderStatus_Ok) {
         const uint32_t* w = S.h_status + (size_t)i * 16;   // [3..7]: last failing section + 1 of lf_ans / lf_finish / hf_decode / alpha_ans / modular
-        if (bits & kErrUnsupportedTransform) SetErr(err, "AFV transforms are not supported (image %d, LF group section %u)", i, w[4]);
+        if (bits & kErrUnsupportedTransform) SetErr(err, "AFV transforms are not supported (image %d, LF group section %u)", file, w[4]);
         else SetErr(err, "GPU decode failed (flags 0x%x:%s%s%s%s%s; image %d, sections lf %u hf %u alpha %u)", bits, bits & kErrBitstream ? " corrupt-bitstream" : "",
                bits & kErrUnsupportedHeader ? " unsupported-modular-header" : "", bits & kErrUnsupportedTree ? " unsupported-tree" : "",
-               bits & kErrBlockLayout ? " invalid-varblock-layout" : "", bits & kErrRange ? " value-out-of-range" : "", i, w[3], w[5], w[6]);
+               bits & kErrBlockLayout ? " invalid-varblock-layout" : "", bits & kErrRange ? " value-out-of-range" : "", file, w[3], w[5], w[6]);
       }
     }
-    if (statuses) statuses[i] = st;
+    if (st != DecoderStatus_Ok && file_st[file] == DecoderStatus_Ok) file_st[file] = st;
     if (st != DecoderStatus_Ok && worst == DecoderStatus_Ok) worst = st;
   }
+  if (statuses) for (int f = 0; f < S.nfiles; f++) statuses[f] = file_st[f];
   if (worst == DecoderStatus_Ok && sticky_status != DecoderStatus_Ok) {
     worst = sticky_status;
     SetErr(err, "%s", sticky_error.c_str());

@@ -215,6 +215,26 @@ struct DevImage {
   uint32_t* status;         // [0] error bits, [1..] debug
 };
 
+// Layered images (compose_kernel, compose_kernels.hip): every frame is decoded on its own into f32 scratch, then one launch blends
+// the frames of every layered image of a batch onto their canvases and writes the displayed image in the output type.
+struct ComposeFrame {
+  const float* px;          // w*h pixels of nch f32 samples (the frame's output kernel wrote them), integer samples as v / (2^bits - 1);
+                            // raw images: w*h pixels of nch samples of the output type, as the frame's own decode writes them
+  int32_t x0, y0, w, h;     // the frame's crop on the canvas (codestream orientation; may start at negative offsets and reach past it)
+  int32_t mode[2];          // blend mode of [0] the colour channels, [1] the alpha channel: 0 replace, 1 add, 2 blend, 3 alpha-weighted add, 4 mul
+  int32_t source[2];        // reference slot each of them blends onto (an empty slot reads as 0)
+  int32_t clamp[2];         // clamp the blending alpha (and, for mul, the new sample) to [0, 1]
+  int32_t save;             // slot the blended canvas is saved to, -1: none
+  int32_t pad;
+};
+struct ComposeImage {
+  int32_t w, h, nch, has_alpha;                 // canvas; nch = colour channels + alpha, alpha last
+  int32_t premul, orientation, out_bits, out_float;
+  int32_t first, count;                         // frames [first, first + count) of the frame table, the last one is displayed
+  int32_t raw, pad0;                            // raw: every frame replaces every channel; frames hold output-type samples (px as bytes)
+  uint8_t* out;                                 // the displayed image, oriented, interleaved samples of the output type
+};
+
 constexpr int kUniGridCells = 2048;   // LDS grid (16-byte leaf records) of the one-section-per-wavefront per-sample Modular decoder (modular_uniform.h)
 constexpr int kBinfoInts = 2 * 1024 + 2 * 65536 + 65536 + 65536 + 64;   // ... + prefix sums of the block widths (placement)
 constexpr int kWpLfInts = 10 * (65536 + 2);   // widest channel of an LF group section: the block-info rows

@@ -547,12 +547,14 @@ void ReadImageHeader(Bits& r, ParsedFrame& f) {
   REQUIRE(r.ok(), "truncated image header");
 }
 
-void ReadBlending(Bits& r, size_t nec, bool partial, uint32_t* mode) {
-  *mode = r.U32(V(0), V(1), V(2), B(2, 3));
-  if (nec && (*mode == 2 || *mode == 3)) r.U32(V(0), V(1), V(2), B(3, 3));
-  if (nec && *mode >= 2 && *mode <= 4) r.b();
-  if (*mode != 0 || partial) r.u(2);
+void ReadBlending(Bits& r, size_t nec, bool partial, BlendInfo* b) {
+  b->mode = r.U32(V(0), V(1), V(2), B(2, 3));
+  if (nec && (b->mode == 2 || b->mode == 3)) b->alpha = r.U32(V(0), V(1), V(2), B(3, 3));
+  if (nec && b->mode >= 2 && b->mode <= 4) b->clamp = r.b();
+  if (b->mode != 0 || partial) b->source = r.u(2);
 }
+
+void FrameGeometry(ParsedFrame& f);
 
 void ReadFrameHeader(Bits& r, ParsedFrame& f) {
   const float w1 = 0.115169525f, w2 = 0.061248592f;
@@ -560,10 +562,15 @@ void ReadFrameHeader(Bits& r, ParsedFrame& f) {
   for (int i = 0; i < 8; i++) f.epf_sharp_lut[i] = i / 7.0f;
   f.epf_channel_scale[0] = 40.f; f.epf_channel_scale[1] = 5.f; f.epf_channel_scale[2] = 3.5f;
   f.epf_quant_mul = 0.46f; f.epf_pass0_sigma_scale = 0.9f; f.epf_pass2_sigma_scale = 6.5f; f.epf_border_sad_mul = 2.0f / 3;
-  bool have_crop = false, do_ycbcr = false;
-  uint32_t upsampling = 1, blend = 0, duration = 0, save_ref = 0;
-  int32_t x0 = 0, y0 = 0;
+  bool& have_crop = f.have_crop;
+  bool& do_ycbcr = f.do_ycbcr;
+  uint32_t& upsampling = f.upsampling;
+  uint32_t& duration = f.duration;
+  uint32_t& save_ref = f.save_ref;
+  int32_t& x0 = f.crop_x0;
+  int32_t& y0 = f.crop_y0;
   uint32_t cw = 0, ch = 0;
+  f.blend.assign(1 + f.ec.size(), BlendInfo());
   if (!r.b()) {
     f.frame_type = r.u(2);
     f.encoding = r.u(1);
@@ -601,15 +608,14 @@ void ReadFrameHeader(Bits& r, ParsedFrame& f) {
     bool normal = f.frame_type == 0 || f.frame_type == 3;
     bool full = !have_crop || (x0 <= 0 && y0 <= 0 && x0 + (int64_t)cw >= f.xsize && y0 + (int64_t)ch >= f.ysize);
     if (normal) {
-      ReadBlending(r, f.ec.size(), !full, &blend);
-      for (size_t i = 0; i < f.ec.size(); i++) { uint32_t m; ReadBlending(r, f.ec.size(), !full, &m); }
+      for (auto& b : f.blend) ReadBlending(r, f.ec.size(), !full, &b);
       if (f.have_animation) { duration = r.U32(V(0), V(1), B(8), B(32)); if (f.have_timecodes) r.u(32); }
       f.is_last = r.b();
     } else f.is_last = false;
     if (f.frame_type != 1 && !f.is_last) save_ref = r.u(2);
     if (f.frame_type != 1) {
       bool can_ref = !f.is_last && (duration == 0 || save_ref != 0);
-      if (f.frame_type == 2 || (full && blend == 0 && can_ref)) r.b();
+      if (f.frame_type == 2 || (full && f.blend[0].mode == 0 && can_ref)) f.save_before_ct = r.b();
     }
     uint32_t nl = r.U32(V(0), B(4), B(5, 16), B(10, 48));
     f.name.resize(nl);
@@ -631,20 +637,65 @@ void ReadFrameHeader(Bits& r, ParsedFrame& f) {
     }
     r.SkipExtensions();
   }
+  REQUIRE(r.ok(), "truncated frame header");
+  // a crop that covers the canvas exactly is no crop; otherwise the frame is as large as its crop
+  if (have_crop && x0 == 0 && y0 == 0 && cw == f.xsize && ch == f.ysize) have_crop = false;
+  if (have_crop) {
+    REQUIRE(cw > 0 && ch > 0, "empty frame crop");
+    f.xsize = cw; f.ysize = ch;
+  }
+  FrameGeometry(f);
+}
+
+// The displayed image is this frame alone: it is displayed, covers the canvas and replaces what was there.  The reference keeps the
+// first frame its decoder library hands out (Decoder/JxlDecoder.cpp:398-400), and that library composes layers: the first DISPLAYED
+// frame is the first frame alone only if it ends the file or is an animation frame with a duration.
+bool IsDisplayed(const ParsedFrame& f) { return f.is_last || (f.have_animation && f.duration > 0); }
+bool ReplacesAll(const ParsedFrame& f) {
+  for (auto& b : f.blend) if (b.mode != 0) return false;
+  return true;
+}
+// (every channel's blend mode: a lone frame that multiplies its alpha onto the empty canvas is a layered image - DESIGN.md §2 gives 0)
+bool IsSingleFrameImage(const ParsedFrame& f) {
+  return IsDisplayed(f) && !f.have_crop && ReplacesAll(f) && (f.frame_type == 0 || f.frame_type == 3);
+}
+
+void CheckSingleFrame(const ParsedFrame& f) {
   REQUIRE(f.frame_type == 0 || f.frame_type == 3, "first frame is not a regular frame (LF / reference frames are not supported yet)");
-  REQUIRE(!have_crop && upsampling == 1, "cropped or upsampled frames are not supported yet");
-  REQUIRE(!do_ycbcr, "YCbCr frames are not supported yet");
-  // The reference keeps the first frame its decoder library hands out (Decoder/JxlDecoder.cpp:398-400), and that library composes
-  // layers: the first DISPLAYED frame is this frame alone only if it ends the file or is an animation frame with a duration.
-  REQUIRE(f.is_last || (f.have_animation && duration > 0), "images composed of several layers are not supported yet");
-  REQUIRE(blend == 0, "frame blend modes other than replace are not supported yet");
+  REQUIRE(f.upsampling == 1, "cropped or upsampled frames are not supported yet");
+  REQUIRE(!f.do_ycbcr, "YCbCr frames are not supported yet");
+}
+
+// One frame of a layered image: what the compositor (decoder.cc, compose_kernel) and the per-frame decode accept.
+void CheckLayerFrame(const ParsedFrame& f, size_t index) {
+  const std::string at = " (layered image, frame " + std::to_string(index) + ")";
+  if (f.frame_type == 2) Fail("reference-only frames are not supported yet" + at);
+  if (f.frame_type == 1 || (f.flags & 32)) Fail("LF frames are not supported yet" + at);
+  if (f.upsampling != 1) Fail("upsampled frames are not supported yet" + at);
+  if (f.flags & 2) Fail("patches are not supported yet" + at);
+  REQUIRE(!f.do_ycbcr, "YCbCr frames are not supported yet");
+  if (f.black_index >= 0) Fail("layered CMYK images are not supported");
+  if (f.encoding == 0) {
+    // which colour space libjxl blends XYB frames in is not pinned here; neither is what it saves before the colour transform
+    for (auto& b : f.blend) if (b.mode != 0) Fail("blend modes other than replace on lossy (XYB) frames are not supported" + at);
+    if (f.save_before_ct) Fail("save_before_ct on lossy (XYB) frames is not supported" + at);
+  }
+  for (size_t c = 0; c < f.blend.size(); c++) {
+    const BlendInfo& b = f.blend[c];
+    if (b.mode > 4) Fail("unknown frame blend mode" + at);
+    // kBlend / kAlphaWeightedAdd weigh by an alpha channel: it must be the image's one alpha channel
+    if ((b.mode == 2 || b.mode == 3) && (f.alpha_index < 0 || (int)b.alpha != f.alpha_index))
+      Fail("blend modes weighted by a channel other than the alpha channel are not supported" + at);
+  }
+}
+
+void FrameGeometry(ParsedFrame& f) {
   f.group_dim = 128u << f.group_size_shift;
   f.w8 = (f.xsize + 7) / 8; f.h8 = (f.ysize + 7) / 8;
   f.xg = (f.xsize + f.group_dim - 1) / f.group_dim; f.yg = (f.ysize + f.group_dim - 1) / f.group_dim;
   f.ng = f.xg * f.yg;
   f.xlf = (f.xsize + f.group_dim * 8 - 1) / (f.group_dim * 8); f.ylf = (f.ysize + f.group_dim * 8 - 1) / (f.group_dim * 8);
   f.nlf = f.xlf * f.ylf;
-  REQUIRE(r.ok(), "truncated frame header");
 }
 
 void ReadToc(Bits& r, ParsedFrame& f, size_t frame_base_bits) {
@@ -668,6 +719,7 @@ void ReadToc(Bits& r, ParsedFrame& f, size_t frame_base_bits) {
   std::vector<uint64_t> phys(n + 1, base);
   for (size_t i = 0; i < n; i++) phys[i + 1] = phys[i] + sizes[i];
   REQUIRE(phys[n] <= f.cs_size, "sections exceed the codestream");
+  f.frame_end = phys[n];
   f.sec_off.resize(n);
   f.sec_size.resize(n);
   for (size_t i = 0; i < n; i++) {
@@ -1488,19 +1540,8 @@ void ReadIcc(Bits& r, ParsedFrame& f) {
   if (!IccUnpredict(enc, &f.icc, &why)) Fail(why);
 }
 
-void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame& f) {
-  f = ParsedFrame();
-  SplitContainer(data, size, f);
-  if (!(f.cs_size >= 2 && f.cs[0] == 0xFF && f.cs[1] == 0x0A)) Fail("invalid codestream signature", stInvalidSignature);
-  Bits r(f.cs, f.cs_size);
-  r.Skip(16);
-  ReadImageHeader(r, f);
-  if (f.color.want_icc) ReadIcc(r, f);
-  r.Align();
-  size_t frame_base = r.pos();
-  ReadFrameHeader(r, f);
-  ReadToc(r, f, frame_base);
-  if (headers_only) return;
+// Everything of one frame after its TOC: what the GPU path accepts, LfGlobal, HfGlobal.
+void ParseFrameBody(ParsedFrame& f) {
   auto depth_ok = [](uint32_t bits, uint32_t exp) { return exp ? ((bits == 32 && exp == 8) || (bits == 16 && exp == 5)) : (bits >= 1 && bits <= 16); };
   if (!depth_ok(f.bits, f.exp_bits)) Fail("only integer samples of up to 16 bits and binary16 / binary32 float samples are supported yet");
   if (f.alpha_index >= 0 && !depth_ok(f.ec[f.alpha_index].bits, f.ec[f.alpha_index].exp_bits))
@@ -1544,6 +1585,75 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
     Bits s(f.cs + f.sec_off[1 + f.nlf], f.sec_size[1 + f.nlf]);
     ReadHfGlobal(s, f, f.custom_dq);
   }
+}
+
+void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame& f) {
+  f = ParsedFrame();
+  SplitContainer(data, size, f);
+  if (!(f.cs_size >= 2 && f.cs[0] == 0xFF && f.cs[1] == 0x0A)) Fail("invalid codestream signature", stInvalidSignature);
+  Bits r(f.cs, f.cs_size);
+  r.Skip(16);
+  ReadImageHeader(r, f);
+  if (f.color.want_icc) ReadIcc(r, f);
+  r.Align();
+  const size_t frame_base = r.pos();
+  // the image header alone (without the container's buffers, which stay with f): where every frame of a layered image starts from
+  ParsedFrame image;
+  {
+    auto cs_copy = std::move(f.cs_copy);
+    auto owned = std::move(f.owned_boxes);
+    image = f;
+    f.cs_copy = std::move(cs_copy);
+    f.owned_boxes = std::move(owned);
+  }
+  ReadFrameHeader(r, f);
+  ReadToc(r, f, frame_base);
+  if (IsSingleFrameImage(f)) {
+    CheckSingleFrame(f);
+    if (!headers_only) ParseFrameBody(f);
+    return;
+  }
+  // A layered image: every frame up to the first displayed one, each parsed on its own; f describes the canvas (its size, the
+  // displayed frame's name) and carries the frames.
+  auto layers = std::make_shared<Layers>();
+  layers->canvas_w = image.xsize; layers->canvas_h = image.ysize;
+  uint64_t pos = frame_base / 8;
+  for (;;) {
+    if (layers->frames.size() >= (size_t)kMaxLayerFrames)
+      Fail("layered images of more than " + std::to_string(kMaxLayerFrames) + " frames before the displayed one are not supported");
+    layers->frames.push_back(image);
+    ParsedFrame& fr = layers->frames.back();
+    fr.is_layer = true;
+    Bits rr(f.cs, f.cs_size);
+    rr.Skip((size_t)pos * 8);
+    ReadFrameHeader(rr, fr);
+    ReadToc(rr, fr, (size_t)pos * 8);
+    CheckLayerFrame(fr, layers->frames.size() - 1);
+    const bool can_ref = !fr.is_last && (fr.duration == 0 || fr.save_ref != 0);
+    layers->save.push_back(can_ref ? (int)fr.save_ref : -1);
+    if (IsDisplayed(fr)) break;
+    pos = fr.frame_end;
+    REQUIRE(pos < f.cs_size, "the codestream ends before a displayed frame");
+  }
+  // Images whose frames all replace every channel are composited from the frames' output-type samples (a selection: each pixel leaves
+  // as its frame's own decode writes it); any other blend mode needs f32 frames, which lossy (XYB) frames do not produce bit-exactly
+  layers->raw = true;
+  for (auto& fr : layers->frames) layers->raw = layers->raw && ReplacesAll(fr);
+  for (size_t k = 0; k < layers->frames.size(); k++) {
+    ParsedFrame& fr = layers->frames[k];
+    fr.layer_f32 = !layers->raw;
+    if (fr.encoding == 0 && !layers->raw)
+      Fail("lossy (XYB) frames are supported only in layered images whose frames all replace (layered image, frame " + std::to_string(k) + ")");
+  }
+  f.xsize = image.xsize; f.ysize = image.ysize;
+  f.have_crop = false; f.crop_x0 = f.crop_y0 = 0;
+  FrameGeometry(f);
+  f.name = layers->frames.back().name;
+  f.is_last = layers->frames.back().is_last;
+  f.duration = layers->frames.back().duration;
+  if (!headers_only)
+    for (auto& fr : layers->frames) ParseFrameBody(fr);
+  f.layers = std::move(layers);
 }
 
 uint64_t ParseHfGlobalAt(ParsedFrame& f, uint64_t bit_pos) {

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <deque>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -61,6 +62,11 @@ struct ColorPlan {
 };
 struct ParsedFrame;
 ColorPlan PlanColor(const ParsedFrame& f);
+struct Layers;
+
+// BlendingInfo of one channel group of a frame (colour channels, or one extra channel)
+struct BlendInfo { uint32_t mode = 0, alpha = 0, clamp = 0, source = 0; };
+constexpr int kMaxLayerFrames = 64;   // frames of a layered image up to and including the displayed one
 
 struct ParsedFrame {
   // ---- container
@@ -95,6 +101,15 @@ struct ParsedFrame {
   uint32_t group_size_shift = 1, x_qm_scale = 3, b_qm_scale = 2, num_passes = 1;
   bool is_last = true;
   std::string name;
+  // placement and blending (layered images): frame size = crop size, offsets in codestream (unoriented) coordinates
+  bool have_crop = false, do_ycbcr = false, save_before_ct = false;
+  int32_t crop_x0 = 0, crop_y0 = 0;
+  uint32_t upsampling = 1, duration = 0, save_ref = 0;
+  std::vector<BlendInfo> blend;     // [0] colour channels, [1 + k] extra channel k
+  uint64_t frame_end = 0;           // byte offset in cs right after the frame's last section (the next frame header starts here)
+  bool is_layer = false;            // one frame of a layered image: decoded to scratch, then composited (decoder.cc)
+  bool layer_f32 = false;           // ... as unclamped f32 samples (images that blend); otherwise in the output type as a lone frame
+  std::shared_ptr<Layers> layers;   // layered image (several frames, a crop or a blend mode make the displayed image); null otherwise
   bool gab = true;
   float gab_w1[3], gab_w2[3];
   uint32_t epf_iters = 2;
@@ -156,6 +171,15 @@ struct ParsedFrame {
     HostCode acode;
   };
   std::vector<PassCodes> extra_passes;
+};
+
+// A layered image: frames[0 .. n) in file order, the last one displayed, each parsed on its own (xsize / ysize = its crop).
+// save[k]: slot frame k is saved to after blending (-1: none).
+struct Layers {
+  uint32_t canvas_w = 0, canvas_h = 0;
+  std::vector<ParsedFrame> frames;
+  std::vector<int> save;
+  bool raw = false;   // every frame replaces every channel: frames are decoded in the output type and the compositor selects
 };
 
 // Throws ParseError.  headers_only: stop after the frame header + TOC (jxlhip_peek / pass 1 of LoadImage).

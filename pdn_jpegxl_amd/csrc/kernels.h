@@ -41,6 +41,9 @@ void LaunchReconTiles(const DevImage* imgs, int nimg, int max_tiles, const float
 void LaunchFilterTiles(const DevImage* imgs, int nimg, int max_w, int max_h, int stage_mask, bool any_unfiltered,
                        int any_fused, int any_fused2, hipStream_t s);
 
+// compose_kernels.hip: blend the frames of `nimg` layered images (tables in device memory) and write their displayed images
+void LaunchCompose(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_segments, hipStream_t s);
+
 // the batch's status words into pinned host memory, by a kernel (kernels.hip)
 void LaunchStatusToHost(const uint32_t* src, uint32_t* dst_pinned, int nwords, hipStream_t s);
 #ifdef JXLHIP_EXPERIMENTS
