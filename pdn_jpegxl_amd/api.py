@@ -246,7 +246,7 @@ def save_image(bgra, distance=1.0, effort=7, lossless=False, exif=None, icc=None
     write_result: HRESULT the Write callback returns instead of S_OK (failure injection)."""
     L = lib()
     bgra = np.asarray(bgra, dtype=np.uint8)
-    if bgra.strides[2] != 1 or bgra.strides[1] != 4:
+    if bgra.strides[2] != 1 or (bgra.shape[1] > 1 and bgra.strides[1] != 4):
         bgra = np.ascontiguousarray(bgra)
     h, w, _ = bgra.shape
     out = bytearray()
@@ -267,7 +267,8 @@ def save_image(bgra, distance=1.0, effort=7, lossless=False, exif=None, icc=None
         pos[0] = p
         return S_OK
 
-    bmp = BitmapData(bgra.ctypes.data, w, h, bgra.strides[0])
+    # numpy leaves the stride of a dimension of size 1 free (a contiguous 1 x 1 array may report 1): one row is w * 4 bytes apart
+    bmp = BitmapData(bgra.ctypes.data, w, h, bgra.strides[0] if h > 1 else w * 4)
     opt = EncoderOptions(distance, effort, lossless)
     keep = [np.frombuffer(b, np.uint8) if b else None for b in (exif, icc, xmp)]
     md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in keep), []))

@@ -5,6 +5,14 @@
 
 namespace jxlhip {
 
+// Index v reflected into [0, n), edge sample repeated (... 1 0 | 0 1 .. n-1 | n-1 n-2 ...), for any n >= 1: the reflection repeats
+// until the index is inside, because a frame 1 or 2 samples across is narrower than the loop filters' reach of 3.  Every loop
+// filter, the encoder's analysis and the oracle reflect by this rule; the CPU suite checks it through jxlhip_selftest_reflect.
+__host__ __device__ __forceinline__ int ReflectIndex(int v, int n) {
+  while (v < 0 || v >= n) v = v < 0 ? -v - 1 : 2 * n - 1 - v;
+  return v;
+}
+
 // Integer sample of `bits` bits -> output sample (8 or 16 bits).  Equal depths pass through clamped; otherwise through a [0, 1]
 // float, like the decoder library behind the reference does for every channel whose depth differs from the output type's.
 __device__ __forceinline__ uint32_t IntToOutSample(int32_t v, int bits, int out_bits) {

@@ -11,6 +11,7 @@
 //   enc_*_tokens_kernel       context modelling: (context, value) tokens + histograms, all data-parallel
 //   enc_sections_kernel       ANS coding, one lane per section (reverse pass for the state, forward pass for the bits)
 #include <hip/hip_runtime.h>
+#include "dev_util.h"
 #include "enc_types.h"
 #include "kernels.h"
 
@@ -20,10 +21,6 @@ namespace {
 
 __device__ __forceinline__ uint32_t PackSignedD(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(int64_t)v)) << 1) - 1; }
 __device__ __forceinline__ int CeilLog2E(uint32_t x) { return x <= 1 ? 0 : 32 - __clz(x - 1); }
-__device__ __forceinline__ int MirrorE(int v, int n) {
-  while (v < 0 || v >= n) v = v < 0 ? -v - 1 : 2 * n - 1 - v;
-  return v;
-}
 // hybrid-uint token of `v` under the config (split_exponent 4, msb_in_token 2, lsb_in_token 0)
 __device__ __forceinline__ void HybridD(uint32_t v, uint32_t* tok, uint32_t* nbits, uint32_t* bits) {
   if (v < 16) { *tok = v; *nbits = 0; *bits = 0; return; }
@@ -96,7 +93,7 @@ __global__ void enc_sharpen_pad_kernel(EncImage im) {
   const size_t n = (size_t)im.wp * im.hp;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int x = min((int)(i % im.wp), im.w - 1), y = min((int)(i / im.wp), im.h - 1);
-    const int xl = MirrorE(x - 1, im.w), xr = MirrorE(x + 1, im.w), yt = MirrorE(y - 1, im.h), yb = MirrorE(y + 1, im.h);
+    const int xl = ReflectIndex(x - 1, im.w), xr = ReflectIndex(x + 1, im.w), yt = ReflectIndex(y - 1, im.h), yb = ReflectIndex(y + 1, im.h);
     for (int c = 0; c < 3; c++) {
       const float* p = im.xyb[c];
       const float v = p[(size_t)y * im.w + x];

@@ -13,10 +13,6 @@ namespace jxlhip {
 
 __constant__ uint8_t c_quant_table[kNumStrategies] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
 __device__ __forceinline__ bool IsSpecial(uint32_t s) { return (s >= 1 && s <= 3) || (s >= 12 && s <= 17); }
-__device__ __forceinline__ int DMirror(int v, int n) {
-  while (v < 0 || v >= n) v = v < 0 ? -v - 1 : 2 * n - 1 - v;
-  return v;
-}
 
 // ------------------------------------------------------------------ LF pixel stages
 __global__ void lf_dequant_kernel(const DevImage* __restrict__ imgs) {

@@ -1,11 +1,13 @@
 // Host-only self tests of the writers (CPU tests, no GPU): the encoder's code builder, MA-tree writer and header writers against the
 // decoder's parsers.  TEST INFRASTRUCTURE: compiled into lib/libjxlhip_selftest.so only (build.py), never into the library the
 // reference's host loads - the production library exports GetLibJxlVersion / LoadImage / SaveImage and the jxlhip_* batch API, no hooks.
+#include <hip/hip_runtime.h>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "dev_util.h"
 #include "enc_types.h"
 #include "host_parse.h"
 #include "host_write.h"
@@ -152,3 +154,7 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers_icc(uint32_t xsize, 
     return 0;
   }
 }
+
+// The edge rule of the loop filters and the encoder's analysis (dev_util.h ReflectIndex), compiled for the host: index v of a
+// dimension of n samples.
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_reflect(int32_t v, int32_t n) { return ReflectIndex(v, n); }

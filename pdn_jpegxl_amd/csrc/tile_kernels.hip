@@ -103,10 +103,6 @@ __device__ __forceinline__ bool MfmaRows(uint32_t tl, uint32_t tr) {   // vertic
 __device__ __forceinline__ bool MfmaCols(uint32_t tl, uint32_t bl) {   // horizontal pass: columns >= 16, same length and column offset
   return (tl >> 31) && (bl >> 31) && ((tl >> 18) & 7) >= 1 && ((tl >> 18) & 7) == ((bl >> 18) & 7) && ((tl >> 8) & 31) == ((bl >> 8) & 31);
 }
-__device__ __forceinline__ int Mirror(int v, int n) {
-  while (v < 0 || v >= n) v = v < 0 ? -v - 1 : 2 * n - 1 - v;
-  return v;
-}
 
 // v^(1/2.4) through the hardware log2 / exp2 (v_log_f32, v_exp_f32: about 1 ulp each, i.e. < 1e-3 of an 8-bit step after the
 // * 255) instead of the ~50-instruction powf: the colour conversion was 46 % of the fused filter kernel.
@@ -600,7 +596,7 @@ __global__ __launch_bounds__(256) void filter_tile_kernel(const DevImage* __rest
     const int e0 = threadIdx.x + it * 256;
     const int e = e0 < LW * LH ? e0 : LW * LH - 1;
     const int ly = e / LW, lx = e % LW;
-    const size_t g = (size_t)Mirror(y0 - HALO + ly, h) * wp + Mirror(x0 - HALO + lx, w);
+    const size_t g = (size_t)ReflectIndex(y0 - HALO + ly, h) * wp + ReflectIndex(x0 - HALO + lx, w);
     const float v0 = in0[g], v1 = in1[g], v2 = in2[g];
     t[0][ly][lx] = v0;
     t[1][ly][lx] = v1;
@@ -698,14 +694,14 @@ struct Row3 { F4 c[3]; };
 // Quad (X .. X + 3) of row y of the three planes; rows and columns outside the frame are mirrored like the unfused stages do.
 __device__ __forceinline__ Row3 LoadRow3(const JXL_GLOBAL float* p0, const JXL_GLOBAL float* p1, const JXL_GLOBAL float* p2, int X, int y, int w, int h,
                                          int wp, bool interior) {
-  const int yy = y < 0 ? -y - 1 : (y >= h ? 2 * h - 1 - y : y);
+  const int yy = ReflectIndex(y, h);   // rows y0 - 3 .. y1 + 2: more than one reflection for h <= 2
   Row3 r;
   if (interior) {
     const size_t g = (size_t)yy * wp + X;
     r.c[0] = *(const JXL_GLOBAL F4*)(p0 + g); r.c[1] = *(const JXL_GLOBAL F4*)(p1 + g); r.c[2] = *(const JXL_GLOBAL F4*)(p2 + g);
   } else {
     const size_t g = (size_t)yy * wp;
-    const int x0 = Mirror(X, w), x1 = Mirror(X + 1, w), x2 = Mirror(X + 2, w), x3 = Mirror(X + 3, w);
+    const int x0 = ReflectIndex(X, w), x1 = ReflectIndex(X + 1, w), x2 = ReflectIndex(X + 2, w), x3 = ReflectIndex(X + 3, w);
     r.c[0] = F4{p0[g + x0], p0[g + x1], p0[g + x2], p0[g + x3]};
     r.c[1] = F4{p1[g + x0], p1[g + x1], p1[g + x2], p1[g + x3]};
     r.c[2] = F4{p2[g + x0], p2[g + x1], p2[g + x2], p2[g + x3]};
@@ -956,7 +952,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t PlaneResource(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7FFFFFFF, 0x00020000);   // raw buffer, no swizzle; the planes are smaller than 2 GB
 }
 __device__ __forceinline__ PairRow LoadPairRow(const PairConst& k, int y) {
-  const int yy = y < 0 ? -y - 1 : (y >= k.h ? 2 * k.h - 1 - y : y);   // uniform over the wavefront
+  const int yy = ReflectIndex(y, k.h);   // uniform over the wavefront (the loop stays on the scalar unit); h <= 2 reflects more than once
   const uint32_t row = (uint32_t)yy * (uint32_t)k.wp * 4u;
   PairRow r;
   r.c[0] = __builtin_bit_cast(F2, __builtin_amdgcn_raw_buffer_load_b64(k.in0, k.in_bytes, row, 0));
@@ -1063,7 +1059,9 @@ __global__ __launch_bounds__(256, 4) void filter_stream_pairs_kernel(const DevIm
   k.y0 = band_lo + seg * kSegRows; k.y1 = min(k.y0 + kSegRows, band_hi);
   k.r_end = k.y1 + 3;
   k.outside = X < 0 || X >= k.w;
-  const int xm = X < 0 ? -X - 2 : (X >= k.w ? 2 * k.w - 2 - X : X);   // the pair this lane loads: itself, or the pair it mirrors
+  // the pair this lane loads: itself, or the pair it mirrors.  One reflection is exact only because the host gate (`even`, decoder.cc)
+  // admits w >= 8: the lanes whose pairs reach a stored pixel have X in [-4, w + 2]; lanes further right are clamped and store nothing
+  const int xm = X < 0 ? -X - 2 : (X >= k.w ? 2 * k.w - 2 - X : X);
   k.in_bytes = (uint32_t)min(max(xm, 0), k.w - 2) * 4u;
   const int xc = min(max(X, 0), k.w - 2);
   k.cell_bytes = (uint32_t)(xc >> 3) * 4u;
@@ -1223,6 +1221,7 @@ __global__ __launch_bounds__(256, 4) void filter_stream2_pairs_kernel(const DevI
   k.y0 = im.band_y0 + seg * kSegRows; k.y1 = min(k.y0 + kSegRows, im.band_y1);
   k.r_end = k.y1 + 1;                               // last input row + 1
   k.outside = X < 0 || X >= k.w;
+  // one reflection is exact only because of the w >= 8 gate (see filter_stream_pairs_kernel): lanes reaching a stored pixel have X in [-2, w]
   const int xm = X < 0 ? -X - 2 : (X >= k.w ? 2 * k.w - 2 - X : X);
   k.in_bytes = (uint32_t)min(max(xm, 0), k.w - 2) * 4u;
   const int xc = min(max(X, 0), k.w - 2);

@@ -384,7 +384,7 @@ def test_scalar_unit_loops_match_the_vector_loops(gpu_decoder, oracle):
         assert np.array_equal(a, c)
 
 
-@pytest.mark.parametrize("size", [(8, 8), (10, 40), (120, 131), (122, 20), (240, 9), (242, 140), (250, 300), (400, 259), (778, 531)])
+@pytest.mark.parametrize("size", [(8, 8), (10, 40), (120, 131), (122, 20), (240, 9), (242, 140), (250, 300), (400, 259), (778, 531), (8, 1), (16, 2), (122, 2)])
 @pytest.mark.parametrize("distance", [1.0, 2.0])
 @pytest.mark.parametrize("layout", ["rgba", "rgb", "gray", "graya"])
 def test_filter_kernel_of_two_pixels_per_lane_matches_the_general_one(gpu_decoder, oracle, size, distance, layout):
@@ -392,7 +392,8 @@ def test_filter_kernel_of_two_pixels_per_lane_matches_the_general_one(gpu_decode
     (two pixels per lane, buffer addressing, mirrored edge pairs loaded from inside the frame); every other layout runs
     filter_stream_kernel.  The same streams through both - widths around the 120-column strips, one and two EPF iterations - must
     give identical bytes for RGBA (both forms convert with v_cvt_pk_u8_f32) and the same pixels up to rounding ties for the other
-    layouts (the general form's paths round half up), and match the oracle."""
+    layouts (the general form's paths round half up), and match the oracle.  Frames 1 and 2 rows high reflect their edge rows more
+    than once (rows y0 - 3 .. y1 + 2 are read)."""
     w, h = size
     img = synth(w, h, 31 + w)
     src = np.ascontiguousarray({"rgba": img, "rgb": img[..., :3], "gray": img[..., 1:2], "graya": img[..., [1, 3]]}[layout])

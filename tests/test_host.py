@@ -217,6 +217,33 @@ def test_encoder_headers_read_back(w, h, gray, alpha, lossless, epf):
     assert info.gaborish == (0 if lossless else 1) and info.epf_iters == (0 if lossless else epf)
 
 
+def _reflect(v, n):
+    """The loop filters' edge rule, restated: reflect (edge sample repeated) until the index is inside [0, n)."""
+    while v < 0 or v >= n:
+        v = -v - 1 if v < 0 else 2 * n - 1 - v
+    return v
+
+
+def test_edge_reflection_of_the_loop_filters():
+    """ReflectIndex (dev_util.h), the one reflection of the GPU loop filters (stage kernels, streaming kernels of four and of two
+    pixels per lane) and of the encoder's analysis, compiled for the host.  The streaming kernels read rows y0 - 3 .. y1 + 2 of every
+    128-row segment: for a frame 1 or 2 rows high a single reflection leaves those rows outside the frame."""
+    L = api.selftest_lib()
+    L.jxlhip_selftest_reflect.restype = C.c_int32
+    L.jxlhip_selftest_reflect.argtypes = [C.c_int32, C.c_int32]
+    for n in range(1, 301):
+        for v in range(-3 * n - 3, 4 * n + 4):
+            got = L.jxlhip_selftest_reflect(v, n)
+            assert 0 <= got < n and got == _reflect(v, n), (v, n, got)
+        for y0 in range(0, n, 128):                       # the rows each segment of the streaming kernels requests
+            y1 = min(y0 + 128, n)
+            for y in range(y0 - 3, y1 + 3):
+                got = L.jxlhip_selftest_reflect(y, n)
+                assert 0 <= got < n and got == _reflect(y, n), (y, n, y0, y1, got)
+    assert [L.jxlhip_selftest_reflect(y, 1) for y in range(-3, 4)] == [0] * 7
+    assert [L.jxlhip_selftest_reflect(y, 2) for y in range(-3, 5)] == [1, 1, 0, 0, 1, 1, 0, 0]
+
+
 def test_a_stale_native_library_is_refused(monkeypatch):
     """The library is git-ignored but travels to the GPU box: one built from other sources than the tree's must not be used silently."""
     from pdn_jpegxl_amd import build as B
