@@ -13,6 +13,15 @@ __host__ __device__ __forceinline__ int ReflectIndex(int v, int n) {
   return v;
 }
 
+// Context offset of the HF coefficient tokens for the predicted non-zero count nzl in [0, 63]: a step function with eight values
+// (0, 31, 62, 93, 123, 152, 180, 206) and thresholds at 2, 3, 5, 9, 13, 21 and 33, computed in registers so that the batched HF
+// token loop has no table lookup in front of its context-map read.  The CPU suite checks all 64 inputs through
+// jxlhip_selftest_nnz_ctx.
+__host__ __device__ __forceinline__ uint32_t NnzBucketCtx(uint32_t nzl) {
+  const uint32_t b = (nzl >= 2) + (nzl >= 3) + (nzl >= 5) + (nzl >= 9) + (nzl >= 13) + (nzl >= 21) + (nzl >= 33);
+  return (uint32_t)(0xCEB4987B5D3E1F00ull >> (8 * b)) & 0xFFu;
+}
+
 // Integer sample of `bits` bits -> output sample (8 or 16 bits).  Equal depths pass through clamped; otherwise through a [0, 1]
 // float, like the decoder library behind the reference does for every channel whose depth differs from the output type's.
 __device__ __forceinline__ uint32_t IntToOutSample(int32_t v, int bits, int out_bits) {

@@ -1487,7 +1487,10 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
   const int gx = g % im.xg, gy = g / im.xg;
   // block descriptors: staged through a small LDS queue that is topped up together with the bit window
   const JXL_GLB uint32_t* const list = G(im.blk_list + (size_t)g * 1024);
-  const uint32_t nblk = im.blk_count[g];
+  uint32_t nblk = im.blk_count[g];
+  // Wait for that load HERE: left pending into the token loop, it made the compiler put a full `s_waitcnt vmcnt(0)` in front of
+  // every `bi < nblk` test - i.e. every block start (nearly every step of a batched wavefront) waited for all coefficient stores.
+  asm volatile("" : "+v"(nblk));
   JXL_LDS uint32_t* const dq = descq + si;
   constexpr uint32_t dqmask = 2u * kQ - 1;
   uint32_t bi = 0, dfilled = 0, it = 0, dpend_n = 0;
@@ -1521,224 +1524,324 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
     cfg_uni = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg_uni);
     cfg_is_uni = __builtin_amdgcn_readfirstlane((int)cfg_is_uni) != 0;
   }
-  while (!err) {
-    if ((it & (kTop - 1)) == 0) {
+  // Batched ANS path (several sections per wavefront): the contexts of a block's three non-zero-count tokens are formed at the
+  // descriptor pop from registers.  The col[] values a block's predictions need are read one block AHEAD, at the previous pop (its
+  // descriptor is held in a register, the one after it is being read), so those reads never head a token; the only col[] entries
+  // they can miss are the previous block's own fills, which are patched in from registers (col[x] is always the value of the last
+  // block covering column x).
+  uint32_t nz_ctx0 = 0, nz_ctx1 = 0, nz_ctx2 = 0;   // contexts of the current block's non-zero-count tokens, channels in ci order
+  uint32_t d_next = 0, d_after = 0;                  // descriptors of blocks bi and bi + 1 (valid from the first pop on)
+  uint32_t up0 = 0, up1 = 0, up2 = 0, lf0 = 0, lf1 = 0, lf2 = 0;   // col[] above (x = bx) / left (x = bx - 1) of block bi, as read
+  uint32_t pbx = 0, pcx = 0, fv0 = 0, fv1 = 0, fv2 = 0;           // the previous block's columns [pbx, pbx + pcx) and its fills
+  // once per period (every kTop tokens): the bit window and the descriptor queue are topped up
+  auto period = [&]() {
 #ifdef JXLHIP_PROFILE_HF
-      const uint64_t pf_t0 = clock64();
-      pf_periods++;
+    const uint64_t pf_t0 = clock64();
+    pf_periods++;
 #endif
-      b.TopUp();
-      // descriptors the same way: a period starts at most kQ blocks, the queue holds 2 * kQ; what the previous period requested is
-      // queued now, the next kQ are requested
-      if (dpend_n) {
+    b.TopUp();
+    // descriptors the same way: a period starts at most kQ blocks, the queue holds 2 * kQ; what the previous period requested is
+    // queued now, the next kQ are requested
+    if (dpend_n) {
 #pragma unroll
-        for (int i = 0; i < kQ; i++) if ((uint32_t)i < dpend_n) dq[__umul24((dfilled + i) & dqmask, nslots)] = dpend[i];
-        dfilled += dpend_n;
-        dpend_n = 0;
-      }
-      if (dfilled < min(nblk, bi + kQ)) {   // start of the section, or a burst: wait for them
-        const uint32_t lim = min(nblk, bi + kQ);
-        uint32_t v[kQ];
-#pragma unroll
-        for (int i = 0; i < kQ; i++) { v[i] = 0u; if (dfilled + i < lim) v[i] = list[dfilled + i]; }
-#pragma unroll
-        for (int i = 0; i < kQ; i++) if (dfilled + i < lim) dq[__umul24((dfilled + i) & dqmask, nslots)] = v[i];
-        dfilled = lim;
-      }
-      {
-        const uint32_t lim = min(nblk, bi + 2 * kQ);
-        if (dfilled < lim) {
-          dpend_n = min(lim - dfilled, (uint32_t)kQ);
-#pragma unroll
-          for (int i = 0; i < kQ; i++) { dpend[i] = 0u; if ((uint32_t)i < dpend_n) dpend[i] = list[dfilled + i]; }
-        }
-      }
-#ifdef JXLHIP_PROFILE_HF
-      pf_period += clock64() - pf_t0;
-#endif
+      for (int i = 0; i < kQ; i++) if ((uint32_t)i < dpend_n) dq[__umul24((dfilled + i) & dqmask, nslots)] = dpend[i];
+      dfilled += dpend_n;
+      dpend_n = 0;
     }
-    // Fast path: while every lane of the wavefront that is still decoding sits inside a run of coefficient tokens (always the
-    // case with one section per wavefront, i.e. small batches), stay in a loop that holds nothing but the coefficient token:
-    // the general iteration below pays for both token kinds and their bookkeeping on every step.
-    if (__all(!want_nz)) {
-      if (per_wave == 1 && !tab.slow) {
-        // One section per wavefront (single frames, small batches): every value of this loop is the same in all lanes, i.e. it is
-        // scalar work - and on this machine a dependent scalar operation costs a fraction of a dependent vector one (which issues
-        // every ~10 cycles).  The loop-carried state is moved to scalar registers (v_readfirstlane), table entries come back from LDS
-        // through the same door, and the recurrence state -> alias entry -> state runs on the scalar unit; only the LDS addresses and
-        // the entry store touch vector registers.
-#define JXL_RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
-#ifdef JXLHIP_PROFILE_HF
-        const uint64_t pf_t1 = clock64();
-        pf_entries++;
-#endif
-        // A lone wavefront issues one instruction every four cycles or so, and every LDS lookup on the chain adds ~80: the loop is
-        // written for few instructions and few dependent lookups - the tokens a period or the block still allows are counted down
-        // (no per-token stop conditions), the non-zero-count bucket is looked up again only after a non-zero coefficient, the range
-        // check is one OR per coefficient, and a code whose clusters share one hybrid-integer configuration skips that lookup.
-        uint32_t s_state = JXL_RFL(state), s_nz = JXL_RFL(nzeros), s_k = JXL_RFL(k), s_prev = JXL_RFL(prev), s_epos = JXL_RFL(epos), s_it = JXL_RFL(it);
-        const uint32_t s_cov = JXL_RFL(covered), s_l2 = JXL_RFL(log2c), s_size = JXL_RFL(size), s_histo = JXL_RFL(histo);
-        uint64_t s_buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);
-        int s_n = (int)JXL_RFL(b.n);
-        uint32_t s_rd = JXL_RFL(b.rd), s_rng = 0;
-        const uint32_t la = JXL_RFL(tab.log_alpha), le = 12 - la;
-        const uint32_t left = kTop - (s_it & (kTop - 1)), room = s_size > s_k ? s_size - s_k : 0u;
-        const uint32_t cnt0 = min(left, room);
-        uint32_t cnt = cnt0;
-        uint32_t s_a = s_histo + 2 * JXL_RFL(nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
-        uint32_t s_cidx = 0xFFFFFFFFu, s_cl = 0;
-        if (cnt) do {
-          const uint32_t ks = s_k >> s_l2;
-          const uint32_t fctx = min(ks - 1, min(7 + (ks >> 1), 15 + (ks >> 2)));   // the three-piece position context, without branches
-          // inside a run of zeros the context only moves when the position context does (every second / fourth position from 16 / 32
-          // on): the cluster of the last lookup is kept while the context-map index stays the same
-          const uint32_t cidx = s_a + fctx * 2 + s_prev;
-          if (cidx != s_cidx) { s_cl = JXL_RFL(tab.cmap[cidx]); s_cidx = cidx; }
-          const uint32_t cl = s_cl;
-          const uint32_t res = s_state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-          const uint64_t e = tab.alias[(cl << la) | i];
-          uint32_t c = cfg_uni;
-          if (__builtin_expect(!cfg_is_uni, 0)) c = JXL_RFL(tab.cfg[cl]);
-          const uint32_t x = JXL_RFL((uint32_t)e), y = JXL_RFL((uint32_t)(e >> 32));
-          const bool gt = pos >= (x & 0xFF);
-          const uint32_t sym = gt ? ((x >> 8) & 0xFF) : i;
-          const uint32_t off = gt ? (y & 0xFFFF) + pos : pos;
-          const uint32_t freq = gt ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-          s_state = freq * (s_state >> 12) + off;
-          if (s_state < 65536u) {
-            if (s_n <= 32) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRing - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
-            s_state = (s_state << 16) | ((uint32_t)s_buf & 0xFFFFu);
-            s_buf >>= 16; s_n -= 16;
-          }
-          uint32_t u = sym;
-          const uint32_t se = c & 0xF, split = 1u << se;
-          if (__builtin_expect(sym >= split, 0)) {
-            const uint32_t msb = (c >> 4) & 0xF, lsb = (c >> 8) & 0xF;
-            const uint32_t nb = se - (msb + lsb) + ((sym - split) >> (msb + lsb)), nbr = nb > 32 ? 32 : nb;
-            if (s_n <= 32) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRing - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
-            const uint32_t bits = (uint32_t)(s_buf & (((uint64_t)1 << nbr) - 1));
-            s_buf >>= nbr; s_n -= (int)nbr;
-            const uint32_t low = sym & ((1u << lsb) - 1), hi = (1u << msb) | ((sym >> lsb) & ((1u << msb) - 1));
-            u = (uint32_t)(((((uint64_t)hi << (nb & 63)) | bits) << lsb) | low);
-          }
-          cnt--;
-          s_prev = 0;
-          if (u) {
-            const int32_t v = UnpackSigned(u);
-            s_rng |= (uint32_t)(v + 0x8000);   // a value outside int16 leaves a bit above bit 15
-            ent[s_epos++] = s_k | (uint32_t)v << 16;
-            s_prev = 1;
-            s_k++;
-            if (--s_nz == 0) break;
-            s_a = s_histo + 2 * JXL_RFL(nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
-          } else {
-            s_k++;
-          }
-        } while (cnt);
-        s_it += cnt0 - cnt;
-#ifdef JXLHIP_PROFILE_HF
-        pf_scalar += clock64() - pf_t1;
-        pf_tokens += cnt0 - cnt;
-#endif
-        uint32_t s_err = s_rng > 0xFFFFu ? (uint32_t)kErrRange : 0u;
-        if (s_nz != 0 && s_k >= s_size) s_err |= kErrBitstream;
-#undef JXL_RFL
-        state = s_state; nzeros = s_nz; k = s_k; prev = s_prev; epos = s_epos; it = s_it;
-        b.buf = s_buf; b.n = s_n; b.rd = s_rd;
-        err |= s_err;
-        if (s_nz == 0 && !s_err) { want_nz = true; ci++; }
-        continue;
+    if (dfilled < min(nblk, bi + kQ)) {   // start of the section, or a burst: wait for them
+      const uint32_t lim = min(nblk, bi + kQ);
+      uint32_t v[kQ];
+#pragma unroll
+      for (int i = 0; i < kQ; i++) { v[i] = 0u; if (dfilled + i < lim) v[i] = list[dfilled + i]; }
+#pragma unroll
+      for (int i = 0; i < kQ; i++) if (dfilled + i < lim) dq[__umul24((dfilled + i) & dqmask, nslots)] = v[i];
+      dfilled = lim;
+    }
+    {
+      const uint32_t lim = min(nblk, bi + 2 * kQ);
+      if (dfilled < lim) {
+        dpend_n = min(lim - dfilled, (uint32_t)kQ);
+#pragma unroll
+        for (int i = 0; i < kQ; i++) { dpend[i] = 0u; if ((uint32_t)i < dpend_n) dpend[i] = list[dfilled + i]; }
       }
-      for (;;) {
-        const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-        const uint32_t ks = k >> log2c;
-        const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
-        const uint32_t u = AnsGet(b, state, tab, histo + ((uint32_t)nnz_tab[nzl] + fctx) * 2 + prev);
-        it++;
-        bool leave = false;
+    }
+#ifdef JXLHIP_PROFILE_HF
+    pf_period += clock64() - pf_t0;
+#endif
+  };
+  if (per_wave > 1 && !tab.slow) {
+    while (!err) {
+      if ((it & (kTop - 1)) == 0) period();
+      // One straight-line step per token for both token kinds: the wavefront almost always holds a lane that starts a block and one
+      // that reads a non-zero count, so what used to be their own code paths (descriptor read -> col[] reads -> context map) headed
+      // nearly every step.  Now the loop-carried chain is context map -> alias entry (+ cfg beside it) -> state.
+      auto colv = [&](uint32_t c, uint32_t x) { return (uint32_t)col[__umul24(c * 32 + x, nslots)]; };
+      auto look_ahead = [&]() {   // col[] around block bi (descriptor d_next), read before the current block's fills land
+        const uint32_t x = d_next & 31, xl = x ? x - 1 : 0;
+        up0 = colv(1, x); lf0 = colv(1, xl);
+        up1 = colv(0, x); lf1 = colv(0, xl);
+        up2 = colv(2, x); lf2 = colv(2, xl);
+      };
+      if (want_nz && ci >= 3) {
+        if (bi >= nblk) break;
+        if (bi == 0) {   // first block of the section: nothing read ahead yet, and no previous block to patch from
+          d_next = dq[0];
+          d_after = dq[__umul24(1u & dqmask, nslots)];
+          look_ahead();
+          pcx = 0;
+        }
+        const uint32_t d = d_next;
+        bx = d & 31; by = (d >> 5) & 31;
+        lcx = (d >> 10) & 7;
+        const uint32_t lcy = (d >> 13) & 7;
+        ctxs = d >> 16;
+        log2c = lcx + lcy; covered = 1u << log2c; size = covered << 6;
+        cell = __umul24(by, w8) + bx;
+        ci = 0;
+        const uint32_t xl = bx ? bx - 1 : 0;
+        const bool up_prev = bx - pbx < pcx, lf_prev = xl - pbx < pcx;   // columns the previous block filled after the reads
+        auto nz_ctx = [&](uint32_t up, uint32_t lf, uint32_t fv, uint32_t block_ctx) {
+          const uint32_t a = up_prev ? fv : up, l = lf_prev ? fv : lf;
+          uint32_t p = bx == 0 ? (by == 0 ? 32u : a) : (by == 0 ? l : (a + l + 1) >> 1);
+          p = p >= 64 ? 64 : p;
+          p = p < 8 ? p : 4 + p / 2;
+          return ctx_offset + p * nbc + block_ctx;
+        };
+        nz_ctx0 = nz_ctx(up0, lf0, fv0, ctxs & 31);
+        nz_ctx1 = nz_ctx(up1, lf1, fv1, (ctxs >> 5) & 31);
+        nz_ctx2 = nz_ctx(up2, lf2, fv2, (ctxs >> 10) & 31);
+        pbx = bx; pcx = 1u << lcx;
+        bi++;
+        // block bi is at most two ahead of the last pop of a period, so its descriptor and the next one are already queued
+        d_next = d_after;
+        look_ahead();
+        d_after = dq[__umul24((bi + 1) & dqmask, nslots)];
+      }
+      const uint32_t nzl = (nzeros + covered - 1) >> log2c;
+      const uint32_t ks = k >> log2c;
+      const uint32_t fctx = min(ks - 1, min(7 + (ks >> 1), 15 + (ks >> 2)));
+      const uint32_t nzc = ci == 0 ? nz_ctx0 : (ci == 1 ? nz_ctx1 : nz_ctx2);
+      const uint32_t u = AnsGet(b, state, tab, want_nz ? nzc : histo + (NnzBucketCtx(nzl) + fctx) * 2 + prev);
+      it++;
+      if (want_nz) {
+        nzeros = u;
+        if (nzeros + covered > size) { err |= kErrBitstream; break; }
+        const uint32_t fill = (nzeros + covered - 1) >> log2c;
+        const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+        JXL_LDS uint8_t* const cc = col + __umul24(c * 32 + bx, nslots);
+        for (uint32_t ix = 0; ix < (1u << lcx); ix++) cc[__umul24(ix, nslots)] = (uint8_t)fill;
+        fv0 = ci == 0 ? fill : fv0; fv1 = ci == 1 ? fill : fv1; fv2 = ci == 2 ? fill : fv2;
+        U2 rec;
+        rec.x = epos; rec.y = nzeros;
+        cblk[(size_t)c * ncells + cell] = rec;
+        if (nzeros) {
+          const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
+          histo = ctx_offset + nbc * 37 + 458 * block_ctx;
+          prev = nzeros > size / 16 ? 0 : 1;
+          k = covered;
+          want_nz = false;
+        } else {
+          ci++;
+        }
+      } else {
         if (u) {
           const int32_t v = UnpackSigned(u);
           if (v != (int32_t)(int16_t)v) err |= kErrRange;
           ent[epos++] = k | (uint32_t)v << 16;
           prev = 1;
-          if (--nzeros == 0) { want_nz = true; ci++; leave = true; }
+          if (--nzeros == 0) { want_nz = true; ci++; }
         } else {
           prev = 0;
         }
-        if (++k >= size && nzeros != 0) { err |= kErrBitstream; leave = true; }
-        if (__any(leave) || (it & (kTop - 1)) == 0) break;
+        if (++k >= size && nzeros != 0) { err |= kErrBitstream; break; }
       }
-      continue;
     }
-#ifdef JXLHIP_PROFILE_HF
-    const uint64_t pf_t2 = clock64();
-    pf_general_n++;
-#endif
-    if (want_nz && ci >= 3) {
-      if (bi >= nblk) break;
-      const uint32_t d = dq[__umul24(bi & dqmask, nslots)];
-      bi++;
-      bx = d & 31; by = (d >> 5) & 31;
-      lcx = (d >> 10) & 7;
-      const uint32_t lcy = (d >> 13) & 7;
-      ctxs = d >> 16;
-      log2c = lcx + lcy; covered = 1u << log2c; size = covered << 6;
-      cell = __umul24(by, w8) + bx;
-      ci = 0;
-    }
-    const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-    uint32_t ctx;
-    if (want_nz) {
-      JXL_LDS uint8_t* const cc = col + __umul24(c * 32, nslots);
-      uint32_t predicted;
-      if (bx == 0) predicted = by == 0 ? 32u : (uint32_t)cc[0];
-      else if (by == 0) predicted = cc[__umul24(bx - 1, nslots)];
-      else predicted = ((uint32_t)cc[__umul24(bx, nslots)] + cc[__umul24(bx - 1, nslots)] + 1) >> 1;
-      const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
-      uint32_t nzc = predicted >= 64 ? 64 : predicted;
-      nzc = nzc < 8 ? nzc : 4 + nzc / 2;
-      ctx = ctx_offset + nzc * nbc + block_ctx;
-    } else {
-      const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-      const uint32_t ks = k >> log2c;
-      const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
-      ctx = histo + ((uint32_t)nnz_tab[nzl] + fctx) * 2 + prev;
-    }
-    const uint32_t u = AnsGet(b, state, tab, ctx);
-    it++;
-    if (want_nz) {
-      nzeros = u;
-      if (nzeros + covered > size) { err |= kErrBitstream; break; }
-      const uint8_t fill = (uint8_t)((nzeros + covered - 1) >> log2c);
-      JXL_LDS uint8_t* const cc = col + __umul24(c * 32 + bx, nslots);
-      for (uint32_t ix = 0; ix < (1u << lcx); ix++) cc[__umul24(ix, nslots)] = fill;
-      U2 rec;
-      rec.x = epos; rec.y = nzeros;
-      cblk[(size_t)c * ncells + cell] = rec;
-      if (nzeros) {
+  } else {
+    while (!err) {
+      if ((it & (kTop - 1)) == 0) period();
+      // Fast path: while every lane of the wavefront that is still decoding sits inside a run of coefficient tokens (always the
+      // case with one section per wavefront, i.e. small batches), stay in a loop that holds nothing but the coefficient token:
+      // the general iteration below pays for both token kinds and their bookkeeping on every step.
+      if (__all(!want_nz)) {
+        if (per_wave == 1 && !tab.slow) {
+          // One section per wavefront (single frames, small batches): every value of this loop is the same in all lanes, i.e. it is
+          // scalar work - and on this machine a dependent scalar operation costs a fraction of a dependent vector one (which issues
+          // every ~10 cycles).  The loop-carried state is moved to scalar registers (v_readfirstlane), table entries come back from LDS
+          // through the same door, and the recurrence state -> alias entry -> state runs on the scalar unit; only the LDS addresses and
+          // the entry store touch vector registers.
+  #define JXL_RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+  #ifdef JXLHIP_PROFILE_HF
+          const uint64_t pf_t1 = clock64();
+          pf_entries++;
+  #endif
+          // A lone wavefront issues one instruction every four cycles or so, and every LDS lookup on the chain adds ~80: the loop is
+          // written for few instructions and few dependent lookups - the tokens a period or the block still allows are counted down
+          // (no per-token stop conditions), the non-zero-count bucket is looked up again only after a non-zero coefficient, the range
+          // check is one OR per coefficient, and a code whose clusters share one hybrid-integer configuration skips that lookup.
+          uint32_t s_state = JXL_RFL(state), s_nz = JXL_RFL(nzeros), s_k = JXL_RFL(k), s_prev = JXL_RFL(prev), s_epos = JXL_RFL(epos), s_it = JXL_RFL(it);
+          const uint32_t s_cov = JXL_RFL(covered), s_l2 = JXL_RFL(log2c), s_size = JXL_RFL(size), s_histo = JXL_RFL(histo);
+          uint64_t s_buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);
+          int s_n = (int)JXL_RFL(b.n);
+          uint32_t s_rd = JXL_RFL(b.rd), s_rng = 0;
+          const uint32_t la = JXL_RFL(tab.log_alpha), le = 12 - la;
+          const uint32_t left = kTop - (s_it & (kTop - 1)), room = s_size > s_k ? s_size - s_k : 0u;
+          const uint32_t cnt0 = min(left, room);
+          uint32_t cnt = cnt0;
+          uint32_t s_a = s_histo + 2 * JXL_RFL(nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
+          uint32_t s_cidx = 0xFFFFFFFFu, s_cl = 0;
+          if (cnt) do {
+            const uint32_t ks = s_k >> s_l2;
+            const uint32_t fctx = min(ks - 1, min(7 + (ks >> 1), 15 + (ks >> 2)));   // the three-piece position context, without branches
+            // inside a run of zeros the context only moves when the position context does (every second / fourth position from 16 / 32
+            // on): the cluster of the last lookup is kept while the context-map index stays the same
+            const uint32_t cidx = s_a + fctx * 2 + s_prev;
+            if (cidx != s_cidx) { s_cl = JXL_RFL(tab.cmap[cidx]); s_cidx = cidx; }
+            const uint32_t cl = s_cl;
+            const uint32_t res = s_state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
+            const uint64_t e = tab.alias[(cl << la) | i];
+            uint32_t c = cfg_uni;
+            if (__builtin_expect(!cfg_is_uni, 0)) c = JXL_RFL(tab.cfg[cl]);
+            const uint32_t x = JXL_RFL((uint32_t)e), y = JXL_RFL((uint32_t)(e >> 32));
+            const bool gt = pos >= (x & 0xFF);
+            const uint32_t sym = gt ? ((x >> 8) & 0xFF) : i;
+            const uint32_t off = gt ? (y & 0xFFFF) + pos : pos;
+            const uint32_t freq = gt ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
+            s_state = freq * (s_state >> 12) + off;
+            if (s_state < 65536u) {
+              if (s_n <= 32) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRing - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
+              s_state = (s_state << 16) | ((uint32_t)s_buf & 0xFFFFu);
+              s_buf >>= 16; s_n -= 16;
+            }
+            uint32_t u = sym;
+            const uint32_t se = c & 0xF, split = 1u << se;
+            if (__builtin_expect(sym >= split, 0)) {
+              const uint32_t msb = (c >> 4) & 0xF, lsb = (c >> 8) & 0xF;
+              const uint32_t nb = se - (msb + lsb) + ((sym - split) >> (msb + lsb)), nbr = nb > 32 ? 32 : nb;
+              if (s_n <= 32) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRing - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
+              const uint32_t bits = (uint32_t)(s_buf & (((uint64_t)1 << nbr) - 1));
+              s_buf >>= nbr; s_n -= (int)nbr;
+              const uint32_t low = sym & ((1u << lsb) - 1), hi = (1u << msb) | ((sym >> lsb) & ((1u << msb) - 1));
+              u = (uint32_t)(((((uint64_t)hi << (nb & 63)) | bits) << lsb) | low);
+            }
+            cnt--;
+            s_prev = 0;
+            if (u) {
+              const int32_t v = UnpackSigned(u);
+              s_rng |= (uint32_t)(v + 0x8000);   // a value outside int16 leaves a bit above bit 15
+              ent[s_epos++] = s_k | (uint32_t)v << 16;
+              s_prev = 1;
+              s_k++;
+              if (--s_nz == 0) break;
+              s_a = s_histo + 2 * JXL_RFL(nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
+            } else {
+              s_k++;
+            }
+          } while (cnt);
+          s_it += cnt0 - cnt;
+  #ifdef JXLHIP_PROFILE_HF
+          pf_scalar += clock64() - pf_t1;
+          pf_tokens += cnt0 - cnt;
+  #endif
+          uint32_t s_err = s_rng > 0xFFFFu ? (uint32_t)kErrRange : 0u;
+          if (s_nz != 0 && s_k >= s_size) s_err |= kErrBitstream;
+  #undef JXL_RFL
+          state = s_state; nzeros = s_nz; k = s_k; prev = s_prev; epos = s_epos; it = s_it;
+          b.buf = s_buf; b.n = s_n; b.rd = s_rd;
+          err |= s_err;
+          if (s_nz == 0 && !s_err) { want_nz = true; ci++; }
+          continue;
+        }
+        for (;;) {
+          const uint32_t nzl = (nzeros + covered - 1) >> log2c;
+          const uint32_t ks = k >> log2c;
+          const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
+          const uint32_t u = AnsGet(b, state, tab, histo + ((uint32_t)nnz_tab[nzl] + fctx) * 2 + prev);
+          it++;
+          bool leave = false;
+          if (u) {
+            const int32_t v = UnpackSigned(u);
+            if (v != (int32_t)(int16_t)v) err |= kErrRange;
+            ent[epos++] = k | (uint32_t)v << 16;
+            prev = 1;
+            if (--nzeros == 0) { want_nz = true; ci++; leave = true; }
+          } else {
+            prev = 0;
+          }
+          if (++k >= size && nzeros != 0) { err |= kErrBitstream; leave = true; }
+          if (__any(leave) || (it & (kTop - 1)) == 0) break;
+        }
+        continue;
+      }
+  #ifdef JXLHIP_PROFILE_HF
+      const uint64_t pf_t2 = clock64();
+      pf_general_n++;
+  #endif
+      if (want_nz && ci >= 3) {
+        if (bi >= nblk) break;
+        const uint32_t d = dq[__umul24(bi & dqmask, nslots)];
+        bi++;
+        bx = d & 31; by = (d >> 5) & 31;
+        lcx = (d >> 10) & 7;
+        const uint32_t lcy = (d >> 13) & 7;
+        ctxs = d >> 16;
+        log2c = lcx + lcy; covered = 1u << log2c; size = covered << 6;
+        cell = __umul24(by, w8) + bx;
+        ci = 0;
+      }
+      const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+      uint32_t ctx;
+      if (want_nz) {
+        JXL_LDS uint8_t* const cc = col + __umul24(c * 32, nslots);
+        uint32_t predicted;
+        if (bx == 0) predicted = by == 0 ? 32u : (uint32_t)cc[0];
+        else if (by == 0) predicted = cc[__umul24(bx - 1, nslots)];
+        else predicted = ((uint32_t)cc[__umul24(bx, nslots)] + cc[__umul24(bx - 1, nslots)] + 1) >> 1;
         const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
-        histo = ctx_offset + nbc * 37 + 458 * block_ctx;
-        prev = nzeros > size / 16 ? 0 : 1;
-        k = covered;
-        want_nz = false;
+        uint32_t nzc = predicted >= 64 ? 64 : predicted;
+        nzc = nzc < 8 ? nzc : 4 + nzc / 2;
+        ctx = ctx_offset + nzc * nbc + block_ctx;
       } else {
-        ci++;
+        const uint32_t nzl = (nzeros + covered - 1) >> log2c;
+        const uint32_t ks = k >> log2c;
+        const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
+        ctx = histo + ((uint32_t)nnz_tab[nzl] + fctx) * 2 + prev;
       }
-    } else {
-      if (u) {
-        const int32_t v = UnpackSigned(u);
-        if (v != (int32_t)(int16_t)v) err |= kErrRange;
-        ent[epos++] = k | (uint32_t)v << 16;
-        prev = 1;
-        if (--nzeros == 0) { want_nz = true; ci++; }
+      const uint32_t u = AnsGet(b, state, tab, ctx);
+      it++;
+      if (want_nz) {
+        nzeros = u;
+        if (nzeros + covered > size) { err |= kErrBitstream; break; }
+        const uint8_t fill = (uint8_t)((nzeros + covered - 1) >> log2c);
+        JXL_LDS uint8_t* const cc = col + __umul24(c * 32 + bx, nslots);
+        for (uint32_t ix = 0; ix < (1u << lcx); ix++) cc[__umul24(ix, nslots)] = fill;
+        U2 rec;
+        rec.x = epos; rec.y = nzeros;
+        cblk[(size_t)c * ncells + cell] = rec;
+        if (nzeros) {
+          const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
+          histo = ctx_offset + nbc * 37 + 458 * block_ctx;
+          prev = nzeros > size / 16 ? 0 : 1;
+          k = covered;
+          want_nz = false;
+        } else {
+          ci++;
+        }
       } else {
-        prev = 0;
+        if (u) {
+          const int32_t v = UnpackSigned(u);
+          if (v != (int32_t)(int16_t)v) err |= kErrRange;
+          ent[epos++] = k | (uint32_t)v << 16;
+          prev = 1;
+          if (--nzeros == 0) { want_nz = true; ci++; }
+        } else {
+          prev = 0;
+        }
+        if (++k >= size && nzeros != 0) { err |= kErrBitstream; break; }
       }
-      if (++k >= size && nzeros != 0) { err |= kErrBitstream; break; }
+  #ifdef JXLHIP_PROFILE_HF
+      pf_general += clock64() - pf_t2;
+  #endif
     }
-#ifdef JXLHIP_PROFILE_HF
-    pf_general += clock64() - pf_t2;
-#endif
   }
   if (!err && (state != 0x130000u || b.slow_err)) err |= kErrBitstream;
   const uint64_t used = b.Consumed();

@@ -158,3 +158,5 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers_icc(uint32_t xsize, 
 // The edge rule of the loop filters and the encoder's analysis (dev_util.h ReflectIndex), compiled for the host: index v of a
 // dimension of n samples.
 extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_reflect(int32_t v, int32_t n) { return ReflectIndex(v, n); }
+
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_nnz_ctx(uint32_t nzl) { return NnzBucketCtx(nzl); }
