@@ -441,7 +441,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   for (int i = 0; i < n; i++)
     if (parse_status[i] == DecoderStatus_Ok && frames[i].layers && band_rows > 0) {
       parse_status[i] = DecoderStatus_DecodeError;
-      parse_msg[i] = "band decode of a layered image is not supported";
+      parse_msg[i] = frames[i].layers->patches ? "band decode of an image with patches is not supported" : "band decode of a layered image is not supported";
     }
   bool any_layered = false;
   for (int i = 0; i < n; i++) any_layered |= parse_status[i] == DecoderStatus_Ok && frames[i].layers != nullptr;
@@ -816,6 +816,68 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (!comps.empty()) {
     off_comp_imgs = blob.Take(sizeof(ComposeImage) * comps.size());
     off_comp_frames = blob.Take(sizeof(ComposeFrame) * (size_t)n);
+  }
+  // patches: every patched frame of the batch, its positions listed per 64x64 tile in dictionary order (patch_kernel); the device
+  // pointers (frame and atlas scratch) are filled in with the image records below
+  struct HostPatchRef { int atlas; uint32_t x0, y0; };
+  std::vector<int> patch_image;            // batch image of each PatchFrame
+  std::vector<HostPatchRef> patch_src;     // per PatchRef
+  std::vector<PatchRef> patch_refs;
+  std::vector<PatchPos> patch_pos;
+  std::vector<PatchTile> patch_tiles;
+  std::vector<int32_t> patch_list;
+  for (const Composite& c : comps)
+    for (int j = 0; j < c.count; j++) {
+      const int i = c.first + j;
+      const ParsedFrame& f = frames[i];
+      if (parse_status[i] != DecoderStatus_Ok || f.patch_pos.empty()) continue;
+      const int pf = (int)patch_image.size(), ref0 = (int)patch_refs.size(), pos0 = (int)patch_pos.size();
+      patch_image.push_back(i);
+      for (auto& rr : f.patch_refs) {
+        PatchRef r;
+        memset(&r, 0, sizeof(r));
+        r.w = (int32_t)rr.w; r.h = (int32_t)rr.h;
+        patch_refs.push_back(r);
+        patch_src.push_back(HostPatchRef{c.first + rr.frame, rr.x0, rr.y0});
+      }
+      const int tx = (int)((f.xsize + kPatchTile - 1) / kPatchTile), ty = (int)((f.ysize + kPatchTile - 1) / kPatchTile);
+      std::vector<std::vector<int32_t>> lists((size_t)tx * ty);
+      std::vector<PatchTile> box((size_t)tx * ty);
+      for (size_t k = 0; k < f.patch_pos.size(); k++) {
+        const ParsedFrame::PatchPlace& q = f.patch_pos[k];
+        PatchPos p;
+        memset(&p, 0, sizeof(p));
+        p.x = (int32_t)q.x; p.y = (int32_t)q.y; p.ref = ref0 + (int32_t)q.ref;
+        for (int g = 0; g < 2; g++) { p.mode[g] = q.mode[g]; p.clamp[g] = q.clamp[g]; }
+        patch_pos.push_back(p);
+        if (q.mode[0] == 0 && (f.alpha_index < 0 || q.mode[1] == 0)) continue;   // None everywhere: no pixel changes
+        const int x1 = p.x + (int)f.patch_refs[q.ref].w, y1 = p.y + (int)f.patch_refs[q.ref].h;
+        for (int b = p.y / kPatchTile; b * kPatchTile < y1; b++)
+          for (int a = p.x / kPatchTile; a * kPatchTile < x1; a++) {
+            const size_t t = (size_t)b * tx + a;
+            PatchTile& bx = box[t];
+            const int cx0 = std::max(p.x, a * kPatchTile), cy0 = std::max(p.y, b * kPatchTile);
+            const int cx1 = std::min(x1, (a + 1) * kPatchTile), cy1 = std::min(y1, (b + 1) * kPatchTile);
+            if (lists[t].empty()) { bx.x0 = cx0; bx.y0 = cy0; bx.x1 = cx1; bx.y1 = cy1; }
+            else { bx.x0 = std::min(bx.x0, cx0); bx.y0 = std::min(bx.y0, cy0); bx.x1 = std::max(bx.x1, cx1); bx.y1 = std::max(bx.y1, cy1); }
+            lists[t].push_back(pos0 + (int32_t)k);
+          }
+      }
+      for (size_t t = 0; t < lists.size(); t++) {
+        if (lists[t].empty()) continue;   // tiles without patches get no workgroup
+        PatchTile tl = box[t];
+        tl.frame = pf; tl.first = (int32_t)patch_list.size(); tl.count = (int32_t)lists[t].size(); tl.pad = 0;
+        patch_tiles.push_back(tl);
+        patch_list.insert(patch_list.end(), lists[t].begin(), lists[t].end());
+      }
+    }
+  size_t off_patch_frames = 0, off_patch_refs = 0, off_patch_pos = 0, off_patch_tiles = 0, off_patch_list = 0;
+  if (!patch_tiles.empty()) {
+    off_patch_frames = blob.Take(sizeof(PatchFrame) * patch_image.size());
+    off_patch_refs = blob.Take(sizeof(PatchRef) * patch_refs.size());
+    off_patch_pos = blob.Take(sizeof(PatchPos) * patch_pos.size());
+    off_patch_tiles = blob.Take(sizeof(PatchTile) * patch_tiles.size());
+    off_patch_list = blob.Take(sizeof(int32_t) * patch_list.size());
   }
   const size_t zero_bytes = Align(ws_zero.off, 256);
   EnsureBlob(blob.off);
@@ -1274,8 +1336,34 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
         cf.source[0] = (int32_t)bc.source; cf.source[1] = (int32_t)ba.source;
         cf.clamp[0] = (int32_t)bc.clamp; cf.clamp[1] = (int32_t)ba.clamp;
         cf.save = c.save[j];
+        // a reference-only frame is read by patches only: an empty crop and no save leave the canvas and the slots as they are
+        if (f.frame_type == 2) { cf.w = cf.h = 0; cf.save = -1; }
       }
     }
+  }
+  if (!patch_tiles.empty()) {
+    PatchFrame* pfr = (PatchFrame*)(h_blob + off_patch_frames);
+    for (size_t k = 0; k < patch_image.size(); k++) {
+      const ParsedFrame& f = frames[patch_image[k]];
+      PatchFrame& p = pfr[k];
+      memset(&p, 0, sizeof(p));
+      p.px = (float*)imgs[patch_image[k]].out;   // the frame's f32 layer scratch (layer_f32: every frame of an image with patches)
+      p.w = (int32_t)f.xsize; p.h = (int32_t)f.ysize;
+      p.has_alpha = f.alpha_index >= 0 ? 1 : 0;
+      p.nch = f.ncolor + p.has_alpha;
+      p.premul = (p.has_alpha && f.ec[f.alpha_index].alpha_associated) ? 1 : 0;
+    }
+    for (size_t k = 0; k < patch_refs.size(); k++) {
+      const HostPatchRef& s = patch_src[k];
+      const ParsedFrame& a = frames[s.atlas];
+      const size_t nch = a.ncolor + (a.alpha_index >= 0 ? 1 : 0);
+      patch_refs[k].px = (const float*)imgs[s.atlas].out + ((size_t)s.y0 * a.xsize + s.x0) * nch;
+      patch_refs[k].stride = (int32_t)a.xsize;
+    }
+    memcpy(h_blob + off_patch_refs, patch_refs.data(), sizeof(PatchRef) * patch_refs.size());
+    memcpy(h_blob + off_patch_pos, patch_pos.data(), sizeof(PatchPos) * patch_pos.size());
+    memcpy(h_blob + off_patch_tiles, patch_tiles.data(), sizeof(PatchTile) * patch_tiles.size());
+    memcpy(h_blob + off_patch_list, patch_list.data(), sizeof(int32_t) * patch_list.size());
   }
   memcpy(h_blob + off_imgs, imgs.data(), sizeof(DevImage) * imgs.size());
   d_imgs = (DevImage*)(d_blob + off_imgs);
@@ -1390,6 +1478,13 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     }
     LaunchModularOut(d_imgs, n, max_mod_pixels, stream);
     Mark("modular", stream, 2);
+  }
+  if (!patch_tiles.empty()) {
+    // patched frames (Modular, f32) are final once modular_out_kernel has run; the compositor reads them next, on the same stream
+    LaunchPatches((const PatchFrame*)(d_blob + off_patch_frames), (const PatchTile*)(d_blob + off_patch_tiles), (int)patch_tiles.size(),
+                  (const int32_t*)(d_blob + off_patch_list), (const PatchPos*)(d_blob + off_patch_pos), (const PatchRef*)(d_blob + off_patch_refs),
+                  stream);
+    Mark("patches", stream, 2);
   }
   if (!comps.empty()) {
     LaunchCompose((const ComposeImage*)(d_blob + off_comp_imgs), (const ComposeFrame*)(d_blob + off_comp_frames), (int)comps.size(), max_segments, stream);

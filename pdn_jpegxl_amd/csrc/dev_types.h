@@ -235,6 +235,34 @@ struct ComposeImage {
   uint8_t* out;                                 // the displayed image, oriented, interleaved samples of the output type
 };
 
+// Patches (patch_kernels.hip): a frame's f32 samples updated in place from rectangles of reference-only frames (atlases), before the
+// frame is composited.  Tables built on the host per batch; positions are listed per 64x64 tile of the patched frame in dictionary order.
+constexpr int kPatchTile = 64;
+struct PatchFrame {
+  float* px;                // w*h pixels of nch f32 samples (the frame's layer scratch, as modular_out_kernel wrote it)
+  int32_t w, h, nch;        // nch = colour channels + alpha, alpha last
+  int32_t has_alpha;
+  int32_t premul;           // associated alpha: blending in premultiplied form (as compose_kernel)
+};
+struct PatchRef {           // one rectangle of an atlas
+  const float* px;          // its top-left pixel in the atlas' f32 samples (same nch as the patched frame)
+  int32_t stride;           // atlas width in pixels
+  int32_t w, h, pad;
+};
+struct PatchPos {           // one position of the dictionary: the rectangle `ref` blended at (x, y) of the frame
+  int32_t x, y, ref;
+  int32_t mode[2];          // [0] colour channels, [1] alpha: 0 None, 1 Replace, 2 Add, 3 Mul, 4 BlendAbove, 5 BlendBelow,
+                            // 6 AlphaWeightedAddAbove, 7 AlphaWeightedAddBelow
+  int32_t clamp[2];
+  int32_t pad;
+};
+struct PatchTile {          // one 64x64 tile of a patched frame with at least one position on it
+  int32_t frame;            // PatchFrame index
+  int32_t x0, y0, x1, y1;   // the union of its positions' rectangles, clipped to the tile: the only pixels read and written
+  int32_t first, count;     // its positions: list[first .. first + count), indices into the PatchPos table, dictionary order
+  int32_t pad;
+};
+
 constexpr int kUniGridCells = 2048;   // LDS grid (16-byte leaf records) of the one-section-per-wavefront per-sample Modular decoder (modular_uniform.h)
 constexpr int kBinfoInts = 2 * 1024 + 2 * 65536 + 65536 + 65536 + 64;   // ... + prefix sums of the block widths (placement)
 constexpr int kWpLfInts = 10 * (65536 + 2);   // widest channel of an LF group section: the block-info rows

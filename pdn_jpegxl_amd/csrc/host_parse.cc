@@ -4,6 +4,7 @@
 #include "icc.h"
 #include "../../include/jxlfiletypeio.h"
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <dlfcn.h>
@@ -666,13 +667,20 @@ void CheckSingleFrame(const ParsedFrame& f) {
   REQUIRE(!f.do_ycbcr, "YCbCr frames are not supported yet");
 }
 
-// One frame of a layered image: what the compositor (decoder.cc, compose_kernel) and the per-frame decode accept.
-void CheckLayerFrame(const ParsedFrame& f, size_t index) {
+// One frame of a layered image: what the compositor (decoder.cc, compose_kernel), patch_kernel and the per-frame decode accept.
+// slot_frame: the frame each reference slot holds before this one (-1: empty), frames: the frames up to this one.
+void CheckLayerFrame(const ParsedFrame& f, size_t index, const int* slot_frame, const std::vector<ParsedFrame>& frames) {
   const std::string at = " (layered image, frame " + std::to_string(index) + ")";
-  if (f.frame_type == 2) Fail("reference-only frames are not supported yet" + at);
+  auto ref_only = [&](int s) { return slot_frame[s] >= 0 && frames[slot_frame[s]].frame_type == 2; };
   if (f.frame_type == 1 || (f.flags & 32)) Fail("LF frames are not supported yet" + at);
   if (f.upsampling != 1) Fail("upsampled frames are not supported yet" + at);
-  if (f.flags & 2) Fail("patches are not supported yet" + at);
+  if (f.flags & 2) {
+    // patches read reference-only frames; a frame with the flag and none in any slot is refused before its LfGlobal is read
+    if (!ref_only(0) && !ref_only(1) && !ref_only(2) && !ref_only(3))
+      Fail("patches are not supported yet" + at + ": no reference-only frame is in a slot");
+    if (f.encoding == 0 || f.xyb_encoded) Fail("patches on lossy (VarDCT / XYB) frames are not supported" + at);
+    if (f.frame_type == 2) Fail("patches on reference-only frames are not supported yet" + at);
+  }
   REQUIRE(!f.do_ycbcr, "YCbCr frames are not supported yet");
   if (f.black_index >= 0) Fail("layered CMYK images are not supported");
   if (f.encoding == 0) {
@@ -773,8 +781,73 @@ void ReadTree(Bits& r, ParsedFrame& f, size_t limit) {
   REQUIRE(sr.Final(), "MA tree: ANS final state");
 }
 
+// The patch dictionary: an entropy-coded integer stream of 10 contexts.  Every count is bounded before anything is
+// allocated (libjxl's limits as recalled); positions must lie inside the frame.  The slots and the rectangles' fit inside their
+// reference frames are checked by ParseFile, which knows what each slot holds.
+void ReadPatchDictionary(Bits& r, ParsedFrame& f) {
+  enum { kNumRef = 0, kRefFrame, kSize, kRefPos, kPos, kMode, kOffset, kCount, kAlpha, kClamp };
+  HostCode c;
+  ReadCode(r, 10, c);
+  SymReader sr(c, r);
+  const uint64_t max_ref = 1024 + (uint64_t)f.xsize * f.ysize / 4, max_pos = 4 * max_ref;
+  const uint64_t num_ref = sr.Get(kNumRef);
+  REQUIRE(num_ref <= max_ref, "patch dictionary: too many reference patches");
+  const size_t nec = f.ec.size();
+  uint64_t total = 0, tile_entries = 0;
+  f.patch_refs.clear();
+  f.patch_pos.clear();
+  for (uint64_t i = 0; i < num_ref; i++) {
+    ParsedFrame::PatchRect rr;
+    rr.slot = sr.Get(kRefFrame);
+    REQUIRE(rr.slot < 4, "patch dictionary: reference slot out of range");
+    const uint64_t x0 = sr.Get(kRefPos), y0 = sr.Get(kRefPos), w = (uint64_t)sr.Get(kSize) + 1, h = (uint64_t)sr.Get(kSize) + 1;
+    // (a rectangle of more than 2^31 pixels a side cannot fit a reference frame; ParseFile checks the fit)
+    REQUIRE(x0 + w <= 0x7FFFFFFFu && y0 + h <= 0x7FFFFFFFu, "patch dictionary: a patch rectangle outside its reference frame");
+    rr.x0 = (uint32_t)x0; rr.y0 = (uint32_t)y0; rr.w = (uint32_t)w; rr.h = (uint32_t)h;
+    const uint64_t count = (uint64_t)sr.Get(kCount) + 1;
+    total += count;
+    REQUIRE(count <= max_pos && total <= max_pos, "patch dictionary: too many patch positions");
+    REQUIRE(r.ok(), "truncated patch dictionary");
+    f.patch_refs.push_back(rr);
+    int64_t px = 0, py = 0;
+    for (uint64_t j = 0; j < count; j++) {
+      if (j == 0) { px = sr.Get(kPos); py = sr.Get(kPos); }
+      else { px += Unpack(sr.Get(kOffset)); py += Unpack(sr.Get(kOffset)); }
+      REQUIRE(px >= 0 && py >= 0 && px + (int64_t)w <= (int64_t)f.xsize && py + (int64_t)h <= (int64_t)f.ysize,
+              "patch dictionary: a patch position outside the frame");
+      // the GPU pass lists every position once per 64x64 tile it touches (decoder.cc): bounded like the positions themselves
+      tile_entries += (uint64_t)((px + w - 1) / kPatchTile - px / kPatchTile + 1) * ((py + h - 1) / kPatchTile - py / kPatchTile + 1);
+      REQUIRE(tile_entries <= 4 * max_pos, "patch dictionary: the patches cover the frame too many times over");
+      ParsedFrame::PatchPlace pp;
+      pp.x = (uint32_t)px; pp.y = (uint32_t)py; pp.ref = (uint32_t)i;
+      for (size_t k = 0; k < 1 + nec; k++) {
+        const uint32_t mode = sr.Get(kMode);
+        REQUIRE(mode < 8, "patch dictionary: blend mode out of range");
+        uint32_t alpha = 0, clamp = 0;
+        if (mode >= 4 && nec > 1) alpha = sr.Get(kAlpha);
+        if (mode >= 3) clamp = sr.Get(kClamp) != 0;
+        // BlendAbove / Below and AlphaWeightedAdd Above / Below weigh by an alpha channel: it must be the image's one alpha channel
+        if (mode >= 4 && (f.alpha_index < 0 || (int)alpha != f.alpha_index))
+          Fail("patch blend modes weighted by a channel other than the alpha channel are not supported");
+        if (k == 0 || (int)k - 1 == f.alpha_index) {
+          const int g = k == 0 ? 0 : 1;
+          pp.mode[g] = (uint8_t)mode; pp.clamp[g] = (uint8_t)clamp;
+        } else if (mode != 0) {
+          Fail("patches on extra channels other than alpha are not supported");
+        }
+      }
+      REQUIRE(r.ok(), "truncated patch dictionary");
+      f.patch_pos.push_back(pp);
+    }
+  }
+  REQUIRE(sr.Final(), "patch dictionary: ANS final state");
+  REQUIRE(r.ok(), "truncated patch dictionary");
+}
+
 void ReadLfGlobal(Bits& r, ParsedFrame& f) {
-  REQUIRE(!(f.flags & (1 | 2 | 16)), "noise / patches / splines are not supported yet");
+  // patches are read only in layered images, after ParseFile has found a reference-only frame for them (CheckLayerFrame)
+  REQUIRE(!(f.flags & (1 | 16)) && (!(f.flags & 2) || f.is_layer), "noise / patches / splines are not supported yet");
+  if (f.flags & 2) ReadPatchDictionary(r, f);
   REQUIRE(!(f.flags & 32), "LF frames are not supported yet");
   f.m_lf[0] = 1.0f / 4096; f.m_lf[1] = 1.0f / 512; f.m_lf[2] = 1.0f / 256;
   if (!r.b()) for (auto& v : f.m_lf) { v = r.F16() / 128; REQUIRE(v >= 1e-8f, "LF dequantisation factor"); }
@@ -1618,26 +1691,56 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
   auto layers = std::make_shared<Layers>();
   layers->canvas_w = image.xsize; layers->canvas_h = image.ysize;
   uint64_t pos = frame_base / 8;
+  int slot_frame[4] = {-1, -1, -1, -1};                 // the frame each reference slot holds (-1: empty)
+  std::vector<std::array<int, 4>> slots_before;         // ... as frame k finds them
   for (;;) {
     if (layers->frames.size() >= (size_t)kMaxLayerFrames)
       Fail("layered images of more than " + std::to_string(kMaxLayerFrames) + " frames before the displayed one are not supported");
     layers->frames.push_back(image);
     ParsedFrame& fr = layers->frames.back();
+    const size_t k = layers->frames.size() - 1;
     fr.is_layer = true;
     Bits rr(f.cs, f.cs_size);
     rr.Skip((size_t)pos * 8);
     ReadFrameHeader(rr, fr);
     ReadToc(rr, fr, (size_t)pos * 8);
-    CheckLayerFrame(fr, layers->frames.size() - 1);
+    CheckLayerFrame(fr, k, slot_frame, layers->frames);
+    slots_before.push_back({slot_frame[0], slot_frame[1], slot_frame[2], slot_frame[3]});
     const bool can_ref = !fr.is_last && (fr.duration == 0 || fr.save_ref != 0);
     layers->save.push_back(can_ref ? (int)fr.save_ref : -1);
+    if (can_ref) slot_frame[fr.save_ref] = (int)k;
+    if (fr.flags & 2) layers->patches = true;
     if (IsDisplayed(fr)) break;
     pos = fr.frame_end;
     REQUIRE(pos < f.cs_size, "the codestream ends before a displayed frame");
   }
+  // A reference-only frame is kept for the patches of later frames; one that no later frame up to the displayed one can read (no
+  // patches frame finds it in its slot) is refused here, one that no dictionary reads once they are parsed (below)
+  const size_t nfr = layers->frames.size();
+  std::vector<uint8_t> readable(nfr, 0);
+  for (size_t j = 0; j < nfr; j++)
+    if (layers->frames[j].flags & 2)
+      for (int s = 0; s < 4; s++) if (slots_before[j][s] >= 0) readable[slots_before[j][s]] = 1;
+  for (size_t k = 0; k < nfr; k++)
+    if (layers->frames[k].frame_type == 2 && !readable[k])
+      Fail("reference-only frames are not supported yet (layered image, frame " + std::to_string(k) + "): no later frame reads it through patches");
+  // a slot holding a reference-only frame is read by patches only, never as the canvas a frame blends onto (the source slot is read
+  // by a blend mode other than kReplace and outside a crop that does not cover the canvas)
+  for (size_t k = 0; k < nfr; k++) {
+    const ParsedFrame& fr = layers->frames[k];
+    if (fr.frame_type != 0 && fr.frame_type != 3) continue;
+    const bool partial = fr.have_crop && !(fr.crop_x0 <= 0 && fr.crop_y0 <= 0 && fr.crop_x0 + (int64_t)fr.xsize >= image.xsize &&
+                                           fr.crop_y0 + (int64_t)fr.ysize >= image.ysize);
+    for (auto& b : fr.blend) {
+      const int src = slots_before[k][b.source & 3];
+      if ((b.mode != 0 || partial) && src >= 0 && layers->frames[src].frame_type == 2)
+        Fail("frames blending onto a slot that holds a reference-only frame are not supported (layered image, frame " + std::to_string(k) + ")");
+    }
+  }
   // Images whose frames all replace every channel are composited from the frames' output-type samples (a selection: each pixel leaves
-  // as its frame's own decode writes it); any other blend mode needs f32 frames, which lossy (XYB) frames do not produce bit-exactly
-  layers->raw = true;
+  // as its frame's own decode writes it); any other blend mode needs f32 frames, which lossy (XYB) frames do not produce bit-exactly.
+  // Patches blend inside a frame: such images always take the f32 route.
+  layers->raw = !layers->patches;
   for (auto& fr : layers->frames) layers->raw = layers->raw && ReplacesAll(fr);
   for (size_t k = 0; k < layers->frames.size(); k++) {
     ParsedFrame& fr = layers->frames[k];
@@ -1651,8 +1754,28 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
   f.name = layers->frames.back().name;
   f.is_last = layers->frames.back().is_last;
   f.duration = layers->frames.back().duration;
-  if (!headers_only)
+  if (!headers_only) {
     for (auto& fr : layers->frames) ParseFrameBody(fr);
+    // the dictionaries against the slots: each rectangle lies in a reference-only frame that its slot holds
+    std::vector<uint8_t> read(nfr, 0);
+    for (size_t j = 0; j < nfr; j++) {
+      ParsedFrame& fr = layers->frames[j];
+      const std::string at = " (layered image, frame " + std::to_string(j) + ")";
+      for (auto& rr : fr.patch_refs) {
+        const int src = slots_before[j][rr.slot];
+        if (src < 0) Fail("patches from an empty reference slot" + at);
+        const ParsedFrame& atlas = layers->frames[src];
+        if (atlas.frame_type != 2) Fail("patches from a slot that holds a regular frame are not supported" + at);
+        if ((uint64_t)rr.x0 + rr.w > atlas.xsize || (uint64_t)rr.y0 + rr.h > atlas.ysize)
+          Fail("patch dictionary: a patch rectangle outside its reference frame" + at);
+        rr.frame = src;
+        read[src] = 1;
+      }
+    }
+    for (size_t k = 0; k < nfr; k++)
+      if (layers->frames[k].frame_type == 2 && !read[k])
+        Fail("reference-only frames are not supported yet (layered image, frame " + std::to_string(k) + "): no patch reads it");
+  }
   f.layers = std::move(layers);
 }
 

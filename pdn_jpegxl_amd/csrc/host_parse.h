@@ -110,6 +110,12 @@ struct ParsedFrame {
   bool is_layer = false;            // one frame of a layered image: decoded to scratch, then composited (decoder.cc)
   bool layer_f32 = false;           // ... as unclamped f32 samples (images that blend); otherwise in the output type as a lone frame
   std::shared_ptr<Layers> layers;   // layered image (several frames, a crop or a blend mode make the displayed image); null otherwise
+  // patches (flags & 2; layered images only): the dictionary that opens LfGlobal, checked against the frame's size when
+  // read and against the reference slots by ParseFile.  Records of extra channels other than alpha are not kept (none can be non-None).
+  struct PatchRect { uint32_t slot = 0, x0 = 0, y0 = 0, w = 1, h = 1; int32_t frame = -1; };   // frame: the atlas, index in Layers::frames
+  struct PatchPlace { uint32_t x = 0, y = 0, ref = 0; uint8_t mode[2] = {0, 0}, clamp[2] = {0, 0}; };   // [0] colour, [1] alpha
+  std::vector<PatchRect> patch_refs;
+  std::vector<PatchPlace> patch_pos;   // dictionary order: where patches overlap, the later one blends onto the earlier result
   bool gab = true;
   float gab_w1[3], gab_w2[3];
   uint32_t epf_iters = 2;
@@ -180,6 +186,7 @@ struct Layers {
   std::vector<ParsedFrame> frames;
   std::vector<int> save;
   bool raw = false;   // every frame replaces every channel: frames are decoded in the output type and the compositor selects
+  bool patches = false;   // some frame applies patches from reference-only (type 2) frames: decoder.cc runs patch_kernel
 };
 
 // Throws ParseError.  headers_only: stop after the frame header + TOC (jxlhip_peek / pass 1 of LoadImage).

@@ -43,6 +43,9 @@ void LaunchFilterTiles(const DevImage* imgs, int nimg, int max_w, int max_h, int
 
 // compose_kernels.hip: blend the frames of `nimg` layered images (tables in device memory) and write their displayed images
 void LaunchCompose(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_segments, hipStream_t s);
+// patch_kernels.hip: apply the patches of every patched frame of the batch in place (one workgroup per tile with positions)
+void LaunchPatches(const PatchFrame* frames, const PatchTile* tiles, int ntiles, const int32_t* list, const PatchPos* pos, const PatchRef* refs,
+                   hipStream_t s);
 
 // the batch's status words into pinned host memory, by a kernel (kernels.hip)
 void LaunchStatusToHost(const uint32_t* src, uint32_t* dst_pinned, int nwords, hipStream_t s);

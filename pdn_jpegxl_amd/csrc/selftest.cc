@@ -160,3 +160,33 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers_icc(uint32_t xsize, 
 extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_reflect(int32_t v, int32_t n) { return ReflectIndex(v, n); }
 
 extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_nnz_ctx(uint32_t nzl) { return NnzBucketCtx(nzl); }
+
+// An entropy-coded stream of n (context, value) tokens over num_ctx contexts, as the encoder writes its host-side streams (code header
+// by BuildAndWriteCode, tokens by WriteTokensHost): the CPU and GPU tests write patch dictionaries with it.  Writes the bytes into dst
+// (zero-padded to a byte) and the exact bit count into *nbits; returns the byte count (0 on failure or when dst is too small).
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_write_tokens(uint32_t num_ctx, const uint32_t* ctxs, const uint32_t* values, uint32_t n,
+                                                                 uint8_t* dst, size_t capacity, uint64_t* nbits) {
+  try {
+    std::vector<uint32_t> hist((size_t)num_ctx * kEncAlphabet, 0);
+    std::vector<EncToken> toks;
+    for (uint32_t i = 0; i < n; i++) {
+      if (ctxs[i] >= num_ctx) return 0;
+      uint32_t tok, nb, bits;
+      HybridEncode(values[i], &tok, &nb, &bits);
+      hist[(size_t)ctxs[i] * kEncAlphabet + tok]++;
+      toks.push_back(EncToken{ctxs[i], values[i]});
+    }
+    BitWriter bw;
+    EncCode code;
+    BuildAndWriteCode(hist.data(), num_ctx, (int)num_ctx, std::vector<uint8_t>(num_ctx, 0), bw, code);
+    WriteTokensHost(toks, code, bw);
+    const uint64_t bit_count = bw.BitCount();
+    std::vector<uint8_t> bytes = bw.Finish();
+    if (bytes.size() > capacity) return 0;
+    memcpy(dst, bytes.data(), bytes.size());
+    *nbits = bit_count;
+    return bytes.size();
+  } catch (...) {
+    return 0;
+  }
+}
