@@ -163,6 +163,8 @@ JXLFILETYPEIO_API DecoderStatus jxlhip_finish(JxlHipDecoder* dec, DecoderStatus*
 
 /* Stage taps of the most recent (synchronised) batch, image `index`, for parity tests.  `name` as in
  * DESIGN.md ("lf", "qcoef", "xyb_idct", "xyb_filtered", "strategy", "raw_quant", "sharpness", "alpha", ...).
+ * Frames with synthetic noise, under "debug_taps": "noise_rnd" (the random planes R_k, channel 0..2) and "noise" (the convolved
+ * planes N_k that the output phase adds), each w * h f32 in tight rows.
  * Copies up to `capacity` bytes device->host; returns the full byte size of the plane (0 = unknown name).
  * `index` counts the batch's decoded images: a layered file contributes one per frame (in file order, in its place among the files),
  * so in a batch with layered files it is not the file index. */

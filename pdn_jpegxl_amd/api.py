@@ -321,7 +321,7 @@ def static_table(name, index, dtype):
 
 _PLANE_DTYPES = {"lf": np.float32, "lf_quant": np.int32, "cellinfo": np.uint32, "raw_quant": np.uint16, "sharpness": np.uint8,
                  "ytox": np.int8, "ytob": np.int8, "alpha": np.uint8, "inv_sigma": np.float32, "qcoef": np.int32,
-                 "xyb_idct": np.float32, "xyb_filtered": np.float32}
+                 "xyb_idct": np.float32, "xyb_filtered": np.float32, "noise_rnd": np.float32, "noise": np.float32}
 
 
 def _last_stage_times(fn_name):

@@ -126,7 +126,7 @@ struct JxlHipDecoder {
   // Per-batch state lives in one of three slots so that, when the caller does not synchronise between batches, the LF
   // stage of batch k+2 (stream_lf), the HF-coefficient stage of batch k+1 (stream_hf) and the alpha + pixel stages of
   // batch k (main stream) run concurrently: the serial entropy kernels leave most issue slots of the chip idle.
-  struct Tap { std::vector<uint8_t> qcoef[3], xyb_idct[3], xyb_filtered[3]; };
+  struct Tap { std::vector<uint8_t> qcoef[3], xyb_idct[3], xyb_filtered[3], noise_rnd[3], noise[3]; };   // (noise: frames with the flag only)
   struct Slot {
     // grow-only buffers
     uint8_t* d_ws = nullptr; size_t ws_cap = 0;        // planes
@@ -146,7 +146,7 @@ struct JxlHipDecoder {
     std::vector<size_t> status_off;      // offset of each image's status words in the workspace
     DevImage* d_imgs = nullptr;
     bool pending = false;
-    hipEvent_t lf_done = nullptr, hf_done = nullptr, done = nullptr;
+    hipEvent_t lf_done = nullptr, hf_done = nullptr, done = nullptr, uploaded = nullptr;
     std::vector<Tap> taps;
     // timing: two event chains (LF stream, main stream)
     std::vector<std::string> stage_names;
@@ -230,6 +230,7 @@ JxlHipDecoder::JxlHipDecoder(int dev) {
     HIP_OK(hipEventCreateWithFlags(&S.lf_done, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&S.hf_done, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&S.uploaded, hipEventDisableTiming));
   }
   if (const char* e = Knob("JXLHIP_NO_OVERLAP")) overlap = atoi(e) == 0;
   const StaticTables& st = GetStaticTables();
@@ -283,6 +284,7 @@ JxlHipDecoder::~JxlHipDecoder() {
     if (S.lf_done) (void)hipEventDestroy(S.lf_done);
     if (S.hf_done) (void)hipEventDestroy(S.hf_done);
     if (S.done) (void)hipEventDestroy(S.done);
+    if (S.uploaded) (void)hipEventDestroy(S.uploaded);
     (void)hipFree(S.d_ws); (void)hipFree(S.d_blob);
     if (S.h_blob) (void)hipHostFree(S.h_blob);
     if (S.h_status) (void)hipHostFree(S.h_status);
@@ -679,6 +681,14 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   std::vector<size_t> chunk_tmp((size_t)pixel_chunk * 3), chunk_xyb((size_t)pixel_chunk * 3), chunk_coef((size_t)pixel_chunk * 3);
   if (chunk_pix)
     for (int k = 0; k < pixel_chunk * 3; k++) { chunk_tmp[k] = ws.Take(4 * chunk_pix); chunk_xyb[k] = ws.Take(4 * chunk_pix); chunk_coef[k] = ws.Take(4 * chunk_pix); }
+  // Frames with synthetic noise: three more planes per chunk slot for the convolved noise the output phase adds (12 B/px, only when
+  // a frame of the batch has noise).  The random planes they are made from need none: they live in the tmp planes.
+  size_t noise_pix = 0;
+  for (int i = 0; i < n; i++)
+    if (parse_status[i] == DecoderStatus_Ok && frames[i].has_noise) noise_pix = std::max(noise_pix, (size_t)frames[i].xsize * frames[i].ysize);
+  std::vector<size_t> chunk_noise((size_t)pixel_chunk * 3);
+  if (noise_pix)
+    for (int k = 0; k < pixel_chunk * 3; k++) chunk_noise[k] = ws.Take(4 * noise_pix);
   // The reference's decoder library hands out the image as displayed (orientation applied; it is only kept when the caller asks,
   // which Decoder/DecoderContext.cpp never does): such frames are decoded into a scratch buffer and re-laid out at the end.
   // A band is a set of VarDCT group rows.  A Modular frame has no band mode (global Squeeze / whole-image transforms: SURVEY 8e
@@ -894,7 +904,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   for (auto& im : imgs) memset(&im, 0, sizeof(DevImage));
   status_off.assign(n, 0);
   size_t lds_hf = 0, lds_hf_lanes = 0, lds_lf = 0, lds_alpha = 0;   // lds_hf: tables + lanes, the largest workgroup; lds_hf_lanes: the most lanes (global-table variant)
-  bool any_alpha = false, any_unfiltered = false;
+  bool any_alpha = false, any_unfiltered = false, any_noise = false;
   int stage_mask = 0;   // LDS-tiled loop-filter stage kernels some frame of the batch needs (bit s: filter_tile_kernel<s>)
   int any_fused = 0, any_fused2 = 0;   // 1: fused frames (with a second iteration) of the two-pixels-per-lane kernels, 2: others
   int max_w = 1, max_h = 1, max_tiles = 1;
@@ -1140,6 +1150,14 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       d.tmp[c] = (float*)(wr + chunk_tmp[(size_t)(i % pixel_chunk) * 3 + c]); d.xyb[c] = (float*)(wr + chunk_xyb[(size_t)(i % pixel_chunk) * 3 + c]);
       d.xyb2[c] = (float*)d.coef[c];   // the dense coefficient planes (generic path only) are dead once the frame is reconstructed
     }
+    if (f.has_noise) {
+      // the generator fills the group rows the band's 5x5 support reaches: the band's rows and one more each side, like the decode
+      d.has_noise = 1; d.noise_gy0 = d.dec_gy0; d.noise_gy1 = d.dec_gy1;
+      d.noise_seed[0] = f.noise_seed[0]; d.noise_seed[1] = f.noise_seed[1];
+      memcpy(d.noise_lut, f.noise_lut, sizeof(d.noise_lut));
+      for (int c = 0; c < 3; c++) { d.noise_rnd[c] = d.tmp[c]; d.noise[c] = (float*)(wr + chunk_noise[(size_t)(i % pixel_chunk) * 3 + c]); }
+      any_noise = true;
+    }
     d.lf_extra = wr + l.lf_extra;
     d.rawq = (uint16_t*)(wr + l.rawq); d.sharp = wr + l.sharp;
     d.ytox = (int8_t*)(wr + l.ytox); d.ytob = (int8_t*)(wr + l.ytob);
@@ -1194,6 +1212,13 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       const bool rgba8 = d.out_bits == 8 && d.to_srgb <= 1 && !d.unpremultiply && (d.ncolor == 3 || d.ncolor == 1) &&
                          d.nch_out == d.ncolor + (d.has_alpha ? 1 : 0) && !d.cmyk;
       d.stream_pairs = (even && (d.fused_gab_epf1 == 2 || rgba8) ? 1 : 0) | (even && d.fused_gab_epf1 == 2 && rgba8 ? 2 : 0);
+      if (d.has_noise) {
+        // noise is added by the general output path: the kernel that writes the pixels is never a pair kernel.  Which conversion to
+        // 8 bits the same frame WITHOUT noise would get is kept, so that noise of strength zero changes no byte.
+        const int out_bit = d.fused_gab_epf1 == 2 ? 2 : 1;
+        d.noise_pairs_twin = (d.stream_pairs & out_bit) ? 1 : 0;
+        d.stream_pairs &= ~out_bit;
+      }
     }
     if (d.fused_gab_epf1) {
       d.final_stage = 5;
@@ -1377,6 +1402,19 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (!(skip_stages & 1)) HIP_OK(hipMemsetAsync(d_ws, 0, zero_bytes, s_lf));
   HIP_OK(hipMemcpyAsync(d_blob, h_blob, blob.off, hipMemcpyHostToDevice, s_lf));
   Mark("upload+clear", s_lf, 0);
+  // Synthetic noise depends on nothing but the uploaded descriptors: the first pixel chunk's planes are generated and convolved on the
+  // main stream while the entropy chains run on theirs (a group's generator is a chain of 12 288 dependent steps, 1.25 ms for a 4K
+  // frame).  The random planes borrow the chunk's tmp planes and are dead again before the reconstruction needs those.  Later chunks
+  // share the first one's planes and wait their turn in the pixel loop; so does everything when one stream carries the whole decode.
+  const bool pix_on_hf = Knob("JXLHIP_PIX_ON_HF") && s_hf != stream;
+  const bool early_noise = any_noise && !debug_taps && s_lf != stream && !pix_on_hf;
+  if (early_noise) {
+    HIP_OK(hipEventRecord(S.uploaded, s_lf));
+    HIP_OK(hipStreamWaitEvent(stream, S.uploaded, 0));
+    Mark("noise_start", stream, 3);
+    LaunchNoise(d_imgs, std::min(pixel_chunk, n), max_groups, max_w, max_h, stream);
+    Mark("noise", stream, 3);
+  }
   // wavefronts that decode one section run their row loops on the scalar unit from the per-residue tables built above
   // (measured at batch 384: LF sections as four such wavefronts per workgroup - 135.7 ms per batch against 125.1 with four lanes of
   // one wavefront: large batches keep the lane layout, the scalar path is for small ones)
@@ -1448,7 +1486,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     Mark("alpha_finish", stream, 2);
   }
   // experiment knob: the pixel stages behind the HF chain on ITS stream (no overlap between a batch's pixels and the next batch's HF decode)
-  hipStream_t s_pix = (Knob("JXLHIP_PIX_ON_HF") && s_hf != stream) ? s_hf : stream;
+  hipStream_t s_pix = pix_on_hf ? s_hf : stream;
   for (int c0 = 0; c0 < n; c0 += pixel_chunk) {
     const int cnt = std::min(pixel_chunk, n - c0);
     if (!(skip_stages & 8))
@@ -1458,6 +1496,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     LaunchGenericReconstruct(d_imgs + c0, cnt, d_basis_all, d_basis_small, d_llf_scale, s_pix);
     Mark("reconstruct_generic", s_pix, 2);
     if (debug_taps) { HIP_OK(hipStreamSynchronize(s_pix)); CopyPlaneTap(1); }
+    // synthetic noise: the random planes go into the tmp planes, which the reconstruction above no longer needs
+    if (any_noise && !(early_noise && c0 == 0)) { LaunchNoise(d_imgs + c0, cnt, max_groups, max_w, max_h, s_pix); Mark("noise", s_pix, 2); }
     if (!(skip_stages & 16))
     LaunchFilterTiles(d_imgs + c0, cnt, max_w, max_h, stage_mask, any_unfiltered, any_fused, any_fused2, s_pix);
     Mark("filters+output", s_pix, 2);
@@ -1635,6 +1675,14 @@ void JxlHipDecoder::CopyPlaneTap(int stage) {
       dst.resize(bytes);
       HIP_OK(hipMemcpy(dst.data(), src, bytes, hipMemcpyDeviceToHost));
     }
+    if (stage == 2 && d.has_noise) {   // w x h, tight rows; rows outside a band's reach are not generated (random planes) / convolved
+      const size_t nb = (size_t)d.w * d.h * 4;
+      for (int c = 0; c < 3; c++) {
+        taps[i].noise_rnd[c].resize(nb); taps[i].noise[c].resize(nb);
+        HIP_OK(hipMemcpy(taps[i].noise_rnd[c].data(), d.noise_rnd[c], nb, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(taps[i].noise[c].data(), d.noise[c], nb, hipMemcpyDeviceToHost));
+      }
+    }
   }
 }
 
@@ -1796,6 +1844,8 @@ size_t jxlhip_read_plane(JxlHipDecoder* dec, int32_t index, const char* name, in
     if (nm == "qcoef") { src = S.taps[index].qcoef[c].data(); bytes = S.taps[index].qcoef[c].size(); }
     else if (nm == "xyb_idct") { src = S.taps[index].xyb_idct[c].data(); bytes = S.taps[index].xyb_idct[c].size(); }
     else if (nm == "xyb_filtered") { src = S.taps[index].xyb_filtered[c].data(); bytes = S.taps[index].xyb_filtered[c].size(); }
+    else if (nm == "noise_rnd") { src = S.taps[index].noise_rnd[c].data(); bytes = S.taps[index].noise_rnd[c].size(); }
+    else if (nm == "noise") { src = S.taps[index].noise[c].data(); bytes = S.taps[index].noise[c].size(); }
   }
   (void)pix;
   if (!src || !bytes) return 0;

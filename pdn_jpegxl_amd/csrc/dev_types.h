@@ -213,6 +213,14 @@ struct DevImage {
   uint8_t* alpha;           // w*h samples of the OUTPUT type (u8, or u16 when out_bits == 16), already scaled from alpha_bits
   uint8_t* out;             // w*h*nch_out interleaved samples of the output type
   uint32_t* status;         // [0] error bits, [1..] debug
+  // Synthetic noise (frame flag 1): noise_generate_kernel fills the random planes of group rows
+  // [noise_gy0, noise_gy1), noise_convolve_kernel turns pixel rows [band_y0, band_y1) of them into the planes the output phase adds
+  int32_t has_noise, noise_gy0, noise_gy1;
+  int32_t noise_pairs_twin; // the frame without noise would be written by a two-pixels-per-lane kernel (its 8-bit conversion is kept)
+  uint32_t noise_seed[2];   // visible / non-visible frame index
+  float noise_lut[8];
+  float* noise_rnd[3];      // R_k: w*h, tight rows (they live in the tmp planes, dead once the frame is reconstructed)
+  float* noise[3];          // N_k: w*h, tight rows
 };
 
 // Layered images (compose_kernel, compose_kernels.hip): every frame is decoded on its own into f32 scratch, then one launch blends

@@ -846,8 +846,15 @@ void ReadPatchDictionary(Bits& r, ParsedFrame& f) {
 
 void ReadLfGlobal(Bits& r, ParsedFrame& f) {
   // patches are read only in layered images, after ParseFile has found a reference-only frame for them (CheckLayerFrame)
-  REQUIRE(!(f.flags & (1 | 16)) && (!(f.flags & 2) || f.is_layer), "noise / patches / splines are not supported yet");
+  REQUIRE(!(f.flags & 16) && (!(f.flags & 2) || f.is_layer), "noise / patches / splines are not supported yet");
   if (f.flags & 2) ReadPatchDictionary(r, f);
+  if (f.flags & 1) {
+    // noise parameters: eight 10-bit strength values; the planes themselves are generated on the GPU
+    REQUIRE(f.encoding == 0, "noise on Modular frames is not supported yet");
+    for (auto& v : f.noise_lut) v = (float)r.u(10) * (1.0f / 1024);
+    REQUIRE(r.ok(), "truncated noise parameters");
+    f.has_noise = true;
+  }
   REQUIRE(!(f.flags & 32), "LF frames are not supported yet");
   f.m_lf[0] = 1.0f / 4096; f.m_lf[1] = 1.0f / 512; f.m_lf[2] = 1.0f / 256;
   if (!r.b()) for (auto& v : f.m_lf) { v = r.F16() / 128; REQUIRE(v >= 1e-8f, "LF dequantisation factor"); }
@@ -1693,6 +1700,7 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
   uint64_t pos = frame_base / 8;
   int slot_frame[4] = {-1, -1, -1, -1};                 // the frame each reference slot holds (-1: empty)
   std::vector<std::array<int, 4>> slots_before;         // ... as frame k finds them
+  uint32_t visible_index = 0, nonvisible_index = 0;     // what seeds a frame's noise
   for (;;) {
     if (layers->frames.size() >= (size_t)kMaxLayerFrames)
       Fail("layered images of more than " + std::to_string(kMaxLayerFrames) + " frames before the displayed one are not supported");
@@ -1705,6 +1713,9 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
     ReadFrameHeader(rr, fr);
     ReadToc(rr, fr, (size_t)pos * 8);
     CheckLayerFrame(fr, k, slot_frame, layers->frames);
+    fr.noise_seed[0] = visible_index; fr.noise_seed[1] = nonvisible_index;
+    if (fr.is_last || fr.duration > 0) { visible_index++; nonvisible_index = 0; }
+    else nonvisible_index++;
     slots_before.push_back({slot_frame[0], slot_frame[1], slot_frame[2], slot_frame[3]});
     const bool can_ref = !fr.is_last && (fr.duration == 0 || fr.save_ref != 0);
     layers->save.push_back(can_ref ? (int)fr.save_ref : -1);

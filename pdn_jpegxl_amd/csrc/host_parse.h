@@ -116,6 +116,11 @@ struct ParsedFrame {
   struct PatchPlace { uint32_t x = 0, y = 0, ref = 0; uint8_t mode[2] = {0, 0}, clamp[2] = {0, 0}; };   // [0] colour, [1] alpha
   std::vector<PatchRect> patch_refs;
   std::vector<PatchPlace> patch_pos;   // dictionary order: where patches overlap, the later one blends onto the earlier result
+  // noise (flags & 1; VarDCT frames): LfGlobal's eight strength values, and the frame's (visible, non-visible) frame indexes that
+  // seed the generator (a lone frame: 0, 0)
+  bool has_noise = false;
+  float noise_lut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t noise_seed[2] = {0, 0};
   bool gab = true;
   float gab_w1[3], gab_w2[3];
   uint32_t epf_iters = 2;

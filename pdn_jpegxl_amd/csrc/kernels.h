@@ -41,6 +41,10 @@ void LaunchReconTiles(const DevImage* imgs, int nimg, int max_tiles, const float
 void LaunchFilterTiles(const DevImage* imgs, int nimg, int max_w, int max_h, int stage_mask, bool any_unfiltered,
                        int any_fused, int any_fused2, hipStream_t s);
 
+// noise_kernels.hip: frames with synthetic noise (the others return at once): the random planes of their decoded group rows, then the
+// 5x5 convolution of the band's pixel rows into the planes the output phase of the filter kernels adds
+void LaunchNoise(const DevImage* imgs, int nimg, int max_groups, int max_w, int max_h, hipStream_t s);
+
 // compose_kernels.hip: blend the frames of `nimg` layered images (tables in device memory) and write their displayed images
 void LaunchCompose(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_segments, hipStream_t s);
 // patch_kernels.hip: apply the patches of every patched frame of the batch in place (one workgroup per tile with positions)

@@ -195,14 +195,69 @@ __device__ __forceinline__ void WritePixelA(const DevImage& im, int x, int y, fl
 }
 // The common layouts (u8 samples, sRGB or linear transfer) without the branches of the general function: used by the fused filter
 // kernel, whose output phase is a large part of its time.
-__device__ __forceinline__ bool PlainOutput(const DevImage& im) { return im.out_bits == 8 && im.to_srgb <= 1 && !im.unpremultiply; }
+// (frames with noise take the general path of the streaming kernels: the addition lives in WritePixelGeneral / WritePixel only)
+__device__ __forceinline__ bool PlainOutput(const DevImage& im) { return im.out_bits == 8 && im.to_srgb <= 1 && !im.unpremultiply && !im.has_noise; }
+// Synthetic noise (rule 4): the strength for intensity v from the frame's eight-entry table, linear between entries
+__device__ __forceinline__ float NoiseStrength(const DevImage& im, float v) {
+  const float s = fmaxf(0.f, 6.0f * v);
+  const int i = (int)fminf(s, 6.0f);
+  const float t = fminf(s - (float)i, 1.0f);
+  const float lo = im.noise_lut[i], hi = im.noise_lut[i + 1];
+  return fminf(fmaxf(lo + (hi - lo) * t, 0.f), 1.0f);
+}
+// ... and the addition of the convolved planes (noise_kernels.hip) to a filtered XYB pixel, before the inverse opsin transform
+__device__ __forceinline__ void AddNoise(const DevImage& im, int x, int y, float& X, float& Y, float& B) {
+  const size_t o = (size_t)y * im.w + x;
+  const float n0 = im.noise[0][o], n1 = im.noise[1][o], n2 = im.noise[2][o];
+  const float sr = NoiseStrength(im, 0.5f * (Y + X)), sg = NoiseStrength(im, 0.5f * (Y - X));
+  const float shared = n2 * (127.0f / 128.0f);
+  const float red = (n0 * (1.0f / 128.0f) + shared) * sr, green = (n1 * (1.0f / 128.0f) + shared) * sg;
+  const float rg = red + green;
+  X += im.base_x * rg + (red - green);
+  Y += rg;
+  B += im.base_b * rg;
+}
+// XYB -> sRGB-encoded u8 (the plain output layouts)
+__device__ __forceinline__ uint32_t PixelToRgba8(const DevImage& im, float X, float Y, float B, uint32_t a) {
+  const float gr = Y + X - im.opsin_bias_cbrt[0], gg = Y - X - im.opsin_bias_cbrt[1], gb = B - im.opsin_bias_cbrt[2];
+  const float mr = gr * gr * gr + im.opsin_bias[0], mg = gg * gg * gg + im.opsin_bias[1], mb = gb * gb * gb + im.opsin_bias[2];
+  float r = im.opsin_inv[0] * mr + im.opsin_inv[1] * mg + im.opsin_inv[2] * mb;
+  float g = im.opsin_inv[3] * mr + im.opsin_inv[4] * mg + im.opsin_inv[5] * mb;
+  float bl = im.opsin_inv[6] * mr + im.opsin_inv[7] * mg + im.opsin_inv[8] * mb;
+  // to 8 bits with v_cvt_pk_u8_f32: converts (round to nearest, ties to even - tools/cvt_probe.hip), saturates to 0 .. 255, maps NaN to
+  // 0 and inserts the byte, in ONE instruction per channel instead of scale / max / min / add / convert / shift / or; the * 255 is
+  // folded into the transfer curve's constants.  (Differs from round-half-up only on exact ties.)
+  if (im.to_srgb) { r = SrgbOetf255T(r); g = SrgbOetf255T(g); bl = SrgbOetf255T(bl); }
+  else { r *= 255.0f; g *= 255.0f; bl *= 255.0f; }
+  uint32_t px = a << 24;
+  px = __builtin_amdgcn_cvt_pk_u8_f32(r, 0, px);
+  px = __builtin_amdgcn_cvt_pk_u8_f32(g, 1, px);
+  px = __builtin_amdgcn_cvt_pk_u8_f32(bl, 2, px);
+  return px;
+}
 // Out of line on purpose: inlined four times into the fused filter kernel's unrolled output phase, the general function more than
 // doubled that kernel's code (2.3 k -> 5.8 k instructions) and cost 8 % of its speed on the plain path that never executes it.
 __device__ __noinline__ void WritePixelGeneral(const DevImage& im, int x, int y, float X, float Y, float B, uint32_t a) {
+  if (im.has_noise) {
+    AddNoise(im, x, y, X, Y, B);
+    // 8-bit sRGB / linear layouts: the conversion this pixel gets in the same frame without noise (PixelToRgba8 in the pair kernels
+    // and for the whole RGBA quads of the four-pixel kernels, WritePixelA elsewhere), so that noise of strength zero changes no byte
+    if (im.out_bits == 8 && im.to_srgb <= 1 && !im.unpremultiply && im.final_stage == 5 &&
+        (im.noise_pairs_twin || (im.nch_out == 4 && (x | 3) < im.w))) {
+      const uint32_t px = PixelToRgba8(im, X, Y, B, a);
+      uint8_t* out = im.out + ((size_t)(y - im.band_y0) * im.w + x) * im.nch_out;
+      if (im.nch_out == 4) *(uint32_t*)out = px;
+      else if (im.nch_out == 3) { out[0] = (uint8_t)px; out[1] = (uint8_t)(px >> 8); out[2] = (uint8_t)(px >> 16); }
+      else { out[0] = (uint8_t)(px >> 8); if (im.nch_out == 2) out[1] = (uint8_t)(px >> 24); }
+      return;
+    }
+  }
   WritePixelA(im, x, y, X, Y, B, a);
 }
 __device__ __forceinline__ void WritePixel(const DevImage& im, int x, int y, float X, float Y, float B) {
-  WritePixelA(im, x, y, X, Y, B, im.has_alpha ? LoadAlpha(im, (size_t)y * im.w + x) : 0u);
+  const uint32_t a = im.has_alpha ? LoadAlpha(im, (size_t)y * im.w + x) : 0u;
+  if (im.has_noise) { WritePixelGeneral(im, x, y, X, Y, B, a); return; }   // (out of line: the stage kernels keep their registers)
+  WritePixelA(im, x, y, X, Y, B, a);
 }
 
 }  // namespace
@@ -708,25 +763,6 @@ __device__ __forceinline__ Row3 LoadRow3(const JXL_GLOBAL float* p0, const JXL_G
   }
   return r;
 }
-// XYB -> sRGB-encoded u8 (the plain output layouts)
-__device__ __forceinline__ uint32_t PixelToRgba8(const DevImage& im, float X, float Y, float B, uint32_t a) {
-  const float gr = Y + X - im.opsin_bias_cbrt[0], gg = Y - X - im.opsin_bias_cbrt[1], gb = B - im.opsin_bias_cbrt[2];
-  const float mr = gr * gr * gr + im.opsin_bias[0], mg = gg * gg * gg + im.opsin_bias[1], mb = gb * gb * gb + im.opsin_bias[2];
-  float r = im.opsin_inv[0] * mr + im.opsin_inv[1] * mg + im.opsin_inv[2] * mb;
-  float g = im.opsin_inv[3] * mr + im.opsin_inv[4] * mg + im.opsin_inv[5] * mb;
-  float bl = im.opsin_inv[6] * mr + im.opsin_inv[7] * mg + im.opsin_inv[8] * mb;
-  // to 8 bits with v_cvt_pk_u8_f32: converts (round to nearest, ties to even - tools/cvt_probe.hip), saturates to 0 .. 255, maps NaN to
-  // 0 and inserts the byte, in ONE instruction per channel instead of scale / max / min / add / convert / shift / or; the * 255 is
-  // folded into the transfer curve's constants.  (Differs from round-half-up only on exact ties.)
-  if (im.to_srgb) { r = SrgbOetf255T(r); g = SrgbOetf255T(g); bl = SrgbOetf255T(bl); }
-  else { r *= 255.0f; g *= 255.0f; bl *= 255.0f; }
-  uint32_t px = a << 24;
-  px = __builtin_amdgcn_cvt_pk_u8_f32(r, 0, px);
-  px = __builtin_amdgcn_cvt_pk_u8_f32(g, 1, px);
-  px = __builtin_amdgcn_cvt_pk_u8_f32(bl, 2, px);
-  return px;
-}
-
 // Rolling windows of one lane, as four slots each, indexed by (row & 3) with COMPILE-TIME phases (the row loop is unrolled by four):
 // no register moves to shift a window.  in / s: input rows and their horizontal neighbour sums; g: Gaborish rows; dv / dh: vertical /
 // horizontal channel-weighted differences of Gaborish rows; hd: dv[x-1] + dv[x+1].
