@@ -187,9 +187,25 @@ JXLFILETYPEIO_API int32_t jxlhip_stage_totals(JxlHipDecoder* dec, const char** n
                                               int32_t reset);
 
 /* Device time of the stages of the calling thread's last LoadImage / lossy SaveImage (HIP events on the streams the kernels were
- * launched on; measurement only: bench.py's single-image and encode workloads read them next to the wall time of the call). */
+ * launched on; measurement only: bench.py's single-image and encode workloads read them next to the wall time of the call).  A save
+ * at effort 8 or 9 adds one stage per evaluation of its closed loop ("evaluation k (...)": everything from the quant field to the
+ * cell distances, host work included). */
 JXLFILETYPEIO_API int32_t jxlhip_last_load_stage_times(const char** names, float* ms, int32_t capacity);
 JXLFILETYPEIO_API int32_t jxlhip_last_save_stage_times(const char** names, float* ms, int32_t capacity);
+
+/* Distance map ("Distance map: rules of this project"; this project's own measure in XYB, not Butteraugli) of
+ * picture b against the original a.  Both are BGRA8 in host memory (`stride` bytes per row, alpha ignored) and go through the
+ * encoder's sRGB -> XYB conversion.  Writes ceil(w / 8) * ceil(h / 8) cell distances (rows of 8 x 8 cells, top to bottom);
+ * `capacity` counts floats and must hold them all. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_distance_map(const uint8_t* a_bgra, uint32_t stride_a, const uint8_t* b_bgra, uint32_t stride_b,
+                                                    uint32_t width, uint32_t height, float* cell_dist, size_t capacity, ErrorInfo* err);
+
+/* What the closed quantisation loop of the calling thread's last SaveImage measured (efforts 8 and 9 of a lossy save): the cell
+ * distances of the evaluation whose quant field was written (up to `capacity` floats are copied), the number of evaluations (0 after
+ * a lossless save or an effort below 8: then the other figures are 0 and 0 is returned), the target tau, and the number of cells over tau
+ * at the first evaluation (the field effort 7 writes) and at the one written.  Returns the number of cells.  Any pointer may be NULL. */
+JXLFILETYPEIO_API size_t jxlhip_last_save_distances(float* dst, size_t capacity, int32_t* evaluations, float* target,
+                                                    int32_t* cells_over_target_first, int32_t* cells_over_target_emitted);
 
 /* Host-only (no GPU): the embedded ICC profile as LoadImage would hand it to setIccProfile (reference Decoder/JxlDecoder.cpp:652-682);
  * returns its size (0: none) and copies up to `capacity` bytes. */

@@ -67,7 +67,7 @@ class ImageInfo(C.Structure):
 
 EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jxlhip_decoder_create", "jxlhip_decoder_destroy", "jxlhip_peek",
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
-           "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times"]
+           "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances"]
 
 _lib = None
 
@@ -141,6 +141,12 @@ def lib(build_if_missing=True):
     L.jxlhip_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]
     L.jxlhip_stage_totals.restype = C.c_int32
     L.jxlhip_stage_totals.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    L.jxlhip_distance_map.restype = C.c_int32
+    L.jxlhip_distance_map.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                      C.POINTER(ErrorInfo)]
+    L.jxlhip_last_save_distances.restype = C.c_size_t
+    L.jxlhip_last_save_distances.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]
     L.jxlhip_parse_check.restype = C.c_int32
     L.jxlhip_parse_check.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_static_table.restype = C.c_size_t
@@ -343,6 +349,45 @@ def last_load_stage_times():
 def last_save_stage_times():
     """Device time per kernel group of this thread's last lossy save_image() call (HIP events)."""
     return _last_stage_times("jxlhip_last_save_stage_times")
+
+
+def _bgra_surface(bgra):
+    bgra = np.asarray(bgra, dtype=np.uint8)
+    if bgra.ndim != 3 or bgra.shape[2] != 4:
+        raise ValueError("a (h, w, 4) BGRA surface is expected")
+    if bgra.strides[2] != 1 or (bgra.shape[1] > 1 and bgra.strides[1] != 4):
+        bgra = np.ascontiguousarray(bgra)
+    h, w, _ = bgra.shape
+    return bgra, w, h, bgra.strides[0] if h > 1 else w * 4
+
+
+def distance_map(a, b):
+    """Cell distances (float32, ceil(h / 8) x ceil(w / 8)) of the BGRA surface b against the original a, by this project's distance
+    map (not Butteraugli).  Alpha is ignored."""
+    L = lib()
+    a, w, h, stride_a = _bgra_surface(a)
+    b, wb, hb, stride_b = _bgra_surface(b)
+    if (w, h) != (wb, hb):
+        raise ValueError("the two pictures differ in size")
+    out = np.empty(((h + 7) // 8, (w + 7) // 8), np.float32)
+    err = ErrorInfo()
+    st = L.jxlhip_distance_map(a.ctypes.data, stride_a, b.ctypes.data, stride_b, w, h, out.ctypes.data, out.size, C.byref(err))
+    if st != 0:
+        raise JxlError(ENCODER_STATUS[st] if 0 <= st < len(ENCODER_STATUS) else str(st), err.errorMessage.decode("ascii", "replace"))
+    return out
+
+
+def last_save_distances():
+    """The closed loop's figures of this thread's last save_image(): dict with `cells` (float32, flat, of the evaluation whose quant
+    field was written), `evaluations` (0: the loop did not run), `target`, `cells_over_target_first`, `cells_over_target_emitted`."""
+    L = lib()
+    ev, first, emitted, target = C.c_int32(), C.c_int32(), C.c_int32(), C.c_float()
+    n = L.jxlhip_last_save_distances(None, 0, C.byref(ev), C.byref(target), C.byref(first), C.byref(emitted))
+    cells = np.empty(n, np.float32)
+    if n:
+        L.jxlhip_last_save_distances(cells.ctypes.data, n, None, None, None, None)
+    return {"cells": cells, "evaluations": ev.value, "target": target.value, "cells_over_target_first": first.value,
+            "cells_over_target_emitted": emitted.value}
 
 
 class Decoder:

@@ -91,4 +91,17 @@ struct EncImage {
   uint64_t sec_cap;
 };
 
+// Distance map of a reconstruction against its original, both as XYB planes (distance_kernels.hip; the rules and the constants:
+// DESIGN.md §2, "Distance map: rules of this project")
+struct DistMap {
+  int32_t w, h, w8, h8;
+  const float* orig[3];     // w*h, tight rows
+  const float* recon[3];    // rows `recon_stride` floats apart
+  int32_t recon_stride, pad0;
+  float* mask;              // w*h: M of the original
+  float* cell;              // w8*h8: T per 8x8 cell
+  float a0, k;              // masking constant, calibration
+  float s2[3];              // squared channel weights
+};
+
 }  // namespace jxlhip

@@ -953,6 +953,15 @@ void LaunchEncFrontEnd(const EncImage& im, hipStream_t s) {
   hipLaunchKernelGGL(enc_strategy_kernel, dim3(GridFor(regions)), dim3(256), 0, s, im);
   hipLaunchKernelGGL(enc_varblock_kernel, dim3(regions), dim3(256), 0, s, im);
 }
+// the pieces of the front end the distance map and the closed loop of efforts 8 and 9 launch on their own: BGRA -> XYB planes; DCTs
+// and quantisation again after the quant field has changed (the kernel rewrites every value it wrote)
+void LaunchEncXyb(const EncImage& im, hipStream_t s) {
+  hipLaunchKernelGGL(enc_xyb_kernel, dim3(GridFor((size_t)im.w * im.h)), dim3(256), 0, s, im);
+}
+void LaunchEncVarblocks(const EncImage& im, hipStream_t s) {
+  const unsigned regions = (unsigned)(((im.w8 + 7) / 8) * ((im.h8 + 7) / 8));
+  hipLaunchKernelGGL(enc_varblock_kernel, dim3(regions), dim3(256), 0, s, im);
+}
 void LaunchEncTokens(const EncImage& im, hipStream_t s) {
   hipLaunchKernelGGL(enc_lf_tokens_kernel, dim3(64, im.nlf), dim3(256), 0, s, im);
   hipLaunchKernelGGL(enc_meta_tokens_kernel, dim3(im.nlf), dim3(1024), 0, s, im);

@@ -31,6 +31,12 @@ void LaunchEncReverse(const EncImage& im, int which, hipStream_t s);
 void LaunchEncSections(const EncImage& im, hipStream_t s);
 void LaunchEncCompact(const EncImage& im, const uint64_t* dst_off, uint8_t* dst, int nsec, hipStream_t s);
 void LaunchEncLossless(const EncImage& im, int stage, hipStream_t s);
+void LaunchEncXyb(const EncImage& im, hipStream_t s);
+void LaunchEncVarblocks(const EncImage& im, hipStream_t s);
+// distance_kernels.hip
+void LaunchDistMask(const DistMap& dm, hipStream_t s);
+void LaunchDistCells(const DistMap& dm, hipStream_t s);
+void LaunchDistCorrect(const EncImage& im, const float* cell, const int32_t* q0, float tau, float p_up, float p_down, bool allow_down, hipStream_t s);
 
 namespace {
 
@@ -113,6 +119,28 @@ struct StageMarks {
   }
 };
 thread_local std::vector<std::pair<const char*, float>> g_last_save_stages;
+
+// What the closed loop of this thread's last SaveImage measured (jxlhip_last_save_distances); evaluations == 0: it did not run
+struct LastDistances {
+  std::vector<float> cells;   // of the evaluation whose field was written
+  int32_t evaluations = 0, over_first = 0, over_emitted = 0;
+  float target = 0.f;
+};
+thread_local LastDistances g_last_dist;
+
+// The constants of the distance map and of the loop (DESIGN.md §2 states them and why)
+constexpr float kDistA0 = 0.02f, kDistK = 1.0f;
+constexpr float kDistS[3] = {8.0f, 1.0f, 0.5f};
+constexpr float kLoopPUp = 0.7f, kLoopPDown = 0.2f;
+
+DistMap MakeDistMap(int32_t w, int32_t h) {
+  DistMap dm;
+  memset(&dm, 0, sizeof(dm));
+  dm.w = w; dm.h = h; dm.w8 = (w + 7) / 8; dm.h8 = (h + 7) / 8;
+  dm.a0 = kDistA0; dm.k = kDistK;
+  for (int c = 0; c < 3; c++) dm.s2[c] = kDistS[c] * kDistS[c];
+  return dm;
+}
 
 void Progress(ProgressProc progress, int percent) {
   if (progress && !progress(percent)) throw EncFail(EncoderStatus_UserCanceled, "");   // Encoder/JxlEncoder.cpp:79-89
@@ -294,6 +322,43 @@ void EncodeLossless(const BitmapData* bmp, const EncoderImageMetadata* md, IOCal
   EmitFile(codestream, md, io, progress);
 }
 
+// What this project's decoder shows of an interim stream of the closed loop, as XYB planes after every loop filter: the stream goes
+// through a JxlHipDecoder that keeps its stage copies ("debug_taps"), and the filtered planes (wp x hp, as the decoder lays them out)
+// are copied into the encoder's device planes.  Biases, LF smoothing and the EPF sigma of the quant field are the decoder's own.
+struct ReconDecoder {
+  JxlHipDecoder* dec = nullptr;
+  uint8_t* d_out = nullptr;
+  std::vector<float> host;
+  ReconDecoder(Arena& A, size_t out_bytes) {
+    ErrorInfo err;
+    memset(&err, 0, sizeof(err));
+    dec = jxlhip_decoder_create(-1, &err);
+    if (!dec) throw EncFail(EncoderStatus_EncodeError, std::string("closed loop: the decoder could not be created: ") + err.errorMessage);
+    (void)jxlhip_set_option(dec, "debug_taps", 1);
+    d_out = A.Get<uint8_t>(out_bytes);
+  }
+  ~ReconDecoder() { jxlhip_decoder_destroy(dec); }
+  ReconDecoder(const ReconDecoder&) = delete;
+  ReconDecoder& operator=(const ReconDecoder&) = delete;
+  void Reconstruct(const std::vector<uint8_t>& cs, float* const* planes, size_t npad) {
+    const uint8_t* data = cs.data();
+    const uint8_t* dev_data = nullptr;
+    const size_t size = cs.size();
+    uint8_t* out = d_out;
+    DecoderStatus st = DecoderStatus_Ok;
+    ErrorInfo err;
+    memset(&err, 0, sizeof(err));
+    if (jxlhip_decode_batch(dec, 1, &data, &size, &dev_data, &out, nullptr, 1, &st, &err) != DecoderStatus_Ok)
+      throw EncFail(EncoderStatus_EncodeError, std::string("closed loop: an interim stream did not decode: ") + err.errorMessage);
+    host.resize(npad);
+    for (int c = 0; c < 3; c++) {
+      if (jxlhip_read_plane(dec, 0, "xyb_filtered", c, host.data(), npad * 4) != npad * 4)
+        throw EncFail(EncoderStatus_EncodeError, "closed loop: the decoder's filtered planes have another size than the encoder's");
+      ENC_HIP(hipMemcpy(planes[c], host.data(), npad * 4, hipMemcpyHostToDevice));
+    }
+  }
+};
+
 void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
   Arena A;
   hipStream_t s = nullptr;
@@ -343,7 +408,7 @@ void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const Encoder
   }
   // effort (JxlEncoderTypes.h:29, passed to the encoder library as its effort setting, Encoder/JxlEncoder.cpp:319-326): the library's
   // fast settings (1..4) keep every block an 8x8 DCT; 5 and 6 add 16x16 / 32x32 DCTs on flat regions; from 7 (the host's default) the
-  // 64x64 and the rectangular 16x8 ... 64x32 shapes join
+  // 64x64 and the rectangular 16x8 ... 64x32 shapes join; 8 and 9 keep that set and correct the quant field in a closed loop (below)
   im.squares = opt->effort >= 7 ? 2 : (opt->effort >= 5 ? 1 : 0);
   const StaticTables& st = GetStaticTables();
   {
@@ -399,124 +464,203 @@ void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const Encoder
   { const size_t k = marks.Begin("front_end (xyb, sharpen, activity, strategy, DCT + quantise)", s); LaunchEncFrontEnd(im, s); marks.End(k, s); }
   clk.Lap("xyb + sharpen + dct/quant");
   Progress(progress, 20);
-  // ---- 4. tokens + histograms
+  // ---- 4. .. 7. are CodeField below: everything that follows from the quantised data.  Efforts up to 7 run it once; the closed loop
+  // of efforts 8 and 9 runs it once per evaluation.  Its buffers are allocated here, its counters cleared at every run.
   im.tok_lf = A.Get<DevToken>((size_t)im.nlf * kLfTokCap);
   im.tok_meta = A.Get<DevToken>((size_t)im.nlf * kMetaTokCap);
   im.tok_ac = A.Get<DevToken>((size_t)im.ng * kAcTokCap);
   if (im.has_alpha) im.tok_alpha = A.Get<DevToken>((size_t)im.ng * kAlphaTokCap);
-  im.n_ac = A.Get<uint32_t>(im.ng, true);
-  im.n_meta = A.Get<uint32_t>(im.nlf, true);
-  im.hist_mod = A.Get<uint32_t>(kNumEncLeaves * kEncSyms, true);
-  im.hist_ac = A.Get<uint32_t>((size_t)kAcContexts * kEncSyms, true);
-  { const size_t k = marks.Begin("tokens + histograms", s); LaunchEncTokens(im, s); marks.End(k, s); }
-  std::vector<uint32_t> hist_mod(kNumEncLeaves * kEncSyms), hist_ac((size_t)kAcContexts * kEncSyms);
-  ENC_HIP(hipMemcpy(hist_mod.data(), im.hist_mod, hist_mod.size() * 4, hipMemcpyDeviceToHost));
-  ENC_HIP(hipMemcpy(hist_ac.data(), im.hist_ac, hist_ac.size() * 4, hipMemcpyDeviceToHost));
-  clk.Lap("tokens + histograms");
-  Progress(progress, 25);
-  // ---- 5. LfGlobal and HfGlobal (host): quantiser, MA tree, entropy codes
-  const bool single = im.ng == 1;
-  BitWriter lf_global, hf_global;
-  EncCode mcode, acode;
-  lf_global.Bool(true);   // default LF dequantisation factors
-  lf_global.U32(WB(11, 1), WB(11, 2049), WB(12, 4097), WB(16, 8193), global_scale);
-  lf_global.U32(WV(16), WB(5, 1), WB(8, 1), WB(16, 1), quant_lf);
-  lf_global.Bool(true);   // default block-context map
-  lf_global.Bool(true);   // default LF chroma-from-luma parameters
-  lf_global.Bool(true);   // global MA tree
-  WriteTree(MakeEncoderTree((uint32_t)im.nlf), lf_global);
-  {
-    std::vector<uint8_t> pinned(kNumEncLeaves, 0);
-    pinned[kLeafSharp] = pinned[kLeafCfl] = 1;   // constant channels: no token is ever written
-    pinned[kLeafStrategy] = im.squares ? 0 : 1;  // ... and so is the strategy row while every block is an 8x8 DCT
-    BuildAndWriteCode(hist_mod.data(), kNumEncLeaves, 8, pinned, lf_global, mcode);
-  }
-  clk.Lap("host: tree + modular code");
-  // The Modular code is ready: start the recurrences of its streams (the LF coefficients of an LF group are the longest of the frame)
-  // on a stream of their own, and build the HF code meanwhile.
+  im.n_ac = A.Get<uint32_t>(im.ng);
+  im.n_meta = A.Get<uint32_t>(im.nlf);
+  im.hist_mod = A.Get<uint32_t>(kNumEncLeaves * kEncSyms);
+  im.hist_ac = A.Get<uint32_t>((size_t)kAcContexts * kEncSyms);
+  const int nsec = im.nlf + im.ng + 1;   // + the global alpha stream of single-group frames
+  im.sec_cap = ((size_t)std::max(kLfTokCap + kMetaTokCap, kAcTokCap + kAlphaTokCap) * 6 + 256) & ~(size_t)15;
+  im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
+  im.sec_bits = A.Get<uint64_t>(nsec);
+  im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1);
+  // The Modular streams' recurrences run on a stream of their own (the LF coefficients of an LF group are the longest of the frame),
+  // the HF streams' beside them.
   hipStream_t s_ans = nullptr, s_hf = nullptr;
   ENC_HIP(hipStreamCreateWithFlags(&s_ans, hipStreamNonBlocking));
   struct StreamGuard { hipStream_t s; ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } s_ans_guard{s_ans};
-  ENC_HIP(hipStreamCreateWithFlags(&s_hf, hipStreamNonBlocking));   // the HF streams' recurrences run beside the Modular ones
+  ENC_HIP(hipStreamCreateWithFlags(&s_hf, hipStreamNonBlocking));
   StreamGuard s_hf_guard{s_hf};
-  const int nsec = im.nlf + im.ng + 1;   // + the global alpha stream of single-group frames
-  im.mcode = UploadCode(A, mcode);
-  im.sec_cap = ((size_t)std::max(kLfTokCap + kMetaTokCap, kAcTokCap + kAlphaTokCap) * 6 + 256) & ~(size_t)15;
-  im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
-  im.sec_bits = A.Get<uint64_t>(nsec, true);
-  im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1, true);
-  ENC_HIP(hipDeviceSynchronize());   // tokens, histogram downloads and the clears above are done before the other stream starts
-  { const size_t k = marks.Begin("ans recurrences, Modular streams (LF, metadata, alpha)", s_ans); LaunchEncReverse(im, 0, s_ans); marks.End(k, s_ans); }
-  if (im.has_alpha) lf_global.Write(4, 3);   // global Modular image header: global tree, default predictor, no transforms
-  hf_global.Bool(true);                      // default dequantisation matrices
-  hf_global.Write(im.ng <= 1 ? 0 : 32 - __builtin_clz((unsigned)(im.ng - 1)), 0);   // one HF preset
-  hf_global.U32(WV(0x5F), WV(0x13), WV(0), WB(kNumOrders), 0);                       // natural coefficient orders
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    BuildAndWriteCode(hist_ac.data(), kAcContexts, 64, {}, hf_global, acode);
-    if (clk.on) fprintf(stderr, "[enc] %-28s %8.2f ms (host only)\n", "HF code construction", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  }
-  clk.Lap("host: HF code (overlaps the LF recurrences)");
-  // ---- 6. ANS coding of every section on the GPU (the Modular streams' recurrences have been running since their code was built)
-  im.acode = UploadCode(A, acode);
-  { const size_t k = marks.Begin("ans recurrences, HF streams", s_hf); LaunchEncReverse(im, 1, s_hf); marks.End(k, s_hf); }
-  {
-    hipEvent_t hf_done;
-    ENC_HIP(hipEventCreateWithFlags(&hf_done, hipEventDisableTiming));
-    ENC_HIP(hipEventRecord(hf_done, s_hf));
-    ENC_HIP(hipStreamWaitEvent(s_ans, hf_done, 0));
-    const size_t k = marks.Begin("section bit layout", s_ans);
-    LaunchEncSections(im, s_ans);   // bit layout of every section: needs the states of both kinds of stream
-    marks.End(k, s_ans);
-    ENC_HIP(hipStreamSynchronize(s_ans));
-    (void)hipEventDestroy(hf_done);
-  }
-  clk.Lap("ans sections");
-  std::vector<uint64_t> sec_bits(nsec);
-  ENC_HIP(hipMemcpy(sec_bits.data(), im.sec_bits, sec_bits.size() * 8, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> off(nsec + 1, 0);
-  for (int i = 0; i < nsec; i++) off[i + 1] = off[i] + ((sec_bits[i] + 7) >> 3);
-  std::vector<uint8_t> packed(std::max<uint64_t>(off[nsec], 1));
-  {
-    uint64_t* d_off = A.Upload(off);
-    uint8_t* d_packed = A.Get<uint8_t>(packed.size());
-    const size_t k = marks.Begin("compact", s);
-    LaunchEncCompact(im, d_off, d_packed, nsec, s);
-    marks.End(k, s);
-    ENC_HIP(hipMemcpy(packed.data(), d_packed, packed.size(), hipMemcpyDeviceToHost));
-  }
-  ENC_HIP(hipGetLastError());
-  marks.Publish(&g_last_save_stages);
-  clk.Lap("compact + download");
-  Progress(progress, 30);
-  // ---- 7. codestream assembly
+  const bool single = im.ng == 1;
   EncImageInfo ii;
   ii.xsize = w; ii.ysize = h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = true;
   ii.icc = md->iccProfile; ii.icc_size = md->iccProfile ? md->iccProfileSize : 0;
-  BitWriter cs;
-  WriteCodestreamHeaders(ii, cs);
-  WriteFrameHeader(ii, fi, cs);
-  std::vector<std::vector<uint8_t>> sections;
-  if (single) {
-    // LfGlobal | LfGroup | HfGlobal | PassGroup share one bit stream
-    if (im.has_alpha) lf_global.AppendBits(packed.data() + off[im.nlf + im.ng], sec_bits[im.nlf + im.ng]);
-    const uint64_t hg_bits = hf_global.BitCount();
-    std::vector<uint8_t> hg = hf_global.Finish();
-    lf_global.AppendBits(packed.data() + off[0], sec_bits[0]);
-    lf_global.AppendBits(hg.data(), hg_bits);
-    lf_global.AppendBits(packed.data() + off[1], sec_bits[1]);
-    sections.push_back(lf_global.Finish());
+  // The codestream of the quantised data in `im`.  `final`: the call whose stream is (normally) written: it reports progress 25 and
+  // 30; `mk`: where its kernel groups are timed (null: nowhere).
+  auto CodeField = [&](bool final, StageMarks* mk, bool publish) -> std::vector<uint8_t> {
+    Arena E;   // the codes of this run
+    auto begin = [&](const char* name, hipStream_t st) { return mk ? mk->Begin(name, st) : (size_t)-1; };
+    auto end = [&](size_t k, hipStream_t st) { if (mk) mk->End(k, st); };
+    ENC_HIP(hipMemset(im.n_ac, 0, std::max<size_t>((size_t)im.ng * 4, 256)));
+    ENC_HIP(hipMemset(im.n_meta, 0, std::max<size_t>((size_t)im.nlf * 4, 256)));
+    ENC_HIP(hipMemset(im.hist_mod, 0, kNumEncLeaves * kEncSyms * 4));
+    ENC_HIP(hipMemset(im.hist_ac, 0, (size_t)kAcContexts * kEncSyms * 4));
+    ENC_HIP(hipMemset(im.sec_bits, 0, std::max<size_t>((size_t)nsec * 8, 256)));
+    ENC_HIP(hipMemset(im.stream_state, 0, std::max<size_t>(((size_t)2 * (im.nlf + im.ng) + 1) * 4, 256)));
+    // ---- 4. tokens + histograms
+    { const size_t k = begin("tokens + histograms", s); LaunchEncTokens(im, s); end(k, s); }
+    std::vector<uint32_t> hist_mod(kNumEncLeaves * kEncSyms), hist_ac((size_t)kAcContexts * kEncSyms);
+    ENC_HIP(hipMemcpy(hist_mod.data(), im.hist_mod, hist_mod.size() * 4, hipMemcpyDeviceToHost));
+    ENC_HIP(hipMemcpy(hist_ac.data(), im.hist_ac, hist_ac.size() * 4, hipMemcpyDeviceToHost));
+    clk.Lap("tokens + histograms");
+    if (final) Progress(progress, 25);
+    // ---- 5. LfGlobal and HfGlobal (host): quantiser, MA tree, entropy codes
+    BitWriter lf_global, hf_global;
+    EncCode mcode, acode;
+    lf_global.Bool(true);   // default LF dequantisation factors
+    lf_global.U32(WB(11, 1), WB(11, 2049), WB(12, 4097), WB(16, 8193), global_scale);
+    lf_global.U32(WV(16), WB(5, 1), WB(8, 1), WB(16, 1), quant_lf);
+    lf_global.Bool(true);   // default block-context map
+    lf_global.Bool(true);   // default LF chroma-from-luma parameters
+    lf_global.Bool(true);   // global MA tree
+    WriteTree(MakeEncoderTree((uint32_t)im.nlf), lf_global);
+    {
+      std::vector<uint8_t> pinned(kNumEncLeaves, 0);
+      pinned[kLeafSharp] = pinned[kLeafCfl] = 1;   // constant channels: no token is ever written
+      pinned[kLeafStrategy] = im.squares ? 0 : 1;  // ... and so is the strategy row while every block is an 8x8 DCT
+      BuildAndWriteCode(hist_mod.data(), kNumEncLeaves, 8, pinned, lf_global, mcode);
+    }
+    clk.Lap("host: tree + modular code");
+    // The Modular code is ready: start the recurrences of its streams on their stream, and build the HF code meanwhile.
+    im.mcode = UploadCode(E, mcode);
+    ENC_HIP(hipDeviceSynchronize());   // tokens, histogram downloads and the clears above are done before the other stream starts
+    { const size_t k = begin("ans recurrences, Modular streams (LF, metadata, alpha)", s_ans); LaunchEncReverse(im, 0, s_ans); end(k, s_ans); }
+    if (im.has_alpha) lf_global.Write(4, 3);   // global Modular image header: global tree, default predictor, no transforms
+    hf_global.Bool(true);                      // default dequantisation matrices
+    hf_global.Write(im.ng <= 1 ? 0 : 32 - __builtin_clz((unsigned)(im.ng - 1)), 0);   // one HF preset
+    hf_global.U32(WV(0x5F), WV(0x13), WV(0), WB(kNumOrders), 0);                       // natural coefficient orders
+    {
+      const auto t0 = std::chrono::steady_clock::now();
+      BuildAndWriteCode(hist_ac.data(), kAcContexts, 64, {}, hf_global, acode);
+      if (clk.on) fprintf(stderr, "[enc] %-28s %8.2f ms (host only)\n", "HF code construction", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    clk.Lap("host: HF code (overlaps the LF recurrences)");
+    // ---- 6. ANS coding of every section on the GPU (the Modular streams' recurrences have been running since their code was built)
+    im.acode = UploadCode(E, acode);
+    { const size_t k = begin("ans recurrences, HF streams", s_hf); LaunchEncReverse(im, 1, s_hf); end(k, s_hf); }
+    {
+      hipEvent_t hf_done;
+      ENC_HIP(hipEventCreateWithFlags(&hf_done, hipEventDisableTiming));
+      ENC_HIP(hipEventRecord(hf_done, s_hf));
+      ENC_HIP(hipStreamWaitEvent(s_ans, hf_done, 0));
+      const size_t k = begin("section bit layout", s_ans);
+      LaunchEncSections(im, s_ans);   // bit layout of every section: needs the states of both kinds of stream
+      end(k, s_ans);
+      ENC_HIP(hipStreamSynchronize(s_ans));
+      (void)hipEventDestroy(hf_done);
+    }
+    clk.Lap("ans sections");
+    std::vector<uint64_t> sec_bits(nsec);
+    ENC_HIP(hipMemcpy(sec_bits.data(), im.sec_bits, sec_bits.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> off(nsec + 1, 0);
+    for (int i = 0; i < nsec; i++) off[i + 1] = off[i] + ((sec_bits[i] + 7) >> 3);
+    std::vector<uint8_t> packed(std::max<uint64_t>(off[nsec], 1));
+    {
+      uint64_t* d_off = E.Upload(off);
+      uint8_t* d_packed = E.Get<uint8_t>(packed.size());
+      const size_t k = begin("compact", s);
+      LaunchEncCompact(im, d_off, d_packed, nsec, s);
+      end(k, s);
+      ENC_HIP(hipMemcpy(packed.data(), d_packed, packed.size(), hipMemcpyDeviceToHost));
+    }
+    ENC_HIP(hipGetLastError());
+    if (mk && publish) mk->Publish(&g_last_save_stages);
+    clk.Lap("compact + download");
+    if (final) Progress(progress, 30);
+    // ---- 7. codestream assembly
+    BitWriter cs;
+    WriteCodestreamHeaders(ii, cs);
+    WriteFrameHeader(ii, fi, cs);
+    std::vector<std::vector<uint8_t>> sections;
+    if (single) {
+      // LfGlobal | LfGroup | HfGlobal | PassGroup share one bit stream
+      if (im.has_alpha) lf_global.AppendBits(packed.data() + off[im.nlf + im.ng], sec_bits[im.nlf + im.ng]);
+      const uint64_t hg_bits = hf_global.BitCount();
+      std::vector<uint8_t> hg = hf_global.Finish();
+      lf_global.AppendBits(packed.data() + off[0], sec_bits[0]);
+      lf_global.AppendBits(hg.data(), hg_bits);
+      lf_global.AppendBits(packed.data() + off[1], sec_bits[1]);
+      sections.push_back(lf_global.Finish());
+    } else {
+      sections.push_back(lf_global.Finish());
+      for (int g = 0; g < im.nlf; g++) sections.emplace_back(packed.begin() + off[g], packed.begin() + off[g + 1]);
+      sections.push_back(hf_global.Finish());
+      for (int g = 0; g < im.ng; g++) sections.emplace_back(packed.begin() + off[im.nlf + g], packed.begin() + off[im.nlf + g + 1]);
+    }
+    std::vector<uint32_t> sizes;
+    for (auto& sec : sections) sizes.push_back((uint32_t)sec.size());
+    WriteToc(sizes, cs);
+    std::vector<uint8_t> out = cs.Finish();
+    for (auto& sec : sections) out.insert(out.end(), sec.begin(), sec.end());
+    return out;
+  };
+  std::vector<uint8_t> codestream;
+  const int corrections = opt->effort >= 9 ? 4 : (opt->effort >= 8 ? 2 : 0);
+  if (!corrections) {
+    codestream = CodeField(true, &marks, true);
   } else {
-    sections.push_back(lf_global.Finish());
-    for (int g = 0; g < im.nlf; g++) sections.emplace_back(packed.begin() + off[g], packed.begin() + off[g + 1]);
-    sections.push_back(hf_global.Finish());
-    for (int g = 0; g < im.ng; g++) sections.emplace_back(packed.begin() + off[im.nlf + g], packed.begin() + off[im.nlf + g + 1]);
+    // ---- closed loop ("Distance map" and "The loop of efforts 8 and 9"): code the field, reconstruct what a decoder
+    // shows, measure, correct the field, again.  The strategies stay; only the quant field moves, so every interim stream is valid.
+    static const char* const kEvalName[5] = {"evaluation 0 (code, decode, distance map)", "evaluation 1 (code, decode, distance map)",
+                                             "evaluation 2 (code, decode, distance map)", "evaluation 3 (code, decode, distance map)",
+                                             "evaluation 4 (code, decode, distance map)"};
+    int32_t* q0 = A.Get<int32_t>(ncell);
+    ENC_HIP(hipMemcpy(q0, im.rawq, ncell * 4, hipMemcpyDeviceToDevice));
+    DistMap dm = MakeDistMap(im.w, im.h);
+    float* recon[3];
+    for (int c = 0; c < 3; c++) { dm.orig[c] = im.xyb[c]; recon[c] = A.Get<float>(npad); dm.recon[c] = recon[c]; }
+    dm.recon_stride = im.wp;
+    dm.mask = A.Get<float>(npx);
+    dm.cell = A.Get<float>(ncell);
+    LaunchDistMask(dm, s);
+    ReconDecoder rd(A, (size_t)w * h * 4);
+    std::vector<float> cells(ncell), cells0, sorted;
+    float tau = 0.f;
+    int over_first = 0, over_last = 0;
+    const int nev = corrections + 1;
+    for (int e = 0; e < nev; e++) {
+      const size_t k = marks.Begin(kEvalName[e], s);
+      if (e) LaunchEncVarblocks(im, s);
+      codestream = CodeField(e == nev - 1, e == nev - 1 ? &marks : nullptr, false);
+      rd.Reconstruct(codestream, recon, npad);
+      LaunchDistCells(dm, s);
+      ENC_HIP(hipMemcpy(cells.data(), dm.cell, ncell * 4, hipMemcpyDeviceToHost));
+      marks.End(k, s);
+      if (e == 0) {
+        sorted = cells;
+        std::sort(sorted.begin(), sorted.end());
+        tau = sorted[(size_t)std::floor(0.9 * (double)(ncell - 1))];   // the 90th percentile, rank rounded down
+        cells0 = cells;
+      }
+      int over = 0;
+      for (float t : cells) over += t > tau;
+      if (e == 0) over_first = over;
+      over_last = over;
+      if (e < nev - 1) {
+        LaunchDistCorrect(im, dm.cell, q0, tau, kLoopPUp, kLoopPDown, e < nev - 2, s);
+        Progress(progress, 20);   // the loop's value until its last evaluation: a cancel lands within one evaluation
+      }
+    }
+    if (over_last > over_first) {   // never worse than effort 7 by this count: its field is written instead
+      ENC_HIP(hipMemcpy(im.rawq, q0, ncell * 4, hipMemcpyDeviceToDevice));
+      LaunchEncVarblocks(im, s);
+      codestream = CodeField(false, nullptr, false);
+      cells = cells0;
+      over_last = over_first;
+    }
+    ENC_HIP(hipGetLastError());
+    marks.Publish(&g_last_save_stages);
+    g_last_dist.cells = cells;
+    g_last_dist.evaluations = nev;
+    g_last_dist.target = tau;
+    g_last_dist.over_first = over_first;
+    g_last_dist.over_emitted = over_last;
   }
-  std::vector<uint32_t> sizes;
-  for (auto& sec : sections) sizes.push_back((uint32_t)sec.size());
-  WriteToc(sizes, cs);
-  std::vector<uint8_t> codestream = cs.Finish();
-  for (auto& sec : sections) codestream.insert(codestream.end(), sec.begin(), sec.end());
   clk.Lap("assembly");
   EmitFile(codestream, md, io, progress);
   clk.Lap("container + write callbacks");
@@ -539,10 +683,68 @@ extern "C" JXLFILETYPEIO_API int32_t jxlhip_last_save_stage_times(const char** n
   return k;
 }
 
+// The closed loop's figures of this thread's last SaveImage (evaluations == 0: an effort below 8 or a lossless save; no cells)
+extern "C" JXLFILETYPEIO_API size_t jxlhip_last_save_distances(float* dst, size_t capacity, int32_t* evaluations, float* target,
+                                                               int32_t* cells_over_target_first, int32_t* cells_over_target_emitted) {
+  const LastDistances& d = g_last_dist;
+  if (dst) memcpy(dst, d.cells.data(), std::min(capacity, d.cells.size()) * sizeof(float));
+  if (evaluations) *evaluations = d.evaluations;
+  if (target) *target = d.target;
+  if (cells_over_target_first) *cells_over_target_first = d.over_first;
+  if (cells_over_target_emitted) *cells_over_target_emitted = d.over_emitted;
+  return d.cells.size();
+}
+
+// The distance map of picture b against the original a (both BGRA8 in host memory, alpha ignored), through the encoder's
+// sRGB -> XYB conversion: ceil(w / 8) * ceil(h / 8) cell distances, rows of cells top to bottom.
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_distance_map(const uint8_t* a_bgra, uint32_t stride_a, const uint8_t* b_bgra, uint32_t stride_b,
+                                                               uint32_t w, uint32_t h, float* cell_dist, size_t capacity, ErrorInfo* err) {
+  if (!a_bgra || !b_bgra || !cell_dist) return EncoderStatus_NullParameter;
+  try {
+    if (!w || !h || w > (1u << 30) / h || stride_a < (uint64_t)w * 4 || stride_b < (uint64_t)w * 4)
+      throw EncFail(EncoderStatus_EncodeError, "invalid bitmap");
+    DistMap dm = MakeDistMap((int32_t)w, (int32_t)h);
+    const size_t npx = (size_t)w * h, ncell = (size_t)dm.w8 * dm.h8;
+    if (capacity < ncell) throw EncFail(EncoderStatus_EncodeError, "the buffer for the cell distances is too small");
+    Arena A;
+    float* planes[2][3];
+    for (int k = 0; k < 2; k++) {
+      const uint8_t* src = k ? b_bgra : a_bgra;
+      const uint32_t stride = k ? stride_b : stride_a;
+      EncImage im;
+      memset(&im, 0, sizeof(im));
+      im.w = (int32_t)w; im.h = (int32_t)h; im.stride = (int32_t)stride;
+      uint8_t* d_bgra = A.Get<uint8_t>((size_t)stride * h);
+      ENC_HIP(hipMemcpy(d_bgra, src, (size_t)stride * (h - 1) + (size_t)w * 4, hipMemcpyHostToDevice));   // the last row may end at its pixels
+      im.bgra = d_bgra;
+      for (int c = 0; c < 3; c++) planes[k][c] = im.xyb[c] = A.Get<float>(npx);
+      LaunchEncXyb(im, nullptr);
+    }
+    for (int c = 0; c < 3; c++) { dm.orig[c] = planes[0][c]; dm.recon[c] = planes[1][c]; }
+    dm.recon_stride = (int32_t)w;
+    dm.mask = A.Get<float>(npx);
+    dm.cell = A.Get<float>(ncell);
+    LaunchDistMask(dm, nullptr);
+    LaunchDistCells(dm, nullptr);
+    ENC_HIP(hipMemcpy(cell_dist, dm.cell, ncell * 4, hipMemcpyDeviceToHost));
+    ENC_HIP(hipGetLastError());
+    return EncoderStatus_Ok;
+  } catch (const EncFail& e) {
+    if (e.status == EncoderStatus_EncodeError) SetEncErr(err, e.what());
+    return e.status;
+  } catch (const std::exception& e) {
+    SetEncErr(err, e.what());
+    return EncoderStatus_EncodeError;
+  } catch (...) {
+    return EncoderStatus_EncodeError;
+  }
+}
+
 extern "C" JXLFILETYPEIO_API EncoderStatus SaveImage(const BitmapData* bitmap, const EncoderOptions* options, const EncoderImageMetadata* metadata,
                                    IOCallbacks* callbacks, ErrorInfo* err, ProgressProc progress) {
   if (!bitmap || !options || !callbacks || !metadata) return EncoderStatus_NullParameter;   // Encoder/JxlEncoder.cpp:155-158
   try {
+    g_last_dist = LastDistances();
     Progress(progress, 0);   // :162
     if (!callbacks->Write) throw EncFail(EncoderStatus_NullParameter, "");
     if (options->lossless) EncodeLossless(bitmap, metadata, callbacks, progress);   // :214,325
