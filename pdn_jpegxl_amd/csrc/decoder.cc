@@ -178,6 +178,7 @@ struct JxlHipDecoder {
   // band-restricted decode (multi-GPU sharding of one frame by group rows): 0 rows = whole frame
   int band_first_row = 0, band_rows = 0;
   bool no_stream_pairs = false;   // every fused frame through the four-pixels-per-lane filter kernel (parity tests: same output either way)
+  bool no_lf_pipeline = false;    // every LF channel through lf_finish_kernel's row-per-lane prediction pass (parity tests: same output either way)
   bool no_direct = false, mod_lanes64 = false;   // launch shapes of the vector loops for small launches too (parity tests: same output either way)
   bool overlap = true;
 
@@ -1428,7 +1429,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (!(skip_stages & 1)) {
   LaunchLfAns(d_imgs, (const SectionTask*)(d_blob + off_lf_ans_tasks), nlf_ans_t, lf_per_wave, lds_lf <= kLdsMax ? lds_lf : 0, direct_lf, lean_mod, s_lf);
   Mark("lf_ans", s_lf, 0);
-  LaunchLfFinish(d_imgs, (const SectionTask*)(d_blob + off_lf_tasks), nlf_t, s_lf);
+  LaunchLfFinish(d_imgs, (const SectionTask*)(d_blob + off_lf_tasks), nlf_t, !no_lf_pipeline, s_lf);
   LaunchHfBlockList(d_imgs, n, max_groups, s_lf);
   LaunchLfPixelStages(d_imgs, n, max_cells, s_lf);
   }
@@ -1813,6 +1814,7 @@ int32_t jxlhip_set_option(JxlHipDecoder* dec, const char* name, int32_t value) {
   if (!strcmp(name, "band_rows")) { if (value < 0) return 0; dec->band_rows = value; return 1; }
   if (!strcmp(name, "no_direct")) { dec->no_direct = value != 0; return 1; }
   if (!strcmp(name, "no_stream_pairs")) { dec->no_stream_pairs = value != 0; return 1; }
+  if (!strcmp(name, "no_lf_pipeline")) { dec->no_lf_pipeline = value != 0; return 1; }
   if (!strcmp(name, "mod_lanes64")) { dec->mod_lanes64 = value != 0; return 1; }
   if (!strcmp(name, "overlap")) { dec->overlap = value != 0; return 1; }
   return 0;

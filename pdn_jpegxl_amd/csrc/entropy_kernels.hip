@@ -1219,7 +1219,9 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
     const int chan_of[3] = {1, 0, 2};
     // (measured: an LDS tile per channel wavefront - 48 KB more per workgroup - doubles this kernel's time in a batch and does not
     // change the single-frame time; the untiled pass stays)
-    FinishChannelI32(desc[wave], tree, wave, 1 + g, im.lfq[chan_of[wave]] + (size_t)by0 * im.w8 + bx0, im.w8, bw, bh, carry, lane);
+    // (channels that lf_finish_gradient_kernel has finished - all of them in files as every encoder writes them - carry pad0 = 1)
+    if (desc[wave].pad0 != 1)
+      FinishChannelI32(desc[wave], tree, wave, 1 + g, im.lfq[chan_of[wave]] + (size_t)by0 * im.w8 + bx0, im.w8, bw, bh, carry, lane);
   } else {
     FinishChannelI32(desc[3], tree, 0, sid_meta, s_x, tw, tw, th, carry, lane);
     FinishChannelI32(desc[4], tree, 1, sid_meta, s_b, tw, tw, th, carry, lane);
@@ -2069,6 +2071,128 @@ __global__ __launch_bounds__(64, 3) void alpha_finish_kernel(const DevImage* __r
   }
 }
 
+// ---- LF channels whose rows all use the clamped gradient (what every encoder writes): the same register pipeline, int32 in place ----
+// One wavefront per LF group.  Three teams of sixteen lanes take the modular channels 0..2 (Y, X, B: lfq[1], lfq[0], lfq[2]), the fourth
+// team is idle.  The schedule is alpha_finish_gradient_kernel's: lane i of a team owns rows i, 16 + i, ...; a row is consumed in lines of
+// 16 columns, row r starts at step r, the North samples come from the lane below by DPP, the next line is requested one step ahead.  An
+// LF group is at most 256 cells = 16 lines wide, so a lane goes from one row straight to its next: rows + lines - 1 steps (271 for a
+// full group, where the row-per-lane walk of PredictWave takes 1276, each with 64 cache lines per load and per store).
+// Residuals and samples are the same memory.  A lane stores at step T the line it requested at step T - 1, and no lane reads a line
+// that another lane stores (a lane that is idle at a step still loads, row 0 / line 0 of its channel, and drops the value).
+// Any width: columns at or beyond the group's width are never stored, and their loads are clamped to a valid column of the same row.
+// kVec: every plane of the frame is 16-byte aligned and w8 % 4 == 0 (group origins are multiples of 256, widths then multiples of 4):
+// four 16-byte accesses per line; otherwise sixteen 4-byte ones inside the same schedule.
+// Channels this does not take (another predictor in some row, constant or final channels, a failed phase A) are left to
+// lf_finish_kernel, which skips the channels taken here (ChanDesc::pad0).
+template <bool kVec>
+__device__ __forceinline__ void LfGradientSteps(JXL_GLB int32_t* const plane, const int stride, const int bw, const int rows, const int nq,
+                                                const int steps, const int li) {
+  typedef int32_t __attribute__((ext_vector_type(4))) I4v;
+  auto line_of = [&](int T, int* r_out, int* q_out) {   // the (row, 16-column line) this lane works on at time T; false: idle
+    const int m = T - li;
+    const int r = (m >> 4) * 16 + li, q = m & 15;
+    *r_out = r; *q_out = q;
+    return m >= 0 && r < rows && q < nq;
+  };
+  auto load_line = [&](int T, I4v* v) {   // the lane's residual line of time T (row 0, line 0 when it is idle then)
+    int r, q;
+    const bool act = line_of(T, &r, &q);
+    const JXL_GLB int32_t* const row = plane + (size_t)(act ? r : 0) * stride;
+    const int x = act ? q * 16 : 0;
+    if constexpr (kVec) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = *(const JXL_GLB I4v*)(row + min(x + 4 * k, bw - 4));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; j++) v[j >> 2][j & 3] = row[min(x + j, bw - 1)];
+    }
+  };
+  I4v cur[4], nxt[4];
+  load_line(0, nxt);
+  int32_t prev_out[16];
+#pragma unroll
+  for (int j = 0; j < 16; j++) prev_out[j] = 0;
+  int32_t W = 0, n_last = 0;
+  for (int T = 0; T < steps; T++) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) cur[k] = nxt[k];
+    load_line(T + 1, nxt);   // in flight during this step
+    int r, q;
+    const bool act = line_of(T, &r, &q);
+    int32_t nq16[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) nq16[j] = RowRotateFromBelow(prev_out[j]);   // row r - 1, the same 16 columns
+    const bool top = r == 0;
+    int32_t o[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int32_t res = cur[j >> 2][j & 3];
+      int32_t n, nw;
+      if (top) { n = W; nw = W; }                       // top row: North = North-West = West
+      else { n = nq16[j]; nw = j == 0 ? n_last : nq16[j - 1]; }
+      if (j == 0 && q == 0) {                            // first column: West = North = North-West = the sample above (0 in the top row)
+        const int32_t w0 = top ? 0 : nq16[0];
+        W = w0; n = w0; nw = w0;
+      }
+      const int32_t val = (int32_t)((uint32_t)res + (uint32_t)ClampedGradient32(W, n, nw));
+      o[j] = val;
+      W = val;
+    }
+    n_last = nq16[15];
+    if (act) {
+#pragma unroll
+      for (int j = 0; j < 16; j++) prev_out[j] = o[j];
+      JXL_GLB int32_t* const dst = plane + (size_t)r * stride + q * 16;
+      const int left = bw - q * 16;   // valid columns of this line (the last line of a row may be partial)
+      if constexpr (kVec) {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (4 * k < left) *(JXL_GLB I4v*)(dst + 4 * k) = I4v{o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]};
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+          if (j < left) dst[j] = o[j];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void lf_finish_gradient_kernel(const DevImage* __restrict__ imgs, const SectionTask* tasks) {
+  const DevImage& im = imgs[tasks[blockIdx.x].image];
+  const int g = tasks[blockIdx.x].first;
+  if (!im.lf_count[g]) return;   // phase A failed (already reported): the descriptors mean nothing
+  const int lane = threadIdx.x, sub = lane >> 4, li = lane & 15;
+  const int gx = g % im.xlf, gy = g / im.xlf;
+  const int bx0 = gx * kLfGroupBlocks, by0 = gy * kLfGroupBlocks;
+  const int bw = min(kLfGroupBlocks, im.w8 - bx0), bh = min(kLfGroupBlocks, im.h8 - by0);
+  if (bw <= 0 || bh <= 0) return;
+  const int chan = min(sub, 2);   // (the idle team points at a valid plane: its lanes load like everyone's)
+  const int c = chan == 0 ? 1 : (chan == 1 ? 0 : 2);   // modular channel order Y, X, B
+  bool mine = sub < 3 && im.lf_desc[(size_t)g * 8 + chan].kind == kChanResid;
+  if (mine) {   // every row's leaf must be the gradient
+    const I4* tree = (const I4*)im.tree;
+    for (int r = li; r < bh; r += 16) {
+      bool used_y = false;
+      mine = mine && (RowNode(tree, chan, 1 + g, r, &used_y).a & 0xFF) == 5;
+      if (!used_y) break;   // every row resolves to this leaf
+    }
+  }
+  {  // all sixteen lanes of the team must agree (a team with fewer rows than lanes: the lanes without a row say yes)
+    const uint64_t bal = __ballot(mine);
+    mine = ((bal >> (sub * 16)) & 0xFFFFu) == 0xFFFFu;
+  }
+  if (__ballot(mine) == 0) return;
+  JXL_GLB int32_t* const plane = G(im.lfq[c]) + (size_t)by0 * im.w8 + bx0;
+  const int rows = mine ? bh : 0, nq = mine ? (bw + 15) >> 4 : 0;
+  // uniform loop bound: the longest of the wavefront's teams
+  int steps = mine ? rows + nq - 1 : 0;
+  steps = max(steps, __shfl_xor(steps, 16)); steps = max(steps, __shfl_xor(steps, 32));
+  if (mine && li == 0) im.lf_desc[(size_t)g * 8 + chan].pad0 = 1;   // tells lf_finish_kernel (the next launch) to leave the channel alone
+  const bool vec = (im.w8 & 3) == 0 && (((uintptr_t)im.lfq[0] | (uintptr_t)im.lfq[1] | (uintptr_t)im.lfq[2]) & 15) == 0;
+  if (vec) LfGradientSteps<true>(plane, im.w8, bw, rows, nq, steps, li);
+  else LfGradientSteps<false>(plane, im.w8, bw, rows, nq, steps, li);
+}
+
 // ------------------------------------------------------------------ Modular (lossless) frames
 // Sections of a Modular frame: 0 = GlobalModular stream (channels before mod_first_group), 1 + g = LF group g (channels
 // squeezed by >= 3 in both directions), 1 + nlf + g = pass group g (the rest).  A section codes, for each of its channels, the
@@ -2346,8 +2470,10 @@ void LaunchLfAns(const DevImage* imgs, const SectionTask* tasks, int ntasks, int
   }
 }
 
-void LaunchLfFinish(const DevImage* imgs, const SectionTask* tasks, int ntasks, hipStream_t s) {
+void LaunchLfFinish(const DevImage* imgs, const SectionTask* tasks, int ntasks, bool pipeline, hipStream_t s) {
   if (ntasks <= 0) return;
+  // the gradient channels' prediction pass first, one wavefront per LF group (pipeline = false: every channel on lf_finish_kernel's walk)
+  if (pipeline) hipLaunchKernelGGL(lf_finish_gradient_kernel, dim3(ntasks), dim3(64), 0, s, imgs, tasks);
   hipLaunchKernelGGL(lf_finish_kernel, dim3(ntasks), dim3(256), 0, s, imgs, tasks);
 }
 
