@@ -190,7 +190,9 @@ JXLFILETYPEIO_API int32_t jxlhip_stage_totals(JxlHipDecoder* dec, const char** n
 /* Device time of the stages of the calling thread's last LoadImage / lossy SaveImage (HIP events on the streams the kernels were
  * launched on; measurement only: bench.py's single-image and encode workloads read them next to the wall time of the call).  A save
  * at effort 8 or 9 adds one stage per evaluation of its closed loop ("evaluation k (...)": everything from the quant field to the
- * cell distances, host work included). */
+ * cell distances, host work included).  A lossless save at effort 8 or 9 reports the stages of its search instead ("lossless: colour
+ * count", "... transform and predictor search", "... planes", "... weighted pass", "... tokens", "... sections"; the last two once
+ * per candidate stream, host work between the launches included); a lossless save at a lower effort leaves the list as it was. */
 JXLFILETYPEIO_API int32_t jxlhip_last_load_stage_times(const char** names, float* ms, int32_t capacity);
 JXLFILETYPEIO_API int32_t jxlhip_last_save_stage_times(const char** names, float* ms, int32_t capacity);
 
@@ -207,6 +209,24 @@ JXLFILETYPEIO_API EncoderStatus jxlhip_distance_map(const uint8_t* a_bgra, uint3
  * at the first evaluation (the field effort 7 writes) and at the one written.  Returns the number of cells.  Any pointer may be NULL. */
 JXLFILETYPEIO_API size_t jxlhip_last_save_distances(float* dst, size_t capacity, int32_t* evaluations, float* target,
                                                     int32_t* cells_over_target_first, int32_t* cells_over_target_emitted);
+
+/* What the search of the calling thread's last lossless SaveImage chose ("Lossless efforts 8 and 9").  After a
+ * lossy save, or a lossless one at an effort below 8, `tier` is 0 and so is everything else.  Byte counts are those of the bare
+ * codestream (no container). */
+typedef struct JxlHipLosslessInfo {
+  int32_t tier;                 /* 8 or 9: the effort tier that ran; 0: none */
+  int32_t palette_colours;      /* entries of the palette that replaced the coded channels; 0: no palette */
+  int32_t rct_type;             /* reversible colour transform 0..6 of permutation 0 (0: none, 6: YCoCg-R); -1: not RGB, or a palette */
+  int32_t num_channels;         /* coded channels (1 behind a palette) */
+  int32_t predictor[4];         /* the format's predictor id per coded channel (1..6; 6: weighted); 0 past num_channels */
+  int32_t leaves;               /* leaves of the MA tree = contexts */
+  int32_t clusters;             /* distributions they were clustered into */
+  int32_t fell_back_to_effort7; /* 1: the searched stream was not smaller, so the bytes of effort 7 were written */
+  int32_t reserved;
+  uint64_t searched_bytes;      /* the searched stream */
+  uint64_t effort7_bytes;       /* the stream of effort 7 */
+} JxlHipLosslessInfo;
+JXLFILETYPEIO_API void jxlhip_last_save_lossless_info(JxlHipLosslessInfo* out);
 
 /* Host-only (no GPU): the embedded ICC profile as LoadImage would hand it to setIccProfile (reference Decoder/JxlDecoder.cpp:652-682);
  * returns its size (0: none) and copies up to `capacity` bytes. */

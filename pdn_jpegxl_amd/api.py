@@ -65,9 +65,16 @@ class ImageInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class LosslessInfo(C.Structure):
+    _fields_ = [("tier", C.c_int32), ("palette_colours", C.c_int32), ("rct_type", C.c_int32), ("num_channels", C.c_int32),
+                ("predictor", C.c_int32 * 4), ("leaves", C.c_int32), ("clusters", C.c_int32), ("fell_back_to_effort7", C.c_int32),
+                ("reserved", C.c_int32), ("searched_bytes", C.c_uint64), ("effort7_bytes", C.c_uint64)]
+
+
 EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jxlhip_decoder_create", "jxlhip_decoder_destroy", "jxlhip_peek",
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
-           "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances"]
+           "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
+           "jxlhip_last_save_lossless_info"]
 
 _lib = None
 
@@ -147,6 +154,8 @@ def lib(build_if_missing=True):
     L.jxlhip_last_save_distances.restype = C.c_size_t
     L.jxlhip_last_save_distances.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32)]
+    L.jxlhip_last_save_lossless_info.restype = None
+    L.jxlhip_last_save_lossless_info.argtypes = [C.POINTER(LosslessInfo)]
     L.jxlhip_parse_check.restype = C.c_int32
     L.jxlhip_parse_check.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_static_table.restype = C.c_size_t
@@ -388,6 +397,18 @@ def last_save_distances():
         L.jxlhip_last_save_distances(cells.ctypes.data, n, None, None, None, None)
     return {"cells": cells, "evaluations": ev.value, "target": target.value, "cells_over_target_first": first.value,
             "cells_over_target_emitted": emitted.value}
+
+
+def last_save_lossless_info():
+    """What the search of this thread's last lossless save_image() chose: dict with `tier` (8 or 9; 0 after a lossy save or an effort
+    below 8, and then everything else is 0), `palette_colours` (0: none), `rct_type` (-1: not RGB, or a palette), `predictors` (one per
+    coded channel), `leaves`, `clusters`, `fell_back_to_effort7`, `searched_bytes`, `effort7_bytes` (bare codestreams)."""
+    info = LosslessInfo()
+    lib().jxlhip_last_save_lossless_info(C.byref(info))
+    return {"tier": info.tier, "palette_colours": info.palette_colours, "rct_type": info.rct_type,
+            "predictors": [info.predictor[c] for c in range(info.num_channels)], "leaves": info.leaves, "clusters": info.clusters,
+            "fell_back_to_effort7": bool(info.fell_back_to_effort7), "searched_bytes": info.searched_bytes,
+            "effort7_bytes": info.effort7_bytes}
 
 
 class Decoder:

@@ -83,12 +83,41 @@ struct EncImage {
   int32_t* ll_plane[4];
   int32_t ll_nch, ll_rct;   // ll_rct: RGB is coded as YCoCg-R (reversible colour transform 6)
   DevToken* tok_ll;         // [ng][4 * 65536]
+  uint32_t ll_tok_extra, pad2;   // tokens ahead of the samples in group 0's stream (a palette's colours in a one-group frame)
   // entropy coding
   EncCodeDev mcode, acode;
   uint8_t* sec_bytes;       // section s at s * sec_cap
   uint32_t* stream_state;   // final rANS state per token stream (lossy frames: 2 per LF group, 2 per group, 1 global alpha)
   uint64_t* sec_bits;       // bits written per section
   uint64_t sec_cap;
+};
+
+// The searched lossless stream of efforts 8 and 9 (lossless_kernels.hip; the rules: DESIGN.md §2, "Lossless efforts 8 and 9").
+constexpr uint32_t kPalCap = 1024;        // most colours a palette is written for
+constexpr uint32_t kPalSlots = 4096;      // slots of the colour hash set (a power of two, four times the cap)
+constexpr int kLlSlots = 10;              // candidate planes costed in one pass: R, G, G-R, G-((R+B)>>1), B, B-R, Y, Co, Cg, alpha
+constexpr int kLlPreds = 5;               // predictors 1..5: West, North, average, Select, gradient
+constexpr int kWpLeaves = 11;             // buckets of property 15 (kWpCuts of lossless_kernels.hip)
+constexpr uint32_t kLlMaxLeaves = 4 * kWpLeaves + 4;
+
+struct LlSearch {
+  // palette: the set of distinct pixels over the coded channels, slot = 0 (empty) or 1 << 32 | key; key = channel k in byte k
+  unsigned long long* pal_set;   // [kPalSlots]
+  uint32_t* pal_count;           // [0] colours inserted, [1] set once more than kPalCap were seen (or the set ran full)
+  const uint16_t* pal_index;     // [kPalSlots]: slot -> index in the sorted palette
+  // search: token histograms of the residuals of every (candidate plane, predictor)
+  uint32_t* hist_search;         // [kLlSlots * kLlPreds][kEncSyms]
+  int32_t from_planes;           // 0: candidates from the BGRA surface (RGB); 1: the ll_nch planes as they are (gray, palette indices)
+  // what was chosen
+  int32_t rct_type;              // 0..6 of permutation 0 (RGB), 0 otherwise
+  int32_t pred[4];               // predictor of coded channel c (1..6)
+  int32_t wp_ctx;                // 1: the context of a sample follows property 15
+  uint8_t ctx[4][kWpLeaves + 1]; // context (leaf id) of channel c and bucket k of property 15 (every bucket the same without wp_ctx)
+  // forward weighted predictor: prediction and property 15 of every sample, histogram of its residuals per channel
+  int32_t* wp_pred[4];
+  int32_t* wp_prop[4];
+  uint32_t* hist_wp;             // [4][kEncSyms]
+  uint32_t* hist_ll;             // [kLlMaxLeaves][kEncSyms]
 };
 
 // Distance map of a reconstruction against its original, both as XYB planes (distance_kernels.hip; the rules and the constants:

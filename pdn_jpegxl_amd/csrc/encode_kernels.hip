@@ -12,6 +12,7 @@
 //   enc_sections_kernel       ANS coding, one lane per section (reverse pass for the state, forward pass for the bits)
 #include <hip/hip_runtime.h>
 #include "dev_util.h"
+#include "enc_dev.h"
 #include "enc_types.h"
 #include "kernels.h"
 
@@ -19,20 +20,7 @@ namespace jxlhip {
 
 namespace {
 
-__device__ __forceinline__ uint32_t PackSignedD(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(int64_t)v)) << 1) - 1; }
 __device__ __forceinline__ int CeilLog2E(uint32_t x) { return x <= 1 ? 0 : 32 - __clz(x - 1); }
-// hybrid-uint token of `v` under the config (split_exponent 4, msb_in_token 2, lsb_in_token 0)
-__device__ __forceinline__ void HybridD(uint32_t v, uint32_t* tok, uint32_t* nbits, uint32_t* bits) {
-  if (v < 16) { *tok = v; *nbits = 0; *bits = 0; return; }
-  const uint32_t n = 31 - __clz(v), m = v - (1u << n);
-  *tok = 16 + ((n - 4) << 2) + (m >> (n - 2));
-  *nbits = n - 2;
-  *bits = m & ((1u << (n - 2)) - 1);
-}
-__device__ __forceinline__ int32_t GradientPred(int32_t W, int32_t N, int32_t NW) {
-  const int64_t mn = W < N ? W : N, mx = W < N ? N : W, gr = (int64_t)W + N - NW;
-  return (int32_t)(gr < mn ? mn : (gr > mx ? mx : gr));
-}
 
 __device__ const uint8_t e_nnz_ctx[64] = {0,   0,   31,  62,  62,  93,  93,  93,  93,  123, 123, 123, 123, 152, 152, 152, 152, 152, 152, 152, 152, 180,
                                           180, 180, 180, 180, 180, 180, 180, 180, 180, 180, 180, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206,
@@ -931,7 +919,7 @@ __global__ __launch_bounds__(64 * kSectionsPerWg) void enc_ll_sections_kernel(En
   WaveWriter w;
   w.Init(im.sec_bytes + (size_t)g * im.sec_cap, sc, lane);
   if (im.ng > 1) w.PutUniform(4, 3);   // group header; a single-group frame continues the GlobalModular stream of LfGlobal
-  EncodeStream<true>(im.tok_ll + (size_t)g * kLlTokCap, (uint32_t)(gw * gh * im.ll_nch), im.mcode, w, sc);
+  EncodeStream<true>(im.tok_ll + (size_t)g * kLlTokCap, (uint32_t)(gw * gh * im.ll_nch) + (g ? 0u : im.ll_tok_extra), im.mcode, w, sc);
   const uint64_t bits = w.Finish();
   if (lane == 0) im.sec_bits[g] = bits;
 }

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -31,6 +32,7 @@ void LaunchEncReverse(const EncImage& im, int which, hipStream_t s);
 void LaunchEncSections(const EncImage& im, hipStream_t s);
 void LaunchEncCompact(const EncImage& im, const uint64_t* dst_off, uint8_t* dst, int nsec, hipStream_t s);
 void LaunchEncLossless(const EncImage& im, int stage, hipStream_t s);
+void LaunchEncLosslessSearch(const EncImage& im, const LlSearch& ls, int stage, hipStream_t s);   // lossless_kernels.hip
 void LaunchEncXyb(const EncImage& im, hipStream_t s);
 void LaunchEncVarblocks(const EncImage& im, hipStream_t s);
 // distance_kernels.hip
@@ -234,54 +236,20 @@ void BeginImage(const BitmapData* bmp, const EncoderImageMetadata* md, Arena& A,
   Progress(progress, 5);
 }
 
-// Lossless: a Modular frame in the original (sRGB) colour space (Encoder/JxlEncoder.cpp:214,325); 256x256 groups, YCoCg-R for RGB,
-// gradient predictor, one context per channel.
-void EncodeLossless(const BitmapData* bmp, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
-  Arena A;
-  hipStream_t s = nullptr;
-  EncImage im;
-  BeginImage(bmp, md, A, im, progress);
-  const size_t npx = (size_t)im.w * im.h;
-  im.lossless = 1;
-  im.ll_nch = (im.gray ? 1 : 3) + im.has_alpha;
-  im.ll_rct = im.gray ? 0 : 1;
-  for (int c = 0; c < im.ll_nch; c++) im.ll_plane[c] = A.Get<int32_t>(npx);
-  im.tok_ll = A.Get<DevToken>((size_t)im.ng * kLlTokCap);
-  im.hist_mod = A.Get<uint32_t>(kNumEncLeaves * kEncSyms, true);
-  Progress(progress, 15);
-  LaunchEncLossless(im, 0, s);
-  std::vector<uint32_t> hist(4 * kEncSyms);
-  ENC_HIP(hipMemcpy(hist.data(), im.hist_mod, hist.size() * 4, hipMemcpyDeviceToHost));
-  Progress(progress, 25);
-  // LfGlobal: tree on the channel index (leaf ids: channel 3, 2, 1, 0), code, GlobalModular header
+// ANS-codes the groups' tokens (im.tok_ll) with `mcode`, gathers the sections and assembles the codestream behind the finished LfGlobal
+// prefix.  The section buffers are allocated at the first call of a save and reused by the next.
+std::vector<uint8_t> FinishLossless(EncImage& im, Arena& A, const EncCode& mcode, BitWriter& lf_global, const EncoderImageMetadata* md, hipStream_t s) {
   const bool single = im.ng == 1;
-  BitWriter lf_global;
-  EncCode mcode;
-  lf_global.Bool(true);   // default LF dequantisation factors (read for every frame encoding)
-  lf_global.Bool(true);   // global MA tree
-  {
-    std::vector<EncTreeNode> t;
-    t.push_back(EncTreeNode{0, 1, 0, 0, 1});     // 0: channel > 1 ? 1 : 2
-    t.push_back(EncTreeNode{0, 2, 0, 0, 1});     // 1: channel > 2 ? 3 : 4
-    t.push_back(EncTreeNode{0, 0, 0, 0, 1});     // 2: channel > 0 ? 5 : 6
-    for (int i = 0; i < 4; i++) t.push_back(EncTreeNode{-1, 0, 5, 0, 1});   // gradient predictor leaves: channel 3, 2, 1, 0
-    WriteTree(t, lf_global);
-  }
-  BuildAndWriteCode(hist.data(), 4, 4, {}, lf_global, mcode);
-  lf_global.Bool(true);   // use the global tree
-  lf_global.Bool(true);   // default weighted-predictor parameters
-  lf_global.U32(WV(0), WV(1), WB(4, 2), WB(8, 18), im.ll_rct ? 1 : 0);
-  if (im.ll_rct) {
-    lf_global.Write(2, 0);                                            // transform id 0: reversible colour transform
-    lf_global.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);      // first channel
-    lf_global.U32(WV(6), WB(2), WB(4, 2), WB(6, 10), 6);              // type 6: YCoCg-R
-  }
   im.mcode = UploadCode(A, mcode);
   const int nsec = im.ng;
-  im.sec_cap = ((size_t)kLlTokCap * 6 + 256) & ~(size_t)15;
-  im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
-  im.sec_bits = A.Get<uint64_t>(nsec, true);
-  im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1, true);
+  if (!im.sec_bytes) {
+    im.sec_cap = ((size_t)kLlTokCap * 6 + 256) & ~(size_t)15;
+    im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
+    im.sec_bits = A.Get<uint64_t>(nsec, true);
+    im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1, true);
+  } else {
+    ENC_HIP(hipMemset(im.sec_bits, 0, std::max<size_t>((size_t)nsec * 8, 256)));
+  }
   LaunchEncLossless(im, 1, s);
   std::vector<uint64_t> sec_bits(nsec);
   ENC_HIP(hipMemcpy(sec_bits.data(), im.sec_bits, sec_bits.size() * 8, hipMemcpyDeviceToHost));
@@ -295,7 +263,6 @@ void EncodeLossless(const BitmapData* bmp, const EncoderImageMetadata* md, IOCal
     ENC_HIP(hipMemcpy(packed.data(), d_packed, packed.size(), hipMemcpyDeviceToHost));
   }
   ENC_HIP(hipGetLastError());
-  Progress(progress, 30);
   EncImageInfo ii;
   ii.xsize = (uint32_t)im.w; ii.ysize = (uint32_t)im.h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = false;
   ii.icc = md->iccProfile; ii.icc_size = md->iccProfile ? md->iccProfileSize : 0;
@@ -319,6 +286,367 @@ void EncodeLossless(const BitmapData* bmp, const EncoderImageMetadata* md, IOCal
   WriteToc(sizes, cs);
   std::vector<uint8_t> codestream = cs.Finish();
   for (auto& sec : sections) codestream.insert(codestream.end(), sec.begin(), sec.end());
+  return codestream;
+}
+
+// The stream of efforts 1..7: 256x256 groups, YCoCg-R for RGB, gradient predictor, one context per channel.  `progress` (may be
+// null) sees 25 once the histograms are down.
+std::vector<uint8_t> CodeLosslessFixed(EncImage& im, Arena& A, const EncoderImageMetadata* md, hipStream_t s, ProgressProc progress) {
+  im.ll_nch = (im.gray ? 1 : 3) + im.has_alpha;
+  im.ll_rct = im.gray ? 0 : 1;
+  im.ll_tok_extra = 0;
+  im.hist_mod = A.Get<uint32_t>(kNumEncLeaves * kEncSyms, true);
+  LaunchEncLossless(im, 0, s);
+  std::vector<uint32_t> hist(4 * kEncSyms);
+  ENC_HIP(hipMemcpy(hist.data(), im.hist_mod, hist.size() * 4, hipMemcpyDeviceToHost));
+  Progress(progress, 25);
+  // LfGlobal: tree on the channel index (leaf ids: channel 3, 2, 1, 0), code, GlobalModular header
+  BitWriter lf_global;
+  EncCode mcode;
+  lf_global.Bool(true);   // default LF dequantisation factors (read for every frame encoding)
+  lf_global.Bool(true);   // global MA tree
+  {
+    std::vector<EncTreeNode> t;
+    t.push_back(EncTreeNode{0, 1, 0, 0, 1});     // 0: channel > 1 ? 1 : 2
+    t.push_back(EncTreeNode{0, 2, 0, 0, 1});     // 1: channel > 2 ? 3 : 4
+    t.push_back(EncTreeNode{0, 0, 0, 0, 1});     // 2: channel > 0 ? 5 : 6
+    for (int i = 0; i < 4; i++) t.push_back(EncTreeNode{-1, 0, 5, 0, 1});   // gradient predictor leaves: channel 3, 2, 1, 0
+    WriteTree(t, lf_global);
+  }
+  BuildAndWriteCode(hist.data(), 4, 4, {}, lf_global, mcode);
+  lf_global.Bool(true);   // use the global tree
+  lf_global.Bool(true);   // default weighted-predictor parameters
+  lf_global.U32(WV(0), WV(1), WB(4, 2), WB(8, 18), im.ll_rct ? 1 : 0);
+  if (im.ll_rct) {
+    lf_global.Write(2, 0);                                            // transform id 0: reversible colour transform
+    lf_global.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);      // first channel
+    lf_global.U32(WV(6), WB(2), WB(4, 2), WB(6, 10), 6);              // type 6: YCoCg-R
+  }
+  return FinishLossless(im, A, mcode, lf_global, md, s);
+}
+
+// ---- the searched stream of efforts 8 and 9 ("Lossless efforts 8 and 9")
+
+// bits of a token histogram: zero-order entropy plus the extra bits of the hybrid-uint config (4, 2, 0), which the token determines
+double TokenCost(const uint32_t* h) {
+  uint64_t total = 0;
+  for (uint32_t t = 0; t < kEncSyms; t++) total += h[t];
+  double bits = 0;
+  for (uint32_t t = 0; t < kEncSyms; t++) {
+    if (!h[t]) continue;
+    bits += (double)h[t] * std::log2((double)total / (double)h[t]);
+    if (t >= 16) bits += (double)h[t] * (double)(2 + ((t - 16) >> 2));
+  }
+  return bits;
+}
+
+int32_t PredictHost(int pred, int32_t W, int32_t N, int32_t NW) {
+  const int64_t gr = (int64_t)W + N - NW;
+  switch (pred) {
+    case 1: return W;
+    case 2: return N;
+    case 3: return (int32_t)(((int64_t)W + N) / 2);
+    case 4: return std::llabs(gr - W) < std::llabs(gr - N) ? W : N;
+    default: return (int32_t)std::max<int64_t>(std::min(W, N), std::min<int64_t>(std::max(W, N), gr));
+  }
+}
+uint32_t PackSignedHost(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(int64_t)v)) << 1) - 1; }
+
+// An MA tree under construction: nodes point at their children, Flatten puts them in decode (breadth-first) order and numbers the
+// leaves as the decoder will (context id = rank of the leaf in that order).
+struct TreeBuilder {
+  struct Node { int property; int32_t splitval; int pred; int gt, le; };
+  std::vector<Node> nodes;
+  int Leaf(int pred) { nodes.push_back(Node{-1, 0, pred, -1, -1}); return (int)nodes.size() - 1; }
+  int Split(int property, int32_t v, int gt, int le) { nodes.push_back(Node{property, v, 0, gt, le}); return (int)nodes.size() - 1; }
+  std::vector<EncTreeNode> Flatten(int root, std::vector<int>* ctx_of_node) const {
+    std::vector<EncTreeNode> out;
+    ctx_of_node->assign(nodes.size(), -1);
+    std::vector<int> order{root};
+    int leaves = 0;
+    for (size_t k = 0; k < order.size(); k++) {
+      const Node& n = nodes[order[k]];
+      if (n.property < 0) { out.push_back(EncTreeNode{-1, 0, n.pred, 0, 1}); (*ctx_of_node)[order[k]] = leaves++; continue; }
+      out.push_back(EncTreeNode{n.property, n.splitval, 0, 0, 1});
+      order.push_back(n.gt);
+      order.push_back(n.le);
+    }
+    return out;
+  }
+};
+
+}  // namespace
+
+// The thresholds of property 15 that split a channel's contexts at effort 9 (the oracle writer's), and the searched tree: the channel
+// (a palette frame: palette against indices, see below), then, with `wp_ctx`, property 15 searched over the thresholds.  ctx[c][k]:
+// context of channel c, bucket k = number of thresholds the property exceeds.  `palette`: 0 none; 1 a one-group frame, whose global
+// stream holds the colours as channel 0 and the indices as channel 1; 2 a frame of several groups, whose colours are alone in the global
+// stream (stream 0) and whose indices are channel 0 of every group's stream.  *palette_ctx: the colours' context.  (Not file-local:
+// the test library's self tests serialise it, csrc/selftest.cc.)
+extern const int32_t kWpCutsHost[kWpLeaves - 1] = {-80, -24, -8, -3, -1, 0, 2, 7, 23, 79};
+std::vector<EncTreeNode> MakeLosslessSearchTree(int nch, const int32_t* pred, bool wp_ctx, int palette, uint8_t ctx[4][kWpLeaves + 1], int* palette_ctx) {
+  TreeBuilder b;
+  int leaf_of[4][kWpLeaves];
+  int sub[4];
+  for (int c = 0; c < nch; c++) {
+    if (!wp_ctx) {
+      sub[c] = b.Leaf(pred[c]);
+      for (int k = 0; k < kWpLeaves; k++) leaf_of[c][k] = sub[c];
+      continue;
+    }
+    struct R { static int Build(TreeBuilder& b, int lo, int hi, int pred, int* leaf_of) {   // thresholds [lo, hi)
+      if (lo == hi) return leaf_of[lo] = b.Leaf(pred);
+      const int mid = (lo + hi) / 2;
+      const int gt = Build(b, mid + 1, hi, pred, leaf_of), le = Build(b, lo, mid, pred, leaf_of);
+      return b.Split(15, kWpCutsHost[mid], gt, le);
+    } };
+    sub[c] = R::Build(b, 0, kWpLeaves - 1, pred[c], leaf_of[c]);
+  }
+  int root = sub[nch - 1];
+  for (int c = nch - 2; c >= 0; c--) root = b.Split(0, c, root, sub[c]);   // channel > c ? the channels after c : c
+  int pal_leaf = -1;
+  if (palette) {
+    pal_leaf = b.Leaf(pred[nch]);
+    root = palette == 1 ? b.Split(0, 0, root, pal_leaf) : b.Split(1, 0, root, pal_leaf);
+  }
+  std::vector<int> ctx_of;
+  std::vector<EncTreeNode> t = b.Flatten(root, &ctx_of);
+  for (int c = 0; c < nch; c++)
+    for (int k = 0; k < kWpLeaves; k++) ctx[c][k] = (uint8_t)ctx_of[leaf_of[c][k]];
+  if (palette_ctx) *palette_ctx = palette ? ctx_of[pal_leaf] : -1;
+  return t;
+}
+
+// The GlobalModular header of a searched frame: global tree, default weighted-predictor parameters, at most one transform.
+void WriteLosslessSearchHeader(BitWriter& bw, int palette_colours, int palette_channels, int rct_type) {
+  bw.Bool(true);   // use the global tree
+  bw.Bool(true);   // default weighted-predictor parameters
+  const bool rct = !palette_colours && rct_type > 0;
+  bw.U32(WV(0), WV(1), WB(4, 2), WB(8, 18), palette_colours || rct ? 1 : 0);
+  if (palette_colours) {
+    bw.Write(2, 1);                                                             // transform id 1: palette
+    bw.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);                       // first channel
+    bw.U32(WV(1), WV(3), WV(4), WB(13, 1), (uint32_t)palette_channels);         // channels: colour and alpha together
+    bw.U32(WB(8), WB(10, 256), WB(12, 1280), WB(16, 5376), (uint32_t)palette_colours);
+    bw.U32(WV(0), WB(8, 1), WB(10, 257), WB(16, 1281), 0);                      // no delta entries
+    bw.Write(4, 0);                                                             // (their predictor)
+  } else if (rct) {
+    bw.Write(2, 0);                                                             // transform id 0: reversible colour transform
+    bw.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);
+    bw.U32(WV(6), WB(2), WB(4, 2), WB(6, 10), (uint32_t)rct_type);
+  }
+}
+
+namespace {
+
+thread_local JxlHipLosslessInfo g_last_lossless;
+
+constexpr int kLlMaxClusters = 12;   // of the effort-9 code: what enc_ll_sections_kernel stages in LDS
+
+// The searched stream(s).  `im` arrives from BeginImage; `fixed` is the stream of effort 7 (the fallback).  Returns the stream to write.
+std::vector<uint8_t> CodeLosslessSearched(EncImage& im, Arena& A, const EncoderImageMetadata* md, int tier, hipStream_t s, ProgressProc progress,
+                                          StageMarks& marks, const std::vector<uint8_t>& fixed, JxlHipLosslessInfo& info) {
+  const size_t npx = (size_t)im.w * im.h;
+  const bool single = im.ng == 1;
+  const int nch_all = (im.gray ? 1 : 3) + im.has_alpha;
+  LlSearch ls;
+  memset(&ls, 0, sizeof(ls));
+  // ---- 1. palette: the distinct pixels over the coded channels.  A palette of one channel would only rename its values.
+  std::vector<uint32_t> colours;   // sorted keys
+  if (nch_all >= 2) {
+    ls.pal_set = A.Get<unsigned long long>(kPalSlots, true);
+    ls.pal_count = A.Get<uint32_t>(2, true);
+    { const size_t k = marks.Begin("lossless: colour count", s); LaunchEncLosslessSearch(im, ls, 0, s); marks.End(k, s); }
+    uint32_t cnt[2];
+    ENC_HIP(hipMemcpy(cnt, ls.pal_count, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (!cnt[1] && cnt[0] <= kPalCap) {
+      std::vector<unsigned long long> set(kPalSlots);
+      ENC_HIP(hipMemcpy(set.data(), ls.pal_set, set.size() * 8, hipMemcpyDeviceToHost));
+      for (auto v : set) if (v) colours.push_back((uint32_t)v);
+      // a fixed order, so that the stream does not depend on which thread inserted first: luma, then alpha, then the key itself
+      const bool gray = im.gray, alpha = im.has_alpha;
+      auto rank = [gray, alpha](uint32_t k) {
+        const uint32_t luma = gray ? (k & 255) * 1000 : 299 * (k & 255) + 587 * ((k >> 8) & 255) + 114 * ((k >> 16) & 255);
+        const uint32_t a = alpha ? (k >> (gray ? 8 : 24)) & 255 : 0;
+        return ((uint64_t)luma << 40) | ((uint64_t)a << 32) | k;
+      };
+      std::sort(colours.begin(), colours.end(), [&](uint32_t x, uint32_t y) { return rank(x) < rank(y); });
+      std::vector<uint16_t> index(kPalSlots, 0);
+      for (size_t slot = 0; slot < set.size(); slot++)
+        if (set[slot]) index[slot] = (uint16_t)(std::lower_bound(colours.begin(), colours.end(), (uint32_t)set[slot], [&](uint32_t x, uint32_t y) { return rank(x) < rank(y); }) - colours.begin());
+      ls.pal_index = A.Upload(index);
+    }
+  }
+  const int ncol = (int)colours.size();
+  Progress(progress, 17);
+  // ---- 2. planes and the search over transforms and predictors
+  for (int c = 0; c < 4; c++) if (!im.ll_plane[c] && c < nch_all) im.ll_plane[c] = A.Get<int32_t>(npx);
+  ls.hist_search = A.Get<uint32_t>((size_t)kLlSlots * kLlPreds * kEncSyms, true);
+  im.ll_nch = ncol ? 1 : nch_all;
+  im.ll_rct = 0;
+  im.ll_tok_extra = 0;
+  int slot_of[4] = {0, 1, 2, 3};
+  int rct_type = -1;
+  {
+    const size_t k = marks.Begin("lossless: transform and predictor search", s);
+    if (ncol) LaunchEncLosslessSearch(im, ls, 1, s);
+    else if (im.gray) LaunchEncLosslessSearch(im, ls, 3, s);
+    ls.from_planes = ncol || im.gray;
+    LaunchEncLosslessSearch(im, ls, 2, s);
+    marks.End(k, s);
+  }
+  std::vector<uint32_t> hs((size_t)kLlSlots * kLlPreds * kEncSyms);
+  ENC_HIP(hipMemcpy(hs.data(), ls.hist_search, hs.size() * 4, hipMemcpyDeviceToHost));
+  auto cost = [&](int slot, int pred) { return TokenCost(hs.data() + (size_t)(slot * kLlPreds + pred - 1) * kEncSyms); };
+  if (!ls.from_planes) {
+    // candidate planes (enc_types.h: kLlSlots) of types 0..6, priced under the gradient predictor; ties go to YCoCg-R
+    static const int kSlots[7][3] = {{0, 1, 4}, {0, 1, 5}, {0, 2, 4}, {0, 2, 5}, {0, 3, 4}, {0, 3, 5}, {6, 7, 8}};
+    auto type_cost = [&](int t) { return cost(kSlots[t][0], 5) + cost(kSlots[t][1], 5) + cost(kSlots[t][2], 5); };
+    rct_type = 6;
+    double best = type_cost(6);
+    for (int t = 0; t < 6; t++) { const double v = type_cost(t); if (v < best) { best = v; rct_type = t; } }
+    for (int c = 0; c < 3; c++) slot_of[c] = kSlots[rct_type][c];
+    slot_of[3] = kLlSlots - 1;
+    ls.rct_type = rct_type;
+    const size_t k = marks.Begin("lossless: planes", s);
+    LaunchEncLosslessSearch(im, ls, 3, s);
+    marks.End(k, s);
+  }
+  int32_t pred[5] = {5, 5, 5, 5, 5};   // per coded channel; [ll_nch]: the palette's colours
+  double pred_cost[4] = {0, 0, 0, 0};
+  for (int c = 0; c < im.ll_nch; c++) {
+    pred_cost[c] = cost(slot_of[c], 5);   // ties go to the gradient predictor
+    for (int p = 1; p <= 4; p++) { const double v = cost(slot_of[c], p); if (v < pred_cost[c]) { pred_cost[c] = v; pred[c] = p; } }
+  }
+  Progress(progress, 19);
+  // ---- 3. the palette's colours as the host codes them: a channel ncol wide, one row per coded channel
+  std::vector<EncToken> pal_tok;
+  if (ncol) {
+    std::vector<int32_t> meta((size_t)ncol * nch_all);
+    for (int c = 0; c < nch_all; c++)
+      for (int i = 0; i < ncol; i++) meta[(size_t)c * ncol + i] = (int32_t)((colours[i] >> (8 * c)) & 255);
+    auto residuals = [&](int p, std::vector<uint32_t>* out) {
+      out->clear();
+      for (int y = 0; y < nch_all; y++)
+        for (int x = 0; x < ncol; x++) {
+          const int32_t* row = meta.data() + (size_t)y * ncol;
+          int32_t W, N, NW;
+          if (x == 0) { W = y ? row[-ncol] : 0; N = W; NW = W; }
+          else { W = row[x - 1]; N = y ? row[x - ncol] : W; NW = y ? row[x - ncol - 1] : W; }
+          out->push_back(PackSignedHost(row[x] - PredictHost(p, W, N, NW)));
+        }
+    };
+    std::vector<uint32_t> res, best_res;
+    double best = 0;
+    for (int p : {5, 1, 2, 3, 4}) {
+      residuals(p, &res);
+      uint32_t h[kEncSyms] = {0};
+      for (uint32_t v : res) { uint32_t tok, nb, bits; HybridEncode(v, &tok, &nb, &bits); h[tok]++; }
+      const double v = TokenCost(h);
+      if (best_res.empty() || v < best) { best = v; best_res = res; pred[1] = p; }
+    }
+    for (uint32_t v : best_res) pal_tok.push_back(EncToken{0, v});   // (context: below)
+  }
+  im.tok_ll = im.tok_ll ? im.tok_ll : A.Get<DevToken>((size_t)im.ng * kLlTokCap);
+  ls.hist_ll = A.Get<uint32_t>((size_t)kLlMaxLeaves * kEncSyms);
+  // One candidate stream: tokens under `use_pred` (and, with wp_ctx, property-15 contexts), code, sections.
+  struct Candidate { std::vector<uint8_t> bytes; int32_t pred[4]; int leaves = 0, clusters = 0; };
+  auto code = [&](const int32_t* use_pred, bool wp_ctx) {
+    Candidate cand;
+    int32_t tree_pred[5];
+    for (int c = 0; c < im.ll_nch; c++) cand.pred[c] = tree_pred[c] = use_pred[c];
+    for (int c = im.ll_nch; c < 4; c++) cand.pred[c] = 0;
+    tree_pred[im.ll_nch] = pred[1];
+    int pal_ctx = -1;
+    std::vector<EncTreeNode> tree = MakeLosslessSearchTree(im.ll_nch, tree_pred, wp_ctx, ncol ? (single ? 1 : 2) : 0, ls.ctx, &pal_ctx);
+    cand.leaves = (int)(tree.size() + 1) / 2;
+    for (int c = 0; c < 4; c++) ls.pred[c] = cand.pred[c];
+    ls.wp_ctx = wp_ctx;
+    im.ll_tok_extra = ncol && single ? (uint32_t)pal_tok.size() : 0;
+    ENC_HIP(hipMemset(ls.hist_ll, 0, (size_t)kLlMaxLeaves * kEncSyms * 4));
+    { const size_t k = marks.Begin(wp_ctx ? "lossless: tokens (property-15 contexts)" : "lossless: tokens", s); LaunchEncLosslessSearch(im, ls, 5, s); marks.End(k, s); }
+    std::vector<uint32_t> hist((size_t)cand.leaves * kEncSyms);
+    ENC_HIP(hipMemcpy(hist.data(), ls.hist_ll, hist.size() * 4, hipMemcpyDeviceToHost));
+    if (ncol) {
+      for (auto& t : pal_tok) {
+        t.ctx = (uint32_t)pal_ctx;
+        uint32_t tok, nb, bits;
+        HybridEncode(t.value, &tok, &nb, &bits);
+        hist[(size_t)pal_ctx * kEncSyms + tok]++;
+      }
+      if (single) {
+        std::vector<DevToken> dt;
+        for (auto& t : pal_tok) dt.push_back(DevToken{t.ctx, t.value});
+        ENC_HIP(hipMemcpy(im.tok_ll, dt.data(), dt.size() * sizeof(DevToken), hipMemcpyHostToDevice));
+      }
+    }
+    BitWriter lf_global;
+    EncCode mcode;
+    lf_global.Bool(true);   // default LF dequantisation factors
+    lf_global.Bool(true);   // global MA tree
+    WriteTree(tree, lf_global);
+    BuildAndWriteCode(hist.data(), (size_t)cand.leaves, std::min(kLlMaxClusters, cand.leaves), {}, lf_global, mcode);
+    cand.clusters = (int)mcode.num_clusters;
+    WriteLosslessSearchHeader(lf_global, ncol, nch_all, rct_type);
+    if (ncol && !single) WriteTokensHost(pal_tok, mcode, lf_global);   // the colours are the global stream's only channel
+    const size_t k = marks.Begin(wp_ctx ? "lossless: sections (property-15 contexts)" : "lossless: sections", s);
+    cand.bytes = FinishLossless(im, A, mcode, lf_global, md, s);
+    marks.End(k, s);
+    return cand;
+  };
+  Candidate chosen = code(pred, false);
+  Progress(progress, 22);
+  // ---- 4. effort 9: the weighted predictor's state on the encode side.  Palette frames stay as they are.
+  if (tier >= 9 && !ncol) {
+    for (int c = 0; c < im.ll_nch; c++) { ls.wp_pred[c] = A.Get<int32_t>(npx); ls.wp_prop[c] = A.Get<int32_t>(npx); }
+    ls.hist_wp = A.Get<uint32_t>(4 * kEncSyms, true);
+    { const size_t k = marks.Begin("lossless: weighted pass", s); LaunchEncLosslessSearch(im, ls, 4, s); marks.End(k, s); }
+    std::vector<uint32_t> hw(4 * kEncSyms);
+    ENC_HIP(hipMemcpy(hw.data(), ls.hist_wp, hw.size() * 4, hipMemcpyDeviceToHost));
+    int32_t pred9[4];
+    for (int c = 0; c < im.ll_nch; c++) pred9[c] = TokenCost(hw.data() + (size_t)c * kEncSyms) < pred_cost[c] ? 6 : pred[c];
+    Progress(progress, 24);
+    Candidate with_ctx = code(pred9, true);
+    if (with_ctx.bytes.size() < chosen.bytes.size()) chosen = std::move(with_ctx);
+  }
+  Progress(progress, 27);
+  info.tier = tier;
+  info.palette_colours = ncol;
+  info.rct_type = rct_type;
+  info.num_channels = im.ll_nch;
+  for (int c = 0; c < 4; c++) info.predictor[c] = chosen.pred[c];
+  info.leaves = chosen.leaves;
+  info.clusters = chosen.clusters;
+  info.searched_bytes = chosen.bytes.size();
+  info.effort7_bytes = fixed.size();
+  info.fell_back_to_effort7 = chosen.bytes.size() < fixed.size() ? 0 : 1;   // never larger than effort 7: only a strictly smaller stream is written
+  return info.fell_back_to_effort7 ? fixed : chosen.bytes;
+}
+
+// Lossless: a Modular frame in the original (sRGB) colour space (Encoder/JxlEncoder.cpp:214,325).  Efforts up to 7 write the fixed
+// stream; 8 and 9 also search palette, colour transform, predictors and (9) contexts, and write the smaller of the two.
+void EncodeLossless(const BitmapData* bmp, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
+  Arena A;
+  hipStream_t s = nullptr;
+  EncImage im;
+  BeginImage(bmp, md, A, im, progress);
+  const size_t npx = (size_t)im.w * im.h;
+  im.lossless = 1;
+  im.ll_nch = (im.gray ? 1 : 3) + im.has_alpha;
+  for (int c = 0; c < im.ll_nch; c++) im.ll_plane[c] = A.Get<int32_t>(npx);
+  im.tok_ll = A.Get<DevToken>((size_t)im.ng * kLlTokCap);
+  Progress(progress, 15);
+  const int tier = opt->effort >= 9 ? 9 : (opt->effort >= 8 ? 8 : 0);
+  std::vector<uint8_t> codestream = CodeLosslessFixed(im, A, md, s, tier ? nullptr : progress);
+  if (tier) {
+    StageMarks marks;
+    JxlHipLosslessInfo info;
+    memset(&info, 0, sizeof(info));
+    codestream = CodeLosslessSearched(im, A, md, tier, s, progress, marks, codestream, info);
+    marks.Publish(&g_last_save_stages);
+    g_last_lossless = info;
+  }
+  Progress(progress, 30);
   EmitFile(codestream, md, io, progress);
 }
 
@@ -695,6 +1023,11 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_last_save_distances(float* dst, size_
   return d.cells.size();
 }
 
+// What the search of this thread's last lossless SaveImage at effort 8 or 9 chose (tier 0: any other save)
+extern "C" JXLFILETYPEIO_API void jxlhip_last_save_lossless_info(JxlHipLosslessInfo* out) {
+  if (out) *out = g_last_lossless;
+}
+
 // The distance map of picture b against the original a (both BGRA8 in host memory, alpha ignored), through the encoder's
 // sRGB -> XYB conversion: ceil(w / 8) * ceil(h / 8) cell distances, rows of cells top to bottom.
 extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_distance_map(const uint8_t* a_bgra, uint32_t stride_a, const uint8_t* b_bgra, uint32_t stride_b,
@@ -745,9 +1078,10 @@ extern "C" JXLFILETYPEIO_API EncoderStatus SaveImage(const BitmapData* bitmap, c
   if (!bitmap || !options || !callbacks || !metadata) return EncoderStatus_NullParameter;   // Encoder/JxlEncoder.cpp:155-158
   try {
     g_last_dist = LastDistances();
+    g_last_lossless = JxlHipLosslessInfo();
     Progress(progress, 0);   // :162
     if (!callbacks->Write) throw EncFail(EncoderStatus_NullParameter, "");
-    if (options->lossless) EncodeLossless(bitmap, metadata, callbacks, progress);   // :214,325
+    if (options->lossless) EncodeLossless(bitmap, options, metadata, callbacks, progress);   // :214,325
     else EncodeLossy(bitmap, options, metadata, callbacks, progress);
     return EncoderStatus_Ok;
   } catch (const EncFail& e) {
