@@ -152,6 +152,9 @@ JXLFILETYPEIO_API DecoderStatus jxlhip_peek(const uint8_t* data, size_t size, Jx
 /* Decodes n files.  host_data[i]/sizes[i]: the file bytes in host memory (headers are parsed on the host).
  * dev_data[i]: the same bytes already resident in HBM, or NULL (then they are uploaded inside the call).
  * dev_out[i]: device buffer of width*height*num_channels*bytes_per_sample bytes receiving interleaved u8 (or u16) pixels.
+ * With the option "downscale" = 8 the image is written at ceil(width/8) x ceil(height/8) pixels instead (width, height as
+ * jxlhip_peek reports them, i.e. as displayed), tight rows, same channels / sample type / colour encoding / orientation: the
+ * buffer must hold ceil(width/8)*ceil(height/8)*num_channels*bytes_per_sample bytes and nothing behind them is written.
  * Work is enqueued on `stream` (a hipStream_t, may be NULL = default stream); the call returns after
  * enqueueing unless `synchronize` is non-zero.  Per-image status is written to statuses[i] on return when
  * synchronizing, otherwise by jxlhip_finish(). */
@@ -177,7 +180,14 @@ JXLFILETYPEIO_API size_t jxlhip_read_plane(JxlHipDecoder* dec, int32_t index, co
  * 256-pixel group rows of a lossy frame into a band-sized buffer), "no_direct" / "mod_lanes64" (launch shapes of the vector loops for
  * small launches as well; same output), "no_stream_pairs" (every fused Gaborish + EPF frame through the four-pixels-per-lane kernel;
  * same output), "no_lf_pipeline" (every LF channel through the row-per-lane prediction pass instead of the register pipeline; same
- * output).  Returns 1 if the option exists and the value is valid (0: refused, nothing changed). */
+ * output), "downscale" (1 = full size, the default; 8 = every image of the next batches is decoded at 1:8: one pixel per 8x8 cell -
+ * for lossy (VarDCT) frames the LF image after dequantisation and adaptive smoothing through the colour conversion of the full
+ * decode, without Gaborish, EPF or noise, alpha as the mean of the cell; for lossless (Modular) frames the mean of the cell's
+ * output samples, integers as (sum + n/2) / n over the n pixels of the cell that exist.  The HF coefficients are not reconstructed,
+ * and for a frame without alpha not even read: host parsing is the same at both scales, so the same files are accepted and refused,
+ * but a damaged HF section of an opaque frame goes unnoticed at 1:8.  Layered files, files with patches and band decodes are refused
+ * per image at 1:8 (DecodeError); 2 and 4 are reserved and refused like any other value.  LoadImage always decodes at full size).
+ * Returns 1 if the option exists and the value is valid (0: refused, nothing changed). */
 JXLFILETYPEIO_API int32_t jxlhip_set_option(JxlHipDecoder* dec, const char* name, int32_t value);
 
 /* Timing of the last synchronised batch: milliseconds per named stage (HIP events on the decode stream). */

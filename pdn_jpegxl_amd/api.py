@@ -303,6 +303,15 @@ def peek(data):
     return info
 
 
+def reduced_size(width, height, factor):
+    """(width, height) of an image decoded with the decoder option "downscale" = factor (1 or 8): one pixel per factor x factor cell,
+    a partial cell at the right / bottom edge included.  width, height: the image as displayed, i.e. as `peek` reports it (sides
+    already swapped for orientations 5..8); so is the result."""
+    if factor not in (1, 8):
+        raise ValueError("downscale factors are 1 and 8")
+    return (int(width) + factor - 1) // factor, (int(height) + factor - 1) // factor
+
+
 def parse_check(data):
     facts = (C.c_int32 * 8)()
     err = ErrorInfo()
@@ -431,10 +440,17 @@ class Decoder:
         self.close()
 
     def set_option(self, name, value):
+        """Returns 1 when the option was set, 0 for an unknown name or a refused value (the previous value is kept).  "downscale": 1
+        (full size) or 8 - every image of the next batches is decoded at 1:8, see decode_batch."""
         return self._L.jxlhip_set_option(self._h, name.encode(), int(value))
 
     def decode_batch(self, files, dev_out_ptrs, dev_data_ptrs=None, stream=None, synchronize=True, raise_on_error=True):
-        """files: list of bytes; dev_out_ptrs: device pointers (ints); dev_data_ptrs: device pointers of resident file bytes."""
+        """files: list of bytes; dev_out_ptrs: device pointers (ints); dev_data_ptrs: device pointers of resident file bytes.
+
+        Each output buffer receives width x height pixels, tight rows, of num_channels samples of bytes_per_sample bytes, with
+        (width, height) as `peek` reports them - or, after set_option("downscale", 8), reduced_size(width, height, 8) of them: the
+        buffer must hold at least rw * rh * num_channels * bytes_per_sample bytes for (rw, rh) = reduced_size(...).  At 1:8 layered
+        files, files with patches and band decodes are refused per image (DecodeError); the other images of the batch decode."""
         n = len(files)
         hd = (C.c_char_p * n)(*files)
         sz = (C.c_size_t * n)(*[len(f) for f in files])

@@ -181,6 +181,9 @@ struct JxlHipDecoder {
   bool no_lf_pipeline = false;    // every LF channel through lf_finish_kernel's row-per-lane prediction pass (parity tests: same output either way)
   bool no_direct = false, mod_lanes64 = false;   // launch shapes of the vector loops for small launches too (parity tests: same output either way)
   bool overlap = true;
+  // reduced-size decode: 1 = full size; 8 = every image of the next batches leaves at ceil(w / 8) x ceil(h / 8), one pixel
+  // per 8x8 cell (VarDCT: the LF image; Modular: cell means of the full decode)
+  int downscale = 1;
 
   explicit JxlHipDecoder(int dev);
   ~JxlHipDecoder();
@@ -441,6 +444,17 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   std::vector<Composite> comps;
   std::vector<const uint8_t*> x_dev_data;
   std::vector<uint8_t*> x_dev_out;
+  // reduced-size decode: what it does not cover is refused per image, before anything is laid out or launched for it (crop origins and
+  // patch positions are no multiples of 8; a band is a set of full-size pixel rows)
+  const bool ds = downscale == 8;
+  if (ds)
+    for (int i = 0; i < n; i++) {
+      if (parse_status[i] != DecoderStatus_Ok) continue;
+      const char* why = nullptr;
+      if (band_rows > 0) why = "downscale 8: band decode is not supported";
+      else if (frames[i].layers) why = frames[i].layers->patches ? "downscale 8: images with patches are not supported" : "downscale 8: layered images are not supported";
+      if (why) { parse_status[i] = DecoderStatus_DecodeError; parse_msg[i] = why; }
+    }
   for (int i = 0; i < n; i++)
     if (parse_status[i] == DecoderStatus_Ok && frames[i].layers && band_rows > 0) {
       parse_status[i] = DecoderStatus_DecodeError;
@@ -525,6 +539,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     size_t lf[3], lf_tmp[3], lfq[3], lf_extra, rawq, sharp, ytox, ytob, binfo, lf_desc, lf_count, alpha_desc, blk_list, blk_count, bitpos, tile_list, tmp[3], xyb[3], inv_sigma, alpha;
     size_t orient_tmp = 0;   // frames with an orientation other than 1 are decoded here, then laid out as displayed in the caller's buffer
     size_t layer_px = 0;     // frames of a layered image: w*h*nch f32 samples for the compositor
+    size_t ds_full = 0, ds_alpha = 0;   // reduced-size decode: a Modular frame's full-size output samples / a VarDCT frame's reduced alpha plane
   };
   std::vector<PerImg> L((size_t)n);
   // blob space of a codestream uploaded from the host: once per file (every frame of a layered file points into the same bytes)
@@ -598,6 +613,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       if (f.mcode.lz77) l.lz_mod = ws.Take(nsec * ((size_t)4 << 20)) + 1;
       n_mod_tasks += f.single ? 1 : ((int)nsec + mod_lanes - 1) / mod_lanes;
       if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * (f.layer_f32 ? 4 : OutBytesPerSample(f)));
+      // reduced-size decode: the full-size output samples go to scratch, box_reduce_kernel averages them into the caller's buffer
+      if (ds) l.ds_full = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));
       continue;
     }
     l.a_cmap = blob.Take(f.acode.ctx_map.size());
@@ -624,8 +641,11 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       int b0 = 0, b1 = (int)f.yg;
       if (band_rows > 0) { b0 = std::min<int>(band_first_row, (int)f.yg); b1 = std::min<int>(b0 + band_rows, (int)f.yg); }
       const int g0 = std::max(0, b0 - 1), g1 = std::min<int>((int)f.yg, b1 + 1);
-      l.centries = ws.Take((size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4);
-      l.cblk = ws.Take(3 * cells * sizeof(U32x2));
+      // (a reduced-size decode reads the HF tokens only for what follows them in a section - the alpha channel - and keeps no coefficients
+      // of an opaque frame)
+      const bool hf = !ds || f.alpha_index >= 0;
+      l.centries = ws.Take(hf ? (size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4 : 0);
+      l.cblk = ws.Take(hf ? 3 * cells * sizeof(U32x2) : 0);
       for (auto& ep : f.extra_passes) {
         PassLayout pl;
         pl.a_cmap = blob.Take(ep.acode.ctx_map.size());
@@ -637,8 +657,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
           const int o = OrderBucketOfQuantTable(q);
           if (l.dq[q] || !ep.custom_order[o][0].empty() || !ep.custom_order[o][1].empty() || !ep.custom_order[o][2].empty()) pl.scan[q] = blob.Take(8 * 3 * (size_t)dq_n[q], 256) + 1;
         }
-        pl.centries = ws.Take((size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4);
-        pl.cblk = ws.Take(3 * cells * sizeof(U32x2));
+        pl.centries = ws.Take(hf ? (size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4 : 0);
+        pl.cblk = ws.Take(hf ? 3 * cells * sizeof(U32x2) : 0);
         pl.bitpos = ws.Take((size_t)f.ng * 8);
         pl.hf_order = blob.Take(4 * (size_t)std::max<uint32_t>(1, f.ng));
         l.extra.push_back(pl);
@@ -659,9 +679,10 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     l.bitpos = ws.Take((size_t)f.ng * 8);
     l.tile_list = ws.Take(tiles * 4);
     l.alpha32 = ws.Take(4 * (size_t)f.xsize * f.ysize);
-    chunk_pix = std::max(chunk_pix, pix);
+    if (!ds) chunk_pix = std::max(chunk_pix, pix);   // (reduced size: no reconstruction, no filters - no pixel planes)
     l.inv_sigma = ws.Take(4 * cells);
     l.alpha = ws.Take((size_t)f.xsize * f.ysize * OutBytesPerSample(f));
+    if (ds && f.alpha_index >= 0) l.ds_alpha = ws.Take(cells * OutBytesPerSample(f));
     if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));   // (never f32: checked on the host)
     l.lf_end = ws.Take(8);
     if (f.tree_uses_wp) { l.wp_lf = ws.Take((size_t)f.nlf * kWpLfInts * 4); l.wp_grp = ws.Take((size_t)f.ng * 10 * (kGroupDim + 2) * 4); }
@@ -671,7 +692,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       if (band_rows > 0) { b0 = std::min<int>(band_first_row, (int)f.yg); b1 = std::min<int>(b0 + band_rows, (int)f.yg); }
       const int g0 = std::max(0, b0 - 1), g1 = std::min<int>((int)f.yg, b1 + 1);
       total_lf += ((g1 + 7) / 8 - g0 / 8) * (int)f.xlf;
-      total_groups += (g1 - g0) * (int)f.xg * (int)f.num_passes;
+      if (!ds || f.alpha_index >= 0) total_groups += (g1 - g0) * (int)f.xg * (int)f.num_passes;
     }
   }
   // The float planes between reconstruction and the loop filters (24 B/px) are only alive while a frame is in the pixel stages:
@@ -686,7 +707,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // a frame of the batch has noise).  The random planes they are made from need none: they live in the tmp planes.
   size_t noise_pix = 0;
   for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].has_noise) noise_pix = std::max(noise_pix, (size_t)frames[i].xsize * frames[i].ysize);
+    if (parse_status[i] == DecoderStatus_Ok && frames[i].has_noise && !ds) noise_pix = std::max(noise_pix, (size_t)frames[i].xsize * frames[i].ysize);
   std::vector<size_t> chunk_noise((size_t)pixel_chunk * 3);
   if (noise_pix)
     for (int k = 0; k < pixel_chunk * 3; k++) chunk_noise[k] = ws.Take(4 * noise_pix);
@@ -708,6 +729,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     if (parse_status[i] != DecoderStatus_Ok || frames[i].orientation == 1) continue;
     const ParsedFrame& f = frames[i];
     if (band_rows > 0) { parse_status[i] = DecoderStatus_DecodeError; parse_msg[i] = "band decode of a frame with an orientation is not supported"; continue; }
+    if (ds) continue;   // lf_output_kernel / box_reduce_kernel store at the oriented position
     L[i].orient_tmp = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));
   }
   // Lane mapping of the HF kernel: one wavefront per section while every workgroup of the launch can be resident at once
@@ -905,12 +927,12 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   for (auto& im : imgs) memset(&im, 0, sizeof(DevImage));
   status_off.assign(n, 0);
   size_t lds_hf = 0, lds_hf_lanes = 0, lds_lf = 0, lds_alpha = 0;   // lds_hf: tables + lanes, the largest workgroup; lds_hf_lanes: the most lanes (global-table variant)
-  bool any_alpha = false, any_unfiltered = false, any_noise = false;
+  bool any_alpha = false, any_unfiltered = false, any_noise = false, any_vardct = false;
   int stage_mask = 0;   // LDS-tiled loop-filter stage kernels some frame of the batch needs (bit s: filter_tile_kernel<s>)
   int any_fused = 0, any_fused2 = 0;   // 1: fused frames (with a second iteration) of the two-pixels-per-lane kernels, 2: others
   int max_w = 1, max_h = 1, max_tiles = 1;
   auto tiles_of = [](const ParsedFrame& f) { return (size_t)((f.w8 + 7) / 8) * ((f.h8 + 7) / 8); };
-  size_t max_cells = 1, max_padded = 8;
+  size_t max_cells = 1, max_padded = 8, max_ds_cells = 1;   // max_ds_cells: reduced-size decode, over the frames of both kinds
   SectionTask* lf_tasks = (SectionTask*)(h_blob + off_lf_tasks);
   SectionTask* pass_tasks = (SectionTask*)(h_blob + off_pass_tasks);
   SectionTask* alpha_tasks = (SectionTask*)(h_blob + off_alpha_tasks);
@@ -1066,6 +1088,11 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       status_off[i] = l.z_status;
       d.out = f.orientation == 1 ? dev_out[i] : wr + l.orient_tmp;
       if (f.is_layer) d.out = wr + l.layer_px;
+      if (ds) {
+        d.ds = 8; d.ds_w = ((int32_t)f.xsize + 7) / 8; d.ds_h = ((int32_t)f.ysize + 7) / 8; d.ds_orient = (int32_t)f.orientation;
+        d.out = wr + l.ds_full; d.ds_out = dev_out[i];
+        max_ds_cells = std::max(max_ds_cells, (size_t)d.ds_w * d.ds_h);
+      }
       if (f.layer_f32) {   // unclamped f32 samples in the image's colour space; un-premultiply waits for the compositor
         d.out_bits = 32; d.out_float = 1; d.unpremultiply = 0;
       }
@@ -1145,13 +1172,19 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     d.status = (uint32_t*)(wz + l.z_status);
     status_off[i] = l.z_status;
     for (int c = 0; c < 3; c++) {
-      d.coef[c] = (int32_t*)(wr + chunk_coef[(size_t)(i % pixel_chunk) * 3 + c]);
       d.lf[c] = (float*)(wr + l.lf[c]); d.lf_tmp[c] = (float*)(wr + l.lf_tmp[c]); d.lfq[c] = (int32_t*)(wr + l.lfq[c]);
       d.lf_final[c] = d.skip_lf_smoothing ? d.lf[c] : d.lf_tmp[c];
+      if (ds) continue;   // no pixel planes: the image is lf_final
+      d.coef[c] = (int32_t*)(wr + chunk_coef[(size_t)(i % pixel_chunk) * 3 + c]);
       d.tmp[c] = (float*)(wr + chunk_tmp[(size_t)(i % pixel_chunk) * 3 + c]); d.xyb[c] = (float*)(wr + chunk_xyb[(size_t)(i % pixel_chunk) * 3 + c]);
       d.xyb2[c] = (float*)d.coef[c];   // the dense coefficient planes (generic path only) are dead once the frame is reconstructed
     }
-    if (f.has_noise) {
+    if (ds) {
+      d.ds = 8; d.ds_w = (int32_t)f.w8; d.ds_h = (int32_t)f.h8; d.ds_orient = (int32_t)f.orientation;
+      if (l.ds_alpha) d.ds_alpha = wr + l.ds_alpha;
+      max_ds_cells = std::max(max_ds_cells, (size_t)f.w8 * f.h8);
+    }
+    if (f.has_noise && !ds) {   // (a cell is coarser than the noise's 5x5 support: a reduced-size decode adds none)
       // the generator fills the group rows the band's 5x5 support reaches: the band's rows and one more each side, like the decode
       d.has_noise = 1; d.noise_gy0 = d.dec_gy0; d.noise_gy1 = d.dec_gy1;
       d.noise_seed[0] = f.noise_seed[0]; d.noise_seed[1] = f.noise_seed[1];
@@ -1168,8 +1201,9 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     d.grp_bitpos = (uint64_t*)(wr + l.bitpos);
     d.tile_list = (uint32_t*)(wr + l.tile_list);
     d.alpha32 = (int32_t*)(wr + l.alpha32);
-    d.centries = (uint32_t*)(wr + l.centries); d.centries_g0 = d.dec_gy0 * (int32_t)f.xg;
-    d.cblk = (U32x2*)(wr + l.cblk);
+    const bool hf = !ds || d.has_alpha;   // does hf_decode_kernel run for this frame?  (reduced size: only to find the alpha stream)
+    if (hf) { d.centries = (uint32_t*)(wr + l.centries); d.cblk = (U32x2*)(wr + l.cblk); }
+    d.centries_g0 = d.dec_gy0 * (int32_t)f.xg;
     d.inv_sigma = (float*)(wr + l.inv_sigma);
     d.alpha = wr + l.alpha;
     d.lf_end_bits = (uint64_t*)(wr + l.lf_end);
@@ -1183,6 +1217,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     if (f.tree_uses_wp) { d.wp_lf = (int32_t*)(wr + l.wp_lf); d.wp_grp = (int32_t*)(wr + l.wp_grp); d.wp_grp_ints = 10 * (kGroupDim + 2); }
     d.out = f.orientation == 1 ? dev_out[i] : wr + l.orient_tmp;
     if (f.is_layer) d.out = wr + l.layer_px;   // a frame of a layered image whose frames all replace: output-type samples
+    if (ds) d.out = d.ds_out = dev_out[i];
     // Loop-filter routing.  Frames with EPF iterations run iteration 1 (+ Gaborish when no iteration 0 has to come between them) and
     // iteration 2 in the streaming kernels: fused_gab_epf1 = 1: one kernel -> output; 2: two kernels, f32 rows (stream_mid) between
     // them.  Three iterations (distance >= 4): Gaborish and iteration 0 first, as LDS-tiled stage kernels, then the two streaming
@@ -1231,6 +1266,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     max_tiles = std::max<int>(max_tiles, (int)tiles_of(f));
     for (int st = 0; st < 4; st++) if (d.stage_on[st]) stage_mask |= 1 << st;
     any_alpha |= d.has_alpha != 0;
+    any_vardct = true;
     max_cells = std::max(max_cells, (size_t)f.w8 * f.h8);
     max_padded = std::max(max_padded, (size_t)f.w8 * f.h8 * 64);
     // LDS budgets (must mirror the carving in entropy_kernels.hip)
@@ -1288,7 +1324,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     }
     const uint32_t hg0 = (uint32_t)d.dec_gy0 * f.xg, hg1 = (uint32_t)d.dec_gy1 * f.xg;
     const uint32_t pw = (uint32_t)hf_per_wg(f);
-    for (uint32_t pass = 0; pass < f.num_passes; pass++) {
+    for (uint32_t pass = 0; pass < (hf ? f.num_passes : 0u); pass++) {
       // Sections go to lanes in order of their byte size (the TOC has it), largest first: a wavefront runs until its longest
       // section ends, so lanes of similar length finish together (the sum over wavefronts of their longest lane - the
       // wave-instructions of the launch - nearly halves for 4K frames, whose sections spread 1 : 2.2 around the mean), and the
@@ -1430,7 +1466,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   LaunchLfAns(d_imgs, (const SectionTask*)(d_blob + off_lf_ans_tasks), nlf_ans_t, lf_per_wave, lds_lf <= kLdsMax ? lds_lf : 0, direct_lf, lean_mod, s_lf);
   Mark("lf_ans", s_lf, 0);
   LaunchLfFinish(d_imgs, (const SectionTask*)(d_blob + off_lf_tasks), nlf_t, !no_lf_pipeline, s_lf);
-  LaunchHfBlockList(d_imgs, n, max_groups, s_lf);
+  if (!ds || any_alpha) LaunchHfBlockList(d_imgs, n, max_groups, s_lf);   // (the varblock lists serve hf_decode_kernel alone)
   LaunchLfPixelStages(d_imgs, n, max_cells, s_lf);
   }
   Mark("lf_finish+pixels", s_lf, 0);
@@ -1455,15 +1491,17 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
 #endif
   Mark("hf_start", s_hf, 1);
-  if (!(skip_stages & 2))
+  // Reduced-size decode: the HF tokens are read only to find what follows them in a pass-group section, i.e. for frames with alpha
+  // (their pass tasks are the only ones listed); stages that do not run leave no entry in the stage times.
+  if (!(skip_stages & 2) && (!ds || npass_t))
   LaunchHfDecode(d_imgs, (const SectionTask*)(d_blob + off_pass_tasks), npass_t, hf_waves * 64, lane_stride, hf_ring, lds_hf <= kLdsMax ? lds_hf : 0, lds_hf_lanes, s_hf);
-  Mark("hf_decode", s_hf, 1);
+  if (!ds || npass_t) Mark("hf_decode", s_hf, 1);
   // alpha follows the HF tokens in every pass-group section (its first bit is where the HF kernel stopped reading): same chain,
   // necessarily; the main stream carries nothing but the pixel stages
   if (any_alpha && !(skip_stages & 4))
     LaunchAlphaAns(d_imgs, (const SectionTask*)(d_blob + off_alpha_tasks), nalpha_t, alpha_stride, lds_alpha <= kLdsMax ? lds_alpha : 0, direct_alpha, lean_mod, s_hf);
-  Mark("alpha_ans", s_hf, 1);
-  if (debug_taps) {   // the quantised coefficients as dense planes (every frame has its own planes in this mode)
+  if (!ds || any_alpha) Mark("alpha_ans", s_hf, 1);
+  if (debug_taps && !ds) {   // the quantised coefficients as dense planes (every frame has its own planes in this mode)
     taps.assign(n, Tap());
     LaunchExpandCoefficients(d_imgs, n, true, max_tiles, stream);
     HIP_OK(hipStreamSynchronize(stream));
@@ -1475,7 +1513,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   const bool finish_on_hf = s_hf == stream || debug_taps || !Knob("JXLHIP_ALPHA_FINISH_ON_PIX");
   if (finish_on_hf) {
     if (any_alpha && !(skip_stages & 4)) LaunchAlphaFinish(d_imgs, n, max_groups, s_hf);
-    Mark("alpha_finish", s_hf, 1);
+    if (!ds || any_alpha) Mark("alpha_finish", s_hf, 1);
   }
   if (s_hf != stream) {
     HIP_OK(hipEventRecord(S.hf_done, s_hf));
@@ -1488,7 +1526,13 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
   // experiment knob: the pixel stages behind the HF chain on ITS stream (no overlap between a batch's pixels and the next batch's HF decode)
   hipStream_t s_pix = pix_on_hf ? s_hf : stream;
-  for (int c0 = 0; c0 < n; c0 += pixel_chunk) {
+  if (ds && any_vardct) {
+    // the whole pixel stage of a reduced-size decode: no reconstruction, no noise, no filters, and every image in one launch
+    if (any_alpha) LaunchAlphaReduce(d_imgs, n, max_ds_cells, s_pix);
+    LaunchLfOutput(d_imgs, n, max_ds_cells, s_pix);
+    Mark("lf_output", s_pix, 2);
+  }
+  for (int c0 = 0; c0 < (ds ? 0 : n); c0 += pixel_chunk) {
     const int cnt = std::min(pixel_chunk, n - c0);
     if (!(skip_stages & 8))
     LaunchReconTiles(d_imgs + c0, cnt, max_tiles, d_basis_all, d_basis_small, d_llf_scale, d_basis_mfma, s_pix);
@@ -1518,6 +1562,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       else LaunchModularOp(op.kind, op.a, op.b, op.c, op.aw, op.ah, op.rw, op.rh, op.type, stream);
     }
     LaunchModularOut(d_imgs, n, max_mod_pixels, stream);
+    if (ds) LaunchBoxReduce(d_imgs, n, max_ds_cells, stream);
     Mark("modular", stream, 2);
   }
   if (!patch_tiles.empty()) {
@@ -1532,7 +1577,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     Mark("compose", stream, 2);
   }
   for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].orientation != 1) {
+    if (parse_status[i] == DecoderStatus_Ok && frames[i].orientation != 1 && !ds) {
       const ParsedFrame& f = frames[i];
       LaunchOrient(imgs[i].out, dev_out[i], (int)f.xsize, (int)f.ysize, (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * (int)OutBytesPerSample(f),
                    (int)f.orientation, stream);
@@ -1548,7 +1593,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (sync) {
     DecoderStatus st = Finish(statuses, err);
     (void)st;
-    if (debug_taps) CopyPlaneTap(2);
+    if (debug_taps && !ds) CopyPlaneTap(2);
   } else if (statuses) {
     for (int i = 0; i < S.nfiles; i++) statuses[i] = DecoderStatus_Ok;
     for (int i = n - 1; i >= 0; i--) {   // a file's first failing image wins
@@ -1817,6 +1862,8 @@ int32_t jxlhip_set_option(JxlHipDecoder* dec, const char* name, int32_t value) {
   if (!strcmp(name, "no_lf_pipeline")) { dec->no_lf_pipeline = value != 0; return 1; }
   if (!strcmp(name, "mod_lanes64")) { dec->mod_lanes64 = value != 0; return 1; }
   if (!strcmp(name, "overlap")) { dec->overlap = value != 0; return 1; }
+  // 1: full size; 8: the next batches are decoded at 1:8 (2 and 4 are reserved: they need reduced inverse transforms)
+  if (!strcmp(name, "downscale")) { if (value != 1 && value != 8) return 0; dec->downscale = value; return 1; }
   return 0;
 }
 

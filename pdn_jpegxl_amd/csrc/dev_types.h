@@ -221,6 +221,13 @@ struct DevImage {
   float noise_lut[8];
   float* noise_rnd[3];      // R_k: w*h, tight rows (they live in the tmp planes, dead once the frame is reconstructed)
   float* noise[3];          // N_k: w*h, tight rows
+  // Reduced-size decode (decoder option "downscale" = 8): the image leaves as ds_w x ds_h = ceil(w / 8) x ceil(h / 8)
+  // pixels, one per 8x8 cell, in the layout of the full decode.  VarDCT frames: lf_output_kernel converts lf_final (and ds_alpha, the
+  // cell means of the alpha plane from alpha_reduce_kernel); Modular frames: `out` is a full-size scratch image that box_reduce_kernel
+  // averages.  Both write ds_out, the caller's buffer, with the orientation applied (ds_orient, 1..8; sides swapped for 5..8).
+  int32_t ds, ds_w, ds_h, ds_orient;   // ds: 0 (full size) or 8
+  uint8_t* ds_alpha;        // ds_w*ds_h samples of the output type
+  uint8_t* ds_out;          // ds_w*ds_h*nch_out interleaved samples of the output type
 };
 
 // Layered images (compose_kernel, compose_kernels.hip): every frame is decoded on its own into f32 scratch, then one launch blends

@@ -13,6 +13,23 @@ __host__ __device__ __forceinline__ int ReflectIndex(int v, int n) {
   return v;
 }
 
+// Position in the displayed image of sample (x, y) of a w x h image stored in codestream orientation, for EXIF orientation o (1..8):
+// index into tight rows of w (o <= 4) or h (o >= 5) samples.  The inverse of orient_kernel's mapping (kernels.hip).
+__host__ __device__ __forceinline__ size_t OrientedIndex(int o, int x, int y, int w, int h) {
+  int ox, oy;
+  switch (o) {
+    case 2: ox = w - 1 - x; oy = y; break;
+    case 3: ox = w - 1 - x; oy = h - 1 - y; break;
+    case 4: ox = x; oy = h - 1 - y; break;
+    case 5: ox = y; oy = x; break;
+    case 6: ox = h - 1 - y; oy = x; break;
+    case 7: ox = h - 1 - y; oy = w - 1 - x; break;
+    case 8: ox = y; oy = w - 1 - x; break;
+    default: ox = x; oy = y; break;
+  }
+  return (size_t)oy * (size_t)(o >= 5 ? h : w) + (size_t)ox;
+}
+
 // Context offset of the HF coefficient tokens for the predicted non-zero count nzl in [0, 63]: a step function with eight values
 // (0, 31, 62, 93, 123, 152, 180, 206) and thresholds at 2, 3, 5, 9, 13, 21 and 33, computed in registers so that the batched HF
 // token loop has no table lookup in front of its context-map read.  The CPU suite checks all 64 inputs through

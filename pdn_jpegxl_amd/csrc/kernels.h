@@ -41,6 +41,13 @@ void LaunchReconTiles(const DevImage* imgs, int nimg, int max_tiles, const float
 void LaunchFilterTiles(const DevImage* imgs, int nimg, int max_w, int max_h, int stage_mask, bool any_unfiltered,
                        int any_fused, int any_fused2, hipStream_t s);
 
+// Reduced-size decode (DevImage::ds; images without it return at once).  tile_kernels.hip: the LF planes (+ reduced alpha) of VarDCT
+// frames -> output samples; downscale_kernels.hip: cell means of the alpha planes of VarDCT frames / of the full-size output samples of
+// Modular frames.  max_cells: the most 8x8 cells of an image of the launch.
+void LaunchLfOutput(const DevImage* imgs, int nimg, size_t max_cells, hipStream_t s);
+void LaunchAlphaReduce(const DevImage* imgs, int nimg, size_t max_cells, hipStream_t s);
+void LaunchBoxReduce(const DevImage* imgs, int nimg, size_t max_cells, hipStream_t s);
+
 // noise_kernels.hip: frames with synthetic noise (the others return at once): the random planes of their decoded group rows, then the
 // 5x5 convolution of the band's pixel rows into the planes the output phase of the filter kernels adds
 void LaunchNoise(const DevImage* imgs, int nimg, int max_groups, int max_w, int max_h, hipStream_t s);

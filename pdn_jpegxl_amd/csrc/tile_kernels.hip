@@ -15,6 +15,8 @@
 //   filter_tile_kernel    one Gaborish / EPF stage on a 64x32 tile + halo staged in LDS (mirrored at the frame edge); the LAST
 //                         enabled stage of an image converts XYB -> output samples and merges alpha.  Used for frames without EPF
 //                         (Gaborish alone), for Gaborish and iteration 0 of three-iteration frames, and for the stage taps.
+//   lf_output_kernel      reduced-size decode (1:8): the LF planes through the same pixel writers, one pixel per 8x8 cell; none of
+//                         the kernels above runs for such a batch.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "dev_types.h"
@@ -147,8 +149,11 @@ __device__ __forceinline__ uint8_t ToU8T(float v) {   // round half up, clamped;
 __device__ __forceinline__ uint32_t LoadAlpha(const DevImage& im, size_t i) {
   return im.out_bits == 8 ? (uint32_t)im.alpha[i] : (im.out_bits == 16 ? (uint32_t)((const uint16_t*)im.alpha)[i] : ((const uint32_t*)im.alpha)[i]);
 }
-// `a`: the pixel's alpha sample (ignored by layouts without alpha), fetched by the caller ahead of the arithmetic
-__device__ __forceinline__ void WritePixelA(const DevImage& im, int x, int y, float X, float Y, float B, uint32_t a) {
+// `a`: the pixel's alpha sample (ignored by layouts without alpha), fetched by the caller ahead of the arithmetic; `position()`: the
+// pixel's index in the output buffer (the full-size writers address it by the frame's geometry, lf_output_kernel by the reduced
+// one), evaluated after the arithmetic
+template <typename Position>
+__device__ __forceinline__ void WritePixelAt(const DevImage& im, Position position, float X, float Y, float B, uint32_t a) {
   const float gr = Y + X - im.opsin_bias_cbrt[0], gg = Y - X - im.opsin_bias_cbrt[1], gb = B - im.opsin_bias_cbrt[2];
   const float mr = gr * gr * gr + im.opsin_bias[0], mg = gg * gg * gg + im.opsin_bias[1], mb = gb * gb * gb + im.opsin_bias[2];
   float r = im.opsin_inv[0] * mr + im.opsin_inv[1] * mg + im.opsin_inv[2] * mb;
@@ -165,7 +170,7 @@ __device__ __forceinline__ void WritePixelA(const DevImage& im, int x, int y, fl
     const float m = 1.0f / fmaxf(1.0f / 67108864.0f, (float)a * im.alpha_unit);
     r *= m; g *= m; bl *= m;
   }
-  const size_t o = (size_t)(y - im.band_y0) * im.w + x;        // position in the output band
+  const size_t o = position();
   if (im.out_bits != 8) {   // u16 above 8 bits per sample, f16 / f32 for float samples (Decoder/JxlDecoder.cpp:510-548); `a` is raw bits
     const size_t b = o * im.nch_out;
     if (im.ncolor == 3) {
@@ -192,6 +197,9 @@ __device__ __forceinline__ void WritePixelA(const DevImage& im, int x, int y, fl
       if (im.has_alpha) out[1] = (uint8_t)a;
     }
   }
+}
+__device__ __forceinline__ void WritePixelA(const DevImage& im, int x, int y, float X, float Y, float B, uint32_t a) {
+  WritePixelAt(im, [&] { return (size_t)(y - im.band_y0) * im.w + x; }, X, Y, B, a);   // position in the output band
 }
 // The common layouts (u8 samples, sRGB or linear transfer) without the branches of the general function: used by the fused filter
 // kernel, whose output phase is a large part of its time.
@@ -1329,6 +1337,61 @@ __global__ void out_only_kernel(const DevImage* __restrict__ imgs) {
     const size_t o = (size_t)y * wp + x;
     WritePixel(im, x, y, im.stage_in[4][0][o], im.stage_in[4][1][o], im.stage_in[4][2][o]);
   }
+}
+
+// Reduced-size decode (DevImage::ds): output pixel (cx, cy) is the LF sample of cell (cx, cy) - lf_final after
+// dequantisation and adaptive smoothing - through the conversions of the full decode: PixelToRgba8 for the plain 8-bit layouts,
+// WritePixelAt for everything else.  No Gaborish, EPF or noise.  Alpha: the cell means alpha_reduce_kernel left in ds_alpha.
+// The planes and the output have tight rows, so an un-oriented image is one run of ds_w * ds_h pixels: plain RGBA / RGB output takes
+// four pixels per lane (three 16-byte loads, one 16- or 12-byte store; a wavefront stores 1 KiB / 768 B without a gap), the tail of up
+// to three pixels and every other layout or orientation one pixel per lane, stored at its oriented position.
+__device__ __forceinline__ void LfOutputPixel(const DevImage& im, size_t i, float X, float Y, float B) {
+  const int cx = (int)(i % (size_t)im.ds_w), cy = (int)(i / (size_t)im.ds_w);
+  const size_t o = OrientedIndex(im.ds_orient, cx, cy, im.ds_w, im.ds_h);
+  const uint32_t a = !im.has_alpha ? 0u : (im.out_bits == 8 ? (uint32_t)im.ds_alpha[i] : (im.out_bits == 16 ? (uint32_t)((const uint16_t*)im.ds_alpha)[i]
+                                                                                                              : ((const uint32_t*)im.ds_alpha)[i]));
+  if (PlainOutput(im)) {
+    const uint32_t px = PixelToRgba8(im, X, Y, B, a);
+    uint8_t* out = im.out + o * im.nch_out;
+    if (im.nch_out == 4) *(uint32_t*)out = px;
+    else if (im.nch_out == 3) { out[0] = (uint8_t)px; out[1] = (uint8_t)(px >> 8); out[2] = (uint8_t)(px >> 16); }
+    else { out[0] = (uint8_t)(px >> 8); if (im.nch_out == 2) out[1] = (uint8_t)(px >> 24); }
+    return;
+  }
+  WritePixelAt(im, [&] { return o; }, X, Y, B, a);
+}
+__global__ __launch_bounds__(256) void lf_output_kernel(const DevImage* __restrict__ imgs) {
+  const DevImage& im = imgs[blockIdx.y];
+  if (!im.ds || im.is_modular) return;
+  const size_t n = (size_t)im.ds_w * im.ds_h;
+  const float* __restrict__ pX = im.lf_final[0];
+  const float* __restrict__ pY = im.lf_final[1];
+  const float* __restrict__ pB = im.lf_final[2];
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const bool quads = PlainOutput(im) && im.ds_orient == 1 && im.ncolor == 3 && ((uintptr_t)im.out & 15) == 0;
+  if (!quads) {
+    for (size_t i = gid; i < n; i += stride) LfOutputPixel(im, i, pX[i], pY[i], pB[i]);
+    return;
+  }
+  const size_t nq = n >> 2;
+  for (size_t q = gid; q < nq; q += stride) {
+    const float4 X = ((const float4*)pX)[q], Y = ((const float4*)pY)[q], B = ((const float4*)pB)[q];
+    const uint32_t a = im.has_alpha ? ((const uint32_t*)im.ds_alpha)[q] : 0u;
+    const uint32_t p0 = PixelToRgba8(im, X.x, Y.x, B.x, a & 0xFF), p1 = PixelToRgba8(im, X.y, Y.y, B.y, (a >> 8) & 0xFF);
+    const uint32_t p2 = PixelToRgba8(im, X.z, Y.z, B.z, (a >> 16) & 0xFF), p3 = PixelToRgba8(im, X.w, Y.w, B.w, a >> 24);
+    if (im.nch_out == 4) ((uint4*)im.out)[q] = make_uint4(p0, p1, p2, p3);
+    else ((uint3*)im.out)[q] = make_uint3((p0 & 0xFFFFFFu) | (p1 << 24), ((p1 >> 8) & 0xFFFFu) | (p2 << 16), ((p2 >> 16) & 0xFFu) | (p3 << 8));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const size_t i = 4 * nq + threadIdx.x;
+    LfOutputPixel(im, i, pX[i], pY[i], pB[i]);
+  }
+}
+
+void LaunchLfOutput(const DevImage* imgs, int nimg, size_t max_cells, hipStream_t s) {
+  if (nimg <= 0) return;
+  const size_t b = std::min<size_t>((max_cells + 255) / 256, 2048);
+  hipLaunchKernelGGL(lf_output_kernel, dim3((unsigned)std::max<size_t>(1, b), nimg), dim3(256), 0, s, imgs);
 }
 
 void LaunchReconTiles(const DevImage* imgs, int nimg, int max_tiles, const float* basis_all, const float* basis_small,
