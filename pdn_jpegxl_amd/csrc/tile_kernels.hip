@@ -750,9 +750,20 @@ __device__ __forceinline__ float DppFromRight(float v) {   // value of lane + 1 
 __device__ __forceinline__ F4 ShiftFromLeft(F4 v) { return F4{DppFromLeft(v.w), v.x, v.y, v.z}; }      // element x - 1
 __device__ __forceinline__ F4 ShiftFromRight(F4 v) { return F4{v.y, v.z, v.w, DppFromRight(v.x)}; }    // element x + 1
 __device__ __forceinline__ F4 ShiftFromLeft2(F4 v) { return F4{DppFromLeft(v.z), DppFromLeft(v.w), v.x, v.y}; }   // element x - 2
-__device__ __forceinline__ F4 Abs4(F4 v) { return F4{fabsf(v.x), fabsf(v.y), fabsf(v.z), fabsf(v.w)}; }
+__device__ __forceinline__ F4 Abs(F4 v) { return F4{fabsf(v.x), fabsf(v.y), fabsf(v.z), fabsf(v.w)}; }
+// The two-pixels-per-lane forms (filter_stream_pairs_kernel, filter_stream2_pairs_kernel) run the same arithmetic on F2
+typedef float __attribute__((ext_vector_type(2))) F2;
+typedef unsigned __attribute__((ext_vector_type(2))) U2v;
+__device__ __forceinline__ F2 ShiftFromLeft(F2 v) { return F2{DppFromLeft(v.y), v.x}; }
+__device__ __forceinline__ F2 ShiftFromRight(F2 v) { return F2{v.y, DppFromRight(v.x)}; }
+__device__ __forceinline__ F2 ShiftFromLeft2(F2 v) { return F2{DppFromLeft(v.x), DppFromLeft(v.y)}; }
+__device__ __forceinline__ F2 Abs(F2 v) { return F2{fabsf(v.x), fabsf(v.y)}; }
 
-struct Row3 { F4 c[3]; };
+// The lane's pixels (V = F4: a quad, F2: a pair) of one row of the three planes
+template <typename V> struct RowOf { V c[3]; };
+template <typename V> constexpr int kLanePixels = sizeof(V) / sizeof(float);
+typedef RowOf<F4> Row3;
+typedef RowOf<F2> PairRow;
 #define JXL_GLOBAL __attribute__((address_space(1)))
 // Quad (X .. X + 3) of row y of the three planes; rows and columns outside the frame are mirrored like the unfused stages do.
 __device__ __forceinline__ Row3 LoadRow3(const JXL_GLOBAL float* p0, const JXL_GLOBAL float* p1, const JXL_GLOBAL float* p2, int X, int y, int w, int h,
@@ -774,10 +785,185 @@ __device__ __forceinline__ Row3 LoadRow3(const JXL_GLOBAL float* p0, const JXL_G
 // Rolling windows of one lane, as four slots each, indexed by (row & 3) with COMPILE-TIME phases (the row loop is unrolled by four):
 // no register moves to shift a window.  in / s: input rows and their horizontal neighbour sums; g: Gaborish rows; dv / dh: vertical /
 // horizontal channel-weighted differences of Gaborish rows; hd: dv[x-1] + dv[x+1].
-struct StreamState {
-  Row3 in[4], s[4], g[4];
-  F4 dv[4], dh[4], hd[4];
+template <typename V> struct Windows {
+  RowOf<V> in[4], s[4], g[4];
+  V dv[4], dh[4], hd[4];
 };
+typedef Windows<F4> StreamState;
+typedef Windows<F2> PairState;
+template <typename V>
+__device__ __forceinline__ void ZeroWindows(Windows<V>& st) {
+  const V zero = V(0.f);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) { st.in[i].c[c] = zero; st.s[i].c[c] = zero; st.g[i].c[c] = zero; }
+    st.dv[i] = zero; st.dh[i] = zero; st.hd[i] = zero;
+  }
+}
+// What the arithmetic of a Gaborish + EPF-1 row needs besides the windows; both forms' constants start with it
+struct RowConst {
+  float gw0[3], gw1[3], gw2[3], cs[3], bsm;
+  int y0, y1;   // output rows of the lane's segment
+};
+__device__ __forceinline__ void FillRowConst(const DevImage& im, RowConst& k) {
+  const bool no_gab = im.stream_no_gab != 0;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    // without Gaborish the kernel's weights are the identity: x * 1 + a * 0 + b * 0 is x exactly for finite planes
+    k.gw0[c] = no_gab ? 1.0f : im.gab_w[c][0]; k.gw1[c] = no_gab ? 0.0f : im.gab_w[c][1]; k.gw2[c] = no_gab ? 0.0f : im.gab_w[c][2];
+    k.cs[c] = im.epf_channel_scale[c];
+  }
+  k.bsm = im.epf_border_sad_mul;
+}
+// The lane's vector of 1 / sigma terms: inv_b for a first / last pixel that lies in a block-border column, inv_in elsewhere
+template <typename V>
+__device__ __forceinline__ V BorderInv(float inv_in, float inv_b, bool xb_first, bool xb_last) {
+  V inv = V(inv_in);
+  inv[0] = xb_first ? inv_b : inv_in; inv[kLanePixels<V> - 1] = xb_last ? inv_b : inv_in;
+  return inv;
+}
+
+// The arithmetic of one input row r = y + 3 (phase P = (r - first row) & 3), for any lane vector (used by the two-pixel form; the four-pixel
+// form keeps a copy, see StreamRow): Gaborish row r - 1, differences, and, when
+// y is a row of the lane's segment (the function then returns true), EPF pass 1 of the output row y into o[].  `cur`: input row r;
+// `is`: 1 / sigma of row y's cell; xb_first / xb_last: the lane's first / last pixel lies in the first / last column of an 8x8 block.
+// (Operand order and grouping of the floating-point expressions are part of the result: leave them as they are.)
+template <int P, typename V>
+__device__ __forceinline__ bool GabEpf1Row(const RowOf<V>& cur, Windows<V>& st, const RowConst& k, float is, int y, bool xb_first, bool xb_last,
+                                           V o[3]) {
+  constexpr int s0 = P, s1 = (P + 1) & 3, s2 = (P + 2) & 3, s3 = (P + 3) & 3;   // slots of rows r (= r - 4), r - 3, r - 2, r - 1
+  const V zero = V(0.f);
+  V dhn = zero, dvn = zero;
+  st.in[s0] = cur;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    st.s[s0].c[c] = ShiftFromLeft(cur.c[c]) + ShiftFromRight(cur.c[c]);
+    // Gaborish of row r - 1 from input rows r - 2, r - 1, r
+    const V gn = st.in[s3].c[c] * k.gw0[c] + ((st.in[s2].c[c] + cur.c[c]) + st.s[s3].c[c]) * k.gw1[c] + (st.s[s2].c[c] + st.s[s0].c[c]) * k.gw2[c];
+    dhn += Abs(gn - ShiftFromRight(gn)) * k.cs[c];      // dh[r-1][x] = sum_c scale_c |gab[x] - gab[x + 1]|
+    dvn += Abs(st.g[s2].c[c] - gn) * k.cs[c];            // dv[r-2][x] = sum_c scale_c |gab[r-2] - gab[r-1]|
+    st.g[s3].c[c] = gn;
+  }
+  // now: g[s0] = gab[r-4], g[s1] = gab[r-3], g[s2] = gab[r-2]; dv[s3] = dv[r-5], dv[s0] = dv[r-4], dv[s1] = dv[r-3]; dh[s0..s2] = dh[r-4..r-2]
+  const V dv0 = st.dv[s3], dv1 = st.dv[s0], dv2 = st.dv[s1];
+  const V hd2 = ShiftFromLeft(dv2) + ShiftFromRight(dv2);    // dv[y][x-1] + dv[y][x+1]
+  const V hd1 = st.hd[s0];
+  const bool output_row = y >= k.y0 && y < k.y1;   // uniform over the wavefront (four pixels per lane: except in a shorter last segment)
+  if (output_row) {
+    // EPF pass 1 of row y: neighbours up / left / right / down, SAD over the plus-shaped support
+    const V dh0 = st.dh[s0], dh1 = st.dh[s1], dh2 = st.dh[s2];
+    const V a = dv1 + dv2;
+    const V sad_u = a + dv0 + hd1, sad_d = a + dvn + hd2;
+    const V vh = dh0 + dh1 + dh2;
+    const V sad_r = vh + (ShiftFromLeft(dh1) + ShiftFromRight(dh1));
+    const V sad_l = ShiftFromLeft(vh) + (ShiftFromLeft2(dh1) + dh1);
+    const bool yb = ((y & 7) == 0) || ((y & 7) == 7);
+    const V inv = BorderInv<V>(is * (yb ? k.bsm : 1.0f), is * k.bsm, xb_first, xb_last);
+    const bool skip = is < -3.90524291751269967465540850526868f;
+    V wu, wl, wr, wd, iw;
+#pragma unroll
+    for (int j = 0; j < kLanePixels<V>; j++) {
+      wu[j] = fmaxf(0.f, 1.0f + sad_u[j] * inv[j]); wl[j] = fmaxf(0.f, 1.0f + sad_l[j] * inv[j]);
+      wr[j] = fmaxf(0.f, 1.0f + sad_r[j] * inv[j]); wd[j] = fmaxf(0.f, 1.0f + sad_d[j] * inv[j]);
+      iw[j] = __builtin_amdgcn_rcpf(1.0f + wu[j] + wl[j] + wr[j] + wd[j]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const V g1 = st.g[s1].c[c];
+      const V f = (g1 + wu * st.g[s0].c[c] + wl * ShiftFromLeft(g1) + wr * ShiftFromRight(g1) + wd * st.g[s2].c[c]) * iw;
+      o[c] = skip ? g1 : f;
+    }
+  }
+  st.dv[s2] = dvn;   // dv[r-2]
+  st.dh[s3] = dhn;   // dh[r-1]
+  st.hd[s1] = hd2;   // of dv[r-3]: next row's hd1
+  return output_row;
+}
+// The arithmetic of one row y of the second EPF iteration, for both forms: three rows of the first iteration's output, four neighbours,
+// a one-pixel SAD.  cs: channel scales; sm / smb: the iteration's sigma scale, and the same times the border multiplier.
+template <typename V>
+__device__ __forceinline__ void Epf2Row(const RowOf<V>& prev, const RowOf<V>& cur, const RowOf<V>& next, const float (&cs)[3], float sm, float smb,
+                                        float is, int y, bool xb_first, bool xb_last, V o[3]) {
+  const V zero = V(0.f);
+  V su = zero, sd = zero, sl = zero, sr = zero;
+  V lft[3], rgt[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    lft[c] = ShiftFromLeft(cur.c[c]); rgt[c] = ShiftFromRight(cur.c[c]);
+    su += Abs(cur.c[c] - prev.c[c]) * cs[c]; sd += Abs(cur.c[c] - next.c[c]) * cs[c];
+    sl += Abs(cur.c[c] - lft[c]) * cs[c]; sr += Abs(cur.c[c] - rgt[c]) * cs[c];
+  }
+  const bool yb = ((y & 7) == 0) || ((y & 7) == 7);
+  const V inv = BorderInv<V>(is * (yb ? smb : sm), is * smb, xb_first, xb_last);
+  const bool skip = is < -3.90524291751269967465540850526868f;
+  V wu, wl, wr, wd, iw;
+#pragma unroll
+  for (int j = 0; j < kLanePixels<V>; j++) {
+    wu[j] = fmaxf(0.f, 1.0f + su[j] * inv[j]); wl[j] = fmaxf(0.f, 1.0f + sl[j] * inv[j]);
+    wr[j] = fmaxf(0.f, 1.0f + sr[j] * inv[j]); wd[j] = fmaxf(0.f, 1.0f + sd[j] * inv[j]);
+    iw[j] = __builtin_amdgcn_rcpf(1.0f + wu[j] + wl[j] + wr[j] + wd[j]);
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const V f = (cur.c[c] + wu * prev.c[c] + wl * lft[c] + wr * rgt[c] + wd * next.c[c]) * iw;
+    o[c] = skip ? cur.c[c] : f;
+  }
+}
+
+// Which strip and segment a lane works on (filter_stream_kernel decodes the same way, in its own words: see StreamRow).  A wavefront is a strip of 64 lanes with `px` pixels each, of
+// which `halo` lanes at each end only feed their neighbours: out_cols = px * (64 - 2 * halo) output columns.  A strip walks down a
+// segment of kSegRows rows of the band [band_lo, band_hi).
+struct StripTask {
+  bool stores;      // this lane stores its pixels (a lane of a wavefront with a task of its own, not a halo lane, inside the frame)
+  int q;            // the lane's index in the strip
+  int X, y0, y1;    // first column of the lane's pixels (may lie outside the frame); rows of the segment
+};
+// `wave`: the wavefront's index in the workgroup.  False: the whole workgroup is past the end.  Every lane of a workgroup with a task stays
+// in the row loop (DPP reads neighbouring lanes): wavefronts past the end repeat the last task and store nothing.
+__device__ __forceinline__ bool GetStripTask(int wave, int w, int band_lo, int band_hi, int out_cols, int halo, int px, StripTask& t) {
+  const int strips = (w + out_cols - 1) / out_cols;
+  const int segs = (band_hi - band_lo + kSegRows - 1) / kSegRows;
+  if ((int)blockIdx.x * kGroupsPerWg >= strips * segs) return false;
+  const int gidx = blockIdx.x * kGroupsPerWg + wave;
+  const bool task = gidx < strips * segs;
+  const int gi = task ? gidx : strips * segs - 1;
+  const int strip = gi % strips, seg = gi / strips;
+  t.q = threadIdx.x & (kStripLanes - 1);
+  t.X = strip * out_cols - halo * px + px * t.q;
+  t.y0 = band_lo + seg * kSegRows; t.y1 = min(t.y0 + kSegRows, band_hi);
+  t.stores = task && t.q >= halo && t.q <= kStripLanes - 1 - halo && t.X < w;
+  return true;
+}
+
+// Alpha of the quad at p, packed (the plain layouts of the four-pixel kernels)
+__device__ __forceinline__ uint32_t LoadAlphaQuad(const JXL_GLOBAL uint8_t* ap) {
+  return (uint32_t)ap[0] | (uint32_t)ap[1] << 8 | (uint32_t)ap[2] << 16 | (uint32_t)ap[3] << 24;
+}
+// The output block of the four-pixel kernels (StreamRow holds its own copy): quad X .. X + 3 of row y.  Whole RGBA quads of the plain layouts (`fast`) leave as one
+// 16-byte store with the packed alpha quad `al`; everything else pixel by pixel through the general writer.
+__device__ __forceinline__ void StoreQuad(const DevImage& im, const F4 (&o)[3], uint32_t al, int X, int y, int w, bool fast) {
+  if (fast) {
+    typedef unsigned __attribute__((ext_vector_type(4))) U4v;
+    U4v px;
+    px.x = PixelToRgba8(im, o[0].x, o[1].x, o[2].x, al & 0xFF);
+    px.y = PixelToRgba8(im, o[0].y, o[1].y, o[2].y, (al >> 8) & 0xFF);
+    px.z = PixelToRgba8(im, o[0].z, o[1].z, o[2].z, (al >> 16) & 0xFF);
+    px.w = PixelToRgba8(im, o[0].w, o[1].w, o[2].w, al >> 24);
+    *(JXL_GLOBAL U4v*)((JXL_GLOBAL uint8_t*)im.out + ((size_t)(y - im.band_y0) * w + X) * 4) = px;
+  } else {
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) {
+      if (X + j >= w) break;
+      const uint32_t aj = !im.has_alpha ? 0u : LoadAlpha(im, (size_t)y * w + X + j);   // (the packed quad `al` is only valid for whole quads)
+      const float ox = j == 0 ? o[0].x : (j == 1 ? o[0].y : (j == 2 ? o[0].z : o[0].w));
+      const float oy = j == 0 ? o[1].x : (j == 1 ? o[1].y : (j == 2 ? o[1].z : o[1].w));
+      const float ob = j == 0 ? o[2].x : (j == 1 ? o[2].y : (j == 2 ? o[2].z : o[2].w));
+      WritePixelGeneral(im, X + j, y, ox, oy, ob, aj);
+    }
+  }
+}
+
 struct StreamConst {
   const JXL_GLOBAL float *in0, *in1, *in2, *inv_sigma;
   const JXL_GLOBAL uint8_t* alpha;
@@ -788,7 +974,12 @@ struct StreamConst {
   bool to_float;
 };
 
-// One input row r (phase P = (r - first row) & 3): Gaborish row r - 1, differences, and the output row r - 3.
+// One input row r (phase P = (r - first row) & 3) of the four-pixel form: Gaborish row r - 1, differences, and the output row r - 3.
+// The arithmetic is GabEpf1Row's, written out a second time ON PURPOSE, like the set-up in filter_stream_kernel below (task decoding,
+// weights, zeroed windows, output block): this kernel sits at 251 registers, two wavefronts per SIMD, and every way of calling the shared
+// pieces tried so far moved its allocation (244 .. 256 registers, one with scratch) - through GabEpf1Row it measured 1.3 % slower
+// (profiles/shared_bodies_filter_layouts.txt).  As written here its code is the same instruction for instruction as before the bodies
+// were shared.  A change to the filter goes into GabEpf1Row AND here; tests/test_gpu_parity.py holds the two forms to identical bytes.
 template <int P>
 __device__ __forceinline__ void StreamRow(const DevImage& im, const StreamConst& k, StreamState& st, Row3& next, int r) {
   constexpr int s0 = P, s1 = (P + 1) & 3, s2 = (P + 2) & 3, s3 = (P + 3) & 3;   // slots of rows r (= r - 4), r - 3, r - 2, r - 1
@@ -799,10 +990,7 @@ __device__ __forceinline__ void StreamRow(const DevImage& im, const StreamConst&
   const int yc = min(max(y, 0), k.h - 1);
   const float is = k.inv_sigma[(size_t)(yc >> 3) * k.w8 + k.cellx];
   uint32_t al = 0xFFFFFFFFu;
-  if (im.has_alpha && k.plain) {
-    const JXL_GLOBAL uint8_t* ap = k.alpha + (size_t)yc * k.w + k.xa;
-    al = (uint32_t)ap[0] | (uint32_t)ap[1] << 8 | (uint32_t)ap[2] << 16 | (uint32_t)ap[3] << 24;
-  }
+  if (im.has_alpha && k.plain) al = LoadAlphaQuad(k.alpha + (size_t)yc * k.w + k.xa);
   const F4 zero = {0.f, 0.f, 0.f, 0.f};
   F4 dhn = zero, dvn = zero;
   st.in[s0] = cur;
@@ -811,8 +999,8 @@ __device__ __forceinline__ void StreamRow(const DevImage& im, const StreamConst&
     st.s[s0].c[c] = ShiftFromLeft(cur.c[c]) + ShiftFromRight(cur.c[c]);
     // Gaborish of row r - 1 from input rows r - 2, r - 1, r
     const F4 gn = st.in[s3].c[c] * k.gw0[c] + ((st.in[s2].c[c] + cur.c[c]) + st.s[s3].c[c]) * k.gw1[c] + (st.s[s2].c[c] + st.s[s0].c[c]) * k.gw2[c];
-    dhn += Abs4(gn - ShiftFromRight(gn)) * k.cs[c];      // dh[r-1][x] = sum_c scale_c |gab[x] - gab[x + 1]|
-    dvn += Abs4(st.g[s2].c[c] - gn) * k.cs[c];            // dv[r-2][x] = sum_c scale_c |gab[r-2] - gab[r-1]|
+    dhn += Abs(gn - ShiftFromRight(gn)) * k.cs[c];      // dh[r-1][x] = sum_c scale_c |gab[x] - gab[x + 1]|
+    dvn += Abs(st.g[s2].c[c] - gn) * k.cs[c];            // dv[r-2][x] = sum_c scale_c |gab[r-2] - gab[r-1]|
     st.g[s3].c[c] = gn;
   }
   // now: g[s0] = gab[r-4], g[s1] = gab[r-3], g[s2] = gab[r-2]; dv[s3] = dv[r-5], dv[s0] = dv[r-4], dv[s1] = dv[r-3]; dh[s0..s2] = dh[r-4..r-2]
@@ -952,22 +1140,10 @@ __global__ __launch_bounds__(256, 2) void filter_stream_kernel(const DevImage* _
 //    flight at the join and waits for ALL of them, the prefetched row included);
 //  * the sigma cell and the alpha pair of a row are requested one row ahead, like the input pairs.
 // A strip = 128 columns, the outer two pairs each side are halo (the filters reach 3 columns): 120 output columns.
-typedef float __attribute__((ext_vector_type(2))) F2;
-typedef unsigned __attribute__((ext_vector_type(2))) U2v;
 constexpr int kPairOut = 2 * (kStripLanes - 4);
-__device__ __forceinline__ F2 ShiftFromLeft(F2 v) { return F2{DppFromLeft(v.y), v.x}; }
-__device__ __forceinline__ F2 ShiftFromRight(F2 v) { return F2{v.y, DppFromRight(v.x)}; }
-__device__ __forceinline__ F2 ShiftFromLeft2(F2 v) { return F2{DppFromLeft(v.x), DppFromLeft(v.y)}; }
-__device__ __forceinline__ F2 Abs2(F2 v) { return F2{fabsf(v.x), fabsf(v.y)}; }
-struct PairRow { F2 c[3]; };
-struct PairState {
-  PairRow in[4], s[4], g[4];
-  F2 dv[4], dh[4], hd[4];
-};
-struct PairConst {
+struct PairConst : RowConst {
   __amdgpu_buffer_rsrc_t in0, in1, in2, sigma, alpha, out, f0, f1, f2;
-  float gw0[3], gw1[3], gw2[3], cs[3], bsm;
-  int w, h, wp, w8, y0, y1, r_end, band_y0;
+  int w, h, wp, w8, r_end, band_y0;
   uint32_t in_bytes, cell_bytes, alpha_bytes, out_bytes;   // the lane's byte offsets inside a row: mirrored input pair, sigma cell, alpha pair, pair
   bool outside, stores, to_float, use_alpha, xb_lo, xb_hi;
   int bpp;   // bytes per output pixel: 4 RGBA, 3 RGB, 2 gray + alpha, 1 gray
@@ -1016,70 +1192,43 @@ __device__ __forceinline__ PairAux LoadPairAux(const PairConst& k, int y) {
   a.al = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(k.alpha, k.alpha_bytes, (uint32_t)yc * (uint32_t)k.w, 0);
   return a;
 }
+// One input row r of the two-pixel form: its loads (all the next row reads from memory, a whole row of arithmetic ahead of its use; none
+// in a branch) and its stores around GabEpf1Row.
 template <int P>
 __device__ __forceinline__ void PairStreamRow(const DevImage& im, const PairConst& k, PairState& st, PairRow& next, PairAux& next_aux, int r) {
-  constexpr int s0 = P, s1 = (P + 1) & 3, s2 = (P + 2) & 3, s3 = (P + 3) & 3;   // slots of rows r (= r - 4), r - 3, r - 2, r - 1
   const PairRow cur = next;
   const PairAux aux = next_aux;
-  // all the next row reads from memory, a whole row of arithmetic ahead of its use
   next = LoadPairRow(k, min(r + 1, k.r_end - 1));
   next_aux = LoadPairAux(k, r - 2);
   const int y = r - 3;   // the output row
-  const float is = aux.is;
   const uint32_t al = k.use_alpha ? aux.al : 0xFFFFu;
-  const F2 zero = {0.f, 0.f};
-  F2 dhn = zero, dvn = zero;
-  st.in[s0] = cur;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    st.s[s0].c[c] = ShiftFromLeft(cur.c[c]) + ShiftFromRight(cur.c[c]);
-    const F2 gn = st.in[s3].c[c] * k.gw0[c] + ((st.in[s2].c[c] + cur.c[c]) + st.s[s3].c[c]) * k.gw1[c] + (st.s[s2].c[c] + st.s[s0].c[c]) * k.gw2[c];
-    dhn += Abs2(gn - ShiftFromRight(gn)) * k.cs[c];
-    dvn += Abs2(st.g[s2].c[c] - gn) * k.cs[c];
-    st.g[s3].c[c] = gn;
-  }
-  const F2 dv0 = st.dv[s3], dv1 = st.dv[s0], dv2 = st.dv[s1];
-  const F2 hd2 = ShiftFromLeft(dv2) + ShiftFromRight(dv2);
-  const F2 hd1 = st.hd[s0];
-  if (y >= k.y0 && y < k.y1) {   // uniform over the wavefront
-    const F2 dh0 = st.dh[s0], dh1 = st.dh[s1], dh2 = st.dh[s2];
-    const F2 a = dv1 + dv2;
-    const F2 sad_u = a + dv0 + hd1, sad_d = a + dvn + hd2;
-    const F2 vh = dh0 + dh1 + dh2;
-    const F2 sad_r = vh + (ShiftFromLeft(dh1) + ShiftFromRight(dh1));
-    const F2 sad_l = ShiftFromLeft(vh) + (ShiftFromLeft2(dh1) + dh1);
-    const bool yb = ((y & 7) == 0) || ((y & 7) == 7);
-    const float inv_in = is * (yb ? k.bsm : 1.0f), inv_b = is * k.bsm;
-    const F2 inv = {k.xb_lo ? inv_b : inv_in, k.xb_hi ? inv_b : inv_in};
-    const bool skip = is < -3.90524291751269967465540850526868f;
-    F2 wu, wl, wr, wd, iw;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      wu[j] = fmaxf(0.f, 1.0f + sad_u[j] * inv[j]); wl[j] = fmaxf(0.f, 1.0f + sad_l[j] * inv[j]);
-      wr[j] = fmaxf(0.f, 1.0f + sad_r[j] * inv[j]); wd[j] = fmaxf(0.f, 1.0f + sad_d[j] * inv[j]);
-      iw[j] = __builtin_amdgcn_rcpf(1.0f + wu[j] + wl[j] + wr[j] + wd[j]);
-    }
-    F2 o[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const F2 g1 = st.g[s1].c[c];
-      const F2 f = (g1 + wu * st.g[s0].c[c] + wl * ShiftFromLeft(g1) + wr * ShiftFromRight(g1) + wd * st.g[s2].c[c]) * iw;
-      o[c] = skip ? g1 : f;
-    }
-    if (k.stores) {
-      if (k.to_float) {
-        const uint32_t row = (uint32_t)y * (uint32_t)k.wp * 4u;
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2v, o[0]), k.f0, k.out_bytes, row, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2v, o[1]), k.f1, k.out_bytes, row, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2v, o[2]), k.f2, k.out_bytes, row, 0);
-      } else {
-        StorePixelPair(k, PixelToRgba8(im, o[0].x, o[1].x, o[2].x, al & 0xFF), PixelToRgba8(im, o[0].y, o[1].y, o[2].y, (al >> 8) & 0xFF), y - k.band_y0);
-      }
+  F2 o[3];
+  if (!GabEpf1Row<P>(cur, st, k, aux.is, y, k.xb_lo, k.xb_hi, o)) return;
+  if (k.stores) {
+    if (k.to_float) {
+      const uint32_t row = (uint32_t)y * (uint32_t)k.wp * 4u;
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2v, o[0]), k.f0, k.out_bytes, row, 0);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2v, o[1]), k.f1, k.out_bytes, row, 0);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2v, o[2]), k.f2, k.out_bytes, row, 0);
+    } else {
+      StorePixelPair(k, PixelToRgba8(im, o[0].x, o[1].x, o[2].x, al & 0xFF), PixelToRgba8(im, o[0].y, o[1].y, o[2].y, (al >> 8) & 0xFF), y - k.band_y0);
     }
   }
-  st.dv[s2] = dvn;
-  st.dh[s3] = dhn;
-  st.hd[s1] = hd2;
+}
+
+// What both pair kernels derive from the lane's first column X: the pair it loads, its sigma cell, alpha pair and output offsets
+__device__ __forceinline__ void SetPairColumns(PairConst& k, int X) {
+  k.outside = X < 0 || X >= k.w;
+  // the pair this lane loads: itself, or the pair it mirrors.  One reflection is exact only because the host gate (`even`, decoder.cc)
+  // admits w >= 8: the lanes whose pairs reach a stored pixel have X in [-4, w + 2] (second iteration: [-2, w]); lanes further right are
+  // clamped and store nothing
+  const int xm = X < 0 ? -X - 2 : (X >= k.w ? 2 * k.w - 2 - X : X);
+  k.in_bytes = (uint32_t)min(max(xm, 0), k.w - 2) * 4u;
+  const int xc = min(max(X, 0), k.w - 2);
+  k.cell_bytes = (uint32_t)(xc >> 3) * 4u;
+  k.alpha_bytes = (uint32_t)xc;
+  k.out_bytes = (uint32_t)xc * 4u;
+  k.xb_lo = (X & 7) == 0; k.xb_hi = (X & 7) == 6;   // component 0 is column 0 of a block / component 1 is column 7
 }
 
 __global__ __launch_bounds__(256, 4) void filter_stream_pairs_kernel(const DevImage* __restrict__ imgs) {
@@ -1088,54 +1237,25 @@ __global__ __launch_bounds__(256, 4) void filter_stream_pairs_kernel(const DevIm
   if (!im.fused_gab_epf1 || !(im.stream_pairs & 1)) return;
   PairConst k;
   k.w = im.w; k.h = im.h; k.wp = im.wp; k.w8 = im.w8; k.band_y0 = im.band_y0;
-  const int strips = (k.w + kPairOut - 1) / kPairOut;
   k.to_float = im.fused_gab_epf1 == 2;
   const int band_lo = k.to_float ? max(0, im.band_y0 - 1) : im.band_y0, band_hi = k.to_float ? min(k.h, im.band_y1 + 1) : im.band_y1;
-  const int segs = (band_hi - band_lo + kSegRows - 1) / kSegRows;
-  if ((int)blockIdx.x * kGroupsPerWg >= strips * segs) return;
   // (the wavefront's index, given to the compiler as the uniform value it is: rows, segment bounds and row offsets are scalar)
-  const int gidx = blockIdx.x * kGroupsPerWg + __builtin_amdgcn_readfirstlane(threadIdx.x / kStripLanes);
-  const bool task = gidx < strips * segs;
-  const int gi = task ? gidx : strips * segs - 1;   // (every lane stays in the loop: DPP reads neighbouring lanes)
-  const int strip = gi % strips, seg = gi / strips;
-  const int q = threadIdx.x & (kStripLanes - 1);
-  const int X = strip * kPairOut - 4 + 2 * q;       // first column of the lane's pair; strips start on multiples of 8
-  k.y0 = band_lo + seg * kSegRows; k.y1 = min(k.y0 + kSegRows, band_hi);
+  StripTask t;
+  if (!GetStripTask(__builtin_amdgcn_readfirstlane(threadIdx.x / kStripLanes), k.w, band_lo, band_hi, kPairOut, 2, 2, t)) return;
+  k.y0 = t.y0; k.y1 = t.y1;
   k.r_end = k.y1 + 3;
-  k.outside = X < 0 || X >= k.w;
-  // the pair this lane loads: itself, or the pair it mirrors.  One reflection is exact only because the host gate (`even`, decoder.cc)
-  // admits w >= 8: the lanes whose pairs reach a stored pixel have X in [-4, w + 2]; lanes further right are clamped and store nothing
-  const int xm = X < 0 ? -X - 2 : (X >= k.w ? 2 * k.w - 2 - X : X);
-  k.in_bytes = (uint32_t)min(max(xm, 0), k.w - 2) * 4u;
-  const int xc = min(max(X, 0), k.w - 2);
-  k.cell_bytes = (uint32_t)(xc >> 3) * 4u;
-  k.alpha_bytes = (uint32_t)xc;
-  k.out_bytes = (uint32_t)xc * 4u;
-  k.stores = task && q >= 2 && q <= kStripLanes - 3 && X < k.w;
-  k.xb_lo = (X & 7) == 0; k.xb_hi = (X & 7) == 6;   // component 0 is column 0 of a block / component 1 is column 7
+  SetPairColumns(k, t.X);   // strips start on multiples of 8
+  k.stores = t.stores;
   k.use_alpha = im.has_alpha && !k.to_float;
   k.bpp = im.nch_out;
   k.in0 = PlaneResource(im.stream_in[0]); k.in1 = PlaneResource(im.stream_in[1]); k.in2 = PlaneResource(im.stream_in[2]);
-  const bool no_gab = im.stream_no_gab != 0;
   k.sigma = PlaneResource(im.inv_sigma);
   k.alpha = k.use_alpha ? PlaneResource(im.alpha) : k.in0;   // (ignored without alpha: any readable bytes)
   k.out = PlaneResource(im.out);
   k.f0 = PlaneResource(im.stream_mid[0]); k.f1 = PlaneResource(im.stream_mid[1]); k.f2 = PlaneResource(im.stream_mid[2]);
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    // without Gaborish the kernel's weights are the identity: x * 1 + a * 0 + b * 0 is x exactly for finite planes
-    k.gw0[c] = no_gab ? 1.0f : im.gab_w[c][0]; k.gw1[c] = no_gab ? 0.0f : im.gab_w[c][1]; k.gw2[c] = no_gab ? 0.0f : im.gab_w[c][2];
-    k.cs[c] = im.epf_channel_scale[c];
-  }
-  k.bsm = im.epf_border_sad_mul;
+  FillRowConst(im, k);
   PairState st;
-  const F2 zero = {0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) { st.in[i].c[c] = zero; st.s[i].c[c] = zero; st.g[i].c[c] = zero; }
-    st.dv[i] = zero; st.dh[i] = zero; st.hd[i] = zero;
-  }
+  ZeroWindows(st);
   const int r0 = k.y0 - 3;
   PairRow next = LoadPairRow(k, r0);
   PairAux next_aux = LoadPairAux(k, r0 - 3);
@@ -1157,26 +1277,17 @@ __global__ __launch_bounds__(256) void filter_stream2_kernel(const DevImage* __r
   const DevImage& im = imgs[blockIdx.y];
   if (im.fused_gab_epf1 != 2 || (im.stream_pairs & 2)) return;   // (RGBA8 frames of even width: filter_stream2_pairs_kernel)
   const int w = im.w, h = im.h, wp = im.wp;
-  const int strips = (w + kStripOut - 1) / kStripOut;
-  const int band_rows = im.band_y1 - im.band_y0;
-  const int segs = (band_rows + kSegRows - 1) / kSegRows;
-  if ((int)blockIdx.x * kGroupsPerWg >= strips * segs) return;
-  const int gidx = blockIdx.x * kGroupsPerWg + (threadIdx.x / kStripLanes);
-  const bool task = gidx < strips * segs;
-  const int gi = task ? gidx : strips * segs - 1;
-  const int strip = gi % strips, seg = gi / strips;
-  const int q = threadIdx.x & (kStripLanes - 1);
-  const int X = strip * kStripOut - 4 + 4 * q;
-  const int y0 = im.band_y0 + seg * kSegRows, y1 = min(y0 + kSegRows, im.band_y1);
+  StripTask t;
+  if (!GetStripTask(threadIdx.x / kStripLanes, w, im.band_y0, im.band_y1, kStripOut, 1, 4, t)) return;
+  const int q = t.q, X = t.X, y0 = t.y0, y1 = t.y1;
   const bool interior = X >= 0 && X + 3 < w;
-  const bool stores = task && q >= 1 && q <= kStripLanes - 2 && X < w;
-  const bool full_quad = X + 3 < w;
+  const bool plain = PlainOutput(im);
+  const bool fast = plain && im.nch_out == 4 && X + 3 < w;   // whole RGBA quads of the plain layouts
   const JXL_GLOBAL float* in0 = (const JXL_GLOBAL float*)im.stream_mid[0];
   const JXL_GLOBAL float* in1 = (const JXL_GLOBAL float*)im.stream_mid[1];
   const JXL_GLOBAL float* in2 = (const JXL_GLOBAL float*)im.stream_mid[2];
   const JXL_GLOBAL float* inv_sigma = (const JXL_GLOBAL float*)im.inv_sigma;
-  const bool plain = PlainOutput(im);
-  const float cs0 = im.epf_channel_scale[0], cs1 = im.epf_channel_scale[1], cs2 = im.epf_channel_scale[2];
+  const float cs[3] = {im.epf_channel_scale[0], im.epf_channel_scale[1], im.epf_channel_scale[2]};
   const float sm = im.epf_pass2_sigma_scale, smb = sm * im.epf_border_sad_mul;
   const bool xb0 = (q & 1) != 0, xb3 = (q & 1) == 0;
   const int cellx = min(max(X, 0), w - 1) >> 3;
@@ -1187,58 +1298,10 @@ __global__ __launch_bounds__(256) void filter_stream2_kernel(const DevImage* __r
     const Row3 next = LoadRow3(in0, in1, in2, X, y + 1, w, h, wp, interior);
     const float is = inv_sigma[(size_t)(y >> 3) * im.w8 + cellx];
     uint32_t al = 0xFFFFFFFFu;
-    if (im.has_alpha && plain) {
-      const JXL_GLOBAL uint8_t* ap = (const JXL_GLOBAL uint8_t*)im.alpha + (size_t)y * w + xa;
-      al = (uint32_t)ap[0] | (uint32_t)ap[1] << 8 | (uint32_t)ap[2] << 16 | (uint32_t)ap[3] << 24;
-    }
-    const F4 zero = {0.f, 0.f, 0.f, 0.f};
-    F4 su = zero, sd = zero, sl = zero, sr = zero;
-    F4 lft[3], rgt[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float sc = c == 0 ? cs0 : (c == 1 ? cs1 : cs2);
-      lft[c] = ShiftFromLeft(cur.c[c]); rgt[c] = ShiftFromRight(cur.c[c]);
-      su += Abs4(cur.c[c] - prev.c[c]) * sc; sd += Abs4(cur.c[c] - next.c[c]) * sc;
-      sl += Abs4(cur.c[c] - lft[c]) * sc; sr += Abs4(cur.c[c] - rgt[c]) * sc;
-    }
-    const bool yb = ((y & 7) == 0) || ((y & 7) == 7);
-    const float inv_in = is * (yb ? smb : sm), inv_b = is * smb;
-    const F4 inv = {xb0 ? inv_b : inv_in, inv_in, inv_in, xb3 ? inv_b : inv_in};
-    const bool skip = is < -3.90524291751269967465540850526868f;
-    F4 wu, wl, wr, wd, iw;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      wu[j] = fmaxf(0.f, 1.0f + su[j] * inv[j]); wl[j] = fmaxf(0.f, 1.0f + sl[j] * inv[j]);
-      wr[j] = fmaxf(0.f, 1.0f + sr[j] * inv[j]); wd[j] = fmaxf(0.f, 1.0f + sd[j] * inv[j]);
-      iw[j] = __builtin_amdgcn_rcpf(1.0f + wu[j] + wl[j] + wr[j] + wd[j]);
-    }
+    if (im.has_alpha && plain) al = LoadAlphaQuad((const JXL_GLOBAL uint8_t*)im.alpha + (size_t)y * w + xa);
     F4 o[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const F4 f = (cur.c[c] + wu * prev.c[c] + wl * lft[c] + wr * rgt[c] + wd * next.c[c]) * iw;
-      o[c] = skip ? cur.c[c] : f;
-    }
-    if (stores) {
-      if (plain && im.nch_out == 4 && full_quad) {
-        typedef unsigned __attribute__((ext_vector_type(4))) U4v;
-        U4v px;
-        px.x = PixelToRgba8(im, o[0].x, o[1].x, o[2].x, al & 0xFF);
-        px.y = PixelToRgba8(im, o[0].y, o[1].y, o[2].y, (al >> 8) & 0xFF);
-        px.z = PixelToRgba8(im, o[0].z, o[1].z, o[2].z, (al >> 16) & 0xFF);
-        px.w = PixelToRgba8(im, o[0].w, o[1].w, o[2].w, al >> 24);
-        *(JXL_GLOBAL U4v*)((JXL_GLOBAL uint8_t*)im.out + ((size_t)(y - im.band_y0) * w + X) * 4) = px;
-      } else {
-#pragma unroll 1
-        for (int j = 0; j < 4; j++) {
-          if (X + j >= w) break;
-          const uint32_t aj = !im.has_alpha ? 0u : LoadAlpha(im, (size_t)y * w + X + j);
-          const float ox = j == 0 ? o[0].x : (j == 1 ? o[0].y : (j == 2 ? o[0].z : o[0].w));
-          const float oy = j == 0 ? o[1].x : (j == 1 ? o[1].y : (j == 2 ? o[1].z : o[1].w));
-          const float ob = j == 0 ? o[2].x : (j == 1 ? o[2].y : (j == 2 ? o[2].z : o[2].w));
-          WritePixelGeneral(im, X + j, y, ox, oy, ob, aj);
-        }
-      }
-    }
+    Epf2Row(prev, cur, next, cs, sm, smb, is, y, xb0, xb3, o);
+    if (t.stores) StoreQuad(im, o, al, X, y, w, fast);
     prev = cur;
     cur = next;
   }
@@ -1253,34 +1316,19 @@ __global__ __launch_bounds__(256, 4) void filter_stream2_pairs_kernel(const DevI
   if (im.fused_gab_epf1 != 2 || !(im.stream_pairs & 2)) return;
   PairConst k;
   k.w = im.w; k.h = im.h; k.wp = im.wp; k.w8 = im.w8; k.band_y0 = im.band_y0;
-  const int strips = (k.w + kPair2Out - 1) / kPair2Out;
-  const int segs = (im.band_y1 - im.band_y0 + kSegRows - 1) / kSegRows;
-  if ((int)blockIdx.x * kGroupsPerWg >= strips * segs) return;
-  const int gidx = blockIdx.x * kGroupsPerWg + __builtin_amdgcn_readfirstlane(threadIdx.x / kStripLanes);
-  const bool task = gidx < strips * segs;
-  const int gi = task ? gidx : strips * segs - 1;
-  const int strip = gi % strips, seg = gi / strips;
-  const int q = threadIdx.x & (kStripLanes - 1);
-  const int X = strip * kPair2Out - 2 + 2 * q;      // strips start on multiples of 4
-  k.y0 = im.band_y0 + seg * kSegRows; k.y1 = min(k.y0 + kSegRows, im.band_y1);
+  StripTask t;
+  if (!GetStripTask(__builtin_amdgcn_readfirstlane(threadIdx.x / kStripLanes), k.w, im.band_y0, im.band_y1, kPair2Out, 1, 2, t)) return;
+  k.y0 = t.y0; k.y1 = t.y1;
   k.r_end = k.y1 + 1;                               // last input row + 1
-  k.outside = X < 0 || X >= k.w;
-  // one reflection is exact only because of the w >= 8 gate (see filter_stream_pairs_kernel): lanes reaching a stored pixel have X in [-2, w]
-  const int xm = X < 0 ? -X - 2 : (X >= k.w ? 2 * k.w - 2 - X : X);
-  k.in_bytes = (uint32_t)min(max(xm, 0), k.w - 2) * 4u;
-  const int xc = min(max(X, 0), k.w - 2);
-  k.cell_bytes = (uint32_t)(xc >> 3) * 4u;
-  k.alpha_bytes = (uint32_t)xc;
-  k.out_bytes = (uint32_t)xc * 4u;
-  k.stores = task && q >= 1 && q <= kStripLanes - 2 && X < k.w;
-  k.xb_lo = (X & 7) == 0; k.xb_hi = (X & 7) == 6;
+  SetPairColumns(k, t.X);                           // strips start on multiples of 4
+  k.stores = t.stores;
   k.use_alpha = im.has_alpha != 0;
   k.bpp = im.nch_out;
   k.in0 = PlaneResource(im.stream_mid[0]); k.in1 = PlaneResource(im.stream_mid[1]); k.in2 = PlaneResource(im.stream_mid[2]);
   k.sigma = PlaneResource(im.inv_sigma);
   k.alpha = k.use_alpha ? PlaneResource(im.alpha) : k.in0;
   k.out = PlaneResource(im.out);
-  const float cs0 = im.epf_channel_scale[0], cs1 = im.epf_channel_scale[1], cs2 = im.epf_channel_scale[2];
+  const float cs[3] = {im.epf_channel_scale[0], im.epf_channel_scale[1], im.epf_channel_scale[2]};
   const float sm = im.epf_pass2_sigma_scale, smb = sm * im.epf_border_sad_mul;
   PairRow prev = LoadPairRow(k, k.y0 - 1);
   PairRow cur = LoadPairRow(k, k.y0);
@@ -1290,35 +1338,9 @@ __global__ __launch_bounds__(256, 4) void filter_stream2_pairs_kernel(const DevI
     // two rows ahead for the pairs, one for sigma / alpha: nothing this row uses was requested in it
     const PairRow next2 = LoadPairRow(k, min(y + 2, k.r_end - 1));
     const PairAux aux2 = LoadPairAux(k, y + 1);
-    const float is = aux.is;
     const uint32_t al = k.use_alpha ? aux.al : 0xFFFFu;
-    const F2 zero = {0.f, 0.f};
-    F2 su = zero, sd = zero, sl = zero, sr = zero;
-    F2 lft[3], rgt[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float sc = c == 0 ? cs0 : (c == 1 ? cs1 : cs2);
-      lft[c] = ShiftFromLeft(cur.c[c]); rgt[c] = ShiftFromRight(cur.c[c]);
-      su += Abs2(cur.c[c] - prev.c[c]) * sc; sd += Abs2(cur.c[c] - next.c[c]) * sc;
-      sl += Abs2(cur.c[c] - lft[c]) * sc; sr += Abs2(cur.c[c] - rgt[c]) * sc;
-    }
-    const bool yb = ((y & 7) == 0) || ((y & 7) == 7);
-    const float inv_in = is * (yb ? smb : sm), inv_b = is * smb;
-    const F2 inv = {k.xb_lo ? inv_b : inv_in, k.xb_hi ? inv_b : inv_in};
-    const bool skip = is < -3.90524291751269967465540850526868f;
-    F2 wu, wl, wr, wd, iw;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      wu[j] = fmaxf(0.f, 1.0f + su[j] * inv[j]); wl[j] = fmaxf(0.f, 1.0f + sl[j] * inv[j]);
-      wr[j] = fmaxf(0.f, 1.0f + sr[j] * inv[j]); wd[j] = fmaxf(0.f, 1.0f + sd[j] * inv[j]);
-      iw[j] = __builtin_amdgcn_rcpf(1.0f + wu[j] + wl[j] + wr[j] + wd[j]);
-    }
     F2 o[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const F2 f = (cur.c[c] + wu * prev.c[c] + wl * lft[c] + wr * rgt[c] + wd * next.c[c]) * iw;
-      o[c] = skip ? cur.c[c] : f;
-    }
+    Epf2Row(prev, cur, next, cs, sm, smb, aux.is, y, k.xb_lo, k.xb_hi, o);
     if (k.stores) {
       StorePixelPair(k, PixelToRgba8(im, o[0].x, o[1].x, o[2].x, al & 0xFF), PixelToRgba8(im, o[0].y, o[1].y, o[2].y, (al >> 8) & 0xFF), y - k.band_y0);
     }
