@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "entropy_plan.h"
 #include "host_parse.h"
 #include "icc.h"
 #include "kernels.h"
@@ -197,6 +198,7 @@ struct JxlHipDecoder {
   DecoderStatus Finish(DecoderStatus* statuses, ErrorInfo* err);
   void CopyPlaneTap(int stage);
   void PrepassSingle(ParsedFrame& f, const uint8_t* dev_file);
+  EntropyPlanOptions PlanOptions() const;
 };
 
 JxlHipDecoder::JxlHipDecoder(int dev) {
@@ -383,6 +385,21 @@ void JxlHipDecoder::WaitSlot(Slot& S) {
   total_batches++;
 }
 
+// The entropy plan's options: this object's, and the experiment knobs' values.
+EntropyPlanOptions JxlHipDecoder::PlanOptions() const {
+  EntropyPlanOptions o;
+  o.band_first_row = band_first_row; o.band_rows = band_rows;
+  o.downscale = downscale;
+  o.lane_stride_override = lane_stride_override; o.hf_stride_override = hf_stride_override;
+  o.no_direct = no_direct || Knob("JXLHIP_NO_DIRECT"); o.mod_lanes64 = mod_lanes64 || Knob("JXLHIP_MOD_LANES64");
+  o.hf_waves8 = Knob("JXLHIP_HF_WAVES8"); o.alpha_old_shapes = Knob("JXLHIP_ALPHA_OLD_SHAPES"); o.no_hf_sort = Knob("JXLHIP_NO_HF_SORT");
+  o.hf_global = Knob("JXLHIP_HF_GLOBAL"); o.alpha_global = Knob("JXLHIP_ALPHA_GLOBAL"); o.lf_global = Knob("JXLHIP_LF_GLOBAL");
+  if (const char* e = Knob("JXLHIP_HF_LDS_KB")) o.hf_lds_kb = atoi(e);
+  o.alpha_stride = KnobStride("JXLHIP_ALPHA_STRIDE", 0);
+  if (const char* e = Knob("JXLHIP_LF_PER_WAVE")) o.lf_per_wave = std::max(1, atoi(e));
+  return o;
+}
+
 void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const size_t* sizes, const uint8_t* const* dev_data,
                            uint8_t* const* dev_out, hipStream_t stream, bool sync, DecoderStatus* statuses, ErrorInfo* err) {
   HIP_OK(hipSetDevice(device));
@@ -510,16 +527,29 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       parse_msg[i] = e.what();
     }
   }
-  // images that failed to parse are skipped on the device (their DevImage stays zeroed, ng = 0)
-  // ---- 2. layout of blob and workspace
+  // A band is a set of VarDCT group rows.  A Modular frame has no band mode (global Squeeze / whole-image transforms: SURVEY 8e
+  // "replicas only"); its output kernel writes the whole frame, so accepting the option would overrun the caller's band buffer.
+  for (int i = 0; i < n; i++)
+    if (parse_status[i] == DecoderStatus_Ok && band_rows > 0 && (band_first_row < 0 || band_first_row >= (int)frames[i].yg)) {
+      parse_status[i] = DecoderStatus_DecodeError;
+      parse_msg[i] = "band decode: the first group row lies outside the frame";
+    }
+  for (int i = 0; i < n; i++)
+    if (parse_status[i] == DecoderStatus_Ok && band_rows > 0 && frames[i].encoding == 1) {
+      parse_status[i] = DecoderStatus_DecodeError;
+      parse_msg[i] = "band decode of a Modular (lossless) frame is not supported";
+    }
+  for (int i = 0; i < n; i++)
+    if (parse_status[i] == DecoderStatus_Ok && band_rows > 0 && frames[i].orientation != 1) {
+      parse_status[i] = DecoderStatus_DecodeError;
+      parse_msg[i] = "band decode of a frame with an orientation is not supported";
+    }
+  // images that failed to parse or were refused are skipped on the device (their DevImage stays zeroed, ng = 0)
+  // ---- 2. the entropy stage's plan (entropy_plan.h): decoded ranges, lane mappings, task tables, LDS sizes
+  const EntropyPlan plan = PlanEntropy(frames, parse_status, PlanOptions());
+  // ---- 3. layout of blob and workspace
   Bump blob, ws_zero, ws;
-  // every pass after the first of a progressive frame is an image record of its own, after the batch's n (dev_types.h: next_pass)
-  int n_extra = 0;
-  std::vector<int> first_extra((size_t)n, 0);
-  for (int i = 0; i < n; i++) {
-    first_extra[i] = n + n_extra;
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0) n_extra += (int)frames[i].extra_passes.size();
-  }
+  const int n_extra = plan.n_extra;   // every pass after the first of a progressive frame is an image record of its own
   const size_t off_imgs = blob.Take(sizeof(DevImage) * (size_t)(n + n_extra));
   struct PassLayout {   // what a pass owns: its code, scan lists, entry lists, block index, end positions, LZ77 windows
     size_t a_cmap, a_cfg, a_alias, a_pfx[3] = {}, lz_hf = 0, scan[kNumQuantTables] = {}, centries, cblk, bitpos, hf_order;
@@ -555,30 +585,6 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // the images' status words (64 B each) lie side by side: ONE copy brings them back (a copy per image was 384 five-microsecond copy
   // kernels at the end of the pixel stream - 2 ms of the step - and as many API calls)
   const size_t z_status_base = ws_zero.Take((size_t)std::max(1, n) * 64);
-  int total_lf = 0, total_groups = 0, n_mod_tasks = 0;
-  // Modular frames whose MA tree looks at decoded neighbours take the generic per-lane path: give it LDS row buffers (groups of up to
-  // 256 columns); with the weighted predictor its per-sample state goes to LDS as well, which limits a workgroup to 8 sections
-  int mod_lanes = 64, mod_rb = 0, mod_wp_lds = 0;
-  size_t total_mod_sections = 0;
-  for (int i = 0; i < n; i++) {
-    if (parse_status[i] != DecoderStatus_Ok || frames[i].encoding != 1) continue;
-    if (!frames[i].tree_row_static && frames[i].group_dim <= 256) mod_rb = 256;
-    if (frames[i].tree_uses_wp && frames[i].group_dim <= 256) { mod_wp_lds = 1; mod_lanes = 8; }
-    total_mod_sections += frames[i].single ? 1 : 1 + (size_t)frames[i].nlf + frames[i].ng;
-  }
-  if (!mod_rb) { mod_wp_lds = 0; mod_lanes = 64; }
-  // few sections (one frame, a small batch): one section per wavefront - no divergence between sections, and row-static channels
-  // decode on the scalar unit from per-residue tables (see the LF launch below)
-  if (total_mod_sections <= 512 && !mod_lanes64 && !Knob("JXLHIP_MOD_LANES64")) mod_lanes = 1;
-  // Small launches get the Modular code's per-residue tables (the alias tables spelled out for each of the 4096 state residues,
-  // 16 KB per cluster, codes of up to 8 clusters): one-section wavefronts read them through the scalar cache (RowScalar).  Measured
-  // against a copy in LDS (one 4K frame): lf_ans 20.2 -> 18.8 ms, alpha_ans 5.7 -> 5.1 ms, and no LDS spent on them.
-  bool global_direct = false;
-  if (!no_direct && !Knob("JXLHIP_NO_DIRECT")) {
-    int pre_lf = 0;
-    for (int i = 0; i < n; i++) if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0) pre_lf += (int)frames[i].nlf;
-    global_direct = n <= 64 && pre_lf <= 1024 && total_mod_sections <= 512;
-  }
   size_t chunk_pix = 0;   // padded pixels of the largest VarDCT frame of the batch
   for (int i = 0; i < n; i++) {
     if (parse_status[i] != DecoderStatus_Ok) continue;
@@ -592,7 +598,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     l.m_cmap = blob.Take(f.mcode.ctx_map.size());
     l.m_cfg = blob.Take(4 * f.mcode.cfg.size());
     l.m_alias = blob.Take(8 * f.mcode.alias.size());
-    if (global_direct && !f.mcode.use_prefix && !f.mcode.lz77 && f.mcode.num_hist <= 8) l.m_direct = blob.Take((size_t)f.mcode.num_hist << 14) + 1;
+    if (plan.global_direct && !f.mcode.use_prefix && !f.mcode.lz77 && f.mcode.num_hist <= 8) l.m_direct = blob.Take((size_t)f.mcode.num_hist << 14) + 1;
     auto pfx_layout = [&](const HostCode& hc, size_t* o) {
       if (!hc.use_prefix) return;
       size_t total = 0;
@@ -611,7 +617,6 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       l.mod_desc = ws.Take(nsec * f.mod_coded.size() * sizeof(ChanDesc));
       if (f.tree_uses_wp) l.wp_grp = ws.Take(nsec * 10 * (f.group_dim + 2) * 4);
       if (f.mcode.lz77) l.lz_mod = ws.Take(nsec * ((size_t)4 << 20)) + 1;
-      n_mod_tasks += f.single ? 1 : ((int)nsec + mod_lanes - 1) / mod_lanes;
       if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * (f.layer_f32 ? 4 : OutBytesPerSample(f)));
       // reduced-size decode: the full-size output samples go to scratch, box_reduce_kernel averages them into the caller's buffer
       if (ds) l.ds_full = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));
@@ -638,12 +643,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     l.z_status = z_status_base + (size_t)i * 64;
     {
       // entry lists of the decoded group rows only (a band decode touches a band's worth), block index for the whole cell grid
-      int b0 = 0, b1 = (int)f.yg;
-      if (band_rows > 0) { b0 = std::min<int>(band_first_row, (int)f.yg); b1 = std::min<int>(b0 + band_rows, (int)f.yg); }
-      const int g0 = std::max(0, b0 - 1), g1 = std::min<int>((int)f.yg, b1 + 1);
-      // (a reduced-size decode reads the HF tokens only for what follows them in a section - the alpha channel - and keeps no coefficients
-      // of an opaque frame)
-      const bool hf = !ds || f.alpha_index >= 0;
+      const int g0 = plan.frames[i].dec_gy0, g1 = plan.frames[i].dec_gy1;
+      const bool hf = plan.frames[i].hf;
       l.centries = ws.Take(hf ? (size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4 : 0);
       l.cblk = ws.Take(hf ? 3 * cells * sizeof(U32x2) : 0);
       for (auto& ep : f.extra_passes) {
@@ -686,14 +687,6 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));   // (never f32: checked on the host)
     l.lf_end = ws.Take(8);
     if (f.tree_uses_wp) { l.wp_lf = ws.Take((size_t)f.nlf * kWpLfInts * 4); l.wp_grp = ws.Take((size_t)f.ng * 10 * (kGroupDim + 2) * 4); }
-    {
-      // sections this call decodes (a band: its group rows + one each side, the LF groups they touch): what the launch shapes go by
-      int b0 = 0, b1 = (int)f.yg;
-      if (band_rows > 0) { b0 = std::min<int>(band_first_row, (int)f.yg); b1 = std::min<int>(b0 + band_rows, (int)f.yg); }
-      const int g0 = std::max(0, b0 - 1), g1 = std::min<int>((int)f.yg, b1 + 1);
-      total_lf += ((g1 + 7) / 8 - g0 / 8) * (int)f.xlf;
-      if (!ds || f.alpha_index >= 0) total_groups += (g1 - g0) * (int)f.xg * (int)f.num_passes;
-    }
   }
   // The float planes between reconstruction and the loop filters (24 B/px) are only alive while a frame is in the pixel stages:
   // frames go through those stages in chunks that share kPixelChunk sets of planes, so the batch size is bounded by the
@@ -713,138 +706,19 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     for (int k = 0; k < pixel_chunk * 3; k++) chunk_noise[k] = ws.Take(4 * noise_pix);
   // The reference's decoder library hands out the image as displayed (orientation applied; it is only kept when the caller asks,
   // which Decoder/DecoderContext.cpp never does): such frames are decoded into a scratch buffer and re-laid out at the end.
-  // A band is a set of VarDCT group rows.  A Modular frame has no band mode (global Squeeze / whole-image transforms: SURVEY 8e
-  // "replicas only"); its output kernel writes the whole frame, so accepting the option would overrun the caller's band buffer.
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && band_rows > 0 && (band_first_row < 0 || band_first_row >= (int)frames[i].yg)) {
-      parse_status[i] = DecoderStatus_DecodeError;
-      parse_msg[i] = "band decode: the first group row lies outside the frame";
-    }
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && band_rows > 0 && frames[i].encoding == 1) {
-      parse_status[i] = DecoderStatus_DecodeError;
-      parse_msg[i] = "band decode of a Modular (lossless) frame is not supported";
-    }
   for (int i = 0; i < n; i++) {
     if (parse_status[i] != DecoderStatus_Ok || frames[i].orientation == 1) continue;
     const ParsedFrame& f = frames[i];
-    if (band_rows > 0) { parse_status[i] = DecoderStatus_DecodeError; parse_msg[i] = "band decode of a frame with an orientation is not supported"; continue; }
     if (ds) continue;   // lf_output_kernel / box_reduce_kernel store at the oriented position
     L[i].orient_tmp = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));
   }
-  // Lane mapping of the HF kernel: one wavefront per section while every workgroup of the launch can be resident at once
-  // (the kernel is latency-bound, a second round of workgroups doubles its time); otherwise pack more sections per wavefront.
-  int lane_stride = 64;
-  int hf_wg_capacity = 256 * 8;   // workgroups of the HF kernel that can be resident at once (by the LDS of the widest tables)
-  if (lane_stride_override > 0) lane_stride = lane_stride_override;
-  else {
-    size_t lds_est = 0;
-    for (int i = 0; i < n; i++)
-      if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0)
-        lds_est = std::max(lds_est, 8 + 8 * frames[i].acode.alias.size() + 4 * frames[i].acode.cfg.size() + frames[i].acode.ctx_map.size() + 64 + 4 * (96 + 64 + 128));
-    const int wg_per_cu = lds_est ? (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_est)) : 8;
-    const int capacity = 256 * wg_per_cu;   // resident 256-thread workgroups on the chip
-    hf_wg_capacity = capacity;
-    while (lane_stride > 1 && (total_groups + (256 / lane_stride) - 1) / (256 / lane_stride) > capacity) lane_stride >>= 1;
-    // measured (MI355X, 4K frames, batch 384): once a batch holds thousands of sections, 32 sections per wavefront
-    // (half-filled wavefronts, five per image instead of three) is the best trade between instruction efficiency and wavefronts
-    // in flight: hf_decode 72 ms (stride 1) / 61 ms (stride 2) / 87 ms (stride 4)
-    if (total_groups >= 8192) lane_stride = 2;
-    if (hf_stride_override > 0) lane_stride = hf_stride_override;
-  }
-  // Workgroup width of the HF kernel: four wavefronts, or up to eight when the sections are spread thinly over the lanes and one
-  // image's sections would otherwise need a second workgroup (each workgroup stages the image's ~50 KB of tables in LDS).
-  int hf_waves = 4;
-  {
-    int max_ng = 0;
-    for (int i = 0; i < n; i++)
-      if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0) max_ng = std::max<int>(max_ng, (int)frames[i].ng);
-    const int per_wave = 64 / lane_stride;
-    const int need = (max_ng + per_wave - 1) / per_wave;
-    if (need > 4 && lane_stride <= 8) hf_waves = std::min(8, need);
-    if (lane_stride == 64 && !Knob("JXLHIP_HF_WAVES8")) {
-      // One section per wavefront: its token loop runs on the scalar unit, and a CU has ONE scalar unit - eight such wavefronts in
-      // a workgroup share it (measured: hf_decode of one 4K frame 12.5 ms with 17 workgroups of 8 wavefronts).  Spread the sections
-      // over as many workgroups as can be resident at once, one wavefront each if they all fit.
-      hf_waves = 1;
-      while (hf_waves < 8 && (total_groups + hf_waves - 1) / hf_waves > hf_wg_capacity) hf_waves *= 2;
-    }
-  }
-  const int per_wg = hf_waves * (64 / lane_stride);
-  // Sections per workgroup, per image: the HF kernel's LDS is the image's code tables (30 .. 60 KB: they double with the alias-table
-  // width) plus 288 B per lane, and a launch has ONE LDS size.  Sized by the batch-wide maximum, a single image with wide tables
-  // pushed every workgroup from two per CU to one (hf_decode 30 -> 58 ms at batch 384); instead every image gets as many lanes per
-  // workgroup as fit beside ITS tables in the budget (whole wavefronts; images with wide tables use more, smaller workgroups).
-  // The budget (half a CU's LDS) was re-measured in round 3 against 96 / 112 / 128 KB (one workgroup per 4K frame, one copy of its
-  // tables): those won 6 % of the pipelined step while the fused filter kernel held 252 registers, and nothing since it holds 122
-  // (profiles/r03_experiment_hf_lds_budget.txt, r03_experiment_pairs_balance.txt); alone, the HF kernel is 36 ms with 80 KB and 65 ms
-  // with 112 KB (two rounds of workgroups), so 80 KB it stays.
-  auto hf_code_bytes = [](const HostCode& c) { return 8 + 8 * c.alias.size() + 4 * c.cfg.size() + c.ctx_map.size() + 64 + 32; };
-  auto hf_table_bytes = [&](const ParsedFrame& f) {   // the widest of the frame's passes
-    size_t b = hf_code_bytes(f.acode);
-    for (auto& ep : f.extra_passes) b = std::max(b, hf_code_bytes(ep.acode));
-    return b;
-  };
-  size_t kHfLdsTarget = 80 * 1024;
-  if (const char* e = Knob("JXLHIP_HF_LDS_KB")) { const int kb = atoi(e); if (kb >= 32 && kb <= 160) kHfLdsTarget = (size_t)kb * 1024; }   // experiment knob
-  auto hf_per_wg = [&](const ParsedFrame& f) {
-    // the fewest workgroups whose (tables + lanes) fit the budget, the image's sections spread evenly over them: every workgroup
-    // carries a copy of the tables, so a small last workgroup (64 + 64 + 7 sections) costs a full LDS slot for a few lanes
-    const int per_wave = 64 / lane_stride;
-    const size_t tab = hf_table_bytes(f);
-    const int ng = std::max(1, (int)f.ng);
-    for (int nwg = 1; nwg <= ng; nwg++) {
-      const int lanes = (((ng + nwg - 1) / nwg) + per_wave - 1) / per_wave * per_wave;
-      if (lanes <= per_wg && tab + HfLaneLdsBytes(32) * (size_t)lanes <= kHfLdsTarget) return lanes;
-      if (lanes <= per_wave) break;
-    }
-    return per_wave;
-  };
-  int n_pass_wg = 0;
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0)
-      n_pass_wg += (int)frames[i].num_passes * (((int)frames[i].ng + hf_per_wg(frames[i]) - 1) / hf_per_wg(frames[i]));
-  const size_t off_lf_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, total_lf));
-  const size_t off_pass_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_pass_wg));
-  // Lane mapping of the alpha phase-A kernel (one wavefront per workgroup, sections of one image per wavefront): spread the
-  // sections over as many wavefronts as the chip holds in one round, then pack.
-  int alpha_stride = 64;
-  if (lane_stride_override > 0) alpha_stride = lane_stride_override;
-  else {
-    int alpha_sections = 0;
-    for (int i = 0; i < n; i++)
-      if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0 && frames[i].alpha_index >= 0) {
-        int b0 = 0, b1 = (int)frames[i].yg;   // a band decodes the alpha of its own group rows only
-        if (band_rows > 0) { b0 = std::min<int>(band_first_row, b1); b1 = std::min<int>(b0 + band_rows, b1); }
-        alpha_sections += (b1 - b0) * (int)frames[i].xg;
-      }
-    // Two good shapes and a bad middle (measured, 4K frames): one section per wavefront on the scalar unit (5 ms for 135 sections,
-    // degrading gently while a CU holds a dozen such wavefronts) and 32 sections per wavefront on the vector unit (12 ms for 8640
-    // sections); 2 ... 16 sections per wavefront pay the vector chain for a few lanes (21 ms for 2160 sections at 2 per wavefront).
-    if (global_direct && !Knob("JXLHIP_ALPHA_OLD_SHAPES")) alpha_stride = alpha_sections > 3072 ? 2 : 64;
-    else while (alpha_stride > 1 && alpha_sections / (64 / alpha_stride) > 256 * 8) alpha_stride >>= 1;
-    if (alpha_sections >= 8192) alpha_stride = 2;   // measured: alpha_ans 27.8 ms (stride 1) / 22.5 (2) / 26.4 (4) at batch 384
-    alpha_stride = KnobStride("JXLHIP_ALPHA_STRIDE", alpha_stride);   // experiment knob
-  }
-  const int per_alpha_wg = 64 / alpha_stride;
-  int n_alpha_wg = 0;
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0) n_alpha_wg += ((int)frames[i].ng + per_alpha_wg - 1) / per_alpha_wg;
-  // LF groups per wavefront of the LF phase-A kernel.  Measured on MI355X: the 64 LF groups of a 16384^2 frame in ONE wavefront (every
-  // lane walking its own divergent stream) took 68 ms against 33 ms for the four of a 4K frame; one group per wavefront is no faster
-  // for a single frame and much slower for a batch (384 frames: 44 -> 67 ms, four times the wavefronts for the same tokens).  So: four
-  // per wavefront, more only when a batch brings tens of thousands of LF groups.
-  // LF sections per wavefront: one while the batch is small (the wavefront's recurrence then runs on the scalar unit: lower latency),
-  // four for large batches (fewer wavefronts and table copies for the same latency-bound time), more only for huge ones
-  int lf_per_wave = total_lf <= 256 ? 1 : 4;
-  while (lf_per_wave < 64 && total_lf / lf_per_wave > 4096) lf_per_wave *= 2;
-  if (const char* e = Knob("JXLHIP_LF_PER_WAVE")) lf_per_wave = std::min(64, std::max(1, atoi(e)));   // experiment knob
-  int n_lf_ans = 0;
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0) n_lf_ans += ((int)frames[i].nlf + lf_per_wave - 1) / lf_per_wave;
-  const size_t off_lf_ans_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_lf_ans));
-  const size_t off_mod_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_mod_tasks));
-  const size_t off_alpha_tasks = blob.Take(sizeof(SectionTask) * (size_t)std::max(1, n_alpha_wg));
+  // the plan's task tables
+  auto take_tasks = [&](const std::vector<SectionTask>& t) { return blob.Take(sizeof(SectionTask) * std::max<size_t>(1, t.size())); };
+  const size_t off_lf_tasks = take_tasks(plan.lf_finish_tasks);
+  const size_t off_pass_tasks = take_tasks(plan.pass_tasks);
+  const size_t off_lf_ans_tasks = take_tasks(plan.lf_ans_tasks);
+  const size_t off_mod_tasks = take_tasks(plan.mod_tasks);
+  const size_t off_alpha_tasks = take_tasks(plan.alpha_tasks);
   size_t off_comp_imgs = 0, off_comp_frames = 0;
   if (!comps.empty()) {
     off_comp_imgs = blob.Take(sizeof(ComposeImage) * comps.size());
@@ -921,26 +795,19 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     HIP_OK(hipHostMalloc(&h_status, (size_t)n * 16 * 4 + 64, hipHostMallocDefault));
     h_status_cap = (size_t)n * 16;
   }
-  // ---- 3. fill the pinned blob
+  // ---- 4. fill the pinned blob
   memset(h_blob, 0, blob.off);
   imgs.assign(n + n_extra, DevImage());
   for (auto& im : imgs) memset(&im, 0, sizeof(DevImage));
   status_off.assign(n, 0);
-  size_t lds_hf = 0, lds_hf_lanes = 0, lds_lf = 0, lds_alpha = 0;   // lds_hf: tables + lanes, the largest workgroup; lds_hf_lanes: the most lanes (global-table variant)
   bool any_alpha = false, any_unfiltered = false, any_noise = false, any_vardct = false;
   int stage_mask = 0;   // LDS-tiled loop-filter stage kernels some frame of the batch needs (bit s: filter_tile_kernel<s>)
   int any_fused = 0, any_fused2 = 0;   // 1: fused frames (with a second iteration) of the two-pixels-per-lane kernels, 2: others
   int max_w = 1, max_h = 1, max_tiles = 1;
   auto tiles_of = [](const ParsedFrame& f) { return (size_t)((f.w8 + 7) / 8) * ((f.h8 + 7) / 8); };
   size_t max_cells = 1, max_padded = 8, max_ds_cells = 1;   // max_ds_cells: reduced-size decode, over the frames of both kinds
-  SectionTask* lf_tasks = (SectionTask*)(h_blob + off_lf_tasks);
-  SectionTask* pass_tasks = (SectionTask*)(h_blob + off_pass_tasks);
-  SectionTask* alpha_tasks = (SectionTask*)(h_blob + off_alpha_tasks);
-  SectionTask* lf_ans_tasks = (SectionTask*)(h_blob + off_lf_ans_tasks);
-  SectionTask* mod_tasks = (SectionTask*)(h_blob + off_mod_tasks);
-  int nlf_t = 0, npass_t = 0, nalpha_t = 0, nlf_ans_t = 0, nmod_t = 0, max_groups = 1, max_mod_groups = 1;
-  size_t lds_mod = 0, max_mod_pixels = 1;
-  int max_mod_coded = 1;
+  int max_groups = 1;
+  size_t max_mod_pixels = 1;
   struct ModLaunch { int kind; int32_t *a, *b, *c; int aw, ah, rw, rh, type; int32_t* out[4]; int nout; uint32_t* status; };
   std::vector<ModLaunch> mod_ops;
   uint8_t* wz = d_ws;
@@ -960,15 +827,12 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     d.out_bits = 8 * (int32_t)OutBytesPerSample(f); d.out_float = f.exp_bits ? 1 : 0;
     d.unpremultiply = (d.has_alpha && f.ec[f.alpha_index].alpha_associated) ? 1 : 0;
     d.alpha_unit = d.alpha_exp ? 1.0f : 1.0f / (float)((1u << d.alpha_bits) - 1);
-    // band: group rows [b0, b1) are output; one more row each side is decoded for the loop-filter halo
-    int b0 = 0, b1 = (int)f.yg;
-    if (band_rows > 0 && f.encoding == 0) { b0 = std::min<int>(band_first_row, (int)f.yg); b1 = std::min<int>(b0 + band_rows, (int)f.yg); }
-    d.dec_gy0 = std::max(0, b0 - 1); d.dec_gy1 = std::min<int>((int)f.yg, b1 + 1);
-    d.band_y0 = std::min<int>(b0 * kGroupDim, (int)f.ysize); d.band_y1 = std::min<int>(b1 * kGroupDim, (int)f.ysize);
-    const ColorPlan plan = PlanColor(f);
-    d.to_srgb = plan.transfer;   // 0 linear, 1 sRGB, 2 BT.709, 3 PQ, 5 tables
-    if (plan.transfer == 5 && l.trc_lut) {
-      memcpy(h_blob + l.trc_lut - 1, plan.trc_lut.data(), 4 * 3 * 4096);
+    const FramePlan& fp = plan.frames[i];
+    d.dec_gy0 = fp.dec_gy0; d.dec_gy1 = fp.dec_gy1; d.band_y0 = fp.band_y0; d.band_y1 = fp.band_y1;
+    const ColorPlan color = PlanColor(f);
+    d.to_srgb = color.transfer;   // 0 linear, 1 sRGB, 2 BT.709, 3 PQ, 5 tables
+    if (color.transfer == 5 && l.trc_lut) {
+      memcpy(h_blob + l.trc_lut - 1, color.trc_lut.data(), 4 * 3 * 4096);
       d.trc_lut = (const float*)(d_blob + l.trc_lut - 1);
     }
     d.pq_scale = f.intensity_target * 1e-4f;
@@ -1096,17 +960,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
       if (f.layer_f32) {   // unclamped f32 samples in the image's colour space; un-premultiply waits for the compositor
         d.out_bits = 32; d.out_float = 1; d.unpremultiply = 0;
       }
-      auto code_lds_m = [](const HostCode& hc) { return 8 + 8 * hc.alias.size() + 4 * hc.cfg.size() + hc.ctx_map.size(); };
-      // (one section per wavefront with row buffers: three rows and the leaf grid of modular_uniform.h instead of one row per lane)
-      const size_t mod_rows = (mod_lanes == 1 && mod_rb) ? (size_t)3 * mod_rb * 4 + (size_t)kUniGridCells * 16 : (size_t)mod_lanes * mod_rb * 4;
-      lds_mod = std::max(lds_mod, 64 * 128 + mod_rows + (mod_wp_lds ? (size_t)mod_lanes * 10 * (mod_rb + 2) * 4 : 0) + 16 +
-                                      sizeof(DevTreeNode) * f.tree.size() + code_lds_m(f.mcode));
-      const uint32_t nsec = 1 + f.nlf + f.ng;
-      max_mod_groups = std::max<int>(max_mod_groups, (int)nsec);
-      max_mod_coded = std::max<int>(max_mod_coded, (int)f.mod_coded.size());
       max_mod_pixels = std::max(max_mod_pixels, (size_t)f.xsize * f.ysize);
-      if (f.single) mod_tasks[nmod_t++] = SectionTask{i, 0, 1, 0};   // one bit stream: one lane walks all three sections
-      else for (uint32_t g = 0; g < nsec; g += mod_lanes) mod_tasks[nmod_t++] = SectionTask{i, (int32_t)g, (int32_t)std::min<uint32_t>(mod_lanes, nsec - g), 0};
       continue;
     }
     code(f.acode, l.a_cmap, l.a_cfg, l.a_alias, d.acode, l.a_pfx);
@@ -1163,7 +1017,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     for (int r = 0; r < 3; r++)
       for (int k = 0; k < 3; k++) {
         double a = 0;
-        for (int j = 0; j < 3; j++) a += (double)plan.from_srgb[r * 3 + j] * (double)f.opsin_inv[j * 3 + k];
+        for (int j = 0; j < 3; j++) a += (double)color.from_srgb[r * 3 + j] * (double)f.opsin_inv[j * 3 + k];
         d.opsin_inv[r * 3 + k] = (float)a * (255.0f / f.intensity_target);
       }
     for (int k = 0; k < 3; k++) { d.opsin_bias[k] = f.opsin_bias[k]; d.opsin_bias_cbrt[k] = std::cbrt(f.opsin_bias[k]); }
@@ -1201,7 +1055,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     d.grp_bitpos = (uint64_t*)(wr + l.bitpos);
     d.tile_list = (uint32_t*)(wr + l.tile_list);
     d.alpha32 = (int32_t*)(wr + l.alpha32);
-    const bool hf = !ds || d.has_alpha;   // does hf_decode_kernel run for this frame?  (reduced size: only to find the alpha stream)
+    const bool hf = fp.hf;   // does hf_decode_kernel run for this frame?  (reduced size: only to find the alpha stream)
     if (hf) { d.centries = (uint32_t*)(wr + l.centries); d.cblk = (U32x2*)(wr + l.cblk); }
     d.centries_g0 = d.dec_gy0 * (int32_t)f.xg;
     d.inv_sigma = (float*)(wr + l.inv_sigma);
@@ -1269,19 +1123,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     any_vardct = true;
     max_cells = std::max(max_cells, (size_t)f.w8 * f.h8);
     max_padded = std::max(max_padded, (size_t)f.w8 * f.h8 * 64);
-    // LDS budgets (must mirror the carving in entropy_kernels.hip)
-    auto code_lds = [](const HostCode& hc) { return 8 + 8 * hc.alias.size() + 4 * hc.cfg.size() + hc.ctx_map.size(); };
-    lds_lf = std::max(lds_lf, (size_t)lf_per_wave * 128 + 16 + sizeof(DevTreeNode) * f.tree.size() + code_lds(f.mcode));
-    lds_alpha = std::max(lds_alpha, (size_t)per_alpha_wg * 128 + 16 + sizeof(DevTreeNode) * f.tree.size() + code_lds(f.mcode));
     max_groups = std::max<int>(max_groups, (int)f.ng);
-    // LF groups that intersect the decoded group rows (8 group rows per LF group row); HF groups of the decoded rows; alpha of the band
-    const uint32_t lfy0 = (uint32_t)d.dec_gy0 / 8, lfy1 = ((uint32_t)d.dec_gy1 + 7) / 8;
-    for (uint32_t g = lfy0 * f.xlf; g < std::min<uint32_t>(f.nlf, lfy1 * f.xlf); g++) lf_tasks[nlf_t++] = SectionTask{i, (int32_t)g, 1, 0};
-    {
-      const uint32_t l0 = lfy0 * f.xlf, l1 = std::min<uint32_t>(f.nlf, lfy1 * f.xlf);
-      for (uint32_t g = l0; g < l1; g += lf_per_wave)
-        lf_ans_tasks[nlf_ans_t++] = SectionTask{i, (int32_t)g, (int32_t)std::min<uint32_t>((uint32_t)lf_per_wave, l1 - g), 0};
-    }
     // progressive frames: one record per further pass, chained from this one
     d.num_passes = (int32_t)f.num_passes;
     d.pass_shift = (int32_t)f.pass_shift[0];
@@ -1292,7 +1134,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     for (size_t p = 0; p < f.extra_passes.size(); p++) {
       const ParsedFrame::PassCodes& ep = f.extra_passes[p];
       const PassLayout& pl = l.extra[p];
-      DevImage& sh = imgs[(size_t)first_extra[i] + p];
+      DevImage& sh = imgs[(size_t)fp.first_extra + p];
       sh = d;
       memset(&sh.acode, 0, sizeof(sh.acode));
       code(ep.acode, pl.a_cmap, pl.a_cfg, pl.a_alias, sh.acode, pl.a_pfx);
@@ -1317,54 +1159,35 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     {
       const DevImage* d_recs = (const DevImage*)(d_blob + off_imgs);
       for (size_t p = 0; p < f.extra_passes.size(); p++) {
-        DevImage& prev = p ? imgs[(size_t)first_extra[i] + p - 1] : d;
-        prev.next_pass = d_recs + first_extra[i] + p;
-        imgs[(size_t)first_extra[i] + p].alpha_bitpos = d.alpha_bitpos;
+        DevImage& prev = p ? imgs[(size_t)fp.first_extra + p - 1] : d;
+        prev.next_pass = d_recs + fp.first_extra + p;
+        imgs[(size_t)fp.first_extra + p].alpha_bitpos = d.alpha_bitpos;
       }
     }
-    const uint32_t hg0 = (uint32_t)d.dec_gy0 * f.xg, hg1 = (uint32_t)d.dec_gy1 * f.xg;
-    const uint32_t pw = (uint32_t)hf_per_wg(f);
-    for (uint32_t pass = 0; pass < (hf ? f.num_passes : 0u); pass++) {
-      // Sections go to lanes in order of their byte size (the TOC has it), largest first: a wavefront runs until its longest
-      // section ends, so lanes of similar length finish together (the sum over wavefronts of their longest lane - the
-      // wave-instructions of the launch - nearly halves for 4K frames, whose sections spread 1 : 2.2 around the mean), and the
-      // longest sections start first.  Slot j of the (image, pass) decodes group hf_order[j]; tasks index slots.
-      DevImage& rec = pass ? imgs[(size_t)first_extra[i] + pass - 1] : d;
-      const size_t order_off = pass ? l.extra[pass - 1].hf_order : l.hf_order;
-      uint32_t* order = (uint32_t*)(h_blob + order_off);
-      const size_t sec0 = f.single ? 0 : 2 + (size_t)f.nlf + (size_t)pass * f.ng;
-      for (uint32_t g = hg0; g < hg1; g++) order[g - hg0] = g;
-      if (!f.single && !Knob("JXLHIP_NO_HF_SORT"))   // (experiment knob: measured effect of the order, profiles/r03_hf_sort_ab.txt)
-        std::stable_sort(order, order + (hg1 - hg0), [&](uint32_t a, uint32_t b) { return f.sec_size[sec0 + a] > f.sec_size[sec0 + b]; });
-      rec.hf_order = (const uint32_t*)(d_blob + order_off);
-      for (uint32_t j = 0; j < hg1 - hg0; j += pw) {
-        const uint32_t cnt = std::min<uint32_t>(pw, hg1 - hg0 - j);
-        pass_tasks[npass_t++] = SectionTask{pass ? first_extra[i] + (int)pass - 1 : i, (int32_t)j, (int32_t)cnt, 0};
-        const size_t lanes = (size_t)((cnt + 3) & ~3u) * HfLaneLdsBytes(32);   // the kernel lays its per-lane arrays out for the task's lanes
-        lds_hf = std::max(lds_hf, hf_table_bytes(f) + lanes);
-        lds_hf_lanes = std::max(lds_hf_lanes, lanes);
-      }
-    }
-    const uint32_t ag0 = (uint32_t)(d.band_y0 / kGroupDim) * f.xg, ag1 = (uint32_t)((d.band_y1 + kGroupDim - 1) / kGroupDim) * f.xg;
-    if (d.has_alpha)
-      for (uint32_t g = ag0; g < ag1; g += per_alpha_wg)
-        alpha_tasks[nalpha_t++] = SectionTask{i, (int32_t)g, (int32_t)std::min<uint32_t>(per_alpha_wg, ag1 - g), 0};
   }
+  // the plan's tables; slot j of an (image, pass) decodes group hf_order[j]
+  for (const EntropyPlan::HfOrder& o : plan.hf_orders) {
+    const size_t order_off = o.pass ? L[o.image].extra[o.pass - 1].hf_order : L[o.image].hf_order;
+    if (!o.order.empty()) memcpy(h_blob + order_off, o.order.data(), 4 * o.order.size());
+    imgs[o.pass ? (size_t)plan.frames[o.image].first_extra + o.pass - 1 : (size_t)o.image].hf_order = (const uint32_t*)(d_blob + order_off);
+  }
+  auto put_tasks = [&](size_t off, const std::vector<SectionTask>& t) { if (!t.empty()) memcpy(h_blob + off, t.data(), sizeof(SectionTask) * t.size()); };
+  put_tasks(off_lf_tasks, plan.lf_finish_tasks);
+  put_tasks(off_pass_tasks, plan.pass_tasks);
+  put_tasks(off_lf_ans_tasks, plan.lf_ans_tasks);
+  put_tasks(off_mod_tasks, plan.mod_tasks);
+  put_tasks(off_alpha_tasks, plan.alpha_tasks);
+  const int nlf_t = (int)plan.lf_finish_tasks.size(), npass_t = (int)plan.pass_tasks.size(), nalpha_t = (int)plan.alpha_tasks.size();
+  const int nlf_ans_t = (int)plan.lf_ans_tasks.size(), nmod_t = (int)plan.mod_tasks.size();
   if (Knob("JXLHIP_DEBUG_LDS")) {
     for (int i = 0; i < std::min(n, 8); i++)
       if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0)
         fprintf(stderr, "[jxlhip] image %d: hf tables %zu B (clusters %u, log_alpha %u, contexts %zu), lanes/wg %d; modular tables: clusters %u log_alpha %u contexts %zu tree %zu\n", i,
-                hf_table_bytes(frames[i]), frames[i].acode.num_hist, frames[i].acode.log_alpha, frames[i].acode.ctx_map.size(), hf_per_wg(frames[i]),
+                plan.frames[i].hf_table_bytes, frames[i].acode.num_hist, frames[i].acode.log_alpha, frames[i].acode.ctx_map.size(), plan.frames[i].hf_per_wg,
                 frames[i].mcode.num_hist, frames[i].mcode.log_alpha, frames[i].mcode.ctx_map.size(), frames[i].tree.size());
     fprintf(stderr, "[jxlhip] launch LDS: hf %zu B (lanes %zu), lf %zu B, alpha %zu B; hf workgroups %d x %d threads, stride %d; alpha workgroups %d; lf_ans workgroups %d\n",
-            lds_hf, lds_hf_lanes, lds_lf, lds_alpha, npass_t, hf_waves * 64, lane_stride, nalpha_t, nlf_ans_t);
+            plan.hf.lds, plan.lds_hf_lanes, plan.lf.lds, plan.alpha.lds, npass_t, plan.hf_waves * 64, plan.lane_stride, nalpha_t, nlf_ans_t);
   }
-  const int hf_ring = 32;   // words of the per-lane bit window
-  const size_t kLdsMax = 150 * 1024;
-  // experiment knobs: code tables of the entropy kernels read from global memory (L1 / L2) instead of LDS copies
-  if (Knob("JXLHIP_HF_GLOBAL")) lds_hf = kLdsMax + 1;
-  if (Knob("JXLHIP_ALPHA_GLOBAL")) lds_alpha = kLdsMax + 1;
-  if (Knob("JXLHIP_LF_GLOBAL")) lds_lf = kLdsMax + 1;
   int max_segments = 1;
   if (!comps.empty()) {
     // the compositor's tables: one record per layered image, one per frame (frame records indexed like the batch's images)
@@ -1429,7 +1252,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
   memcpy(h_blob + off_imgs, imgs.data(), sizeof(DevImage) * imgs.size());
   d_imgs = (DevImage*)(d_blob + off_imgs);
-  // ---- 4. enqueue: LF chain on s_lf, everything that needs the block layout on the main stream
+  // ---- 5. enqueue: LF chain on s_lf, everything that needs the block layout on the main stream
   stage_names.clear();
   S.stage_chain.clear();
   Mark("start", s_lf, 0);
@@ -1452,18 +1275,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     LaunchNoise(d_imgs, std::min(pixel_chunk, n), max_groups, max_w, max_h, stream);
     Mark("noise", stream, 3);
   }
-  // wavefronts that decode one section run their row loops on the scalar unit from the per-residue tables built above
-  // (measured at batch 384: LF sections as four such wavefronts per workgroup - 135.7 ms per batch against 125.1 with four lanes of
-  // one wavefront: large batches keep the lane layout, the scalar path is for small ones)
-  const int direct_lf = global_direct && lf_per_wave == 1, direct_alpha = global_direct && per_alpha_wg == 1;
-  // the lean forms of the LF / alpha kernels (no per-sample Modular path compiled in: two thirds of the registers) when no lossy frame
-  // of the batch can take that path: row-static MA tree, standard predictors, plain ANS codes
-  bool lean_mod = true;
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].encoding == 0 &&
-        (!frames[i].tree_row_static || frames[i].tree_uses_wp || frames[i].mcode.use_prefix || frames[i].mcode.lz77)) lean_mod = false;
   if (!(skip_stages & 1)) {
-  LaunchLfAns(d_imgs, (const SectionTask*)(d_blob + off_lf_ans_tasks), nlf_ans_t, lf_per_wave, lds_lf <= kLdsMax ? lds_lf : 0, direct_lf, lean_mod, s_lf);
+  LaunchLfAns(d_imgs, (const SectionTask*)(d_blob + off_lf_ans_tasks), nlf_ans_t, plan.lf_per_wave, plan.lf.Bytes(), plan.direct_lf, plan.lean_mod, s_lf);
   Mark("lf_ans", s_lf, 0);
   LaunchLfFinish(d_imgs, (const SectionTask*)(d_blob + off_lf_tasks), nlf_t, !no_lf_pipeline, s_lf);
   if (!ds || any_alpha) LaunchHfBlockList(d_imgs, n, max_groups, s_lf);   // (the varblock lists serve hf_decode_kernel alone)
@@ -1494,12 +1307,12 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // Reduced-size decode: the HF tokens are read only to find what follows them in a pass-group section, i.e. for frames with alpha
   // (their pass tasks are the only ones listed); stages that do not run leave no entry in the stage times.
   if (!(skip_stages & 2) && (!ds || npass_t))
-  LaunchHfDecode(d_imgs, (const SectionTask*)(d_blob + off_pass_tasks), npass_t, hf_waves * 64, lane_stride, hf_ring, lds_hf <= kLdsMax ? lds_hf : 0, lds_hf_lanes, s_hf);
+  LaunchHfDecode(d_imgs, (const SectionTask*)(d_blob + off_pass_tasks), npass_t, plan.hf_waves * 64, plan.lane_stride, plan.hf.Bytes(), plan.lds_hf_lanes, s_hf);
   if (!ds || npass_t) Mark("hf_decode", s_hf, 1);
   // alpha follows the HF tokens in every pass-group section (its first bit is where the HF kernel stopped reading): same chain,
   // necessarily; the main stream carries nothing but the pixel stages
   if (any_alpha && !(skip_stages & 4))
-    LaunchAlphaAns(d_imgs, (const SectionTask*)(d_blob + off_alpha_tasks), nalpha_t, alpha_stride, lds_alpha <= kLdsMax ? lds_alpha : 0, direct_alpha, lean_mod, s_hf);
+    LaunchAlphaAns(d_imgs, (const SectionTask*)(d_blob + off_alpha_tasks), nalpha_t, plan.alpha_stride, plan.alpha.Bytes(), plan.direct_alpha, plan.lean_mod, s_hf);
   if (!ds || any_alpha) Mark("alpha_ans", s_hf, 1);
   if (debug_taps && !ds) {   // the quantised coefficients as dense planes (every frame has its own planes in this mode)
     taps.assign(n, Tap());
@@ -1554,9 +1367,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (nmod_t) {
     // Modular (lossless) frames of the batch; they depend on nothing but the upload
     if (s_lf != stream) { HIP_OK(hipEventRecord(S.lf_done, s_lf)); HIP_OK(hipStreamWaitEvent(stream, S.lf_done, 0)); }
-    const int direct_mod = global_direct && mod_lanes == 1;
-    LaunchModularAns(d_imgs, n, (const SectionTask*)(d_blob + off_mod_tasks), nmod_t, lds_mod <= kLdsMax ? lds_mod : 0, max_mod_groups,
-                     max_mod_coded, mod_lanes, mod_rb, mod_wp_lds, direct_mod, stream);
+    LaunchModularAns(d_imgs, n, (const SectionTask*)(d_blob + off_mod_tasks), nmod_t, plan.mod.Bytes(), plan.max_mod_groups,
+                     plan.max_mod_coded, plan.mod_lanes, plan.mod_rb, plan.mod_wp_lds, plan.direct_mod, stream);
     for (auto& op : mod_ops) {
       if (op.kind == 3) LaunchModularPalette(op.a, op.b, op.out, op.nout, op.type, op.rw, op.rh, op.status, stream);   // a: palette, b: indices (rw x rh)
       else LaunchModularOp(op.kind, op.a, op.b, op.c, op.aw, op.ah, op.rw, op.rh, op.type, stream);
@@ -1696,8 +1508,8 @@ void JxlHipDecoder::PrepassSingle(ParsedFrame& f, const uint8_t* dev_file) {
   uint32_t st_words[16] = {0};
   uint64_t lf_end = 0;
   if (e == hipSuccess) {
-    const size_t lds = 64 * 128 + 16 + sizeof(DevTreeNode) * f.tree.size() + 8 + 8 * f.mcode.alias.size() + 4 * f.mcode.cfg.size() + f.mcode.ctx_map.size();
-    LaunchLfAns((const DevImage*)(d + o_img), (const SectionTask*)(d + o_task), 1, 64, lds <= 150 * 1024 ? lds : 0, 0, false, own_stream);
+    const size_t lds = SlotsLdsBytes(64, f.tree.size(), ShapeOf(f.mcode));
+    LaunchLfAns((const DevImage*)(d + o_img), (const SectionTask*)(d + o_task), 1, 64, lds <= kLdsMax ? lds : 0, 0, false, own_stream);
     e = hipStreamSynchronize(own_stream);
   }
   if (e == hipSuccess) e = hipMemcpy(st_words, d + o_status, 64, hipMemcpyDeviceToHost);

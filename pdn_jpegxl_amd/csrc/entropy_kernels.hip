@@ -17,6 +17,7 @@
 #include "dev_types.h"
 #include "dev_util.h"
 #include "kernels.h"
+#include "lds_layout.h"
 
 namespace jxlhip {
 
@@ -63,7 +64,6 @@ typedef unsigned __attribute__((ext_vector_type(4))) U4;   // one MA-tree node (
 // per token).  Instead every lane owns a 32-word window of its stream in LDS (word j at ring[(j & 31) * slots + slot]:
 // lanes reading the same j hit distinct banks); the token loops call TopUp() every 16 tokens (a token consumes at most
 // 48 bits, so 24 words), which is the only place that waits on global memory.
-constexpr int kRingWords = 32;
 constexpr int kTopUpEvery = 16;
 template <int kRing, int kBatch>
 struct LaneBitsT {
@@ -345,24 +345,24 @@ __device__ __forceinline__ uint32_t AnsGet(Bits& b, uint32_t& state, const CodeT
   return HybridTail(b, c, sym);
 }
 
-// Cooperative copy of a code's tables into LDS; returns the carved end offset.
+// Cooperative copy of a code's tables into LDS (layout: CodeLds); returns the carved end offset.
 __device__ __forceinline__ size_t StageCode(JXL_LDS uint8_t* smem, size_t off, const DevCode& dc, CodeTab<true>& t, int tid, int nt,
                                             bool one_section = false) {
-  const uint32_t na = (dc.slow & 1) ? 0u : dc.num_clusters << dc.log_alpha;   // prefix codes have no alias tables
+  const uint32_t na = ShapeOf(dc).AliasEntries();   // prefix codes have no alias tables
   // One-section wavefronts run their row loops on the scalar unit (RowScalar) and read the code's per-residue tables - the alias
   // tables spelled out for each of the 4096 state residues, built by the host for small launches - through the scalar cache: such a
   // wavefront issues an instruction every four to five cycles whatever unit executes it, so its time per token is its instruction
   // count, and the alias arithmetic (bucket, cutoff compare, three selects) is a third of the token.
   t.direct = (one_section && !dc.slow) ? dc.direct : nullptr;
-  off = (off + 7) & ~(size_t)7;
-  JXL_LDS uint64_t* sa = (JXL_LDS uint64_t*)(smem + off); off += (size_t)na * 8;
-  JXL_LDS uint32_t* sc = (JXL_LDS uint32_t*)(smem + off); off += (size_t)dc.num_clusters * 4;
-  JXL_LDS uint8_t* sm = smem + off; off += dc.num_ctx;
+  const CodeLds at(off, ShapeOf(dc));
+  JXL_LDS uint64_t* sa = (JXL_LDS uint64_t*)(smem + at.alias);
+  JXL_LDS uint32_t* sc = (JXL_LDS uint32_t*)(smem + at.cfg);
+  JXL_LDS uint8_t* sm = smem + at.cmap;
   for (uint32_t i = tid; i < na; i += nt) sa[i] = dc.alias[i];
   for (uint32_t i = tid; i < dc.num_clusters; i += nt) sc[i] = dc.cfg[i];
   for (uint32_t i = tid; i < dc.num_ctx; i += nt) sm[i] = dc.ctx_map[i];
   t.cmap = sm; t.cfg = sc; t.alias = sa; t.log_alpha = dc.log_alpha; t.slow = dc.slow; t.dc = &dc;
-  return off;
+  return at.end;
 }
 
 __device__ __forceinline__ void GlobalCode(const DevCode& dc, CodeTab<false>& t) {
@@ -435,7 +435,7 @@ struct WpState {
     w2 = w + 2;
     err = scratch;
     pe = (uint32_t*)(err + 2 * w2);
-    for (int i = 0; i < 10 * w2; i++) err[i] = 0;
+    for (int i = 0; i < kWpStateInts * w2; i++) err[i] = 0;
   }
   static __device__ __forceinline__ uint32_t Div(uint32_t i) { return (1u << 24) / (i + 1); }
   static __device__ __forceinline__ uint32_t ErrorWeight(uint64_t x, uint32_t maxweight) {
@@ -752,7 +752,7 @@ __device__ __forceinline__ void RowScalar(LaneBits& b, uint32_t& state, TabPtr d
 // LDS areas of the one-section-per-wavefront per-sample decoder (modular_uniform.h); unused (null) in every other launch shape
 struct UniAreas {
   JXL_LDS int32_t* rows = nullptr;   // 3 * rw
-  JXL_LDS int32_t* wp = nullptr;     // 10 * (rw + 2), null when the tree does not use the weighted predictor
+  JXL_LDS int32_t* wp = nullptr;     // kWpStateInts * (rw + 2), null when the tree does not use the weighted predictor
   JXL_LDS uint32_t* grid = nullptr;  // kUniGridCells records of 16 bytes
   int rw = 0;
   bool use_wp = false;
@@ -1081,17 +1081,17 @@ struct ModTables {
   typename AS<kLds>::Tree tree;
 };
 
-// Stages the MA tree + modular code of `im` (LDS variant) or points at them in global memory.
+// Stages the MA tree + modular code of `im` (LDS variant, layout: ModTablesLds) or points at them in global memory.
 template <bool kLds>
 __device__ __forceinline__ void LoadModTables(const DevImage& im, uint8_t* smem, size_t off, ModTables<kLds>& t, int tid, int nt,
                                               bool one_section = false) {
   if constexpr (kLds) {
     JXL_LDS uint8_t* lds = (JXL_LDS uint8_t*)smem;
-    off = (off + 15) & ~(size_t)15;
-    JXL_LDS I4* st = (JXL_LDS I4*)(lds + off); off += (size_t)im.tree_size * sizeof(DevTreeNode);
+    const ModTablesLds at(off, (size_t)im.tree_size, ShapeOf(im.mcode));
+    JXL_LDS I4* st = (JXL_LDS I4*)(lds + at.tree);
     for (int i = tid; i < im.tree_size; i += nt) st[i] = ((const I4*)im.tree)[i];
     t.tree = st;
-    StageCode(lds, off, im.mcode, t.tab, tid, nt, one_section);
+    StageCode(lds, at.code, im.mcode, t.tab, tid, nt, one_section);
     __syncthreads();
   } else {
     GlobalCode(im.mcode, t.tab);
@@ -1113,7 +1113,7 @@ __global__ __launch_bounds__(64) void lf_ans_kernel(const DevImage* imgs, const 
   ModTables<kLds> mt;
   // `slots` lanes of the wavefront decode (the launch's sections per workgroup): the bit windows take slots * 128 B of LDS, not 8 KB -
   // LDS is what decides whether this kernel can share a CU with the HF decoder of the batch before
-  LoadModTables<kLds>(im, smem, (size_t)slots * kRingWords * 4, mt, threadIdx.x, 64, slots == 1 && scalar_rows);
+  LoadModTables<kLds>(im, smem, SlotsLds(slots).tables, mt, threadIdx.x, 64, slots == 1 && scalar_rows);
   const int lane = threadIdx.x;
   if (lane >= task.count || lane >= slots) return;
   const int g = task.first + lane;
@@ -1440,13 +1440,13 @@ template <bool kLds, int kRing>
 __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, const SectionTask* tasks, int lane_stride) {
   JXL_SERIAL_PRIO();
   constexpr int kTop = kRing / 2;   // tokens between top-ups: a token consumes at most 48 bits and starts at most one block ...
-  constexpr int kQ = kRing / 4;     // ... so kTop tokens never outrun kRing - kRing / 4 + 1 words / kTop / 3 + 1 descriptors
+  constexpr int kQ = HfQueueDepth(kRing);   // ... so kTop tokens never outrun kRing - kRing / 4 + 1 words / kTop / 3 + 1 descriptors
   typedef LaneBitsT<kRing, kRing / 4> Bits;
   extern __shared__ __align__(16) uint8_t smem[];
   const SectionTask task = tasks[blockIdx.x];
   const DevImage& im = imgs[task.image];
   const int per_wave = 64 / lane_stride;
-  const int nslots = (task.count + 3) & ~3;
+  const int nslots = HfSlots(task.count);
   CodeTab<kLds> tab;
   typename AS<kLds>::U8 nnz_tab;
   JXL_LDS uint8_t* nzcol;
@@ -1454,14 +1454,13 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
   JXL_LDS uint32_t* descq;   // per lane: queue of the next 2 * kQ varblock descriptors, entry j at descq[(j & (2 * kQ - 1)) * nslots + slot]
   {
     JXL_LDS uint8_t* lds = (JXL_LDS uint8_t*)smem;
-    size_t off = 0;
-    ring_base = (JXL_LDS uint32_t*)lds; off += (size_t)nslots * kRing * 4;
-    descq = (JXL_LDS uint32_t*)(lds + off); off += (size_t)nslots * 2 * kQ * 4;
-    nzcol = lds + off; off += (size_t)nslots * 96;
+    const HfLds at(nslots, kRing);
+    ring_base = (JXL_LDS uint32_t*)(lds + at.ring);
+    descq = (JXL_LDS uint32_t*)(lds + at.descq);
+    nzcol = lds + at.nzcol;
     if constexpr (kLds) {
-      off = StageCode(lds, off, im.acode, tab, threadIdx.x, blockDim.x);
-      JXL_LDS uint8_t* sn = lds + off; off += 64;
-      if (threadIdx.x < 64) sn[threadIdx.x] = d_nnz_ctx[threadIdx.x];
+      JXL_LDS uint8_t* sn = lds + StageCode(lds, at.tables, im.acode, tab, threadIdx.x, blockDim.x);   // kNnzCtxBytes behind the code
+      if (threadIdx.x < kNnzCtxBytes) sn[threadIdx.x] = d_nnz_ctx[threadIdx.x];
       nnz_tab = sn;
       __syncthreads();
     } else {
@@ -1475,7 +1474,7 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
   const int si = (threadIdx.x >> 6) * per_wave + (threadIdx.x & 63);
   if (si >= task.count || si >= nslots) return;
   JXL_LDS uint8_t* const col = nzcol + si;   // col[(c * 32 + x) * nslots]
-  const int g = im.hf_order[task.first + si];   // lanes in order of section size (see the task table in decoder.cc)
+  const int g = im.hf_order[task.first + si];   // lanes in order of section size (see the task table in entropy_plan.cc)
   const int sec = im.single ? 0 : im.hf_sec_base + g;
   const uint64_t sec_bits = im.single ? im.hf_start_bits : im.sec_off[sec] * 8;
   Bits b;
@@ -1870,7 +1869,7 @@ __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, con
   if (!im.has_alpha || im.alpha_in_global) return;
   ModTables<kLds> mt;
   const int slots = 64 / lane_stride;
-  LoadModTables<kLds>(im, smem, (size_t)slots * kRingWords * 4, mt, threadIdx.x, 64, slots == 1 && scalar_rows);
+  LoadModTables<kLds>(im, smem, SlotsLds(slots).tables, mt, threadIdx.x, 64, slots == 1 && scalar_rows);
   const int lane = threadIdx.x;
   if (lane >= slots || lane >= task.count) return;
   const int g = task.first + lane;
@@ -2211,11 +2210,8 @@ __global__ __launch_bounds__(64) void modular_ans_kernel(const DevImage* imgs, c
   const SectionTask task = tasks[blockIdx.x];
   const DevImage& im = imgs[task.image];
   // LDS: bit windows | previous-row buffers (rb_width ints per lane, interleaved) | weighted-predictor state | tree + code
-  const size_t off_rows = (size_t)64 * kRingWords * 4;
-  const size_t off_wp = off_rows + (size_t)(kUni ? 3 : lanes) * rb_width * 4;
-  const size_t wp_ints = (size_t)10 * (rb_width + 2);
-  const size_t off_grid = off_wp + (wp_lds ? (size_t)lanes * wp_ints * 4 : 0);
-  const size_t off_tab = off_grid + (kUni ? (size_t)kUniGridCells * 16 : 0);
+  const ModularLds at(lanes, rb_width, wp_lds, kUni);
+  const size_t off_rows = at.rows, off_wp = at.wp, wp_ints = at.wp_ints, off_grid = at.grid, off_tab = at.tables;
   ModTables<kLds> mt;
   LoadModTables<kLds>(im, smem, off_tab, mt, threadIdx.x, 64, lanes == 1 && scalar_rows);
   const int lane = kUni ? 0 : (int)threadIdx.x;   // kUni: every lane plays lane 0 (same slot, same section)
@@ -2445,7 +2441,7 @@ void LaunchLfAns(const DevImage* imgs, const SectionTask* tasks, int ntasks, int
     RaiseLds((const void*)lf_ans_kernel<true>, lds_bytes);
     hipLaunchKernelGGL(lf_ans_kernel<true>, dim3(ntasks), dim3(64), lds_bytes, s, imgs, tasks, slots, scalar_rows);
   } else {
-    hipLaunchKernelGGL(lf_ans_kernel<false>, dim3(ntasks), dim3(64), (size_t)slots * kRingWords * 4, s, imgs, tasks, slots, 0);
+    hipLaunchKernelGGL(lf_ans_kernel<false>, dim3(ntasks), dim3(64), SlotsLds(slots).tables, s, imgs, tasks, slots, 0);
   }
 }
 
@@ -2461,18 +2457,16 @@ void LaunchHfBlockList(const DevImage* imgs, int nimg, int max_groups, hipStream
   hipLaunchKernelGGL(hf_blocklist_kernel, dim3(max_groups, nimg), dim3(64), 0, s, imgs);
 }
 
-size_t HfLaneLdsBytes(int ring_words) { return 96 + (size_t)ring_words * 4 + (size_t)(ring_words / 2) * 4; }
-
-void LaunchHfDecode(const DevImage* imgs, const SectionTask* tasks, int nwg, int threads, int lane_stride, int ring_words,
-                    size_t lds_bytes, size_t lane_bytes, hipStream_t s) {
+void LaunchHfDecode(const DevImage* imgs, const SectionTask* tasks, int nwg, int threads, int lane_stride, size_t lds_bytes, size_t lane_bytes,
+                    hipStream_t s) {
   if (nwg <= 0) return;   // lds_bytes: tables + lanes of the largest workgroup; lane_bytes: the lanes alone (tables in global memory)
-  (void)ring_words;   // one window size: 32 words (a 16-word variant paid off while the coefficient orders lived in LDS; not any more)
+  // one window size: kHfRingWords (a 16-word variant paid off while the coefficient orders lived in LDS; not any more)
   if (lds_bytes) {
-    RaiseLds((const void*)hf_decode_kernel<true, 32>, lds_bytes);
-    hipLaunchKernelGGL((hf_decode_kernel<true, 32>), dim3(nwg), dim3(threads), lds_bytes, s, imgs, tasks, lane_stride);
+    RaiseLds((const void*)hf_decode_kernel<true, kHfRingWords>, lds_bytes);
+    hipLaunchKernelGGL((hf_decode_kernel<true, kHfRingWords>), dim3(nwg), dim3(threads), lds_bytes, s, imgs, tasks, lane_stride);
   } else {
-    RaiseLds((const void*)hf_decode_kernel<false, 32>, lane_bytes);
-    hipLaunchKernelGGL((hf_decode_kernel<false, 32>), dim3(nwg), dim3(threads), lane_bytes, s, imgs, tasks, lane_stride);
+    RaiseLds((const void*)hf_decode_kernel<false, kHfRingWords>, lane_bytes);
+    hipLaunchKernelGGL((hf_decode_kernel<false, kHfRingWords>), dim3(nwg), dim3(threads), lane_bytes, s, imgs, tasks, lane_stride);
   }
 }
 
@@ -2485,21 +2479,21 @@ void LaunchAlphaAns(const DevImage* imgs, const SectionTask* tasks, int nwg, int
     RaiseLds((const void*)alpha_ans_kernel<true>, lds_bytes);
     hipLaunchKernelGGL(alpha_ans_kernel<true>, dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows);
   } else {
-    hipLaunchKernelGGL(alpha_ans_kernel<false>, dim3(nwg), dim3(64), (size_t)(64 / lane_stride) * kRingWords * 4, s, imgs, tasks, lane_stride, 0);
+    hipLaunchKernelGGL(alpha_ans_kernel<false>, dim3(nwg), dim3(64), SlotsLds(64 / lane_stride).tables, s, imgs, tasks, lane_stride, 0);
   }
 }
 
 void LaunchModularAns(const DevImage* imgs, int nimg, const SectionTask* tasks, int ntasks, size_t lds_bytes, int max_sections, int max_coded,
                       int lanes, int rb_width, int wp_lds, int scalar_rows, hipStream_t s) {
   if (ntasks <= 0) return;
-  if (lds_bytes && lanes == 1 && rb_width > 0) {   // one section per wavefront: the uniform shape (host sizes lds_bytes for its layout)
+  if (lds_bytes && ModularUniform(lanes, rb_width)) {   // one section per wavefront: the uniform shape (host sizes lds_bytes for its layout)
     RaiseLds((const void*)modular_ans_kernel<true, true>, lds_bytes);
     hipLaunchKernelGGL((modular_ans_kernel<true, true>), dim3(ntasks), dim3(64), lds_bytes, s, imgs, tasks, lanes, rb_width, wp_lds, scalar_rows);
   } else if (lds_bytes) {
     RaiseLds((const void*)modular_ans_kernel<true>, lds_bytes);
     hipLaunchKernelGGL(modular_ans_kernel<true>, dim3(ntasks), dim3(64), lds_bytes, s, imgs, tasks, lanes, rb_width, wp_lds, scalar_rows);
   } else {
-    const size_t lds = (size_t)64 * kRingWords * 4 + (size_t)lanes * rb_width * 4 + (wp_lds ? (size_t)lanes * 10 * (rb_width + 2) * 4 : 0);
+    const size_t lds = ModularLds(lanes, rb_width, wp_lds, false).tables;
     RaiseLds((const void*)modular_ans_kernel<false>, lds);
     hipLaunchKernelGGL(modular_ans_kernel<false>, dim3(ntasks), dim3(64), lds, s, imgs, tasks, lanes, rb_width, wp_lds, 0);
   }

@@ -452,7 +452,7 @@ __device__ __forceinline__ void UniRows(UniCtx& c, LaneBits& b) {
 }
 
 // Returns false when the channel has to take the old path (general symbol reader, rows wider than the LDS rows).
-// lds_rows: 3 * rw ints; lds_wp: 10 * (rw + 2) ints (null: the tree does not use the weighted predictor); lds_grid: grid_cells
+// lds_rows: kUniRows * rw ints; lds_wp: kWpStateInts * (rw + 2) ints (null: the tree does not use the weighted predictor); lds_grid: grid_cells
 // records of 16 bytes.
 __device__ __forceinline__ bool ModularChannelUniform(LaneBits& b, uint32_t& state_io, const CodeTab<true>& tab_in, const JXL_LDS I4* tree_in, int chan_in, int sid_in,
                                                    int w_in, int h_in, int32_t* out_generic, int stride_in, JXL_LDS int32_t* lds_rows_in, int rw_in,
@@ -655,7 +655,7 @@ __device__ __forceinline__ bool ModularChannelUniform(LaneBits& b, uint32_t& sta
   const uint32_t ncl = JXL_RFL(dc->num_clusters);
   c.vcfg = (int32_t)((uint32_t)lane < ncl ? c.cfg[lane] : 0u);
   c.cfg_in_lanes = ncl <= 64;
-  if (use_wp) for (int i = lane; i < 10 * c.w2; i += 64) lds_wp[i] = 0;
+  if (use_wp) for (int i = lane; i < kWpStateInts * c.w2; i += 64) lds_wp[i] = 0;
   // the stream state in scalar registers
   c.s_state = JXL_RFL(state_io); c.s_rd = JXL_RFL(b.rd);
   c.s_buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);

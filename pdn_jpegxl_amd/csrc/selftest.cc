@@ -10,6 +10,7 @@
 #include "../../include/jxlfiletypeio.h"
 #include "dev_util.h"
 #include "enc_types.h"
+#include "entropy_plan.h"
 #include "host_parse.h"
 #include "host_write.h"
 #include "icc.h"
@@ -311,4 +312,106 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_lossless_file(uint32_t w, ui
   } catch (...) {
     return 0;
   }
+}
+
+// The LDS layouts of the entropy kernels (lds_layout.h) as numbers, for tests/test_entropy_plan.py.  in: the numbers a layout is made
+// from, a code's shape being (clusters, log_alpha, contexts, prefix); out: its pieces' offsets in carving order, its end, then the sizes
+// the host launches with.  Returns how many numbers it wrote (0: unknown kind).
+//   0 code          in: off, shape                                   out: alias, cfg, cmap, end | CodeLdsBytes
+//   1 tree + code   in: off, nodes, shape                            out: tree, alias, cfg, cmap, end | ModTablesLdsBytes
+//   2 lf / alpha    in: slots, nodes, shape                          out: windows, tree, alias, cfg, cmap, end | SlotsLdsBytes, lanes only
+//   3 Modular       in: lanes, rb_width, wp_lds, uniform, nodes, shape   out: windows, rows, wp, grid, tree, alias, cfg, cmap, end | ModularLdsBytes, lanes only
+//   4 HF            in: sections, shape                              out: ring, descq, nzcol, alias, cfg, cmap, nnz, end | tables + lanes, lanes only, slots
+//   5 constants     out: kLdsMax, kRingWords, kHfRingWords, kNzColBytes, kNnzCtxBytes, kWpStateInts, kUniRows, kUniGridBytes, sizeof(DevTreeNode)
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_lds_layout(int32_t kind, const int64_t* in, int64_t* out) {
+  int k = 0;
+  auto put = [&](size_t v) { out[k++] = (int64_t)v; };
+  auto shape = [&](int at) { return CodeShape{(uint32_t)in[at], (uint32_t)in[at + 1], (uint32_t)in[at + 2], in[at + 3] != 0}; };
+  auto put_code = [&](const CodeLds& c) { put(c.alias); put(c.cfg); put(c.cmap); };
+  if (kind == 0) {
+    const CodeLds c((size_t)in[0], shape(1));
+    put_code(c); put(c.end); put(CodeLdsBytes(shape(1)));
+  } else if (kind == 1) {
+    const ModTablesLds t((size_t)in[0], (size_t)in[1], shape(2));
+    put(t.tree); put_code(CodeLds(t.code, shape(2))); put(t.end); put(ModTablesLdsBytes((size_t)in[1], shape(2)));
+  } else if (kind == 2) {
+    const SlotsLds l((int)in[0]);
+    const ModTablesLds t(l.tables, (size_t)in[1], shape(2));
+    put(0); put(t.tree); put_code(CodeLds(t.code, shape(2))); put(t.end);
+    put(SlotsLdsBytes((int)in[0], (size_t)in[1], shape(2))); put(l.tables);
+  } else if (kind == 3) {
+    const ModularLds l((int)in[0], (int)in[1], (int)in[2], in[3] != 0);
+    const ModTablesLds t(l.tables, (size_t)in[4], shape(5));
+    put(0); put(l.rows); put(l.wp); put(l.grid); put(t.tree); put_code(CodeLds(t.code, shape(5))); put(t.end);
+    put(ModularLdsBytes((int)in[0], (int)in[1], (int)in[2], in[3] != 0, (size_t)in[4], shape(5)));
+    put(ModularLds((int)in[0], (int)in[1], (int)in[2], false).tables);
+  } else if (kind == 4) {
+    const int nslots = HfSlots((int)in[0]);
+    const HfLds l(nslots, kHfRingWords);
+    const CodeLds c(l.tables, shape(1));
+    put(l.ring); put(l.descq); put(l.nzcol); put_code(c); put(c.end); put(HfTablesEnd(l.tables, shape(1)));
+    put(HfTablesBytes(shape(1)) + HfLaneBytes(nslots)); put(HfLaneBytes(nslots)); put((size_t)nslots);
+  } else if (kind == 5) {
+    put(kLdsMax); put(kRingWords); put(kHfRingWords); put(kNzColBytes); put(kNnzCtxBytes); put(kWpStateInts); put(kUniRows); put(kUniGridBytes);
+    put(sizeof(DevTreeNode));
+  }
+  return k;
+}
+
+// Parses n files on the host and plans their batch's entropy stage (entropy_plan.h; nothing touches a GPU).  opts: band first row, band
+// rows, downscale, lane_stride_override, no_direct, mod_lanes64.  One-group lossy frames are planned without the LF pre-pass that reads
+// their HfGlobal (the plan needs no hf_start_bits): their HF code is empty here.  The plan goes to out as numbers, in the order written below; returns
+// how many (0: they do not fit `capacity`).
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_entropy_plan(int32_t n, const uint8_t* const* data, const size_t* sizes, const int32_t* opts,
+                                                                 int64_t* out, size_t capacity) {
+  std::vector<ParsedFrame> frames((size_t)n);
+  std::vector<int> status((size_t)n, DecoderStatus_Ok);
+  for (int i = 0; i < n; i++) {
+    try {
+      ParseFile(data[i], sizes[i], false, frames[i]);
+    } catch (const std::exception&) {
+      status[i] = DecoderStatus_DecodeError;
+    }
+  }
+  EntropyPlanOptions o;
+  o.band_first_row = opts[0]; o.band_rows = opts[1]; o.downscale = opts[2]; o.lane_stride_override = opts[3];
+  o.no_direct = opts[4] != 0; o.mod_lanes64 = opts[5] != 0;
+  const EntropyPlan P = PlanEntropy(frames, status, o);
+  std::vector<int64_t> v;
+  auto put = [&](int64_t x) { v.push_back(x); };
+  auto put_shape = [&](const HostCode& hc) { const CodeShape s = ShapeOf(hc); put(s.clusters); put(s.log_alpha); put(s.contexts); put(s.prefix); };
+  for (int64_t x : {(int64_t)n, (int64_t)P.n_extra, (int64_t)P.global_direct, (int64_t)P.lean_mod, (int64_t)P.lane_stride, (int64_t)P.hf_waves,
+                    (int64_t)P.alpha_stride, (int64_t)P.per_alpha_wg, (int64_t)P.lf_per_wave, (int64_t)P.mod_lanes, (int64_t)P.mod_rb, (int64_t)P.mod_wp_lds,
+                    (int64_t)P.direct_lf, (int64_t)P.direct_alpha, (int64_t)P.direct_mod, (int64_t)P.lf.lds, (int64_t)P.lf.global, (int64_t)P.hf.lds,
+                    (int64_t)P.hf.global, (int64_t)P.lds_hf_lanes, (int64_t)P.alpha.lds, (int64_t)P.alpha.global, (int64_t)P.mod.lds, (int64_t)P.mod.global,
+                    (int64_t)P.max_mod_groups, (int64_t)P.max_mod_coded})
+    put(x);
+  for (int i = 0; i < n; i++) {
+    const ParsedFrame& f = frames[i];
+    const FramePlan& r = P.frames[i];
+    for (int64_t x : {(int64_t)status[i], (int64_t)r.decoded, (int64_t)f.encoding, (int64_t)f.single, (int64_t)f.xg, (int64_t)f.yg, (int64_t)f.ng, (int64_t)f.xlf,
+                      (int64_t)f.ylf, (int64_t)f.nlf, (int64_t)f.num_passes, (int64_t)(f.alpha_index >= 0), (int64_t)f.ysize, (int64_t)f.tree.size(),
+                      (int64_t)f.tree_row_static, (int64_t)f.tree_uses_wp, (int64_t)r.dec_gy0, (int64_t)r.dec_gy1, (int64_t)r.band_y0, (int64_t)r.band_y1,
+                      (int64_t)r.lf0, (int64_t)r.lf1, (int64_t)r.hf0, (int64_t)r.hf1, (int64_t)r.alpha0, (int64_t)r.alpha1, (int64_t)r.hf, (int64_t)r.first_extra,
+                      (int64_t)r.hf_per_wg, (int64_t)r.hf_table_bytes})
+      put(x);
+    put_shape(f.mcode);
+    put((int64_t)(1 + f.extra_passes.size()));
+    put_shape(f.acode);
+    for (auto& ep : f.extra_passes) put_shape(ep.acode);
+    put((int64_t)f.sec_size.size());
+    for (uint32_t s : f.sec_size) put(s);
+  }
+  for (const std::vector<SectionTask>* t : {&P.lf_finish_tasks, &P.lf_ans_tasks, &P.pass_tasks, &P.alpha_tasks, &P.mod_tasks}) {
+    put((int64_t)t->size());
+    for (const SectionTask& k : *t) { put(k.image); put(k.first); put(k.count); }
+  }
+  put((int64_t)P.hf_orders.size());
+  for (auto& ho : P.hf_orders) {
+    put(ho.image); put(ho.pass); put((int64_t)ho.order.size());
+    for (uint32_t g : ho.order) put(g);
+  }
+  if (v.size() > capacity) return 0;
+  memcpy(out, v.data(), v.size() * sizeof(int64_t));
+  return v.size();
 }
