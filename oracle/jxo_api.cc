@@ -95,6 +95,10 @@ static thread_local bool g_next_cmyk = false;
 static thread_local int g_next_frames = 1;
 static thread_local uint32_t g_next_flags = 0;   // 1: explicit (custom) dequantisation tables; 2: prefix codes; 4: LZ77; 8 / 16: two / three passes; 32: custom coefficient orders; 64: block contexts from LF / quant-field thresholds; 128: palette; 256: some DCT8 blocks labelled AFV (refusal tests); 512: alpha signalled as premultiplied
 void jxo_set_next_flags(uint32_t flags) { g_next_flags = flags; }
+// Side information of the next lossy frame (jxo_codec.h: SideInfo, a plain struct of 32-bit fields that ctypes mirrors)
+static thread_local SideInfo g_next_side;
+void jxo_set_next_side_info(const SideInfo* s) { g_next_side = *s; }
+size_t jxo_side_info_size() { return sizeof(SideInfo); }
 void jxo_set_next_animation(int frames) { g_next_frames = frames; }
 void jxo_set_next_icc(const uint8_t* icc, size_t size, int cmyk) {
   g_next_icc.assign(icc ? icc : nullptr, icc ? icc + size : nullptr);
@@ -143,6 +147,7 @@ JxoBytes* jxo_encode(const uint8_t* px, uint32_t w, uint32_t h, int32_t nch, con
     p.mislabel_afv = (g_next_flags & 256) != 0;
     p.premultiplied_alpha = (g_next_flags & 512) != 0;
     p.num_passes = (g_next_flags & 16) ? 3 : ((g_next_flags & 8) ? 2 : 1);
+    p.side = g_next_side; g_next_side = SideInfo();
     const uint32_t g_next_flags_entropy = g_next_flags;
     g_next_flags = 0;
     JxoBytes* b = new JxoBytes();

@@ -47,7 +47,45 @@ struct DecodeOptions {
 
 void DecodeJxl(const uint8_t* data, size_t size, const DecodeOptions& opt, DecodeResult& out);
 
+// Side information of a lossy frame that the writer can vary (parity-test coverage; the defaults are what every stream carried
+// before this existed and keep its bytes).  Every float that the stream stores as F16 is rounded first and the writer itself works
+// with the rounded value.  The layout is mirrored by tests/oracle_lib.py (SideInfo) and handed over through jxo_set_next_side_info.
+//
+// The formula modes draw from one integer hash of (seed, x, y, k), all arithmetic modulo 2^32:
+//   u = seed * 0x9E3779B1 + x * 0x85EBCA6B + y * 0xC2B2AE35 + k * 0x27D4EB2F;  u ^= u >> 15;  u *= 0x2C1B3C6D;  u ^= u >> 12
+//   ytox[ty, tx] = (u(seed, tx, ty, 0) & 255) - 128, ytob[ty, tx] = (u(seed, tx, ty, 1) & 255) - 128   (64 x 64 tiles of the frame)
+//   sharpness[by, bx] = u(seed, bx, by, 2) & 7                                                          (8 x 8 cells of the frame)
+// and then pin the extremes: tile 0 of the frame holds (ytox, ytob) = (-128, 127), tile 1 (127, -128); cell 0 holds 0, cell 1 holds 7.
+struct SideInfo {
+  int32_t cfl_mode = 0;        // 0: both maps zero (Zero-predictor leaf, every residual 0); 1: fitted - per tile the least-squares factor of X
+                               // and of B on the dequantised Y over the tile's HF coefficients (Zero predictor); 2: formula (Gradient predictor)
+  int32_t sharp_mode = 0;      // 0: 4 in every cell (Zero predictor + leaf offset 4, every residual 0); 1: formula (Gradient predictor);
+                               // 2: `sharp_value` in every cell (Zero predictor, no leaf offset: one real token per cell)
+  int32_t sharp_value = 4;
+  uint32_t seed = 0;
+  int32_t refuse = 0;          // REFUSAL TESTS ONLY.  1: the last cell's sharpness is 8; 2: the last tile's ytox is 128 (outside int8)
+  int32_t custom_cfl = 0;      // LfGlobal carries the five chroma-from-luma parameters below
+  uint32_t color_factor = 84;
+  float base_x = 0.f, base_b = 1.f;
+  int32_t ytox_lf = 0, ytob_lf = 0;          // -128 ... 127
+  int32_t custom_lf_factors = 0;
+  float lf_factor[3] = {1.0f / 32, 1.0f / 4, 1.0f / 2};   // as stored: 128 x the step of X, Y, B at global_scale * quant_lf = 65536
+  int32_t x_qm_scale = -1, b_qm_scale = -1;  // -1: the defaults 3 and 2
+  int32_t custom_gab = 0;
+  float gab_w1[3] = {0, 0, 0}, gab_w2[3] = {0, 0, 0};
+  int32_t custom_sharp_lut = 0;
+  float sharp_lut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t custom_epf_weights = 0;
+  float epf_channel_scale[3] = {40.0f, 5.0f, 3.5f};
+  int32_t custom_epf_sigma = 0;
+  float epf_quant_mul = 0.46f, epf_pass0_sigma_scale = 0.9f, epf_pass2_sigma_scale = 6.5f, epf_border_sad_mul = 2.0f / 3;
+  int32_t custom_transform = 0;   // custom transform data: inverse opsin matrix and biases at their defaults as F16 rounds them, and these
+  float quant_bias[4] = {0, 0, 0, 0};   // quant biases (the writer dequantises Y with them for its chroma-from-luma compensation)
+};
+uint32_t SideInfoHash(uint32_t seed, uint32_t x, uint32_t y, uint32_t k);
+
 struct EncodeParams {
+  SideInfo side;
   float distance = 1.0f;
   bool lossless = false;
   int effort = 7;

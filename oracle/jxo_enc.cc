@@ -42,7 +42,7 @@ struct TreeBuilder {
   }
 };
 
-Tree MakeVarDctTree(uint32_t nlf) {
+Tree MakeVarDctTree(uint32_t nlf, const SideInfo& side) {
   TreeBuilder b;
   // alpha: one gradient-predicted context (extra local-gradient contexts bought < 0.01 % on the synthetic masks and
   // cost a tree walk per sample in every decoder)
@@ -52,10 +52,12 @@ Tree MakeVarDctTree(uint32_t nlf) {
   int lf1 = b.Split(0, 0, lf_x, lf_y);
   int lfn = b.Split(0, 1, lf_b, lf1);
   // HF metadata
-  // constant maps (EPF sharpness 4, chroma-from-luma 0): Zero predictor + leaf offset => every residual is 0, the
-  // cluster has a single symbol and a decoder can fill the channel without touching the stream
-  int sharp = b.Leaf(0), qrow = b.Leaf(1), srow = b.Leaf(0), cfl = b.Leaf(0);
-  b.t[sharp].offset = 4;
+  // by default constant maps (EPF sharpness 4, chroma-from-luma 0): Zero predictor + leaf offset => every residual is 0, the
+  // cluster has a single symbol and a decoder can fill the channel without touching the stream.  Maps that vary (SideInfo) get
+  // real leaves: the formula modes a Gradient predictor, the fitted chroma-from-luma maps and the constant sharpness of
+  // sharp_mode 2 a Zero predictor without offset, so both predictor kinds run on these planes and every sample costs a token
+  int sharp = b.Leaf(side.sharp_mode == 1 ? 5 : 0), qrow = b.Leaf(1), srow = b.Leaf(0), cfl = b.Leaf(side.cfl_mode == 2 ? 5 : 0);
+  if (side.sharp_mode == 0) b.t[sharp].offset = 4;
   int binfo = b.Split(2, 0, qrow, srow);
   int m1 = b.Split(0, 1, binfo, cfl);
   int meta = b.Split(0, 2, sharp, m1);
@@ -149,6 +151,8 @@ struct VarDctEncoder {
   uint32_t global_scale, quant_lf;
   DequantMatrices dq;
   BlockCtxMap bctx;
+  std::vector<int32_t> ytox, ytob;   // per 64 x 64 tile of the frame (int32: the refusal switch writes a value outside int8)
+  std::vector<int32_t> sharp;        // per cell
   std::vector<int32_t> lfq[3];
   std::vector<int32_t> alpha;
   bool has_alpha;
@@ -298,7 +302,7 @@ struct VarDctEncoder {
           img[2].d[i] = (float)((inv[6] * r + inv[7] * g + inv[8] * b) * sc);
         }
     }
-    LinearToXyb(img);
+    LinearToXyb(img, &m);
     // 2. approximate inverse of the decoder-side Gaborish: 2*I - K
     if (f.lf.gab) {
       Plane blur[3] = {img[0], img[1], img[2]};
@@ -322,16 +326,95 @@ struct VarDctEncoder {
     bctx.SetDefault();
     ChooseStrategies();
     const float inv_gs = 65536.0f / global_scale;
-    const float m_lf[3] = {1.0f / 4096, 1.0f / 512, 1.0f / 256};
+    const SideInfo& side = p.side;
+    float m_lf[3] = {1.0f / 4096, 1.0f / 512, 1.0f / 256};
+    if (side.custom_lf_factors) for (int c = 0; c < 3; c++) m_lf[c] = side.lf_factor[c] * (1.0f / 128);
     float mul_lf[3];
     for (int c = 0; c < 3; c++) mul_lf[c] = m_lf[c] * inv_gs / quant_lf;
+    // chroma-from-luma: what the decoder adds is (base + map / color_factor) * Y, so X and B code what is left of them after that
+    const uint32_t color_factor = side.custom_cfl ? side.color_factor : 84;
+    const float base_x = side.custom_cfl ? side.base_x : 0.0f, base_b = side.custom_cfl ? side.base_b : 1.0f;
+    const float lf_fac_x = base_x + (side.custom_cfl ? side.ytox_lf : 0) * (1.0f / color_factor);
+    const float lf_fac_b = base_b + (side.custom_cfl ? side.ytob_lf : 0) * (1.0f / color_factor);
     // 4. transforms, LF, quantised AC (kept per varblock)
     const size_t ncell = (size_t)w8 * h8;
     for (int c = 0; c < 3; c++) lfq[c].assign(ncell, 0);
     std::vector<std::vector<int32_t>> qac[3];  // per cell (first cells only): quantised block in stored layout
     for (int c = 0; c < 3; c++) qac[c].resize(ncell);
     const float xmul = std::pow(0.8f, (float)f.x_qm_scale - 2.0f), bmul = std::pow(0.8f, (float)f.b_qm_scale - 2.0f);
-    const float base_b = 1.0f;
+    // the maps
+    ytox.assign((size_t)wt * ht, 0);
+    ytob.assign((size_t)wt * ht, 0);
+    sharp.assign(ncell, side.sharp_mode == 2 ? side.sharp_value : 4);
+    if (side.sharp_mode == 1) {
+      for (int by = 0; by < h8; by++)
+        for (int bx = 0; bx < w8; bx++) sharp[(size_t)by * w8 + bx] = (int32_t)(SideInfoHash(side.seed, bx, by, 2) & 7);
+      sharp[0] = 0;
+      if (ncell > 1) sharp[1] = 7;
+    }
+    if (side.cfl_mode == 2) {
+      for (int ty = 0; ty < ht; ty++)
+        for (int tx = 0; tx < wt; tx++) {
+          ytox[(size_t)ty * wt + tx] = (int32_t)(SideInfoHash(side.seed, tx, ty, 0) & 255) - 128;
+          ytob[(size_t)ty * wt + tx] = (int32_t)(SideInfoHash(side.seed, tx, ty, 1) & 255) - 128;
+        }
+      ytox[0] = -128; ytob[0] = 127;
+      if (ytox.size() > 1) { ytox[1] = 127; ytob[1] = -128; }
+    }
+    // Y of one varblock: quantised values and what the decoder makes of them (its quant biases included)
+    auto quant_y = [&](int s, size_t cell, const float* coef_y, std::vector<int32_t>* q, float* yd) {
+      const size_t size = (size_t)kCoveredX[s] * kCoveredY[s] * 64;
+      const float dqs = inv_gs / raw_quant[cell];
+      const float* wq = dq.Get(s, 1);
+      if (q) q->assign(size, 0);
+      for (size_t k = 0; k < size; k++) {
+        float v = coef_y[k] / (dqs * wq[k]);
+        float a = std::fabs(v);
+        int32_t qi = a < 0.6f ? 0 : (int32_t)std::lrint(v);
+        if (q) (*q)[k] = qi;
+        float adj = qi == 0 ? 0 : (std::abs(qi) == 1 ? (qi > 0 ? m.quant_bias[1] : -m.quant_bias[1]) : qi - m.quant_bias[3] / qi);
+        yd[k] = adj * dqs * wq[k];
+      }
+    };
+    if (side.cfl_mode == 1) {
+      // fitted maps: per tile the least-squares factor of X and of B on the dequantised Y over the HF coefficients of the varblocks
+      // that start in the tile (the tile whose factor the decoder applies to them), as a step of 1 / color_factor above the base
+      // correlation, rounded and clamped to int8.  Sums are kept per cell row and added up in row order: the result does not depend
+      // on the number of threads.
+      std::vector<double> sxy((size_t)h8 * wt, 0.0), sby((size_t)h8 * wt, 0.0), syy((size_t)h8 * wt, 0.0);
+      ParallelFor(h8, p.num_threads, [&](int by) {
+        std::vector<float> coef[3], yd;
+        for (int bx = 0; bx < w8; bx++) {
+          size_t cell = (size_t)by * w8 + bx;
+          if (!(strategy[cell] & 0x80)) continue;
+          int s = strategy[cell] & 0x7F, cx = kCoveredX[s], cy = kCoveredY[s];
+          size_t size = (size_t)cx * cy * 64;
+          for (int c = 0; c < 3; c++) {
+            coef[c].resize(size);
+            ForwardTransform(s, xyb[c].Row(by * 8) + bx * 8, wp, coef[c].data());
+          }
+          yd.resize(size);
+          quant_y(s, cell, coef[1].data(), nullptr, yd.data());
+          const uint32_t* nat = NaturalOrder(s).data();
+          double a = 0, b = 0, d = 0;
+          for (size_t k = (size_t)cx * cy; k < size; k++) {
+            const size_t pos = nat[k];
+            a += (double)coef[0][pos] * yd[pos]; b += (double)coef[2][pos] * yd[pos]; d += (double)yd[pos] * yd[pos];
+          }
+          sxy[(size_t)by * wt + bx / 8] += a; sby[(size_t)by * wt + bx / 8] += b; syy[(size_t)by * wt + bx / 8] += d;
+        }
+      });
+      for (int ty = 0; ty < ht; ty++)
+        for (int tx = 0; tx < wt; tx++) {
+          double a = 0, b = 0, d = 0;
+          for (int by = ty * 8; by < std::min(h8, ty * 8 + 8); by++) { a += sxy[(size_t)by * wt + tx]; b += sby[(size_t)by * wt + tx]; d += syy[(size_t)by * wt + tx]; }
+          if (d <= 0) continue;
+          ytox[(size_t)ty * wt + tx] = (int32_t)std::max(-128L, std::min(127L, std::lrint((a / d - base_x) * color_factor)));
+          ytob[(size_t)ty * wt + tx] = (int32_t)std::max(-128L, std::min(127L, std::lrint((b / d - base_b) * color_factor)));
+        }
+    }
+    if (side.refuse == 1) sharp[ncell - 1] = 8;
+    if (side.refuse == 2) ytox[ytox.size() - 1] = 128;
     ParallelFor(h8, p.num_threads, [&](int by) {
       std::vector<float> coef[3], lfv;
       for (int bx = 0; bx < w8; bx++) {
@@ -352,36 +435,32 @@ struct VarDctEncoder {
             int32_t qy = (int32_t)std::lrint(lfs[1][iy * cx + ix] / mul_lf[1]);
             float fy = qy * mul_lf[1];
             lfq[1][cc] = qy;
-            lfq[0][cc] = (int32_t)std::lrint(lfs[0][iy * cx + ix] / mul_lf[0]);
-            lfq[2][cc] = (int32_t)std::lrint((lfs[2][iy * cx + ix] - base_b * fy) / mul_lf[2]);
+            lfq[0][cc] = (int32_t)std::lrint((lfs[0][iy * cx + ix] - lf_fac_x * fy) / mul_lf[0]);
+            lfq[2][cc] = (int32_t)std::lrint((lfs[2][iy * cx + ix] - lf_fac_b * fy) / mul_lf[2]);
           }
-        // AC quantisation
+        // AC quantisation: the factors of the tile that holds the varblock's first cell, as the decoder computes them
         const float scale = inv_gs / raw_quant[cell];
         const float dqs[3] = {scale * xmul, scale, scale * bmul};
-        const float cfl[3] = {0.f, 0.f, base_b};
+        const size_t tile = (size_t)(by / 8) * wt + bx / 8;
+        const float cfl[3] = {base_x + ytox[tile] * (1.0f / color_factor), 0.f, base_b + ytob[tile] * (1.0f / color_factor)};
         std::vector<float> yd(size);
-        for (int c : {1, 0, 2}) {
+        quant_y(s, cell, coef[1].data(), &qac[1][cell], yd.data());
+        for (int c : {0, 2}) {
           const float* wq = dq.Get(s, c);
           std::vector<int32_t>& q = qac[c][cell];
           q.assign(size, 0);
           for (size_t k = 0; k < size; k++) {
-            float target = coef[c][k];
-            if (c != 1) target -= cfl[c] * yd[k];
+            float target = coef[c][k] - cfl[c] * yd[k];
             float v = target / (dqs[c] * wq[k]);
             float a = std::fabs(v);
-            int32_t qi = a < 0.6f ? 0 : (int32_t)std::lrint(v);
-            q[k] = qi;
-            if (c == 1) {
-              float adj = qi == 0 ? 0 : (std::abs(qi) == 1 ? (qi > 0 ? m.quant_bias[1] : -m.quant_bias[1]) : qi - m.quant_bias[3] / qi);
-              yd[k] = adj * dqs[1] * wq[k];
-            }
+            q[k] = a < 0.6f ? 0 : (int32_t)std::lrint(v);
           }
         }
       }
     });
     // 5. tokens
     const uint32_t nlf = f.num_lf_groups, ng = f.num_groups;
-    Tree tree = MakeVarDctTree(nlf);
+    Tree tree = MakeVarDctTree(nlf, p.side);
     WPHeader wp_default;
     const uint32_t np = (uint32_t)std::max(1, std::min(3, p.num_passes));
     f.num_passes = np;
@@ -420,7 +499,13 @@ struct VarDctEncoder {
       mi.ch.emplace_back(bw, bh, 0, 0);
       memcpy(mi.ch[2].Row(0), srow.data(), srow.size() * 4);
       memcpy(mi.ch[2].Row(1), qrow.data(), qrow.size() * 4);
-      for (auto& v : mi.ch[3].d) v = 4;  // EPF sharpness
+      for (int y = 0; y < th; y++)
+        for (int x = 0; x < tw; x++) {
+          mi.ch[0].Row(y)[x] = ytox[(size_t)(by0 / 8 + y) * wt + bx0 / 8 + x];
+          mi.ch[1].Row(y)[x] = ytob[(size_t)(by0 / 8 + y) * wt + bx0 / 8 + x];
+        }
+      for (int y = 0; y < bh; y++)
+        for (int x = 0; x < bw; x++) mi.ch[3].Row(y)[x] = sharp[(size_t)(by0 + y) * w8 + bx0 + x];   // EPF sharpness
       for (int mc = 0; mc < 4; mc++) TokenizeChannel(tree, wp_default, mi, mc, 1 + 2 * nlf + g, meta_tok[g]);
     });
     // block contexts from thresholds on the quantised LF (quartiles of Y, zero for X and B) and on the quant field
@@ -556,7 +641,8 @@ struct VarDctEncoder {
     std::vector<BitWriter> sec(single ? 4 : 2 + nlf + (size_t)ng * np);
     // --- LfGlobal
     BitWriter& g0 = sec[0];
-    g0.Bool(true);  // LF dequant defaults
+    g0.Bool(!side.custom_lf_factors);  // LF dequant defaults
+    if (side.custom_lf_factors) for (int c = 0; c < 3; c++) g0.F16(side.lf_factor[c]);
     g0.U32(BitsOff(11, 1), BitsOff(11, 2049), BitsOff(12, 4097), BitsOff(16, 8193), global_scale);
     g0.U32(Val(16), BitsOff(5, 1), BitsOff(8, 1), BitsOff(16, 1), quant_lf);
     if (!p.lf_contexts) {
@@ -571,7 +657,12 @@ struct VarDctEncoder {
       for (uint32_t t : bctx.qf_thresholds) g0.U32(Bits(2), BitsOff(3, 4), BitsOff(5, 12), BitsOff(8, 44), t - 1);
       EncodeContextMap(g0, bctx.ctx_map);
     }
-    g0.Bool(true);  // default LF chroma-from-luma
+    g0.Bool(!side.custom_cfl);  // default chroma-from-luma parameters
+    if (side.custom_cfl) {
+      g0.U32(Val(84), Val(256), BitsOff(8, 2), BitsOff(16, 258), side.color_factor);
+      g0.F16(side.base_x); g0.F16(side.base_b);
+      g0.Write(8, (uint32_t)(side.ytox_lf + 128)); g0.Write(8, (uint32_t)(side.ytob_lf + 128));
+    }
     g0.Bool(true);  // has global tree
     WriteTree(g0, tree);
     std::vector<const std::vector<Token>*> sets;
@@ -775,6 +866,14 @@ std::vector<uint8_t> EncodeLosslessFrame(const ImageMetadata& m, FrameHeader& f,
 
 }  // namespace
 
+uint32_t SideInfoHash(uint32_t seed, uint32_t x, uint32_t y, uint32_t k) {
+  uint32_t u = seed * 0x9E3779B1u + x * 0x85EBCA6Bu + y * 0xC2B2AE35u + k * 0x27D4EB2Fu;
+  u ^= u >> 15;
+  u *= 0x2C1B3C6Du;
+  u ^= u >> 12;
+  return u;
+}
+
 static thread_local uint64_t g_token_counts[4] = {0, 0, 0, 0};
 void SetLastEncodeTokenCounts(const uint64_t n[4]) { for (int i = 0; i < 4; i++) g_token_counts[i] = n[i]; }
 void GetLastEncodeTokenCounts(uint64_t n[4]) { for (int i = 0; i < 4; i++) n[i] = g_token_counts[i]; }
@@ -820,6 +919,30 @@ std::vector<uint8_t> EncodeJxl(const uint8_t* px, uint32_t w, uint32_t h, int nc
     if (nch == 5) { m.ec.push_back(ExtraChannelInfo()); m.ec.back().bits = m.bits; }
   } else if (nch == 2 || nch == 4) { m.ec.push_back(ExtraChannelInfo()); m.ec.back().bits = m.bits; m.ec.back().exp_bits = m.exp_bits; m.ec.back().alpha_associated = p.premultiplied_alpha; }
   m.have_animation = p.animation_frames > 1;
+  // side information (lossy frames): every stored F16 is rounded here, and the frame is encoded with the rounded values
+  EncodeParams rounded = p;
+  SideInfo& side = rounded.side;
+  if (!p.lossless) {
+    auto r16 = [](float* v, int n) { for (int i = 0; i < n; i++) v[i] = RoundToF16(v[i]); };
+    JXO_CHECK(side.cfl_mode >= 0 && side.cfl_mode <= 2 && side.sharp_mode >= 0 && side.sharp_mode <= 2 && side.sharp_value >= 0 && side.sharp_value <= 7,
+              "side information: map modes");
+    JXO_CHECK(side.x_qm_scale >= -1 && side.x_qm_scale <= 7 && side.b_qm_scale >= -1 && side.b_qm_scale <= 7, "side information: qm scales are 0..7");
+    if (side.custom_cfl) {
+      JXO_CHECK(side.color_factor >= 1 && side.color_factor <= 65793 && side.ytox_lf >= -128 && side.ytox_lf <= 127 && side.ytob_lf >= -128 && side.ytob_lf <= 127,
+                "side information: chroma-from-luma parameters");
+      r16(&side.base_x, 1); r16(&side.base_b, 1);
+    }
+    if (side.custom_lf_factors) {
+      r16(side.lf_factor, 3);
+      for (float v : side.lf_factor) JXO_CHECK(v * (1.0f / 128) >= 1e-8f, "side information: LF dequantisation factor");
+    }
+    if (side.custom_transform) {
+      m.default_transform = false;
+      r16(m.opsin_inverse, 9); r16(m.opsin_bias, 3);
+      r16(side.quant_bias, 4);
+      memcpy(m.quant_bias, side.quant_bias, sizeof(m.quant_bias));
+    }
+  }
   std::vector<uint8_t> frame;
   const size_t bytes_per_px = (size_t)nch * (m.bits > 16 ? 4 : (m.bits > 8 ? 2 : 1));
   for (int k = 0; k < std::max(1, p.animation_frames); k++) {
@@ -838,7 +961,7 @@ std::vector<uint8_t> EncodeJxl(const uint8_t* px, uint32_t w, uint32_t h, int nc
     f.duration = m.have_animation ? 10 : 0;
     std::vector<uint8_t> one;
     if (p.lossless) {
-      one = EncodeLosslessFrame(m, f, src, nch, p);
+      one = EncodeLosslessFrame(m, f, src, nch, rounded);
     } else {
       f.encoding = 0;
       f.lf.gab = p.gaborish;
@@ -848,8 +971,18 @@ std::vector<uint8_t> EncodeJxl(const uint8_t* px, uint32_t w, uint32_t h, int nc
         for (float t : {0.7f, 1.5f, 4.0f}) if (p.distance >= t) iters++;
       }
       f.lf.epf_iters = iters;
+      auto r16 = [](float* dst, const float* src, int n) { for (int i = 0; i < n; i++) dst[i] = RoundToF16(src[i]); };
+      if (side.x_qm_scale >= 0) f.x_qm_scale = (uint32_t)side.x_qm_scale;
+      if (side.b_qm_scale >= 0) f.b_qm_scale = (uint32_t)side.b_qm_scale;
+      if (side.custom_gab) { r16(f.lf.gab_w1, side.gab_w1, 3); r16(f.lf.gab_w2, side.gab_w2, 3); }
+      if (side.custom_sharp_lut) r16(f.lf.epf_sharp_lut, side.sharp_lut, 8);
+      if (side.custom_epf_weights) r16(f.lf.epf_channel_scale, side.epf_channel_scale, 3);
+      if (side.custom_epf_sigma) {
+        r16(&f.lf.epf_quant_mul, &side.epf_quant_mul, 1); r16(&f.lf.epf_pass0_sigma_scale, &side.epf_pass0_sigma_scale, 1);
+        r16(&f.lf.epf_pass2_sigma_scale, &side.epf_pass2_sigma_scale, 1); r16(&f.lf.epf_border_sad_mul, &side.epf_border_sad_mul, 1);
+      }
       if (!p.adaptive_lf_smoothing) f.flags |= FrameHeader::kSkipAdaptiveLfSmoothing;
-      VarDctEncoder enc(p);
+      VarDctEncoder enc(rounded);
       enc.m = m;
       enc.f = f;
       one = enc.Encode(src, nch);

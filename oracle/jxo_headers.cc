@@ -243,7 +243,16 @@ void WriteImageMetadata(BitWriter& bw, const ImageMetadata& m) {
     }
     bw.U64(0);  // extensions
   }
-  bw.Bool(true);  // default transform data
+  bw.Bool(m.default_transform);
+  if (!m.default_transform) {
+    // the opsin bundle (the values must already be F16 numbers: the writer works with what the stream says); default upsampling weights
+    JXO_CHECK(m.xyb_encoded, "custom transform data is written for XYB streams");
+    bw.Bool(false);
+    for (int i = 0; i < 9; i++) bw.F16(m.opsin_inverse[i]);
+    for (int i = 0; i < 3; i++) bw.F16(m.opsin_bias[i]);
+    for (int i = 0; i < 4; i++) bw.F16(m.quant_bias[i]);
+    bw.Write(3, 0);
+  }
 }
 
 // ------------------------------------------------------------------ frame header
@@ -379,8 +388,12 @@ void ReadFrameHeader(BitReader& br, const ImageMetadata& m, FrameHeader& f) {
 
 void WriteFrameHeader(BitWriter& bw, const ImageMetadata& m, const FrameHeader& f) {
   LoopFilter dlf;
+  const bool lut_custom = memcmp(f.lf.epf_sharp_lut, dlf.epf_sharp_lut, sizeof(dlf.epf_sharp_lut)) != 0;
+  const bool weights_custom = memcmp(f.lf.epf_channel_scale, dlf.epf_channel_scale, sizeof(dlf.epf_channel_scale)) != 0;
+  const bool sigma_custom = f.lf.epf_quant_mul != dlf.epf_quant_mul || f.lf.epf_pass0_sigma_scale != dlf.epf_pass0_sigma_scale ||
+                            f.lf.epf_pass2_sigma_scale != dlf.epf_pass2_sigma_scale || f.lf.epf_border_sad_mul != dlf.epf_border_sad_mul;
   bool lf_default = f.lf.gab == dlf.gab && f.lf.epf_iters == dlf.epf_iters && !memcmp(f.lf.gab_w1, dlf.gab_w1, sizeof(dlf.gab_w1)) &&
-                    !memcmp(f.lf.gab_w2, dlf.gab_w2, sizeof(dlf.gab_w2));
+                    !memcmp(f.lf.gab_w2, dlf.gab_w2, sizeof(dlf.gab_w2)) && !lut_custom && !weights_custom && !sigma_custom;
   bool all_default = f.frame_type == 0 && f.encoding == 0 && f.flags == 0 && m.xyb_encoded && f.upsampling == 1 && m.ec.empty() &&
                      f.x_qm_scale == 3 && f.b_qm_scale == 2 && f.num_passes == 1 && !f.have_crop && f.blend_mode == 0 && f.is_last &&
                      f.name.empty() && lf_default && !m.have_animation;
@@ -426,9 +439,21 @@ void WriteFrameHeader(BitWriter& bw, const ImageMetadata& m, const FrameHeader& 
     }
     bw.Write(2, f.lf.epf_iters);
     if (f.lf.epf_iters) {
-      if (f.encoding == 0) bw.Bool(false);  // sharp lut default
-      bw.Bool(false);                       // weights default
-      bw.Bool(false);                       // sigma default
+      // the three EPF bundles; a bundle that differs from the defaults must hold F16 numbers
+      if (f.encoding == 0) {
+        bw.Bool(lut_custom);
+        if (lut_custom) for (int i = 0; i < 8; i++) bw.F16(f.lf.epf_sharp_lut[i]);
+      }
+      bw.Bool(weights_custom);
+      if (weights_custom) {
+        for (int i = 0; i < 3; i++) bw.F16(f.lf.epf_channel_scale[i]);
+        bw.Write(32, 0);
+      }
+      bw.Bool(sigma_custom);
+      if (sigma_custom) {
+        if (f.encoding == 0) bw.F16(f.lf.epf_quant_mul);
+        bw.F16(f.lf.epf_pass0_sigma_scale); bw.F16(f.lf.epf_pass2_sigma_scale); bw.F16(f.lf.epf_border_sad_mul);
+      }
       if (f.encoding == 1) bw.F16(f.lf.epf_sigma_for_modular);
     }
     bw.U64(0);

@@ -871,18 +871,29 @@ void XybToLinear(const ImageMetadata& m, Plane xyb[3]) {
   }
 }
 
-void LinearToXyb(Plane rgb[3]) {
-  const float kM[9] = {0.30f, 0.622f, 0.078f, 0.23f, 0.692f, 0.078f, 0.24342268924547819f, 0.20476744424496821f, 0.55180986650955360f};
-  const float kB = 0.0037930732552754493f;
-  const float cb = std::cbrt(kB);
+void LinearToXyb(Plane rgb[3], const ImageMetadata* m) {
+  float kM[9] = {0.30f, 0.622f, 0.078f, 0.23f, 0.692f, 0.078f, 0.24342268924547819f, 0.20476744424496821f, 0.55180986650955360f};
+  float kB[3] = {0.0037930732552754493f, 0.0037930732552754493f, 0.0037930732552754493f};
+  if (m && !m->default_transform) {
+    const float* a = m->opsin_inverse;
+    const double d = (double)a[0] * ((double)a[4] * a[8] - (double)a[5] * a[7]) - (double)a[1] * ((double)a[3] * a[8] - (double)a[5] * a[6]) +
+                     (double)a[2] * ((double)a[3] * a[7] - (double)a[4] * a[6]);
+    JXO_CHECK(std::fabs(d) > 1e-6, "singular inverse opsin matrix");
+    const double inv[9] = {((double)a[4] * a[8] - (double)a[5] * a[7]) / d, ((double)a[2] * a[7] - (double)a[1] * a[8]) / d, ((double)a[1] * a[5] - (double)a[2] * a[4]) / d,
+                           ((double)a[5] * a[6] - (double)a[3] * a[8]) / d, ((double)a[0] * a[8] - (double)a[2] * a[6]) / d, ((double)a[2] * a[3] - (double)a[0] * a[5]) / d,
+                           ((double)a[3] * a[7] - (double)a[4] * a[6]) / d, ((double)a[1] * a[6] - (double)a[0] * a[7]) / d, ((double)a[0] * a[4] - (double)a[1] * a[3]) / d};
+    for (int i = 0; i < 9; i++) kM[i] = (float)inv[i];
+    for (int i = 0; i < 3; i++) kB[i] = -m->opsin_bias[i];
+  }
+  const float cb[3] = {std::cbrt(kB[0]), std::cbrt(kB[1]), std::cbrt(kB[2])};
   size_t n = rgb[0].d.size();
   for (size_t i = 0; i < n; i++) {
     float r = rgb[0].d[i], g = rgb[1].d[i], b = rgb[2].d[i];
-    float mr = kM[0] * r + kM[1] * g + kM[2] * b + kB;
-    float mg = kM[3] * r + kM[4] * g + kM[5] * b + kB;
-    float mb = kM[6] * r + kM[7] * g + kM[8] * b + kB;
+    float mr = kM[0] * r + kM[1] * g + kM[2] * b + kB[0];
+    float mg = kM[3] * r + kM[4] * g + kM[5] * b + kB[1];
+    float mb = kM[6] * r + kM[7] * g + kM[8] * b + kB[2];
     mr = std::max(mr, 0.f); mg = std::max(mg, 0.f); mb = std::max(mb, 0.f);
-    float gr = std::cbrt(mr) - cb, gg = std::cbrt(mg) - cb, gb = std::cbrt(mb) - cb;
+    float gr = std::cbrt(mr) - cb[0], gg = std::cbrt(mg) - cb[1], gb = std::cbrt(mb) - cb[2];
     rgb[0].d[i] = 0.5f * (gr - gg);
     rgb[1].d[i] = 0.5f * (gr + gg);
     rgb[2].d[i] = gb;

@@ -68,7 +68,8 @@ void Gaborish(Plane xyb[3], const LoopFilter& lf);
 // inv_sigma: one value per 8x8 block (w8 x h8), as stored by the decoder (negative).
 void Epf(Plane xyb[3], const LoopFilter& lf, const Plane& inv_sigma);
 void XybToLinear(const ImageMetadata& m, Plane xyb[3]);   // in place: X,Y,B -> linear R,G,B
-void LinearToXyb(Plane rgb[3]);                            // in place
+void LinearToXyb(Plane rgb[3], const ImageMetadata* m = nullptr);   // in place; m with custom transform data: the forward matrix is
+                                                                    // the inverse of the stream's inverse matrix, the biases are the stream's
 float LinearToSrgb(float v);
 float SrgbToLinear(float v);
 // Enumerated colour encodings the reference's host knows by name (Decoder/JxlDecoder.cpp:36-108): D65, primaries sRGB / P3 /

@@ -1219,7 +1219,7 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
     const int chan_of[3] = {1, 0, 2};
     // (measured: an LDS tile per channel wavefront - 48 KB more per workgroup - doubles this kernel's time in a batch and does not
     // change the single-frame time; the untiled pass stays)
-    // (channels that lf_finish_gradient_kernel has finished - all of them in files as every encoder writes them - carry pad0 = 1)
+    // (channels that lf_finish_gradient_kernel has finished carry pad0 = 1)
     if (desc[wave].pad0 != 1)
       FinishChannelI32(desc[wave], tree, wave, 1 + g, im.lfq[chan_of[wave]] + (size_t)by0 * im.w8 + bx0, im.w8, bw, bh, carry, lane);
   } else {

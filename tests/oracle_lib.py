@@ -15,6 +15,65 @@ class EncodeParams(C.Structure):
                 ("lossless_squeeze", C.c_int32), ("lossless_tree", C.c_int32), ("num_threads", C.c_int32), ("bits", C.c_int32), ("orientation", C.c_int32), ("float_samples", C.c_int32), ("colour", C.c_int32)]
 
 
+class SideInfo(C.Structure):
+    """oracle/jxo_codec.h: SideInfo (the side information of a lossy frame that the writer can vary), field for field."""
+    _fields_ = [("cfl_mode", C.c_int32), ("sharp_mode", C.c_int32), ("sharp_value", C.c_int32), ("seed", C.c_uint32), ("refuse", C.c_int32),
+                ("custom_cfl", C.c_int32), ("color_factor", C.c_uint32), ("base_x", C.c_float), ("base_b", C.c_float),
+                ("ytox_lf", C.c_int32), ("ytob_lf", C.c_int32), ("custom_lf_factors", C.c_int32), ("lf_factor", C.c_float * 3),
+                ("x_qm_scale", C.c_int32), ("b_qm_scale", C.c_int32), ("custom_gab", C.c_int32), ("gab_w1", C.c_float * 3),
+                ("gab_w2", C.c_float * 3), ("custom_sharp_lut", C.c_int32), ("sharp_lut", C.c_float * 8), ("custom_epf_weights", C.c_int32),
+                ("epf_channel_scale", C.c_float * 3), ("custom_epf_sigma", C.c_int32), ("epf_quant_mul", C.c_float),
+                ("epf_pass0_sigma_scale", C.c_float), ("epf_pass2_sigma_scale", C.c_float), ("epf_border_sad_mul", C.c_float),
+                ("custom_transform", C.c_int32), ("quant_bias", C.c_float * 4)]
+
+
+_CFL_MODES = {"zero": 0, "fitted": 1, "formula": 2}
+
+
+def make_side_info(cfl=None, sharpness=None, seed=0, refuse=None, cfl_params=None, lf_factors=None, qm_scales=None, gaborish_weights=None,
+                   sharp_lut=None, epf_channel_scale=None, epf_sigma=None, quant_biases=None):
+    """The keyword arguments of encode(side_info=dict(...)):
+    cfl: "fitted" / "formula"; sharpness: "formula" or a constant 0..7 (one token per cell; None keeps the stream's leaf-offset 4);
+    seed: of the two formulas; refuse: "sharpness" / "cfl" (one value out of range, for refusal tests);
+    cfl_params: (color_factor, base_correlation_x, base_correlation_b, ytox_lf, ytob_lf); lf_factors: three stored values (128 x step);
+    qm_scales: (x_qm_scale, b_qm_scale); gaborish_weights: ((w1, w2) for X, Y, B); sharp_lut: eight values;
+    epf_channel_scale: three values; epf_sigma: (quant_mul, pass0_sigma_scale, pass2_sigma_scale, border_sad_mul);
+    quant_biases: four values, written in a custom transform-data bundle whose opsin values are the defaults as F16 rounds them."""
+    s = SideInfo()
+    s.cfl_mode = _CFL_MODES[cfl or "zero"]
+    s.seed = seed
+    if sharpness == "formula":
+        s.sharp_mode = 1
+    elif sharpness is not None:
+        s.sharp_mode, s.sharp_value = 2, int(sharpness)
+    s.refuse = {None: 0, "sharpness": 1, "cfl": 2}[refuse]
+    s.color_factor, s.base_x, s.base_b = 84, 0.0, 1.0
+    if cfl_params is not None:
+        s.custom_cfl = 1
+        s.color_factor, s.base_x, s.base_b, s.ytox_lf, s.ytob_lf = cfl_params
+    if lf_factors is not None:
+        s.custom_lf_factors = 1
+        s.lf_factor[:] = lf_factors
+    s.x_qm_scale, s.b_qm_scale = qm_scales if qm_scales is not None else (-1, -1)
+    if gaborish_weights is not None:
+        s.custom_gab = 1
+        s.gab_w1[:] = [w[0] for w in gaborish_weights]
+        s.gab_w2[:] = [w[1] for w in gaborish_weights]
+    if sharp_lut is not None:
+        s.custom_sharp_lut = 1
+        s.sharp_lut[:] = sharp_lut
+    if epf_channel_scale is not None:
+        s.custom_epf_weights = 1
+        s.epf_channel_scale[:] = epf_channel_scale
+    if epf_sigma is not None:
+        s.custom_epf_sigma = 1
+        s.epf_quant_mul, s.epf_pass0_sigma_scale, s.epf_pass2_sigma_scale, s.epf_border_sad_mul = epf_sigma
+    if quant_biases is not None:
+        s.custom_transform = 1
+        s.quant_bias[:] = quant_biases
+    return s
+
+
 def build():
     subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(_ROOT, "oracle")])
 
@@ -83,9 +142,10 @@ class OracleError(RuntimeError):
 def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, seed=1, epf_iters=-1, gaborish=True,
            container=True, adaptive_lf_smoothing=True, lossless_predictor=6, lossless_squeeze=False, num_threads=8, exif=None,
            xmp=None, lossless_tree=0, bits=8, orientation=1, float_samples=0, colour=0, icc=None, cmyk=False, animation_frames=1, custom_quant_tables=False, prefix_codes=False, lz77=False, num_passes=1, custom_orders=False, lf_contexts=False, palette=False, mislabel_afv=False,
-           premultiplied_alpha=False):
+           premultiplied_alpha=False, side_info=None):
     """px: uint8 array (h, w, nch) with nch in 1..4 (Gray, GrayA, RGB, RGBA); with bits > 8 (up to 16) a uint16 array whose
-    samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes."""
+    samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes.
+    side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters)."""
     L = lib()
     if float_samples:
         px = np.ascontiguousarray(px, dtype=np.float16 if float_samples == 16 else np.float32)
@@ -100,6 +160,11 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
         L.jxo_set_next_flags.argtypes = [C.c_uint32]
         L.jxo_set_next_flags((1 if custom_quant_tables else 0) | (2 if prefix_codes else 0) | (4 if lz77 else 0) | {1: 0, 2: 8, 3: 16}[num_passes] | (32 if custom_orders else 0) | (64 if lf_contexts else 0) | (128 if palette else 0) |
                              (256 if mislabel_afv else 0) | (512 if premultiplied_alpha else 0))
+    if side_info:
+        L.jxo_set_next_side_info.argtypes = [C.POINTER(SideInfo)]
+        L.jxo_side_info_size.restype = C.c_size_t
+        assert L.jxo_side_info_size() == C.sizeof(SideInfo), "SideInfo: the ctypes mirror and jxo_codec.h disagree"
+        L.jxo_set_next_side_info(C.byref(make_side_info(**side_info)))
     if animation_frames > 1:
         L.jxo_set_next_animation.argtypes = [C.c_int]
         L.jxo_set_next_animation(animation_frames)
