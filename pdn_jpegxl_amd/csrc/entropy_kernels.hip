@@ -14,6 +14,7 @@
 //  * `lane_stride` picks the mapping: 64 = one section per wavefront, 1 = one section per lane.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 #include "dev_types.h"
 #include "dev_util.h"
 #include "kernels.h"
@@ -758,7 +759,19 @@ struct UniAreas {
   bool use_wp = false;
 };
 
+// What alpha_ans_kernel asks of DecodeChannelLane beyond the plain decode (LF and Modular channels pass none).
+struct AlphaNarrow {
+  uint32_t limit;       // largest |residual| the narrow form may hold; 0: this group keeps the int32 form
+  uint32_t* counters;   // the image's status words (kStatusAlphaNarrow / kStatusAlphaRedo)
+  bool redo;            // out: a residual did not fit, the group is marked kChanRedo and the stream was left half read
+};
+typedef uint32_t __attribute__((ext_vector_type(4))) U4v;
+
 // Phase A of one channel on one lane.  Writes residuals (kChanResid), final samples (kChanFinal) or nothing (kChanConst).
+// An alpha group whose rows all end in a gradient leaf leaves its residuals as int16 instead (kChanResid16, `nar`): every lane of a
+// store instruction hits a cache line of its own, so a sample stored alone is a write request of its own; eight residuals gathered
+// in registers leave as one 16-byte store, an eighth of the requests and half the bytes, and phase B reads half the bytes back.
+// The residual does not depend on the sample before it on these rows, so the range check sits beside the token chain, not on it.
 // kGeneric = false: the per-sample path (ModularChannel: weighted predictor, any tree) is not compiled in.  The LF and alpha kernels
 // carry both forms: the generic path alone raises their register allocation by half (lf_ans 156 -> 203 VGPRs, alpha_ans 96 -> 135)
 // whether or not a stream ever takes it, and these wavefronts sit on their registers for tens of milliseconds while the pixel
@@ -766,7 +779,7 @@ struct UniAreas {
 template <bool kLds, bool kUni = false, bool kGeneric = true>
 __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, const CodeTab<kLds>& tab, typename AS<kLds>::Tree tree, int chan, int sid,
                                   int w, int h, int32_t* out_generic, int stride, ChanDesc* desc, int32_t* wp_scratch = nullptr,
-                                  const RowBuf<kLds>* lane_rows = nullptr, const UniAreas* uni = nullptr) {
+                                  const RowBuf<kLds>* lane_rows = nullptr, const UniAreas* uni = nullptr, AlphaNarrow* nar = nullptr) {
   ChanDesc d;
   d.kind = kChanFinal; d.value = 0; d.pad0 = 0; d.pad1 = 0;
   if (w <= 0 || h <= 0) { *desc = d; return; }
@@ -798,6 +811,19 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
     return;
   }
   JXL_GLB int32_t* const out = G(out_generic);
+  // the narrow form: exactly the groups alpha_finish_gradient_kernel takes (the caller has checked the frame: AlphaGroupStatic), on the
+  // lane path, and no row of one-symbol tokens
+  bool narrow = false;
+  if (nar && nar->limit) {
+    narrow = needs_n && !tab.direct && (w & 15) == 0;
+    for (int y = 0; narrow && y < h; y++) {
+      bool used_y = false;
+      const DevTreeNode nd = RowNode(tree, chan, sid, y, &used_y);
+      const uint32_t c = tab.cfg[tab.cmap[nd.a >> 8]];
+      narrow = (nd.a & 0xFF) == 5 && !((c & 0x1000) && ((c >> 16) & 0xFF) < (1u << (c & 0xF)));
+      if (!used_y) break;   // every row resolves to this leaf
+    }
+  }
   uint32_t first_prev = 0;   // sample (0, y - 1): what West means at the start of a row
   for (int y = 0; y < h; y++) {
     // row constants: leaf -> cluster, hybrid-uint config, multiplier / offset, predictor
@@ -836,6 +862,35 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
       }
     }
     uint64_t entry = AnsPrefetch<kLds>(state, abase, tab.log_alpha);
+    if (narrow) {   // w is a multiple of kTopUpEvery = 16: two 16-byte stores per top-up period
+      static_assert(kTopUpEvery == 16, "the narrow rows store two vectors of eight residuals per top-up period");
+      JXL_GLB U4v* const row16 = (JXL_GLB U4v*)row;
+      const uint32_t lim = nar->limit;
+      uint32_t top = 0;   // max of residual + limit as unsigned: above 2 * limit when some |residual| > limit
+      for (int x0 = 0; x0 < w; x0 += kTopUpEvery) {
+        b.TopUp();
+        uint32_t pk[kTopUpEvery / 2];
+#pragma unroll
+        for (int k = 0; k < kTopUpEvery; k++) {
+          const uint32_t sym = AnsSymPf<kLds>(b, state, abase, tab.log_alpha, entry);
+          const uint32_t val = (uint32_t)UnpackSigned(HybridTail(b, cfg, sym)) * mul + off;
+          top = max(top, val + lim);
+          if (k & 1) pk[k >> 1] |= val << 16;
+          else pk[k >> 1] = val & 0xFFFFu;
+        }
+        row16[x0 >> 3] = U4v{pk[0], pk[1], pk[2], pk[3]};
+        row16[(x0 >> 3) + 1] = U4v{pk[4], pk[5], pk[6], pk[7]};
+        if (top > 2 * lim) break;
+      }
+      if (top > 2 * lim) {   // a legal stream, only not one for this form: the redo launch decodes the group again, as int32
+        d.kind = kChanRedo;
+        *desc = d;
+        atomicAdd(nar->counters + kStatusAlphaRedo, 1u);
+        nar->redo = true;
+        return;
+      }
+      continue;
+    }
     for (int x0 = 0; x0 < w; x0 += kTopUpEvery) {
       b.TopUp();
       const int xe = min(w, x0 + kTopUpEvery);
@@ -849,8 +904,9 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
     }
     first_prev = first;
   }
-  d.kind = needs_n ? kChanResid : kChanFinal;
+  d.kind = narrow ? kChanResid16 : (needs_n ? kChanResid : kChanFinal);
   *desc = d;
+  if (narrow) atomicAdd(nar->counters + kStatusAlphaNarrow, 1u);
 }
 
 // Phase B: a wavefront applies the predictors of a row-static channel in place.  Lane r owns row y0 + r of a 64-row
@@ -1860,13 +1916,19 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
 
 // ------------------------------------------------------------------ alpha (Modular stream after the HF tokens), phase A
 // One lane per pass-group section; a workgroup (one wavefront) holds sections of ONE image.
+// narrow_limit: groups that alpha_finish_gradient_kernel takes leave int16 residuals (kChanResid16) while every |residual| is at most
+// this; 0: int32 residuals for all.  A stream may code any residual: a lane that meets a larger one marks its group kChanRedo and
+// stops, and the same kernel launched once more behind this one (redo = 1) decodes those groups alone, as int32 (kChanResid).  Its
+// workgroups leave before they stage a table where the image counted no such group.
 template <bool kLds, bool kGeneric = true>
-__global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, const SectionTask* tasks, int lane_stride, int scalar_rows) {
+__global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, const SectionTask* tasks, int lane_stride, int scalar_rows, int narrow_limit,
+                                                       int redo) {
   JXL_SERIAL_PRIO();
   extern __shared__ __align__(16) uint8_t smem[];
   const SectionTask task = tasks[blockIdx.x];
   const DevImage& im = imgs[task.image];
   if (!im.has_alpha || im.alpha_in_global) return;
+  if (redo && im.status[kStatusAlphaRedo] == 0) return;
   ModTables<kLds> mt;
   const int slots = 64 / lane_stride;
   LoadModTables<kLds>(im, smem, SlotsLds(slots).tables, mt, threadIdx.x, 64, slots == 1 && scalar_rows);
@@ -1874,6 +1936,7 @@ __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, con
   if (lane >= slots || lane >= task.count) return;
   const int g = task.first + lane;
   ChanDesc* desc = im.alpha_desc + g;
+  if (redo && desc->kind != kChanRedo) return;
   const uint64_t start = im.alpha_bitpos[g];
   if (start == ~(uint64_t)0) {   // the HF decoder already reported the failure
     ChanDesc d;
@@ -1893,8 +1956,12 @@ __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, con
     if (im.lz_grp) b.SetLz(im.lz_grp + ((size_t)g << 16), 16, (uint32_t)gw);
     uint32_t state = InitAnsState(b, mt.tab);
     const int sid = 1 + 3 * im.nlf + kNumQuantTables + g;
+    // (the frame's side of what AlphaGroupStatic asks; the group's side is DecodeChannelLane's)
+    const bool frame_ok = !redo && !im.is_modular && im.out_bits == 8 && im.alpha_bits == 8 && !im.alpha_exp && (im.w & 3) == 0;
+    AlphaNarrow nar = {frame_ok ? (uint32_t)narrow_limit : 0u, im.status, false};
     DecodeChannelLane<kLds, false, kGeneric>(b, state, mt.tab, mt.tree, 0, sid, gw, gh, im.alpha32 + (size_t)y0 * im.w + x0, im.w, desc,
-                            im.wp_grp ? im.wp_grp + (size_t)g * im.wp_grp_ints : nullptr);
+                            im.wp_grp ? im.wp_grp + (size_t)g * im.wp_grp_ints : nullptr, nullptr, nullptr, &nar);
+    if (nar.redo) return;   // (stopped in mid-stream: nothing to check yet)
     if (state != 0x130000u || b.slow_err) err |= kErrBitstream;
     if (start + b.Consumed() > (im.sec_off[sec] + im.sec_size[sec]) * 8) err |= kErrBitstream;
   }
@@ -2000,8 +2067,20 @@ struct AlphaLines {
       for (int b = 0; b < 4; b++) { const int32_t v = o[4 * k + b]; wd |= (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)) << (8 * b); }
       pk[k] = wd;
     }
-    typedef uint32_t __attribute__((ext_vector_type(4))) U4v;
     *(JXL_GLB U4v*)(out + (size_t)r * stride + q * 16) = U4v{pk[0], pk[1], pk[2], pk[3]};
+  }
+};
+// the same for groups whose residuals phase A left as int16 (kChanResid16): a line of 16 columns is 32 bytes, widened in registers
+struct AlphaLines16 : AlphaLines {
+  __device__ __forceinline__ void load(int r, int q, bool act, I4v* v) const {
+    const int rc = act ? r : 0, qc = act ? q : 0;
+    const JXL_GLB I4v* p = (const JXL_GLB I4v*)(plane + (size_t)(mine ? rc : 0) * stride + qc * 8);   // (row pitch as for int32)
+    const I4v lo = p[0], hi = p[1];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int32_t a = k < 2 ? lo[2 * k] : hi[2 * k - 4], c = k < 2 ? lo[2 * k + 1] : hi[2 * k - 3];
+      v[k] = I4v{(int32_t)(int16_t)a, a >> 16, (int32_t)(int16_t)c, c >> 16};
+    }
   }
 };
 // whether rows [row0, row0 + step * k) ... of the group's alpha channel all end in a gradient leaf; called by `nlanes` lanes (lane index
@@ -2011,7 +2090,7 @@ __device__ __forceinline__ bool AlphaRowsAreGradient(const I4* tree, int sid, in
   for (int r = li; r < gh; r += nlanes) { bool u = false; ok = ok && (RowNode(tree, 0, sid, r, &u).a & 0xFF) == 5; }
   return ok;
 }
-__device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int* gw, int* gh, int* sid, ChanDesc* d) {
+__device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int* gw, int* gh, int* sid, ChanDesc* d, int32_t kind = kChanResid) {
   // (a Modular frame has no alpha_desc, no group grid of this kind: nothing of it may be touched)
   if (!im.has_alpha || im.is_modular || g < 0 || g >= im.ng || im.out_bits != 8 || im.alpha_bits != 8 || im.alpha_exp || (im.w & 3) != 0) return false;
   const int gx = g % im.xg, gy = g / im.xg;
@@ -2019,8 +2098,11 @@ __device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int*
   *gw = min(kGroupDim, im.w - gx * kGroupDim); *gh = min(kGroupDim, im.h - gy * kGroupDim);
   *sid = im.alpha_in_global ? 0 : 1 + 3 * im.nlf + kNumQuantTables + g;
   *d = im.alpha_desc[g];
-  return d->kind == kChanResid && (*gw & 15) == 0;
+  return d->kind == kind && (*gw & 15) == 0;
 }
+// kNarrow: the launch behind a phase A that wrote int16 residuals takes those groups (kChanResid16) and no other: what phase A left
+// as int32 there (groups decoded again, rows of one-symbol tokens) is alpha_finish_kernel's.
+template <bool kNarrow>
 __global__ __launch_bounds__(64) void alpha_finish_gradient_kernel(const DevImage* __restrict__ imgs) {
   const DevImage& im = imgs[blockIdx.y];
   const int lane = threadIdx.x, sub = lane >> 4, li = lane & 15;
@@ -2028,7 +2110,7 @@ __global__ __launch_bounds__(64) void alpha_finish_gradient_kernel(const DevImag
   int gw = 0, gh = 0, sid = 0;
   ChanDesc d;
   d.kind = kChanFinal;
-  bool mine = AlphaGroupStatic(im, g, &gw, &gh, &sid, &d);
+  bool mine = AlphaGroupStatic(im, g, &gw, &gh, &sid, &d, kNarrow ? kChanResid16 : kChanResid);
   if (mine) mine = AlphaRowsAreGradient((const I4*)im.tree, sid, gh, li, 16);
   {  // all sixteen lanes of the group must agree
     const uint64_t bal = __ballot(mine);
@@ -2038,7 +2120,8 @@ __global__ __launch_bounds__(64) void alpha_finish_gradient_kernel(const DevImag
   const int gx = mine ? g % im.xg : 0, gy = mine ? g / im.xg : 0;
   const int x0 = gx * kGroupDim, y0 = gy * kGroupDim;
   const int nq = mine ? gw >> 4 : 0, rows = mine ? gh : 0;
-  const AlphaLines mem = {G(im.alpha32) + (size_t)y0 * im.w + x0, G(im.alpha) + (size_t)y0 * im.w + x0, im.w, mine};
+  typename std::conditional<kNarrow, AlphaLines16, AlphaLines>::type mem;
+  mem.plane = G(im.alpha32) + (size_t)y0 * im.w + x0; mem.out = G(im.alpha) + (size_t)y0 * im.w + x0; mem.stride = im.w; mem.mine = mine;
   // uniform loop bound: the longest of the wavefront's groups
   int steps = rows + 15;
   steps = max(steps, __shfl_xor(steps, 16)); steps = max(steps, __shfl_xor(steps, 32));
@@ -2061,6 +2144,10 @@ __global__ __launch_bounds__(64, 3) void alpha_finish_kernel(const DevImage* __r
   int32_t* plane = im.alpha32 + (size_t)y0 * im.w + x0;
   const int sid = im.alpha_in_global ? 0 : 1 + 3 * im.nlf + kNumQuantTables + g;
   if (d.pad0 == 1) return;   // finished by alpha_finish_gradient_kernel (phase A writes pad0 = 0)
+  if (d.kind == kChanResid16 || d.kind == kChanRedo) {   // never reached (the narrow pass takes every such group, the redo launch leaves none): not read as int32
+    if (lane == 0) SetError(im, kErrBitstream, 4, g);
+    return;
+  }
   if (im.out_bits == 8 && im.alpha_bits == 8 && !im.alpha_exp) {   // the common case: clamp to u8, packed stores
     uint8_t* out = im.alpha + (size_t)y0 * im.w + x0;
     if (d.kind == kChanResid) {
@@ -2470,16 +2557,20 @@ void LaunchHfDecode(const DevImage* imgs, const SectionTask* tasks, int nwg, int
   }
 }
 
-void LaunchAlphaAns(const DevImage* imgs, const SectionTask* tasks, int nwg, int lane_stride, size_t lds_bytes, int scalar_rows, bool lean, hipStream_t s) {
+void LaunchAlphaAns(const DevImage* imgs, const SectionTask* tasks, int nwg, int lane_stride, size_t lds_bytes, int scalar_rows, bool lean, int narrow_limit,
+                    hipStream_t s) {
   if (nwg <= 0) return;
-  if (lds_bytes && lean) {
-    RaiseLds((const void*)alpha_ans_kernel<true, false>, lds_bytes);
-    hipLaunchKernelGGL((alpha_ans_kernel<true, false>), dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows);
-  } else if (lds_bytes) {
-    RaiseLds((const void*)alpha_ans_kernel<true>, lds_bytes);
-    hipLaunchKernelGGL(alpha_ans_kernel<true>, dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows);
-  } else {
-    hipLaunchKernelGGL(alpha_ans_kernel<false>, dim3(nwg), dim3(64), SlotsLds(64 / lane_stride).tables, s, imgs, tasks, lane_stride, 0);
+  // narrow_limit > 0 (lane path only, see AlphaNarrowLaunch): a second launch behind the first decodes the groups it gave up on
+  for (int redo = 0; redo <= (narrow_limit > 0 ? 1 : 0); redo++) {
+    if (lds_bytes && lean) {
+      RaiseLds((const void*)alpha_ans_kernel<true, false>, lds_bytes);
+      hipLaunchKernelGGL((alpha_ans_kernel<true, false>), dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows, narrow_limit, redo);
+    } else if (lds_bytes) {
+      RaiseLds((const void*)alpha_ans_kernel<true>, lds_bytes);
+      hipLaunchKernelGGL(alpha_ans_kernel<true>, dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows, narrow_limit, redo);
+    } else {
+      hipLaunchKernelGGL(alpha_ans_kernel<false>, dim3(nwg), dim3(64), SlotsLds(64 / lane_stride).tables, s, imgs, tasks, lane_stride, 0, narrow_limit, redo);
+    }
   }
 }
 
@@ -2541,9 +2632,11 @@ void LaunchModularOut(const DevImage* imgs, int nimg, size_t max_pixels, hipStre
   hipLaunchKernelGGL(modular_out_kernel, dim3((unsigned)b, nimg), dim3(256), 0, s, imgs);
 }
 
-void LaunchAlphaFinish(const DevImage* imgs, int nimg, int max_groups, hipStream_t s) {
+void LaunchAlphaFinish(const DevImage* imgs, int nimg, int max_groups, bool narrow, hipStream_t s) {
   if (nimg <= 0 || max_groups <= 0) return;
-  hipLaunchKernelGGL(alpha_finish_gradient_kernel, dim3((max_groups + 3) / 4, nimg), dim3(64), 0, s, imgs);
+  // narrow: phase A ran with a narrow limit (LaunchAlphaAns), the gradient groups hold int16 residuals
+  if (narrow) hipLaunchKernelGGL(alpha_finish_gradient_kernel<true>, dim3((max_groups + 3) / 4, nimg), dim3(64), 0, s, imgs);
+  else hipLaunchKernelGGL(alpha_finish_gradient_kernel<false>, dim3((max_groups + 3) / 4, nimg), dim3(64), 0, s, imgs);
   hipLaunchKernelGGL(alpha_finish_kernel, dim3(max_groups, nimg), dim3(64), 0, s, imgs);
 }
 
