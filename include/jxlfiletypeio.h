@@ -12,6 +12,9 @@
  *
  * Part 2 (jxlhip_*) is the device-resident batch entry point used by bench.py / tests: same decode path,
  * but bitstreams and RGBA8 outputs stay in HBM and several images are decoded per call.
+ *
+ * Part 3 (jxlhip_save_pixels) is SaveImage for every sample type LoadImage hands out: 8- to 16-bit integers, binary16 and binary32,
+ * Gray | GrayA | RGB | RGBA, in any of the colour encodings the host knows by name.
  */
 #ifndef JXLFILETYPEIO_H_
 #define JXLFILETYPEIO_H_
@@ -242,8 +245,39 @@ JXLFILETYPEIO_API void jxlhip_last_save_lossless_info(JxlHipLosslessInfo* out);
  * returns its size (0: none) and copies up to `capacity` bytes. */
 JXLFILETYPEIO_API size_t jxlhip_parse_icc(const uint8_t* data, size_t size, uint8_t* dst, size_t capacity, DecoderStatus* status, ErrorInfo* err);
 
+/* =====================================================================================================
+ * Part 3: saving 16-bit and float images (not in the reference; SaveImage takes a BGRA8 surface and nothing else).
+ * ===================================================================================================== */
+typedef struct JxlHipPixels {
+  const void* data;            /* host memory, interleaved, channel order Gray | Gray,A | R,G,B | R,G,B,A (as setLayerData hands pixels out) */
+  uint32_t width, height;
+  uint64_t stride_bytes;       /* >= width * num_channels * bytes per sample */
+  int32_t num_channels;        /* 1..4; 2 and 4 carry (unassociated) alpha */
+  ImageChannelRepresentation sample_type;   /* Uint8, Uint16, Float16, Float32 */
+  int32_t bits_per_sample;     /* integers: 8 for Uint8; 9..16 for Uint16 (samples use the low bits); floats: 0 */
+  KnownColorProfile colour;    /* the space the samples are ALREADY in */
+} JxlHipPixels;
+
+/* Encodes `pixels` like SaveImage encodes its surface: the same options and effort tiers, container, Exif / XMP boxes, writes of at
+ * most 64 KiB, progress checkpoints and cancellation, HRESULT mapping, and the same jxlhip_last_save_stage_times /
+ * jxlhip_last_save_distances / jxlhip_last_save_lossless_info afterwards.  What differs:
+ *  - The channels are as stated: nothing is dropped or added by looking at the pixels (GetOutputPixelFormat is the plugin's rule).
+ *  - Lossy: integer samples mean v / (2^bits - 1), floats mean themselves (samples outside [0, 1] are kept); they reach XYB through
+ *    the inverse transfer function and the primaries of `colour`.  Alpha is lossless: integers by value, floats by bit pattern.
+ *  - Lossless: integer samples only, exact.  Uint8 input writes SaveImage's streams, the searched tiers 8 and 9 included; deeper
+ *    samples get the fixed stream (YCoCg-R, gradient predictor, one context per channel) at every effort.
+ *  - `colour` is signalled by its enum: Srgb and LinearSrgb stand for gray with the sRGB curve and linear gray when there are 1 or 2
+ *    channels; the other RGB profiles need 3 or 4 channels, the gray profiles 1 or 2.
+ * Refused on the host, before any device work, with EncoderStatus_EncodeError and a message each (null pointers:
+ * EncoderStatus_NullParameter): zero size, a stride below a row, channels outside 1..4, bits_per_sample that does not fit
+ * sample_type, a profile that does not fit the channels, metadata->iccProfile set, and lossless float samples. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels* pixels, const EncoderOptions* options,
+                                                   const EncoderImageMetadata* metadata, IOCallbacks* callbacks, ErrorInfo* errorInfo,
+                                                   ProgressProc progressCallback);
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(JxlHipPixels) == 40, "JxlHipPixels layout");
 static_assert(sizeof(BitmapData) == 24, "BitmapData layout");
 static_assert(sizeof(EncoderOptions) == 12, "EncoderOptions layout");
 static_assert(sizeof(EncoderImageMetadata) == 48, "EncoderImageMetadata layout");

@@ -71,10 +71,15 @@ class LosslessInfo(C.Structure):
                 ("reserved", C.c_int32), ("searched_bytes", C.c_uint64), ("effort7_bytes", C.c_uint64)]
 
 
+class JxlHipPixels(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("stride_bytes", C.c_uint64),
+                ("num_channels", C.c_int32), ("sample_type", C.c_int32), ("bits_per_sample", C.c_int32), ("colour", C.c_int32)]
+
+
 EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jxlhip_decoder_create", "jxlhip_decoder_destroy", "jxlhip_peek",
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
-           "jxlhip_last_save_lossless_info"]
+           "jxlhip_last_save_lossless_info", "jxlhip_save_pixels"]
 
 _lib = None
 
@@ -156,6 +161,9 @@ def lib(build_if_missing=True):
                                              C.POINTER(C.c_int32)]
     L.jxlhip_last_save_lossless_info.restype = None
     L.jxlhip_last_save_lossless_info.argtypes = [C.POINTER(LosslessInfo)]
+    L.jxlhip_save_pixels.restype = C.c_int32
+    L.jxlhip_save_pixels.argtypes = [C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions), C.POINTER(EncoderImageMetadata),
+                                     C.POINTER(IOCallbacks), C.POINTER(ErrorInfo), ProgressFn]
     L.jxlhip_parse_check.restype = C.c_int32
     L.jxlhip_parse_check.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_static_table.restype = C.c_size_t
@@ -290,6 +298,46 @@ def save_image(bgra, distance=1.0, effort=7, lossless=False, exif=None, icc=None
     io = IOCallbacks(WriteFn(write), SeekFn(seek))
     err = ErrorInfo()
     st = L.SaveImage(C.byref(bmp), C.byref(opt), C.byref(md), C.byref(io), C.byref(err), ProgressFn(progress) if progress else ProgressFn())
+    if st != 0:
+        raise JxlError(ENCODER_STATUS[st] if 0 <= st < len(ENCODER_STATUS) else str(st), err.errorMessage.decode("ascii", "replace"))
+    return bytes(out)
+
+
+_SAMPLE_TYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float16): 2, np.dtype(np.float32): 3}
+
+
+def save_pixels(px, distance=1.0, effort=7, lossless=False, colour="Srgb", bits=None, exif=None, xmp=None, progress=None):
+    """jxlhip_save_pixels: px = numpy array (h, w[, c]) of uint8, uint16, float16 or float32, c = 1..4 (Gray | Gray,A | R,G,B |
+    R,G,B,A; rows may be strided).  colour: a KNOWN_PROFILE name, the space the samples are already in.  bits: of integer samples
+    (default 8 for uint8, 16 for uint16; uint16 samples use the low `bits` bits).  Returns the encoded bytes."""
+    L = lib()
+    px = np.asarray(px)
+    if px.dtype not in _SAMPLE_TYPES:
+        raise ValueError("samples are uint8, uint16, float16 or float32")
+    if px.ndim == 2:
+        px = px[:, :, None]
+    if px.ndim != 3:
+        raise ValueError("a (h, w[, c]) array is expected")
+    h, w, c = px.shape
+    item = px.dtype.itemsize
+    if px.strides[2] != item or (w > 1 and px.strides[1] != c * item) or (h > 1 and px.strides[0] < w * c * item):
+        px = np.ascontiguousarray(px)
+    if bits is None:
+        bits = {1: 8, 2: 16}[item] if px.dtype.kind == "u" else 0
+    out = bytearray()
+
+    def write(p, n):
+        out.extend(C.string_at(p, n))
+        return S_OK
+
+    desc = JxlHipPixels(px.ctypes.data, w, h, px.strides[0] if h > 1 else w * c * item, c, _SAMPLE_TYPES[px.dtype], bits,
+                        KNOWN_PROFILE.index(colour))
+    opt = EncoderOptions(distance, effort, lossless)
+    keep = [np.frombuffer(b, np.uint8) if b else None for b in (exif, None, xmp)]
+    md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in keep), []))
+    io = IOCallbacks(WriteFn(write), SeekFn(lambda p: S_OK))
+    err = ErrorInfo()
+    st = L.jxlhip_save_pixels(C.byref(desc), C.byref(opt), C.byref(md), C.byref(io), C.byref(err), ProgressFn(progress) if progress else ProgressFn())
     if st != 0:
         raise JxlError(ENCODER_STATUS[st] if 0 <= st < len(ENCODER_STATUS) else str(st), err.errorMessage.decode("ascii", "replace"))
     return bytes(out)

@@ -17,8 +17,24 @@ constexpr uint32_t kAcContexts = 495 * 15;    // one preset, default block-conte
 constexpr uint32_t kLfTokCap = 3 * 65536;     // tokens per LF group: LF coefficients
 constexpr uint32_t kMetaTokCap = 2 * 65536;   // ... and the two rows of the block info (strategies, quant field)
 constexpr uint32_t kAcTokCap = 3 * 65 * 1024; // tokens per group: 1 + 64 per (block, channel)
-constexpr uint32_t kAlphaTokCap = 65536;
-constexpr uint32_t kLlTokCap = 4 * 65536;     // lossless: up to four channels per group
+// Capacities and the sample depth (jxlhip_save_pixels takes up to 16-bit integers and binary16 / binary32 samples).  The token COUNTS
+// do not depend on the depth: one token per sample, a group is at most 256 x 256 samples per channel.  What grows with the depth is
+// the value a token carries, and with it the bits a token takes in its section:
+//   - a sample of a lossless frame is below 2^16; YCoCg-R puts the chroma into [-65535, 65535] (an int32 plane holds it with room to
+//     spare), a gradient residual of such planes is below 2^17 in magnitude, PackSigned of it below 2^18: token at most
+//     16 + 13 * 4 + 3 = 71, 15 raw bits;
+//   - the alpha of a lossy binary32 frame is the sample's bit pattern (an int32): a residual packs into any 32-bit value, token at most
+//     16 + 27 * 4 + 3 = 127 < kEncSyms, 29 raw bits.
+// A token writes at most one 16-bit flush of the rANS state and its raw bits: 16 + 29 = 45 bits for a 32-bit value, so the 6 bytes
+// (48 bits) per token that every section buffer (sec_cap) allows hold the worst cases - a 256 x 256 group of 16-bit RGBA noise
+// (4 x 65536 tokens of at most 16 + 15 bits) and one of binary32 alpha bit patterns (65536 tokens of at most 45 bits) - with the 32
+// bits of the final state and the group header inside the 256 bytes of slack.  WaveWriter::PutParallel takes up to 48 bits per lane.
+constexpr uint32_t kAlphaTokCap = 65536;      // one alpha sample per pixel of a 256 x 256 group, whatever its depth
+constexpr uint32_t kLlTokCap = 4 * 65536;     // lossless: up to four channels per group, whatever their depth
+constexpr uint32_t kSecBytesPerTok = 6;       // bytes of section buffer per token (see above: 45 bits at most)
+
+enum EncSampleType : int32_t { kSampleUint8 = 0, kSampleUint16 = 1, kSampleFloat16 = 2, kSampleFloat32 = 3 };   // ImageChannelRepresentation
+enum EncTransfer : int32_t { kTransferLinear = 0, kTransferSrgb = 1, kTransfer709 = 2, kTransferPq = 3 };
 
 struct EncCodeDev {
   const uint8_t* ctx_map;
@@ -32,12 +48,19 @@ struct EncImage {
   int32_t w, h, w8, h8, wp, hp;
   int32_t xg, yg, ng, xlf, ylf, nlf;
   int32_t gray, has_alpha, gab, lossless;
-  // source (host layout BitmapData: BGRA8, `stride` bytes per row)
+  // source: the BGRA8 surface of SaveImage (host layout BitmapData, `stride` bytes per row; 8-bit input of jxlhip_save_pixels is
+  // repacked into one), or `src_nch` interleaved samples per pixel in tight rows (`stride` = w * src_nch * sample bytes)
   const uint8_t* bgra;
-  int32_t stride, pad0;
+  int64_t stride;
+  int32_t src_type;         // EncSampleType of the interleaved samples
+  int32_t src_nch;          // interleaved samples per pixel: Gray | Gray,A | R,G,B | R,G,B,A (0: the BGRA8 surface)
+  int32_t transfer;         // transfer function of the samples: 0 linear, 1 sRGB, 2 BT.709, 3 PQ (EncTransfer)
+  float sample_scale;       // integer samples: 1 / (2^bits - 1); floats: unused
+  int32_t pad0;
+  int32_t use_matrix;       // 1: icc_to_srgb takes the linear samples of the space's primaries to linear sRGB (relative to 255 nits)
   uint32_t* flags;          // [0] some pixel is not gray, [1] some pixel has alpha < 255
   // documents with an (evaluated, matrix / TRC) ICC profile: 3 x 256 samples -> linear of the profile, then 3x3 -> linear sRGB
-  const float* icc_lin;     // nullptr: the samples are sRGB
+  const float* icc_lin;     // nullptr: the samples are in the space `transfer` / `use_matrix` describe
   float icc_to_srgb[9];
   // planes
   float* xyb[3];            // w*h

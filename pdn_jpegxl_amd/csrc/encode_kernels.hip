@@ -3,6 +3,8 @@
 //
 //   enc_analyze_kernel        GetOutputPixelFormat (:33-77): is every pixel gray / opaque?                 (reduction)
 //   enc_xyb_kernel            PixelFormatConversion (BGRA -> channels) + sRGB -> linear -> XYB              (elementwise)
+//                             written once over a pixel loader: the BGRA8 surface, or interleaved 16-bit / float samples of
+//                             jxlhip_save_pixels in any of the named colour encodings (enc_pack_bgra_kernel: its 8-bit input)
 //   enc_sharpen_pad_kernel    inverse-Gaborish pre-sharpening, edge replication to whole 8x8 cells          (3x3 stencil)
 //   enc_activity / enc_strategy / enc_varblock_kernel
 //                             per-cell activity; 8x8 / 16x16 / 32x32 DCT per aligned region from it (effort), adaptive quant
@@ -11,6 +13,7 @@
 //   enc_*_tokens_kernel       context modelling: (context, value) tokens + histograms, all data-parallel
 //   enc_sections_kernel       ANS coding, one lane per section (reverse pass for the state, forward pass for the bits)
 #include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
 #include "dev_util.h"
 #include "enc_dev.h"
 #include "enc_types.h"
@@ -42,9 +45,163 @@ __global__ void enc_analyze_kernel(EncImage im) {
   if (__any(alpha) && (threadIdx.x & 63) == 0) atomicOr(&im.flags[1], 1u);
 }
 
-// ------------------------------------------------------------------ BGRA8 -> XYB (+ alpha plane)
-// Channel selection as PixelFormatConversion.cpp:16-121 (gray takes the B channel); sRGB decoding, opsin absorbance.
+// ------------------------------------------------------------------ pixel loaders
+// What the front-end kernels read a pixel through (a template parameter: each algorithm below is written once).  A loader hands out
+//   Nominal:  the colour samples on the nominal scale (1.0 = the largest integer sample; floats as they are, samples outside [0, 1]
+//             kept), gray replicated, the alpha sample as it is coded (the integer; a float's bit pattern, as the oracle's writer does)
+//             and, where the samples are bytes (kCodes8), the bytes themselves: the index into an ICC profile's tone curves;
+//   Integers: the samples of a lossless frame, colour first, then alpha.
+struct EncPixel {
+  float v[3];
+  int32_t alpha;
+  uint32_t code[3];
+};
+
+// The BGRA8 surface of SaveImage.  Channel selection as PixelFormatConversion.cpp:16-121 (gray takes the B channel).
+struct Bgra8Surface {
+  static constexpr bool kCodes8 = true;
+  static __device__ __forceinline__ uchar4 Load(const EncImage& im, int x, int y) {
+    return *(const uchar4*)(im.bgra + (size_t)y * im.stride + (size_t)x * 4);   // B, G, R, A
+  }
+  static __device__ __forceinline__ EncPixel Nominal(const EncImage& im, int x, int y) {
+    const uchar4 p = Load(im, x, y);
+    EncPixel o;
+    o.code[0] = im.gray ? p.x : p.z; o.code[1] = im.gray ? p.x : p.y; o.code[2] = p.x;
+    for (int c = 0; c < 3; c++) o.v[c] = (float)(uint8_t)o.code[c] * (1.0f / 255.0f);
+    o.alpha = p.w;
+    return o;
+  }
+  static __device__ __forceinline__ void Integers(const EncImage& im, int x, int y, int32_t* c, int32_t* alpha) {
+    const uchar4 p = Load(im, x, y);
+    if (im.gray) c[0] = p.x;
+    else { c[0] = p.z; c[1] = p.y; c[2] = p.x; }
+    *alpha = p.w;
+  }
+};
+
+struct Bgra8Any : Bgra8Surface {};   // the same surface where the template kernels are wanted (see enc_xyb_kernel<Bgra8Surface>)
+
+// kN interleaved samples of type T (uint16_t, binary16 as EncHalf, float) per pixel, tight rows.  The host packs the rows when it
+// uploads them, whatever stride the caller's memory has, and the base of a device allocation is aligned to 256 bytes: a pixel whose
+// size is a power of two (2, 4, 8, 16 bytes) is therefore aligned to its size and is read with one load of that width; a 6-byte
+// (RGB16) or 12-byte (RGB32) pixel is only as aligned as one sample, and is read sample by sample.  Either way the 64 lanes of a
+// wavefront read 64 neighbouring pixels, so every byte of a cache line that is fetched is used.
+struct EncHalf { uint16_t bits; };
+template <class T> struct SampleBits { typedef uint32_t Type; };
+template <> struct SampleBits<uint16_t> { typedef uint16_t Type; };
+template <> struct SampleBits<EncHalf> { typedef uint16_t Type; };
+template <int kBytes> struct PixelWord { typedef void Type; };
+template <> struct PixelWord<2> { typedef uint16_t Type; };
+template <> struct PixelWord<4> { typedef uint32_t Type; };
+template <> struct PixelWord<8> { typedef uint2 Type; };
+template <> struct PixelWord<16> { typedef uint4 Type; };
+
+template <class T, int kN>
+struct Samples {
+  static constexpr bool kCodes8 = false;
+  typedef typename SampleBits<T>::Type Raw;
+  static constexpr int kBytes = kN * (int)sizeof(Raw);
+  static constexpr bool kOneLoad = kBytes == 2 || kBytes == 4 || kBytes == 8 || kBytes == 16;
+  static __device__ __forceinline__ void Load(const EncImage& im, int x, int y, Raw* s) {
+    const uint8_t* p = im.bgra + (size_t)y * im.stride + (size_t)x * kBytes;
+    if constexpr (kOneLoad) {
+      typedef typename PixelWord<kOneLoad ? kBytes : 4>::Type Word;
+      const Word w = *(const Word*)p;
+      __builtin_memcpy(s, &w, kBytes);
+    } else {
+      for (int k = 0; k < kN; k++) s[k] = ((const Raw*)p)[k];
+    }
+  }
+  static __device__ __forceinline__ float Value(const EncImage& im, Raw r) {
+    if constexpr (sizeof(T) == 4) return __uint_as_float(r);
+    else if constexpr (sizeof(Raw) == 2 && !__is_same(T, uint16_t)) return __half2float(__ushort_as_half(r));
+    else return (float)r * im.sample_scale;
+  }
+  static __device__ __forceinline__ EncPixel Nominal(const EncImage& im, int x, int y) {
+    Raw s[kN];
+    Load(im, x, y, s);
+    constexpr int kColour = kN >= 3 ? 3 : 1;
+    EncPixel o;
+    for (int c = 0; c < 3; c++) { o.v[c] = Value(im, s[kColour == 3 ? c : 0]); o.code[c] = 0; }
+    o.alpha = (kN & 1) ? 0 : (int32_t)s[kN - 1];
+    return o;
+  }
+  static __device__ __forceinline__ void Integers(const EncImage& im, int x, int y, int32_t* c, int32_t* alpha) {
+    Raw s[kN];
+    Load(im, x, y, s);
+    constexpr int kColour = kN >= 3 ? 3 : 1;
+    for (int k = 0; k < kColour; k++) c[k] = (int32_t)s[k];
+    *alpha = (kN & 1) ? 0 : (int32_t)s[kN - 1];
+  }
+};
+
+// Inverse of the transfer function `tf` (EncTransfer), odd in its argument: samples below 0 and above 1 stay what they are.
+// kUnsigned: the samples are bytes, never negative - no |e| stands between the byte's scaling and the curve's first addition, so the
+// BGRA8 instantiation contracts them into the one fused multiply-add it has always been (SaveImage's bytes are pinned on it).
+template <bool kUnsigned>
+__device__ __forceinline__ float SampleToLinear(int tf, float e) {
+  const float a = kUnsigned ? e : fabsf(e);
+  float r;
+  switch (tf) {
+    case kTransferSrgb: r = a <= 0.04045f ? a / 12.92f : powf((a + 0.055f) / 1.055f, 2.4f); break;
+    case kTransfer709: r = a < 0.081f ? a / 4.5f : powf((a + 0.099f) / 1.099f, 1.0f / 0.45f); break;
+    case kTransferPq: {   // SMPTE ST 2084, 1.0 = 10000 nits (the matrix scales to the 255 nits XYB is built on)
+      const float xp = powf(a, 1.0f / 78.84375f);
+      const float num = fmaxf(xp - 0.8359375f, 0.0f), den = 18.8515625f - 18.6875f * xp;
+      r = powf(num / den, 1.0f / 0.1593017578125f);
+      break;
+    }
+    default: return e;
+  }
+  return kUnsigned ? r : copysignf(r, e);
+}
+
+// ------------------------------------------------------------------ samples -> XYB (+ alpha plane)
+// Nominal samples -> linear (the space's transfer function, or the tone curves of an ICC profile) -> linear sRGB (3x3, where the
+// space has other primaries or another reference intensity) -> opsin absorbance.
+template <class L>
 __global__ void enc_xyb_kernel(EncImage im) {
+  const size_t n = (size_t)im.w * im.h;
+  const float kM[9] = {0.30f, 0.622f, 0.078f, 0.23f, 0.692f, 0.078f, 0.24342268924547819f, 0.20476744424496821f, 0.55180986650955360f};
+  const float kB = 0.0037930732552754493f;
+  const float cb = cbrtf(kB);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % im.w), y = (int)(i / im.w);
+    const EncPixel p = L::Nominal(im, x, y);
+    float r = SampleToLinear<L::kCodes8>(im.transfer, p.v[0]), g = SampleToLinear<L::kCodes8>(im.transfer, p.v[1]),
+          b = SampleToLinear<L::kCodes8>(im.transfer, p.v[2]);
+    bool matrix = im.use_matrix != 0;
+    if constexpr (L::kCodes8) {
+      if (im.icc_lin) {   // the document's own tone curves and primaries
+        r = im.icc_lin[p.code[0]]; g = im.icc_lin[256 + p.code[1]]; b = im.icc_lin[512 + p.code[2]];
+        matrix = true;
+      }
+    }
+    if (matrix) {
+      const float pr = r, pg = g, pb = b;
+      r = im.icc_to_srgb[0] * pr + im.icc_to_srgb[1] * pg + im.icc_to_srgb[2] * pb;
+      g = im.icc_to_srgb[3] * pr + im.icc_to_srgb[4] * pg + im.icc_to_srgb[5] * pb;
+      b = im.icc_to_srgb[6] * pr + im.icc_to_srgb[7] * pg + im.icc_to_srgb[8] * pb;
+    }
+    float mr = kM[0] * r + kM[1] * g + kM[2] * b + kB;
+    float mg = kM[3] * r + kM[4] * g + kM[5] * b + kB;
+    float mb = kM[6] * r + kM[7] * g + kM[8] * b + kB;
+    mr = fmaxf(mr, 0.f); mg = fmaxf(mg, 0.f); mb = fmaxf(mb, 0.f);
+    const float gr = cbrtf(mr) - cb, gg = cbrtf(mg) - cb, gb = cbrtf(mb) - cb;
+    im.xyb[0][i] = 0.5f * (gr - gg);
+    im.xyb[1][i] = 0.5f * (gr + gg);
+    im.xyb[2][i] = gb;
+    if (im.has_alpha) im.alpha_px[i] = p.alpha;
+  }
+}
+
+// The sRGB BGRA8 surface of SaveImage keeps the text it has always had.  SaveImage's files are pinned byte for byte
+// (tests/golden/effort7_sha256.json), and with them the fused multiply-adds the compiler forms out of this text: the template above,
+// instantiated for the same loader, computes the same expressions but came out with another contraction of the opsin sums (fma(g,
+// 0.622, r * 0.30) for fma(r, 0.30, g * 0.622)), which moves XYB samples by an ulp and a 56 KB file by two bytes.  8-bit input in
+// another colour encoding goes through the template (Bgra8Any).
+template <>
+__global__ void enc_xyb_kernel<Bgra8Surface>(EncImage im) {
   const size_t n = (size_t)im.w * im.h;
   const float kM[9] = {0.30f, 0.622f, 0.078f, 0.23f, 0.692f, 0.078f, 0.24342268924547819f, 0.20476744424496821f, 0.55180986650955360f};
   const float kB = 0.0037930732552754493f;
@@ -73,6 +230,22 @@ __global__ void enc_xyb_kernel(EncImage im) {
     im.xyb[1][i] = 0.5f * (gr + gg);
     im.xyb[2][i] = gb;
     if (im.has_alpha) im.alpha_px[i] = p.w;
+  }
+}
+
+// 8-bit interleaved samples (jxlhip_save_pixels) -> the BGRA8 surface every 8-bit path reads: gray into B = G = R, a missing alpha
+// as 255.  `src`: tight rows of kN bytes per pixel; the surface: im.bgra, im.stride.
+template <int kN>
+__global__ void enc_pack_bgra_kernel(EncImage im, const uint8_t* src) {
+  const size_t n = (size_t)im.w * im.h;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % im.w), y = (int)(i / im.w);
+    const uint8_t* p = src + i * kN;
+    uchar4 o;
+    if (kN >= 3) { o.z = p[0]; o.y = p[1]; o.x = p[2]; }
+    else { o.x = o.y = o.z = p[0]; }
+    o.w = (kN & 1) ? 255 : p[kN - 1];
+    *(uchar4*)(const_cast<uint8_t*>(im.bgra) + (size_t)y * im.stride + (size_t)x * 4) = o;
   }
 }
 
@@ -847,22 +1020,25 @@ __global__ void enc_compact_kernel(EncImage im, const uint64_t* dst_off, uint8_t
 }
 
 // ------------------------------------------------------------------ lossless (Modular) frames
-// BGRA8 -> integer channel planes: Gray(A) takes the B channel (PixelFormatConversion.cpp:34,60); RGB goes through the
-// reversible YCoCg-R transform (RCT type 6), alpha is the last channel.
+// Integer samples -> integer channel planes: RGB goes through the reversible YCoCg-R transform (RCT type 6; 16-bit samples put its
+// chroma into [-65535, 65535]), alpha is the last channel.  Of the BGRA8 surface Gray(A) takes the B channel
+// (PixelFormatConversion.cpp:34,60).
+template <class L>
 __global__ void enc_ll_planes_kernel(EncImage im) {
   const size_t n = (size_t)im.w * im.h;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % im.w), y = (int)(i / im.w);
-    const uchar4 p = *(const uchar4*)(im.bgra + (size_t)y * im.stride + (size_t)x * 4);   // B, G, R, A
+    int32_t v[3], alpha;
+    L::Integers(im, x, y, v, &alpha);
     int c = 0;
-    if (im.gray) im.ll_plane[c++][i] = p.x;
+    if (im.gray) im.ll_plane[c++][i] = v[0];
     else {
-      const int32_t R = p.z, G = p.y, B = p.x;
+      const int32_t R = v[0], G = v[1], B = v[2];
       const int32_t co = R - B, tmp = B + (co >> 1), cg = G - tmp, yy = tmp + (cg >> 1);
       im.ll_plane[0][i] = yy; im.ll_plane[1][i] = co; im.ll_plane[2][i] = cg;
       c = 3;
     }
-    if (im.has_alpha) im.ll_plane[c][i] = p.w;
+    if (im.has_alpha) im.ll_plane[c][i] = alpha;
   }
 }
 
@@ -933,19 +1109,47 @@ static inline unsigned GridFor(size_t work, unsigned cap = 8192) {
 void LaunchEncAnalyze(const EncImage& im, hipStream_t s) {
   hipLaunchKernelGGL(enc_analyze_kernel, dim3(GridFor((size_t)im.w * im.h, 2048)), dim3(256), 0, s, im);
 }
+// The loader of the source `im` describes: the BGRA8 surface, or src_nch interleaved samples of `src_type` (EncSampleType).
+template <class T>
+static void LaunchXybSamples(const EncImage& im, hipStream_t s) {
+  const dim3 grid(GridFor((size_t)im.w * im.h)), block(256);
+  switch (im.src_nch) {
+    case 1: hipLaunchKernelGGL((enc_xyb_kernel<Samples<T, 1>>), grid, block, 0, s, im); break;
+    case 2: hipLaunchKernelGGL((enc_xyb_kernel<Samples<T, 2>>), grid, block, 0, s, im); break;
+    case 3: hipLaunchKernelGGL((enc_xyb_kernel<Samples<T, 3>>), grid, block, 0, s, im); break;
+    default: hipLaunchKernelGGL((enc_xyb_kernel<Samples<T, 4>>), grid, block, 0, s, im); break;
+  }
+}
+void LaunchEncXyb(const EncImage& im, hipStream_t s) {
+  switch (im.src_nch ? im.src_type : 0) {
+    case kSampleUint16: LaunchXybSamples<uint16_t>(im, s); break;
+    case kSampleFloat16: LaunchXybSamples<EncHalf>(im, s); break;
+    case kSampleFloat32: LaunchXybSamples<float>(im, s); break;
+    default:
+      if (im.transfer == kTransferSrgb && !im.use_matrix) hipLaunchKernelGGL(enc_xyb_kernel<Bgra8Surface>, dim3(GridFor((size_t)im.w * im.h)), dim3(256), 0, s, im);
+      else hipLaunchKernelGGL(enc_xyb_kernel<Bgra8Any>, dim3(GridFor((size_t)im.w * im.h)), dim3(256), 0, s, im);
+      break;
+  }
+}
+void LaunchEncPackBgra(const EncImage& im, const uint8_t* src, int nch, hipStream_t s) {
+  const dim3 grid(GridFor((size_t)im.w * im.h)), block(256);
+  switch (nch) {
+    case 1: hipLaunchKernelGGL(enc_pack_bgra_kernel<1>, grid, block, 0, s, im, src); break;
+    case 2: hipLaunchKernelGGL(enc_pack_bgra_kernel<2>, grid, block, 0, s, im, src); break;
+    case 3: hipLaunchKernelGGL(enc_pack_bgra_kernel<3>, grid, block, 0, s, im, src); break;
+    default: hipLaunchKernelGGL(enc_pack_bgra_kernel<4>, grid, block, 0, s, im, src); break;
+  }
+}
 void LaunchEncFrontEnd(const EncImage& im, hipStream_t s) {
-  hipLaunchKernelGGL(enc_xyb_kernel, dim3(GridFor((size_t)im.w * im.h)), dim3(256), 0, s, im);
+  LaunchEncXyb(im, s);
   hipLaunchKernelGGL(enc_sharpen_pad_kernel, dim3(GridFor((size_t)im.wp * im.hp)), dim3(256), 0, s, im);
   hipLaunchKernelGGL(enc_activity_kernel, dim3(GridFor((size_t)im.w8 * im.h8)), dim3(256), 0, s, im);
   const unsigned regions = (unsigned)(((im.w8 + 7) / 8) * ((im.h8 + 7) / 8));
   hipLaunchKernelGGL(enc_strategy_kernel, dim3(GridFor(regions)), dim3(256), 0, s, im);
   hipLaunchKernelGGL(enc_varblock_kernel, dim3(regions), dim3(256), 0, s, im);
 }
-// the pieces of the front end the distance map and the closed loop of efforts 8 and 9 launch on their own: BGRA -> XYB planes; DCTs
-// and quantisation again after the quant field has changed (the kernel rewrites every value it wrote)
-void LaunchEncXyb(const EncImage& im, hipStream_t s) {
-  hipLaunchKernelGGL(enc_xyb_kernel, dim3(GridFor((size_t)im.w * im.h)), dim3(256), 0, s, im);
-}
+// the pieces of the front end the distance map and the closed loop of efforts 8 and 9 launch on their own: samples -> XYB planes
+// (LaunchEncXyb above); DCTs and quantisation again after the quant field has changed (the kernel rewrites every value it wrote)
 void LaunchEncVarblocks(const EncImage& im, hipStream_t s) {
   const unsigned regions = (unsigned)(((im.w8 + 7) / 8) * ((im.h8 + 7) / 8));
   hipLaunchKernelGGL(enc_varblock_kernel, dim3(regions), dim3(256), 0, s, im);
@@ -972,7 +1176,17 @@ void LaunchEncSections(const EncImage& im, hipStream_t s) {
 }
 void LaunchEncLossless(const EncImage& im, int stage, hipStream_t s) {
   if (stage == 0) {
-    hipLaunchKernelGGL(enc_ll_planes_kernel, dim3(GridFor((size_t)im.w * im.h)), dim3(256), 0, s, im);
+    const dim3 grid(GridFor((size_t)im.w * im.h)), block(256);
+    if (im.src_nch && im.src_type == kSampleUint16) {
+      switch (im.src_nch) {
+        case 1: hipLaunchKernelGGL((enc_ll_planes_kernel<Samples<uint16_t, 1>>), grid, block, 0, s, im); break;
+        case 2: hipLaunchKernelGGL((enc_ll_planes_kernel<Samples<uint16_t, 2>>), grid, block, 0, s, im); break;
+        case 3: hipLaunchKernelGGL((enc_ll_planes_kernel<Samples<uint16_t, 3>>), grid, block, 0, s, im); break;
+        default: hipLaunchKernelGGL((enc_ll_planes_kernel<Samples<uint16_t, 4>>), grid, block, 0, s, im); break;
+      }
+    } else {
+      hipLaunchKernelGGL(enc_ll_planes_kernel<Bgra8Surface>, grid, block, 0, s, im);
+    }
     hipLaunchKernelGGL(enc_ll_tokens_kernel, dim3(64, im.ng), dim3(256), 0, s, im);
   } else {
     const size_t lds = EncCodeLds(im.mcode, true) + 16 + kSectionsPerWg * sizeof(WaveScratch);

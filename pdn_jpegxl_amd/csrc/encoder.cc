@@ -34,6 +34,7 @@ void LaunchEncCompact(const EncImage& im, const uint64_t* dst_off, uint8_t* dst,
 void LaunchEncLossless(const EncImage& im, int stage, hipStream_t s);
 void LaunchEncLosslessSearch(const EncImage& im, const LlSearch& ls, int stage, hipStream_t s);   // lossless_kernels.hip
 void LaunchEncXyb(const EncImage& im, hipStream_t s);
+void LaunchEncPackBgra(const EncImage& im, const uint8_t* src, int nch, hipStream_t s);
 void LaunchEncVarblocks(const EncImage& im, hipStream_t s);
 // distance_kernels.hip
 void LaunchDistMask(const DistMap& dm, hipStream_t s);
@@ -213,19 +214,91 @@ void EmitFile(const std::vector<uint8_t>& codestream, const EncoderImageMetadata
   Progress(progress, 95);
 }
 
-// Geometry + upload + pixel-format analysis shared by the lossy and the lossless path (Encoder/JxlEncoder.cpp:33-77).
-void BeginImage(const BitmapData* bmp, const EncoderImageMetadata* md, Arena& A, EncImage& im, ProgressProc progress) {
-  const uint32_t w = bmp->width, h = bmp->height;
-  if (!w || !h || !bmp->scan0 || bmp->stride < (uint64_t)w * 4) throw EncFail(EncoderStatus_EncodeError, "invalid bitmap");
+// Where the pixels of a save come from and what the headers say about them: the BGRA8 surface of SaveImage (8-bit integers, sRGB), or
+// the samples of jxlhip_save_pixels, already checked (CheckPixels).
+struct EncSource {
+  const BitmapData* bmp = nullptr;
+  const JxlHipPixels* px = nullptr;
+  uint32_t bits = 8, exp_bits = 0;          // as EncImageInfo
+  uint32_t primaries = 1, transfer = 13;
+  bool pq = false;
+  uint32_t width() const { return bmp ? bmp->width : px->width; }
+  uint32_t height() const { return bmp ? bmp->height : px->height; }
+  size_t sample_bytes() const { return exp_bits == 8 ? 4 : (bits > 8 ? 2 : 1); }
+  bool deep() const { return bits > 8; }    // more than 8 bits per sample, floats included
+  void Describe(EncImageInfo& ii) const {
+    ii.bits = bits; ii.exp_bits = exp_bits; ii.primaries = primaries; ii.transfer = transfer; ii.pq_intensity = pq;
+  }
+};
+
+void Inv3(const double m[9], double o[9]) {
+  const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+  o[0] = (m[4] * m[8] - m[5] * m[7]) / d; o[1] = (m[2] * m[7] - m[1] * m[8]) / d; o[2] = (m[1] * m[5] - m[2] * m[4]) / d;
+  o[3] = (m[5] * m[6] - m[3] * m[8]) / d; o[4] = (m[0] * m[8] - m[2] * m[6]) / d; o[5] = (m[2] * m[3] - m[0] * m[5]) / d;
+  o[6] = (m[3] * m[7] - m[4] * m[6]) / d; o[7] = (m[1] * m[6] - m[0] * m[7]) / d; o[8] = (m[0] * m[4] - m[1] * m[3]) / d;
+}
+
+void SetGeometry(uint32_t w, uint32_t h, EncImage& im) {
   memset(&im, 0, sizeof(im));
   im.w = (int32_t)w; im.h = (int32_t)h;
   im.w8 = (int32_t)((w + 7) / 8); im.h8 = (int32_t)((h + 7) / 8);
   im.wp = im.w8 * 8; im.hp = im.h8 * 8;
   im.xg = (int32_t)((w + 255) / 256); im.yg = (int32_t)((h + 255) / 256); im.ng = im.xg * im.yg;
   im.xlf = (int32_t)((w + 2047) / 2048); im.ylf = (int32_t)((h + 2047) / 2048); im.nlf = im.xlf * im.ylf;
+}
+
+// jxlhip_save_pixels: geometry + upload.  The channels are as stated (nothing is analysed); the rows are packed on the way up, so
+// the device rows are tight whatever stride the caller's memory has (what the loaders of encode_kernels.hip rely on).  8-bit samples
+// become the BGRA8 surface of SaveImage on the device, and every 8-bit path - the byte-keyed lossless search included - runs as it
+// does for SaveImage.
+void BeginPixels(const EncSource& src, Arena& A, EncImage& im, ProgressProc progress) {
+  const JxlHipPixels& px = *src.px;
+  const uint32_t w = px.width, h = px.height;
+  SetGeometry(w, h, im);
+  const int nch = px.num_channels;
+  const size_t row = (size_t)w * nch * src.sample_bytes();
+  uint8_t* d_src = A.Get<uint8_t>(row * h);
+  ENC_HIP(hipMemcpy2D(d_src, row, px.data, px.stride_bytes, row, h, hipMemcpyHostToDevice));
+  im.gray = nch < 3;
+  im.has_alpha = (nch & 1) ? 0 : 1;
+  im.transfer = src.transfer == 8 ? kTransferLinear : (src.transfer == 1 ? kTransfer709 : (src.transfer == 16 ? kTransferPq : kTransferSrgb));
+  if (!im.gray && (src.primaries != 1 || src.pq)) {
+    // linear samples of the space's primaries, relative to its intensity target -> linear sRGB relative to 255 nits
+    static const double kSrgb[3][2] = {{0.639998686, 0.330010138}, {0.300003784, 0.600003357}, {0.150002046, 0.059997204}};
+    static const double kP3[3][2] = {{0.680, 0.320}, {0.265, 0.690}, {0.150, 0.060}}, k2100[3][2] = {{0.708, 0.292}, {0.170, 0.797}, {0.131, 0.046}};
+    const double white[2] = {0.3127, 0.3290};
+    double from_srgb[9], to_srgb[9];
+    if (!MatrixFromLinearSrgb(src.primaries == 11 ? kP3 : (src.primaries == 9 ? k2100 : kSrgb), white, from_srgb))
+      throw EncFail(EncoderStatus_EncodeError, "the colour encoding's primaries have no matrix");
+    Inv3(from_srgb, to_srgb);
+    const double sc = src.pq ? 10000.0 / 255.0 : 1.0;
+    for (int k = 0; k < 9; k++) im.icc_to_srgb[k] = (float)(to_srgb[k] * sc);
+    im.use_matrix = 1;
+  }
+  if (src.deep()) {
+    im.bgra = d_src; im.stride = (int64_t)row;
+    im.src_nch = nch;
+    im.src_type = px.sample_type;
+    im.sample_scale = 1.0f / (float)((1u << src.bits) - 1);
+  } else {
+    uint8_t* d_bgra = A.Get<uint8_t>((size_t)w * 4 * h);
+    im.bgra = d_bgra; im.stride = (int64_t)w * 4;
+    LaunchEncPackBgra(im, d_src, nch, nullptr);
+  }
+  Progress(progress, 5);
+}
+
+// Geometry + upload + pixel-format analysis shared by the lossy and the lossless path (Encoder/JxlEncoder.cpp:33-77).
+void BeginImage(const EncSource& src, const EncoderImageMetadata* md, Arena& A, EncImage& im, ProgressProc progress) {
+  if (src.px) return BeginPixels(src, A, im, progress);
+  const BitmapData* bmp = src.bmp;
+  const uint32_t w = bmp->width, h = bmp->height;
+  if (!w || !h || !bmp->scan0 || bmp->stride < (uint64_t)w * 4) throw EncFail(EncoderStatus_EncodeError, "invalid bitmap");
+  SetGeometry(w, h, im);
   uint8_t* d_bgra = A.Get<uint8_t>((size_t)bmp->stride * h);
   ENC_HIP(hipMemcpy(d_bgra, bmp->scan0, (size_t)bmp->stride * h, hipMemcpyHostToDevice));
-  im.bgra = d_bgra; im.stride = (int32_t)bmp->stride;
+  im.bgra = d_bgra; im.stride = (int64_t)bmp->stride;
+  im.transfer = kTransferSrgb;
   im.flags = A.Get<uint32_t>(4, true);
   LaunchEncAnalyze(im, nullptr);
   uint32_t flags[2] = {0, 0};
@@ -238,12 +311,12 @@ void BeginImage(const BitmapData* bmp, const EncoderImageMetadata* md, Arena& A,
 
 // ANS-codes the groups' tokens (im.tok_ll) with `mcode`, gathers the sections and assembles the codestream behind the finished LfGlobal
 // prefix.  The section buffers are allocated at the first call of a save and reused by the next.
-std::vector<uint8_t> FinishLossless(EncImage& im, Arena& A, const EncCode& mcode, BitWriter& lf_global, const EncoderImageMetadata* md, hipStream_t s) {
+std::vector<uint8_t> FinishLossless(EncImage& im, const EncSource& src, Arena& A, const EncCode& mcode, BitWriter& lf_global, const EncoderImageMetadata* md, hipStream_t s) {
   const bool single = im.ng == 1;
   im.mcode = UploadCode(A, mcode);
   const int nsec = im.ng;
   if (!im.sec_bytes) {
-    im.sec_cap = ((size_t)kLlTokCap * 6 + 256) & ~(size_t)15;
+    im.sec_cap = ((size_t)kLlTokCap * kSecBytesPerTok + 256) & ~(size_t)15;
     im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
     im.sec_bits = A.Get<uint64_t>(nsec, true);
     im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1, true);
@@ -266,6 +339,7 @@ std::vector<uint8_t> FinishLossless(EncImage& im, Arena& A, const EncCode& mcode
   EncImageInfo ii;
   ii.xsize = (uint32_t)im.w; ii.ysize = (uint32_t)im.h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = false;
   ii.icc = md->iccProfile; ii.icc_size = md->iccProfile ? md->iccProfileSize : 0;
+  src.Describe(ii);
   EncFrameInfo fi;
   fi.encoding = 1; fi.group_size_shift = 1; fi.gab = false; fi.epf_iters = 0;
   BitWriter cs;
@@ -291,7 +365,7 @@ std::vector<uint8_t> FinishLossless(EncImage& im, Arena& A, const EncCode& mcode
 
 // The stream of efforts 1..7: 256x256 groups, YCoCg-R for RGB, gradient predictor, one context per channel.  `progress` (may be
 // null) sees 25 once the histograms are down.
-std::vector<uint8_t> CodeLosslessFixed(EncImage& im, Arena& A, const EncoderImageMetadata* md, hipStream_t s, ProgressProc progress) {
+std::vector<uint8_t> CodeLosslessFixed(EncImage& im, const EncSource& src, Arena& A, const EncoderImageMetadata* md, hipStream_t s, ProgressProc progress) {
   im.ll_nch = (im.gray ? 1 : 3) + im.has_alpha;
   im.ll_rct = im.gray ? 0 : 1;
   im.ll_tok_extra = 0;
@@ -322,7 +396,7 @@ std::vector<uint8_t> CodeLosslessFixed(EncImage& im, Arena& A, const EncoderImag
     lf_global.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);      // first channel
     lf_global.U32(WV(6), WB(2), WB(4, 2), WB(6, 10), 6);              // type 6: YCoCg-R
   }
-  return FinishLossless(im, A, mcode, lf_global, md, s);
+  return FinishLossless(im, src, A, mcode, lf_global, md, s);
 }
 
 // ---- the searched stream of efforts 8 and 9 ("Lossless efforts 8 and 9")
@@ -444,7 +518,7 @@ thread_local JxlHipLosslessInfo g_last_lossless;
 constexpr int kLlMaxClusters = 12;   // of the effort-9 code: what enc_ll_sections_kernel stages in LDS
 
 // The searched stream(s).  `im` arrives from BeginImage; `fixed` is the stream of effort 7 (the fallback).  Returns the stream to write.
-std::vector<uint8_t> CodeLosslessSearched(EncImage& im, Arena& A, const EncoderImageMetadata* md, int tier, hipStream_t s, ProgressProc progress,
+std::vector<uint8_t> CodeLosslessSearched(EncImage& im, const EncSource& src, Arena& A, const EncoderImageMetadata* md, int tier, hipStream_t s, ProgressProc progress,
                                           StageMarks& marks, const std::vector<uint8_t>& fixed, JxlHipLosslessInfo& info) {
   const size_t npx = (size_t)im.w * im.h;
   const bool single = im.ng == 1;
@@ -590,7 +664,7 @@ std::vector<uint8_t> CodeLosslessSearched(EncImage& im, Arena& A, const EncoderI
     WriteLosslessSearchHeader(lf_global, ncol, nch_all, rct_type);
     if (ncol && !single) WriteTokensHost(pal_tok, mcode, lf_global);   // the colours are the global stream's only channel
     const size_t k = marks.Begin(wp_ctx ? "lossless: sections (property-15 contexts)" : "lossless: sections", s);
-    cand.bytes = FinishLossless(im, A, mcode, lf_global, md, s);
+    cand.bytes = FinishLossless(im, src, A, mcode, lf_global, md, s);
     marks.End(k, s);
     return cand;
   };
@@ -625,24 +699,25 @@ std::vector<uint8_t> CodeLosslessSearched(EncImage& im, Arena& A, const EncoderI
 
 // Lossless: a Modular frame in the original (sRGB) colour space (Encoder/JxlEncoder.cpp:214,325).  Efforts up to 7 write the fixed
 // stream; 8 and 9 also search palette, colour transform, predictors and (9) contexts, and write the smaller of the two.
-void EncodeLossless(const BitmapData* bmp, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
+void EncodeLossless(const EncSource& src, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
   Arena A;
   hipStream_t s = nullptr;
   EncImage im;
-  BeginImage(bmp, md, A, im, progress);
+  BeginImage(src, md, A, im, progress);
   const size_t npx = (size_t)im.w * im.h;
   im.lossless = 1;
   im.ll_nch = (im.gray ? 1 : 3) + im.has_alpha;
   for (int c = 0; c < im.ll_nch; c++) im.ll_plane[c] = A.Get<int32_t>(npx);
   im.tok_ll = A.Get<DevToken>((size_t)im.ng * kLlTokCap);
   Progress(progress, 15);
-  const int tier = opt->effort >= 9 ? 9 : (opt->effort >= 8 ? 8 : 0);
-  std::vector<uint8_t> codestream = CodeLosslessFixed(im, A, md, s, tier ? nullptr : progress);
+  // the search keys palettes and candidates on bytes: samples of more than 8 bits get the fixed stream at every effort
+  const int tier = src.deep() ? 0 : (opt->effort >= 9 ? 9 : (opt->effort >= 8 ? 8 : 0));
+  std::vector<uint8_t> codestream = CodeLosslessFixed(im, src, A, md, s, tier ? nullptr : progress);
   if (tier) {
     StageMarks marks;
     JxlHipLosslessInfo info;
     memset(&info, 0, sizeof(info));
-    codestream = CodeLosslessSearched(im, A, md, tier, s, progress, marks, codestream, info);
+    codestream = CodeLosslessSearched(im, src, A, md, tier, s, progress, marks, codestream, info);
     marks.Publish(&g_last_save_stages);
     g_last_lossless = info;
   }
@@ -687,12 +762,12 @@ struct ReconDecoder {
   }
 };
 
-void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
+void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
   Arena A;
   hipStream_t s = nullptr;
   EncImage im;
   PhaseClock clk;
-  BeginImage(bmp, md, A, im, progress);
+  BeginImage(src, md, A, im, progress);
   if (md->iccProfile && md->iccProfileSize) {
     // Lossy with a profile: the samples reach XYB through the profile (the reference leaves that to its encoder library's colour
     // management, Encoder/JxlEncoder.cpp:258-268).  Matrix / TRC profiles are evaluated here; a profile that would need a full
@@ -708,7 +783,7 @@ void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const Encoder
     for (int k = 0; k < 9; k++) im.icc_to_srgb[k] = (float)model.to_linear_srgb[k];
   }
   clk.Lap("upload + analysis");
-  const uint32_t w = bmp->width, h = bmp->height;
+  const uint32_t w = src.width(), h = src.height();
   const size_t npx = (size_t)w * h, npad = (size_t)im.wp * im.hp, ncell = (size_t)im.w8 * im.h8;
   // ---- 2. quantiser and loop-filter parameters (distance, :319); the effort picks the transform set below
   const float distance = std::max(0.05f, std::min(25.0f, opt->distance));
@@ -803,7 +878,7 @@ void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const Encoder
   im.hist_mod = A.Get<uint32_t>(kNumEncLeaves * kEncSyms);
   im.hist_ac = A.Get<uint32_t>((size_t)kAcContexts * kEncSyms);
   const int nsec = im.nlf + im.ng + 1;   // + the global alpha stream of single-group frames
-  im.sec_cap = ((size_t)std::max(kLfTokCap + kMetaTokCap, kAcTokCap + kAlphaTokCap) * 6 + 256) & ~(size_t)15;
+  im.sec_cap = ((size_t)std::max(kLfTokCap + kMetaTokCap, kAcTokCap + kAlphaTokCap) * kSecBytesPerTok + 256) & ~(size_t)15;
   im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
   im.sec_bits = A.Get<uint64_t>(nsec);
   im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1);
@@ -818,6 +893,7 @@ void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const Encoder
   EncImageInfo ii;
   ii.xsize = w; ii.ysize = h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = true;
   ii.icc = md->iccProfile; ii.icc_size = md->iccProfile ? md->iccProfileSize : 0;
+  src.Describe(ii);
   // The codestream of the quantised data in `im`.  `final`: the call whose stream is (normally) written: it reports progress 25 and
   // 30; `mk`: where its kernel groups are timed (null: nowhere).
   auto CodeField = [&](bool final, StageMarks* mk, bool publish) -> std::vector<uint8_t> {
@@ -946,7 +1022,7 @@ void EncodeLossy(const BitmapData* bmp, const EncoderOptions* opt, const Encoder
     dm.mask = A.Get<float>(npx);
     dm.cell = A.Get<float>(ncell);
     LaunchDistMask(dm, s);
-    ReconDecoder rd(A, (size_t)w * h * 4);
+    ReconDecoder rd(A, (size_t)w * h * 4 * src.sample_bytes());   // what the decoder writes: up to four samples per pixel
     std::vector<float> cells(ncell), cells0, sorted;
     float tau = 0.f;
     int over_first = 0, over_last = 0;
@@ -1046,7 +1122,8 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_distance_map(const uint8_t* a_
       const uint32_t stride = k ? stride_b : stride_a;
       EncImage im;
       memset(&im, 0, sizeof(im));
-      im.w = (int32_t)w; im.h = (int32_t)h; im.stride = (int32_t)stride;
+      im.w = (int32_t)w; im.h = (int32_t)h; im.stride = (int64_t)stride;
+      im.transfer = kTransferSrgb;
       uint8_t* d_bgra = A.Get<uint8_t>((size_t)stride * h);
       ENC_HIP(hipMemcpy(d_bgra, src, (size_t)stride * (h - 1) + (size_t)w * 4, hipMemcpyHostToDevice));   // the last row may end at its pixels
       im.bgra = d_bgra;
@@ -1081,8 +1158,10 @@ extern "C" JXLFILETYPEIO_API EncoderStatus SaveImage(const BitmapData* bitmap, c
     g_last_lossless = JxlHipLosslessInfo();
     Progress(progress, 0);   // :162
     if (!callbacks->Write) throw EncFail(EncoderStatus_NullParameter, "");
-    if (options->lossless) EncodeLossless(bitmap, options, metadata, callbacks, progress);   // :214,325
-    else EncodeLossy(bitmap, options, metadata, callbacks, progress);
+    EncSource src;
+    src.bmp = bitmap;
+    if (options->lossless) EncodeLossless(src, options, metadata, callbacks, progress);   // :214,325
+    else EncodeLossy(src, options, metadata, callbacks, progress);
     return EncoderStatus_Ok;
   } catch (const EncFail& e) {
     if (e.status == EncoderStatus_EncodeError) SetEncErr(err, e.what());
@@ -1094,5 +1173,83 @@ extern "C" JXLFILETYPEIO_API EncoderStatus SaveImage(const BitmapData* bitmap, c
     return EncoderStatus_EncodeError;
   } catch (...) {
     return EncoderStatus_EncodeError;   // never throw across the ABI (:382-389)
+  }
+}
+
+namespace {
+
+// The refusals of jxlhip_save_pixels, decided on the host before any HIP call.  Fills `src` with what the headers will say.
+void CheckPixels(const JxlHipPixels* px, const EncoderOptions* opt, const EncoderImageMetadata* md, EncSource& src) {
+  auto refuse = [](const char* why) { throw EncFail(EncoderStatus_EncodeError, why); };
+  if (!px->data) throw EncFail(EncoderStatus_NullParameter, "");
+  if (!px->width || !px->height) refuse("the image has no pixels");
+  if (px->width > (1u << 30) / px->height) refuse("the image is too large");
+  if (px->num_channels < 1 || px->num_channels > 4) refuse("the number of channels must be 1 (Gray), 2 (Gray, A), 3 (R, G, B) or 4 (R, G, B, A)");
+  size_t sample_bytes = 0;
+  switch (px->sample_type) {
+    case ImageChannelRepresentation_Uint8:
+      if (px->bits_per_sample != 8) refuse("bits_per_sample must be 8 for Uint8 samples");
+      src.bits = 8; sample_bytes = 1;
+      break;
+    case ImageChannelRepresentation_Uint16:
+      if (px->bits_per_sample < 9 || px->bits_per_sample > 16) refuse("bits_per_sample must be 9..16 for Uint16 samples");
+      src.bits = (uint32_t)px->bits_per_sample; sample_bytes = 2;
+      break;
+    case ImageChannelRepresentation_Float16:
+    case ImageChannelRepresentation_Float32:
+      if (px->bits_per_sample != 0) refuse("bits_per_sample must be 0 for float samples");
+      if (px->sample_type == ImageChannelRepresentation_Float16) { src.bits = 16; src.exp_bits = 5; sample_bytes = 2; }
+      else { src.bits = 32; src.exp_bits = 8; sample_bytes = 4; }
+      break;
+    default: refuse("unknown sample type");
+  }
+  if (px->stride_bytes < (uint64_t)px->width * (uint64_t)px->num_channels * sample_bytes) refuse("stride_bytes is smaller than a row of pixels");
+  const bool gray = px->num_channels < 3;
+  switch (px->colour) {
+    case KnownColorProfile_Srgb: break;                                  // 1 or 2 channels: gray with the sRGB curve
+    case KnownColorProfile_LinearSrgb: src.transfer = 8; break;          // 1 or 2 channels: linear gray
+    case KnownColorProfile_LinearGray:
+    case KnownColorProfile_GraySrgbTRC:
+      if (!gray) refuse("a gray colour profile needs 1 or 2 channels");
+      if (px->colour == KnownColorProfile_LinearGray) src.transfer = 8;
+      break;
+    case KnownColorProfile_DisplayP3: src.primaries = 11; break;
+    case KnownColorProfile_Rec709: src.transfer = 1; break;
+    case KnownColorProfile_Rec2020Linear: src.primaries = 9; src.transfer = 8; break;
+    case KnownColorProfile_Rec2020PQ: src.primaries = 9; src.transfer = 16; src.pq = true; break;
+    default: refuse("unknown colour profile");
+  }
+  if (gray && px->colour >= KnownColorProfile_DisplayP3) refuse("an RGB colour profile needs 3 or 4 channels");
+  if (md->iccProfile && md->iccProfileSize) refuse("jxlhip_save_pixels signals colour by the KnownColorProfile only: no ICC profile");
+  if (opt->lossless && src.exp_bits) refuse("lossless float samples are not supported (save lossy, or as integers)");
+}
+
+}  // namespace
+
+// Part 3 of the C-ABI: SaveImage for every sample type the decoder hands out.  Everything behind the front end is SaveImage's.
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels* pixels, const EncoderOptions* options, const EncoderImageMetadata* metadata,
+                                                              IOCallbacks* callbacks, ErrorInfo* err, ProgressProc progress) {
+  if (!pixels || !options || !callbacks || !metadata) return EncoderStatus_NullParameter;
+  try {
+    g_last_dist = LastDistances();
+    g_last_lossless = JxlHipLosslessInfo();
+    EncSource src;
+    src.px = pixels;
+    CheckPixels(pixels, options, metadata, src);
+    if (!callbacks->Write) throw EncFail(EncoderStatus_NullParameter, "");
+    Progress(progress, 0);
+    if (options->lossless) EncodeLossless(src, options, metadata, callbacks, progress);
+    else EncodeLossy(src, options, metadata, callbacks, progress);
+    return EncoderStatus_Ok;
+  } catch (const EncFail& e) {
+    if (e.status == EncoderStatus_EncodeError) SetEncErr(err, e.what());
+    return e.status;
+  } catch (const std::bad_alloc&) {
+    return EncoderStatus_OutOfMemory;
+  } catch (const std::exception& e) {
+    SetEncErr(err, e.what());
+    return EncoderStatus_EncodeError;
+  } catch (...) {
+    return EncoderStatus_EncodeError;
   }
 }

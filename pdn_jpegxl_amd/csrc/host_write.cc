@@ -411,25 +411,56 @@ void WriteCodestreamHeaders(const EncImageInfo& im, BitWriter& bw) {
   bw.Write(8, 0x0A);
   WriteSize(bw, im.xsize, im.ysize);
   // ImageMetadata
+  const bool is_float = im.exp_bits != 0;
+  auto bit_depth = [&] {
+    bw.Bool(is_float);
+    if (!is_float) bw.U32(WV(8), WV(10), WV(12), WB(6, 1), im.bits);                       // integer samples of `bits` bits
+    else { bw.U32(WV(32), WV(16), WV(24), WB(6, 1), im.bits); bw.Write(4, im.exp_bits - 1); }   // floats: bits, exponent bits - 1
+  };
   bw.Bool(false);                                   // not all_default
-  bw.Bool(false);                                   // no extra fields (orientation 1, no animation, default tone mapping)
-  bw.Bool(false);                                   // integer samples ...
-  bw.U32(WV(8), WV(10), WV(12), WB(6, 1), 8);       // ... of 8 bits
-  bw.Bool(true);                                    // modular_16_bit_buffer_sufficient
+  bw.Bool(im.pq_intensity);                         // extra fields: only the tone mapping of PQ needs them
+  if (im.pq_intensity) {
+    bw.Write(3, 0);                                 // orientation 1
+    bw.Bool(false);                                 // no intrinsic size
+    bw.Bool(false);                                 // no preview
+    bw.Bool(false);                                 // no animation
+  }
+  bit_depth();
+  // modular_16_bit_buffer_sufficient: true up to 12 bits (YCoCg-R and the predictors stay inside an int16 then), false beyond and
+  // for floats (their bit patterns are coded)
+  bw.Bool(!is_float && im.bits <= 12);
   bw.U32(WV(0), WV(1), WB(4, 2), WB(12, 1), im.alpha ? 1 : 0);
-  if (im.alpha) bw.Bool(true);                      // the default extra channel: 8-bit unassociated alpha
+  if (im.alpha) {
+    const bool d_alpha = !is_float && im.bits == 8;
+    bw.Bool(d_alpha);                               // the default extra channel: 8-bit unassociated alpha
+    if (!d_alpha) {
+      bw.Enum(0);                                   // type: alpha
+      bit_depth();                                  // the depth and type of the colour samples
+      bw.U32(WV(0), WV(3), WV(4), WB(3, 1), 0);     // dim_shift
+      bw.U32(WV(0), WB(4), WB(5, 16), WB(10, 48), 0);   // no name
+      bw.Bool(false);                               // not associated
+    }
+  }
   bw.Bool(im.xyb);
-  // colour encoding: sRGB (or gray with the sRGB transfer curve), D65, perceptual intent (Encoder/JxlEncoder.cpp:269-282)
+  // colour encoding: sRGB (or gray with the sRGB transfer curve), D65, perceptual intent (Encoder/JxlEncoder.cpp:269-282) unless
+  // jxlhip_save_pixels names another of the host's known profiles
   const bool want_icc = im.icc && im.icc_size;
   bw.Bool(false);                                   // not all_default
   bw.Bool(want_icc);
   bw.Enum(im.gray ? 1 : 0);
   if (!want_icc) {
     bw.Enum(1);                                     // white point D65
-    if (!im.gray) bw.Enum(1);                       // primaries sRGB
+    if (!im.gray) bw.Enum(im.primaries);            // primaries (sRGB)
     bw.Bool(false);                                 // no gamma
-    bw.Enum(13);                                    // transfer function sRGB
+    bw.Enum(im.transfer);                           // transfer function (sRGB)
     bw.Enum(0);                                     // rendering intent perceptual
+  }
+  if (im.pq_intensity) {
+    bw.Bool(false);                                 // tone mapping not all_default
+    bw.Write(16, 0x70E2);                           // intensity target 10000 (binary16)
+    bw.Write(16, 0);                                // min nits 0
+    bw.Bool(false);                                 // not relative to the display's maximum
+    bw.Write(16, 0);                                // linear below 0
   }
   bw.U64(0);                                        // extensions
   bw.Bool(true);                                    // default transform data

@@ -76,6 +76,12 @@ struct EncImageInfo {
   bool xyb = true;       // false: lossless (original colour space, Encoder/JxlEncoder.cpp:214)
   const uint8_t* icc = nullptr;   // embedded ICC profile (JxlEncoderSetICCProfile, Encoder/JxlEncoder.cpp:258-268) instead of the enum encoding
   size_t icc_size = 0;
+  // sample depth and colour encoding (jxlhip_save_pixels; SaveImage keeps the defaults: 8-bit integers, sRGB)
+  uint32_t bits = 8;       // bits per sample: integers 8..16; floats 16 or 32
+  uint32_t exp_bits = 0;   // 0: integers; 5: binary16; 8: binary32.  An alpha channel has the depth and type of the colour samples
+  uint32_t primaries = 1;  // the format's enum: 1 sRGB, 9 BT.2100 (= BT.2020), 11 P3; white point D65 always; ignored for gray
+  uint32_t transfer = 13;  // the format's enum: 1 BT.709, 8 linear, 13 sRGB, 16 PQ
+  bool pq_intensity = false;   // tone mapping: intensity target 10000 (the other fields at their defaults) instead of the default 255
 };
 struct EncFrameInfo {
   uint32_t encoding = 0;           // 0 VarDCT, 1 Modular

@@ -134,6 +134,43 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers(uint32_t xsize, uint
   }
 }
 
+// The same for the sample depth and colour encoding of a jxlhip_save_pixels call: bits / exp_bits as the headers state them (8..16 / 0
+// integers, 16 / 5 binary16, 32 / 8 binary32), `colour` a KnownColorProfile (the gray ones with gray != 0).
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers_deep(uint32_t xsize, uint32_t ysize, int32_t gray, int32_t alpha, int32_t lossless,
+                                                                 uint32_t bits, uint32_t exp_bits, int32_t colour, uint8_t* dst, size_t capacity) {
+  try {
+    EncImageInfo ii;
+    ii.xsize = xsize; ii.ysize = ysize; ii.gray = gray != 0; ii.alpha = alpha != 0; ii.xyb = !lossless;
+    ii.bits = bits; ii.exp_bits = exp_bits;
+    switch (colour) {
+      case KnownColorProfile_Srgb: case KnownColorProfile_GraySrgbTRC: break;
+      case KnownColorProfile_LinearSrgb: case KnownColorProfile_LinearGray: ii.transfer = 8; break;
+      case KnownColorProfile_DisplayP3: ii.primaries = 11; break;
+      case KnownColorProfile_Rec709: ii.transfer = 1; break;
+      case KnownColorProfile_Rec2020Linear: ii.primaries = 9; ii.transfer = 8; break;
+      case KnownColorProfile_Rec2020PQ: ii.primaries = 9; ii.transfer = 16; ii.pq_intensity = true; break;
+      default: return 0;
+    }
+    EncFrameInfo fi;
+    fi.encoding = lossless ? 1 : 0;
+    fi.gab = !lossless; fi.epf_iters = lossless ? 0 : 1;
+    BitWriter cs;
+    WriteCodestreamHeaders(ii, cs);
+    WriteFrameHeader(ii, fi, cs);
+    const uint32_t ng = ((xsize + 255) / 256) * ((ysize + 255) / 256), nlf = ((xsize + 2047) / 2048) * ((ysize + 2047) / 2048);
+    std::vector<uint32_t> sizes(ng == 1 ? 1 : 2 + nlf + ng, 3);
+    WriteToc(sizes, cs);
+    std::vector<uint8_t> bytes = cs.Finish();
+    bytes.resize(bytes.size() + 3 * sizes.size(), 0);
+    std::vector<uint8_t> file = WriteContainer(bytes, nullptr, 0, nullptr, 0);
+    if (file.size() > capacity) return 0;
+    memcpy(dst, file.data(), file.size());
+    return file.size();
+  } catch (...) {
+    return 0;
+  }
+}
+
 // The same with an embedded ICC profile (host only: the ICC stream writer against the parser's reader).
 extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers_icc(uint32_t xsize, uint32_t ysize, int32_t alpha, int32_t lossless, const uint8_t* icc,
                                                                 size_t icc_size, uint8_t* dst, size_t capacity) {
