@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "batch_layout.h"
 #include "entropy_plan.h"
 #include "host_parse.h"
 #include "icc.h"
@@ -46,18 +47,6 @@ static void SetErr(ErrorInfo* e, const char* fmt, ...) {
   else if (n > 255) { memcpy(e->errorMessage, buf, 255); e->errorMessage[255] = 0; }
 }
 
-static inline size_t Align(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Bump {
-  size_t off = 0;
-  size_t Take(size_t bytes, size_t align = 256) {
-    off = Align(off, align);
-    size_t r = off;
-    off += bytes;
-    return r;
-  }
-};
-
 struct StageTimer {
   std::vector<const char*> names;
   std::vector<hipEvent_t> ev;
@@ -67,7 +56,6 @@ struct StageTimer {
 
 using namespace jxlhip;
 
-// Bytes per output sample: the sample type follows the colour channels' depth (Decoder/JxlDecoder.cpp:510-556): u8, u16, f16, f32.
 // Experiment knobs (environment variables read by tools/sweep_*.sh) exist only in a library built with -DJXLHIP_EXPERIMENTS
 // (JXLHIP_EXTRA_CFLAGS): a host process's environment must not be able to change what the shipping library decodes.
 static inline const char* Knob(const char* name) {
@@ -84,32 +72,6 @@ static inline int KnobStride(const char* name, int fallback) {   // lane strides
   if (!e) return fallback;
   const int v = atoi(e);
   return PowerOfTwoUpTo64(v) ? v : fallback;
-}
-static inline size_t OutBytesPerSample(const ParsedFrame& f) { return f.exp_bits ? (f.bits <= 16 ? 2 : 4) : (f.bits > 8 ? 2 : 1); }
-
-// Order bucket of a quant table (every strategy of a quant table shares one bucket).
-static int OrderBucketOfQuantTable(int q) {
-  for (int s = 0; s < kNumStrategies; s++) if (kStrategyQuantTable[s] == q) return kStrategyOrderBucket[s];
-  return 0;
-}
-// Scan list of quant table q: for each channel (X, Y, B) and scan position k, the stored-layout index order[k] and the bits of
-// the dequantisation weight at that index.  custom: the frame's own coefficient orders ([bucket][channel], empty = natural).
-static void BuildScanList(int q, const std::vector<uint16_t> (*custom)[3], std::vector<U32x2>& out, const std::vector<float>* custom_dq = nullptr) {
-  const StaticTables& st = GetStaticTables();
-  const int o = OrderBucketOfQuantTable(q);
-  const std::vector<float>& dq = (custom_dq && custom_dq->size() == st.dq[q].size()) ? *custom_dq : st.dq[q];
-  const size_t n = st.dq[q].size() / 3;
-  out.resize(3 * n);
-  for (int c = 0; c < 3; c++) {
-    const std::vector<uint16_t>& ord = (custom && !custom[o][c].empty()) ? custom[o][c] : st.natural_order[o];
-    for (size_t k = 0; k < n; k++) {
-      const uint32_t p = k < ord.size() ? ord[k] : 0u;
-      uint32_t wb;
-      const float w = dq[(size_t)c * n + (p < n ? p : 0)];
-      memcpy(&wb, &w, 4);
-      out[(size_t)c * n + k] = U32x2{p, wb};
-    }
-  }
 }
 
 struct JxlHipDecoder {
@@ -276,8 +238,8 @@ JxlHipDecoder::JxlHipDecoder(int dev) {
     HIP_OK(hipMalloc(&d_dq[q], st.dq[q].size() * 4));
     HIP_OK(hipMemcpy(d_dq[q], st.dq[q].data(), st.dq[q].size() * 4, hipMemcpyHostToDevice));
     dq_n[q] = (uint32_t)(st.dq[q].size() / 3);
-    std::vector<U32x2> sl;
-    BuildScanList(q, nullptr, sl);
+    std::vector<U32x2> sl(3 * (size_t)dq_n[q]);
+    BuildScanList(q, nullptr, sl.data());
     HIP_OK(hipMalloc(&d_scan[q], sl.size() * sizeof(U32x2)));
     HIP_OK(hipMemcpy(d_scan[q], sl.data(), sl.size() * sizeof(U32x2), hipMemcpyHostToDevice));
   }
@@ -460,7 +422,6 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   S.nfiles = n;
   S.file_of.clear();
   S.files.clear();
-  struct Composite { int file, first, count; std::vector<int> save; uint8_t* out; };
   std::vector<Composite> comps;
   std::vector<const uint8_t*> x_dev_data;
   std::vector<uint8_t*> x_dev_out;
@@ -550,248 +511,22 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // images that failed to parse or were refused are skipped on the device (their DevImage stays zeroed, ng = 0)
   // ---- 2. the entropy stage's plan (entropy_plan.h): decoded ranges, lane mappings, task tables, LDS sizes
   const EntropyPlan plan = PlanEntropy(frames, parse_status, PlanOptions());
-  // ---- 3. layout of blob and workspace
-  Bump blob, ws_zero, ws;
-  const int n_extra = plan.n_extra;   // every pass after the first of a progressive frame is an image record of its own
-  const size_t off_imgs = blob.Take(sizeof(DevImage) * (size_t)(n + n_extra));
-  struct PassLayout {   // what a pass owns: its code, scan lists, entry lists, block index, end positions, LZ77 windows
-    size_t a_cmap, a_cfg, a_alias, a_pfx[3] = {}, lz_hf = 0, scan[kNumQuantTables] = {}, centries, cblk, bitpos, hf_order;
-  };
-  struct PerImg {
-    std::vector<PassLayout> extra;
-    size_t m_direct = 0;   // + 1 when present
-    size_t sec_off, sec_size, tree, m_cmap, m_cfg, m_alias, a_cmap, a_cfg, a_alias, order[kNumOrders][3], cs;
-    size_t m_pfx[3] = {}, a_pfx[3] = {};           // prefix codes: counts, symbol offsets, sorted symbols
-    size_t lz_lf = 0, lz_grp = 0, lz_hf = 0, lz_mod = 0;   // LZ77 windows (+1; 0: none)
-    size_t scan[kNumQuantTables] = {};   // frames with their own coefficient orders: scan lists of the affected quant tables
-    size_t trc_lut = 0;                  // tone-curve tables of an evaluated ICC profile (+1; 0: none)
-    size_t dq[kNumQuantTables] = {};     // frames with their own dequantisation tables (+1; 0: the library table)
-    size_t z_cellinfo, z_status, centries, cblk, hf_order;
-    std::vector<size_t> mod_planes;
-    size_t mod_chan, mod_desc, wp_lf, wp_grp, lf_end, alpha32;
-    size_t lf[3], lf_tmp[3], lfq[3], lf_extra, rawq, sharp, ytox, ytob, binfo, lf_desc, lf_count, alpha_desc, blk_list, blk_count, bitpos, tile_list, tmp[3], xyb[3], inv_sigma, alpha;
-    size_t orient_tmp = 0;   // frames with an orientation other than 1 are decoded here, then laid out as displayed in the caller's buffer
-    size_t layer_px = 0;     // frames of a layered image: w*h*nch f32 samples for the compositor
-    size_t ds_full = 0, ds_alpha = 0;   // reduced-size decode: a Modular frame's full-size output samples / a VarDCT frame's reduced alpha plane
-  };
-  std::vector<PerImg> L((size_t)n);
-  // blob space of a codestream uploaded from the host: once per file (every frame of a layered file points into the same bytes)
-  std::vector<size_t> file_cs((size_t)S.nfiles, 0);   // offset + 1
-  std::vector<uint8_t> cs_put((size_t)S.nfiles, 0);
-  auto take_cs = [&](int i) {
-    const ParsedFrame& f = frames[i];
-    if (!f.is_layer) return blob.Take(f.cs_size + 16);
-    size_t& o = file_cs[S.file_of[i]];
-    if (!o) o = blob.Take(f.cs_size + 16) + 1;
-    return o - 1;
-  };
-  // the images' status words (64 B each) lie side by side: ONE copy brings them back (a copy per image was 384 five-microsecond copy
-  // kernels at the end of the pixel stream - 2 ms of the step - and as many API calls)
-  const size_t z_status_base = ws_zero.Take((size_t)std::max(1, n) * 64);
-  size_t chunk_pix = 0;   // padded pixels of the largest VarDCT frame of the batch
-  for (int i = 0; i < n; i++) {
-    if (parse_status[i] != DecoderStatus_Ok) continue;
-    const ParsedFrame& f = frames[i];
-    PerImg& l = L[i];
-    const size_t cells = (size_t)f.w8 * f.h8, pix = cells * 64, tiles = (size_t)((f.w8 + 7) / 8) * ((f.h8 + 7) / 8);
-    l.sec_off = blob.Take(8 * f.sec_off.size());
-    l.sec_size = blob.Take(4 * f.sec_size.size());
-    l.hf_order = blob.Take(4 * (size_t)std::max<uint32_t>(1, f.ng));
-    l.tree = blob.Take(sizeof(DevTreeNode) * f.tree.size());
-    l.m_cmap = blob.Take(f.mcode.ctx_map.size());
-    l.m_cfg = blob.Take(4 * f.mcode.cfg.size());
-    l.m_alias = blob.Take(8 * f.mcode.alias.size());
-    if (plan.global_direct && !f.mcode.use_prefix && !f.mcode.lz77 && f.mcode.num_hist <= 8) l.m_direct = blob.Take((size_t)f.mcode.num_hist << 14) + 1;
-    auto pfx_layout = [&](const HostCode& hc, size_t* o) {
-      if (!hc.use_prefix) return;
-      size_t total = 0;
-      for (auto& pc : hc.prefix) total += pc.sorted.size();
-      o[0] = blob.Take(2 * 16 * hc.prefix.size()); o[1] = blob.Take(4 * hc.prefix.size()); o[2] = blob.Take(2 * std::max<size_t>(1, total));
-    };
-    pfx_layout(f.mcode, l.m_pfx);
-    if (f.encoding == 1) {
-      // Modular (lossless) frame: whole-image int32 channel planes, no VarDCT workspace
-      const bool resident_m = dev_data && dev_data[i] && f.cs_contiguous;
-      l.cs = resident_m ? 0 : take_cs(i);
-      l.z_status = z_status_base + (size_t)i * 64;
-      for (auto& pl : f.mod_planes) l.mod_planes.push_back(ws.Take(4 * (size_t)std::max(1, pl.w) * std::max(1, pl.h)));
-      const size_t nsec = 1 + (size_t)f.nlf + f.ng;
-      l.mod_chan = blob.Take(sizeof(ModChanDev) * f.mod_coded.size());
-      l.mod_desc = ws.Take(nsec * f.mod_coded.size() * sizeof(ChanDesc));
-      if (f.tree_uses_wp) l.wp_grp = ws.Take(nsec * 10 * (f.group_dim + 2) * 4);
-      if (f.mcode.lz77) l.lz_mod = ws.Take(nsec * ((size_t)4 << 20)) + 1;
-      if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * (f.layer_f32 ? 4 : OutBytesPerSample(f)));
-      // reduced-size decode: the full-size output samples go to scratch, box_reduce_kernel averages them into the caller's buffer
-      if (ds) l.ds_full = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));
-      continue;
-    }
-    l.a_cmap = blob.Take(f.acode.ctx_map.size());
-    l.a_cfg = blob.Take(4 * f.acode.cfg.size());
-    l.a_alias = blob.Take(8 * f.acode.alias.size());
-    pfx_layout(f.acode, l.a_pfx);
-    if (f.mcode.lz77) { l.lz_lf = ws.Take((size_t)f.nlf * ((size_t)4 << 20)) + 1; l.lz_grp = ws.Take((size_t)f.ng * ((size_t)4 << 16)) + 1; }
-    if (f.acode.lz77) l.lz_hf = ws.Take((size_t)f.ng * ((size_t)4 << 18)) + 1;
-    for (int o = 0; o < kNumOrders; o++)
-      for (int c = 0; c < 3; c++) l.order[o][c] = f.custom_order[o][c].empty() ? 0 : blob.Take(2 * f.custom_order[o][c].size());
-    for (int q = 0; q < kNumQuantTables; q++) {
-      const int o = OrderBucketOfQuantTable(q);
-      const bool own_dq = !f.dq_default && f.custom_dq[q].size() == 3 * (size_t)dq_n[q];
-      if (own_dq) l.dq[q] = blob.Take(4 * 3 * (size_t)dq_n[q], 256) + 1;
-      if (own_dq || !f.custom_order[o][0].empty() || !f.custom_order[o][1].empty() || !f.custom_order[o][2].empty()) l.scan[q] = blob.Take(8 * 3 * (size_t)dq_n[q], 256) + 1;
-    }
-    const bool resident = dev_data && dev_data[i] && f.cs_contiguous;
-    l.cs = resident ? 0 : take_cs(i);
-    if (PlanColor(f).transfer == 5) l.trc_lut = blob.Take(4 * 3 * 4096, 256) + 1;
-    l.z_cellinfo = ws_zero.Take(4 * cells);
-    l.z_status = z_status_base + (size_t)i * 64;
-    {
-      // entry lists of the decoded group rows only (a band decode touches a band's worth), block index for the whole cell grid
-      const int g0 = plan.frames[i].dec_gy0, g1 = plan.frames[i].dec_gy1;
-      const bool hf = plan.frames[i].hf;
-      l.centries = ws.Take(hf ? (size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4 : 0);
-      l.cblk = ws.Take(hf ? 3 * cells * sizeof(U32x2) : 0);
-      for (auto& ep : f.extra_passes) {
-        PassLayout pl;
-        pl.a_cmap = blob.Take(ep.acode.ctx_map.size());
-        pl.a_cfg = blob.Take(4 * ep.acode.cfg.size());
-        pl.a_alias = blob.Take(8 * ep.acode.alias.size());
-        pfx_layout(ep.acode, pl.a_pfx);
-        if (ep.acode.lz77) pl.lz_hf = ws.Take((size_t)f.ng * ((size_t)4 << 18)) + 1;
-        for (int q = 0; q < kNumQuantTables; q++) {
-          const int o = OrderBucketOfQuantTable(q);
-          if (l.dq[q] || !ep.custom_order[o][0].empty() || !ep.custom_order[o][1].empty() || !ep.custom_order[o][2].empty()) pl.scan[q] = blob.Take(8 * 3 * (size_t)dq_n[q], 256) + 1;
-        }
-        pl.centries = ws.Take(hf ? (size_t)std::max(1, g1 - g0) * f.xg * kGroupEntriesCap * 4 : 0);
-        pl.cblk = ws.Take(hf ? 3 * cells * sizeof(U32x2) : 0);
-        pl.bitpos = ws.Take((size_t)f.ng * 8);
-        pl.hf_order = blob.Take(4 * (size_t)std::max<uint32_t>(1, f.ng));
-        l.extra.push_back(pl);
-      }
-    }
-    for (int c = 0; c < 3; c++) { l.lf[c] = ws.Take(4 * cells); l.lf_tmp[c] = ws.Take(4 * cells); l.lfq[c] = ws.Take(4 * cells); }
-    l.lf_extra = ws.Take(f.nlf);
-    l.rawq = ws.Take(2 * cells);
-    l.sharp = ws.Take(cells);
-    l.ytox = ws.Take(tiles);
-    l.ytob = ws.Take(tiles);
-    l.binfo = ws.Take((size_t)f.nlf * kBinfoInts * 4);
-    l.lf_desc = ws.Take((size_t)f.nlf * 8 * sizeof(ChanDesc));
-    l.lf_count = ws.Take((size_t)f.nlf * 4);
-    l.alpha_desc = ws.Take((size_t)f.ng * sizeof(ChanDesc));
-    l.blk_list = ws.Take((size_t)f.ng * 1024 * 4);
-    l.blk_count = ws.Take((size_t)f.ng * 4);
-    l.bitpos = ws.Take((size_t)f.ng * 8);
-    l.tile_list = ws.Take(tiles * 4);
-    l.alpha32 = ws.Take(4 * (size_t)f.xsize * f.ysize);
-    if (!ds) chunk_pix = std::max(chunk_pix, pix);   // (reduced size: no reconstruction, no filters - no pixel planes)
-    l.inv_sigma = ws.Take(4 * cells);
-    l.alpha = ws.Take((size_t)f.xsize * f.ysize * OutBytesPerSample(f));
-    if (ds && f.alpha_index >= 0) l.ds_alpha = ws.Take(cells * OutBytesPerSample(f));
-    if (f.is_layer) l.layer_px = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));   // (never f32: checked on the host)
-    l.lf_end = ws.Take(8);
-    if (f.tree_uses_wp) { l.wp_lf = ws.Take((size_t)f.nlf * kWpLfInts * 4); l.wp_grp = ws.Take((size_t)f.ng * 10 * (kGroupDim + 2) * 4); }
+  // ---- 3. layout of blob and workspace (batch_layout.h): one pass measures, the same code then places
+  const PatchTables patches = comps.empty() ? PatchTables() : BuildPatchTables(frames, parse_status, comps);
+  BatchInput in;
+  in.frames = &frames; in.parse_status = &parse_status; in.plan = &plan;
+  in.dev_data = dev_data; in.dev_out = dev_out;
+  in.comps = &comps; in.patches = &patches; in.file_of = &S.file_of; in.files = &S.files; in.nfiles = S.nfiles;
+  in.d_natural = d_natural; in.d_scan = d_scan; in.d_dq = d_dq; in.dq_n = dq_n;
+  in.ds = ds; in.debug_taps = debug_taps; in.no_stream_pairs = no_stream_pairs; in.pixel_chunk_cap = kPixelChunk;
+  BatchRegions measured;
+  {
+    BatchOutput unplaced;
+    BuildBatch(in, measured, unplaced);
   }
-  // The float planes between reconstruction and the loop filters (24 B/px) are only alive while a frame is in the pixel stages:
-  // frames go through those stages in chunks that share kPixelChunk sets of planes, so the batch size is bounded by the
-  // entropy-stage state (12 B/px of coefficients), not by 36 B/px.
-  const int pixel_chunk = debug_taps ? std::max(1, n) : std::min(std::max(1, n), kPixelChunk);
-  // (a third set: the loop-filter ping-pong planes, which double as the dense coefficient planes of the generic path)
-  std::vector<size_t> chunk_tmp((size_t)pixel_chunk * 3), chunk_xyb((size_t)pixel_chunk * 3), chunk_coef((size_t)pixel_chunk * 3);
-  if (chunk_pix)
-    for (int k = 0; k < pixel_chunk * 3; k++) { chunk_tmp[k] = ws.Take(4 * chunk_pix); chunk_xyb[k] = ws.Take(4 * chunk_pix); chunk_coef[k] = ws.Take(4 * chunk_pix); }
-  // Frames with synthetic noise: three more planes per chunk slot for the convolved noise the output phase adds (12 B/px, only when
-  // a frame of the batch has noise).  The random planes they are made from need none: they live in the tmp planes.
-  size_t noise_pix = 0;
-  for (int i = 0; i < n; i++)
-    if (parse_status[i] == DecoderStatus_Ok && frames[i].has_noise && !ds) noise_pix = std::max(noise_pix, (size_t)frames[i].xsize * frames[i].ysize);
-  std::vector<size_t> chunk_noise((size_t)pixel_chunk * 3);
-  if (noise_pix)
-    for (int k = 0; k < pixel_chunk * 3; k++) chunk_noise[k] = ws.Take(4 * noise_pix);
-  // The reference's decoder library hands out the image as displayed (orientation applied; it is only kept when the caller asks,
-  // which Decoder/DecoderContext.cpp never does): such frames are decoded into a scratch buffer and re-laid out at the end.
-  for (int i = 0; i < n; i++) {
-    if (parse_status[i] != DecoderStatus_Ok || frames[i].orientation == 1) continue;
-    const ParsedFrame& f = frames[i];
-    if (ds) continue;   // lf_output_kernel / box_reduce_kernel store at the oriented position
-    L[i].orient_tmp = ws.Take((size_t)f.xsize * f.ysize * (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * OutBytesPerSample(f));
-  }
-  // the plan's task tables
-  auto take_tasks = [&](const std::vector<SectionTask>& t) { return blob.Take(sizeof(SectionTask) * std::max<size_t>(1, t.size())); };
-  const size_t off_lf_tasks = take_tasks(plan.lf_finish_tasks);
-  const size_t off_pass_tasks = take_tasks(plan.pass_tasks);
-  const size_t off_lf_ans_tasks = take_tasks(plan.lf_ans_tasks);
-  const size_t off_mod_tasks = take_tasks(plan.mod_tasks);
-  const size_t off_alpha_tasks = take_tasks(plan.alpha_tasks);
-  size_t off_comp_imgs = 0, off_comp_frames = 0;
-  if (!comps.empty()) {
-    off_comp_imgs = blob.Take(sizeof(ComposeImage) * comps.size());
-    off_comp_frames = blob.Take(sizeof(ComposeFrame) * (size_t)n);
-  }
-  // patches: every patched frame of the batch, its positions listed per 64x64 tile in dictionary order (patch_kernel); the device
-  // pointers (frame and atlas scratch) are filled in with the image records below
-  struct HostPatchRef { int atlas; uint32_t x0, y0; };
-  std::vector<int> patch_image;            // batch image of each PatchFrame
-  std::vector<HostPatchRef> patch_src;     // per PatchRef
-  std::vector<PatchRef> patch_refs;
-  std::vector<PatchPos> patch_pos;
-  std::vector<PatchTile> patch_tiles;
-  std::vector<int32_t> patch_list;
-  for (const Composite& c : comps)
-    for (int j = 0; j < c.count; j++) {
-      const int i = c.first + j;
-      const ParsedFrame& f = frames[i];
-      if (parse_status[i] != DecoderStatus_Ok || f.patch_pos.empty()) continue;
-      const int pf = (int)patch_image.size(), ref0 = (int)patch_refs.size(), pos0 = (int)patch_pos.size();
-      patch_image.push_back(i);
-      for (auto& rr : f.patch_refs) {
-        PatchRef r;
-        memset(&r, 0, sizeof(r));
-        r.w = (int32_t)rr.w; r.h = (int32_t)rr.h;
-        patch_refs.push_back(r);
-        patch_src.push_back(HostPatchRef{c.first + rr.frame, rr.x0, rr.y0});
-      }
-      const int tx = (int)((f.xsize + kPatchTile - 1) / kPatchTile), ty = (int)((f.ysize + kPatchTile - 1) / kPatchTile);
-      std::vector<std::vector<int32_t>> lists((size_t)tx * ty);
-      std::vector<PatchTile> box((size_t)tx * ty);
-      for (size_t k = 0; k < f.patch_pos.size(); k++) {
-        const ParsedFrame::PatchPlace& q = f.patch_pos[k];
-        PatchPos p;
-        memset(&p, 0, sizeof(p));
-        p.x = (int32_t)q.x; p.y = (int32_t)q.y; p.ref = ref0 + (int32_t)q.ref;
-        for (int g = 0; g < 2; g++) { p.mode[g] = q.mode[g]; p.clamp[g] = q.clamp[g]; }
-        patch_pos.push_back(p);
-        if (q.mode[0] == 0 && (f.alpha_index < 0 || q.mode[1] == 0)) continue;   // None everywhere: no pixel changes
-        const int x1 = p.x + (int)f.patch_refs[q.ref].w, y1 = p.y + (int)f.patch_refs[q.ref].h;
-        for (int b = p.y / kPatchTile; b * kPatchTile < y1; b++)
-          for (int a = p.x / kPatchTile; a * kPatchTile < x1; a++) {
-            const size_t t = (size_t)b * tx + a;
-            PatchTile& bx = box[t];
-            const int cx0 = std::max(p.x, a * kPatchTile), cy0 = std::max(p.y, b * kPatchTile);
-            const int cx1 = std::min(x1, (a + 1) * kPatchTile), cy1 = std::min(y1, (b + 1) * kPatchTile);
-            if (lists[t].empty()) { bx.x0 = cx0; bx.y0 = cy0; bx.x1 = cx1; bx.y1 = cy1; }
-            else { bx.x0 = std::min(bx.x0, cx0); bx.y0 = std::min(bx.y0, cy0); bx.x1 = std::max(bx.x1, cx1); bx.y1 = std::max(bx.y1, cy1); }
-            lists[t].push_back(pos0 + (int32_t)k);
-          }
-      }
-      for (size_t t = 0; t < lists.size(); t++) {
-        if (lists[t].empty()) continue;   // tiles without patches get no workgroup
-        PatchTile tl = box[t];
-        tl.frame = pf; tl.first = (int32_t)patch_list.size(); tl.count = (int32_t)lists[t].size(); tl.pad = 0;
-        patch_tiles.push_back(tl);
-        patch_list.insert(patch_list.end(), lists[t].begin(), lists[t].end());
-      }
-    }
-  size_t off_patch_frames = 0, off_patch_refs = 0, off_patch_pos = 0, off_patch_tiles = 0, off_patch_list = 0;
-  if (!patch_tiles.empty()) {
-    off_patch_frames = blob.Take(sizeof(PatchFrame) * patch_image.size());
-    off_patch_refs = blob.Take(sizeof(PatchRef) * patch_refs.size());
-    off_patch_pos = blob.Take(sizeof(PatchPos) * patch_pos.size());
-    off_patch_tiles = blob.Take(sizeof(PatchTile) * patch_tiles.size());
-    off_patch_list = blob.Take(sizeof(int32_t) * patch_list.size());
-  }
-  const size_t zero_bytes = Align(ws_zero.off, 256);
-  EnsureBlob(blob.off);
-  EnsureWs(zero_bytes + ws.off);
+  const size_t blob_bytes = measured.blob.off, zero_bytes = measured.ZeroBytes();
+  EnsureBlob(blob_bytes);
+  EnsureWs(measured.WorkspaceBytes());
   if ((size_t)n * 16 > h_status_cap) {
     if (h_status) HIP_OK(hipHostFree(h_status));
     h_status = nullptr;
@@ -799,387 +534,16 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     h_status_cap = (size_t)n * 16;
   }
   // ---- 4. fill the pinned blob
-  memset(h_blob, 0, blob.off);
-  imgs.assign(n + n_extra, DevImage());
-  for (auto& im : imgs) memset(&im, 0, sizeof(DevImage));
-  status_off.assign(n, 0);
-  bool any_alpha = false, any_unfiltered = false, any_noise = false, any_vardct = false;
-  int stage_mask = 0;   // LDS-tiled loop-filter stage kernels some frame of the batch needs (bit s: filter_tile_kernel<s>)
-  int any_fused = 0, any_fused2 = 0;   // 1: fused frames (with a second iteration) of the two-pixels-per-lane kernels, 2: others
-  int max_w = 1, max_h = 1, max_tiles = 1;
-  auto tiles_of = [](const ParsedFrame& f) { return (size_t)((f.w8 + 7) / 8) * ((f.h8 + 7) / 8); };
-  size_t max_cells = 1, max_padded = 8, max_ds_cells = 1;   // max_ds_cells: reduced-size decode, over the frames of both kinds
-  int max_groups = 1;
-  size_t max_mod_pixels = 1;
-  struct ModLaunch { int kind; int32_t *a, *b, *c; int aw, ah, rw, rh, type; int32_t* out[4]; int nout; uint32_t* status; };
-  std::vector<ModLaunch> mod_ops;
-  uint8_t* wz = d_ws;
-  uint8_t* wr = d_ws + zero_bytes;
-  for (int i = 0; i < n; i++) {
-    memset(&imgs[i], 0, sizeof(DevImage));
-    if (parse_status[i] != DecoderStatus_Ok) continue;
-    const ParsedFrame& f = frames[i];
-    const PerImg& l = L[i];
-    DevImage& d = imgs[i];
-    d.w = f.xsize; d.h = f.ysize; d.w8 = f.w8; d.h8 = f.h8; d.wp = f.w8 * 8; d.hp = f.h8 * 8;
-    d.wt = (f.w8 + 7) / 8; d.ht = (f.h8 + 7) / 8;
-    d.xg = f.xg; d.yg = f.yg; d.ng = f.ng; d.xlf = f.xlf; d.ylf = f.ylf; d.nlf = f.nlf;
-    d.ncolor = f.ncolor; d.has_alpha = f.alpha_index >= 0; d.nch_out = d.ncolor + d.has_alpha;
-    d.sample_bits = (int32_t)f.bits; d.sample_exp = (int32_t)f.exp_bits;
-    d.alpha_bits = d.has_alpha ? (int32_t)f.ec[f.alpha_index].bits : 8; d.alpha_exp = d.has_alpha ? (int32_t)f.ec[f.alpha_index].exp_bits : 0;
-    d.out_bits = 8 * (int32_t)OutBytesPerSample(f); d.out_float = f.exp_bits ? 1 : 0;
-    d.unpremultiply = (d.has_alpha && f.ec[f.alpha_index].alpha_associated) ? 1 : 0;
-    d.alpha_unit = d.alpha_exp ? 1.0f : 1.0f / (float)((1u << d.alpha_bits) - 1);
-    const FramePlan& fp = plan.frames[i];
-    d.dec_gy0 = fp.dec_gy0; d.dec_gy1 = fp.dec_gy1; d.band_y0 = fp.band_y0; d.band_y1 = fp.band_y1;
-    const ColorPlan color = PlanColor(f);
-    d.to_srgb = color.transfer;   // 0 linear, 1 sRGB, 2 BT.709, 3 PQ, 5 tables
-    if (color.transfer == 5 && l.trc_lut) {
-      memcpy(h_blob + l.trc_lut - 1, color.trc_lut.data(), 4 * 3 * 4096);
-      d.trc_lut = (const float*)(d_blob + l.trc_lut - 1);
-    }
-    d.pq_scale = f.intensity_target * 1e-4f;
-    auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(h_blob + off, src, bytes); };
-    put(l.sec_off, f.sec_off.data(), 8 * f.sec_off.size());
-    put(l.sec_size, f.sec_size.data(), 4 * f.sec_size.size());
-    put(l.tree, f.tree.data(), sizeof(DevTreeNode) * f.tree.size());
-    auto code = [&](const HostCode& hc, size_t cm, size_t cf, size_t al, DevCode& dc, const size_t* pfx = nullptr) {
-      put(cm, hc.ctx_map.data(), hc.ctx_map.size());
-      std::vector<uint32_t> cfgp(hc.cfg.size());
-      for (size_t k = 0; k < hc.cfg.size(); k++) {
-        cfgp[k] = hc.cfg[k].split | hc.cfg[k].msb << 4 | hc.cfg[k].lsb << 8;
-        if (hc.use_prefix) {   // one-symbol prefix codes read no bits
-          if (hc.prefix[k].single >= 0) cfgp[k] |= 1u << 12 | (uint32_t)hc.prefix[k].single << 16;
-          continue;
-        }
-        // single-symbol clusters: decoding never changes the ANS state nor reads bits (alias special form)
-        const uint64_t e0 = hc.alias[k << hc.log_alpha];
-        const uint32_t x0 = (uint32_t)e0, y0 = (uint32_t)(e0 >> 32);
-        if ((x0 >> 16) == 0 && (y0 >> 16) == 4096) cfgp[k] |= 1u << 12 | ((x0 >> 8) & 0xFF) << 16;
-      }
-      dc.slow = (hc.use_prefix ? 1u : 0u) | (hc.lz77 ? 2u : 0u);
-      if (hc.use_prefix && pfx) {
-        std::vector<uint16_t> counts(16 * hc.prefix.size(), 0), sorted;
-        std::vector<uint32_t> offs(hc.prefix.size(), 0);
-        for (size_t k = 0; k < hc.prefix.size(); k++) {
-          memcpy(&counts[16 * k], hc.prefix[k].count, 32);
-          offs[k] = (uint32_t)sorted.size();
-          sorted.insert(sorted.end(), hc.prefix[k].sorted.begin(), hc.prefix[k].sorted.end());
-        }
-        put(pfx[0], counts.data(), 2 * counts.size()); put(pfx[1], offs.data(), 4 * offs.size()); put(pfx[2], sorted.data(), 2 * sorted.size());
-        dc.pfx_count = (const uint16_t*)(d_blob + pfx[0]); dc.pfx_off = (const uint32_t*)(d_blob + pfx[1]); dc.pfx_sorted = (const uint16_t*)(d_blob + pfx[2]);
-      }
-      if (hc.lz77) {
-        dc.lz_min_symbol = hc.lz_min_symbol; dc.lz_min_length = hc.lz_min_length;
-        dc.lz_len_cfg = hc.lz_len.split | hc.lz_len.msb << 4 | hc.lz_len.lsb << 8;
-        dc.lz_dist_cluster = hc.ctx_map.back();
-      }
-      put(cf, cfgp.data(), 4 * cfgp.size());
-      put(al, hc.alias.data(), 8 * hc.alias.size());
-      dc.ctx_map = d_blob + cm;
-      dc.cfg = (const uint32_t*)(d_blob + cf);
-      dc.alias = (const uint64_t*)(d_blob + al);
-      dc.num_ctx = (uint32_t)hc.ctx_map.size();
-      dc.num_clusters = hc.num_hist;
-      dc.log_alpha = hc.log_alpha;
-      dc.direct = nullptr;
-    };
-    code(f.mcode, l.m_cmap, l.m_cfg, l.m_alias, d.mcode, l.m_pfx);
-    if (l.m_direct) {   // the alias tables spelled out per state residue
-      uint32_t* dt = (uint32_t*)(h_blob + l.m_direct - 1);
-      const uint32_t la = f.mcode.log_alpha, le = 12 - la;
-      for (uint32_t r = 0; r < (f.mcode.num_hist << 12); r++) {
-        const uint32_t cl = r >> 12, res = r & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-        const uint64_t e = f.mcode.alias[(cl << la) + i];
-        const uint32_t x = (uint32_t)e, y = (uint32_t)(e >> 32);
-        const bool g = pos >= (x & 0xFF);
-        const uint32_t sym = g ? ((x >> 8) & 0xFF) : i, o = g ? (y & 0xFFFF) + pos : pos, freq = g ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-        dt[r] = ((freq - 1) & 0xFFF) | ((o & 0xFFF) << 12) | (sym << 24);
-      }
-      d.mcode.direct = (const uint32_t*)(d_blob + l.m_direct - 1);
-    }
-    d.sec_off = (const uint64_t*)(d_blob + l.sec_off);
-    d.sec_size = (const uint32_t*)(d_blob + l.sec_size);
-    d.tree = (const DevTreeNode*)(d_blob + l.tree);
-    d.tree_size = (int32_t)f.tree.size();
-    const bool resident = dev_data && dev_data[i] && f.cs_contiguous;
-    if (resident) d.cs = dev_data[i] + f.cs_file_offset;
-    else {
-      // the frames of a layered file share one upload of its codestream
-      const int file = S.file_of.empty() ? i : S.file_of[i];
-      if (!f.is_layer || !cs_put[file]) put(l.cs, f.cs, f.cs_size);
-      if (f.is_layer) cs_put[file] = 1;
-      d.cs = d_blob + l.cs;
-    }
-    d.cs_size = f.cs_size;
-    if (f.encoding == 1) {
-      d.is_modular = 1;
-      d.w8 = d.h8 = d.wt = d.ht = d.wp = d.hp = 0;   // nothing of the VarDCT pipeline runs for this image
-      d.cmyk = f.black_index >= 0 ? 1 : 0;
-      d.black_bits = d.cmyk ? (int32_t)f.ec[f.black_index].bits : 8;
-      d.nch_out = d.ncolor + d.cmyk + d.has_alpha;
-      d.mod_nch = d.nch_out;
-      // stream order: colour channels, then the extra channels as listed; output order: colour, black, alpha
-      for (int c = 0; c < d.ncolor; c++) d.mod_out_pos[c] = c;
-      if (d.cmyk) d.mod_out_pos[d.ncolor + f.black_index] = d.ncolor;
-      if (d.has_alpha) d.mod_out_pos[d.ncolor + f.alpha_index] = d.nch_out - 1;
-      d.group_dim = (int32_t)f.group_dim;
-      d.single = f.single ? 1 : 0;
-      d.mod_data_bits = f.mod_data_bits;
-      // without Squeeze (at most four colour transforms) the RCTs are undone inside modular_out_kernel; otherwise every inverse
-      // operation is its own launch (below) and the output kernel only clamps and interleaves
-      const bool inline_rct = !f.mod_has_squeeze && !f.mod_has_palette && f.mod_transforms.size() <= 4;
-      d.mod_ntr = inline_rct ? (int32_t)f.mod_transforms.size() : 0;
-      for (int t = 0; t < d.mod_ntr; t++) { d.mod_tr[t][0] = (int32_t)f.mod_transforms[t].begin_c; d.mod_tr[t][1] = (int32_t)f.mod_transforms[t].rct_type; }
-      for (int c = 0; c < d.mod_nch; c++) d.mod_plane[c] = (int32_t*)(wr + l.mod_planes[c]);
-      {
-        std::vector<ModChanDev> table;
-        for (auto& ch : f.mod_coded) table.push_back(ModChanDev{ch.w, ch.h, ch.hshift, ch.vshift, (int32_t*)(wr + l.mod_planes[ch.plane])});
-        put(l.mod_chan, table.data(), sizeof(ModChanDev) * table.size());
-      }
-      d.mod_chan = (const ModChanDev*)(d_blob + l.mod_chan);
-      d.mod_ncoded = (int32_t)f.mod_coded.size();
-      d.mod_first_group = (int32_t)f.mod_first_group_channel;
-      d.mod_desc = (ChanDesc*)(wr + l.mod_desc);
-      if (f.tree_uses_wp) { d.wp_grp = (int32_t*)(wr + l.wp_grp); d.wp_grp_ints = 10 * ((int64_t)f.group_dim + 2); }
-      if (l.lz_mod) d.lz_mod = (uint32_t*)(wr + l.lz_mod - 1);
-      if (!inline_rct)
-        for (auto& op : f.mod_ops) {
-          const ParsedFrame::ModPlane &pa = f.mod_planes[op.a], &pb = f.mod_planes[op.b];
-          ModLaunch ml{op.kind, (int32_t*)(wr + l.mod_planes[op.a]), (int32_t*)(wr + l.mod_planes[op.b]),
-                       (int32_t*)(wr + l.mod_planes[op.c]), pa.w, pa.h, pb.w, pb.h, op.type, {nullptr, nullptr, nullptr, nullptr}, op.nout, (uint32_t*)(wz + l.z_status)};
-          for (int k = 0; k < op.nout && k < 4; k++) ml.out[k] = (int32_t*)(wr + l.mod_planes[op.out[k]]);
-          mod_ops.push_back(ml);
-        }
-      d.status = (uint32_t*)(wz + l.z_status);
-      status_off[i] = l.z_status;
-      d.out = f.orientation == 1 ? dev_out[i] : wr + l.orient_tmp;
-      if (f.is_layer) d.out = wr + l.layer_px;
-      if (ds) {
-        d.ds = 8; d.ds_w = ((int32_t)f.xsize + 7) / 8; d.ds_h = ((int32_t)f.ysize + 7) / 8; d.ds_orient = (int32_t)f.orientation;
-        d.out = wr + l.ds_full; d.ds_out = dev_out[i];
-        max_ds_cells = std::max(max_ds_cells, (size_t)d.ds_w * d.ds_h);
-      }
-      if (f.layer_f32) {   // unclamped f32 samples in the image's colour space; un-premultiply waits for the compositor
-        d.out_bits = 32; d.out_float = 1; d.unpremultiply = 0;
-      }
-      max_mod_pixels = std::max(max_mod_pixels, (size_t)f.xsize * f.ysize);
-      continue;
-    }
-    code(f.acode, l.a_cmap, l.a_cfg, l.a_alias, d.acode, l.a_pfx);
-    if (l.lz_lf) d.lz_lf = (uint32_t*)(wr + l.lz_lf - 1);
-    if (l.lz_grp) d.lz_grp = (uint32_t*)(wr + l.lz_grp - 1);
-    if (l.lz_hf) d.lz_hf = (uint32_t*)(wr + l.lz_hf - 1);
-    d.num_presets = f.num_presets;
-    d.num_block_ctx = f.num_block_ctx;
-    memcpy(d.block_ctx_map, f.block_ctx_map.data(), std::min(sizeof(d.block_ctx_map), f.block_ctx_map.size()));
-    d.n_qf = (int32_t)f.qf_thr.size();
-    d.num_lf_ctx = 1;
-    for (int j = 0; j < 3; j++) {
-      d.n_lf_thr[j] = (int32_t)std::min<size_t>(15, f.lf_thr[j].size());
-      for (int k = 0; k < d.n_lf_thr[j]; k++) d.lf_thr[j][k] = f.lf_thr[j][k];
-      d.num_lf_ctx *= d.n_lf_thr[j] + 1;
-    }
-    d.custom_orders = 0;
-    for (size_t k = 0; k < f.qf_thr.size() && k < 15; k++) d.qf_thr[k] = f.qf_thr[k];
-    for (int o = 0; o < kNumOrders; o++)
-      for (int c = 0; c < 3; c++) {
-        if (f.custom_order[o][c].empty()) d.order[o * 3 + c] = d_natural[o];
-        else { put(l.order[o][c], f.custom_order[o][c].data(), 2 * f.custom_order[o][c].size()); d.order[o * 3 + c] = (const uint16_t*)(d_blob + l.order[o][c]); d.custom_orders = 1; }
-      }
-    d.inv_global_scale = 65536.0f / f.global_scale;
-    d.quant_scale = f.global_scale / 65536.0f;
-    for (int c = 0; c < 3; c++) d.mul_lf[c] = f.m_lf[c] * (d.inv_global_scale / f.quant_lf);
-    d.inv_color_factor = 1.0f / f.color_factor;
-    d.lf_cfl_x = f.base_x + f.ytox_lf * d.inv_color_factor;
-    d.lf_cfl_b = f.base_b + f.ytob_lf * d.inv_color_factor;
-    d.base_x = f.base_x; d.base_b = f.base_b;
-    d.x_dm = std::pow(0.8f, (float)f.x_qm_scale - 2.0f);
-    d.b_dm = std::pow(0.8f, (float)f.b_qm_scale - 2.0f);
-    memcpy(d.qbias, f.qbias, sizeof(d.qbias));
-    for (int q = 0; q < kNumQuantTables; q++) {
-      d.dq[q] = d_dq[q]; d.dq_n[q] = dq_n[q]; d.scan[q] = d_scan[q];
-      if (l.dq[q]) { put(l.dq[q] - 1, f.custom_dq[q].data(), 4 * f.custom_dq[q].size()); d.dq[q] = (const float*)(d_blob + l.dq[q] - 1); }
-      if (l.scan[q]) {
-        std::vector<U32x2> sl;
-        BuildScanList(q, f.custom_order, sl, l.dq[q] ? &f.custom_dq[q] : nullptr);
-        put(l.scan[q] - 1, sl.data(), sl.size() * sizeof(U32x2));
-        d.scan[q] = (const U32x2*)(d_blob + l.scan[q] - 1);
-      }
-    }
-    d.gab = f.gab; d.epf_iters = f.epf_iters; d.skip_lf_smoothing = (f.flags & 128) ? 1 : 0;
-    for (int c = 0; c < 3; c++) {
-      float div = 1.0f + 4.0f * (f.gab_w1[c] + f.gab_w2[c]);
-      d.gab_w[c][0] = 1.0f / div; d.gab_w[c][1] = f.gab_w1[c] / div; d.gab_w[c][2] = f.gab_w2[c] / div;
-    }
-    memcpy(d.epf_sharp_lut, f.epf_sharp_lut, sizeof(d.epf_sharp_lut));
-    memcpy(d.epf_channel_scale, f.epf_channel_scale, sizeof(d.epf_channel_scale));
-    d.epf_quant_mul = f.epf_quant_mul; d.epf_pass0_sigma_scale = f.epf_pass0_sigma_scale;
-    d.epf_pass2_sigma_scale = f.epf_pass2_sigma_scale; d.epf_border_sad_mul = f.epf_border_sad_mul;
-    // linear RGB of the image's own primaries, relative to its intensity target: change of primaries folded into the inverse opsin matrix
-    for (int r = 0; r < 3; r++)
-      for (int k = 0; k < 3; k++) {
-        double a = 0;
-        for (int j = 0; j < 3; j++) a += (double)color.from_srgb[r * 3 + j] * (double)f.opsin_inv[j * 3 + k];
-        d.opsin_inv[r * 3 + k] = (float)a * (255.0f / f.intensity_target);
-      }
-    for (int k = 0; k < 3; k++) { d.opsin_bias[k] = f.opsin_bias[k]; d.opsin_bias_cbrt[k] = std::cbrt(f.opsin_bias[k]); }
-    // planes
-    d.cellinfo = (uint32_t*)(wz + l.z_cellinfo);
-    d.status = (uint32_t*)(wz + l.z_status);
-    status_off[i] = l.z_status;
-    for (int c = 0; c < 3; c++) {
-      d.lf[c] = (float*)(wr + l.lf[c]); d.lf_tmp[c] = (float*)(wr + l.lf_tmp[c]); d.lfq[c] = (int32_t*)(wr + l.lfq[c]);
-      d.lf_final[c] = d.skip_lf_smoothing ? d.lf[c] : d.lf_tmp[c];
-      if (ds) continue;   // no pixel planes: the image is lf_final
-      d.coef[c] = (int32_t*)(wr + chunk_coef[(size_t)(i % pixel_chunk) * 3 + c]);
-      d.tmp[c] = (float*)(wr + chunk_tmp[(size_t)(i % pixel_chunk) * 3 + c]); d.xyb[c] = (float*)(wr + chunk_xyb[(size_t)(i % pixel_chunk) * 3 + c]);
-      d.xyb2[c] = (float*)d.coef[c];   // the dense coefficient planes (generic path only) are dead once the frame is reconstructed
-    }
-    if (ds) {
-      d.ds = 8; d.ds_w = (int32_t)f.w8; d.ds_h = (int32_t)f.h8; d.ds_orient = (int32_t)f.orientation;
-      if (l.ds_alpha) d.ds_alpha = wr + l.ds_alpha;
-      max_ds_cells = std::max(max_ds_cells, (size_t)f.w8 * f.h8);
-    }
-    if (f.has_noise && !ds) {   // (a cell is coarser than the noise's 5x5 support: a reduced-size decode adds none)
-      // the generator fills the group rows the band's 5x5 support reaches: the band's rows and one more each side, like the decode
-      d.has_noise = 1; d.noise_gy0 = d.dec_gy0; d.noise_gy1 = d.dec_gy1;
-      d.noise_seed[0] = f.noise_seed[0]; d.noise_seed[1] = f.noise_seed[1];
-      memcpy(d.noise_lut, f.noise_lut, sizeof(d.noise_lut));
-      for (int c = 0; c < 3; c++) { d.noise_rnd[c] = d.tmp[c]; d.noise[c] = (float*)(wr + chunk_noise[(size_t)(i % pixel_chunk) * 3 + c]); }
-      any_noise = true;
-    }
-    d.lf_extra = wr + l.lf_extra;
-    d.rawq = (uint16_t*)(wr + l.rawq); d.sharp = wr + l.sharp;
-    d.ytox = (int8_t*)(wr + l.ytox); d.ytob = (int8_t*)(wr + l.ytob);
-    d.binfo = (int32_t*)(wr + l.binfo);
-    d.lf_desc = (ChanDesc*)(wr + l.lf_desc); d.lf_count = (uint32_t*)(wr + l.lf_count); d.alpha_desc = (ChanDesc*)(wr + l.alpha_desc);
-    d.blk_list = (uint32_t*)(wr + l.blk_list); d.blk_count = (uint32_t*)(wr + l.blk_count);
-    d.grp_bitpos = (uint64_t*)(wr + l.bitpos);
-    d.tile_list = (uint32_t*)(wr + l.tile_list);
-    d.alpha32 = (int32_t*)(wr + l.alpha32);
-    const bool hf = fp.hf;   // does hf_decode_kernel run for this frame?  (reduced size: only to find the alpha stream)
-    if (hf) { d.centries = (uint32_t*)(wr + l.centries); d.cblk = (U32x2*)(wr + l.cblk); }
-    d.centries_g0 = d.dec_gy0 * (int32_t)f.xg;
-    d.inv_sigma = (float*)(wr + l.inv_sigma);
-    d.alpha = wr + l.alpha;
-    d.lf_end_bits = (uint64_t*)(wr + l.lf_end);
-    // a frame of one group has its alpha channel in LfGlobal (channels no larger than a group are coded globally)
-    d.alpha_in_global = (d.has_alpha && f.ng == 1) ? 1 : 0;
-    d.lf_start_bits = f.after_lf_global_bits;
-    if (f.single) {
-      d.single = 1;
-      d.hf_start_bits = f.hf_start_bits;
-    }
-    if (f.tree_uses_wp) { d.wp_lf = (int32_t*)(wr + l.wp_lf); d.wp_grp = (int32_t*)(wr + l.wp_grp); d.wp_grp_ints = 10 * (kGroupDim + 2); }
-    d.out = f.orientation == 1 ? dev_out[i] : wr + l.orient_tmp;
-    if (f.is_layer) d.out = wr + l.layer_px;   // a frame of a layered image whose frames all replace: output-type samples
-    if (ds) d.out = d.ds_out = dev_out[i];
-    // Loop-filter routing.  Frames with EPF iterations run iteration 1 (+ Gaborish when no iteration 0 has to come between them) and
-    // iteration 2 in the streaming kernels: fused_gab_epf1 = 1: one kernel -> output; 2: two kernels, f32 rows (stream_mid) between
-    // them.  Three iterations (distance >= 4): Gaborish and iteration 0 first, as LDS-tiled stage kernels, then the two streaming
-    // kernels without Gaborish (stream_no_gab).  Stage kernels ping-pong between xyb and xyb2 (the dead dense-coefficient planes).
-    float** cur = d.xyb;
-    float** other = d.xyb2;
-    d.fused_gab_epf1 = (!debug_taps && f.epf_iters >= 1) ? (f.epf_iters == 1 ? 1 : 2) : 0;
-    d.stream_no_gab = (d.fused_gab_epf1 && (!f.gab || f.epf_iters == 3)) ? 1 : 0;
-    d.stage_on[0] = (f.gab && (!d.fused_gab_epf1 || f.epf_iters == 3)) ? 1 : 0;
-    d.stage_on[1] = f.epf_iters == 3;
-    d.stage_on[2] = f.epf_iters >= 1 && !d.fused_gab_epf1;
-    d.stage_on[3] = f.epf_iters >= 2 && !d.fused_gab_epf1;
-    d.stage_on[4] = 1;
-    for (int s = 0; s < 5; s++) {
-      if (s == 2) for (int c = 0; c < 3; c++) { d.stream_in[c] = cur[c]; d.stream_mid[c] = other[c]; }
-      for (int c = 0; c < 3; c++) { d.stage_in[s][c] = cur[c]; d.stage_out[s][c] = other[c]; }
-      if (s < 4 && d.stage_on[s]) std::swap(cur, other);
-    }
-    d.final_stage = 4;
-    for (int s = 0; s < 4; s++) if (d.stage_on[s]) d.final_stage = s;
-    if (debug_taps) d.final_stage = 4;   // keep the filtered float planes for the stage taps; out_only_kernel converts
-    // the layouts the two-pixels-per-lane kernels handle: even width; 8-bit RGBA / RGB / gray + alpha / gray output (bit 0: the Gaborish + first
-    // iteration kernel, which for a two-iteration frame writes f32 rows whatever the output; bit 1: the second iteration's kernel)
-    {
-      // (their buffer resources address 2 GB from a plane's base: larger planes take the general kernels)
-      const bool even = d.fused_gab_epf1 && (d.w & 1) == 0 && d.w >= 8 && !no_stream_pairs && (uint64_t)d.wp * (uint64_t)d.hp * 4u < (1ull << 31);
-      // 8-bit samples, sRGB or linear: RGBA, RGB, gray + alpha, gray (a frame's channel count is ncolor + has_alpha)
-      const bool rgba8 = d.out_bits == 8 && d.to_srgb <= 1 && !d.unpremultiply && (d.ncolor == 3 || d.ncolor == 1) &&
-                         d.nch_out == d.ncolor + (d.has_alpha ? 1 : 0) && !d.cmyk;
-      d.stream_pairs = (even && (d.fused_gab_epf1 == 2 || rgba8) ? 1 : 0) | (even && d.fused_gab_epf1 == 2 && rgba8 ? 2 : 0);
-      if (d.has_noise) {
-        // noise is added by the general output path: the kernel that writes the pixels is never a pair kernel.  Which conversion to
-        // 8 bits the same frame WITHOUT noise would get is kept, so that noise of strength zero changes no byte.
-        const int out_bit = d.fused_gab_epf1 == 2 ? 2 : 1;
-        d.noise_pairs_twin = (d.stream_pairs & out_bit) ? 1 : 0;
-        d.stream_pairs &= ~out_bit;
-      }
-    }
-    if (d.fused_gab_epf1) {
-      d.final_stage = 5;
-      any_fused |= (d.stream_pairs & 1) ? 1 : 2;
-      if (d.fused_gab_epf1 == 2) any_fused2 |= (d.stream_pairs & 2) ? 1 : 2;
-    }
-    any_unfiltered |= d.final_stage == 4;
-    max_w = std::max<int>(max_w, f.xsize); max_h = std::max<int>(max_h, f.ysize);
-    max_tiles = std::max<int>(max_tiles, (int)tiles_of(f));
-    for (int st = 0; st < 4; st++) if (d.stage_on[st]) stage_mask |= 1 << st;
-    any_alpha |= d.has_alpha != 0;
-    any_vardct = true;
-    max_cells = std::max(max_cells, (size_t)f.w8 * f.h8);
-    max_padded = std::max(max_padded, (size_t)f.w8 * f.h8 * 64);
-    max_groups = std::max<int>(max_groups, (int)f.ng);
-    // progressive frames: one record per further pass, chained from this one
-    d.num_passes = (int32_t)f.num_passes;
-    d.pass_shift = (int32_t)f.pass_shift[0];
-    d.hf_sec_base = 2 + (int32_t)f.nlf;
-    d.alpha_sec_base = 2 + (int32_t)f.nlf + (int32_t)((f.num_passes - 1) * f.ng);   // the Modular streams of all shifts below 3 are in the last pass
-    d.alpha_bitpos = d.grp_bitpos;
-    d.next_pass = nullptr;
-    for (size_t p = 0; p < f.extra_passes.size(); p++) {
-      const ParsedFrame::PassCodes& ep = f.extra_passes[p];
-      const PassLayout& pl = l.extra[p];
-      DevImage& sh = imgs[(size_t)fp.first_extra + p];
-      sh = d;
-      memset(&sh.acode, 0, sizeof(sh.acode));
-      code(ep.acode, pl.a_cmap, pl.a_cfg, pl.a_alias, sh.acode, pl.a_pfx);
-      sh.lz_hf = pl.lz_hf ? (uint32_t*)(wr + pl.lz_hf - 1) : nullptr;
-      for (int q = 0; q < kNumQuantTables; q++) {
-        sh.scan[q] = d_scan[q];
-        if (pl.scan[q]) {
-          std::vector<U32x2> sl;
-          BuildScanList(q, ep.custom_order, sl, l.dq[q] ? &f.custom_dq[q] : nullptr);
-          put(pl.scan[q] - 1, sl.data(), sl.size() * sizeof(U32x2));
-          sh.scan[q] = (const U32x2*)(d_blob + pl.scan[q] - 1);
-        }
-      }
-      sh.centries = (uint32_t*)(wr + pl.centries);
-      sh.cblk = (U32x2*)(wr + pl.cblk);
-      sh.grp_bitpos = (uint64_t*)(wr + pl.bitpos);
-      sh.pass_shift = p + 1 < f.num_passes - 1 ? (int32_t)f.pass_shift[p + 1] : 0;
-      sh.hf_sec_base = 2 + (int32_t)f.nlf + (int32_t)((p + 1) * f.ng);
-      sh.next_pass = nullptr;
-      d.alpha_bitpos = sh.grp_bitpos;
-    }
-    {
-      const DevImage* d_recs = (const DevImage*)(d_blob + off_imgs);
-      for (size_t p = 0; p < f.extra_passes.size(); p++) {
-        DevImage& prev = p ? imgs[(size_t)fp.first_extra + p - 1] : d;
-        prev.next_pass = d_recs + fp.first_extra + p;
-        imgs[(size_t)fp.first_extra + p].alpha_bitpos = d.alpha_bitpos;
-      }
-    }
-  }
-  // the plan's tables; slot j of an (image, pass) decodes group hf_order[j]
-  for (const EntropyPlan::HfOrder& o : plan.hf_orders) {
-    const size_t order_off = o.pass ? L[o.image].extra[o.pass - 1].hf_order : L[o.image].hf_order;
-    if (!o.order.empty()) memcpy(h_blob + order_off, o.order.data(), 4 * o.order.size());
-    imgs[o.pass ? (size_t)plan.frames[o.image].first_extra + o.pass - 1 : (size_t)o.image].hf_order = (const uint32_t*)(d_blob + order_off);
-  }
-  auto put_tasks = [&](size_t off, const std::vector<SectionTask>& t) { if (!t.empty()) memcpy(h_blob + off, t.data(), sizeof(SectionTask) * t.size()); };
-  put_tasks(off_lf_tasks, plan.lf_finish_tasks);
-  put_tasks(off_pass_tasks, plan.pass_tasks);
-  put_tasks(off_lf_ans_tasks, plan.lf_ans_tasks);
-  put_tasks(off_mod_tasks, plan.mod_tasks);
-  put_tasks(off_alpha_tasks, plan.alpha_tasks);
+  memset(h_blob, 0, blob_bytes);
+  BatchRegions placed{Region(h_blob, d_blob, blob_bytes), Region(nullptr, d_ws, measured.zero.off), Region(nullptr, d_ws + zero_bytes, measured.ws.off),
+                      Region(nullptr, d_ws + measured.PixStart(), measured.pix.off)};
+  BatchOutput B;
+  BuildBatch(in, placed, B);
+  imgs.swap(B.imgs);
+  status_off.swap(B.status_off);
+  d_imgs = B.d_imgs;
+  const bool any_alpha = B.any_alpha, any_noise = B.any_noise;
+  const int pixel_chunk = B.pixel_chunk, max_groups = B.max_groups;
   const int nlf_t = (int)plan.lf_finish_tasks.size(), npass_t = (int)plan.pass_tasks.size(), nalpha_t = (int)plan.alpha_tasks.size();
   const int nlf_ans_t = (int)plan.lf_ans_tasks.size(), nmod_t = (int)plan.mod_tasks.size();
   if (Knob("JXLHIP_DEBUG_LDS")) {
@@ -1191,70 +555,6 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     fprintf(stderr, "[jxlhip] launch LDS: hf %zu B (lanes %zu), lf %zu B, alpha %zu B; hf workgroups %d x %d threads, stride %d; alpha workgroups %d; lf_ans workgroups %d\n",
             plan.hf.lds, plan.lds_hf_lanes, plan.lf.lds, plan.alpha.lds, npass_t, plan.hf_waves * 64, plan.lane_stride, nalpha_t, nlf_ans_t);
   }
-  int max_segments = 1;
-  if (!comps.empty()) {
-    // the compositor's tables: one record per layered image, one per frame (frame records indexed like the batch's images)
-    ComposeImage* cimgs = (ComposeImage*)(h_blob + off_comp_imgs);
-    ComposeFrame* cframes = (ComposeFrame*)(h_blob + off_comp_frames);
-    for (size_t k = 0; k < comps.size(); k++) {
-      const Composite& c = comps[k];
-      const ParsedFrame& top = S.files[k];
-      ComposeImage& ci = cimgs[k];
-      memset(&ci, 0, sizeof(ci));
-      ci.w = (int32_t)top.xsize; ci.h = (int32_t)top.ysize;
-      ci.has_alpha = top.alpha_index >= 0 ? 1 : 0;
-      ci.nch = top.ncolor + ci.has_alpha;
-      ci.premul = (ci.has_alpha && top.ec[top.alpha_index].alpha_associated) ? 1 : 0;
-      ci.orientation = (int32_t)top.orientation;
-      ci.out_bits = 8 * (int32_t)OutBytesPerSample(top); ci.out_float = top.exp_bits ? 1 : 0;
-      ci.first = c.first; ci.count = c.count;
-      ci.raw = top.layers->raw ? 1 : 0;
-      ci.out = c.out;
-      max_segments = std::max(max_segments, (int)top.ysize * (int)((top.xsize + 255) / 256));   // compose_kernel: 256-pixel row segments
-      for (int j = 0; j < c.count; j++) {
-        const ParsedFrame& f = frames[c.first + j];
-        ComposeFrame& cf = cframes[c.first + j];
-        memset(&cf, 0, sizeof(cf));
-        cf.px = (const float*)imgs[c.first + j].out;
-        cf.x0 = f.have_crop ? f.crop_x0 : 0; cf.y0 = f.have_crop ? f.crop_y0 : 0;
-        cf.w = (int32_t)f.xsize; cf.h = (int32_t)f.ysize;
-        const BlendInfo& bc = f.blend[0];
-        const BlendInfo& ba = ci.has_alpha ? f.blend[1 + top.alpha_index] : bc;
-        cf.mode[0] = (int32_t)bc.mode; cf.mode[1] = (int32_t)ba.mode;
-        cf.source[0] = (int32_t)bc.source; cf.source[1] = (int32_t)ba.source;
-        cf.clamp[0] = (int32_t)bc.clamp; cf.clamp[1] = (int32_t)ba.clamp;
-        cf.save = c.save[j];
-        // a reference-only frame is read by patches only: an empty crop and no save leave the canvas and the slots as they are
-        if (f.frame_type == 2) { cf.w = cf.h = 0; cf.save = -1; }
-      }
-    }
-  }
-  if (!patch_tiles.empty()) {
-    PatchFrame* pfr = (PatchFrame*)(h_blob + off_patch_frames);
-    for (size_t k = 0; k < patch_image.size(); k++) {
-      const ParsedFrame& f = frames[patch_image[k]];
-      PatchFrame& p = pfr[k];
-      memset(&p, 0, sizeof(p));
-      p.px = (float*)imgs[patch_image[k]].out;   // the frame's f32 layer scratch (layer_f32: every frame of an image with patches)
-      p.w = (int32_t)f.xsize; p.h = (int32_t)f.ysize;
-      p.has_alpha = f.alpha_index >= 0 ? 1 : 0;
-      p.nch = f.ncolor + p.has_alpha;
-      p.premul = (p.has_alpha && f.ec[f.alpha_index].alpha_associated) ? 1 : 0;
-    }
-    for (size_t k = 0; k < patch_refs.size(); k++) {
-      const HostPatchRef& s = patch_src[k];
-      const ParsedFrame& a = frames[s.atlas];
-      const size_t nch = a.ncolor + (a.alpha_index >= 0 ? 1 : 0);
-      patch_refs[k].px = (const float*)imgs[s.atlas].out + ((size_t)s.y0 * a.xsize + s.x0) * nch;
-      patch_refs[k].stride = (int32_t)a.xsize;
-    }
-    memcpy(h_blob + off_patch_refs, patch_refs.data(), sizeof(PatchRef) * patch_refs.size());
-    memcpy(h_blob + off_patch_pos, patch_pos.data(), sizeof(PatchPos) * patch_pos.size());
-    memcpy(h_blob + off_patch_tiles, patch_tiles.data(), sizeof(PatchTile) * patch_tiles.size());
-    memcpy(h_blob + off_patch_list, patch_list.data(), sizeof(int32_t) * patch_list.size());
-  }
-  memcpy(h_blob + off_imgs, imgs.data(), sizeof(DevImage) * imgs.size());
-  d_imgs = (DevImage*)(d_blob + off_imgs);
   // ---- 5. enqueue: LF chain on s_lf, everything that needs the block layout on the main stream
   stage_names.clear();
   S.stage_chain.clear();
@@ -1263,7 +563,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // with the same files resubmitted, a skipped stage's results of the previous batch in this workspace slot are still in place
   static const int skip_stages = Knob("JXLHIP_SKIP_STAGES") ? atoi(Knob("JXLHIP_SKIP_STAGES")) : 0;
   if (!(skip_stages & 1)) HIP_OK(hipMemsetAsync(d_ws, 0, zero_bytes, s_lf));
-  HIP_OK(hipMemcpyAsync(d_blob, h_blob, blob.off, hipMemcpyHostToDevice, s_lf));
+  HIP_OK(hipMemcpyAsync(d_blob, h_blob, blob_bytes, hipMemcpyHostToDevice, s_lf));
   Mark("upload+clear", s_lf, 0);
   // Synthetic noise depends on nothing but the uploaded descriptors: the first pixel chunk's planes are generated and convolved on the
   // main stream while the entropy chains run on theirs (a group's generator is a chain of 12 288 dependent steps, 1.25 ms for a 4K
@@ -1275,15 +575,15 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     HIP_OK(hipEventRecord(S.uploaded, s_lf));
     HIP_OK(hipStreamWaitEvent(stream, S.uploaded, 0));
     Mark("noise_start", stream, 3);
-    LaunchNoise(d_imgs, std::min(pixel_chunk, n), max_groups, max_w, max_h, stream);
+    LaunchNoise(d_imgs, std::min(pixel_chunk, n), max_groups, B.max_w, B.max_h, stream);
     Mark("noise", stream, 3);
   }
   if (!(skip_stages & 1)) {
-  LaunchLfAns(d_imgs, (const SectionTask*)(d_blob + off_lf_ans_tasks), nlf_ans_t, plan.lf_per_wave, plan.lf.Bytes(), plan.direct_lf, plan.lean_mod, s_lf);
+  LaunchLfAns(d_imgs, B.lf_ans_tasks, nlf_ans_t, plan.lf_per_wave, plan.lf.Bytes(), plan.direct_lf, plan.lean_mod, s_lf);
   Mark("lf_ans", s_lf, 0);
-  LaunchLfFinish(d_imgs, (const SectionTask*)(d_blob + off_lf_tasks), nlf_t, !no_lf_pipeline, s_lf);
+  LaunchLfFinish(d_imgs, B.lf_tasks, nlf_t, !no_lf_pipeline, s_lf);
   if (!ds || any_alpha) LaunchHfBlockList(d_imgs, n, max_groups, s_lf);   // (the varblock lists serve hf_decode_kernel alone)
-  LaunchLfPixelStages(d_imgs, n, max_cells, s_lf);
+  LaunchLfPixelStages(d_imgs, n, B.max_cells, s_lf);
   }
   Mark("lf_finish+pixels", s_lf, 0);
   // three chains, three streams: LF (batch k+2) | HF coefficients (batch k+1) | alpha + pixels (batch k)
@@ -1312,17 +612,17 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // Reduced-size decode: the HF tokens are read only to find what follows them in a pass-group section, i.e. for frames with alpha
   // (their pass tasks are the only ones listed); stages that do not run leave no entry in the stage times.
   if (!(skip_stages & 2) && (!ds || npass_t))
-  LaunchHfDecode(d_imgs, (const SectionTask*)(d_blob + off_pass_tasks), npass_t, plan.hf_waves * 64, plan.lane_stride, plan.hf.Bytes(), plan.lds_hf_lanes, s_hf);
+  LaunchHfDecode(d_imgs, B.pass_tasks, npass_t, plan.hf_waves * 64, plan.lane_stride, plan.hf.Bytes(), plan.lds_hf_lanes, s_hf);
   if (!ds || npass_t) Mark("hf_decode", s_hf, 1);
   // alpha follows the HF tokens in every pass-group section (its first bit is where the HF kernel stopped reading): same chain,
   // necessarily; the main stream carries nothing but the pixel stages
   if (any_alpha && !(skip_stages & 4))
-    LaunchAlphaAns(d_imgs, (const SectionTask*)(d_blob + off_alpha_tasks), nalpha_t, plan.alpha_stride, plan.alpha.Bytes(), plan.direct_alpha, plan.lean_mod,
+    LaunchAlphaAns(d_imgs, B.alpha_tasks, nalpha_t, plan.alpha_stride, plan.alpha.Bytes(), plan.direct_alpha, plan.lean_mod,
                    alpha_narrow, s_hf);
   if (!ds || any_alpha) Mark("alpha_ans", s_hf, 1);
   if (debug_taps && !ds) {   // the quantised coefficients as dense planes (every frame has its own planes in this mode)
     taps.assign(n, Tap());
-    LaunchExpandCoefficients(d_imgs, n, true, max_tiles, stream);
+    LaunchExpandCoefficients(d_imgs, n, true, B.max_tiles, stream);
     HIP_OK(hipStreamSynchronize(stream));
     CopyPlaneTap(0);
   }
@@ -1345,25 +645,25 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
   // experiment knob: the pixel stages behind the HF chain on ITS stream (no overlap between a batch's pixels and the next batch's HF decode)
   hipStream_t s_pix = pix_on_hf ? s_hf : stream;
-  if (ds && any_vardct) {
+  if (ds && B.any_vardct) {
     // the whole pixel stage of a reduced-size decode: no reconstruction, no noise, no filters, and every image in one launch
-    if (any_alpha) LaunchAlphaReduce(d_imgs, n, max_ds_cells, s_pix);
-    LaunchLfOutput(d_imgs, n, max_ds_cells, s_pix);
+    if (any_alpha) LaunchAlphaReduce(d_imgs, n, B.max_ds_cells, s_pix);
+    LaunchLfOutput(d_imgs, n, B.max_ds_cells, s_pix);
     Mark("lf_output", s_pix, 2);
   }
   for (int c0 = 0; c0 < (ds ? 0 : n); c0 += pixel_chunk) {
     const int cnt = std::min(pixel_chunk, n - c0);
     if (!(skip_stages & 8))
-    LaunchReconTiles(d_imgs + c0, cnt, max_tiles, d_basis_all, d_basis_small, d_llf_scale, d_basis_mfma, s_pix);
+    LaunchReconTiles(d_imgs + c0, cnt, B.max_tiles, d_basis_all, d_basis_small, d_llf_scale, d_basis_mfma, s_pix);
     Mark("reconstruct", s_pix, 2);   // exactly recon_tile_kernel; one mark per chunk, the per-stage totals add them up
-    LaunchExpandCoefficients(d_imgs + c0, cnt, false, max_tiles, s_pix);
+    LaunchExpandCoefficients(d_imgs + c0, cnt, false, B.max_tiles, s_pix);
     LaunchGenericReconstruct(d_imgs + c0, cnt, d_basis_all, d_basis_small, d_llf_scale, s_pix);
     Mark("reconstruct_generic", s_pix, 2);
     if (debug_taps) { HIP_OK(hipStreamSynchronize(s_pix)); CopyPlaneTap(1); }
     // synthetic noise: the random planes go into the tmp planes, which the reconstruction above no longer needs
-    if (any_noise && !(early_noise && c0 == 0)) { LaunchNoise(d_imgs + c0, cnt, max_groups, max_w, max_h, s_pix); Mark("noise", s_pix, 2); }
+    if (any_noise && !(early_noise && c0 == 0)) { LaunchNoise(d_imgs + c0, cnt, max_groups, B.max_w, B.max_h, s_pix); Mark("noise", s_pix, 2); }
     if (!(skip_stages & 16))
-    LaunchFilterTiles(d_imgs + c0, cnt, max_w, max_h, stage_mask, any_unfiltered, any_fused, any_fused2, s_pix);
+    LaunchFilterTiles(d_imgs + c0, cnt, B.max_w, B.max_h, B.stage_mask, B.any_unfiltered, B.any_fused, B.any_fused2, s_pix);
     Mark("filters+output", s_pix, 2);
   }
   if (s_pix != stream) {
@@ -1373,41 +673,37 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (nmod_t) {
     // Modular (lossless) frames of the batch; they depend on nothing but the upload
     if (s_lf != stream) { HIP_OK(hipEventRecord(S.lf_done, s_lf)); HIP_OK(hipStreamWaitEvent(stream, S.lf_done, 0)); }
-    LaunchModularAns(d_imgs, n, (const SectionTask*)(d_blob + off_mod_tasks), nmod_t, plan.mod.Bytes(), plan.max_mod_groups,
+    LaunchModularAns(d_imgs, n, B.mod_tasks, nmod_t, plan.mod.Bytes(), plan.max_mod_groups,
                      plan.max_mod_coded, plan.mod_lanes, plan.mod_rb, plan.mod_wp_lds, plan.direct_mod, stream);
-    for (auto& op : mod_ops) {
+    for (auto& op : B.mod_ops) {
       if (op.kind == 3) LaunchModularPalette(op.a, op.b, op.out, op.nout, op.type, op.rw, op.rh, op.status, stream);   // a: palette, b: indices (rw x rh)
       else LaunchModularOp(op.kind, op.a, op.b, op.c, op.aw, op.ah, op.rw, op.rh, op.type, stream);
     }
-    LaunchModularOut(d_imgs, n, max_mod_pixels, stream);
-    if (ds) LaunchBoxReduce(d_imgs, n, max_ds_cells, stream);
+    LaunchModularOut(d_imgs, n, B.max_mod_pixels, stream);
+    if (ds) LaunchBoxReduce(d_imgs, n, B.max_ds_cells, stream);
     Mark("modular", stream, 2);
   }
-  if (!patch_tiles.empty()) {
+  if (!patches.tiles.empty()) {
     // patched frames (Modular, f32) are final once modular_out_kernel has run; the compositor reads them next, on the same stream
-    LaunchPatches((const PatchFrame*)(d_blob + off_patch_frames), (const PatchTile*)(d_blob + off_patch_tiles), (int)patch_tiles.size(),
-                  (const int32_t*)(d_blob + off_patch_list), (const PatchPos*)(d_blob + off_patch_pos), (const PatchRef*)(d_blob + off_patch_refs),
-                  stream);
+    LaunchPatches(B.patch_frames, B.patch_tiles, (int)patches.tiles.size(), B.patch_list, B.patch_pos, B.patch_refs, stream);
     Mark("patches", stream, 2);
   }
   if (!comps.empty()) {
-    LaunchCompose((const ComposeImage*)(d_blob + off_comp_imgs), (const ComposeFrame*)(d_blob + off_comp_frames), (int)comps.size(), max_segments, stream);
+    LaunchCompose(B.comp_imgs, B.comp_frames, (int)comps.size(), B.max_segments, stream);
     Mark("compose", stream, 2);
   }
   for (int i = 0; i < n; i++)
     if (parse_status[i] == DecoderStatus_Ok && frames[i].orientation != 1 && !ds) {
       const ParsedFrame& f = frames[i];
-      LaunchOrient(imgs[i].out, dev_out[i], (int)f.xsize, (int)f.ysize, (f.ncolor + (f.black_index >= 0 ? 1 : 0) + (f.alpha_index >= 0 ? 1 : 0)) * (int)OutBytesPerSample(f),
-                   (int)f.orientation, stream);
+      LaunchOrient(imgs[i].out, dev_out[i], (int)f.xsize, (int)f.ysize, (int)(OutSamplesPerPixel(f) * OutBytesPerSample(f)), (int)f.orientation, stream);
     }
-  LaunchStatusToHost((const uint32_t*)(d_ws + z_status_base), h_status, n * 16, stream);   // (images that failed to parse: zeros)
+  LaunchStatusToHost(B.status_base, h_status, n * 16, stream);   // (images that failed to parse: zeros)
   HIP_OK(hipEventRecord(S.done, stream));
   HIP_OK(hipGetLastError());
   last_stream = stream;
   S.pending = true;
   last = cur;
   cur = (cur + 1) % kSlots;
-  (void)max_padded;
   if (sync) {
     DecoderStatus st = Finish(statuses, err);
     (void)st;
@@ -1424,102 +720,57 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
 // LF stage of ONE single-section frame on temporary buffers, synchronously: yields the bit position where HfGlobal starts,
 // which the host then parses (ParseHfGlobalAt).  The main pass decodes the (tiny) LF group again with everything in place.
 void JxlHipDecoder::PrepassSingle(ParsedFrame& f, const uint8_t* dev_file) {
-  Bump b;
-  const size_t cells = (size_t)f.w8 * f.h8;
-  const size_t o_img = b.Take(sizeof(DevImage)), o_task = b.Take(sizeof(SectionTask));
-  const size_t o_secoff = b.Take(8 * f.sec_off.size()), o_secsize = b.Take(4 * f.sec_size.size());
-  const size_t o_tree = b.Take(sizeof(DevTreeNode) * f.tree.size());
-  const size_t o_cmap = b.Take(f.mcode.ctx_map.size()), o_cfg = b.Take(4 * f.mcode.cfg.size()), o_alias = b.Take(8 * f.mcode.alias.size());
-  // prefix codes: counts per length, symbol offsets, symbols sorted by code (as the main pass lays them out)
-  std::vector<uint16_t> pfx_counts, pfx_sorted;
-  std::vector<uint32_t> pfx_offs;
-  if (f.mcode.use_prefix)
-    for (auto& pc : f.mcode.prefix) {
-      pfx_counts.insert(pfx_counts.end(), pc.count, pc.count + 16);
-      pfx_offs.push_back((uint32_t)pfx_sorted.size());
-      pfx_sorted.insert(pfx_sorted.end(), pc.sorted.begin(), pc.sorted.end());
-    }
-  const size_t o_pcount = b.Take(2 * std::max<size_t>(1, pfx_counts.size())), o_poff = b.Take(4 * std::max<size_t>(1, pfx_offs.size())),
-               o_psorted = b.Take(2 * std::max<size_t>(1, pfx_sorted.size()));
-  const bool resident = dev_file && f.cs_contiguous;
-  const size_t o_cs = resident ? 0 : b.Take(f.cs_size + 16);
-  const size_t upload = b.off;
-  const size_t o_status = b.Take(64), o_end = b.Take(8), o_count = b.Take(4), o_extra = b.Take(4), o_desc = b.Take(8 * sizeof(ChanDesc));
-  const size_t o_adesc = b.Take(sizeof(ChanDesc));
-  const size_t zero_end = b.off;
-  size_t o_lfq[3];
-  for (int c = 0; c < 3; c++) o_lfq[c] = b.Take(4 * cells);
-  const size_t o_binfo = b.Take((size_t)kBinfoInts * 4);
-  const size_t o_alpha = b.Take(4 * (size_t)f.xsize * f.ysize);
-  const size_t o_wp = f.tree_uses_wp ? b.Take((size_t)kWpLfInts * 4) : 0;
-  const size_t o_lz = f.mcode.lz77 ? b.Take((size_t)4 << 20) : 0;   // the LF group's LZ77 window
+  // One temporary holds the uploaded tables and, from the next 256 bytes on, what the kernel expects cleared and then scratch; laid out
+  // like a batch (batch_layout.h): measured, allocated, placed.  The host writes the first region only, whose staging buffer is as
+  // large as that region.
+  struct Pre { const DevImage* img; const SectionTask* task; uint32_t* status; uint64_t* lf_end; size_t zero_end; };
+  auto lay_out = [&](Region& up, Region& r) {
+    Pre p;
+    DevImage im;
+    memset(&im, 0, sizeof(im));
+    im.w = f.xsize; im.h = f.ysize; im.w8 = f.w8; im.h8 = f.h8; im.xlf = im.ylf = im.nlf = 1; im.xg = im.yg = im.ng = 1;
+    im.has_alpha = f.alpha_index >= 0;
+    im.single = 1; im.alpha_in_global = im.has_alpha;
+    im.lf_start_bits = f.after_lf_global_bits;
+    p.img = up.Array<DevImage>(1);
+    const SectionTask task{0, 0, 1, 0};
+    p.task = up.Put(&task, 1);
+    im.sec_off = up.Put(f.sec_off.data(), f.sec_off.size());
+    im.sec_size = up.Put(f.sec_size.data(), f.sec_size.size());
+    im.tree = up.Put(f.tree.data(), f.tree.size()); im.tree_size = (int32_t)f.tree.size();
+    PackCode(f.mcode, up, im.mcode);
+    im.cs = (dev_file && f.cs_contiguous) ? dev_file + f.cs_file_offset : up.Put(f.cs, f.cs_size, f.cs_size + 16);
+    im.cs_size = f.cs_size;
+    im.status = p.status = r.Array<uint32_t>(16); im.lf_end_bits = p.lf_end = r.Array<uint64_t>(1); im.lf_count = r.Array<uint32_t>(1);
+    im.lf_extra = r.Array<uint8_t>(4); im.lf_desc = r.Array<ChanDesc>(8); im.alpha_desc = r.Array<ChanDesc>(1);
+    p.zero_end = r.off;
+    for (int c = 0; c < 3; c++) im.lfq[c] = r.Array<int32_t>((size_t)f.w8 * f.h8);
+    im.binfo = r.Array<int32_t>(kBinfoInts);
+    im.alpha32 = r.Array<int32_t>((size_t)f.xsize * f.ysize);
+    if (f.tree_uses_wp) im.wp_lf = r.Array<int32_t>(kWpLfInts);
+    if (f.mcode.lz77) im.lz_lf = r.Array<uint32_t>((size_t)1 << 20);   // the LF group's LZ77 window
+    if (DevImage* h = up.Host(p.img)) *h = im;
+    return p;
+  };
+  Region m_up, m_rest;
+  lay_out(m_up, m_rest);
+  const size_t upload = m_up.off, rest_at = Align(upload, 256);
   uint8_t* d = nullptr;
-  HIP_OK(hipMalloc(&d, b.off));
+  HIP_OK(hipMalloc(&d, rest_at + m_rest.off));
   std::vector<uint8_t> h(upload, 0);
-  DevImage im;
-  memset(&im, 0, sizeof(im));
-  im.w = f.xsize; im.h = f.ysize; im.w8 = f.w8; im.h8 = f.h8; im.xlf = im.ylf = im.nlf = 1; im.xg = im.yg = im.ng = 1;
-  im.has_alpha = f.alpha_index >= 0;
-  im.single = 1; im.alpha_in_global = im.has_alpha;
-  im.lf_start_bits = f.after_lf_global_bits;
-  im.cs = resident ? dev_file + f.cs_file_offset : d + o_cs;
-  im.cs_size = f.cs_size;
-  im.sec_off = (const uint64_t*)(d + o_secoff); im.sec_size = (const uint32_t*)(d + o_secsize);
-  im.tree = (const DevTreeNode*)(d + o_tree); im.tree_size = (int32_t)f.tree.size();
-  im.mcode.ctx_map = d + o_cmap; im.mcode.cfg = (const uint32_t*)(d + o_cfg); im.mcode.alias = (const uint64_t*)(d + o_alias);
-  im.mcode.num_ctx = (uint32_t)f.mcode.ctx_map.size(); im.mcode.num_clusters = f.mcode.num_hist; im.mcode.log_alpha = f.mcode.log_alpha;
-  im.mcode.slow = (f.mcode.use_prefix ? 1u : 0u) | (f.mcode.lz77 ? 2u : 0u);
-  if (f.mcode.use_prefix) {
-    im.mcode.pfx_count = (const uint16_t*)(d + o_pcount); im.mcode.pfx_off = (const uint32_t*)(d + o_poff); im.mcode.pfx_sorted = (const uint16_t*)(d + o_psorted);
-  }
-  if (f.mcode.lz77) {
-    im.mcode.lz_min_symbol = f.mcode.lz_min_symbol; im.mcode.lz_min_length = f.mcode.lz_min_length;
-    im.mcode.lz_len_cfg = f.mcode.lz_len.split | f.mcode.lz_len.msb << 4 | f.mcode.lz_len.lsb << 8;
-    im.mcode.lz_dist_cluster = f.mcode.ctx_map.back();
-    im.lz_lf = (uint32_t*)(d + o_lz);
-  }
-  im.status = (uint32_t*)(d + o_status); im.lf_end_bits = (uint64_t*)(d + o_end); im.lf_count = (uint32_t*)(d + o_count);
-  im.lf_extra = d + o_extra; im.lf_desc = (ChanDesc*)(d + o_desc); im.alpha_desc = (ChanDesc*)(d + o_adesc);
-  for (int c = 0; c < 3; c++) im.lfq[c] = (int32_t*)(d + o_lfq[c]);
-  im.binfo = (int32_t*)(d + o_binfo); im.alpha32 = (int32_t*)(d + o_alpha);
-  if (f.tree_uses_wp) im.wp_lf = (int32_t*)(d + o_wp);
-  memcpy(h.data() + o_img, &im, sizeof(im));
-  const SectionTask task{0, 0, 1, 0};
-  memcpy(h.data() + o_task, &task, sizeof(task));
-  memcpy(h.data() + o_secoff, f.sec_off.data(), 8 * f.sec_off.size());
-  memcpy(h.data() + o_secsize, f.sec_size.data(), 4 * f.sec_size.size());
-  memcpy(h.data() + o_tree, f.tree.data(), sizeof(DevTreeNode) * f.tree.size());
-  memcpy(h.data() + o_cmap, f.mcode.ctx_map.data(), f.mcode.ctx_map.size());
-  {
-    std::vector<uint32_t> cfgp(f.mcode.cfg.size());
-    for (size_t k = 0; k < cfgp.size(); k++) {
-      cfgp[k] = f.mcode.cfg[k].split | f.mcode.cfg[k].msb << 4 | f.mcode.cfg[k].lsb << 8;
-      if (f.mcode.use_prefix) {   // one-symbol prefix codes read no bits
-        if (f.mcode.prefix[k].single >= 0) cfgp[k] |= 1u << 12 | (uint32_t)f.mcode.prefix[k].single << 16;
-        continue;
-      }
-      const uint64_t e0 = f.mcode.alias[k << f.mcode.log_alpha];
-      const uint32_t x0 = (uint32_t)e0, y0 = (uint32_t)(e0 >> 32);
-      if ((x0 >> 16) == 0 && (y0 >> 16) == 4096) cfgp[k] |= 1u << 12 | ((x0 >> 8) & 0xFF) << 16;
-    }
-    memcpy(h.data() + o_cfg, cfgp.data(), 4 * cfgp.size());
-  }
-  if (!pfx_counts.empty()) memcpy(h.data() + o_pcount, pfx_counts.data(), 2 * pfx_counts.size());
-  if (!pfx_offs.empty()) memcpy(h.data() + o_poff, pfx_offs.data(), 4 * pfx_offs.size());
-  if (!pfx_sorted.empty()) memcpy(h.data() + o_psorted, pfx_sorted.data(), 2 * pfx_sorted.size());
-  memcpy(h.data() + o_alias, f.mcode.alias.data(), 8 * f.mcode.alias.size());
-  if (!resident) memcpy(h.data() + o_cs, f.cs, f.cs_size);
+  Region up(h.data(), d, upload), rest(nullptr, d + rest_at, m_rest.off);
+  const Pre p = lay_out(up, rest);
   hipError_t e = hipMemcpy(d, h.data(), upload, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d + upload, 0, zero_end - upload);
+  if (e == hipSuccess) e = hipMemset(d + rest_at, 0, p.zero_end);
   uint32_t st_words[16] = {0};
   uint64_t lf_end = 0;
   if (e == hipSuccess) {
     const size_t lds = SlotsLdsBytes(64, f.tree.size(), ShapeOf(f.mcode));
-    LaunchLfAns((const DevImage*)(d + o_img), (const SectionTask*)(d + o_task), 1, 64, lds <= kLdsMax ? lds : 0, 0, false, own_stream);
+    LaunchLfAns(p.img, p.task, 1, 64, lds <= kLdsMax ? lds : 0, 0, false, own_stream);
     e = hipStreamSynchronize(own_stream);
   }
-  if (e == hipSuccess) e = hipMemcpy(st_words, d + o_status, 64, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&lf_end, d + o_end, 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(st_words, p.status, 64, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&lf_end, p.lf_end, 8, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   if (e != hipSuccess) throw HipError(std::string("single-group LF pre-pass: ") + hipGetErrorString(e));
   if (st_words[0]) throw ParseError(DecoderStatus_DecodeError, "GPU decode failed in the LF group of a single-group frame (corrupt bitstream)");

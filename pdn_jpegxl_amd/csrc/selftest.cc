@@ -10,6 +10,7 @@
 #include "../../include/jxlfiletypeio.h"
 #include "dev_util.h"
 #include "enc_types.h"
+#include "batch_layout.h"
 #include "entropy_plan.h"
 #include "host_parse.h"
 #include "host_write.h"
@@ -447,6 +448,196 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_entropy_plan(int32_t n, cons
   for (auto& ho : P.hf_orders) {
     put(ho.image); put(ho.pass); put((int64_t)ho.order.size());
     for (uint32_t g : ho.order) put(g);
+  }
+  if (v.size() > capacity) return 0;
+  memcpy(out, v.data(), v.size() * sizeof(int64_t));
+  return v.size();
+}
+
+// Parses n files, plans them and lays their batch out twice (batch_layout.h; nothing touches a GPU): measuring, then placing with the blob
+// in an ordinary host buffer (host base = device base) and distinct fake bases, never dereferenced, for the zeroed workspace head (region
+// 1), the workspace (2), the callers' output buffers (3), the decoder's static tables (4) and the pixel-chunk planes (5).  opts: as jxlhip_selftest_entropy_plan,
+// then debug_taps.  No layered files (composites empty); one-group lossy frames go in without the LF pre-pass.  Read-back: what the
+// placed DevImages and task tables point at in the blob is compared with the parsed frames and the plan, one comparison per table.
+// out, as numbers (returns how many, 0: they do not fit `capacity`):
+//   n, n_extra, pixel_chunk, measured blob / zero / ws bytes, where the placing pass ended in each, comparisons and mismatches of the
+//   task and hf_order tables, then the toy sequence that places one allocation more than it measured: did it throw, is the guard behind
+//   its buffer intact; measured bytes of the pixel-chunk planes, where the placing pass ended in them;
+//   the measuring pass's allocation log: count, then (region, offset, bytes, align) each; the placing pass's likewise;
+//   per image record (the batch's images, then the later passes' records): image it belongs to, parse status, decoded, are its DevImage
+//   bytes all zero, encoding, w, h, w8, h8, ng, nlf, cs_size, region and offset of cs, comparisons, mismatches; count, then (field, region,
+//   offset) of every non-null pointer of `fields` below, in its order; count, then (split, msb, lsb, packed cfg word) of every cluster of its
+//   codes (images: Modular code, then the first pass's HF code; pass records: their HF code).
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_batch_layout(int32_t n, const uint8_t* const* data, const size_t* sizes, const int32_t* opts,
+                                                                 int64_t* out, size_t capacity) {
+  std::vector<ParsedFrame> frames((size_t)n);
+  std::vector<int> status((size_t)n, DecoderStatus_Ok);
+  for (int i = 0; i < n; i++) {
+    try {
+      ParseFile(data[i], sizes[i], false, frames[i]);
+    } catch (const std::exception&) {
+      status[i] = DecoderStatus_DecodeError;
+    }
+  }
+  EntropyPlanOptions o;
+  o.band_first_row = opts[0]; o.band_rows = opts[1]; o.downscale = opts[2]; o.lane_stride_override = opts[3];
+  o.no_direct = opts[4] != 0; o.mod_lanes64 = opts[5] != 0;
+  const EntropyPlan P = PlanEntropy(frames, status, o);
+  const uintptr_t kZero = (uintptr_t)1 << 44, kWs = (uintptr_t)2 << 44, kOut = (uintptr_t)3 << 44, kStatic = (uintptr_t)4 << 44, kPix = (uintptr_t)5 << 44,
+                  kSpan = (uintptr_t)1 << 44;
+  std::vector<uint8_t*> dev_out((size_t)n);
+  for (int i = 0; i < n; i++) dev_out[i] = (uint8_t*)(kOut + ((uintptr_t)i << 34));
+  const uint16_t* d_natural[kNumOrders]; const U32x2* d_scan[kNumQuantTables]; const float* d_dq[kNumQuantTables]; uint32_t dq_n[kNumQuantTables];
+  for (int k = 0; k < kNumOrders; k++) d_natural[k] = (const uint16_t*)(kStatic + ((uintptr_t)k << 24));
+  for (int q = 0; q < kNumQuantTables; q++) {
+    d_scan[q] = (const U32x2*)(kStatic + ((uintptr_t)(64 + q) << 24)); d_dq[q] = (const float*)(kStatic + ((uintptr_t)(128 + q) << 24));
+    dq_n[q] = (uint32_t)(GetStaticTables().dq[q].size() / 3);
+  }
+  const std::vector<Composite> comps;
+  const std::vector<int> file_of;
+  const std::vector<ParsedFrame> files;
+  BatchInput in;
+  in.frames = &frames; in.parse_status = &status; in.plan = &P;
+  in.dev_out = dev_out.data();
+  in.comps = &comps; in.file_of = &file_of; in.files = &files; in.nfiles = n;
+  in.d_natural = d_natural; in.d_scan = d_scan; in.d_dq = d_dq; in.dq_n = dq_n;
+  in.ds = opts[2] == 8; in.debug_taps = opts[6] != 0;
+  std::vector<Region::Entry> log_m, log_p;
+  BatchRegions M;
+  M.blob.id = 0; M.zero.id = 1; M.ws.id = 2; M.pix.id = 5;
+  M.blob.log = M.zero.log = M.ws.log = M.pix.log = &log_m;
+  {
+    BatchOutput unplaced;
+    BuildBatch(in, M, unplaced);
+  }
+  std::vector<uint8_t> blob(M.blob.off + 1, 0);
+  BatchRegions R{Region(blob.data(), blob.data(), M.blob.off), Region(nullptr, (const void*)kZero, M.zero.off), Region(nullptr, (const void*)kWs, M.ws.off),
+                 Region(nullptr, (const void*)kPix, M.pix.off)};
+  R.blob.id = 0; R.zero.id = 1; R.ws.id = 2; R.pix.id = 5;
+  R.blob.log = R.zero.log = R.ws.log = R.pix.log = &log_p;
+  BatchOutput B;
+  BuildBatch(in, R, B);
+  std::vector<int64_t> v;
+  auto put = [&](int64_t x) { v.push_back(x); };
+  const uintptr_t blob0 = (uintptr_t)blob.data();
+  auto region_of = [&](const void* p, int64_t* off) {
+    const uintptr_t a = (uintptr_t)p;
+    if (a >= blob0 && a < blob0 + M.blob.off) { *off = (int64_t)(a - blob0); return 0; }
+    const uintptr_t bases[5] = {kZero, kWs, kOut, kStatic, kPix};
+    for (int k = 0; k < 5; k++) if (a >= bases[k] && a < bases[k] + kSpan) { *off = (int64_t)(a - bases[k]); return k + 1; }
+    *off = 0;
+    return -1;
+  };
+  // one comparison: `bytes` at p, which must lie in the blob, equal `want` (null: only where they lie is checked)
+  int64_t cmp = 0, bad = 0;
+  auto same = [&](const void* p, const void* want, size_t bytes) {
+    cmp++;
+    const uintptr_t a = (uintptr_t)p;
+    if (a < blob0 || a > blob0 + M.blob.off || bytes > blob0 + M.blob.off - a || (bytes && want && memcmp(p, want, bytes))) bad++;
+  };
+  auto same_code = [&](const DevCode& dc, const HostCode& hc, std::vector<int64_t>& cfg) {
+    same(dc.ctx_map, hc.ctx_map.data(), hc.ctx_map.size());
+    same(dc.alias, hc.alias.data(), 8 * hc.alias.size());
+    cmp++;
+    if (dc.num_ctx != hc.ctx_map.size() || dc.num_clusters != hc.num_hist || dc.log_alpha != hc.log_alpha) bad++;
+    same(dc.cfg, nullptr, 4 * hc.cfg.size());   // in the blob; the test checks the words
+    for (size_t k = 0; k < hc.cfg.size(); k++) { cfg.push_back(hc.cfg[k].split); cfg.push_back(hc.cfg[k].msb); cfg.push_back(hc.cfg[k].lsb); cfg.push_back(dc.cfg[k]); }
+    if (hc.use_prefix) {
+      size_t at = 0;
+      for (size_t k = 0; k < hc.prefix.size(); k++) {
+        same(dc.pfx_count + 16 * k, hc.prefix[k].count, 32);
+        const uint32_t off = (uint32_t)at;
+        same(dc.pfx_off + k, &off, 4);
+        same(dc.pfx_sorted + at, hc.prefix[k].sorted.data(), 2 * hc.prefix[k].sorted.size());
+        at += hc.prefix[k].sorted.size();
+      }
+    }
+  };
+  auto same_tasks = [&](const SectionTask* t, const std::vector<SectionTask>& want) { same(t, want.data(), sizeof(SectionTask) * want.size()); };
+  same_tasks(B.lf_tasks, P.lf_finish_tasks); same_tasks(B.pass_tasks, P.pass_tasks); same_tasks(B.lf_ans_tasks, P.lf_ans_tasks);
+  same_tasks(B.mod_tasks, P.mod_tasks); same_tasks(B.alpha_tasks, P.alpha_tasks);
+  for (const EntropyPlan::HfOrder& ho : P.hf_orders)
+    same(B.imgs[ho.pass ? (size_t)P.frames[ho.image].first_extra + ho.pass - 1 : (size_t)ho.image].hf_order, ho.order.data(), 4 * ho.order.size());
+  same(B.d_imgs, B.imgs.data(), sizeof(DevImage) * B.imgs.size());
+  // the toy sequence: two allocations measured, three placed
+  int64_t threw = 0, guard_ok = 1;
+  {
+    Region m;
+    m.Take(100); m.Take(50);
+    std::vector<uint8_t> buf(m.off + 64, 0xA5);
+    Region r(buf.data(), buf.data(), m.off);
+    const std::vector<uint8_t> src(100, 0x11);
+    try {
+      r.Put(src.data(), 100); r.Put(src.data(), 50); r.Put(src.data(), 8);
+    } catch (const std::length_error&) {
+      threw = 1;
+    }
+    for (size_t k = m.off; k < buf.size(); k++) if (buf[k] != 0xA5) guard_ok = 0;
+  }
+  for (int64_t x : {(int64_t)n, (int64_t)P.n_extra, (int64_t)B.pixel_chunk, (int64_t)M.blob.off, (int64_t)M.zero.off, (int64_t)M.ws.off, (int64_t)R.blob.off,
+                    (int64_t)R.zero.off, (int64_t)R.ws.off, cmp, bad, threw, guard_ok, (int64_t)M.pix.off, (int64_t)R.pix.off})
+    put(x);
+  for (const std::vector<Region::Entry>* log : {&log_m, &log_p}) {
+    put((int64_t)log->size());
+    for (const Region::Entry& e : *log) { put(e.region); put((int64_t)e.off); put((int64_t)e.bytes); put((int64_t)e.align); }
+  }
+  std::vector<int> image_of(B.imgs.size(), -1);
+  for (int i = 0; i < n; i++) {
+    image_of[i] = i;
+    if (status[i] == DecoderStatus_Ok && frames[i].encoding == 0)
+      for (size_t p = 0; p < frames[i].extra_passes.size(); p++) image_of[(size_t)P.frames[i].first_extra + p] = i;
+  }
+  for (size_t r = 0; r < B.imgs.size(); r++) {
+    const DevImage& d = B.imgs[r];
+    const int i = image_of[r];
+    const ParsedFrame& f = frames[i];
+    const bool decoded = status[i] == DecoderStatus_Ok;
+    bool all_zero = true;
+    for (size_t k = 0; k < sizeof(DevImage); k++) all_zero &= ((const uint8_t*)&d)[k] == 0;
+    cmp = bad = 0;
+    std::vector<int64_t> cfg;
+    if (decoded) {
+      same(d.cs, f.cs, f.cs_size);
+      same(d.sec_off, f.sec_off.data(), 8 * f.sec_off.size());
+      same(d.sec_size, f.sec_size.data(), 4 * f.sec_size.size());
+      same(d.tree, f.tree.data(), sizeof(DevTreeNode) * f.tree.size());
+      if ((int)r < n) same_code(d.mcode, f.mcode, cfg);
+      if (f.encoding == 0) {
+        const size_t pass = (int)r < n ? 0 : r - (size_t)P.frames[i].first_extra + 1;
+        same_code(d.acode, pass ? f.extra_passes[pass - 1].acode : f.acode, cfg);
+        for (int ob = 0; ob < kNumOrders; ob++)
+          for (int c = 0; c < 3; c++) {
+            const std::vector<uint16_t>& own = f.custom_order[ob][c];
+            if (!own.empty()) same(d.order[ob * 3 + c], own.data(), 2 * own.size());
+            else { cmp++; if (d.order[ob * 3 + c] != d_natural[ob]) bad++; }
+          }
+      }
+    }
+    int64_t cs_off = 0;
+    const int cs_region = region_of(d.cs, &cs_off);
+    for (int64_t x : {(int64_t)i, (int64_t)status[i], (int64_t)decoded, (int64_t)all_zero, (int64_t)f.encoding, (int64_t)f.xsize, (int64_t)f.ysize, (int64_t)f.w8,
+                      (int64_t)f.h8, (int64_t)f.ng, (int64_t)f.nlf, (int64_t)f.cs_size, (int64_t)cs_region, cs_off, cmp, bad})
+      put(x);
+    // every pointer of a DevImage into the workspace (or, for `out`, the caller's buffer), in the order of
+    // tests/test_batch_layout.py's FIELDS
+    const void* const fields[] = {
+        d.lf[0], d.lf[1], d.lf[2], d.lf_tmp[0], d.lf_tmp[1], d.lf_tmp[2], d.lf_final[0], d.lf_final[1], d.lf_final[2], d.lfq[0], d.lfq[1], d.lfq[2],
+        d.lf_extra, d.cellinfo, d.rawq, d.sharp, d.ytox, d.ytob, d.binfo, d.lf_desc, d.lf_count, d.alpha_desc, d.blk_list, d.blk_count, d.grp_bitpos,
+        d.alpha_bitpos, d.lf_end_bits, d.mod_plane[0], d.mod_plane[1], d.mod_plane[2], d.mod_plane[3], d.mod_plane[4], d.mod_desc, d.wp_lf, d.wp_grp,
+        d.lz_lf, d.lz_grp, d.lz_hf, d.lz_mod, d.alpha32, d.centries, d.cblk, d.coef[0], d.coef[1], d.coef[2], d.tmp[0], d.tmp[1], d.tmp[2], d.xyb[0],
+        d.xyb[1], d.xyb[2], d.xyb2[0], d.xyb2[1], d.xyb2[2], d.inv_sigma, d.tile_list, d.alpha, d.out, d.status, d.noise_rnd[0], d.noise_rnd[1],
+        d.noise_rnd[2], d.noise[0], d.noise[1], d.noise[2], d.ds_alpha, d.ds_out};
+    std::vector<int64_t> fl;
+    for (size_t k = 0; k < sizeof(fields) / sizeof(fields[0]); k++) {
+      if (!fields[k]) continue;
+      int64_t off = 0;
+      const int reg = region_of(fields[k], &off);
+      fl.push_back((int64_t)k); fl.push_back(reg); fl.push_back(off);
+    }
+    put((int64_t)fl.size() / 3);
+    for (int64_t x : fl) put(x);
+    put((int64_t)cfg.size() / 4);
+    for (int64_t x : cfg) put(x);
   }
   if (v.size() > capacity) return 0;
   memcpy(out, v.data(), v.size() * sizeof(int64_t));
