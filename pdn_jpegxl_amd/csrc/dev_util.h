@@ -39,6 +39,26 @@ __host__ __device__ __forceinline__ uint32_t NnzBucketCtx(uint32_t nzl) {
   return (uint32_t)(0xCEB4987B5D3E1F00ull >> (8 * b)) & 0xFFu;
 }
 
+// Position context of an HF coefficient token, for ks = scan position / cells the varblock covers, in [1, 63]: the format's three pieces
+// (ks - 1 below 16, then one context per two positions, from 32 on one per four) as the minimum of three lines, without branches.
+// The CPU suite checks all 63 inputs against the piecewise definition through jxlhip_selftest_hf_pos_ctx.
+__host__ __device__ __forceinline__ uint32_t HfPosCtx(uint32_t ks) {
+  const uint32_t a = ks - 1, b = 7 + (ks >> 1), c = 15 + (ks >> 2);
+  const uint32_t bc = b < c ? b : c;
+  return a < bc ? a : bc;
+}
+
+// Context of a block's non-zero-count token.  The prediction: from the counts of the block above and the block to the left (each
+// already divided by the cells its block covers), 32 for the group's first block.  Its bucket: clamped at 64, one context per value below
+// 8 and one per two values from there on (0 .. 36).  The CPU suite checks both through jxlhip_selftest_hf_nnz_predict / _bucket.
+__host__ __device__ __forceinline__ uint32_t HfNnzPredict(uint32_t bx, uint32_t by, uint32_t above, uint32_t left) {
+  return bx == 0 ? (by == 0 ? 32u : above) : (by == 0 ? left : (above + left + 1) >> 1);
+}
+__host__ __device__ __forceinline__ uint32_t HfNnzCountBucket(uint32_t predicted) {
+  const uint32_t p = predicted >= 64 ? 64 : predicted;
+  return p < 8 ? p : 4 + p / 2;
+}
+
 // Integer sample of `bits` bits -> output sample (8 or 16 bits).  Equal depths pass through clamped; otherwise through a [0, 1]
 // float, like the decoder library behind the reference does for every channel whose depth differs from the output type's.
 __device__ __forceinline__ uint32_t IntToOutSample(int32_t v, int bits, int out_bits) {

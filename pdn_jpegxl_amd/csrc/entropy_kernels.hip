@@ -53,6 +53,10 @@ __device__ __forceinline__ void SetError(const DevImage& im, uint32_t bits, int 
 // Table pointers are typed by address space so that the LDS variants compile to ds_read (not flat_load).
 #define JXL_LDS __attribute__((address_space(3)))
 #define JXL_GLB __attribute__((address_space(1)))
+// a value every lane holds alike, moved to a scalar register (a no-op for values the compiler already holds in one)
+#define JXL_RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+// What an ANS stream's state must be after its last symbol (and the state a prefix-coded stream, which has none, is given).
+constexpr uint32_t kAnsEndState = 0x130000u;
 // pointers read out of DevImage are generic; cast the hot ones so they compile to global_load/global_store
 template <class T> __device__ __forceinline__ JXL_GLB T* G(T* p) { return (JXL_GLB T*)p; }
 typedef int __attribute__((ext_vector_type(4))) I4;
@@ -78,6 +82,7 @@ struct LaneBitsT {
   int skip;
   uint32_t pend[kBatch];       // words [filled, filled + kBatch) as requested by the previous top-up, not yet in the ring
   bool has_pend;
+  static constexpr bool kScalar = false;
   // state of the general symbol reader (prefix codes / LZ77), per stream like the bit position
   JXL_GLB uint32_t* lz_win;    // window of decoded values (LZ77), lz_mask + 1 entries
   uint32_t lz_mask, lz_dm, lz_copy, lz_src, lz_done, slow_err;
@@ -158,6 +163,38 @@ struct LaneBitsT {
 // the default window: 32 words, topped up (two 16-byte loads at a time) every 16 tokens
 typedef LaneBitsT<kRingWords, 8> LaneBits;
 
+// The scalar copy of a bit window, for a wavefront that decodes ONE section: position and buffer live in scalar registers, the window's
+// words come back from LDS through v_readfirstlane.  Load() lifts them out of the lane's reader, Store() hands them back; TopUp() is
+// the hand-over in between (the lane's reader refills the ring from where the scalar copy has read to).  The refill is hinted as
+// rare (the hint sits on the branch itself: one inside a helper that returns the condition is dropped before inlining).
+template <int kRing>
+struct ScalarBitsT {
+  uint64_t buf;
+  int n;
+  uint32_t rd;
+  JXL_LDS uint32_t* ring;   // as the lane's reader holds them (callers whose lanes all hold the same move them to scalar registers)
+  uint32_t rs;
+  static constexpr bool kScalar = true;
+  template <class Bits> __device__ __forceinline__ void Load(const Bits& b) {
+    buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);
+    n = (int)JXL_RFL(b.n); rd = JXL_RFL(b.rd);
+    ring = b.ring; rs = b.rs;
+  }
+  template <class Bits> __device__ __forceinline__ void Store(Bits& b) const { b.buf = buf; b.n = n; b.rd = rd; }
+  template <class Bits> __device__ __forceinline__ void TopUp(Bits& b) const { b.rd = rd; b.TopUp(); }
+  __device__ __forceinline__ void Word() {
+    if (__builtin_expect(n <= 32, 0)) { buf |= (uint64_t)JXL_RFL(ring[__umul24(rd & (kRing - 1), rs)]) << n; n += 32; rd++; }
+  }
+  __device__ __forceinline__ uint32_t Read(uint32_t k) {   // k <= 32
+    Word();
+    const uint32_t v = (uint32_t)(buf & (((uint64_t)1 << k) - 1));
+    buf >>= k;
+    n -= (int)k;
+    return v;
+  }
+};
+typedef ScalarBitsT<kRingWords> ScalarBits;
+
 template <bool kLds> struct AS;
 template <> struct AS<true> {
   typedef const JXL_LDS uint8_t* U8;
@@ -193,33 +230,51 @@ __device__ __forceinline__ DevTreeNode NodeOf(I4 v) {
   return n;
 }
 
+// The hybrid-integer tail of a token: symbol + configuration (split | msb << 4 | lsb << 8) -> value, its extra bits from any bit source
+// (a lane's reader or the scalar copy of one).
 template <class Bits>
 __device__ __forceinline__ uint32_t HybridTail(Bits& b, uint32_t c, uint32_t sym) {
   const uint32_t se = c & 0xF, split = 1u << se;
-  if (sym < split) return sym;
+  // (a scalar source: the tail out of line - a taken scalar branch costs far more than a scalar instruction in those loops)
+  if constexpr (Bits::kScalar) { if (__builtin_expect(sym < split, 1)) return sym; }
+  else { if (sym < split) return sym; }
   const uint32_t msb = (c >> 4) & 0xF, lsb = (c >> 8) & 0xF;
   const uint32_t nb = se - (msb + lsb) + ((sym - split) >> (msb + lsb));
   const uint32_t low = sym & ((1u << lsb) - 1);
   const uint32_t t = sym >> lsb;
   const uint32_t bits = b.Read(nb > 32 ? 32 : nb);
   const uint32_t hi = (1u << msb) | (t & ((1u << msb) - 1));
-  return (uint32_t)(((((uint64_t)hi << nb) | bits) << lsb) | low);
+  return (uint32_t)(((((uint64_t)hi << (nb & 63)) | bits) << lsb) | low);
+}
+
+// The ANS step, written once: the alias-table entry (x, y) of the state's bucket -> symbol, and the state advanced and renormalised
+// from `b`.  The entry is at index AnsBucket() of the cluster's table (1 << log_alpha entries); le = 12 - log_alpha.  Scalar loops pass
+// x and y as they come out of v_readfirstlane and a scalar bit window, and the whole step stays on the scalar unit.
+// kMul24: the 13 x 20 bit product as a full-rate v_mad_u32_u24 (v_mul_lo_u32 is quarter rate); the scalar unit has no such form.
+// kRareRenorm: hint the renormalisation as the rare branch (scalar loops that were measured with it).
+__device__ __forceinline__ uint32_t AnsBucket(uint32_t state, uint32_t le) { return (state & 0xFFF) >> le; }
+template <bool kMul24 = true, bool kRareRenorm = false, class Bits>
+__device__ __forceinline__ uint32_t AnsStep(Bits& b, uint32_t& state, uint32_t x, uint32_t y, uint32_t le) {
+  const uint32_t res = state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
+  const bool g = pos >= (x & 0xFF);
+  const uint32_t sym = g ? ((x >> 8) & 0xFF) : i;
+  const uint32_t off = g ? (y & 0xFFFF) + pos : pos;
+  const uint32_t freq = g ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
+  state = (kMul24 ? __umul24(freq, state >> 12) : freq * (state >> 12)) + off;
+  if constexpr (kRareRenorm) { if (__builtin_expect(state < 65536u, 0)) state = (state << 16) | b.Read(16); }
+  else { if (state < 65536u) state = (state << 16) | b.Read(16); }
+  return sym;
+}
+template <bool kMul24 = true, class Bits>
+__device__ __forceinline__ uint32_t AnsStep(Bits& b, uint32_t& state, uint64_t e, uint32_t le) {
+  return AnsStep<kMul24>(b, state, (uint32_t)e, (uint32_t)(e >> 32), le);
 }
 
 // One ANS symbol from the alias table of a fixed cluster (`abase` = that cluster's table).
 template <bool kLds>
 __device__ __forceinline__ uint32_t AnsSym(LaneBits& b, uint32_t& state, typename AS<kLds>::U64 abase, uint32_t log_alpha) {
   const uint32_t le = 12 - log_alpha;
-  const uint32_t res = state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-  const uint64_t e = abase[i];
-  const uint32_t x = (uint32_t)e, y = (uint32_t)(e >> 32);
-  const bool g = pos >= (x & 0xFF);
-  const uint32_t sym = g ? ((x >> 8) & 0xFF) : i;
-  const uint32_t off = g ? (y & 0xFFFF) + pos : pos;
-  const uint32_t freq = g ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-  state = __umul24(freq, state >> 12) + off;   // 13 x 20 bits: full-rate v_mad_u32_u24 (v_mul_lo_u32 is quarter rate)
-  if (state < 65536u) state = (state << 16) | b.Read(16);
-  return sym;
+  return AnsStep(b, state, abase[AnsBucket(state, le)], le);
 }
 
 // The same with the alias entry of the NEXT token requested as soon as the new state is known: its LDS round trip then overlaps the
@@ -232,15 +287,8 @@ __device__ __forceinline__ uint64_t AnsPrefetch(uint32_t state, typename AS<kLds
 template <bool kLds>
 __device__ __forceinline__ uint32_t AnsSymPf(LaneBits& b, uint32_t& state, typename AS<kLds>::U64 abase, uint32_t log_alpha, uint64_t& e) {
   const uint32_t le = 12 - log_alpha;
-  const uint32_t res = state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-  const uint32_t x = (uint32_t)e, y = (uint32_t)(e >> 32);
-  const bool g = pos >= (x & 0xFF);
-  const uint32_t sym = g ? ((x >> 8) & 0xFF) : i;
-  const uint32_t off = g ? (y & 0xFFFF) + pos : pos;
-  const uint32_t freq = g ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-  state = __umul24(freq, state >> 12) + off;
-  if (state < 65536u) state = (state << 16) | b.Read(16);
-  e = abase[(state & 0xFFF) >> le];
+  const uint32_t sym = AnsStep(b, state, e, le);
+  e = abase[AnsBucket(state, le)];
   return sym;
 }
 
@@ -280,16 +328,7 @@ __device__ __forceinline__ uint32_t SlowSymbol(Bits& b, uint32_t& state, const C
     return 0;
   }
   const uint32_t le = 12 - t.log_alpha;
-  const uint32_t res = state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-  const uint64_t e = t.alias[(cl << t.log_alpha) | i];
-  const uint32_t x = (uint32_t)e, y = (uint32_t)(e >> 32);
-  const bool g = pos >= (x & 0xFF);
-  const uint32_t sym = g ? ((x >> 8) & 0xFF) : i;
-  const uint32_t off = g ? (y & 0xFFFF) + pos : pos;
-  const uint32_t freq = g ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-  state = freq * (state >> 12) + off;
-  if (state < 65536u) state = (state << 16) | b.Read(16);
-  return sym;
+  return AnsStep<false>(b, state, t.alias[(cl << t.log_alpha) | AnsBucket(state, le)], le);
 }
 
 template <bool kLds, class Bits>
@@ -326,24 +365,16 @@ __device__ __forceinline__ uint32_t SlowGet(Bits& b, uint32_t& state, const Code
 }
 // first value of a stream's ANS state: read from the stream, except for prefix codes (no state)
 template <bool kLds, class Bits>
-__device__ __forceinline__ uint32_t InitAnsState(Bits& b, const CodeTab<kLds>& t) { return (t.slow & 1) ? 0x130000u : b.Read(32); }
+__device__ __forceinline__ uint32_t InitAnsState(Bits& b, const CodeTab<kLds>& t) { return (t.slow & 1) ? kAnsEndState : b.Read(32); }
 
 template <bool kLds, class Bits>
 __device__ __forceinline__ uint32_t AnsGet(Bits& b, uint32_t& state, const CodeTab<kLds>& t, uint32_t ctx) {
   if (t.slow) return SlowGet(b, state, t, ctx);   // uniform over the wavefront: one image, one code
   const uint32_t cl = t.cmap[ctx];
   const uint32_t le = 12 - t.log_alpha;
-  const uint32_t res = state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-  const uint64_t e = t.alias[(cl << t.log_alpha) | i];
+  const uint64_t e = t.alias[(cl << t.log_alpha) | AnsBucket(state, le)];
   const uint32_t c = t.cfg[cl];
-  const uint32_t x = (uint32_t)e, y = (uint32_t)(e >> 32);
-  const bool g = pos >= (x & 0xFF);
-  const uint32_t sym = g ? ((x >> 8) & 0xFF) : i;
-  const uint32_t off = g ? (y & 0xFFFF) + pos : pos;
-  const uint32_t freq = g ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-  state = __umul24(freq, state >> 12) + off;   // 13 x 20 bits: full-rate v_mad_u32_u24 (v_mul_lo_u32 is quarter rate)
-  if (state < 65536u) state = (state << 16) | b.Read(16);
-  return HybridTail(b, c, sym);
+  return HybridTail(b, c, AnsStep(b, state, e, le));
 }
 
 // Cooperative copy of a code's tables into LDS (layout: CodeLds); returns the carved end offset.
@@ -685,21 +716,16 @@ __device__ int ClassifyChannel(const CodeTab<kLds>& tab, typename AS<kLds>::Tree
 // issues one instruction every four to five cycles whichever unit executes it, so what counts here is the instruction count per
 // token: sixteen tokens unrolled between top-ups (no loop or address arithmetic per token), the common leaf (multiplier 1, offset
 // 0, predictor applied in phase B) without the multiply / offset / West instructions.
-#define JXL_RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
 typedef const __attribute__((address_space(4))) uint32_t* ConstU32;   // constant address space: uniform reads become scalar loads
 template <bool kPlain, class TabPtr>
 __device__ __forceinline__ void RowScalar(LaneBits& b, uint32_t& state, TabPtr dt, uint32_t cfg, uint32_t mul, uint32_t off,
                                           bool add_w, uint32_t W, uint32_t& first_out, JXL_GLB int32_t* row, int w) {
-  uint32_t s_state = JXL_RFL(state), s_w = JXL_RFL(W), s_first = 0, s_rd = JXL_RFL(b.rd);
-  uint64_t s_buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);
-  int s_n = (int)JXL_RFL(b.n);
+  uint32_t s_state = JXL_RFL(state), s_w = JXL_RFL(W), s_first = 0;
+  ScalarBits sb;
+  sb.Load(b);
   const uint32_t s_cfg = JXL_RFL(cfg), s_mul = JXL_RFL(mul), s_off = JXL_RFL(off);
-  const uint32_t se = s_cfg & 0xF, split = 1u << se, msb = (s_cfg >> 4) & 0xF, lsb = (s_cfg >> 8) & 0xF;
   const bool s_addw = JXL_RFL(add_w ? 1u : 0u) != 0;
   const int sw = (int)JXL_RFL(w);
-  auto word = [&]() {
-    if (__builtin_expect(s_n <= 32, 0)) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRingWords - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
-  };
   auto token = [&](int x) {
     const uint32_t e = JXL_RFL(dt[s_state & 0xFFF]);
     const uint32_t hi = s_state >> 12;
@@ -708,21 +734,8 @@ __device__ __forceinline__ void RowScalar(LaneBits& b, uint32_t& state, TabPtr d
     uint32_t t = hi + ((e >> 12) & 0xFFF);
     asm volatile("" : "+s"(t));
     s_state = (e & 0xFFF) * hi + t;
-    if (__builtin_expect(s_state < 65536u, 0)) {
-      word();
-      s_state = (s_state << 16) | ((uint32_t)s_buf & 0xFFFFu);
-      s_buf >>= 16; s_n -= 16;
-    }
-    const uint32_t sym = e >> 24;
-    uint32_t u = sym;
-    if (__builtin_expect(sym >= split, 0)) {   // out of line: a taken scalar branch costs far more than a scalar instruction here
-      const uint32_t nb = se - (msb + lsb) + ((sym - split) >> (msb + lsb)), nbr = nb > 32 ? 32 : nb;
-      word();
-      const uint32_t bits = (uint32_t)(s_buf & (((uint64_t)1 << nbr) - 1));
-      s_buf >>= nbr; s_n -= (int)nbr;
-      const uint32_t low = sym & ((1u << lsb) - 1), top = (1u << msb) | ((sym >> lsb) & ((1u << msb) - 1));
-      u = (uint32_t)(((((uint64_t)top << (nb & 63)) | bits) << lsb) | low);
-    }
+    if (__builtin_expect(s_state < 65536u, 0)) s_state = (s_state << 16) | sb.Read(16);
+    const uint32_t u = HybridTail(sb, s_cfg, e >> 24);
     if constexpr (kPlain) {
       row[x] = UnpackSigned(u);
     } else {
@@ -734,17 +747,16 @@ __device__ __forceinline__ void RowScalar(LaneBits& b, uint32_t& state, TabPtr d
   };
   int x0 = 0;
   for (; x0 + kTopUpEvery <= sw; x0 += kTopUpEvery) {
-    b.rd = s_rd;
-    b.TopUp();
+    sb.TopUp(b);
 #pragma unroll
     for (int k = 0; k < kTopUpEvery; k++) token(x0 + k);
   }
   if (x0 < sw) {
-    b.rd = s_rd;
-    b.TopUp();
+    sb.TopUp(b);
     for (int x = x0; x < sw; x++) token(x);
   }
-  state = s_state; b.buf = s_buf; b.n = s_n; b.rd = s_rd;
+  state = s_state;
+  sb.Store(b);
   first_out = s_first;
 }
 
@@ -760,6 +772,13 @@ struct UniAreas {
 };
 
 // What alpha_ans_kernel asks of DecodeChannelLane beyond the plain decode (LF and Modular channels pass none).
+// What a channel is left as when nothing more is to be done with it: decoded in place, or given up after an error.
+__device__ __forceinline__ ChanDesc FinalChan() {
+  ChanDesc d;
+  d.kind = kChanFinal; d.value = 0; d.pad0 = 0; d.pad1 = 0;
+  return d;
+}
+
 struct AlphaNarrow {
   uint32_t limit;       // largest |residual| the narrow form may hold; 0: this group keeps the int32 form
   uint32_t* counters;   // the image's status words (kStatusAlphaNarrow / kStatusAlphaRedo)
@@ -780,8 +799,7 @@ template <bool kLds, bool kUni = false, bool kGeneric = true>
 __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, const CodeTab<kLds>& tab, typename AS<kLds>::Tree tree, int chan, int sid,
                                   int w, int h, int32_t* out_generic, int stride, ChanDesc* desc, int32_t* wp_scratch = nullptr,
                                   const RowBuf<kLds>* lane_rows = nullptr, const UniAreas* uni = nullptr, AlphaNarrow* nar = nullptr) {
-  ChanDesc d;
-  d.kind = kChanFinal; d.value = 0; d.pad0 = 0; d.pad1 = 0;
+  ChanDesc d = FinalChan();
   if (w <= 0 || h <= 0) { *desc = d; return; }
   bool needs_n = false;
   int32_t cval = 0;
@@ -1155,6 +1173,13 @@ __device__ __forceinline__ void LoadModTables(const DevImage& im, uint8_t* smem,
   }
 }
 
+// A section ended well: the ANS state is back where every stream ends, the general reader met no error, and (bounded: the section has
+// a size of its own) no bit behind the section's end was consumed.  start_bits: the bit offset `b` was initialised with.
+template <class Bits>
+__device__ __forceinline__ bool SectionEndOk(const DevImage& im, const Bits& b, uint32_t state, uint64_t start_bits, int sec, bool bounded = true) {
+  return state == kAnsEndState && !b.slow_err && (!bounded || start_bits + b.Consumed() <= (im.sec_off[sec] + im.sec_size[sec]) * 8);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ LF groups, phase A: one lane per LF group
@@ -1200,7 +1225,7 @@ __global__ __launch_bounds__(64) void lf_ans_kernel(const DevImage* imgs, const 
     }
     if (i == 0) {
       if (im.alpha_in_global) {
-        if (state != 0x130000u || b.slow_err) { err |= kErrBitstream; break; }
+        if (state != kAnsEndState || b.slow_err) { err |= kErrBitstream; break; }
         if (!im.single) {
           if (im.lf_start_bits + b.Consumed() > (im.sec_off[0] + im.sec_size[0]) * 8) { err |= kErrBitstream; break; }
           b.Init(im.cs, im.cs_size, start_bits, (JXL_LDS uint32_t*)smem + lane, (uint32_t)slots);
@@ -1214,7 +1239,7 @@ __global__ __launch_bounds__(64) void lf_ans_kernel(const DevImage* imgs, const 
       state = InitAnsState(b, mt.tab);
     }
     if (i == 3) {
-      if (state != 0x130000u) { err |= kErrBitstream; break; }
+      if (state != kAnsEndState) { err |= kErrBitstream; break; }
       count = b.Read(CeilLog2D((uint32_t)(bw * bh))) + 1;
       if (count > (uint32_t)(bw * bh)) { err |= kErrBlockLayout; break; }
       if (b.Read(4) != 3) { err |= kErrUnsupportedHeader; break; }
@@ -1240,7 +1265,7 @@ __global__ __launch_bounds__(64) void lf_ans_kernel(const DevImage* imgs, const 
     }
     DecodeChannelLane<kLds, false, kGeneric>(b, state, mt.tab, mt.tree, chan, sid, w, h, out, stride, cd, wps);
   }
-  if (!err && (state != 0x130000u || b.slow_err || start_bits + b.Consumed() > (im.sec_off[lf_sec] + im.sec_size[lf_sec]) * 8)) err |= kErrBitstream;
+  if (!err && !SectionEndOk(im, b, state, start_bits, lf_sec)) err |= kErrBitstream;
   if (im.single) im.lf_end_bits[0] = start_bits + b.Consumed();
   im.lf_count[g] = err ? 0u : count;
   if (err) SetError(im, err, 1, g);
@@ -1485,43 +1510,396 @@ __global__ __launch_bounds__(64) void hf_blocklist_kernel(const DevImage* __rest
 // Output: every NON-ZERO coefficient becomes one 32-bit entry (scan position | value << 16) appended to the group's list -
 // sequential 4-byte stores, no coefficient order in the loop, nothing to pre-zero; the (first entry, count) pair of each
 // (block, channel) goes to cblk at the block's origin cell.  recon_tile_kernel scatters the entries into its LDS tile.
-// kRing: words of the per-lane bit window.  32 (top-up every 16 tokens, 8 queued descriptors: 288 B of LDS per lane) is the
-// faster loop for one frame; 16 (top-up every 8 tokens, 4 descriptors: 192 B per lane) lets more workgroups share a CU, which is
-// what matters when a batch launches more workgroups than the chip has CUs.  `nslots` = lanes the LDS arrays are laid out for
-// (the task's section count rounded up to four: every workgroup uses what ITS image's tables leave of the launch's LDS).
+// The per-lane bit window holds kHfRingWords = 32 words (top-up every 16 tokens, 8 queued descriptors: 288 B of LDS per lane).
+// `nslots` = lanes the LDS arrays are laid out for (the task's section count rounded up to four: every workgroup uses what ITS
+// image's tables leave of the launch's LDS).
 // (the four serial decoders do NOT take the DevImage array as __restrict__ like the other kernels do: with it the compiler re-reads
 // frame fields through the scalar cache inside the token loops - 101 scalar loads instead of 24 in this kernel - and a lone section's
 // chain gets longer: hf_decode of one 4K frame 12.3 -> 12.8 ms)
-template <bool kLds, int kRing>
+//
+// The kernel is set-up, one of three token loops, epilogue.  The loops differ in how they schedule a token, not in what a token means:
+// the format's rules are the helpers below (and HfPosCtx / HfNnzPredict / HfNnzCountBucket / NnzBucketCtx in dev_util.h).
+//   HfBatchedLoop   several sections per wavefront, plain ANS: one straight-line step per token, contexts formed a block ahead
+//   HfScalarRun     one section per wavefront, plain ANS: a run of coefficient tokens on the scalar unit (entered from HfGeneralLoop,
+//                   whose step takes that wavefront's non-zero counts and block starts)
+//   HfGeneralLoop   everything else: prefix codes, LZ77, tables in global memory
+namespace {
+
+constexpr int kHfTop = kHfRingWords / 2;   // tokens between top-ups: a token consumes at most 48 bits and starts at most one block ...
+constexpr int kHfQ = kHfQueueDepth;        // ... so kHfTop tokens never outrun kHfRingWords * 3 / 4 + 1 words / kHfTop / 3 + 1 descriptors
+constexpr uint32_t kHfDqMask = 2u * kHfQ - 1;
+typedef LaneBitsT<kHfRingWords, kHfRingWords / 4> HfBits;
+typedef ScalarBitsT<kHfRingWords> HfScalarBits;
+
+// Cycle counters of the profile build (-DJXLHIP_PROFILE_HF; tools/hf_prof.py parses the line Print() writes).  In a normal build
+// the methods are empty and the loops carry nothing.
+struct HfProfile {
+#ifdef JXLHIP_PROFILE_HF
+  uint64_t start = clock64(), scalar = 0, period = 0, tokens = 0, entries = 0, periods = 0, general = 0, general_n = 0;
+  __device__ __forceinline__ uint64_t Now() const { return clock64(); }
+  __device__ __forceinline__ void Period(uint64_t t0) { periods++; period += clock64() - t0; }
+  __device__ __forceinline__ void ScalarRun(uint64_t t0, uint32_t n) { entries++; scalar += clock64() - t0; tokens += n; }
+  __device__ __forceinline__ uint64_t GeneralBegin() { general_n++; return clock64(); }
+  __device__ __forceinline__ void GeneralEnd(uint64_t t0) { general += clock64() - t0; }
+  __device__ __forceinline__ void Print(int g, uint32_t nblk, int per_wave) const {
+    if (per_wave == 1)
+      printf("[hfprof] g %d total %llu scalar-loop %llu (%llu entries, %llu tokens) period %llu (%llu periods) blocks %u general %llu (%llu iterations)\n", g,
+             (unsigned long long)(clock64() - start), (unsigned long long)scalar, (unsigned long long)entries, (unsigned long long)tokens,
+             (unsigned long long)period, (unsigned long long)periods, nblk, (unsigned long long)general, (unsigned long long)general_n);
+  }
+#else
+  __device__ __forceinline__ uint64_t Now() const { return 0; }
+  __device__ __forceinline__ void Period(uint64_t) {}
+  __device__ __forceinline__ void ScalarRun(uint64_t, uint32_t) {}
+  __device__ __forceinline__ uint64_t GeneralBegin() { return 0; }
+  __device__ __forceinline__ void GeneralEnd(uint64_t) {}
+  __device__ __forceinline__ void Print(int, uint32_t, int) const {}
+#endif
+};
+
+// What a lane's section is decoded with and into; fixed before the token loop starts (no global load may sit in the token loop -
+// its wait would also wait for the stores - so every pointer is formed up front).
+template <bool kLds>
+struct HfLane {
+  CodeTab<kLds> tab;
+  typename AS<kLds>::U8 nnz_tab;   // d_nnz_ctx
+  int nslots;
+  JXL_LDS uint8_t* col;            // col[(c * 32 + x) * nslots]
+  JXL_LDS uint32_t* dq;            // queue of the next 2 * kHfQ varblock descriptors, entry j at dq[(j & kHfDqMask) * nslots]
+  const JXL_GLB uint32_t* list;    // the group's descriptors in decode order, nblk of them
+  uint32_t nblk;
+  JXL_GLB uint32_t* ent;           // output: the group's entry list ...
+  JXL_GLB U2* cblk;                // ... and the per-(block, channel) index, at the group's origin cell
+  uint32_t ncells, w8;
+  uint32_t ctx_offset, nbc;        // first context of the section's preset; block contexts
+};
+
+// The descriptor queue: staged through LDS and topped up together with the bit window.
+struct HfQueue {
+  uint32_t bi, filled, pend_n;   // next block to start; descriptors [0, filled) are queued; [filled, filled + pend_n) are requested
+  uint32_t pend[kHfQ];
+};
+
+// The current block, the current (block, channel) and the token the lane is at.
+struct HfState {
+  uint32_t bx, by, lcx, log2c, covered, size, ctxs, cell;
+  int ci;   // 0..2: channel slot in coding order (Y, X, B); 3: the block is finished
+  uint32_t nzeros, k, prev, histo;
+  bool want_nz;   // the next token is a non-zero count (else a coefficient)
+  uint32_t epos;
+};
+
+// once per period (every kHfTop tokens): the bit window and the descriptor queue are topped up
+template <bool kLds>
+__device__ __forceinline__ void HfPeriod(const HfLane<kLds>& L, HfBits& b, HfQueue& q, HfProfile& pf) {
+  const uint64_t t0 = pf.Now();
+  b.TopUp();
+  // descriptors the same way: a period starts at most kHfQ blocks, the queue holds 2 * kHfQ; what the previous period requested is
+  // queued now, the next kHfQ are requested
+  if (q.pend_n) {
+#pragma unroll
+    for (int i = 0; i < kHfQ; i++) if ((uint32_t)i < q.pend_n) L.dq[__umul24((q.filled + i) & kHfDqMask, L.nslots)] = q.pend[i];
+    q.filled += q.pend_n;
+    q.pend_n = 0;
+  }
+  if (q.filled < min(L.nblk, q.bi + kHfQ)) {   // start of the section, or a burst: wait for them
+    const uint32_t lim = min(L.nblk, q.bi + kHfQ);
+    uint32_t v[kHfQ];
+#pragma unroll
+    for (int i = 0; i < kHfQ; i++) { v[i] = 0u; if (q.filled + i < lim) v[i] = L.list[q.filled + i]; }
+#pragma unroll
+    for (int i = 0; i < kHfQ; i++) if (q.filled + i < lim) L.dq[__umul24((q.filled + i) & kHfDqMask, L.nslots)] = v[i];
+    q.filled = lim;
+  }
+  {
+    const uint32_t lim = min(L.nblk, q.bi + 2 * kHfQ);
+    if (q.filled < lim) {
+      q.pend_n = min(lim - q.filled, (uint32_t)kHfQ);
+#pragma unroll
+      for (int i = 0; i < kHfQ; i++) { q.pend[i] = 0u; if ((uint32_t)i < q.pend_n) q.pend[i] = L.list[q.filled + i]; }
+    }
+  }
+  pf.Period(t0);
+}
+
+// ---- the format's rules, each stated once
+// channel of coding slot ci (Y, X, B)
+__device__ __forceinline__ int HfChannel(int ci) { return ci == 0 ? 1 : (ci == 1 ? 0 : 2); }
+// a varblock starts: descriptor -> block state (the word hf_blocklist_kernel wrote)
+__device__ __forceinline__ void HfUnpackBlock(HfState& t, uint32_t d, uint32_t w8) {
+  t.bx = d & 31; t.by = (d >> 5) & 31;
+  t.lcx = (d >> 10) & 7;
+  const uint32_t lcy = (d >> 13) & 7;
+  t.ctxs = d >> 16;
+  t.log2c = t.lcx + lcy; t.covered = 1u << t.log2c; t.size = t.covered << 6;
+  t.cell = __umul24(t.by, w8) + t.bx;
+  t.ci = 0;
+}
+// non-zeros left per covered cell, rounded up: what the columns record of a block, and what buckets the coefficient contexts
+__device__ __forceinline__ uint32_t HfNzPerCell(const HfState& t) { return (t.nzeros + t.covered - 1) >> t.log2c; }
+// context of the non-zero-count token of slot ci, from the column values above (x = bx) and to the left (x = bx - 1, or 0)
+template <bool kLds>
+__device__ __forceinline__ uint32_t HfNnzCtx(const HfLane<kLds>& L, const HfState& t, int ci, uint32_t above, uint32_t left) {
+  return L.ctx_offset + HfNnzCountBucket(HfNnzPredict(t.bx, t.by, above, left)) * L.nbc + ((t.ctxs >> (5 * ci)) & 31);
+}
+// context of the coefficient token at t.k; nz_ctx: the context offset of HfNzPerCell (NnzBucketCtx, or d_nnz_ctx where a lookup is cheaper)
+__device__ __forceinline__ uint32_t HfCoeffCtx(const HfState& t, uint32_t nz_ctx) {
+  return t.histo + (nz_ctx + HfPosCtx(t.k >> t.log2c)) * 2 + t.prev;
+}
+// A non-zero count u arrives: bound check (false: the stream is corrupt, nothing recorded), the columns the block covers, the
+// (first entry, count) record, and on to the channel's coefficients - or, with none, to the next channel.
+template <bool kLds>
+__device__ __forceinline__ bool HfTakeNnz(const HfLane<kLds>& L, HfState& t, uint32_t u) {
+  t.nzeros = u;
+  if (t.nzeros + t.covered > t.size) return false;
+  const uint32_t fill = HfNzPerCell(t);
+  const int c = HfChannel(t.ci);
+  JXL_LDS uint8_t* const cc = L.col + __umul24(c * 32 + t.bx, L.nslots);
+  for (uint32_t ix = 0; ix < (1u << t.lcx); ix++) cc[__umul24(ix, L.nslots)] = (uint8_t)fill;
+  U2 rec;
+  rec.x = t.epos; rec.y = t.nzeros;
+  L.cblk[(size_t)c * L.ncells + t.cell] = rec;
+  if (t.nzeros) {
+    const uint32_t block_ctx = (t.ctxs >> (5 * t.ci)) & 31;
+    t.histo = L.ctx_offset + L.nbc * 37 + 458 * block_ctx;
+    t.prev = t.nzeros > t.size / 16 ? 0 : 1;
+    t.k = t.covered;
+    t.want_nz = false;
+  } else {
+    t.ci++;
+  }
+  return true;
+}
+// A coefficient token u arrives at position t.k: a non-zero value must fit int16 (else kErrRange) and becomes an entry; the channel
+// ends with its last non-zero.  false: the block's positions ran out before its non-zeros did (the stream is corrupt).
+// (HfScalarRun has its own form of this: counted down instead of tested per token, the range check one OR per value.)
+template <bool kLds>
+__device__ __forceinline__ bool HfTakeCoeff(const HfLane<kLds>& L, HfState& t, uint32_t u, uint32_t& err) {
+  if (u) {
+    const int32_t v = UnpackSigned(u);
+    if (v != (int32_t)(int16_t)v) err |= kErrRange;
+    L.ent[t.epos++] = t.k | (uint32_t)v << 16;
+    t.prev = 1;
+    if (--t.nzeros == 0) { t.want_nz = true; t.ci++; }
+  } else {
+    t.prev = 0;
+  }
+  return !(++t.k >= t.size && t.nzeros != 0);
+}
+
+// ---- loop 1: several sections per wavefront, plain ANS.
+// The contexts of a block's three non-zero-count tokens are formed at the descriptor pop from registers.  The col[] values a block's
+// predictions need are read one block AHEAD, at the previous pop (its descriptor is held in a register, the one after it is being
+// read), so those reads never head a token; the only col[] entries they can miss are the previous block's own fills, which are
+// patched in from registers (col[x] is always the value of the last block covering column x).
+template <bool kLds>
+__device__ __forceinline__ void HfBatchedLoop(const HfLane<kLds>& L, HfBits& b, uint32_t& state, HfQueue& q, HfState& t, uint32_t& it, uint32_t& err,
+                                              HfProfile& pf) {
+  const int nslots = L.nslots;
+  uint32_t nz_ctx0 = 0, nz_ctx1 = 0, nz_ctx2 = 0;   // contexts of the current block's non-zero-count tokens, channels in ci order
+  uint32_t d_next = 0, d_after = 0;                  // descriptors of blocks bi and bi + 1 (valid from the first pop on)
+  uint32_t up0 = 0, up1 = 0, up2 = 0, lf0 = 0, lf1 = 0, lf2 = 0;   // col[] above (x = bx) / left (x = bx - 1) of block bi, as read
+  uint32_t pbx = 0, pcx = 0, fv0 = 0, fv1 = 0, fv2 = 0;           // the previous block's columns [pbx, pbx + pcx) and its fills
+  while (!err) {
+    if ((it & (kHfTop - 1)) == 0) HfPeriod(L, b, q, pf);
+    // One straight-line step per token for both token kinds: the wavefront almost always holds a lane that starts a block and one
+    // that reads a non-zero count, so what used to be their own code paths (descriptor read -> col[] reads -> context map) headed
+    // nearly every step.  Now the loop-carried chain is context map -> alias entry (+ cfg beside it) -> state.
+    auto colv = [&](uint32_t c, uint32_t x) { return (uint32_t)L.col[__umul24(c * 32 + x, nslots)]; };
+    auto look_ahead = [&]() {   // col[] around block bi (descriptor d_next), read before the current block's fills land
+      const uint32_t x = d_next & 31, xl = x ? x - 1 : 0;
+      up0 = colv(1, x); lf0 = colv(1, xl);
+      up1 = colv(0, x); lf1 = colv(0, xl);
+      up2 = colv(2, x); lf2 = colv(2, xl);
+    };
+    if (t.want_nz && t.ci >= 3) {
+      if (q.bi >= L.nblk) break;
+      if (q.bi == 0) {   // first block of the section: nothing read ahead yet, and no previous block to patch from
+        d_next = L.dq[0];
+        d_after = L.dq[__umul24(1u & kHfDqMask, nslots)];
+        look_ahead();
+        pcx = 0;
+      }
+      HfUnpackBlock(t, d_next, L.w8);
+      const uint32_t xl = t.bx ? t.bx - 1 : 0;
+      const bool up_prev = t.bx - pbx < pcx, lf_prev = xl - pbx < pcx;   // columns the previous block filled after the reads
+      nz_ctx0 = HfNnzCtx(L, t, 0, up_prev ? fv0 : up0, lf_prev ? fv0 : lf0);
+      nz_ctx1 = HfNnzCtx(L, t, 1, up_prev ? fv1 : up1, lf_prev ? fv1 : lf1);
+      nz_ctx2 = HfNnzCtx(L, t, 2, up_prev ? fv2 : up2, lf_prev ? fv2 : lf2);
+      pbx = t.bx; pcx = 1u << t.lcx;
+      q.bi++;
+      // block bi is at most two ahead of the last pop of a period, so its descriptor and the next one are already queued
+      d_next = d_after;
+      // That copy is made HERE: left to the compiler it can sink behind the read below, which then lands in a temporary that has to be
+      // waited for - with the six col[] reads in front of it - at the end of this very pop: an LDS round trip heading nearly every step.
+      asm volatile("" : "+v"(d_next));
+      look_ahead();
+      d_after = L.dq[__umul24((q.bi + 1) & kHfDqMask, nslots)];
+    }
+    const uint32_t nzc = t.ci == 0 ? nz_ctx0 : (t.ci == 1 ? nz_ctx1 : nz_ctx2);
+    const uint32_t u = AnsGet(b, state, L.tab, t.want_nz ? nzc : HfCoeffCtx(t, NnzBucketCtx(HfNzPerCell(t))));
+    it++;
+    if (t.want_nz) {
+      const int ci = t.ci;
+      if (!HfTakeNnz(L, t, u)) { err |= kErrBitstream; break; }
+      const uint32_t fill = HfNzPerCell(t);   // what the block's columns now hold
+      fv0 = ci == 0 ? fill : fv0; fv1 = ci == 1 ? fill : fv1; fv2 = ci == 2 ? fill : fv2;
+    } else if (!HfTakeCoeff(L, t, u, err)) {
+      err |= kErrBitstream;
+      break;
+    }
+  }
+}
+
+// ---- loop 2: one section per wavefront (single frames, small batches), plain ANS: one run of coefficient tokens.
+// Every value of this loop is the same in all lanes, i.e. it is scalar work - and on this machine a dependent scalar operation costs a
+// fraction of a dependent vector one (which issues every ~10 cycles).  The loop-carried state is moved to scalar registers
+// (v_readfirstlane), table entries come back from LDS through the same door, and the recurrence state -> alias entry -> state runs on
+// the scalar unit; only the LDS addresses and the entry store touch vector registers.
+// A lone wavefront issues one instruction every four cycles or so, and every LDS lookup on the chain adds ~80: the loop is
+// written for few instructions and few dependent lookups - the tokens a period or the block still allows are counted down
+// (no per-token stop conditions), the non-zero-count bucket is looked up again only after a non-zero coefficient, the range
+// check is one OR per coefficient, and a code whose clusters share one hybrid-integer configuration (cfg_is_uni) skips that lookup.
+template <bool kLds>
+__device__ __forceinline__ void HfScalarRun(const HfLane<kLds>& L, HfBits& b, uint32_t& state, HfState& t, uint32_t& it, uint32_t& err, uint32_t cfg_uni,
+                                            bool cfg_is_uni, HfProfile& pf) {
+  const uint64_t t0 = pf.Now();
+  uint32_t s_state = JXL_RFL(state), s_nz = JXL_RFL(t.nzeros), s_k = JXL_RFL(t.k), s_prev = JXL_RFL(t.prev), s_epos = JXL_RFL(t.epos), s_it = JXL_RFL(it);
+  const uint32_t s_cov = JXL_RFL(t.covered), s_l2 = JXL_RFL(t.log2c), s_size = JXL_RFL(t.size), s_histo = JXL_RFL(t.histo);
+  HfScalarBits sb;
+  sb.Load(b);
+  uint32_t s_rng = 0;
+  const uint32_t la = JXL_RFL(L.tab.log_alpha), le = 12 - la;
+  const uint32_t left = kHfTop - (s_it & (kHfTop - 1)), room = s_size > s_k ? s_size - s_k : 0u;
+  const uint32_t cnt0 = min(left, room);
+  uint32_t cnt = cnt0;
+  uint32_t s_a = s_histo + 2 * JXL_RFL(L.nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
+  uint32_t s_cidx = 0xFFFFFFFFu, s_cl = 0;
+  if (cnt) do {
+    // inside a run of zeros the context only moves when the position context does (every second / fourth position from 16 / 32
+    // on): the cluster of the last lookup is kept while the context-map index stays the same
+    const uint32_t cidx = s_a + HfPosCtx(s_k >> s_l2) * 2 + s_prev;
+    if (cidx != s_cidx) { s_cl = JXL_RFL(L.tab.cmap[cidx]); s_cidx = cidx; }
+    const uint32_t cl = s_cl;
+    const uint64_t e = L.tab.alias[(cl << la) | AnsBucket(s_state, le)];
+    uint32_t c = cfg_uni;
+    if (__builtin_expect(!cfg_is_uni, 0)) c = JXL_RFL(L.tab.cfg[cl]);
+    const uint32_t sym = AnsStep<false>(sb, s_state, JXL_RFL((uint32_t)e), JXL_RFL((uint32_t)(e >> 32)), le);
+    const uint32_t u = HybridTail(sb, c, sym);
+    cnt--;
+    s_prev = 0;
+    if (u) {
+      const int32_t v = UnpackSigned(u);
+      s_rng |= (uint32_t)(v + 0x8000);   // a value outside int16 leaves a bit above bit 15
+      L.ent[s_epos++] = s_k | (uint32_t)v << 16;
+      s_prev = 1;
+      s_k++;
+      if (--s_nz == 0) break;
+      s_a = s_histo + 2 * JXL_RFL(L.nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
+    } else {
+      s_k++;
+    }
+  } while (cnt);
+  s_it += cnt0 - cnt;
+  pf.ScalarRun(t0, cnt0 - cnt);
+  uint32_t s_err = s_rng > 0xFFFFu ? (uint32_t)kErrRange : 0u;
+  if (s_nz != 0 && s_k >= s_size) s_err |= kErrBitstream;
+  state = s_state; t.nzeros = s_nz; t.k = s_k; t.prev = s_prev; t.epos = s_epos; it = s_it;
+  sb.Store(b);
+  err |= s_err;
+  if (s_nz == 0 && !s_err) { t.want_nz = true; t.ci++; }
+}
+
+// ---- loop 3: the general loop (prefix codes, LZ77, tables in global memory; and the non-zero counts and block starts of a
+// one-section wavefront, whose coefficient runs are HfScalarRun's).
+template <bool kLds>
+__device__ __forceinline__ void HfGeneralLoop(const HfLane<kLds>& L, HfBits& b, uint32_t& state, HfQueue& q, HfState& t, uint32_t& it, uint32_t& err,
+                                              bool one_section, HfProfile& pf) {
+  const int nslots = L.nslots;
+  // one-section wavefronts: do all clusters share one hybrid-integer configuration?  (then the token loop keeps it in a register)
+  uint32_t cfg_uni = 0;
+  bool cfg_is_uni = false;
+  if (one_section) {
+    cfg_uni = L.tab.cfg[0] & 0xFFF;
+    cfg_is_uni = true;
+    for (uint32_t i = 1; i < L.tab.dc->num_clusters; i++) cfg_is_uni &= (L.tab.cfg[i] & 0xFFF) == cfg_uni;
+    cfg_uni = JXL_RFL(cfg_uni);
+    cfg_is_uni = JXL_RFL(cfg_is_uni) != 0;
+  }
+  while (!err) {
+    if ((it & (kHfTop - 1)) == 0) HfPeriod(L, b, q, pf);
+    // Fast path: while every lane of the wavefront that is still decoding sits inside a run of coefficient tokens (always the
+    // case with one section per wavefront, i.e. small batches), stay in a loop that holds nothing but the coefficient token:
+    // the general iteration below pays for both token kinds and their bookkeeping on every step.
+    if (__all(!t.want_nz)) {
+      if (one_section) {
+        HfScalarRun(L, b, state, t, it, err, cfg_uni, cfg_is_uni, pf);
+        continue;
+      }
+      for (;;) {
+        const uint32_t u = AnsGet(b, state, L.tab, HfCoeffCtx(t, L.nnz_tab[HfNzPerCell(t)]));
+        it++;
+        const bool ok = HfTakeCoeff(L, t, u, err);
+        if (!ok) err |= kErrBitstream;
+        if (__any(!ok || t.want_nz) || (it & (kHfTop - 1)) == 0) break;
+      }
+      continue;
+    }
+    const uint64_t t0 = pf.GeneralBegin();
+    if (t.want_nz && t.ci >= 3) {
+      if (q.bi >= L.nblk) break;
+      HfUnpackBlock(t, L.dq[__umul24(q.bi & kHfDqMask, nslots)], L.w8);
+      q.bi++;
+    }
+    uint32_t ctx;
+    if (t.want_nz) {
+      const JXL_LDS uint8_t* const cc = L.col + __umul24(HfChannel(t.ci) * 32, nslots);
+      const uint32_t xl = t.bx ? t.bx - 1 : 0;
+      ctx = HfNnzCtx(L, t, t.ci, cc[__umul24(t.bx, nslots)], cc[__umul24(xl, nslots)]);
+    } else {
+      ctx = HfCoeffCtx(t, L.nnz_tab[HfNzPerCell(t)]);
+    }
+    const uint32_t u = AnsGet(b, state, L.tab, ctx);
+    it++;
+    if (t.want_nz) {
+      if (!HfTakeNnz(L, t, u)) { err |= kErrBitstream; break; }
+    } else if (!HfTakeCoeff(L, t, u, err)) {
+      err |= kErrBitstream;
+      break;
+    }
+    pf.GeneralEnd(t0);
+  }
+}
+
+}  // namespace
+
+template <bool kLds>
 __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, const SectionTask* tasks, int lane_stride) {
   JXL_SERIAL_PRIO();
-  constexpr int kTop = kRing / 2;   // tokens between top-ups: a token consumes at most 48 bits and starts at most one block ...
-  constexpr int kQ = HfQueueDepth(kRing);   // ... so kTop tokens never outrun kRing - kRing / 4 + 1 words / kTop / 3 + 1 descriptors
-  typedef LaneBitsT<kRing, kRing / 4> Bits;
   extern __shared__ __align__(16) uint8_t smem[];
   const SectionTask task = tasks[blockIdx.x];
   const DevImage& im = imgs[task.image];
   const int per_wave = 64 / lane_stride;
   const int nslots = HfSlots(task.count);
-  CodeTab<kLds> tab;
-  typename AS<kLds>::U8 nnz_tab;
+  HfLane<kLds> L;
+  L.nslots = nslots;
   JXL_LDS uint8_t* nzcol;
   JXL_LDS uint32_t* ring_base;
-  JXL_LDS uint32_t* descq;   // per lane: queue of the next 2 * kQ varblock descriptors, entry j at descq[(j & (2 * kQ - 1)) * nslots + slot]
+  JXL_LDS uint32_t* descq;
   {
     JXL_LDS uint8_t* lds = (JXL_LDS uint8_t*)smem;
-    const HfLds at(nslots, kRing);
+    const HfLds at(nslots);
     ring_base = (JXL_LDS uint32_t*)(lds + at.ring);
     descq = (JXL_LDS uint32_t*)(lds + at.descq);
     nzcol = lds + at.nzcol;
     if constexpr (kLds) {
-      JXL_LDS uint8_t* sn = lds + StageCode(lds, at.tables, im.acode, tab, threadIdx.x, blockDim.x);   // kNnzCtxBytes behind the code
+      JXL_LDS uint8_t* sn = lds + StageCode(lds, at.tables, im.acode, L.tab, threadIdx.x, blockDim.x);   // kNnzCtxBytes behind the code
       if (threadIdx.x < kNnzCtxBytes) sn[threadIdx.x] = d_nnz_ctx[threadIdx.x];
-      nnz_tab = sn;
+      L.nnz_tab = sn;
       __syncthreads();
     } else {
-      GlobalCode(im.acode, tab);
-      nnz_tab = d_nnz_ctx;
+      GlobalCode(im.acode, L.tab);
+      L.nnz_tab = d_nnz_ctx;
     }
   }
   // Active lanes are the FIRST 64/lane_stride lanes of every wavefront: a wave64 whose upper 32 lanes are idle issues
@@ -1529,388 +1907,48 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
   if ((int)(threadIdx.x & 63) >= per_wave) return;
   const int si = (threadIdx.x >> 6) * per_wave + (threadIdx.x & 63);
   if (si >= task.count || si >= nslots) return;
-  JXL_LDS uint8_t* const col = nzcol + si;   // col[(c * 32 + x) * nslots]
+  L.col = nzcol + si;
   const int g = im.hf_order[task.first + si];   // lanes in order of section size (see the task table in entropy_plan.cc)
   const int sec = im.single ? 0 : im.hf_sec_base + g;
   const uint64_t sec_bits = im.single ? im.hf_start_bits : im.sec_off[sec] * 8;
-  Bits b;
+  HfBits b;
   b.Init(im.cs, im.cs_size, sec_bits, ring_base + si, (uint32_t)nslots);
   const uint32_t preset = b.Read(CeilLog2D((uint32_t)im.num_presets));
-  const uint32_t nbc = im.num_block_ctx;
-  const uint32_t ctx_offset = preset * nbc * 495;
+  L.nbc = im.num_block_ctx;
+  L.ctx_offset = preset * L.nbc * 495;
   uint32_t err = preset >= (uint32_t)im.num_presets ? (uint32_t)kErrBitstream : 0u;
   if (im.lz_hf) b.SetLz(im.lz_hf + ((size_t)g << 18), 18, 0);   // one-dimensional stream: plain distances
-  uint32_t state = InitAnsState(b, tab);
+  uint32_t state = InitAnsState(b, L.tab);
   const int gx = g % im.xg, gy = g / im.xg;
   // block descriptors: staged through a small LDS queue that is topped up together with the bit window
-  const JXL_GLB uint32_t* const list = G(im.blk_list + (size_t)g * 1024);
+  L.list = G(im.blk_list + (size_t)g * 1024);
   uint32_t nblk = im.blk_count[g];
   // Wait for that load HERE: left pending into the token loop, it made the compiler put a full `s_waitcnt vmcnt(0)` in front of
   // every `bi < nblk` test - i.e. every block start (nearly every step of a batched wavefront) waited for all coefficient stores.
   asm volatile("" : "+v"(nblk));
-  JXL_LDS uint32_t* const dq = descq + si;
-  constexpr uint32_t dqmask = 2u * kQ - 1;
-  uint32_t bi = 0, dfilled = 0, it = 0, dpend_n = 0;
-  uint32_t dpend[kQ];
+  L.nblk = nblk;
+  L.dq = descq + si;
+  HfQueue q;
+  q.bi = 0; q.filled = 0; q.pend_n = 0;
 #pragma unroll
-  for (int i = 0; i < kQ; i++) dpend[i] = 0u;
-  // output: the group's entry list and the per-(block, channel) index (no global load may sit in the token loop - its wait would
-  // also wait for the stores - so every pointer is formed up front)
-  JXL_GLB uint32_t* const ent = G(im.centries) + (size_t)(g - im.centries_g0) * kGroupEntriesCap;
-  const uint32_t ncells = (uint32_t)im.w8 * (uint32_t)im.h8;
-  JXL_GLB U2* const cblk = (JXL_GLB U2*)G(im.cblk) + (size_t)(gy * kGroupBlocks) * im.w8 + (size_t)gx * kGroupBlocks;
-  const uint32_t w8 = (uint32_t)im.w8;
-  uint32_t epos = 0;
-  // current block
-  uint32_t bx = 0, by = 0, lcx = 0, log2c = 0, covered = 1, size = 64, ctxs = 0, cell = 0;
-  // current (block, channel)
-  int ci = 3;
-  uint32_t nzeros = 0, k = 0, prev = 0, histo = 0;
-  bool want_nz = true;
-#ifdef JXLHIP_PROFILE_HF
-  const uint64_t pf_start = clock64();
-  uint64_t pf_scalar = 0, pf_period = 0, pf_tokens = 0, pf_entries = 0, pf_periods = 0, pf_general = 0, pf_general_n = 0;
-#endif
-  // one-section wavefronts: do all clusters share one hybrid-integer configuration?  (then the token loop keeps it in a register)
-  uint32_t cfg_uni = 0;
-  bool cfg_is_uni = false;
-  if (per_wave == 1 && !tab.slow) {
-    cfg_uni = tab.cfg[0] & 0xFFF;
-    cfg_is_uni = true;
-    for (uint32_t i = 1; i < tab.dc->num_clusters; i++) cfg_is_uni &= (tab.cfg[i] & 0xFFF) == cfg_uni;
-    cfg_uni = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg_uni);
-    cfg_is_uni = __builtin_amdgcn_readfirstlane((int)cfg_is_uni) != 0;
-  }
-  // Batched ANS path (several sections per wavefront): the contexts of a block's three non-zero-count tokens are formed at the
-  // descriptor pop from registers.  The col[] values a block's predictions need are read one block AHEAD, at the previous pop (its
-  // descriptor is held in a register, the one after it is being read), so those reads never head a token; the only col[] entries
-  // they can miss are the previous block's own fills, which are patched in from registers (col[x] is always the value of the last
-  // block covering column x).
-  uint32_t nz_ctx0 = 0, nz_ctx1 = 0, nz_ctx2 = 0;   // contexts of the current block's non-zero-count tokens, channels in ci order
-  uint32_t d_next = 0, d_after = 0;                  // descriptors of blocks bi and bi + 1 (valid from the first pop on)
-  uint32_t up0 = 0, up1 = 0, up2 = 0, lf0 = 0, lf1 = 0, lf2 = 0;   // col[] above (x = bx) / left (x = bx - 1) of block bi, as read
-  uint32_t pbx = 0, pcx = 0, fv0 = 0, fv1 = 0, fv2 = 0;           // the previous block's columns [pbx, pbx + pcx) and its fills
-  // once per period (every kTop tokens): the bit window and the descriptor queue are topped up
-  auto period = [&]() {
-#ifdef JXLHIP_PROFILE_HF
-    const uint64_t pf_t0 = clock64();
-    pf_periods++;
-#endif
-    b.TopUp();
-    // descriptors the same way: a period starts at most kQ blocks, the queue holds 2 * kQ; what the previous period requested is
-    // queued now, the next kQ are requested
-    if (dpend_n) {
-#pragma unroll
-      for (int i = 0; i < kQ; i++) if ((uint32_t)i < dpend_n) dq[__umul24((dfilled + i) & dqmask, nslots)] = dpend[i];
-      dfilled += dpend_n;
-      dpend_n = 0;
-    }
-    if (dfilled < min(nblk, bi + kQ)) {   // start of the section, or a burst: wait for them
-      const uint32_t lim = min(nblk, bi + kQ);
-      uint32_t v[kQ];
-#pragma unroll
-      for (int i = 0; i < kQ; i++) { v[i] = 0u; if (dfilled + i < lim) v[i] = list[dfilled + i]; }
-#pragma unroll
-      for (int i = 0; i < kQ; i++) if (dfilled + i < lim) dq[__umul24((dfilled + i) & dqmask, nslots)] = v[i];
-      dfilled = lim;
-    }
-    {
-      const uint32_t lim = min(nblk, bi + 2 * kQ);
-      if (dfilled < lim) {
-        dpend_n = min(lim - dfilled, (uint32_t)kQ);
-#pragma unroll
-        for (int i = 0; i < kQ; i++) { dpend[i] = 0u; if ((uint32_t)i < dpend_n) dpend[i] = list[dfilled + i]; }
-      }
-    }
-#ifdef JXLHIP_PROFILE_HF
-    pf_period += clock64() - pf_t0;
-#endif
-  };
-  if (per_wave > 1 && !tab.slow) {
-    while (!err) {
-      if ((it & (kTop - 1)) == 0) period();
-      // One straight-line step per token for both token kinds: the wavefront almost always holds a lane that starts a block and one
-      // that reads a non-zero count, so what used to be their own code paths (descriptor read -> col[] reads -> context map) headed
-      // nearly every step.  Now the loop-carried chain is context map -> alias entry (+ cfg beside it) -> state.
-      auto colv = [&](uint32_t c, uint32_t x) { return (uint32_t)col[__umul24(c * 32 + x, nslots)]; };
-      auto look_ahead = [&]() {   // col[] around block bi (descriptor d_next), read before the current block's fills land
-        const uint32_t x = d_next & 31, xl = x ? x - 1 : 0;
-        up0 = colv(1, x); lf0 = colv(1, xl);
-        up1 = colv(0, x); lf1 = colv(0, xl);
-        up2 = colv(2, x); lf2 = colv(2, xl);
-      };
-      if (want_nz && ci >= 3) {
-        if (bi >= nblk) break;
-        if (bi == 0) {   // first block of the section: nothing read ahead yet, and no previous block to patch from
-          d_next = dq[0];
-          d_after = dq[__umul24(1u & dqmask, nslots)];
-          look_ahead();
-          pcx = 0;
-        }
-        const uint32_t d = d_next;
-        bx = d & 31; by = (d >> 5) & 31;
-        lcx = (d >> 10) & 7;
-        const uint32_t lcy = (d >> 13) & 7;
-        ctxs = d >> 16;
-        log2c = lcx + lcy; covered = 1u << log2c; size = covered << 6;
-        cell = __umul24(by, w8) + bx;
-        ci = 0;
-        const uint32_t xl = bx ? bx - 1 : 0;
-        const bool up_prev = bx - pbx < pcx, lf_prev = xl - pbx < pcx;   // columns the previous block filled after the reads
-        auto nz_ctx = [&](uint32_t up, uint32_t lf, uint32_t fv, uint32_t block_ctx) {
-          const uint32_t a = up_prev ? fv : up, l = lf_prev ? fv : lf;
-          uint32_t p = bx == 0 ? (by == 0 ? 32u : a) : (by == 0 ? l : (a + l + 1) >> 1);
-          p = p >= 64 ? 64 : p;
-          p = p < 8 ? p : 4 + p / 2;
-          return ctx_offset + p * nbc + block_ctx;
-        };
-        nz_ctx0 = nz_ctx(up0, lf0, fv0, ctxs & 31);
-        nz_ctx1 = nz_ctx(up1, lf1, fv1, (ctxs >> 5) & 31);
-        nz_ctx2 = nz_ctx(up2, lf2, fv2, (ctxs >> 10) & 31);
-        pbx = bx; pcx = 1u << lcx;
-        bi++;
-        // block bi is at most two ahead of the last pop of a period, so its descriptor and the next one are already queued
-        d_next = d_after;
-        look_ahead();
-        d_after = dq[__umul24((bi + 1) & dqmask, nslots)];
-      }
-      const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-      const uint32_t ks = k >> log2c;
-      const uint32_t fctx = min(ks - 1, min(7 + (ks >> 1), 15 + (ks >> 2)));
-      const uint32_t nzc = ci == 0 ? nz_ctx0 : (ci == 1 ? nz_ctx1 : nz_ctx2);
-      const uint32_t u = AnsGet(b, state, tab, want_nz ? nzc : histo + (NnzBucketCtx(nzl) + fctx) * 2 + prev);
-      it++;
-      if (want_nz) {
-        nzeros = u;
-        if (nzeros + covered > size) { err |= kErrBitstream; break; }
-        const uint32_t fill = (nzeros + covered - 1) >> log2c;
-        const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-        JXL_LDS uint8_t* const cc = col + __umul24(c * 32 + bx, nslots);
-        for (uint32_t ix = 0; ix < (1u << lcx); ix++) cc[__umul24(ix, nslots)] = (uint8_t)fill;
-        fv0 = ci == 0 ? fill : fv0; fv1 = ci == 1 ? fill : fv1; fv2 = ci == 2 ? fill : fv2;
-        U2 rec;
-        rec.x = epos; rec.y = nzeros;
-        cblk[(size_t)c * ncells + cell] = rec;
-        if (nzeros) {
-          const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
-          histo = ctx_offset + nbc * 37 + 458 * block_ctx;
-          prev = nzeros > size / 16 ? 0 : 1;
-          k = covered;
-          want_nz = false;
-        } else {
-          ci++;
-        }
-      } else {
-        if (u) {
-          const int32_t v = UnpackSigned(u);
-          if (v != (int32_t)(int16_t)v) err |= kErrRange;
-          ent[epos++] = k | (uint32_t)v << 16;
-          prev = 1;
-          if (--nzeros == 0) { want_nz = true; ci++; }
-        } else {
-          prev = 0;
-        }
-        if (++k >= size && nzeros != 0) { err |= kErrBitstream; break; }
-      }
-    }
-  } else {
-    while (!err) {
-      if ((it & (kTop - 1)) == 0) period();
-      // Fast path: while every lane of the wavefront that is still decoding sits inside a run of coefficient tokens (always the
-      // case with one section per wavefront, i.e. small batches), stay in a loop that holds nothing but the coefficient token:
-      // the general iteration below pays for both token kinds and their bookkeeping on every step.
-      if (__all(!want_nz)) {
-        if (per_wave == 1 && !tab.slow) {
-          // One section per wavefront (single frames, small batches): every value of this loop is the same in all lanes, i.e. it is
-          // scalar work - and on this machine a dependent scalar operation costs a fraction of a dependent vector one (which issues
-          // every ~10 cycles).  The loop-carried state is moved to scalar registers (v_readfirstlane), table entries come back from LDS
-          // through the same door, and the recurrence state -> alias entry -> state runs on the scalar unit; only the LDS addresses and
-          // the entry store touch vector registers.
-  #define JXL_RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
-  #ifdef JXLHIP_PROFILE_HF
-          const uint64_t pf_t1 = clock64();
-          pf_entries++;
-  #endif
-          // A lone wavefront issues one instruction every four cycles or so, and every LDS lookup on the chain adds ~80: the loop is
-          // written for few instructions and few dependent lookups - the tokens a period or the block still allows are counted down
-          // (no per-token stop conditions), the non-zero-count bucket is looked up again only after a non-zero coefficient, the range
-          // check is one OR per coefficient, and a code whose clusters share one hybrid-integer configuration skips that lookup.
-          uint32_t s_state = JXL_RFL(state), s_nz = JXL_RFL(nzeros), s_k = JXL_RFL(k), s_prev = JXL_RFL(prev), s_epos = JXL_RFL(epos), s_it = JXL_RFL(it);
-          const uint32_t s_cov = JXL_RFL(covered), s_l2 = JXL_RFL(log2c), s_size = JXL_RFL(size), s_histo = JXL_RFL(histo);
-          uint64_t s_buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);
-          int s_n = (int)JXL_RFL(b.n);
-          uint32_t s_rd = JXL_RFL(b.rd), s_rng = 0;
-          const uint32_t la = JXL_RFL(tab.log_alpha), le = 12 - la;
-          const uint32_t left = kTop - (s_it & (kTop - 1)), room = s_size > s_k ? s_size - s_k : 0u;
-          const uint32_t cnt0 = min(left, room);
-          uint32_t cnt = cnt0;
-          uint32_t s_a = s_histo + 2 * JXL_RFL(nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
-          uint32_t s_cidx = 0xFFFFFFFFu, s_cl = 0;
-          if (cnt) do {
-            const uint32_t ks = s_k >> s_l2;
-            const uint32_t fctx = min(ks - 1, min(7 + (ks >> 1), 15 + (ks >> 2)));   // the three-piece position context, without branches
-            // inside a run of zeros the context only moves when the position context does (every second / fourth position from 16 / 32
-            // on): the cluster of the last lookup is kept while the context-map index stays the same
-            const uint32_t cidx = s_a + fctx * 2 + s_prev;
-            if (cidx != s_cidx) { s_cl = JXL_RFL(tab.cmap[cidx]); s_cidx = cidx; }
-            const uint32_t cl = s_cl;
-            const uint32_t res = s_state & 0xFFF, i = res >> le, pos = res & ((1u << le) - 1);
-            const uint64_t e = tab.alias[(cl << la) | i];
-            uint32_t c = cfg_uni;
-            if (__builtin_expect(!cfg_is_uni, 0)) c = JXL_RFL(tab.cfg[cl]);
-            const uint32_t x = JXL_RFL((uint32_t)e), y = JXL_RFL((uint32_t)(e >> 32));
-            const bool gt = pos >= (x & 0xFF);
-            const uint32_t sym = gt ? ((x >> 8) & 0xFF) : i;
-            const uint32_t off = gt ? (y & 0xFFFF) + pos : pos;
-            const uint32_t freq = gt ? ((x >> 16) ^ (y >> 16)) : (x >> 16);
-            s_state = freq * (s_state >> 12) + off;
-            if (s_state < 65536u) {
-              if (s_n <= 32) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRing - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
-              s_state = (s_state << 16) | ((uint32_t)s_buf & 0xFFFFu);
-              s_buf >>= 16; s_n -= 16;
-            }
-            uint32_t u = sym;
-            const uint32_t se = c & 0xF, split = 1u << se;
-            if (__builtin_expect(sym >= split, 0)) {
-              const uint32_t msb = (c >> 4) & 0xF, lsb = (c >> 8) & 0xF;
-              const uint32_t nb = se - (msb + lsb) + ((sym - split) >> (msb + lsb)), nbr = nb > 32 ? 32 : nb;
-              if (s_n <= 32) { s_buf |= (uint64_t)JXL_RFL(b.ring[__umul24(s_rd & (kRing - 1), b.rs)]) << s_n; s_n += 32; s_rd++; }
-              const uint32_t bits = (uint32_t)(s_buf & (((uint64_t)1 << nbr) - 1));
-              s_buf >>= nbr; s_n -= (int)nbr;
-              const uint32_t low = sym & ((1u << lsb) - 1), hi = (1u << msb) | ((sym >> lsb) & ((1u << msb) - 1));
-              u = (uint32_t)(((((uint64_t)hi << (nb & 63)) | bits) << lsb) | low);
-            }
-            cnt--;
-            s_prev = 0;
-            if (u) {
-              const int32_t v = UnpackSigned(u);
-              s_rng |= (uint32_t)(v + 0x8000);   // a value outside int16 leaves a bit above bit 15
-              ent[s_epos++] = s_k | (uint32_t)v << 16;
-              s_prev = 1;
-              s_k++;
-              if (--s_nz == 0) break;
-              s_a = s_histo + 2 * JXL_RFL(nnz_tab[(s_nz + s_cov - 1) >> s_l2]);
-            } else {
-              s_k++;
-            }
-          } while (cnt);
-          s_it += cnt0 - cnt;
-  #ifdef JXLHIP_PROFILE_HF
-          pf_scalar += clock64() - pf_t1;
-          pf_tokens += cnt0 - cnt;
-  #endif
-          uint32_t s_err = s_rng > 0xFFFFu ? (uint32_t)kErrRange : 0u;
-          if (s_nz != 0 && s_k >= s_size) s_err |= kErrBitstream;
-  #undef JXL_RFL
-          state = s_state; nzeros = s_nz; k = s_k; prev = s_prev; epos = s_epos; it = s_it;
-          b.buf = s_buf; b.n = s_n; b.rd = s_rd;
-          err |= s_err;
-          if (s_nz == 0 && !s_err) { want_nz = true; ci++; }
-          continue;
-        }
-        for (;;) {
-          const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-          const uint32_t ks = k >> log2c;
-          const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
-          const uint32_t u = AnsGet(b, state, tab, histo + ((uint32_t)nnz_tab[nzl] + fctx) * 2 + prev);
-          it++;
-          bool leave = false;
-          if (u) {
-            const int32_t v = UnpackSigned(u);
-            if (v != (int32_t)(int16_t)v) err |= kErrRange;
-            ent[epos++] = k | (uint32_t)v << 16;
-            prev = 1;
-            if (--nzeros == 0) { want_nz = true; ci++; leave = true; }
-          } else {
-            prev = 0;
-          }
-          if (++k >= size && nzeros != 0) { err |= kErrBitstream; leave = true; }
-          if (__any(leave) || (it & (kTop - 1)) == 0) break;
-        }
-        continue;
-      }
-  #ifdef JXLHIP_PROFILE_HF
-      const uint64_t pf_t2 = clock64();
-      pf_general_n++;
-  #endif
-      if (want_nz && ci >= 3) {
-        if (bi >= nblk) break;
-        const uint32_t d = dq[__umul24(bi & dqmask, nslots)];
-        bi++;
-        bx = d & 31; by = (d >> 5) & 31;
-        lcx = (d >> 10) & 7;
-        const uint32_t lcy = (d >> 13) & 7;
-        ctxs = d >> 16;
-        log2c = lcx + lcy; covered = 1u << log2c; size = covered << 6;
-        cell = __umul24(by, w8) + bx;
-        ci = 0;
-      }
-      const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-      uint32_t ctx;
-      if (want_nz) {
-        JXL_LDS uint8_t* const cc = col + __umul24(c * 32, nslots);
-        uint32_t predicted;
-        if (bx == 0) predicted = by == 0 ? 32u : (uint32_t)cc[0];
-        else if (by == 0) predicted = cc[__umul24(bx - 1, nslots)];
-        else predicted = ((uint32_t)cc[__umul24(bx, nslots)] + cc[__umul24(bx - 1, nslots)] + 1) >> 1;
-        const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
-        uint32_t nzc = predicted >= 64 ? 64 : predicted;
-        nzc = nzc < 8 ? nzc : 4 + nzc / 2;
-        ctx = ctx_offset + nzc * nbc + block_ctx;
-      } else {
-        const uint32_t nzl = (nzeros + covered - 1) >> log2c;
-        const uint32_t ks = k >> log2c;
-        const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
-        ctx = histo + ((uint32_t)nnz_tab[nzl] + fctx) * 2 + prev;
-      }
-      const uint32_t u = AnsGet(b, state, tab, ctx);
-      it++;
-      if (want_nz) {
-        nzeros = u;
-        if (nzeros + covered > size) { err |= kErrBitstream; break; }
-        const uint8_t fill = (uint8_t)((nzeros + covered - 1) >> log2c);
-        JXL_LDS uint8_t* const cc = col + __umul24(c * 32 + bx, nslots);
-        for (uint32_t ix = 0; ix < (1u << lcx); ix++) cc[__umul24(ix, nslots)] = fill;
-        U2 rec;
-        rec.x = epos; rec.y = nzeros;
-        cblk[(size_t)c * ncells + cell] = rec;
-        if (nzeros) {
-          const uint32_t block_ctx = (ctxs >> (5 * ci)) & 31;
-          histo = ctx_offset + nbc * 37 + 458 * block_ctx;
-          prev = nzeros > size / 16 ? 0 : 1;
-          k = covered;
-          want_nz = false;
-        } else {
-          ci++;
-        }
-      } else {
-        if (u) {
-          const int32_t v = UnpackSigned(u);
-          if (v != (int32_t)(int16_t)v) err |= kErrRange;
-          ent[epos++] = k | (uint32_t)v << 16;
-          prev = 1;
-          if (--nzeros == 0) { want_nz = true; ci++; }
-        } else {
-          prev = 0;
-        }
-        if (++k >= size && nzeros != 0) { err |= kErrBitstream; break; }
-      }
-  #ifdef JXLHIP_PROFILE_HF
-      pf_general += clock64() - pf_t2;
-  #endif
-    }
-  }
-  if (!err && (state != 0x130000u || b.slow_err)) err |= kErrBitstream;
-  const uint64_t used = b.Consumed();
-  if (!err && sec_bits + used > (im.sec_off[sec] + im.sec_size[sec]) * 8) err |= kErrBitstream;
-  im.grp_bitpos[g] = err ? ~(uint64_t)0 : sec_bits + used;
-#ifdef JXLHIP_PROFILE_HF
-  if (per_wave == 1)
-    printf("[hfprof] g %d total %llu scalar-loop %llu (%llu entries, %llu tokens) period %llu (%llu periods) blocks %u general %llu (%llu iterations)\n", g,
-           (unsigned long long)(clock64() - pf_start), (unsigned long long)pf_scalar, (unsigned long long)pf_entries,
-           (unsigned long long)pf_tokens, (unsigned long long)pf_period, (unsigned long long)pf_periods, nblk,
-           (unsigned long long)pf_general, (unsigned long long)pf_general_n);
-#endif
+  for (int i = 0; i < kHfQ; i++) q.pend[i] = 0u;
+  L.ent = G(im.centries) + (size_t)(g - im.centries_g0) * kGroupEntriesCap;
+  L.ncells = (uint32_t)im.w8 * (uint32_t)im.h8;
+  L.cblk = (JXL_GLB U2*)G(im.cblk) + (size_t)(gy * kGroupBlocks) * im.w8 + (size_t)gx * kGroupBlocks;
+  L.w8 = (uint32_t)im.w8;
+  HfState t;
+  t.bx = 0; t.by = 0; t.lcx = 0; t.log2c = 0; t.covered = 1; t.size = 64; t.ctxs = 0; t.cell = 0;
+  t.ci = 3;
+  t.nzeros = 0; t.k = 0; t.prev = 0; t.histo = 0;
+  t.want_nz = true;
+  t.epos = 0;
+  uint32_t it = 0;
+  HfProfile pf;
+  if (per_wave > 1 && !L.tab.slow) HfBatchedLoop(L, b, state, q, t, it, err, pf);
+  else HfGeneralLoop(L, b, state, q, t, it, err, per_wave == 1 && !L.tab.slow, pf);
+  if (!err && !SectionEndOk(im, b, state, sec_bits, sec)) err |= kErrBitstream;
+  im.grp_bitpos[g] = err ? ~(uint64_t)0 : sec_bits + b.Consumed();
+  pf.Print(g, nblk, per_wave);
   if (err) SetError(im, err, 3, g);
 }
 
@@ -1939,9 +1977,7 @@ __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, con
   if (redo && desc->kind != kChanRedo) return;
   const uint64_t start = im.alpha_bitpos[g];
   if (start == ~(uint64_t)0) {   // the HF decoder already reported the failure
-    ChanDesc d;
-    d.kind = kChanFinal; d.value = 0; d.pad0 = 0; d.pad1 = 0;
-    *desc = d;
+    *desc = FinalChan();
     return;
   }
   const int gx = g % im.xg, gy = g / im.xg;
@@ -1962,13 +1998,10 @@ __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, con
     DecodeChannelLane<kLds, false, kGeneric>(b, state, mt.tab, mt.tree, 0, sid, gw, gh, im.alpha32 + (size_t)y0 * im.w + x0, im.w, desc,
                             im.wp_grp ? im.wp_grp + (size_t)g * im.wp_grp_ints : nullptr, nullptr, nullptr, &nar);
     if (nar.redo) return;   // (stopped in mid-stream: nothing to check yet)
-    if (state != 0x130000u || b.slow_err) err |= kErrBitstream;
-    if (start + b.Consumed() > (im.sec_off[sec] + im.sec_size[sec]) * 8) err |= kErrBitstream;
+    if (!SectionEndOk(im, b, state, start, sec)) err |= kErrBitstream;
   }
   if (err) {
-    ChanDesc d;
-    d.kind = kChanFinal; d.value = 0; d.pad0 = 0; d.pad1 = 0;
-    *desc = d;
+    *desc = FinalChan();
     SetError(im, err, 4, g);
   }
 }
@@ -2359,12 +2392,10 @@ __global__ __launch_bounds__(64) void modular_ans_kernel(const DevImage* imgs, c
                                     (wps && wp_local && r.w <= rb_width) ? wp_local : wps, rb_width ? &rows : nullptr, kUni ? &uni : nullptr);
       sub++;
     }
-    if (state != 0x130000u || b.slow_err) err |= kErrBitstream;
-    if (!im.single && start + b.Consumed() > (im.sec_off[sec] + im.sec_size[sec]) * 8) err |= kErrBitstream;
+    if (!SectionEndOk(im, b, state, start, sec, !im.single)) err |= kErrBitstream;   // (one stream: the sections have no ends of their own)
   }
   if (err) {
-    ChanDesc d;
-    d.kind = kChanFinal; d.value = 0; d.pad0 = 0; d.pad1 = 0;
+    const ChanDesc d = FinalChan();
     for (int k = 0; k < nsub; k++)
       for (int c = 0; c < im.mod_ncoded; c++) im.mod_desc[(size_t)(s0 + k) * im.mod_ncoded + c] = d;
     SetError(im, err);
@@ -2547,13 +2578,12 @@ void LaunchHfBlockList(const DevImage* imgs, int nimg, int max_groups, hipStream
 void LaunchHfDecode(const DevImage* imgs, const SectionTask* tasks, int nwg, int threads, int lane_stride, size_t lds_bytes, size_t lane_bytes,
                     hipStream_t s) {
   if (nwg <= 0) return;   // lds_bytes: tables + lanes of the largest workgroup; lane_bytes: the lanes alone (tables in global memory)
-  // one window size: kHfRingWords (a 16-word variant paid off while the coefficient orders lived in LDS; not any more)
   if (lds_bytes) {
-    RaiseLds((const void*)hf_decode_kernel<true, kHfRingWords>, lds_bytes);
-    hipLaunchKernelGGL((hf_decode_kernel<true, kHfRingWords>), dim3(nwg), dim3(threads), lds_bytes, s, imgs, tasks, lane_stride);
+    RaiseLds((const void*)hf_decode_kernel<true>, lds_bytes);
+    hipLaunchKernelGGL((hf_decode_kernel<true>), dim3(nwg), dim3(threads), lds_bytes, s, imgs, tasks, lane_stride);
   } else {
-    RaiseLds((const void*)hf_decode_kernel<false, kHfRingWords>, lane_bytes);
-    hipLaunchKernelGGL((hf_decode_kernel<false, kHfRingWords>), dim3(nwg), dim3(threads), lane_bytes, s, imgs, tasks, lane_stride);
+    RaiseLds((const void*)hf_decode_kernel<false>, lane_bytes);
+    hipLaunchKernelGGL((hf_decode_kernel<false>), dim3(nwg), dim3(threads), lane_bytes, s, imgs, tasks, lane_stride);
   }
 }
 

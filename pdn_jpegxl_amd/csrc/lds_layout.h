@@ -13,7 +13,7 @@ namespace jxlhip {
 #define JXL_LAYOUT __host__ __device__ __forceinline__
 
 constexpr int kRingWords = 32;       // words of a lane's bit window in the LF, alpha and Modular decoders (LaneBits)
-constexpr int kHfRingWords = 32;     // ... and in the HF decoder (hf_decode_kernel's kRing)
+constexpr int kHfRingWords = 32;     // ... and in the HF decoder (one size: a 16-word variant paid off only while the coefficient orders lived in LDS)
 constexpr int kModWindowLanes = 64;  // modular_ans_kernel lays its bit windows out for a whole wavefront whatever `lanes` is
 constexpr int kNzColBytes = 96;      // HF decoder, per lane: non-zero counts of 32 columns x 3 channels
 constexpr int kNnzCtxBytes = 64;     // HF decoder: the LDS copy of d_nnz_ctx
@@ -89,18 +89,18 @@ JXL_LAYOUT size_t ModularLdsBytes(int lanes, int rb_width, int wp_lds, bool unif
 }
 
 // ---- hf_decode_kernel: bit windows | descriptor queues | non-zero columns (each for `nslots` lanes) | code | non-zero contexts
-__host__ __device__ constexpr int HfQueueDepth(int ring_words) { return ring_words / 4; }   // hf_decode_kernel's kQ: a lane queues 2 * kQ varblock descriptors
+constexpr int kHfQueueDepth = kHfRingWords / 4;   // hf_decode_kernel: a lane queues 2 * kHfQueueDepth varblock descriptors
 JXL_LAYOUT int HfSlots(int sections) { return (sections + 3) & ~3; }   // lanes a task's arrays are laid out for
 struct HfLds {
   size_t ring, descq, nzcol, tables;   // tables: the lanes' bytes alone
-  JXL_LAYOUT HfLds(int nslots, int ring_words) {
+  JXL_LAYOUT explicit HfLds(int nslots) {
     ring = 0;
-    descq = ring + (size_t)nslots * ring_words * 4;
-    nzcol = descq + (size_t)nslots * 2 * HfQueueDepth(ring_words) * 4;
+    descq = ring + (size_t)nslots * kHfRingWords * 4;
+    nzcol = descq + (size_t)nslots * 2 * kHfQueueDepth * 4;
     tables = nzcol + (size_t)nslots * kNzColBytes;
   }
 };
-JXL_LAYOUT size_t HfLaneBytes(int nslots) { return HfLds(nslots, kHfRingWords).tables; }
+JXL_LAYOUT size_t HfLaneBytes(int nslots) { return HfLds(nslots).tables; }
 JXL_LAYOUT size_t HfTablesEnd(size_t off, const CodeShape& s) { return CodeLds(off, s).end + kNnzCtxBytes; }
 JXL_LAYOUT size_t HfTablesBytes(const CodeShape& s) { return CodeLdsBytes(s) + kNnzCtxBytes + kHfTailAllowance; }
 // what the lane-stride heuristic takes for a workgroup's LDS: the tables (without the tail allowance) and four lanes

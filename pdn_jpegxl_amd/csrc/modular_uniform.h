@@ -98,8 +98,7 @@ struct UniCtx {
   int w, h, stride, rw, w2, chan, sid;
   JXL_GLB int32_t* out;
   JXL_LDS int32_t *rows, *werr, *wpe;
-  JXL_LDS uint32_t* ring;
-  uint32_t ring_rs, la, le;
+  uint32_t la, le;
   const JXL_LDS uint64_t* alias;
   const JXL_LDS uint8_t* cmap;
   const JXL_LDS uint32_t* cfg;
@@ -123,23 +122,16 @@ struct UniCtx {
   int32_t vleaf0, vleaf1, vleaf2;       // grids of at most 64 cells: the leaf record of cell `lane` (packed word, multiplier, offset)
   const JXL_LDS U4* grid;
   // stream state
-  uint32_t s_state, s_rd;
-  uint64_t s_buf;
-  int s_n;
+  uint32_t s_state;
+  ScalarBits sb;
 };
 
 template <bool kWp, int kPred>
 __device__ __forceinline__ void UniRows(UniCtx& c, LaneBits& b) {
   const int lane = (int)(threadIdx.x & 63);
   const int w = c.w, h = c.h, rw = c.rw, w2 = c.w2;
-  uint32_t s_state = c.s_state, s_rd = c.s_rd;
-  uint64_t s_buf = c.s_buf;
-  int s_n = c.s_n;
-  JXL_LDS uint32_t* const ring = c.ring;
-  const uint32_t ring_rs = c.ring_rs;
-  auto word = [&]() {
-    if (__builtin_expect(s_n <= 32, 0)) { s_buf |= (uint64_t)JXL_RFL(ring[__umul24(s_rd & (kRingWords - 1), ring_rs)]) << s_n; s_n += 32; s_rd++; }
-  };
+  uint32_t s_state = c.s_state;
+  ScalarBits sb = c.sb;
   bool big = false;   // a sample (or an error of the weighted predictor) beyond the bound of the 32-bit forms has been seen
   // Weighted predictor, 32-bit form: its four sub-predictors are four lanes (lane & 3; every quad computes the same).  Per lane: the
   // coefficients of ITS prediction over (W, N, NE) and over the true errors (West, N, NW, NE) - the format's four formulas as one -
@@ -194,8 +186,7 @@ __device__ __forceinline__ void UniRows(UniCtx& c, LaneBits& b) {
         prev9 = 0;
       }
       for (int p0 = 0; p0 < cnt; p0 += kTopUpEvery) {
-        b.rd = s_rd;
-        b.TopUp();
+        sb.TopUp(b);
         const int pe = min(cnt, p0 + kTopUpEvery);
         for (int li = p0; li < pe; li++) {
           const int x = x0 + li;
@@ -370,33 +361,9 @@ __device__ __forceinline__ void UniRows(UniCtx& c, LaneBits& b) {
             default: guess = 0; break;
           }
           // ---- token
-          const uint32_t res = s_state & 0xFFF, ai = res >> c.le, pos = res & ((1u << c.le) - 1);
-          const uint64_t ae = c.alias[(l_cl << c.la) | ai];
-          const uint32_t ax = JXL_RFL((uint32_t)ae), ay = JXL_RFL((uint32_t)(ae >> 32));
-          const uint32_t cf = l_cfg;
-          const bool gtc = pos >= (ax & 0xFF);
-          const uint32_t sym = gtc ? ((ax >> 8) & 0xFF) : ai;
-          const uint32_t aoff = gtc ? (ay & 0xFFFF) + pos : pos;
-          const uint32_t freq = gtc ? ((ax >> 16) ^ (ay >> 16)) : (ax >> 16);
-          s_state = freq * (s_state >> 12) + aoff;
-          if (__builtin_expect(s_state < 65536u, 0)) {
-            word();
-            s_state = (s_state << 16) | ((uint32_t)s_buf & 0xFFFFu);
-            s_buf >>= 16; s_n -= 16;
-          }
-          uint32_t u = sym;
-          {
-            const uint32_t se = cf & 0xF, split = 1u << se;
-            if (__builtin_expect(sym >= split, 0)) {
-              const uint32_t msb = (cf >> 4) & 0xF, lsb = (cf >> 8) & 0xF;
-              const uint32_t nb = se - (msb + lsb) + ((sym - split) >> (msb + lsb)), nbr = nb > 32 ? 32 : nb;
-              word();
-              const uint32_t bits = (uint32_t)(s_buf & (((uint64_t)1 << nbr) - 1));
-              s_buf >>= nbr; s_n -= (int)nbr;
-              const uint32_t low = sym & ((1u << lsb) - 1), top = (1u << msb) | ((sym >> lsb) & ((1u << msb) - 1));
-              u = (uint32_t)(((((uint64_t)top << (nb & 63)) | bits) << lsb) | low);
-            }
-          }
+          const uint64_t ae = c.alias[(l_cl << c.la) | AnsBucket(s_state, c.le)];
+          const uint32_t sym = AnsStep<false, true>(sb, s_state, JXL_RFL((uint32_t)ae), JXL_RFL((uint32_t)(ae >> 32)), c.le);
+          const uint32_t u = HybridTail(sb, l_cfg, sym);
           const int32_t val = (int32_t)((int64_t)UnpackSigned(u) * (int64_t)l_mul + l_off + guess);
           vout = UWriteLane(val, (uint32_t)li, vout);
           if constexpr (kWp) {
@@ -448,7 +415,7 @@ __device__ __forceinline__ void UniRows(UniCtx& c, LaneBits& b) {
       __builtin_amdgcn_wave_barrier();
     }
   }
-  c.s_state = s_state; c.s_rd = s_rd; c.s_buf = s_buf; c.s_n = s_n;
+  c.s_state = s_state; c.sb = sb;
 }
 
 // Returns false when the channel has to take the old path (general symbol reader, rows wider than the LDS rows).
@@ -471,8 +438,6 @@ __device__ __forceinline__ bool ModularChannelUniform(LaneBits& b, uint32_t& sta
   c.cfg = UniPtrLds((JXL_LDS uint32_t*)tab_in.cfg);
   c.alias = UniPtrLds((JXL_LDS uint64_t*)tab_in.alias);
   const DevCode* const dc = UniPtr64(tab_in.dc);
-  c.ring = UniPtrLds(b.ring);
-  c.ring_rs = JXL_RFL(b.rs);
   const int w = c.w, h = c.h, chan = c.chan, sid = c.sid;
   if (JXL_RFL(tab_in.slow) || w > c.rw || w <= 0 || h <= 0 || (use_wp && !lds_wp)) return false;
   const int lane = (int)(threadIdx.x & 63);
@@ -657,9 +622,9 @@ __device__ __forceinline__ bool ModularChannelUniform(LaneBits& b, uint32_t& sta
   c.cfg_in_lanes = ncl <= 64;
   if (use_wp) for (int i = lane; i < kWpStateInts * c.w2; i += 64) lds_wp[i] = 0;
   // the stream state in scalar registers
-  c.s_state = JXL_RFL(state_io); c.s_rd = JXL_RFL(b.rd);
-  c.s_buf = ((uint64_t)JXL_RFL((uint32_t)(b.buf >> 32)) << 32) | JXL_RFL((uint32_t)b.buf);
-  c.s_n = (int)JXL_RFL(b.n);
+  c.s_state = JXL_RFL(state_io);
+  c.sb.Load(b);
+  c.sb.ring = UniPtrLds(b.ring); c.sb.rs = JXL_RFL(b.rs);   // (every lane plays lane 0 here: the window's address is uniform too)
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   // the row loops, specialised for what a channel's leaves usually share (everything else: the generic instance)
@@ -670,6 +635,7 @@ __device__ __forceinline__ bool ModularChannelUniform(LaneBits& b, uint32_t& sta
     if (all_pred == 5) UniRows<false, 5>(c, b);
     else UniRows<false, -1>(c, b);
   }
-  state_io = c.s_state; b.buf = c.s_buf; b.n = c.s_n; b.rd = c.s_rd;
+  state_io = c.s_state;
+  c.sb.Store(b);
   return true;
 }

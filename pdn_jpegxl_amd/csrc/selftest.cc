@@ -204,6 +204,11 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_headers_icc(uint32_t xsize, 
 extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_reflect(int32_t v, int32_t n) { return ReflectIndex(v, n); }
 
 extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_nnz_ctx(uint32_t nzl) { return NnzBucketCtx(nzl); }
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_hf_pos_ctx(uint32_t ks) { return HfPosCtx(ks); }
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_hf_nnz_predict(uint32_t bx, uint32_t by, uint32_t above, uint32_t left) {
+  return HfNnzPredict(bx, by, above, left);
+}
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_hf_nnz_bucket(uint32_t predicted) { return HfNnzCountBucket(predicted); }
 
 // An entropy-coded stream of n (context, value) tokens over num_ctx contexts, as the encoder writes its host-side streams (code header
 // by BuildAndWriteCode, tokens by WriteTokensHost): the CPU and GPU tests write patch dictionaries with it.  Writes the bytes into dst
@@ -385,7 +390,7 @@ extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_lds_layout(int32_t kind, co
     put(ModularLds((int)in[0], (int)in[1], (int)in[2], false).tables);
   } else if (kind == 4) {
     const int nslots = HfSlots((int)in[0]);
-    const HfLds l(nslots, kHfRingWords);
+    const HfLds l(nslots);
     const CodeLds c(l.tables, shape(1));
     put(l.ring); put(l.descq); put(l.nzcol); put_code(c); put(c.end); put(HfTablesEnd(l.tables, shape(1)));
     put(HfTablesBytes(shape(1)) + HfLaneBytes(nslots)); put(HfLaneBytes(nslots)); put((size_t)nslots);
