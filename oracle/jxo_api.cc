@@ -99,6 +99,11 @@ void jxo_set_next_flags(uint32_t flags) { g_next_flags = flags; }
 static thread_local SideInfo g_next_side;
 void jxo_set_next_side_info(const SideInfo* s) { g_next_side = *s; }
 size_t jxo_side_info_size() { return sizeof(SideInfo); }
+// Explicit MA tree of the next jxo_encode call (EncodeParams::tree): role 0 lossless frame, 1 alpha of a lossy frame, 2 its LF channels
+static thread_local std::vector<int32_t> g_next_tree[3];
+void jxo_set_next_tree(const int32_t* nodes, size_t n, int role) {
+  if (role >= 0 && role < 3) g_next_tree[role].assign(nodes, nodes + 7 * n);
+}
 void jxo_set_next_animation(int frames) { g_next_frames = frames; }
 void jxo_set_next_icc(const uint8_t* icc, size_t size, int cmyk) {
   g_next_icc.assign(icc ? icc : nullptr, icc ? icc + size : nullptr);
@@ -148,6 +153,7 @@ JxoBytes* jxo_encode(const uint8_t* px, uint32_t w, uint32_t h, int32_t nch, con
     p.premultiplied_alpha = (g_next_flags & 512) != 0;
     p.num_passes = (g_next_flags & 16) ? 3 : ((g_next_flags & 8) ? 2 : 1);
     p.side = g_next_side; g_next_side = SideInfo();
+    for (int r = 0; r < 3; r++) { p.tree[r].swap(g_next_tree[r]); g_next_tree[r].clear(); }
     const uint32_t g_next_flags_entropy = g_next_flags;
     g_next_flags = 0;
     JxoBytes* b = new JxoBytes();

@@ -86,6 +86,11 @@ uint32_t SideInfoHash(uint32_t seed, uint32_t x, uint32_t y, uint32_t k);
 
 struct EncodeParams {
   SideInfo side;
+  // Explicit MA trees (parity-test coverage; empty: the writer's own).  7 ints per node - property (or -1 for a leaf), split value, child taken when
+  // property > split value, the other child, predictor, offset, multiplier - linked by index, node 0 the root, children after their parent.
+  // [0]: the whole tree of a lossless frame; [1]: what a lossy frame's alpha channel is coded with (in place of both alpha leaves of the
+  // frame's tree); [2]: what each of the three LF channels is coded with (in place of their leaves, below the tree's channel splits)
+  std::vector<int32_t> tree[3];
   float distance = 1.0f;
   bool lossless = false;
   int effort = 7;

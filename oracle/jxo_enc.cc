@@ -42,13 +42,38 @@ struct TreeBuilder {
   }
 };
 
-Tree MakeVarDctTree(uint32_t nlf, const SideInfo& side) {
+// Appends a caller-supplied tree (EncodeParams::tree) to `b`; returns the index of its root.
+int AppendUserTree(TreeBuilder& b, const std::vector<int32_t>& nodes) {
+  JXO_CHECK(!nodes.empty() && nodes.size() % 7 == 0, "explicit tree: 7 ints per node");
+  const int n = (int)(nodes.size() / 7), base = (int)b.t.size();
+  for (int i = 0; i < n; i++) {
+    const int32_t* v = &nodes[(size_t)i * 7];
+    TreeNode t;
+    t.property = v[0];
+    JXO_CHECK(t.property >= -1 && t.property < kNumNonrefProps, "explicit tree: property");
+    if (t.property >= 0) {
+      JXO_CHECK(v[2] > i && v[2] < n && v[3] > i && v[3] < n, "explicit tree: children follow their parent");
+      t.splitval = v[1]; t.lchild = base + v[2]; t.rchild = base + v[3];
+    } else {
+      JXO_CHECK(v[4] >= 0 && v[4] < 14, "explicit tree: predictor");
+      JXO_CHECK(v[6] >= 1, "explicit tree: multiplier");
+      t.predictor = v[4]; t.offset = v[5]; t.multiplier = (uint32_t)v[6];
+      const uint32_t ml = (uint32_t)__builtin_ctz(t.multiplier);
+      JXO_CHECK(ml < 31 && (t.multiplier >> ml) < (1u << (31 - ml)), "explicit tree: multiplier not (bits + 1) << log");
+    }
+    b.t.push_back(t);
+  }
+  return base;
+}
+
+Tree MakeVarDctTree(uint32_t nlf, const SideInfo& side, const std::vector<int32_t>& alpha_tree, const std::vector<int32_t>& lf_tree) {
   TreeBuilder b;
   // alpha: one gradient-predicted context (extra local-gradient contexts bought < 0.01 % on the synthetic masks and
   // cost a tree walk per sample in every decoder)
-  int alpha = b.Leaf(5);
+  int alpha = alpha_tree.empty() ? b.Leaf(5) : AppendUserTree(b, alpha_tree);
   // LF coefficients
-  int lf_b = b.Leaf(5), lf_x = b.Leaf(5), lf_y = b.Leaf(5);
+  auto lf_leaf = [&]() { return lf_tree.empty() ? b.Leaf(5) : AppendUserTree(b, lf_tree); };
+  int lf_b = lf_leaf(), lf_x = lf_leaf(), lf_y = lf_leaf();
   int lf1 = b.Split(0, 0, lf_x, lf_y);
   int lfn = b.Split(0, 1, lf_b, lf1);
   // HF metadata
@@ -61,7 +86,7 @@ Tree MakeVarDctTree(uint32_t nlf, const SideInfo& side) {
   int binfo = b.Split(2, 0, qrow, srow);
   int m1 = b.Split(0, 1, binfo, cfl);
   int meta = b.Split(0, 2, sharp, m1);
-  int a_global = b.Leaf(5);                       // alpha coded in the GlobalModular section (stream 0)
+  int a_global = alpha_tree.empty() ? b.Leaf(5) : AppendUserTree(b, alpha_tree);   // alpha coded in the GlobalModular section (stream 0)
   int n2 = b.Split(1, 0, lfn, a_global);
   int n1 = b.Split(1, (int32_t)(2 * nlf), meta, n2);
   int root = b.Split(1, (int32_t)(3 * nlf + kNumQuantTables), alpha, n1);
@@ -460,7 +485,7 @@ struct VarDctEncoder {
     });
     // 5. tokens
     const uint32_t nlf = f.num_lf_groups, ng = f.num_groups;
-    Tree tree = MakeVarDctTree(nlf, p.side);
+    Tree tree = MakeVarDctTree(nlf, p.side, p.tree[1], p.tree[2]);
     WPHeader wp_default;
     const uint32_t np = (uint32_t)std::max(1, std::min(3, p.num_passes));
     f.num_passes = np;
@@ -793,7 +818,13 @@ std::vector<uint8_t> EncodeLosslessFrame(const ImageMetadata& m, FrameHeader& f,
     ForwardSqueeze(full, sp);
   }
   gh_global.transforms = full.transforms;
-  Tree tree = MakeLosslessTree(p.lossless_predictor, p.lossless_tree);
+  Tree tree;
+  if (p.tree[0].empty()) {
+    tree = MakeLosslessTree(p.lossless_predictor, p.lossless_tree);
+  } else {
+    TreeBuilder b;
+    tree = MakeBfsTree(b.t, AppendUserTree(b, p.tree[0]));
+  }
   WPHeader wph;
   const uint32_t nlf = f.num_lf_groups, ng = f.num_groups;
   const int gd = f.group_dim;

@@ -80,7 +80,7 @@ void ModularDecode(BitReader& br, ModularImage& img, GroupHeader* header_out, ui
                    const Tree* global_tree, const EntropyCode* global_code);
 
 // ------------------------------------------------------------------ encoder helpers
-// Tokenises channel `chan` of img against `tree` (multiplier 1, offset 0 leaves only).
+// Tokenises channel `chan` of img against `tree`; throws when a residual is not a multiple of its leaf's multiplier.
 void TokenizeChannel(const Tree& tree, const WPHeader& wp, const ModularImage& img, int chan, uint32_t stream_id,
                      std::vector<Token>& out);
 void TokenizeTree(const Tree& tree, std::vector<Token>& out);

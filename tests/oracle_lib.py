@@ -142,10 +142,13 @@ class OracleError(RuntimeError):
 def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, seed=1, epf_iters=-1, gaborish=True,
            container=True, adaptive_lf_smoothing=True, lossless_predictor=6, lossless_squeeze=False, num_threads=8, exif=None,
            xmp=None, lossless_tree=0, bits=8, orientation=1, float_samples=0, colour=0, icc=None, cmyk=False, animation_frames=1, custom_quant_tables=False, prefix_codes=False, lz77=False, num_passes=1, custom_orders=False, lf_contexts=False, palette=False, mislabel_afv=False,
-           premultiplied_alpha=False, side_info=None):
+           premultiplied_alpha=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None):
     """px: uint8 array (h, w, nch) with nch in 1..4 (Gray, GrayA, RGB, RGBA); with bits > 8 (up to 16) a uint16 array whose
     samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes.
-    side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters)."""
+    side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters).
+    tree / alpha_tree / lf_tree: an explicit MA tree for a lossless frame / for the alpha channel / for each LF channel of a lossy frame:
+    a list of nodes (property or -1, split value, child for property > split value, other child, predictor, offset, multiplier), node 0
+    the root, children after their parent (oracle/jxo_codec.h: EncodeParams::tree)."""
     L = lib()
     if float_samples:
         px = np.ascontiguousarray(px, dtype=np.float16 if float_samples == 16 else np.float32)
@@ -165,6 +168,11 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
         L.jxo_side_info_size.restype = C.c_size_t
         assert L.jxo_side_info_size() == C.sizeof(SideInfo), "SideInfo: the ctypes mirror and jxo_codec.h disagree"
         L.jxo_set_next_side_info(C.byref(make_side_info(**side_info)))
+    for role, nodes in enumerate((tree, alpha_tree, lf_tree)):
+        if nodes is not None:
+            flat = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 7)
+            L.jxo_set_next_tree.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+            L.jxo_set_next_tree(flat.ctypes.data, len(flat), role)
     if animation_frames > 1:
         L.jxo_set_next_animation.argtypes = [C.c_int]
         L.jxo_set_next_animation(animation_frames)
