@@ -497,14 +497,14 @@ __global__ __launch_bounds__(256) void enc_lf_tokens_kernel(EncImage im) {
     const int c = mc == 0 ? 1 : (mc == 1 ? 0 : 2);   // modular channel order Y, X, B
     const int32_t* pl = im.lfq[c] + (size_t)by0 * im.w8 + bx0;
     const int32_t v = pl[(size_t)y * im.w8 + x];
-    int32_t W, N, NW;
+    int32_t W, N, NW;   // (ModularWNNWAt written out: through the helper this kernel took one more register)
     if (x == 0) { W = y ? pl[(size_t)(y - 1) * im.w8] : 0; N = W; NW = W; }
     else {
       W = pl[(size_t)y * im.w8 + x - 1];
       N = y ? pl[(size_t)(y - 1) * im.w8 + x] : W;
       NW = y ? pl[(size_t)(y - 1) * im.w8 + x - 1] : W;
     }
-    const uint32_t val = PackSignedD(v - GradientPred(W, N, NW));
+    const uint32_t val = PackSigned(v - ModularPredictWNNW(5, W, N, NW));
     DevToken t;
     t.ctx = mc == 0 ? kLeafLfY : (mc == 1 ? kLeafLfX : kLeafLfB);
     t.value = val;
@@ -562,7 +562,7 @@ __global__ __launch_bounds__(1024) void enc_meta_tokens_kernel(EncImage im) {
     DevToken t;
     if (with_strategies) {
       t.ctx = kLeafStrategy;
-      t.value = PackSignedD(strategy);
+      t.value = PackSigned(strategy);
       out[idx] = t;
       HybridD(t.value, &tok, &nb, &bits);
       atomicAdd(&s_hs[tok], 1u);
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(1024) void enc_meta_tokens_kernel(EncImage im) {
       W = im.rawq[cell_of(kk)] - 1;
     }
     t.ctx = kLeafQf;
-    t.value = PackSignedD(im.rawq[cell] - 1 - W);
+    t.value = PackSigned(im.rawq[cell] - 1 - W);
     out[qbase + idx] = t;
     HybridD(t.value, &tok, &nb, &bits);
     atomicAdd(&s_hq[tok], 1u);
@@ -605,16 +605,10 @@ __global__ __launch_bounds__(256) void enc_alpha_tokens_kernel(EncImage im) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const int y = i / gw, x = i % gw;
     const int32_t v = pl[(size_t)y * im.w + x];
-    int32_t W, N, NW;
-    if (x == 0) { W = y ? pl[(size_t)(y - 1) * im.w] : 0; N = W; NW = W; }
-    else {
-      W = pl[(size_t)y * im.w + x - 1];
-      N = y ? pl[(size_t)(y - 1) * im.w + x] : W;
-      NW = y ? pl[(size_t)(y - 1) * im.w + x - 1] : W;
-    }
+    const ModularWNNW hd = ModularWNNWAt([&](int sx, int sy) { return pl[(size_t)sy * im.w + sx]; }, x, y);
     DevToken t;
     t.ctx = leaf;
-    t.value = PackSignedD(v - GradientPred(W, N, NW));
+    t.value = PackSigned(v - ModularPredictWNNW(5, hd.W, hd.N, hd.NW));
     out[i] = t;
     uint32_t tok, nb, bits;
     HybridD(t.value, &tok, &nb, &bits);
@@ -701,7 +695,7 @@ __global__ __launch_bounds__(256) void enc_ac_tokens_kernel(EncImage im) {
       const uint32_t ks = kk >> log2c;
       const uint32_t fctx = ks < 16 ? ks - 1 : (ks < 32 ? 15 + ((ks - 16) >> 1) : 23 + ((ks - 32) >> 2));
       t.ctx = histo + ((uint32_t)e_nnz_ctx[(nzeros + covered - 1) >> log2c] + fctx) * 2 + prev;
-      t.value = PackSignedD(q);
+      t.value = PackSigned(q);
       out[pos++] = t;
       HybridD(t.value, &tok, &nb, &bits);
       atomicAdd(&im.hist_ac[(size_t)t.ctx * kEncSyms + tok], 1u);
@@ -1057,16 +1051,10 @@ __global__ __launch_bounds__(256) void enc_ll_tokens_kernel(EncImage im) {
     const int c = i / per, r = i % per, y = r / gw, x = r % gw;
     const int32_t* pl = im.ll_plane[c] + (size_t)y0 * im.w + x0;
     const int32_t v = pl[(size_t)y * im.w + x];
-    int32_t W, N, NW;
-    if (x == 0) { W = y ? pl[(size_t)(y - 1) * im.w] : 0; N = W; NW = W; }
-    else {
-      W = pl[(size_t)y * im.w + x - 1];
-      N = y ? pl[(size_t)(y - 1) * im.w + x] : W;
-      NW = y ? pl[(size_t)(y - 1) * im.w + x - 1] : W;
-    }
+    const ModularWNNW hd = ModularWNNWAt([&](int sx, int sy) { return pl[(size_t)sy * im.w + sx]; }, x, y);
     DevToken t;
     t.ctx = 3 - c;
-    t.value = PackSignedD(v - GradientPred(W, N, NW));
+    t.value = PackSigned(v - ModularPredictWNNW(5, hd.W, hd.N, hd.NW));
     out[i] = t;
     uint32_t tok, nb, bits;
     HybridD(t.value, &tok, &nb, &bits);

@@ -22,6 +22,7 @@
 #include "host_write.h"
 #include "icc.h"
 #include "kernels.h"
+#include "modular_rules.h"
 
 namespace jxlhip {
 
@@ -414,18 +415,6 @@ double TokenCost(const uint32_t* h) {
   return bits;
 }
 
-int32_t PredictHost(int pred, int32_t W, int32_t N, int32_t NW) {
-  const int64_t gr = (int64_t)W + N - NW;
-  switch (pred) {
-    case 1: return W;
-    case 2: return N;
-    case 3: return (int32_t)(((int64_t)W + N) / 2);
-    case 4: return std::llabs(gr - W) < std::llabs(gr - N) ? W : N;
-    default: return (int32_t)std::max<int64_t>(std::min(W, N), std::min<int64_t>(std::max(W, N), gr));
-  }
-}
-uint32_t PackSignedHost(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(int64_t)v)) << 1) - 1; }
-
 // An MA tree under construction: nodes point at their children, Flatten puts them in decode (breadth-first) order and numbers the
 // leaves as the decoder will (context id = rank of the leaf in that order).
 struct TreeBuilder {
@@ -603,11 +592,8 @@ std::vector<uint8_t> CodeLosslessSearched(EncImage& im, const EncSource& src, Ar
       out->clear();
       for (int y = 0; y < nch_all; y++)
         for (int x = 0; x < ncol; x++) {
-          const int32_t* row = meta.data() + (size_t)y * ncol;
-          int32_t W, N, NW;
-          if (x == 0) { W = y ? row[-ncol] : 0; N = W; NW = W; }
-          else { W = row[x - 1]; N = y ? row[x - ncol] : W; NW = y ? row[x - ncol - 1] : W; }
-          out->push_back(PackSignedHost(row[x] - PredictHost(p, W, N, NW)));
+          const ModularWNNW hd = ModularWNNWAt([&](int sx, int sy) { return meta[(size_t)sy * ncol + sx]; }, x, y);
+          out->push_back(PackSigned(meta[(size_t)y * ncol + x] - ModularPredictWNNW(p, hd.W, hd.N, hd.NW)));
         }
     };
     std::vector<uint32_t> res, best_res;

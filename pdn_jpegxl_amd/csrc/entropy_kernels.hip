@@ -19,6 +19,7 @@
 #include "dev_util.h"
 #include "kernels.h"
 #include "lds_layout.h"
+#include "modular_rules.h"
 
 namespace jxlhip {
 
@@ -32,7 +33,6 @@ __device__ const uint8_t d_nnz_ctx[64] = {0,   0,   31,  62,  62,  93,  93,  93,
                                           206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206};
 
 __device__ __forceinline__ int CeilLog2D(uint32_t x) { return x <= 1 ? 0 : 32 - __clz(x - 1); }
-__device__ __forceinline__ int32_t UnpackSigned(uint32_t u) { return (int32_t)(u >> 1) ^ -(int32_t)(u & 1); }
 // who: 1 lf_ans, 2 lf_finish, 3 hf_decode, 4 alpha_ans, 5 modular; where: section index (diagnostics: status[2 + who] = where + 1)
 // Wavefront issue priority (s_setprio) of the serial decoders, for tools/ab_prio.sh.  Measured in the pipelined step (round 3):
 // raising it changes nothing (123-125 ms at 0, 1 and 3), so the default emits no instruction.
@@ -310,7 +310,7 @@ __device__ __forceinline__ uint32_t SlowSymbol(Bits& b, uint32_t& state, const C
   const DevCode& dc = *t.dc;
   if (dc.slow & 1) {
     const uint32_t c = t.cfg[cl];
-    if (c & 0x1000) return c >> 16;   // one-symbol code: no bits
+    if (OneSymbolCode(c)) return OneSymbol(c);   // no bits
     b.Refill();
     const uint32_t bits = (uint32_t)b.buf;
     const uint16_t* cnt = dc.pfx_count + cl * 16;
@@ -418,109 +418,34 @@ struct RowBuf {
 template <bool kLds, int kPred>
 __device__ __forceinline__ void LeafRow(LaneBits& b, uint32_t& state, const CodeTab<kLds>& tab, const DevTreeNode& leaf, int w, int y,
                                         JXL_GLB int32_t* row, int stride, typename AS<kLds>::Row rb, int rs, bool use_rb) {
-  const uint32_t cl = tab.cmap[leaf.a >> 8];
+  const uint32_t cl = tab.cmap[LeafContext(leaf)];
   const uint32_t cfg = tab.cfg[cl];
   const typename AS<kLds>::U64 abase = tab.alias + (cl << tab.log_alpha);
-  const bool constant_token = (cfg & 0x1000) && ((cfg >> 16) & 0xFF) < (1u << (cfg & 0xF));
-  const uint32_t const_res = (uint32_t)UnpackSigned((cfg >> 16) & 0xFF) * leaf.b + (uint32_t)leaf.splitval;
+  const bool constant_token = OneSymbolToken(cfg);
+  const uint32_t const_res = LeafResidual(OneSymbol(cfg), leaf.b, (uint32_t)leaf.splitval);
   const JXL_GLB int32_t* prow = row - stride;
-  int32_t W = y ? (use_rb ? rb[0] : prow[0]) : 0, N = W, NW = W;
+  ModularRoll r;
+  r.StartRow(y ? (use_rb ? rb[0] : prow[0]) : 0);
   uint64_t entry = constant_token ? 0 : AnsPrefetch<kLds>(state, abase, tab.log_alpha);
   for (int x = 0; x < w; x++) {
     if ((x & (kTopUpEvery - 1)) == 0) b.TopUp();
-    int32_t NE = N;
-    if (kPred != 0 && kPred != 1) {
-      if (x + 1 < w && y) NE = use_rb ? rb[(x + 1) * rs] : prow[x + 1];
+    int32_t NE = r.N;
+    if (kPred != 0 && kPred != 1) {   // (those two never look at the row above)
+      if (HasNE(x, y, w)) NE = use_rb ? rb[(x + 1) * rs] : prow[x + 1];
     }
-    uint32_t guess;
-    if (kPred == 0) guess = 0;
-    else if (kPred == 1) guess = (uint32_t)W;
-    else if (kPred == 2) guess = (uint32_t)N;
-    else {   // 5: clamped gradient
-      const int64_t mn = W < N ? W : N, mx = W < N ? N : W, gr = (int64_t)W + N - NW;
-      guess = (uint32_t)(int32_t)(gr < mn ? mn : (gr > mx ? mx : gr));
-    }
+    const uint32_t guess = (uint32_t)ModularPredictT<kPred>(r.W, r.N, r.NW, NE, 0, 0, 0, 0);
     uint32_t res;
     if (constant_token) res = const_res;
     else {
       const uint32_t sym = AnsSymPf<kLds>(b, state, abase, tab.log_alpha, entry);
-      res = (uint32_t)UnpackSigned(HybridTail(b, cfg, sym)) * leaf.b + (uint32_t)leaf.splitval;
+      res = LeafResidual(HybridTail(b, cfg, sym), leaf.b, (uint32_t)leaf.splitval);
     }
     const int32_t val = (int32_t)(res + guess);   // low 32 bits of the 64-bit reference arithmetic
     row[x] = val;
     if (use_rb) rb[x * rs] = val;
-    W = val;
-    if (y) { NW = N; N = NE; } else { NW = val; N = val; }
+    r.Step(val, NE, x, y);
   }
 }
-
-// ------------------------------------------------------------------ weighted ("self-correcting") predictor, default parameters
-// Per-channel state in a lane-private global scratch: the true error and the four sub-predictor errors of the current
-// and the previous row ((w + 2) entries each), exactly as the format defines them.
-struct WpState {
-  int32_t* err;                // [2][w + 2]   (generic pointers: the scratch is LDS when it fits, global memory otherwise)
-  uint32_t* pe;                // [4][2][w + 2]
-  int w2;                      // w + 2
-  int64_t prediction[4];
-  int64_t pred;
-  __device__ void Init(int32_t* scratch, int w) {
-    w2 = w + 2;
-    err = scratch;
-    pe = (uint32_t*)(err + 2 * w2);
-    for (int i = 0; i < kWpStateInts * w2; i++) err[i] = 0;
-  }
-  static __device__ __forceinline__ uint32_t Div(uint32_t i) { return (1u << 24) / (i + 1); }
-  static __device__ __forceinline__ uint32_t ErrorWeight(uint64_t x, uint32_t maxweight) {
-    int shift = (63 - __clzll((long long)(x + 1))) - 5;
-    if (shift < 0) shift = 0;
-    return 4 + (uint32_t)((maxweight * (uint64_t)Div((uint32_t)(x >> shift))) >> shift);
-  }
-  static __device__ __forceinline__ int64_t Abs(int64_t v) { return v < 0 ? -v : v; }
-  __device__ int64_t Predict(int x, int y, int w, int64_t N, int64_t W, int64_t NE, int64_t NW, int64_t NN, int64_t* max_err) {
-    const int cur = (y & 1) ? 0 : w2, prev = (y & 1) ? w2 : 0;
-    const int pN = prev + x, pNE = x < w - 1 ? pN + 1 : pN, pNW = x > 0 ? pN - 1 : pN;
-    const uint32_t kW[4] = {13, 12, 12, 12};
-    uint32_t weights[4];
-    for (int i = 0; i < 4; i++) {
-      const uint32_t* p = pe + (size_t)i * 2 * w2;
-      weights[i] = ErrorWeight((uint64_t)p[pN] + p[pNE] + p[pNW], kW[i]);
-    }
-    N <<= 3; W <<= 3; NE <<= 3; NW <<= 3; NN <<= 3;
-    const int64_t teW = x == 0 ? 0 : err[cur + x - 1], teN = err[pN], teNW = err[pNW], teNE = err[pNE];
-    const int64_t sumWN = teN + teW;
-    int64_t p = teW;
-    if (Abs(teN) > Abs(p)) p = teN;
-    if (Abs(teNW) > Abs(p)) p = teNW;
-    if (Abs(teNE) > Abs(p)) p = teNE;
-    *max_err = p;
-    prediction[0] = W + NE - N;
-    prediction[1] = N - (((sumWN + teNE) * 16) >> 5);
-    prediction[2] = W - (((sumWN + teNW) * 10) >> 5);
-    prediction[3] = N - ((teNW * 7 + teN * 7 + teNE * 7) >> 5);
-    uint32_t weight_sum = weights[0] + weights[1] + weights[2] + weights[3];
-    const int log_weight = 31 - __clz(weight_sum);
-    weight_sum = 0;
-    for (int i = 0; i < 4; i++) { weights[i] >>= log_weight - 4; weight_sum += weights[i]; }
-    int64_t sum = (int64_t)(weight_sum >> 1) - 1;
-    for (int i = 0; i < 4; i++) sum += prediction[i] * (int64_t)weights[i];
-    pred = (sum * (int64_t)Div(weight_sum - 1)) >> 24;
-    if (((teN ^ teW) | (teN ^ teNW)) > 0) return (pred + 3) >> 3;
-    const int64_t mx = W > NE ? (W > N ? W : N) : (NE > N ? NE : N), mn = W < NE ? (W < N ? W : N) : (NE < N ? NE : N);
-    pred = pred < mn ? mn : (pred > mx ? mx : pred);
-    return (pred + 3) >> 3;
-  }
-  __device__ void Update(int64_t val, int x, int y) {
-    const int cur = (y & 1) ? 0 : w2, prev = (y & 1) ? w2 : 0;
-    val <<= 3;
-    err[cur + x] = (int32_t)(pred - val);
-    for (int i = 0; i < 4; i++) {
-      const uint32_t e = (uint32_t)((Abs(prediction[i] - val) + 3) >> 3);
-      uint32_t* p = pe + (size_t)i * 2 * w2;
-      p[cur + x] = e;
-      p[prev + x + 1] += e;
-    }
-  }
-};
 
 // Decodes one channel (w x h) into `out` (row stride `stride`).  Every property 0..14 and every predictor
 // except the weighted one are supported; the host rejects trees that need more.
@@ -580,8 +505,7 @@ __device__ __forceinline__ void ModularChannel(LaneBits& b, uint32_t& state, con
     const int32_t NE = (x + 1 < w && y) ? (use_rb ? rb[(x + 1) * rs] : prow[x + 1]) : N;
     int64_t wp_pred = 0, wp_err = 0;
     if (use_wp) {
-      const int32_t NNw = y > 1 ? prow[x - stride] : N;
-      wp_pred = wp.Predict(x, y, w, N, W, NE, NW, NNw, &wp_err);
+      wp_pred = wp.Predict(x, y, w, N, W, NE, &wp_err);
     }
     DevTreeNode nd = leaf;
     if (!row_leaf) {
@@ -612,42 +536,17 @@ __device__ __forceinline__ void ModularChannel(LaneBits& b, uint32_t& state, con
         nd = NodeOf(tree[node]);
       }
     }
-    const uint32_t pred = nd.a & 0xFF, ctx = nd.a >> 8;
+    const uint32_t pred = LeafPredictor(nd);
     int64_t guess;
-    switch (pred) {
-      case 0: guess = 0; break;
-      case 1: guess = W; break;
-      case 2: guess = N; break;
-      case 3: guess = ((int64_t)W + N) / 2; break;
-      case 4: {
-        int64_t pp = (int64_t)W + N - NW, pa = pp - W, pb = pp - N;
-        if (pa < 0) pa = -pa;
-        if (pb < 0) pb = -pb;
-        guess = pa < pb ? W : N;
-        break;
-      }
-      case 5: {
-        const int64_t mn = W < N ? W : N, mx = W < N ? N : W, gr = (int64_t)W + N - NW;
-        guess = gr < mn ? mn : (gr > mx ? mx : gr);
-        break;
-      }
-      case 6: guess = wp_pred; break;
-      case 7: guess = NE; break;
-      case 8: guess = NW; break;
-      case 9: guess = WW; break;
-      case 10: guess = ((int64_t)W + NW) / 2; break;
-      case 11: guess = ((int64_t)NW + N) / 2; break;
-      case 12: guess = ((int64_t)N + NE) / 2; break;
-      case 13: {
-        const int32_t NN = y > 1 ? prow[x - stride] : N;
-        const int32_t NEE = (x + 2 < w && y) ? (use_rb ? rb[(x + 2) * rs] : prow[x + 2]) : NE;
-        guess = (6 * (int64_t)N - 2 * (int64_t)NN + 7 * (int64_t)W + WW + NEE + 3 * (int64_t)NE + 8) / 16;
-        break;
-      }
-      default: guess = 0; break;
+    if (pred == 13) {   // the one predictor that reads NN and NEE
+      const int32_t NN = HasNN(y) ? prow[x - stride] : N;
+      const int32_t NEE = HasNEE(x, y, w) ? (use_rb ? rb[(x + 2) * rs] : prow[x + 2]) : NE;
+      guess = ModularPredictT<13>(W, N, NW, NE, NN, WW, NEE, 0);
+    } else {
+      guess = ModularPredict(pred, W, N, NW, NE, 0, WW, 0, wp_pred);
     }
-    const uint32_t tok = AnsGet(b, state, tab, ctx);
-    const int32_t val = (int32_t)((int64_t)UnpackSigned(tok) * (int64_t)nd.b + nd.splitval + guess);
+    const uint32_t tok = AnsGet(b, state, tab, LeafContext(nd));
+    const int32_t val = (int32_t)(LeafResidual(tok, nd.b, (uint32_t)nd.splitval) + (uint32_t)guess);
     row[x] = val;
     if (use_wp) wp.Update(val, x, y);
     if (use_rb) rb[x * rs] = val;   // slot x held prev[x], which now lives in N
@@ -667,14 +566,11 @@ __device__ __forceinline__ void ModularChannel(LaneBits& b, uint32_t& state, con
 // channel) applies the predictors.  Everything else takes the generic per-lane ModularChannel path in phase A.
 constexpr int kCarryInts = 1024;   // widest channel whose last row can be carried between 64-row batches in LDS
 
+// The node row y of a channel ends in by the static properties alone (modular_rules.h: StaticWalk), from the tree's root.
 template <class TreeP>
 __device__ __forceinline__ DevTreeNode RowNode(TreeP tree, int chan, int sid, int y, bool* used_y) {
-  DevTreeNode nd = NodeOf(tree[0]);
-  while (nd.property >= 0 && nd.property <= 2) {
-    if (nd.property == 2) *used_y = true;
-    const int v = nd.property == 0 ? chan : (nd.property == 1 ? sid : y);
-    nd = NodeOf(tree[v > nd.splitval ? nd.a : nd.b]);
-  }
+  DevTreeNode nd;
+  StaticWalk<true>([&](uint32_t i) { return NodeOf(tree[i]); }, 0u, chan, sid, y, used_y, &nd);
   return nd;
 }
 
@@ -690,13 +586,12 @@ __device__ int ClassifyChannel(const CodeTab<kLds>& tab, typename AS<kLds>::Tree
     bool used_y = false;
     const DevTreeNode nd = RowNode(tree, chan, sid, y, &used_y);
     if (nd.property >= 0) return 0;
-    const uint32_t p = nd.a & 0xFF;
+    const uint32_t p = LeafPredictor(nd);
     if (!SkewPred(p)) return 0;
     if (p == 2 || p == 5) nn = true;
-    const uint32_t c = tab.cfg[tab.cmap[nd.a >> 8]];
-    const uint32_t sym = (c >> 16) & 0xFF;
-    if (p == 0 && (c & 0x1000) && sym < (1u << (c & 0xF))) {
-      const int32_t v = (int32_t)((uint32_t)UnpackSigned(sym) * nd.b + (uint32_t)nd.splitval);
+    const uint32_t c = tab.cfg[tab.cmap[LeafContext(nd)]];
+    if (p == 0 && OneSymbolToken(c)) {
+      const int32_t v = (int32_t)LeafResidual(OneSymbol(c), nd.b, (uint32_t)nd.splitval);
       if (first) { cv = v; first = false; }
       else if (v != cv) all_const = false;
     } else {
@@ -737,9 +632,9 @@ __device__ __forceinline__ void RowScalar(LaneBits& b, uint32_t& state, TabPtr d
     if (__builtin_expect(s_state < 65536u, 0)) s_state = (s_state << 16) | sb.Read(16);
     const uint32_t u = HybridTail(sb, s_cfg, e >> 24);
     if constexpr (kPlain) {
-      row[x] = UnpackSigned(u);
+      row[x] = UnpackSigned(u);   // LeafResidual with multiplier 1 and offset 0
     } else {
-      const uint32_t val = (uint32_t)UnpackSigned(u) * s_mul + s_off + (s_addw ? s_w : 0u);
+      const uint32_t val = LeafResidual(u, s_mul, s_off) + (s_addw ? s_w : 0u);
       row[x] = (int32_t)val;
       s_w = val;
       s_first = x == 0 ? val : s_first;
@@ -837,8 +732,7 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
     for (int y = 0; narrow && y < h; y++) {
       bool used_y = false;
       const DevTreeNode nd = RowNode(tree, chan, sid, y, &used_y);
-      const uint32_t c = tab.cfg[tab.cmap[nd.a >> 8]];
-      narrow = (nd.a & 0xFF) == 5 && !((c & 0x1000) && ((c >> 16) & 0xFF) < (1u << (c & 0xF)));
+      narrow = LeafPredictor(nd) == 5 && !OneSymbolToken(tab.cfg[tab.cmap[LeafContext(nd)]]);
       if (!used_y) break;   // every row resolves to this leaf
     }
   }
@@ -847,14 +741,13 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
     // row constants: leaf -> cluster, hybrid-uint config, multiplier / offset, predictor
     bool used_y = false;
     const DevTreeNode nd = RowNode(tree, chan, sid, y, &used_y);
-    const uint32_t cl = tab.cmap[nd.a >> 8];
+    const uint32_t cl = tab.cmap[LeafContext(nd)];
     const uint32_t cfg = tab.cfg[cl];
     const typename AS<kLds>::U64 abase = tab.alias + (cl << tab.log_alpha);
     const uint32_t mul = nd.b, off = (uint32_t)nd.splitval;
-    const bool add_w = !needs_n && (nd.a & 0xFF) == 1;   // Zero / West rows need no row above: finished inline
-    const uint32_t csym = (cfg >> 16) & 0xFF;
-    const bool ctok = (cfg & 0x1000) && csym < (1u << (cfg & 0xF));
-    const uint32_t cres = (uint32_t)UnpackSigned(csym) * mul + off;
+    const bool add_w = !needs_n && LeafPredictor(nd) == 1;   // Zero / West rows need no row above: finished inline
+    const bool ctok = OneSymbolToken(cfg);
+    const uint32_t cres = LeafResidual(OneSymbol(cfg), mul, off);
     JXL_GLB int32_t* const row = out + (size_t)y * stride;
     uint32_t W = y ? first_prev : 0u;
     if (ctok) {   // a row of one-symbol tokens: nothing is read from the stream
@@ -891,7 +784,7 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
 #pragma unroll
         for (int k = 0; k < kTopUpEvery; k++) {
           const uint32_t sym = AnsSymPf<kLds>(b, state, abase, tab.log_alpha, entry);
-          const uint32_t val = (uint32_t)UnpackSigned(HybridTail(b, cfg, sym)) * mul + off;
+          const uint32_t val = LeafResidual(HybridTail(b, cfg, sym), mul, off);
           top = max(top, val + lim);
           if (k & 1) pk[k >> 1] |= val << 16;
           else pk[k >> 1] = val & 0xFFFFu;
@@ -914,7 +807,7 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
       const int xe = min(w, x0 + kTopUpEvery);
       for (int x = x0; x < xe; x++) {
         const uint32_t sym = AnsSymPf<kLds>(b, state, abase, tab.log_alpha, entry);
-        const uint32_t val = (uint32_t)UnpackSigned(HybridTail(b, cfg, sym)) * mul + off + (add_w ? W : 0u);
+        const uint32_t val = LeafResidual(HybridTail(b, cfg, sym), mul, off) + (add_w ? W : 0u);
         row[x] = (int32_t)val;
         W = val;
         first = x == 0 ? val : first;
@@ -935,16 +828,7 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
 __device__ __forceinline__ int32_t FromLaneBelow(int32_t v) {
   return __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
 }
-// min(W, N) if NW >= max, max if NW <= min, else W + N - NW: the clamped gradient without 64-bit arithmetic (inside the
-// interval the sum cannot overflow).
-__device__ __forceinline__ int32_t ClampedGradient32(int32_t W, int32_t N, int32_t NW) {
-  const int32_t mn = W < N ? W : N, mx = W < N ? N : W;
-  return NW >= mx ? mn : (NW <= mn ? mx : (int32_t)((uint32_t)W + (uint32_t)N - (uint32_t)NW));
-}
-__device__ __forceinline__ uint32_t RowGuess(uint32_t pred, int32_t W, int32_t N, int32_t NW) {
-  const uint32_t g = (uint32_t)ClampedGradient32(W, N, NW);
-  return pred == 0 ? 0u : (pred == 1 ? (uint32_t)W : (pred == 2 ? (uint32_t)N : g));
-}
+// (the predictors here in 32-bit arithmetic: modular_rules.h, RowGuess / ClampedGradient32)
 template <bool kU8Out>
 __device__ void PredictWave(const I4* tree, int chan, int sid, int32_t* plane_generic, int stride, int w, int h, int kind, int32_t cvalue,
                             uint8_t* out8_generic, int out_stride, JXL_LDS int32_t* carry, int lane) {
@@ -958,7 +842,9 @@ __device__ void PredictWave(const I4* tree, int chan, int sid, int32_t* plane_ge
     if (row_active) { bool u = false; pred = RowNode(tree, chan, sid, y, &u).a & 0xFF; }
     JXL_GLB int32_t* const prow = plane + (size_t)(row_active ? y : y0) * stride;
     const bool more = y0 + 64 < h;
-    int32_t W = 0, N = 0, NW = 0, val = 0;
+    ModularRoll hd;
+    hd.StartRow(0);
+    int32_t val = 0;
     int32_t r_next = (row_active && lane == 0 && kind == kChanResid) ? prow[0] : cvalue;
     const int steps = w + nrows - 1;
     for (int t = 0; t < steps; t++) {
@@ -968,15 +854,15 @@ __device__ void PredictWave(const I4* tree, int chan, int sid, int32_t* plane_ge
       if (row_active && kind == kChanResid && x + 1 >= 0 && x + 1 < w) r_next = prow[x + 1];   // in flight during this step
       if (row_active && x >= 0 && x < w) {
         const int32_t n_in = lane == 0 ? (y ? carry[x] : 0) : from_up;
-        if (x == 0) { W = y ? n_in : 0; N = W; NW = W; }
-        else if (y) { NW = N; N = n_in; }
-        else { NW = W; N = W; }
-        const uint32_t guess = RowGuess(pred, W, N, NW);
+        // the second half of the roll: this sample's N (the NE of the one before) has arrived from the lane below only now
+        if (x == 0) hd.StartRow(y ? n_in : 0);
+        else hd.StepN(n_in, y);
+        const uint32_t guess = RowGuess(pred, hd.W, hd.N, hd.NW);
         val = (int32_t)((uint32_t)r + guess);
         if (kU8Out) out8[(size_t)y * out_stride + x] = (uint8_t)(val < 0 ? 0 : (val > 255 ? 255 : val));
         else prow[x] = val;
         if (more && lane == nrows - 1) carry[x] = val;
-        W = val;
+        hd.StepW(val, x);
       }
     }
   }
@@ -2120,7 +2006,7 @@ struct AlphaLines16 : AlphaLines {
 // `li`) that must then combine their answers
 __device__ __forceinline__ bool AlphaRowsAreGradient(const I4* tree, int sid, int gh, int li, int nlanes) {
   bool ok = true;
-  for (int r = li; r < gh; r += nlanes) { bool u = false; ok = ok && (RowNode(tree, 0, sid, r, &u).a & 0xFF) == 5; }
+  for (int r = li; r < gh; r += nlanes) { bool u = false; ok = ok && LeafPredictor(RowNode(tree, 0, sid, r, &u)) == 5; }
   return ok;
 }
 __device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int* gw, int* gh, int* sid, ChanDesc* d, int32_t kind = kChanResid) {
@@ -2271,7 +2157,7 @@ __global__ __launch_bounds__(64) void lf_finish_gradient_kernel(const DevImage* 
     const I4* tree = (const I4*)im.tree;
     for (int r = li; r < bh; r += 16) {
       bool used_y = false;
-      mine = mine && (RowNode(tree, chan, 1 + g, r, &used_y).a & 0xFF) == 5;
+      mine = mine && LeafPredictor(RowNode(tree, chan, 1 + g, r, &used_y)) == 5;
       if (!used_y) break;   // every row resolves to this leaf
     }
   }

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include "dev_types.h"
+#include "modular_rules.h"
 
 namespace jxlhip {
 
@@ -17,7 +18,7 @@ constexpr int kHfRingWords = 32;     // ... and in the HF decoder (one size: a 1
 constexpr int kModWindowLanes = 64;  // modular_ans_kernel lays its bit windows out for a whole wavefront whatever `lanes` is
 constexpr int kNzColBytes = 96;      // HF decoder, per lane: non-zero counts of 32 columns x 3 channels
 constexpr int kNnzCtxBytes = 64;     // HF decoder: the LDS copy of d_nnz_ctx
-constexpr int kWpStateInts = 10;     // weighted-predictor state: ints per column (of rb_width + 2 columns)
+constexpr int kWpStateInts = WpState::kInts;     // weighted-predictor state: ints per column (of rb_width + 2 columns)
 constexpr int kUniRows = 3;          // modular_uniform.h: rows the one-section-per-wavefront decoder keeps
 constexpr size_t kUniGridBytes = (size_t)kUniGridCells * 16;   // ... and its grid of 16-byte leaf records
 // The most dynamic LDS a launch asks for; tables that need more stay in global memory (the kLds = false variants).

@@ -8,6 +8,7 @@
 //   enc_ll_wp_kernel        forward weighted predictor: prediction + property 15 of every sample, one wavefront per (group, channel),
 //                           rows skewed over the lanes                                                                  (register pipeline)
 //   enc_ll_tokens2_kernel   tokens + per-leaf histograms under the chosen predictors and (effort 9) property-15 contexts
+// Predictors, neighbourhood and the weighted predictor's arithmetic are the decoder's own: modular_rules.h (through enc_dev.h).
 #include <hip/hip_runtime.h>
 #include "dev_util.h"
 #include "enc_dev.h"
@@ -34,23 +35,6 @@ __device__ __forceinline__ uchar4 LoadPixel(const EncImage& im, int x, int y) {
   return *(const uchar4*)(im.bgra + (size_t)y * im.stride + (size_t)x * 4);
 }
 
-// predictors 1..5 of the format on the neighbours W, N, NW
-__device__ __forceinline__ int32_t PredictLl(int pred, int32_t W, int32_t N, int32_t NW) {
-  switch (pred) {
-    case 1: return W;
-    case 2: return N;
-    case 3: return (int32_t)(((int64_t)W + N) / 2);
-    case 4: {
-      const int64_t pp = (int64_t)W + N - NW;
-      int64_t pa = pp - W, pb = pp - N;
-      if (pa < 0) pa = -pa;
-      if (pb < 0) pb = -pb;
-      return pa < pb ? W : N;
-    }
-    default: return GradientPred(W, N, NW);
-  }
-}
-
 // forward reversible colour transform `type` (0..6, permutation 0) of one pixel
 __device__ __forceinline__ void ForwardRct(int type, int32_t R, int32_t G, int32_t B, int32_t* out) {
   if (type == 6) {
@@ -75,15 +59,6 @@ __device__ __forceinline__ void Candidates(uchar4 p, int32_t* v) {
 
 // Value of `v` in the lane below (lane - 1) by a DPP wave shift: one VALU move, no LDS traffic (lane 0 reads 0)
 __device__ __forceinline__ int32_t LaneAbove(int32_t v) { return __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false); }
-
-// the weighted predictor's arithmetic, as entropy_kernels.hip: WpState has it
-__device__ __forceinline__ uint32_t WpDiv(uint32_t i) { return (1u << 24) / (i + 1); }
-__device__ __forceinline__ uint32_t WpErrorWeight(uint64_t x, uint32_t maxweight) {
-  int shift = (63 - __clzll((long long)(x + 1))) - 5;
-  if (shift < 0) shift = 0;
-  return 4 + (uint32_t)((maxweight * (uint64_t)WpDiv((uint32_t)(x >> shift))) >> shift);
-}
-__device__ __forceinline__ int64_t WpAbs(int64_t v) { return v < 0 ? -v : v; }
 
 }  // namespace
 
@@ -182,7 +157,7 @@ __global__ __launch_bounds__(256) void enc_ll_search_kernel(EncImage im, LlSearc
 #pragma unroll
       for (int p = 1; p <= kLlPreds; p++) {
         uint32_t tok, nb, bits;
-        HybridD(PackSignedD(v[k] - PredictLl(p, W[k], N[k], NW[k])), &tok, &nb, &bits);
+        HybridD(PackSigned(v[k] - ModularPredictWNNW(p, W[k], N[k], NW[k])), &tok, &nb, &bits);
         atomicAdd(&s_h[(k * kLlPreds + p - 1) * kEncSyms + tok], 1u);
       }
     }
@@ -216,7 +191,8 @@ __global__ void enc_ll_planes2_kernel(EncImage im, LlSearch ls) {
 // t - 2l at step t, so the lane above finished column x+1 one step earlier and hands its five values down by a wave shift; N and NW
 // are what came down one and two steps before.  The own row's state stays in registers.  A 256-row group is four 64-row bands; the
 // last row of a band reaches the next band's lane 0 through one LDS row of 5 * (w + 2) words.  Bit-identical to the decoder's
-// WpState (entropy_kernels.hip), edge clamps and carry included: tests/test_gpu_lossless_effort.py round-trips through it.
+// WpState (modular_rules.h: WpPredictFromState, written out here once more with that header's WpErrorWeight / WpAbs - through the shared
+// function this kernel took two more registers), edge clamps and carry included: tests/test_gpu_lossless_effort.py round-trips through it.
 __global__ __launch_bounds__(64) void enc_ll_wp_kernel(EncImage im, LlSearch ls) {
   __shared__ int32_t s_row[5][kGroupDim + 2];
   __shared__ uint32_t s_h[kEncSyms];
@@ -289,7 +265,7 @@ __global__ __launch_bounds__(64) void enc_ll_wp_kernel(EncImage im, LlSearch ls)
         const uint32_t pN = a_e[i][1] + o_e1[i];
         const uint32_t pNW = first ? pN : a_e[i][0] + o_e2[i];
         const uint32_t pNE = last ? pN : a_e[i][2];
-        weights[i] = WpErrorWeight((uint64_t)pN + pNE + pNW, kW[i]);
+        weights[i] = WpErrorWeight((uint64_t)pN + pNE + pNW, kW[i], WpDivExact());
       }
       const int64_t N8 = (int64_t)Np << 3, W8 = (int64_t)W << 3, NE8 = (int64_t)NEp << 3;
       const int64_t sumWN = teN + teW;
@@ -310,7 +286,7 @@ __global__ __launch_bounds__(64) void enc_ll_wp_kernel(EncImage im, LlSearch ls)
       int64_t sum = (int64_t)(weight_sum >> 1) - 1;
 #pragma unroll
       for (int i = 0; i < 4; i++) sum += prediction[i] * (int64_t)weights[i];
-      int64_t pred = (sum * (int64_t)WpDiv(weight_sum - 1)) >> 24;
+      int64_t pred = (sum * (int64_t)WpDivExact()(weight_sum - 1)) >> 24;
       if (((teN ^ teW) | (teN ^ teNW)) <= 0) {
         const int64_t mx = W8 > NE8 ? (W8 > N8 ? W8 : N8) : (NE8 > N8 ? NE8 : N8), mn = W8 < NE8 ? (W8 < N8 ? W8 : N8) : (NE8 < N8 ? NE8 : N8);
         pred = pred < mn ? mn : (pred > mx ? mx : pred);
@@ -320,7 +296,7 @@ __global__ __launch_bounds__(64) void enc_ll_wp_kernel(EncImage im, LlSearch ls)
       out_prop[(size_t)y * im.w + x] = (int32_t)p;
       {
         uint32_t tok, nb, bits;
-        HybridD(PackSignedD(v - guess), &tok, &nb, &bits);
+        HybridD(PackSigned(v - guess), &tok, &nb, &bits);
         atomicAdd(&s_h[tok], 1u);
       }
       // the state after this sample
@@ -365,14 +341,8 @@ __global__ __launch_bounds__(256) void enc_ll_tokens2_kernel(EncImage im, LlSear
     int32_t guess;
     if (pred == 6) guess = ls.wp_pred[c][origin + at];
     else {
-      int32_t W, N, NW;
-      if (x == 0) { W = y ? pl[at - im.w] : 0; N = W; NW = W; }
-      else {
-        W = pl[at - 1];
-        N = y ? pl[at - im.w] : W;
-        NW = y ? pl[at - im.w - 1] : W;
-      }
-      guess = PredictLl(pred, W, N, NW);
+      const ModularWNNW hd = ModularWNNWAt([&](int sx, int sy) { return pl[(size_t)sy * im.w + sx]; }, x, y);
+      guess = ModularPredictWNNW(pred, hd.W, hd.N, hd.NW);
     }
     int bucket = 0;
     if (ls.wp_ctx) {
@@ -382,7 +352,7 @@ __global__ __launch_bounds__(256) void enc_ll_tokens2_kernel(EncImage im, LlSear
     }
     DevToken t;
     t.ctx = ls.ctx[c][bucket];
-    t.value = PackSignedD(v - guess);
+    t.value = PackSigned(v - guess);
     out[i] = t;
     uint32_t tok, nb, bits;
     HybridD(t.value, &tok, &nb, &bits);

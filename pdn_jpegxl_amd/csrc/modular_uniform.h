@@ -14,7 +14,8 @@
 //   * MA tree: the subtree of the channel is flattened once per channel into a grid over the thresholds of the (at most four)
 //     sample-dependent properties it tests (at most 64 thresholds in all).  Every threshold sits in one lane together with the
 //     coefficients of ITS property over the neighbourhood (each property of the format is a signed sum of W, N, NW, NE, NN, WW,
-//     x, y, the previous W + N - NW and the weighted predictor's error, two of them with an absolute value): per sample the lanes
+//     x, y, the previous W + N - NW and the weighted predictor's error, two of them with an absolute value - ModularPropertyForm
+//     in modular_rules.h, which the CPU suite holds against ModularProperty for every id): per sample the lanes
 //     evaluate their property with a few multiply-adds on the uniform neighbourhood - no branch on the property id - one vector
 //     compare against the thresholds gives all buckets at once (population counts of the slots' lane ranges), and the grid cell
 //     holds the leaf (predictor, cluster, multiplier, offset): in a lane when the grid has at most 64 cells, else one LDS read -
@@ -58,32 +59,6 @@ __device__ __forceinline__ DevTreeNode UniNode(const JXL_LDS I4* tree, uint32_t 
   DevTreeNode n;
   n.property = (int32_t)JXL_RFL(v.x); n.splitval = (int32_t)JXL_RFL(v.y); n.a = JXL_RFL(v.z); n.b = JXL_RFL(v.w);
   return n;
-}
-
-// The sample-dependent properties of the format (ids 2 .. 15) from the uniform neighbourhood (tree-walk fallback only).
-struct UniHood {
-  int32_t W, N, NW, NE, NN, WW;
-  int64_t prev9, wp_err;
-  int x, y;
-};
-__device__ __forceinline__ int64_t UniProperty(int id, const UniHood& h) {
-  switch (id) {
-    case 2: return h.y;
-    case 3: return h.x;
-    case 4: return h.N < 0 ? -(int64_t)h.N : h.N;
-    case 5: return h.W < 0 ? -(int64_t)h.W : h.W;
-    case 6: return h.N;
-    case 7: return h.W;
-    case 8: return (int64_t)h.W - h.prev9;
-    case 9: return (int64_t)h.W + h.N - h.NW;
-    case 10: return (int64_t)h.W - h.NW;
-    case 11: return (int64_t)h.NW - h.N;
-    case 12: return (int64_t)h.N - h.NE;
-    case 13: return (int64_t)h.N - h.NN;
-    case 14: return (int64_t)h.W - h.WW;
-    case 15: return h.wp_err;
-    default: return 0;
-  }
 }
 
 template <class T> __device__ __forceinline__ T* UniPtr64(T* p) {   // a pointer every lane holds alike -> scalar registers
@@ -314,12 +289,12 @@ __device__ __forceinline__ void UniRows(UniCtx& c, LaneBits& b) {
               else { const U4 rec = c.grid[cell]; l_mul = JXL_RFL(rec.y); l_off = (int32_t)JXL_RFL(rec.z); }
             }
           } else {
-            UniHood hd;
-            hd.W = W; hd.N = N; hd.NW = NW; hd.NE = NE; hd.NN = NN; hd.WW = WW; hd.prev9 = prev9; hd.wp_err = wp_err; hd.x = x; hd.y = y;
+            ModularHood hd;
+            hd.W = W; hd.N = N; hd.NW = NW; hd.NE = NE; hd.NN = NN; hd.WW = WW; hd.NEE = NE; hd.prev9 = prev9; hd.wp_err = wp_err; hd.x = x; hd.y = y;
             uint32_t node = c.root;
             DevTreeNode nd = UniNode(c.tree, node);
             while (nd.property >= 0) {
-              const int64_t pv = nd.property == 0 ? (int64_t)c.chan : (nd.property == 1 ? (int64_t)c.sid : UniProperty(nd.property, hd));
+              const int64_t pv = nd.property == 0 ? (int64_t)c.chan : (nd.property == 1 ? (int64_t)c.sid : ModularProperty(nd.property, hd));
               node = pv > nd.splitval ? nd.a : nd.b;
               nd = UniNode(c.tree, node);
             }
@@ -594,22 +569,15 @@ __device__ __forceinline__ bool ModularChannelUniform(LaneBits& b, uint32_t& sta
       if (lane >= lane0[k] && lane < lane0[k] + nthr[k]) { c.vthr = t; c.vthr32 = (int32_t)t; vpid = prop_id[k]; }
     }
   }
-  c.vcW = (vpid == 5 || vpid == 7 || vpid == 8 || vpid == 9 || vpid == 10 || vpid == 14) ? 1 : 0;
-  c.vcN = (vpid == 4 || vpid == 6 || vpid == 9 || vpid == 12 || vpid == 13) ? 1 : (vpid == 11 ? -1 : 0);
-  c.vcNW = vpid == 11 ? 1 : ((vpid == 9 || vpid == 10) ? -1 : 0);
-  c.vcNE = vpid == 12 ? -1 : 0;
-  c.vcNN = vpid == 13 ? -1 : 0;
-  c.vcWW = vpid == 14 ? -1 : 0;
-  c.vcX = vpid == 3 ? 1 : 0;
-  c.vcY = vpid == 2 ? 1 : 0;
-  c.vcE = vpid == 15 ? 1 : 0;
-  c.vabs = vpid == 4 || vpid == 5;
-  c.vp8 = vpid == 8;
-  c.use_far = __ballot(vpid == 12 || vpid == 13 || vpid == 14) != 0;
-  c.use_xy = __ballot(vpid == 2 || vpid == 3) != 0;
-  c.use_e = __ballot(vpid == 15) != 0;
-  c.use_p8 = __ballot(vpid == 8) != 0;
-  c.use_abs = __ballot(vpid == 4 || vpid == 5) != 0;
+  const PropertyForm pf = ModularPropertyForm(vpid);   // (lanes outside every slot: all zero)
+  c.vcW = pf.cW; c.vcN = pf.cN; c.vcNW = pf.cNW; c.vcNE = pf.cNE; c.vcNN = pf.cNN; c.vcWW = pf.cWW; c.vcX = pf.cX; c.vcY = pf.cY; c.vcE = pf.cE;
+  c.vabs = pf.abs;
+  c.vp8 = pf.minus_prev9;
+  c.use_far = __ballot(pf.cNE || pf.cNN || pf.cWW) != 0;
+  c.use_xy = __ballot(pf.cX || pf.cY) != 0;
+  c.use_e = __ballot(pf.cE != 0) != 0;
+  c.use_p8 = __ballot(pf.minus_prev9) != 0;
+  c.use_abs = __ballot(pf.abs) != 0;
   c.vleaf0 = 0; c.vleaf1 = 0; c.vleaf2 = 0;
   if (c.leaf_in_lanes) {
     const U4 rec = c.grid[(uint32_t)lane < cells ? lane : 0];

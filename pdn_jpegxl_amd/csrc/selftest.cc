@@ -15,6 +15,7 @@
 #include "host_parse.h"
 #include "host_write.h"
 #include "icc.h"
+#include "modular_rules.h"
 
 namespace jxlhip {
 std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf);
@@ -647,4 +648,108 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_batch_layout(int32_t n, cons
   if (v.size() > capacity) return 0;
   memcpy(out, v.data(), v.size() * sizeof(int64_t));
   return v.size();
+}
+
+// ---- the Modular sample rules (csrc/modular_rules.h), as the kernels and the host encoder call them; tests/test_modular_rules.py
+// holds each against the format's definition.  Neighbourhoods travel as rows of seven int32: W, N, NW, NE, NN, WW, NEE.
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_pack_signed(int32_t v) { return PackSigned(v); }
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_unpack_signed(uint32_t u) { return UnpackSigned(u); }
+
+namespace {
+template <int kPred>
+void PredictAllT(const int32_t* h, int64_t wp, int32_t* out) {
+  out[kPred] = (int32_t)ModularPredictT<kPred>(h[0], h[1], h[2], h[3], h[4], h[5], h[6], wp);
+  if constexpr (kPred < 13) PredictAllT<kPred + 1>(h, wp, out);
+}
+}  // namespace
+
+// Per neighbourhood: the low 32 bits of predictors 0 .. 13 by the run-time id (by_id) and by the compile-time id (by_template),
+// ClampedGradient32, and RowGuess for the ids 0, 1, 2 and 5.
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_modular_predict(int32_t n, const int32_t* hoods, const int64_t* wp_pred, int32_t* by_id,
+                                                                  int32_t* by_template, int32_t* gradient32, uint32_t* row_guess) {
+  for (int i = 0; i < n; i++) {
+    const int32_t* h = hoods + 7 * (size_t)i;
+    for (uint32_t p = 0; p < 14; p++) by_id[14 * (size_t)i + p] = (int32_t)ModularPredict(p, h[0], h[1], h[2], h[3], h[4], h[5], h[6], wp_pred[i]);
+    PredictAllT<0>(h, wp_pred[i], by_template + 14 * (size_t)i);
+    gradient32[i] = ClampedGradient32(h[0], h[1], h[2]);
+    const uint32_t ids[4] = {0, 1, 2, 5};
+    for (int k = 0; k < 4; k++) row_guess[4 * (size_t)i + k] = RowGuess(ids[k], h[0], h[1], h[2]);
+  }
+}
+
+// Per neighbourhood (with prev9, wp_err and x, y of its own): properties 2 .. 15, out[14 * i + id - 2]
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_modular_property(int32_t n, const int32_t* hoods, const int64_t* prev9, const int64_t* wp_err,
+                                                                   const int32_t* xy, int64_t* out) {
+  for (int i = 0; i < n; i++) {
+    const int32_t* h = hoods + 7 * (size_t)i;
+    ModularHood hd;
+    hd.W = h[0]; hd.N = h[1]; hd.NW = h[2]; hd.NE = h[3]; hd.NN = h[4]; hd.WW = h[5]; hd.NEE = h[6];
+    hd.prev9 = prev9[i]; hd.wp_err = wp_err[i]; hd.x = xy[2 * i]; hd.y = xy[2 * i + 1];
+    for (int id = 2; id < 16; id++) out[14 * (size_t)i + id - 2] = ModularProperty(id, hd);
+  }
+}
+// The linear form of property `id`: coefficients over W, N, NW, NE, NN, WW, x, y, wp_err, then the abs and the minus-prev9 flags
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_modular_property_form(int32_t id, int32_t* out) {
+  const PropertyForm f = ModularPropertyForm(id);
+  const int32_t v[11] = {f.cW, f.cN, f.cNW, f.cNE, f.cNN, f.cWW, f.cX, f.cY, f.cE, f.abs ? 1 : 0, f.minus_prev9 ? 1 : 0};
+  memcpy(out, v, sizeof(v));
+}
+
+// The neighbourhood and prev9 of every sample of a w x h image as a decode loop carries it (ModularRoll, HasNE / HasNN / HasNEE);
+// by_roll == 0: W, N and NW by position instead (ModularWNNWAt), the rest as before.
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_modular_hoods(int32_t w, int32_t h, const int32_t* img, int32_t by_roll, int32_t* hoods,
+                                                                int64_t* prev9) {
+  const auto at = [&](int x, int y) { return img[(size_t)y * w + x]; };
+  for (int y = 0; y < h; y++) {
+    ModularRoll r;
+    r.StartRow(y ? at(0, y - 1) : 0);
+    for (int x = 0; x < w; x++) {
+      int32_t* o = hoods + 7 * ((size_t)y * w + x);
+      const int32_t NE = HasNE(x, y, w) ? at(x + 1, y - 1) : r.N;
+      o[0] = r.W; o[1] = r.N; o[2] = r.NW; o[3] = NE; o[4] = HasNN(y) ? at(x, y - 2) : r.N; o[5] = r.WW;
+      o[6] = HasNEE(x, y, w) ? at(x + 2, y - 1) : NE;
+      prev9[(size_t)y * w + x] = r.prev9;
+      if (!by_roll) { const ModularWNNW p = ModularWNNWAt(at, x, y); o[0] = p.W; o[1] = p.N; o[2] = p.NW; }
+      r.Step(at(x, y), NE, x, y);
+    }
+  }
+}
+
+// -1 when a token under configuration word `cfg` has to be read from the stream, else the symbol it is known to be
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_one_symbol_token(uint32_t cfg) { return OneSymbolToken(cfg) ? (int32_t)OneSymbol(cfg) : -1; }
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_leaf_residual(uint32_t u, uint32_t mul, uint32_t off) { return LeafResidual(u, mul, off); }
+
+// StaticWalk over `count` nodes of (property, splitval, a, b) from the root: the index of the node it ends in; out[0] = whether the
+// row was looked at, out[1] / out[2] = LeafPredictor / LeafContext of that node.  with_row = 0: channel and stream only.
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_static_walk(const int32_t* nodes, int32_t count, int32_t chan, int32_t sid, int32_t y,
+                                                                 int32_t with_row, int32_t* out) {
+  const auto node_at = [&](uint32_t i) {
+    DevTreeNode nd{-1, 0, 0, 0};
+    if (i < (uint32_t)count) { nd.property = nodes[4 * i]; nd.splitval = nodes[4 * i + 1]; nd.a = (uint32_t)nodes[4 * i + 2]; nd.b = (uint32_t)nodes[4 * i + 3]; }
+    return nd;
+  };
+  DevTreeNode nd;
+  bool used_y = false;
+  const uint32_t at = with_row ? StaticWalk<true>(node_at, 0u, chan, sid, y, &used_y, &nd) : StaticWalk<false>(node_at, 0u, chan, sid, y, &used_y, &nd);
+  out[0] = used_y ? 1 : 0; out[1] = (int32_t)LeafPredictor(nd); out[2] = (int32_t)LeafContext(nd);
+  return (int32_t)at;
+}
+
+// The weighted predictor over a whole image, state in the memory form (WpState, as ModularChannel keeps it): per sample the
+// predictor-6 guess and property 15.
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_wp(int32_t w, int32_t h, const int32_t* img, int64_t* guess, int64_t* max_err) {
+  std::vector<int32_t> scratch((size_t)WpState::kInts * (w + 2));
+  WpState wp;
+  wp.Init(scratch.data(), w);
+  const auto at = [&](int x, int y) { return img[(size_t)y * w + x]; };
+  for (int y = 0; y < h; y++) {
+    ModularRoll r;
+    r.StartRow(y ? at(0, y - 1) : 0);
+    for (int x = 0; x < w; x++) {
+      const int32_t NE = HasNE(x, y, w) ? at(x + 1, y - 1) : r.N;
+      guess[(size_t)y * w + x] = wp.Predict(x, y, w, r.N, r.W, NE, &max_err[(size_t)y * w + x]);
+      wp.Update(at(x, y), x, y);
+      r.Step(at(x, y), NE, x, y);
+    }
+  }
 }
