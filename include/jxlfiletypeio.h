@@ -249,7 +249,7 @@ JXLFILETYPEIO_API size_t jxlhip_parse_icc(const uint8_t* data, size_t size, uint
  * Part 3: saving 16-bit and float images (not in the reference; SaveImage takes a BGRA8 surface and nothing else).
  * ===================================================================================================== */
 typedef struct JxlHipPixels {
-  const void* data;            /* host memory, interleaved, channel order Gray | Gray,A | R,G,B | R,G,B,A (as setLayerData hands pixels out) */
+  const void* data;            /* host memory (jxlhip_encode_batch: device memory), interleaved, channel order Gray | Gray,A | R,G,B | R,G,B,A (as setLayerData hands pixels out) */
   uint32_t width, height;
   uint64_t stride_bytes;       /* >= width * num_channels * bytes per sample */
   int32_t num_channels;        /* 1..4; 2 and 4 carry (unassociated) alpha */
@@ -274,6 +274,41 @@ typedef struct JxlHipPixels {
 JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels* pixels, const EncoderOptions* options,
                                                    const EncoderImageMetadata* metadata, IOCallbacks* callbacks, ErrorInfo* errorInfo,
                                                    ProgressProc progressCallback);
+
+/* =====================================================================================================
+ * Part 4: batch encode of device-resident images (not in the reference).
+ * ===================================================================================================== */
+typedef struct JxlHipEncoder JxlHipEncoder;
+
+/* device < 0: current HIP device.  Returns NULL on failure (message in err, may be NULL).  The encoder owns its streams and one
+ * device workspace that grows to the largest batch it has seen and is reused: a call that needs no more than an earlier one
+ * allocates nothing. */
+JXLFILETYPEIO_API JxlHipEncoder* jxlhip_encoder_create(int32_t device, ErrorInfo* err);
+JXLFILETYPEIO_API void jxlhip_encoder_destroy(JxlHipEncoder* enc);
+
+/* Encodes n images in one call.  images[i] is a JxlHipPixels whose `data` is a DEVICE pointer (any alignment a sample allows; it is
+ * only read); every other field means what it means for jxlhip_save_pixels.  options[i] is per image.  metadata may be NULL, and so
+ * may any metadata[i]; Exif and XMP are host pointers.  The call is synchronous: on return every file lies in host memory owned by the
+ * encoder (jxlhip_encoder_result).
+ * The file of image i is, byte for byte, what jxlhip_save_pixels hands its Write callback, concatenated, for the same pixels in host
+ * memory with options[i] and metadata[i].
+ * Scope: lossy, and lossless of integer samples, at efforts 1..7.  Efforts 8 and 9 are refused per image (EncoderStatus_EncodeError,
+ * decided on the host), and so is everything jxlhip_save_pixels refuses, an ICC profile included.  A refused image gets its status in
+ * statuses[i] and the others still encode.  An error on the device (EncoderStatus_OutOfMemory when the workspace of the batch does not
+ * fit) fails every accepted image of the batch; the encoder stays usable.  Returns the first status that is not Ok; err then names the
+ * image ("image 3: ...").  n == 0 returns Ok.  There are no progress callbacks and no cancellation, and the thread-local
+ * jxlhip_last_save_* reporters are not touched. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
+                                                    const EncoderImageMetadata* const* metadata, EncoderStatus* statuses, ErrorInfo* err);
+
+/* The file of image i of the last batch: host memory owned by the encoder, valid until the next batch or destroy.  Returns 1, or 0
+ * when there is none (an index outside the batch, a refused or failed image). */
+JXLFILETYPEIO_API int32_t jxlhip_encoder_result(JxlHipEncoder* enc, int32_t i, const uint8_t** data, size_t* size);
+
+/* Timing of the last batch, shaped like jxlhip_stage_times: device milliseconds per named stage (HIP events on the stream the stage
+ * ran on; stages on different streams overlap), then the host's stages on the host clock, named "host: ...".  The stages that
+ * allocate ("host: ... allocation") appear only in a call that had to grow a buffer. */
+JXLFILETYPEIO_API int32_t jxlhip_encoder_stage_times(JxlHipEncoder* enc, const char** names, float* ms, int32_t capacity);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 
 `load_image` / `save_image` / `get_libjxl_version` call the three C-ABI exports exactly like the C# host
 does (callback struct of six function pointers, ErrorInfo, status -> exception mapping).  `Decoder` wraps the
-device-resident batch entry points used by bench.py and the GPU parity tests.
+device-resident batch entry points used by bench.py and the GPU parity tests, `Encoder` the device-resident batch encode.
 
 The native library must exist: there is no CPU fallback.  Build it with `python -m pdn_jpegxl_amd.build`.
 """
@@ -79,7 +79,8 @@ class JxlHipPixels(C.Structure):
 EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jxlhip_decoder_create", "jxlhip_decoder_destroy", "jxlhip_peek",
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
-           "jxlhip_last_save_lossless_info", "jxlhip_save_pixels"]
+           "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
+           "jxlhip_encoder_result", "jxlhip_encoder_stage_times"]
 
 _lib = None
 
@@ -164,6 +165,17 @@ def lib(build_if_missing=True):
     L.jxlhip_save_pixels.restype = C.c_int32
     L.jxlhip_save_pixels.argtypes = [C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions), C.POINTER(EncoderImageMetadata),
                                      C.POINTER(IOCallbacks), C.POINTER(ErrorInfo), ProgressFn]
+    L.jxlhip_encoder_create.restype = C.c_void_p
+    L.jxlhip_encoder_create.argtypes = [C.c_int32, C.POINTER(ErrorInfo)]
+    L.jxlhip_encoder_destroy.restype = None
+    L.jxlhip_encoder_destroy.argtypes = [C.c_void_p]
+    L.jxlhip_encode_batch.restype = C.c_int32
+    L.jxlhip_encode_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions),
+                                      C.POINTER(C.POINTER(EncoderImageMetadata)), C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
+    L.jxlhip_encoder_result.restype = C.c_int32
+    L.jxlhip_encoder_result.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.jxlhip_encoder_stage_times.restype = C.c_int32
+    L.jxlhip_encoder_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]
     L.jxlhip_parse_check.restype = C.c_int32
     L.jxlhip_parse_check.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_static_table.restype = C.c_size_t
@@ -540,4 +552,98 @@ class Decoder:
         names = (C.c_char_p * 16)()
         ms = (C.c_float * 16)()
         k = self._L.jxlhip_stage_times(self._h, names, ms, 16)
+        return {names[i].decode(): ms[i] for i in range(k)}
+
+
+class EncodeItem:
+    """One image of Encoder.encode_batch: pixels in DEVICE memory and how to encode them.
+
+    ptr: device pointer (int) of interleaved samples, Gray | Gray,A | R,G,B | R,G,B,A; dtype: numpy dtype of a sample (uint8, uint16,
+    float16, float32); stride_bytes: bytes from one row to the next (default: tight rows); bits: of integer samples (default 8 / 16).
+    The other arguments are save_pixels' own.  `from_tensor` takes a torch tensor (h, w[, c]) on the GPU, rows may be strided."""
+
+    def __init__(self, ptr, width, height, channels, dtype, stride_bytes=None, bits=None, colour="Srgb", distance=1.0, effort=7,
+                 lossless=False, exif=None, xmp=None, icc=None, keep=None):
+        dtype = np.dtype(dtype)
+        if dtype not in _SAMPLE_TYPES:
+            raise ValueError("samples are uint8, uint16, float16 or float32")
+        self.ptr, self.width, self.height, self.channels, self.dtype = ptr, int(width), int(height), int(channels), dtype
+        self.stride_bytes = int(stride_bytes) if stride_bytes is not None else self.width * self.channels * dtype.itemsize
+        self.bits = ({1: 8, 2: 16}[dtype.itemsize] if dtype.kind == "u" else 0) if bits is None else int(bits)
+        self.colour, self.distance, self.effort, self.lossless = colour, float(distance), int(effort), bool(lossless)
+        self.exif, self.xmp, self.icc = exif, xmp, icc
+        self.keep = keep   # whatever owns the device memory
+
+    @classmethod
+    def from_tensor(cls, t, **kw):
+        if t.dim() == 2:
+            t = t.unsqueeze(2)
+        h, w, c = t.shape
+        item = t.element_size()
+        if t.stride(2) != 1 or (w > 1 and t.stride(1) != c) or (h > 1 and t.stride(0) < w * c):
+            t = t.contiguous()
+        dtype = {"torch.uint8": np.uint8, "torch.uint16": np.uint16, "torch.int16": np.uint16, "torch.float16": np.float16,
+                 "torch.float32": np.float32}[str(t.dtype)]
+        return cls(t.data_ptr(), w, h, c, dtype, stride_bytes=t.stride(0) * item if h > 1 else w * c * item, keep=t, **kw)
+
+
+class Encoder:
+    """Device-resident batch encoder (jxlhip_encoder_* / jxlhip_encode_batch): many images already in HBM, encoded in one call.
+    The file of each image is byte for byte what save_pixels writes for the same pixels and arguments."""
+
+    def __init__(self, device=-1):
+        self._h = None
+        self._L = lib()
+        err = ErrorInfo()
+        self._h = self._L.jxlhip_encoder_create(device, C.byref(err))
+        if not self._h:
+            raise JxlError("EncoderCreate", err.errorMessage.decode("ascii", "replace"))
+        self.last_error = ""
+        self.last_statuses = []
+
+    def close(self):
+        if self._h:
+            self._L.jxlhip_encoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def encode_batch(self, items, raise_on_error=True):
+        """items: list of EncodeItem.  Returns one bytes object per image (None for an image that was refused or failed; its status
+        name is in last_statuses[i], the first message in last_error).  Synchronous.  With raise_on_error the first status that is not
+        Ok raises JxlError."""
+        n = len(items)
+        px = (JxlHipPixels * max(n, 1))()
+        opt = (EncoderOptions * max(n, 1))()
+        mds = (C.POINTER(EncoderImageMetadata) * max(n, 1))()
+        keep = []
+        for i, it in enumerate(items):
+            px[i] = JxlHipPixels(it.ptr, it.width, it.height, it.stride_bytes, it.channels, _SAMPLE_TYPES[it.dtype], it.bits,
+                                 KNOWN_PROFILE.index(it.colour))
+            opt[i] = EncoderOptions(it.distance, it.effort, it.lossless)
+            if it.exif or it.xmp or it.icc:
+                bufs = [np.frombuffer(b, np.uint8) if b else None for b in (it.exif, it.icc, it.xmp)]
+                md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in bufs), []))
+                keep.append((bufs, md))
+                mds[i] = C.pointer(md)
+        st = (C.c_int32 * max(n, 1))()
+        err = ErrorInfo()
+        r = self._L.jxlhip_encode_batch(self._h, n, px, opt, mds, st, C.byref(err))
+        self.last_error = err.errorMessage.decode("ascii", "replace")
+        self.last_statuses = [ENCODER_STATUS[st[i]] if 0 <= st[i] < len(ENCODER_STATUS) else str(st[i]) for i in range(n)]
+        if r != 0 and raise_on_error:
+            raise JxlError(ENCODER_STATUS[r] if 0 <= r < len(ENCODER_STATUS) else str(r), self.last_error)
+        out = []
+        for i in range(n):
+            p, size = C.c_void_p(), C.c_size_t()
+            out.append(C.string_at(p.value, size.value) if self._L.jxlhip_encoder_result(self._h, i, C.byref(p), C.byref(size)) else None)
+        return out
+
+    def stage_times(self):
+        """{stage: ms} of the last batch: device time per kernel group (stages on different streams overlap), then the host's stages
+        ("host: ...") on the host clock."""
+        names = (C.c_char_p * 48)()
+        ms = (C.c_float * 48)()
+        k = self._L.jxlhip_encoder_stage_times(self._h, names, ms, 48)
         return {names[i].decode(): ms[i] for i in range(k)}

@@ -115,6 +115,17 @@ struct EncImage {
   uint64_t sec_cap;
 };
 
+// Which images a batch kernel covers and where each one's share of the grid begins (encode_kernels.hip, "batch forms"): entry k is a
+// run of workgroups (the compaction: sections) of image image_of[k] of the batch's record array, beginning at that image's workgroup
+// wg0[k]; first[k] counts the workgroups of the entries before it.  An image may have several entries: the reverse pass of the Modular
+// streams lists the workgroups with the LF streams of every image first, so that the longest recurrences of the batch all start at once.
+struct EncBatchTable {
+  const uint32_t* first;      // [entries], ascending, first[0] = 0
+  const int32_t* image_of;    // [entries]
+  const uint32_t* wg0;        // [entries]
+  int32_t entries, pad;
+};
+
 // The searched lossless stream of efforts 8 and 9 (lossless_kernels.hip; the rules: DESIGN.md §2, "Lossless efforts 8 and 9").
 constexpr uint32_t kPalCap = 1024;        // most colours a palette is written for
 constexpr uint32_t kPalSlots = 4096;      // slots of the colour hash set (a power of two, four times the cap)

@@ -932,33 +932,33 @@ __device__ __forceinline__ bool LossyStream(const EncImage& im, int st, DevToken
 // `which` = 0: the streams coded with the Modular code (LF coefficients, block metadata, alpha); 1: the HF coefficient streams.  Two
 // launches, because the Modular code is ready long before the (much larger) HF code: the host builds the latter while the longest
 // recurrence of the frame - the LF coefficients of an LF group - is already running.
-__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_reverse_kernel(EncImage im, int which) {
-  extern __shared__ __align__(16) uint8_t enc_smem[];
-  size_t off;
-  {
-    EncCodeDev l;
-    if (which == 0) { off = StageEncCode(enc_smem, 0, im.mcode, &l, true, threadIdx.x, blockDim.x); im.mcode = l; }
-    else { off = StageEncCode(enc_smem, 0, im.acode, &l, false, threadIdx.x, blockDim.x); im.acode = l; }
-    __syncthreads();
-  }
+// (The bodies of the serial kernels are device functions of (image, workgroup of that image): the single-image kernels call them with
+// their own image and blockIdx.x, the batch forms further down with an image and a workgroup looked up in a prefix table.)
+__device__ __forceinline__ void ReverseBody(const EncImage& im, int which, int wg, uint8_t* smem) {
+  EncCodeDev code;
+  const size_t off = StageEncCode(smem, 0, which == 0 ? im.mcode : im.acode, &code, which == 0, threadIdx.x, blockDim.x);
+  __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  WaveScratch* sc = CarveScratch(enc_smem, off, wave);
-  const int st = blockIdx.x * kSectionsPerWg + wave;
+  WaveScratch* sc = CarveScratch(smem, off, wave);
+  const int st = wg * kSectionsPerWg + wave;
   DevToken* tok;
   uint32_t n;
   bool modular;
   if (!LossyStream(im, st, &tok, &n, &modular)) return;
   if (modular != (which == 0)) return;
-  const uint32_t state = modular ? ReversePass<true>(tok, n, im.mcode, sc, lane) : ReversePass<false>(tok, n, im.acode, sc, lane);
+  const uint32_t state = modular ? ReversePass<true>(tok, n, code, sc, lane) : ReversePass<false>(tok, n, code, sc, lane);
   if (lane == 0) im.stream_state[st] = state;
+}
+__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_reverse_kernel(EncImage im, int which) {
+  extern __shared__ __align__(16) uint8_t enc_smem[];
+  ReverseBody(im, which, (int)blockIdx.x, enc_smem);
 }
 
 // Bit layout of every section (after enc_reverse_kernel): header fields and, per stream, state + flushes + raw bits; no tables needed.
-__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_sections_kernel(EncImage im) {
-  __shared__ WaveScratch s_sc[kSectionsPerWg];
+__device__ __forceinline__ void SectionsBody(const EncImage& im, int wg, WaveScratch* s_sc) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   WaveScratch* sc = &s_sc[wave];
-  const int s = blockIdx.x * kSectionsPerWg + wave;
+  const int s = wg * kSectionsPerWg + wave;
   if (s >= im.nlf + im.ng) return;
   WaveWriter w;
   w.Init(im.sec_bytes + (size_t)s * im.sec_cap, sc, lane);
@@ -991,26 +991,37 @@ __global__ __launch_bounds__(64 * kSectionsPerWg) void enc_sections_kernel(EncIm
   const uint64_t bits = w.Finish();
   if (lane == 0) im.sec_bits[s] = bits;
 }
+__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_sections_kernel(EncImage im) {
+  __shared__ WaveScratch s_sc[kSectionsPerWg];
+  SectionsBody(im, (int)blockIdx.x, s_sc);
+}
 
 // single-group frames carry their alpha in the global Modular section: coded on its own (section index nlf + ng)
-__global__ __launch_bounds__(64) void enc_global_alpha_kernel(EncImage im) {
-  __shared__ WaveScratch sc;
-  if (blockIdx.x) return;
+__device__ __forceinline__ void GlobalAlphaBody(const EncImage& im, WaveScratch* sc) {
   WaveWriter w;
   const int s = im.nlf + im.ng;
-  w.Init(im.sec_bytes + (size_t)s * im.sec_cap, &sc, threadIdx.x);
-  EncodeStream<false>(im.tok_alpha, (uint32_t)(im.w * im.h), im.mcode, w, &sc);
+  w.Init(im.sec_bytes + (size_t)s * im.sec_cap, sc, threadIdx.x);
+  EncodeStream<false>(im.tok_alpha, (uint32_t)(im.w * im.h), im.mcode, w, sc);
   const uint64_t bits = w.Finish();
   if (threadIdx.x == 0) im.sec_bits[s] = bits;
 }
+__global__ __launch_bounds__(64) void enc_global_alpha_kernel(EncImage im) {
+  __shared__ WaveScratch sc;
+  if (blockIdx.x) return;
+  GlobalAlphaBody(im, &sc);
+}
 
 // gathers the used bytes of every section into one contiguous buffer
+// section s of `im` -> dst, by workgroup `block` of the `nblocks` that share the section
+__device__ __forceinline__ void CompactBody(const EncImage& im, int s, uint8_t* dst, uint32_t block, uint32_t nblocks) {
+  const uint64_t nbytes = (im.sec_bits[s] + 7) >> 3;
+  const uint8_t* src = im.sec_bytes + (size_t)s * im.sec_cap;
+  for (uint64_t i = (uint64_t)block * blockDim.x + threadIdx.x; i < nbytes; i += (uint64_t)nblocks * blockDim.x) dst[i] = src[i];
+}
 __global__ void enc_compact_kernel(EncImage im, const uint64_t* dst_off, uint8_t* dst, int nsec) {
   const int s = blockIdx.y;
   if (s >= nsec) return;
-  const uint64_t nbytes = (im.sec_bits[s] + 7) >> 3;
-  const uint8_t* src = im.sec_bytes + (size_t)s * im.sec_cap;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbytes; i += (uint64_t)gridDim.x * blockDim.x) dst[dst_off[s] + i] = src[i];
+  CompactBody(im, s, dst + dst_off[s], blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------ lossless (Modular) frames
@@ -1065,27 +1076,69 @@ __global__ __launch_bounds__(256) void enc_ll_tokens_kernel(EncImage im) {
     if (s_h[i]) atomicAdd(&im.hist_mod[i], s_h[i]);
 }
 
-__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_ll_sections_kernel(EncImage im) {
-  extern __shared__ __align__(16) uint8_t enc_smem[];
-  size_t off;
-  {
-    EncCodeDev lm;
-    off = StageEncCode(enc_smem, 0, im.mcode, &lm, true, threadIdx.x, blockDim.x);
-    im.mcode = lm;
-    __syncthreads();
-  }
+__device__ __forceinline__ void LlSectionsBody(const EncImage& im, int wg, uint8_t* smem) {
+  EncCodeDev code;
+  const size_t off = StageEncCode(smem, 0, im.mcode, &code, true, threadIdx.x, blockDim.x);
+  __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  WaveScratch* sc = CarveScratch(enc_smem, off, wave);
-  const int g = blockIdx.x * kSectionsPerWg + wave;
+  WaveScratch* sc = CarveScratch(smem, off, wave);
+  const int g = wg * kSectionsPerWg + wave;
   if (g >= im.ng) return;
   const int gx = g % im.xg, gy = g / im.xg;
   const int gw = min(kGroupDim, im.w - gx * kGroupDim), gh = min(kGroupDim, im.h - gy * kGroupDim);
   WaveWriter w;
   w.Init(im.sec_bytes + (size_t)g * im.sec_cap, sc, lane);
   if (im.ng > 1) w.PutUniform(4, 3);   // group header; a single-group frame continues the GlobalModular stream of LfGlobal
-  EncodeStream<true>(im.tok_ll + (size_t)g * kLlTokCap, (uint32_t)(gw * gh * im.ll_nch) + (g ? 0u : im.ll_tok_extra), im.mcode, w, sc);
+  EncodeStream<true>(im.tok_ll + (size_t)g * kLlTokCap, (uint32_t)(gw * gh * im.ll_nch) + (g ? 0u : im.ll_tok_extra), code, w, sc);
   const uint64_t bits = w.Finish();
   if (lane == 0) im.sec_bits[g] = bits;
+}
+__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_ll_sections_kernel(EncImage im) {
+  extern __shared__ __align__(16) uint8_t enc_smem[];
+  LlSectionsBody(im, (int)blockIdx.x, enc_smem);
+}
+
+// ------------------------------------------------------------------ batch forms of the serial kernels (jxlhip_encode_batch)
+// One launch covers every image of a batch.  `ims`: the EncImage records of the batch in device memory; `t`: a prefix table built on the
+// host (EncBatchTable), so the grid is exactly the sum of what the images need, however ragged, and a launch lists only the images its
+// kernel applies to - lossy frames, lossless frames, one-group frames with alpha.  A workgroup belongs to one image, so the code it
+// stages in LDS is that image's.  The index is uniform over the workgroup: the search and every field of the record it reads are
+// scalar loads.
+__device__ __forceinline__ int BatchEntry(const uint32_t* __restrict__ first, int entries, uint32_t unit) {
+  int lo = 0, hi = entries - 1;   // last k with first[k] <= unit
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first[mid] <= unit) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_reverse_batch_kernel(const EncImage* __restrict__ ims, EncBatchTable t, int which) {
+  extern __shared__ __align__(16) uint8_t enc_smem[];
+  const int k = BatchEntry(t.first, t.entries, blockIdx.x);
+  ReverseBody(ims[t.image_of[k]], which, (int)(blockIdx.x - t.first[k] + t.wg0[k]), enc_smem);
+}
+__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_sections_batch_kernel(const EncImage* __restrict__ ims, EncBatchTable t) {
+  __shared__ WaveScratch s_sc[kSectionsPerWg];
+  const int k = BatchEntry(t.first, t.entries, blockIdx.x);
+  SectionsBody(ims[t.image_of[k]], (int)(blockIdx.x - t.first[k] + t.wg0[k]), s_sc);
+}
+__global__ __launch_bounds__(64) void enc_global_alpha_batch_kernel(const EncImage* __restrict__ ims, EncBatchTable t) {
+  __shared__ WaveScratch sc;
+  if ((int)blockIdx.x >= t.entries) return;
+  GlobalAlphaBody(ims[t.image_of[blockIdx.x]], &sc);   // one workgroup per listed image
+}
+__global__ __launch_bounds__(64 * kSectionsPerWg) void enc_ll_sections_batch_kernel(const EncImage* __restrict__ ims, EncBatchTable t) {
+  extern __shared__ __align__(16) uint8_t enc_smem[];
+  const int k = BatchEntry(t.first, t.entries, blockIdx.x);
+  LlSectionsBody(ims[t.image_of[k]], (int)(blockIdx.x - t.first[k] + t.wg0[k]), enc_smem);
+}
+// first[k]: sections of the images before entry k; dst_off: one offset per section of the batch, in that order, into `dst`.
+// kCompactBlocks workgroups per section, the section in the slow part of blockIdx.x (grid.y would cap a batch at 65535 sections).
+constexpr uint32_t kCompactBlocks = 16;
+__global__ void enc_compact_batch_kernel(const EncImage* __restrict__ ims, EncBatchTable t, const uint64_t* __restrict__ dst_off, uint8_t* dst) {
+  const uint32_t sec = blockIdx.x / kCompactBlocks;
+  const int k = BatchEntry(t.first, t.entries, sec);
+  CompactBody(ims[t.image_of[k]], (int)(sec - t.first[k] + t.wg0[k]), dst + dst_off[sec], blockIdx.x % kCompactBlocks, kCompactBlocks);
 }
 
 // ------------------------------------------------------------------ launch wrappers
@@ -1184,6 +1237,34 @@ void LaunchEncLossless(const EncImage& im, int stage, hipStream_t s) {
 }
 void LaunchEncCompact(const EncImage& im, const uint64_t* dst_off, uint8_t* dst, int nsec, hipStream_t s) {
   hipLaunchKernelGGL(enc_compact_kernel, dim3(64, nsec), dim3(256), 0, s, im, dst_off, dst, nsec);
+}
+
+// ---- batch forms.  `units`: the table's total (workgroups, or sections for the compaction); nothing is launched for 0.
+size_t EncReverseLds(uint32_t num_clusters, uint32_t num_ctx, int which) {
+  EncCodeDev c;
+  c.num_clusters = num_clusters; c.num_ctx = num_ctx;
+  return EncCodeLds(c, which == 0) + 32 + kSectionsPerWg * sizeof(WaveScratch);
+}
+int EncSectionsPerWg() { return kSectionsPerWg; }
+// `lds`: EncReverseLds of the largest code of the batch
+void LaunchEncReverseBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, int which, size_t lds, hipStream_t s) {
+  if (!units) return;
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)enc_reverse_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(enc_reverse_batch_kernel, dim3(units), dim3(64 * kSectionsPerWg), lds, s, ims, t, which);
+}
+void LaunchEncSectionsBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, hipStream_t s) {
+  if (units) hipLaunchKernelGGL(enc_sections_batch_kernel, dim3(units), dim3(64 * kSectionsPerWg), 0, s, ims, t);
+}
+void LaunchEncGlobalAlphaBatch(const EncImage* ims, const EncBatchTable& t, hipStream_t s) {
+  if (t.entries) hipLaunchKernelGGL(enc_global_alpha_batch_kernel, dim3((unsigned)t.entries), dim3(64), 0, s, ims, t);
+}
+void LaunchEncLlSectionsBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, size_t lds, hipStream_t s) {
+  if (!units) return;
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)enc_ll_sections_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(enc_ll_sections_batch_kernel, dim3(units), dim3(64 * kSectionsPerWg), lds, s, ims, t);
+}
+void LaunchEncCompactBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, const uint64_t* dst_off, uint8_t* dst, hipStream_t s) {
+  if (units) hipLaunchKernelGGL(enc_compact_batch_kernel, dim3(units * kCompactBlocks), dim3(256), 0, s, ims, t, dst_off, dst);
 }
 
 }  // namespace jxlhip

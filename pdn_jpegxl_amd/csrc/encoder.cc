@@ -13,10 +13,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <atomic>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "enc_batch_layout.h"
 #include "enc_types.h"
 #include "host_parse.h"
 #include "host_write.h"
@@ -37,6 +41,14 @@ void LaunchEncLosslessSearch(const EncImage& im, const LlSearch& ls, int stage, 
 void LaunchEncXyb(const EncImage& im, hipStream_t s);
 void LaunchEncPackBgra(const EncImage& im, const uint8_t* src, int nch, hipStream_t s);
 void LaunchEncVarblocks(const EncImage& im, hipStream_t s);
+// batch forms of the serial kernels: every image of `ims` that the table lists, in one launch (encode_kernels.hip)
+size_t EncReverseLds(uint32_t num_clusters, uint32_t num_ctx, int which);
+int EncSectionsPerWg();
+void LaunchEncReverseBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, int which, size_t lds, hipStream_t s);
+void LaunchEncSectionsBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, hipStream_t s);
+void LaunchEncGlobalAlphaBatch(const EncImage* ims, const EncBatchTable& t, hipStream_t s);
+void LaunchEncLlSectionsBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, size_t lds, hipStream_t s);
+void LaunchEncCompactBatch(const EncImage* ims, const EncBatchTable& t, uint32_t units, const uint64_t* dst_off, uint8_t* dst, hipStream_t s);
 // distance_kernels.hip
 void LaunchDistMask(const DistMap& dm, hipStream_t s);
 void LaunchDistCells(const DistMap& dm, hipStream_t s);
@@ -76,6 +88,7 @@ struct Arena {
     if (zero) ENC_HIP(hipMemset(p, 0, bytes));
     return (T*)p;
   }
+  template <class T> T* Counter(EncCounterKind, size_t count) { return Get<T>(count); }   // (a batch keeps the kinds apart: enc_batch_layout.h)
   template <class T> T* Upload(const std::vector<T>& v) {
     T* p = Get<T>(std::max<size_t>(v.size(), 1));
     if (!v.empty()) ENC_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -239,27 +252,17 @@ void Inv3(const double m[9], double o[9]) {
   o[6] = (m[3] * m[7] - m[4] * m[6]) / d; o[7] = (m[1] * m[6] - m[0] * m[7]) / d; o[8] = (m[0] * m[4] - m[1] * m[3]) / d;
 }
 
-void SetGeometry(uint32_t w, uint32_t h, EncImage& im) {
-  memset(&im, 0, sizeof(im));
-  im.w = (int32_t)w; im.h = (int32_t)h;
-  im.w8 = (int32_t)((w + 7) / 8); im.h8 = (int32_t)((h + 7) / 8);
-  im.wp = im.w8 * 8; im.hp = im.h8 * 8;
-  im.xg = (int32_t)((w + 255) / 256); im.yg = (int32_t)((h + 255) / 256); im.ng = im.xg * im.yg;
-  im.xlf = (int32_t)((w + 2047) / 2048); im.ylf = (int32_t)((h + 2047) / 2048); im.nlf = im.xlf * im.ylf;
-}
-
 // jxlhip_save_pixels: geometry + upload.  The channels are as stated (nothing is analysed); the rows are packed on the way up, so
 // the device rows are tight whatever stride the caller's memory has (what the loaders of encode_kernels.hip rely on).  8-bit samples
 // become the BGRA8 surface of SaveImage on the device, and every 8-bit path - the byte-keyed lossless search included - runs as it
 // does for SaveImage.
-void BeginPixels(const EncSource& src, Arena& A, EncImage& im, ProgressProc progress) {
+// What the stated channels and colour encoding mean for the kernels, once the samples are on the device: `d_src` holds them in tight
+// rows, `d_bgra` is room for the BGRA8 surface of 8-bit input (deeper input: unused).  im has its geometry.
+void SetPixelSource(const EncSource& src, const uint8_t* d_src, uint8_t* d_bgra, EncImage& im, hipStream_t s) {
   const JxlHipPixels& px = *src.px;
-  const uint32_t w = px.width, h = px.height;
-  SetGeometry(w, h, im);
+  const uint32_t w = px.width;
   const int nch = px.num_channels;
   const size_t row = (size_t)w * nch * src.sample_bytes();
-  uint8_t* d_src = A.Get<uint8_t>(row * h);
-  ENC_HIP(hipMemcpy2D(d_src, row, px.data, px.stride_bytes, row, h, hipMemcpyHostToDevice));
   im.gray = nch < 3;
   im.has_alpha = (nch & 1) ? 0 : 1;
   im.transfer = src.transfer == 8 ? kTransferLinear : (src.transfer == 1 ? kTransfer709 : (src.transfer == 16 ? kTransferPq : kTransferSrgb));
@@ -282,10 +285,19 @@ void BeginPixels(const EncSource& src, Arena& A, EncImage& im, ProgressProc prog
     im.src_type = px.sample_type;
     im.sample_scale = 1.0f / (float)((1u << src.bits) - 1);
   } else {
-    uint8_t* d_bgra = A.Get<uint8_t>((size_t)w * 4 * h);
     im.bgra = d_bgra; im.stride = (int64_t)w * 4;
-    LaunchEncPackBgra(im, d_src, nch, nullptr);
+    LaunchEncPackBgra(im, d_src, nch, s);
   }
+}
+
+void BeginPixels(const EncSource& src, Arena& A, EncImage& im, ProgressProc progress) {
+  const JxlHipPixels& px = *src.px;
+  const uint32_t w = px.width, h = px.height;
+  SetEncGeometry(w, h, im);
+  const size_t row = (size_t)w * px.num_channels * src.sample_bytes();
+  uint8_t* d_src = A.Get<uint8_t>(row * h);
+  ENC_HIP(hipMemcpy2D(d_src, row, px.data, px.stride_bytes, row, h, hipMemcpyHostToDevice));
+  SetPixelSource(src, d_src, src.deep() ? nullptr : A.Get<uint8_t>((size_t)w * 4 * h), im, nullptr);
   Progress(progress, 5);
 }
 
@@ -295,7 +307,7 @@ void BeginImage(const EncSource& src, const EncoderImageMetadata* md, Arena& A, 
   const BitmapData* bmp = src.bmp;
   const uint32_t w = bmp->width, h = bmp->height;
   if (!w || !h || !bmp->scan0 || bmp->stride < (uint64_t)w * 4) throw EncFail(EncoderStatus_EncodeError, "invalid bitmap");
-  SetGeometry(w, h, im);
+  SetEncGeometry(w, h, im);
   uint8_t* d_bgra = A.Get<uint8_t>((size_t)bmp->stride * h);
   ENC_HIP(hipMemcpy(d_bgra, bmp->scan0, (size_t)bmp->stride * h, hipMemcpyHostToDevice));
   im.bgra = d_bgra; im.stride = (int64_t)bmp->stride;
@@ -310,17 +322,18 @@ void BeginImage(const EncSource& src, const EncoderImageMetadata* md, Arena& A, 
   Progress(progress, 5);
 }
 
+std::vector<uint8_t> AssembleLossless(const EncImage& im, const EncSource& src, const EncoderImageMetadata* md, BitWriter& lf_global, const uint8_t* packed,
+                                      const uint64_t* off, const uint64_t* sec_bits);
+
 // ANS-codes the groups' tokens (im.tok_ll) with `mcode`, gathers the sections and assembles the codestream behind the finished LfGlobal
 // prefix.  The section buffers are allocated at the first call of a save and reused by the next.
 std::vector<uint8_t> FinishLossless(EncImage& im, const EncSource& src, Arena& A, const EncCode& mcode, BitWriter& lf_global, const EncoderImageMetadata* md, hipStream_t s) {
-  const bool single = im.ng == 1;
   im.mcode = UploadCode(A, mcode);
   const int nsec = im.ng;
   if (!im.sec_bytes) {
-    im.sec_cap = ((size_t)kLlTokCap * kSecBytesPerTok + 256) & ~(size_t)15;
-    im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
-    im.sec_bits = A.Get<uint64_t>(nsec, true);
-    im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1, true);
+    LayLosslessSections(A, im);
+    ENC_HIP(hipMemset(im.sec_bits, 0, std::max<size_t>((size_t)nsec * 8, 256)));
+    ENC_HIP(hipMemset(im.stream_state, 0, std::max<size_t>(EncNumStreamStates(im) * 4, 256)));
   } else {
     ENC_HIP(hipMemset(im.sec_bits, 0, std::max<size_t>((size_t)nsec * 8, 256)));
   }
@@ -337,10 +350,23 @@ std::vector<uint8_t> FinishLossless(EncImage& im, const EncSource& src, Arena& A
     ENC_HIP(hipMemcpy(packed.data(), d_packed, packed.size(), hipMemcpyDeviceToHost));
   }
   ENC_HIP(hipGetLastError());
+  return AssembleLossless(im, src, md, lf_global, packed.data(), off.data(), sec_bits.data());
+}
+
+// What the image headers say: size and channels of `im`, depth and colour encoding of `src`, the profile of `md`.
+EncImageInfo DescribeImage(const EncImage& im, const EncSource& src, const EncoderImageMetadata* md, bool xyb) {
   EncImageInfo ii;
-  ii.xsize = (uint32_t)im.w; ii.ysize = (uint32_t)im.h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = false;
+  ii.xsize = (uint32_t)im.w; ii.ysize = (uint32_t)im.h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = xyb;
   ii.icc = md->iccProfile; ii.icc_size = md->iccProfile ? md->iccProfileSize : 0;
   src.Describe(ii);
+  return ii;
+}
+
+// The codestream of a Modular frame behind its finished LfGlobal prefix.  packed + off[g], sec_bits[g]: the coded section of group g.
+std::vector<uint8_t> AssembleLossless(const EncImage& im, const EncSource& src, const EncoderImageMetadata* md, BitWriter& lf_global, const uint8_t* packed,
+                                      const uint64_t* off, const uint64_t* sec_bits) {
+  const bool single = im.ng == 1;
+  const EncImageInfo ii = DescribeImage(im, src, md, false);
   EncFrameInfo fi;
   fi.encoding = 1; fi.group_size_shift = 1; fi.gab = false; fi.epf_iters = 0;
   BitWriter cs;
@@ -348,13 +374,13 @@ std::vector<uint8_t> FinishLossless(EncImage& im, const EncSource& src, Arena& A
   WriteFrameHeader(ii, fi, cs);
   std::vector<std::vector<uint8_t>> sections;
   if (single) {
-    lf_global.AppendBits(packed.data(), sec_bits[0]);   // the channels of a frame that fits one group belong to the global stream
+    lf_global.AppendBits(packed + off[0], sec_bits[0]);   // the channels of a frame that fits one group belong to the global stream
     sections.push_back(lf_global.Finish());
   } else {
     sections.push_back(lf_global.Finish());
     for (int g = 0; g < im.nlf; g++) sections.emplace_back();   // no channel is small enough for the LF groups
     sections.emplace_back();                                    // HfGlobal is empty in a Modular frame
-    for (int g = 0; g < im.ng; g++) sections.emplace_back(packed.begin() + off[g], packed.begin() + off[g + 1]);
+    for (int g = 0; g < im.ng; g++) sections.emplace_back(packed + off[g], packed + off[g] + ((sec_bits[g] + 7) >> 3));
   }
   std::vector<uint32_t> sizes;
   for (auto& sec : sections) sizes.push_back((uint32_t)sec.size());
@@ -362,6 +388,30 @@ std::vector<uint8_t> FinishLossless(EncImage& im, const EncSource& src, Arena& A
   std::vector<uint8_t> codestream = cs.Finish();
   for (auto& sec : sections) codestream.insert(codestream.end(), sec.begin(), sec.end());
   return codestream;
+}
+
+// LfGlobal of the fixed lossless stream: tree on the channel index (leaf ids: channel 3, 2, 1, 0), the code of the channels' token
+// histograms hist[4][kEncSyms], GlobalModular header.
+void WriteLosslessFixedGlobal(const EncImage& im, const uint32_t* hist, BitWriter& lf_global, EncCode& mcode) {
+  lf_global.Bool(true);   // default LF dequantisation factors (read for every frame encoding)
+  lf_global.Bool(true);   // global MA tree
+  {
+    std::vector<EncTreeNode> t;
+    t.push_back(EncTreeNode{0, 1, 0, 0, 1});     // 0: channel > 1 ? 1 : 2
+    t.push_back(EncTreeNode{0, 2, 0, 0, 1});     // 1: channel > 2 ? 3 : 4
+    t.push_back(EncTreeNode{0, 0, 0, 0, 1});     // 2: channel > 0 ? 5 : 6
+    for (int i = 0; i < 4; i++) t.push_back(EncTreeNode{-1, 0, 5, 0, 1});   // gradient predictor leaves: channel 3, 2, 1, 0
+    WriteTree(t, lf_global);
+  }
+  BuildAndWriteCode(hist, 4, 4, {}, lf_global, mcode);
+  lf_global.Bool(true);   // use the global tree
+  lf_global.Bool(true);   // default weighted-predictor parameters
+  lf_global.U32(WV(0), WV(1), WB(4, 2), WB(8, 18), im.ll_rct ? 1 : 0);
+  if (im.ll_rct) {
+    lf_global.Write(2, 0);                                            // transform id 0: reversible colour transform
+    lf_global.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);      // first channel
+    lf_global.U32(WV(6), WB(2), WB(4, 2), WB(6, 10), 6);              // type 6: YCoCg-R
+  }
 }
 
 // The stream of efforts 1..7: 256x256 groups, YCoCg-R for RGB, gradient predictor, one context per channel.  `progress` (may be
@@ -375,28 +425,9 @@ std::vector<uint8_t> CodeLosslessFixed(EncImage& im, const EncSource& src, Arena
   std::vector<uint32_t> hist(4 * kEncSyms);
   ENC_HIP(hipMemcpy(hist.data(), im.hist_mod, hist.size() * 4, hipMemcpyDeviceToHost));
   Progress(progress, 25);
-  // LfGlobal: tree on the channel index (leaf ids: channel 3, 2, 1, 0), code, GlobalModular header
   BitWriter lf_global;
   EncCode mcode;
-  lf_global.Bool(true);   // default LF dequantisation factors (read for every frame encoding)
-  lf_global.Bool(true);   // global MA tree
-  {
-    std::vector<EncTreeNode> t;
-    t.push_back(EncTreeNode{0, 1, 0, 0, 1});     // 0: channel > 1 ? 1 : 2
-    t.push_back(EncTreeNode{0, 2, 0, 0, 1});     // 1: channel > 2 ? 3 : 4
-    t.push_back(EncTreeNode{0, 0, 0, 0, 1});     // 2: channel > 0 ? 5 : 6
-    for (int i = 0; i < 4; i++) t.push_back(EncTreeNode{-1, 0, 5, 0, 1});   // gradient predictor leaves: channel 3, 2, 1, 0
-    WriteTree(t, lf_global);
-  }
-  BuildAndWriteCode(hist.data(), 4, 4, {}, lf_global, mcode);
-  lf_global.Bool(true);   // use the global tree
-  lf_global.Bool(true);   // default weighted-predictor parameters
-  lf_global.U32(WV(0), WV(1), WB(4, 2), WB(8, 18), im.ll_rct ? 1 : 0);
-  if (im.ll_rct) {
-    lf_global.Write(2, 0);                                            // transform id 0: reversible colour transform
-    lf_global.U32(WB(3), WB(6, 8), WB(10, 72), WB(13, 1096), 0);      // first channel
-    lf_global.U32(WV(6), WB(2), WB(4, 2), WB(6, 10), 6);              // type 6: YCoCg-R
-  }
+  WriteLosslessFixedGlobal(im, hist.data(), lf_global, mcode);
   return FinishLossless(im, src, A, mcode, lf_global, md, s);
 }
 
@@ -690,11 +721,9 @@ void EncodeLossless(const EncSource& src, const EncoderOptions* opt, const Encod
   hipStream_t s = nullptr;
   EncImage im;
   BeginImage(src, md, A, im, progress);
-  const size_t npx = (size_t)im.w * im.h;
   im.lossless = 1;
   im.ll_nch = (im.gray ? 1 : 3) + im.has_alpha;
-  for (int c = 0; c < im.ll_nch; c++) im.ll_plane[c] = A.Get<int32_t>(npx);
-  im.tok_ll = A.Get<DevToken>((size_t)im.ng * kLlTokCap);
+  LayLosslessPlanes(A, im);
   Progress(progress, 15);
   // the search keys palettes and candidates on bytes: samples of more than 8 bits get the fixed stream at every effort
   const int tier = src.deep() ? 0 : (opt->effort >= 9 ? 9 : (opt->effort >= 8 ? 8 : 0));
@@ -748,32 +777,16 @@ struct ReconDecoder {
   }
 };
 
-void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
-  Arena A;
-  hipStream_t s = nullptr;
-  EncImage im;
-  PhaseClock clk;
-  BeginImage(src, md, A, im, progress);
-  if (md->iccProfile && md->iccProfileSize) {
-    // Lossy with a profile: the samples reach XYB through the profile (the reference leaves that to its encoder library's colour
-    // management, Encoder/JxlEncoder.cpp:258-268).  Matrix / TRC profiles are evaluated here; a profile that would need a full
-    // colour management system cannot be encoded lossily without misrepresenting its colours.
-    IccModel model;
-    if (!IccBuildModel(md->iccProfile, md->iccProfileSize, &model) || model.gray)
-      throw EncFail(EncoderStatus_EncodeError, "this ICC profile is not an RGB matrix/TRC profile: lossy saving needs a full colour management system (save lossless instead)");
-    std::vector<float> lin;
-    for (int c = 0; c < 3; c++) lin.insert(lin.end(), model.to_linear[c].begin(), model.to_linear[c].end());
-    float* d_lin = A.Get<float>(lin.size());
-    ENC_HIP(hipMemcpy(d_lin, lin.data(), lin.size() * 4, hipMemcpyHostToDevice));
-    im.icc_lin = d_lin;
-    for (int k = 0; k < 9; k++) im.icc_to_srgb[k] = (float)model.to_linear_srgb[k];
-  }
-  clk.Lap("upload + analysis");
-  const uint32_t w = src.width(), h = src.height();
-  const size_t npx = (size_t)w * h, npad = (size_t)im.wp * im.hp, ncell = (size_t)im.w8 * im.h8;
-  // ---- 2. quantiser and loop-filter parameters (distance, :319); the effort picks the transform set below
-  const float distance = std::max(0.05f, std::min(25.0f, opt->distance));
+// What the distance and the effort of a lossy save fix before any pixel is looked at
+struct LossyParams {
   EncFrameInfo fi;
+  uint32_t global_scale, quant_lf;
+};
+// quantiser and loop-filter parameters (distance, :319); the effort picks the transform set
+LossyParams SetLossyParams(const EncoderOptions* opt, EncImage& im) {
+  LossyParams qp;
+  EncFrameInfo& fi = qp.fi;
+  const float distance = std::max(0.05f, std::min(25.0f, opt->distance));
   fi.encoding = 0;
   fi.gab = true;
   fi.epf_iters = 0;
@@ -799,6 +812,12 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
   // fast settings (1..4) keep every block an 8x8 DCT; 5 and 6 add 16x16 / 32x32 DCTs on flat regions; from 7 (the host's default) the
   // 64x64 and the rectangular 16x8 ... 64x32 shapes join; 8 and 9 keep that set and correct the quant field in a closed loop (below)
   im.squares = opt->effort >= 7 ? 2 : (opt->effort >= 5 ? 1 : 0);
+  qp.global_scale = global_scale; qp.quant_lf = quant_lf;
+  return qp;
+}
+
+// The tables the front end reads (see EncImage), uploaded through `A`
+void UploadEncTables(Arena& A, EncImage& im) {
   const StaticTables& st = GetStaticTables();
   {
     for (auto& q : im.scan_of) q = nullptr;
@@ -833,20 +852,106 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
           for (int kx = 0; kx < (1 << lx); kx++) rs[(ly * 4 + lx) * 64 + ky * 8 + kx] = (float)(resample(1 << ly, ky) * resample(1 << lx, kx));
     im.rs = A.Upload(rs);
   }
-  // ---- 3. planes, front end
-  for (int c = 0; c < 3; c++) {
-    im.xyb[c] = A.Get<float>(npx);
-    im.pad[c] = A.Get<float>(npad);
-    im.lfq[c] = A.Get<int32_t>(ncell);
-    im.qs[c] = A.Get<int32_t>(ncell * 64);
-    im.nz[c] = A.Get<uint8_t>(ncell);
-    im.nzc[c] = A.Get<uint16_t>(ncell);
-    im.last[c] = A.Get<uint16_t>(ncell);
+}
+
+// the same tables for another image: they depend on nothing of it
+void CopyEncTables(const EncImage& from, EncImage& to) {
+  memcpy(to.scan_of, from.scan_of, sizeof(to.scan_of));
+  memcpy(to.dq, from.dq, sizeof(to.dq));
+  memcpy(to.basis, from.basis, sizeof(to.basis));
+  memcpy(to.basis_div, from.basis_div, sizeof(to.basis_div));
+  memcpy(to.bsmall, from.bsmall, sizeof(to.bsmall));
+  to.rs = from.rs;
+}
+
+// LfGlobal of a lossy frame up to and including the Modular code: quantiser, MA tree, the code of the Modular streams' token
+// histograms hist_mod[kNumEncLeaves][kEncSyms], and the global Modular image header of a frame with alpha.
+void WriteLossyLfGlobal(const EncImage& im, const LossyParams& qp, const uint32_t* hist_mod, BitWriter& lf_global, EncCode& mcode) {
+  lf_global.Bool(true);   // default LF dequantisation factors
+  lf_global.U32(WB(11, 1), WB(11, 2049), WB(12, 4097), WB(16, 8193), qp.global_scale);
+  lf_global.U32(WV(16), WB(5, 1), WB(8, 1), WB(16, 1), qp.quant_lf);
+  lf_global.Bool(true);   // default block-context map
+  lf_global.Bool(true);   // default LF chroma-from-luma parameters
+  lf_global.Bool(true);   // global MA tree
+  WriteTree(MakeEncoderTree((uint32_t)im.nlf), lf_global);
+  {
+    std::vector<uint8_t> pinned(kNumEncLeaves, 0);
+    pinned[kLeafSharp] = pinned[kLeafCfl] = 1;   // constant channels: no token is ever written
+    pinned[kLeafStrategy] = im.squares ? 0 : 1;  // ... and so is the strategy row while every block is an 8x8 DCT
+    BuildAndWriteCode(hist_mod, kNumEncLeaves, kEncModClusters, pinned, lf_global, mcode);
   }
-  im.rawq = A.Get<int32_t>(ncell);
-  im.act = A.Get<float>(ncell);
-  im.strat = A.Get<uint8_t>(ncell);
-  if (im.has_alpha) im.alpha_px = A.Get<int32_t>(npx);
+  if (im.has_alpha) lf_global.Write(4, 3);   // global Modular image header: global tree, default predictor, no transforms
+}
+
+// HfGlobal: default matrices, one preset, natural orders, the code of the HF token histograms hist_ac[kAcContexts][kEncSyms]
+void WriteLossyHfGlobal(const EncImage& im, const uint32_t* hist_ac, BitWriter& hf_global, EncCode& acode) {
+  hf_global.Bool(true);                      // default dequantisation matrices
+  hf_global.Write(im.ng <= 1 ? 0 : 32 - __builtin_clz((unsigned)(im.ng - 1)), 0);   // one HF preset
+  hf_global.U32(WV(0x5F), WV(0x13), WV(0), WB(kNumOrders), 0);                       // natural coefficient orders
+  BuildAndWriteCode(hist_ac, kAcContexts, kEncHfClusters, {}, hf_global, acode);
+}
+
+// The codestream of a lossy frame from its finished LfGlobal and HfGlobal and the coded sections: packed + off[s], sec_bits[s] for
+// section s (LF groups, groups, then the global alpha stream of a one-group frame).
+std::vector<uint8_t> AssembleLossy(const EncImage& im, const EncImageInfo& ii, const EncFrameInfo& fi, BitWriter& lf_global, BitWriter& hf_global,
+                                   const uint8_t* packed, const uint64_t* off, const uint64_t* sec_bits) {
+  BitWriter cs;
+  WriteCodestreamHeaders(ii, cs);
+  WriteFrameHeader(ii, fi, cs);
+  auto bytes = [&](int sec) { return std::vector<uint8_t>(packed + off[sec], packed + off[sec] + ((sec_bits[sec] + 7) >> 3)); };
+  std::vector<std::vector<uint8_t>> sections;
+  if (im.ng == 1) {
+    // LfGlobal | LfGroup | HfGlobal | PassGroup share one bit stream
+    if (im.has_alpha) lf_global.AppendBits(packed + off[im.nlf + im.ng], sec_bits[im.nlf + im.ng]);
+    const uint64_t hg_bits = hf_global.BitCount();
+    std::vector<uint8_t> hg = hf_global.Finish();
+    lf_global.AppendBits(packed + off[0], sec_bits[0]);
+    lf_global.AppendBits(hg.data(), hg_bits);
+    lf_global.AppendBits(packed + off[1], sec_bits[1]);
+    sections.push_back(lf_global.Finish());
+  } else {
+    sections.push_back(lf_global.Finish());
+    for (int g = 0; g < im.nlf; g++) sections.push_back(bytes(g));
+    sections.push_back(hf_global.Finish());
+    for (int g = 0; g < im.ng; g++) sections.push_back(bytes(im.nlf + g));
+  }
+  std::vector<uint32_t> sizes;
+  for (auto& sec : sections) sizes.push_back((uint32_t)sec.size());
+  WriteToc(sizes, cs);
+  std::vector<uint8_t> out = cs.Finish();
+  for (auto& sec : sections) out.insert(out.end(), sec.begin(), sec.end());
+  return out;
+}
+
+void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
+  Arena A;
+  hipStream_t s = nullptr;
+  EncImage im;
+  PhaseClock clk;
+  BeginImage(src, md, A, im, progress);
+  if (md->iccProfile && md->iccProfileSize) {
+    // Lossy with a profile: the samples reach XYB through the profile (the reference leaves that to its encoder library's colour
+    // management, Encoder/JxlEncoder.cpp:258-268).  Matrix / TRC profiles are evaluated here; a profile that would need a full
+    // colour management system cannot be encoded lossily without misrepresenting its colours.
+    IccModel model;
+    if (!IccBuildModel(md->iccProfile, md->iccProfileSize, &model) || model.gray)
+      throw EncFail(EncoderStatus_EncodeError, "this ICC profile is not an RGB matrix/TRC profile: lossy saving needs a full colour management system (save lossless instead)");
+    std::vector<float> lin;
+    for (int c = 0; c < 3; c++) lin.insert(lin.end(), model.to_linear[c].begin(), model.to_linear[c].end());
+    float* d_lin = A.Get<float>(lin.size());
+    ENC_HIP(hipMemcpy(d_lin, lin.data(), lin.size() * 4, hipMemcpyHostToDevice));
+    im.icc_lin = d_lin;
+    for (int k = 0; k < 9; k++) im.icc_to_srgb[k] = (float)model.to_linear_srgb[k];
+  }
+  clk.Lap("upload + analysis");
+  const uint32_t w = src.width(), h = src.height();
+  const size_t npx = (size_t)w * h, npad = (size_t)im.wp * im.hp, ncell = (size_t)im.w8 * im.h8;
+  // ---- 2. quantiser and loop-filter parameters, transform set, tables
+  const LossyParams qp = SetLossyParams(opt, im);
+  const EncFrameInfo& fi = qp.fi;
+  UploadEncTables(A, im);
+  // ---- 3. planes, front end
+  LayLossyPlanes(A, im);
   Progress(progress, 15);
   clk.Lap("allocation");
   StageMarks marks;
@@ -855,19 +960,8 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
   Progress(progress, 20);
   // ---- 4. .. 7. are CodeField below: everything that follows from the quantised data.  Efforts up to 7 run it once; the closed loop
   // of efforts 8 and 9 runs it once per evaluation.  Its buffers are allocated here, its counters cleared at every run.
-  im.tok_lf = A.Get<DevToken>((size_t)im.nlf * kLfTokCap);
-  im.tok_meta = A.Get<DevToken>((size_t)im.nlf * kMetaTokCap);
-  im.tok_ac = A.Get<DevToken>((size_t)im.ng * kAcTokCap);
-  if (im.has_alpha) im.tok_alpha = A.Get<DevToken>((size_t)im.ng * kAlphaTokCap);
-  im.n_ac = A.Get<uint32_t>(im.ng);
-  im.n_meta = A.Get<uint32_t>(im.nlf);
-  im.hist_mod = A.Get<uint32_t>(kNumEncLeaves * kEncSyms);
-  im.hist_ac = A.Get<uint32_t>((size_t)kAcContexts * kEncSyms);
-  const int nsec = im.nlf + im.ng + 1;   // + the global alpha stream of single-group frames
-  im.sec_cap = ((size_t)std::max(kLfTokCap + kMetaTokCap, kAcTokCap + kAlphaTokCap) * kSecBytesPerTok + 256) & ~(size_t)15;
-  im.sec_bytes = A.Get<uint8_t>((size_t)nsec * im.sec_cap);
-  im.sec_bits = A.Get<uint64_t>(nsec);
-  im.stream_state = A.Get<uint32_t>((size_t)2 * (im.nlf + im.ng) + 1);
+  LayLossyCoding(A, im);
+  const int nsec = EncNumSections(im);   // + the global alpha stream of single-group frames
   // The Modular streams' recurrences run on a stream of their own (the LF coefficients of an LF group are the longest of the frame),
   // the HF streams' beside them.
   hipStream_t s_ans = nullptr, s_hf = nullptr;
@@ -875,11 +969,7 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
   struct StreamGuard { hipStream_t s; ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } s_ans_guard{s_ans};
   ENC_HIP(hipStreamCreateWithFlags(&s_hf, hipStreamNonBlocking));
   StreamGuard s_hf_guard{s_hf};
-  const bool single = im.ng == 1;
-  EncImageInfo ii;
-  ii.xsize = w; ii.ysize = h; ii.gray = im.gray; ii.alpha = im.has_alpha; ii.xyb = true;
-  ii.icc = md->iccProfile; ii.icc_size = md->iccProfile ? md->iccProfileSize : 0;
-  src.Describe(ii);
+  const EncImageInfo ii = DescribeImage(im, src, md, true);
   // The codestream of the quantised data in `im`.  `final`: the call whose stream is (normally) written: it reports progress 25 and
   // 30; `mk`: where its kernel groups are timed (null: nowhere).
   auto CodeField = [&](bool final, StageMarks* mk, bool publish) -> std::vector<uint8_t> {
@@ -891,7 +981,7 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
     ENC_HIP(hipMemset(im.hist_mod, 0, kNumEncLeaves * kEncSyms * 4));
     ENC_HIP(hipMemset(im.hist_ac, 0, (size_t)kAcContexts * kEncSyms * 4));
     ENC_HIP(hipMemset(im.sec_bits, 0, std::max<size_t>((size_t)nsec * 8, 256)));
-    ENC_HIP(hipMemset(im.stream_state, 0, std::max<size_t>(((size_t)2 * (im.nlf + im.ng) + 1) * 4, 256)));
+    ENC_HIP(hipMemset(im.stream_state, 0, std::max<size_t>(EncNumStreamStates(im) * 4, 256)));
     // ---- 4. tokens + histograms
     { const size_t k = begin("tokens + histograms", s); LaunchEncTokens(im, s); end(k, s); }
     std::vector<uint32_t> hist_mod(kNumEncLeaves * kEncSyms), hist_ac((size_t)kAcContexts * kEncSyms);
@@ -902,31 +992,15 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
     // ---- 5. LfGlobal and HfGlobal (host): quantiser, MA tree, entropy codes
     BitWriter lf_global, hf_global;
     EncCode mcode, acode;
-    lf_global.Bool(true);   // default LF dequantisation factors
-    lf_global.U32(WB(11, 1), WB(11, 2049), WB(12, 4097), WB(16, 8193), global_scale);
-    lf_global.U32(WV(16), WB(5, 1), WB(8, 1), WB(16, 1), quant_lf);
-    lf_global.Bool(true);   // default block-context map
-    lf_global.Bool(true);   // default LF chroma-from-luma parameters
-    lf_global.Bool(true);   // global MA tree
-    WriteTree(MakeEncoderTree((uint32_t)im.nlf), lf_global);
-    {
-      std::vector<uint8_t> pinned(kNumEncLeaves, 0);
-      pinned[kLeafSharp] = pinned[kLeafCfl] = 1;   // constant channels: no token is ever written
-      pinned[kLeafStrategy] = im.squares ? 0 : 1;  // ... and so is the strategy row while every block is an 8x8 DCT
-      BuildAndWriteCode(hist_mod.data(), kNumEncLeaves, 8, pinned, lf_global, mcode);
-    }
+    WriteLossyLfGlobal(im, qp, hist_mod.data(), lf_global, mcode);
     clk.Lap("host: tree + modular code");
     // The Modular code is ready: start the recurrences of its streams on their stream, and build the HF code meanwhile.
     im.mcode = UploadCode(E, mcode);
     ENC_HIP(hipDeviceSynchronize());   // tokens, histogram downloads and the clears above are done before the other stream starts
     { const size_t k = begin("ans recurrences, Modular streams (LF, metadata, alpha)", s_ans); LaunchEncReverse(im, 0, s_ans); end(k, s_ans); }
-    if (im.has_alpha) lf_global.Write(4, 3);   // global Modular image header: global tree, default predictor, no transforms
-    hf_global.Bool(true);                      // default dequantisation matrices
-    hf_global.Write(im.ng <= 1 ? 0 : 32 - __builtin_clz((unsigned)(im.ng - 1)), 0);   // one HF preset
-    hf_global.U32(WV(0x5F), WV(0x13), WV(0), WB(kNumOrders), 0);                       // natural coefficient orders
     {
       const auto t0 = std::chrono::steady_clock::now();
-      BuildAndWriteCode(hist_ac.data(), kAcContexts, 64, {}, hf_global, acode);
+      WriteLossyHfGlobal(im, hist_ac.data(), hf_global, acode);
       if (clk.on) fprintf(stderr, "[enc] %-28s %8.2f ms (host only)\n", "HF code construction", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
     clk.Lap("host: HF code (overlaps the LF recurrences)");
@@ -963,31 +1037,7 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
     clk.Lap("compact + download");
     if (final) Progress(progress, 30);
     // ---- 7. codestream assembly
-    BitWriter cs;
-    WriteCodestreamHeaders(ii, cs);
-    WriteFrameHeader(ii, fi, cs);
-    std::vector<std::vector<uint8_t>> sections;
-    if (single) {
-      // LfGlobal | LfGroup | HfGlobal | PassGroup share one bit stream
-      if (im.has_alpha) lf_global.AppendBits(packed.data() + off[im.nlf + im.ng], sec_bits[im.nlf + im.ng]);
-      const uint64_t hg_bits = hf_global.BitCount();
-      std::vector<uint8_t> hg = hf_global.Finish();
-      lf_global.AppendBits(packed.data() + off[0], sec_bits[0]);
-      lf_global.AppendBits(hg.data(), hg_bits);
-      lf_global.AppendBits(packed.data() + off[1], sec_bits[1]);
-      sections.push_back(lf_global.Finish());
-    } else {
-      sections.push_back(lf_global.Finish());
-      for (int g = 0; g < im.nlf; g++) sections.emplace_back(packed.begin() + off[g], packed.begin() + off[g + 1]);
-      sections.push_back(hf_global.Finish());
-      for (int g = 0; g < im.ng; g++) sections.emplace_back(packed.begin() + off[im.nlf + g], packed.begin() + off[im.nlf + g + 1]);
-    }
-    std::vector<uint32_t> sizes;
-    for (auto& sec : sections) sizes.push_back((uint32_t)sec.size());
-    WriteToc(sizes, cs);
-    std::vector<uint8_t> out = cs.Finish();
-    for (auto& sec : sections) out.insert(out.end(), sec.begin(), sec.end());
-    return out;
+    return AssembleLossy(im, ii, fi, lf_global, hf_global, packed.data(), off.data(), sec_bits.data());
   };
   std::vector<uint8_t> codestream;
   const int corrections = opt->effort >= 9 ? 4 : (opt->effort >= 8 ? 2 : 0);
@@ -1238,4 +1288,436 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels
   } catch (...) {
     return EncoderStatus_EncodeError;
   }
+}
+
+// =====================================================================================================
+// Part 4 of the C-ABI: batch encode of device-resident images.  The flow of EncodeLossy / EncodeLossless reshaped into phases over
+// the whole batch ("Batch encode"): the per-image functions above do the work, this only orders it.
+// =====================================================================================================
+namespace {
+
+constexpr int kEncStreams = 4;        // the front ends of the images are spread over them; the batch kernels use them side by side
+constexpr int kEncHostThreads = 16;   // code construction and assembly of independent images (a constant: never the machine's core count)
+
+// fn(i) for i in [0, n) on up to kEncHostThreads threads; the first exception is rethrown on the caller's thread
+template <class F>
+void ParallelFor(int n, F fn) {
+  if (n <= 0) return;
+  std::atomic<int> next{0};
+  std::exception_ptr failed;
+  std::atomic<bool> has_failed{false};
+  auto work = [&]() {
+    for (int i = next++; i < n; i = next++) {
+      try { fn(i); } catch (...) { if (!has_failed.exchange(true)) failed = std::current_exception(); }
+    }
+  };
+  std::vector<std::thread> pool;
+  const int nt = std::min(n, kEncHostThreads);
+  try {
+    for (int t = 1; t < nt; t++) pool.emplace_back(work);
+  } catch (...) {}   // fewer threads than wanted: the ones that started, and this one, do the work
+  work();
+  for (auto& t : pool) t.join();
+  if (has_failed) std::rethrow_exception(failed);
+}
+
+// Appends `c` to the host image `blob` of a code region that begins at `d_region`; the device view of it.  256-byte alignment of
+// every array, as hipMalloc gives the arrays of the single-image path (EncCodeBytes counts it).
+EncCodeDev PackEncCode(const EncCode& c, std::vector<uint8_t>& blob, uint8_t* d_region) {
+  auto put = [&](const void* p, size_t bytes) {
+    const size_t o = (blob.size() + 255) & ~(size_t)255;
+    blob.resize(o + bytes);
+    if (bytes) memcpy(blob.data() + o, p, bytes);
+    return d_region + o;
+  };
+  EncCodeDev d;
+  d.ctx_map = put(c.ctx_map.data(), c.ctx_map.size());
+  d.freq = (const uint16_t*)put(c.freq.data(), c.freq.size() * 2);
+  d.start = (const uint16_t*)put(c.start.data(), c.start.size() * 2);
+  d.rmap = (const uint16_t*)put(c.rmap.data(), c.rmap.size() * 2);
+  d.num_clusters = c.num_clusters;
+  d.num_ctx = (uint32_t)c.ctx_map.size();
+  return d;
+}
+
+// pinned host memory that grows to the largest request and is reused
+struct PinnedBuffer {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  ~PinnedBuffer() { if (p) (void)hipHostFree(p); }
+  bool Reserve(size_t bytes) {   // true: it had to grow
+    if (bytes <= cap) return false;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 4;
+    ENC_HIP(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
+    cap = want;
+    return true;
+  }
+};
+struct DeviceBuffer {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+  bool Reserve(size_t bytes, bool slack) {
+    if (bytes <= cap) return false;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = slack ? bytes + bytes / 4 : bytes;
+    ENC_HIP(hipMalloc((void**)&p, want));
+    cap = want;
+    return true;
+  }
+};
+
+double MsSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// one accepted image of a batch
+struct BatchJob {
+  int index = 0;               // in the caller's arrays
+  EncSource src;
+  EncoderImageMetadata md;
+  EncoderOptions opt;
+  bool lossless = false;
+  LossyParams qp;
+  BitWriter lf_global, hf_global;
+  EncCode mcode, acode;
+  size_t first_section = 0;    // of the batch's section list
+};
+
+}  // namespace
+
+struct JxlHipEncoder {
+  int device = 0;
+  hipStream_t streams[kEncStreams] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t fork = nullptr, join[kEncStreams] = {nullptr, nullptr, nullptr, nullptr};
+  Arena tables;                // the front end's tables, uploaded once
+  EncImage table_ptrs;         // an EncImage that holds nothing but their pointers
+  DeviceBuffer ws, packed;     // the workspace (enc_batch_layout.h); the compaction's destination
+  PinnedBuffer h_hist, h_packed;
+  std::vector<std::vector<uint8_t>> files;   // the results of the last batch
+  std::vector<std::pair<const char*, float>> stages;
+
+  explicit JxlHipEncoder(int dev) {
+    if (dev >= 0) ENC_HIP(hipSetDevice(dev));
+    ENC_HIP(hipGetDevice(&device));
+    try {
+      for (auto& s : streams) ENC_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      ENC_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+      for (auto& e : join) ENC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      memset(&table_ptrs, 0, sizeof(table_ptrs));
+      UploadEncTables(tables, table_ptrs);
+    } catch (...) {
+      Release();
+      throw;
+    }
+  }
+  ~JxlHipEncoder() { Release(); }
+  JxlHipEncoder(const JxlHipEncoder&) = delete;
+  JxlHipEncoder& operator=(const JxlHipEncoder&) = delete;
+  void Release() {
+    for (auto& s : streams) if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); s = nullptr; }
+    if (fork) { (void)hipEventDestroy(fork); fork = nullptr; }
+    for (auto& e : join) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  }
+  void WaitAll() { for (auto& s : streams) (void)hipStreamSynchronize(s); }
+  // streams[to] continues once everything enqueued so far on the streams `from` (a bit mask) is done
+  void Join(unsigned from, int to) {
+    for (int k = 0; k < kEncStreams; k++) {
+      if (!((from >> k) & 1) || k == to) continue;
+      ENC_HIP(hipEventRecord(join[k], streams[k]));
+      ENC_HIP(hipStreamWaitEvent(streams[to], join[k], 0));
+    }
+  }
+  // every stream continues once everything enqueued so far on streams[from] is done
+  void Fork(int from) {
+    ENC_HIP(hipEventRecord(fork, streams[from]));
+    for (int k = 0; k < kEncStreams; k++) if (k != from) ENC_HIP(hipStreamWaitEvent(streams[k], fork, 0));
+  }
+  void Run(std::vector<BatchJob>& jobs);
+};
+
+// The accepted images of a batch, start to finish.  Throws EncFail for what fails the whole batch (device errors, out of memory).
+void JxlHipEncoder::Run(std::vector<BatchJob>& jobs) {
+  const int n = (int)jobs.size();
+  StageMarks marks;
+  std::vector<std::pair<const char*, float>> host_stages;
+  auto t0 = std::chrono::steady_clock::now();
+  auto host_stage = [&](const char* name) { host_stages.push_back({name, (float)MsSince(t0)}); t0 = std::chrono::steady_clock::now(); };
+  hipStream_t s0 = streams[0], s_ans = streams[1], s_ll = streams[2], s_ga = streams[3];
+  // ---- 1. geometry, layout, records
+  std::vector<EncBatchItem> items((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const JxlHipPixels& px = *jobs[i].src.px;
+    items[i] = EncBatchItem{px.width, px.height, px.num_channels, (int32_t)jobs[i].src.sample_bytes(), jobs[i].lossless ? 1 : 0, 0};
+  }
+  std::vector<EncImage> ims((size_t)n);
+  EncBatchLayout lay;
+  LayEncBatch(items.data(), n, nullptr, ims.data(), &lay);   // measures
+  host_stage("host: checks and layout");
+  if (ws.Reserve(lay.total_bytes, false)) host_stage("host: workspace allocation");
+  LayEncBatch(items.data(), n, ws.p, ims.data(), &lay);      // places
+  const size_t hist_bytes = lay.region[kEncSecBits] - lay.region[kEncHist], secbits_bytes = lay.region[kEncCount] - lay.region[kEncSecBits];
+  if (h_hist.Reserve(std::max(hist_bytes, secbits_bytes))) host_stage("host: pinned buffer allocation");
+  // the tables of the batch kernels: which images each covers, and where each image's share of its grid begins
+  const size_t tstride = EncBatchTableStride(n);
+  std::vector<uint8_t> up1(lay.records_a - lay.tables, 0);   // host image of the first upload: tables | records | Modular codes
+  enum { kTabReverseMod = 0, kTabReverseHf = 1, kTabSections = 2, kTabLl = 3, kTabGlobalAlpha = 4, kTabCompact = 5 };
+  EncBatchTable tab[kEncBatchTables];
+  uint32_t units[kEncBatchTables] = {0, 0, 0, 0, 0, 0};
+  const int per_wg = EncSectionsPerWg();
+  for (int t = 0; t < kEncBatchTables; t++) {
+    uint32_t* first = (uint32_t*)(up1.data() + (size_t)(3 * t) * tstride);
+    int32_t* image_of = (int32_t*)(up1.data() + (size_t)(3 * t + 1) * tstride);
+    uint32_t* wg0 = (uint32_t*)(up1.data() + (size_t)(3 * t + 2) * tstride);
+    int entries = 0;
+    auto add = [&](int i, uint32_t from, uint32_t to) {   // workgroups [from, to) of image i
+      if (to <= from) return;
+      first[entries] = units[t]; image_of[entries] = i; wg0[entries] = from;
+      entries++;
+      units[t] += to - from;
+    };
+    // the streams of a lossy frame are numbered LF groups first (encode_kernels.hip: LossyStream): these workgroups hold its LF streams
+    auto lf_wgs = [&](const EncImage& im) { return (uint32_t)((2 * im.nlf + per_wg - 1) / per_wg); };
+    auto reverse_wgs = [&](const EncImage& im) { return (uint32_t)((2 * (im.nlf + im.ng) + per_wg - 1) / per_wg); };
+    if (t == kTabReverseMod) {
+      // the LF coefficients of an LF group are the longest recurrence of a frame: those of every image start first, side by side
+      for (int i = 0; i < n; i++) if (!ims[i].lossless) add(i, 0, std::min(lf_wgs(ims[i]), reverse_wgs(ims[i])));
+      for (int i = 0; i < n; i++) if (!ims[i].lossless) add(i, std::min(lf_wgs(ims[i]), reverse_wgs(ims[i])), reverse_wgs(ims[i]));
+    } else {
+      for (int i = 0; i < n; i++) {
+        const EncImage& im = ims[i];
+        switch (t) {
+          case kTabReverseHf: if (!im.lossless) add(i, 0, reverse_wgs(im)); break;
+          case kTabSections: if (!im.lossless) add(i, 0, (uint32_t)((im.nlf + im.ng + per_wg - 1) / per_wg)); break;
+          case kTabLl: if (im.lossless) add(i, 0, (uint32_t)((im.ng + per_wg - 1) / per_wg)); break;
+          case kTabGlobalAlpha: if (!im.lossless && im.has_alpha && im.ng == 1) add(i, 0, 1); break;
+          default: add(i, 0, (uint32_t)EncNumSections(im)); break;
+        }
+      }
+    }
+    tab[t].first = (const uint32_t*)(ws.p + lay.tables + (size_t)(3 * t) * tstride);
+    tab[t].image_of = (const int32_t*)(ws.p + lay.tables + (size_t)(3 * t + 1) * tstride);
+    tab[t].wg0 = (const uint32_t*)(ws.p + lay.tables + (size_t)(3 * t + 2) * tstride);
+    tab[t].entries = entries; tab[t].pad = 0;
+  }
+  {
+    size_t sec = 0;
+    for (int i = 0; i < n; i++) { jobs[i].first_section = sec; sec += (size_t)EncNumSections(ims[i]); }
+  }
+  host_stage("host: records and tables");
+  // ---- 2. per image, spread over the streams: pixels into tight rows, front end, tokens and histograms
+  ENC_HIP(hipMemsetAsync(ws.p, 0, lay.head_bytes, s0));   // every counter and histogram of the batch
+  Fork(0);
+  const size_t k_front = marks.Begin("pixels, front end, tokens + histograms (per image, on four streams)", s0);
+  for (int i = 0; i < n; i++) {
+    BatchJob& job = jobs[i];
+    EncImage& im = ims[i];
+    hipStream_t s = streams[i % kEncStreams];
+    const JxlHipPixels& px = *job.src.px;
+    const size_t row = (size_t)px.width * px.num_channels * job.src.sample_bytes();
+    uint8_t* d_src = ws.p + lay.slots[i].src;
+    // tight, 256-byte aligned rows whatever the caller's pointer and stride are: what the loaders of encode_kernels.hip rely on
+    ENC_HIP(hipMemcpy2DAsync(d_src, row, px.data, px.stride_bytes, row, px.height, hipMemcpyDeviceToDevice, s));
+    SetPixelSource(job.src, d_src, ws.p + lay.slots[i].surface, im, s);
+    if (job.lossless) {
+      im.ll_rct = im.gray ? 0 : 1;
+      im.ll_tok_extra = 0;
+      LaunchEncLossless(im, 0, s);
+    } else {
+      job.qp = SetLossyParams(&job.opt, im);
+      CopyEncTables(table_ptrs, im);
+      LaunchEncFrontEnd(im, s);
+      LaunchEncTokens(im, s);
+    }
+  }
+  Join(~0u, 0);
+  marks.End(k_front, s0);
+  { const size_t k = marks.Begin("histogram download (one copy)", s0); ENC_HIP(hipMemcpyAsync(h_hist.p, ws.p + lay.region[kEncHist], hist_bytes, hipMemcpyDeviceToHost, s0)); marks.End(k, s0); }
+  ENC_HIP(hipStreamSynchronize(s0));   // the one synchronisation before the codes
+  host_stage("host: enqueue and wait for the histograms");
+  auto host_hist = [&](const uint32_t* dev) { return (const uint32_t*)(h_hist.p + ((const uint8_t*)dev - (ws.p + lay.region[kEncHist]))); };
+  // ---- 3a. the Modular codes of every image; up they go with the records, and the recurrences that need nothing else start
+  ParallelFor(n, [&](int i) {
+    BatchJob& job = jobs[i];
+    if (job.lossless) WriteLosslessFixedGlobal(ims[i], host_hist(ims[i].hist_mod), job.lf_global, job.mcode);
+    else WriteLossyLfGlobal(ims[i], job.qp, host_hist(ims[i].hist_mod), job.lf_global, job.mcode);
+  });
+  host_stage("host: Modular code construction");
+  size_t lds_m = 0, lds_ll = 0;
+  {
+    std::vector<uint8_t> blob;
+    for (int i = 0; i < n; i++) {
+      ims[i].mcode = PackEncCode(jobs[i].mcode, blob, ws.p + lay.mcodes);
+      size_t& lds = jobs[i].lossless ? lds_ll : lds_m;
+      lds = std::max(lds, EncReverseLds(ims[i].mcode.num_clusters, ims[i].mcode.num_ctx, 0));
+    }
+    if (blob.size() > lay.records_a - lay.mcodes) throw EncFail(EncoderStatus_EncodeError, "the Modular codes outgrew their room");
+    memcpy(up1.data() + (lay.records_m - lay.tables), ims.data(), (size_t)n * sizeof(EncImage));
+    memcpy(up1.data() + (lay.mcodes - lay.tables), blob.data(), blob.size());
+    ENC_HIP(hipMemcpyAsync(ws.p + lay.tables, up1.data(), (lay.mcodes - lay.tables) + blob.size(), hipMemcpyHostToDevice, s_ans));
+  }
+  const EncImage* d_ims_m = (const EncImage*)(ws.p + lay.records_m);
+  const EncImage* d_ims_a = (const EncImage*)(ws.p + lay.records_a);
+  Fork(1);
+  { const size_t k = marks.Begin("reverse pass, Modular streams of every image (one launch)", s_ans); LaunchEncReverseBatch(d_ims_m, tab[kTabReverseMod], units[kTabReverseMod], 0, lds_m, s_ans); marks.End(k, s_ans); }
+  { const size_t k = marks.Begin("lossless sections of every image (one launch)", s_ll); LaunchEncLlSectionsBatch(d_ims_m, tab[kTabLl], units[kTabLl], lds_ll, s_ll); marks.End(k, s_ll); }
+  { const size_t k = marks.Begin("global alpha sections (one launch)", s_ga); LaunchEncGlobalAlphaBatch(d_ims_m, tab[kTabGlobalAlpha], s_ga); marks.End(k, s_ga); }
+  host_stage("host: Modular code upload and launches");
+  // ---- 3b. the HF codes, built while the Modular streams' recurrences run
+  std::vector<int> lossy;
+  for (int i = 0; i < n; i++) if (!jobs[i].lossless) lossy.push_back(i);
+  ParallelFor((int)lossy.size(), [&](int k) {
+    const int i = lossy[k];
+    WriteLossyHfGlobal(ims[i], host_hist(ims[i].hist_ac), jobs[i].hf_global, jobs[i].acode);
+  });
+  host_stage("host: HF code construction");
+  size_t lds_a = 0;
+  {
+    std::vector<uint8_t> up2(lay.acodes - lay.records_a, 0);   // records | HF codes
+    std::vector<uint8_t> blob;
+    for (int i : lossy) {
+      ims[i].acode = PackEncCode(jobs[i].acode, blob, ws.p + lay.acodes);
+      lds_a = std::max(lds_a, EncReverseLds(ims[i].acode.num_clusters, ims[i].acode.num_ctx, 1));
+    }
+    if (blob.size() > lay.dst_off - lay.acodes) throw EncFail(EncoderStatus_EncodeError, "the HF codes outgrew their room");
+    memcpy(up2.data(), ims.data(), (size_t)n * sizeof(EncImage));
+    up2.insert(up2.end(), blob.begin(), blob.end());
+    ENC_HIP(hipMemcpyAsync(ws.p + lay.records_a, up2.data(), up2.size(), hipMemcpyHostToDevice, s0));
+    ENC_HIP(hipStreamSynchronize(s0));   // up2 leaves scope; the copy from pageable memory has been staged by then anyway
+  }
+  // ---- 4. reverse passes of the HF streams, bit layout of every section, compaction, download
+  { const size_t k = marks.Begin("reverse pass, HF streams of every image (one launch)", s0); LaunchEncReverseBatch(d_ims_a, tab[kTabReverseHf], units[kTabReverseHf], 1, lds_a, s0); marks.End(k, s0); }
+  Join(1u << 1, 0);   // the section layout needs the states of both kinds of stream
+  { const size_t k = marks.Begin("section bit layout of every image (one launch)", s0); LaunchEncSectionsBatch(d_ims_a, tab[kTabSections], units[kTabSections], s0); marks.End(k, s0); }
+  Join((1u << 2) | (1u << 3), 0);
+  ENC_HIP(hipMemcpyAsync(h_hist.p, ws.p + lay.region[kEncSecBits], secbits_bytes, hipMemcpyDeviceToHost, s0));
+  ENC_HIP(hipStreamSynchronize(s0));
+  host_stage("host: HF code upload, launches and wait for the sections");
+  auto host_bits = [&](const uint64_t* dev) { return (const uint64_t*)(h_hist.p + ((const uint8_t*)dev - (ws.p + lay.region[kEncSecBits]))); };
+  std::vector<uint64_t> off(lay.total_sections + 1, 0);
+  for (int i = 0; i < n; i++) {
+    const uint64_t* bits = host_bits(ims[i].sec_bits);
+    const int nsec = EncNumSections(ims[i]);
+    for (int k = 0; k < nsec; k++) off[jobs[i].first_section + k + 1] = off[jobs[i].first_section + k] + ((bits[k] + 7) >> 3);
+  }
+  const size_t packed_bytes = std::max<uint64_t>(off[lay.total_sections], 1);
+  {
+    const bool grew_d = packed.Reserve(packed_bytes, true), grew_h = h_packed.Reserve(packed_bytes);
+    if (grew_d || grew_h) host_stage("host: output buffer allocation");
+  }
+  ENC_HIP(hipMemcpyAsync(ws.p + lay.dst_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, s0));
+  { const size_t k = marks.Begin("compaction of every section (one launch)", s0); LaunchEncCompactBatch(d_ims_a, tab[kTabCompact], units[kTabCompact], (const uint64_t*)(ws.p + lay.dst_off), packed.p, s0); marks.End(k, s0); }
+  { const size_t k = marks.Begin("section download (one copy)", s0); ENC_HIP(hipMemcpyAsync(h_packed.p, packed.p, packed_bytes, hipMemcpyDeviceToHost, s0)); marks.End(k, s0); }
+  ENC_HIP(hipStreamSynchronize(s0));
+  ENC_HIP(hipGetLastError());
+  host_stage("host: compaction and download");
+  // ---- 5. codestream and container of every image
+  ParallelFor(n, [&](int i) {
+    BatchJob& job = jobs[i];
+    const uint64_t* o = off.data() + job.first_section;
+    const uint64_t* bits = host_bits(ims[i].sec_bits);
+    const std::vector<uint8_t> cs = job.lossless ? AssembleLossless(ims[i], job.src, &job.md, job.lf_global, h_packed.p, o, bits)
+                                                 : AssembleLossy(ims[i], DescribeImage(ims[i], job.src, &job.md, true), job.qp.fi, job.lf_global, job.hf_global, h_packed.p, o, bits);
+    files[(size_t)job.index] = WriteContainer(cs, job.md.exif, job.md.exifSize, job.md.xmp, job.md.xmpSize);
+  });
+  host_stage("host: assembly");
+  marks.Publish(&stages);
+  stages.insert(stages.end(), host_stages.begin(), host_stages.end());
+}
+
+extern "C" JXLFILETYPEIO_API JxlHipEncoder* jxlhip_encoder_create(int32_t device, ErrorInfo* err) {
+  try {
+    return new JxlHipEncoder(device);
+  } catch (const std::exception& e) {
+    SetEncErr(err, e.what());
+    return nullptr;
+  } catch (...) {
+    return nullptr;
+  }
+}
+
+extern "C" JXLFILETYPEIO_API void jxlhip_encoder_destroy(JxlHipEncoder* enc) { delete enc; }
+
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
+                                                               const EncoderImageMetadata* const* metadata, EncoderStatus* statuses, ErrorInfo* err) {
+  if (!enc || n < 0 || (n > 0 && (!images || !options || !statuses))) return EncoderStatus_NullParameter;
+  enc->files.assign((size_t)n, std::vector<uint8_t>());
+  enc->stages.clear();
+  EncoderStatus first = EncoderStatus_Ok;
+  auto report = [&](int i, EncoderStatus st, const char* what) {
+    if (first != EncoderStatus_Ok) return;
+    first = st;
+    if (st != EncoderStatus_EncodeError) return;
+    char msg[256];
+    snprintf(msg, sizeof(msg), "image %d: %s", i, what);
+    SetEncErr(err, msg);
+  };
+  // the refusals, per image, on the host, before any device work
+  std::vector<BatchJob> jobs;
+  jobs.reserve((size_t)n);
+  for (int i = 0; i < n; i++) {
+    statuses[i] = EncoderStatus_Ok;
+    BatchJob job;
+    job.index = i;
+    job.src.px = &images[i];
+    job.opt = options[i];
+    memset(&job.md, 0, sizeof(job.md));
+    if (metadata && metadata[i]) job.md = *metadata[i];
+    try {
+      CheckPixels(&images[i], &options[i], &job.md, job.src);
+      if (options[i].effort >= 8)
+        throw EncFail(EncoderStatus_EncodeError, "efforts 8 and 9 (the closed loop and the lossless search) are not available in a batch: use jxlhip_save_pixels");
+      job.lossless = options[i].lossless;
+      jobs.push_back(std::move(job));
+    } catch (const EncFail& e) {
+      statuses[i] = e.status;
+      report(i, e.status, e.what());
+    }
+  }
+  if (jobs.empty()) return first;
+  EncoderStatus failed = EncoderStatus_Ok;
+  std::string why;
+  int caller_device = enc->device;   // the calling thread's current device is restored before the call returns
+  (void)hipGetDevice(&caller_device);
+  try {
+    if (caller_device != enc->device) ENC_HIP(hipSetDevice(enc->device));
+    enc->Run(jobs);
+  } catch (const EncFail& e) {
+    failed = e.status; why = e.what();
+  } catch (const std::bad_alloc&) {
+    failed = EncoderStatus_OutOfMemory;
+  } catch (const std::exception& e) {
+    failed = EncoderStatus_EncodeError; why = e.what();
+  } catch (...) {
+    failed = EncoderStatus_EncodeError;   // never throw across the ABI
+  }
+  if (failed != EncoderStatus_Ok) {
+    // what fails on the device fails the batch: every accepted image reports it, and the encoder is left idle and usable
+    enc->WaitAll();
+    (void)hipGetLastError();
+    for (auto& job : jobs) { statuses[job.index] = failed; enc->files[(size_t)job.index].clear(); }
+    if (first == EncoderStatus_Ok) { first = failed; if (failed == EncoderStatus_EncodeError) SetEncErr(err, ("the batch: " + why).c_str()); }
+  }
+  if (caller_device != enc->device) (void)hipSetDevice(caller_device);
+  return first;
+}
+
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_result(JxlHipEncoder* enc, int32_t i, const uint8_t** data, size_t* size) {
+  if (!enc || i < 0 || (size_t)i >= enc->files.size() || enc->files[(size_t)i].empty()) return 0;
+  if (data) *data = enc->files[(size_t)i].data();
+  if (size) *size = enc->files[(size_t)i].size();
+  return 1;
+}
+
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_stage_times(JxlHipEncoder* enc, const char** names, float* ms, int32_t capacity) {
+  if (!enc) return 0;
+  int32_t k = 0;
+  for (auto& e : enc->stages) {
+    if (k >= capacity) break;
+    if (names) names[k] = e.first;
+    if (ms) ms[k] = e.second;
+    k++;
+  }
+  return k;
 }

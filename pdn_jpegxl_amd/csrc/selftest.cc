@@ -11,6 +11,7 @@
 #include "dev_util.h"
 #include "enc_types.h"
 #include "batch_layout.h"
+#include "enc_batch_layout.h"
 #include "entropy_plan.h"
 #include "host_parse.h"
 #include "host_write.h"
@@ -752,4 +753,58 @@ extern "C" JXLFILETYPEIO_API void jxlhip_selftest_wp(int32_t w, int32_t h, const
       r.Step(at(x, y), NE, x, y);
     }
   }
+}
+
+// ---- the workspace of a batch encode (csrc/enc_batch_layout.cc: LayEncBatch), measured and then placed at a made-up base.
+// items: 6 int32 per image (w, h, channels, bytes per sample, lossless, 0).  out (int64 each; returns how many the full answer takes):
+//   n; total bytes measured; total bytes placed; head bytes; the four region bounds; tables, records_m, mcodes, records_a, acodes, dst_off,
+//   body; total sections; sizeof(EncImage); kEncModCodeBytes; kEncHfCodeBytes; then per image: begin, end, src, surface, sections, count,
+//   and per non-null buffer pointer of its EncImage (in the order of `fields` below) the field's number, the offset the measuring pass
+//   gave it and the offset the placing pass gave it.
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_enc_batch_layout(int32_t n, const int32_t* items, int64_t* out, size_t capacity) {
+  std::vector<EncBatchItem> it((size_t)n);
+  for (int i = 0; i < n; i++)
+    it[i] = EncBatchItem{(uint32_t)items[6 * i], (uint32_t)items[6 * i + 1], items[6 * i + 2], items[6 * i + 3], items[6 * i + 4], 0};
+  std::vector<EncImage> a((size_t)n), b((size_t)n);
+  EncBatchLayout la, lb;
+  uint8_t* const base = (uint8_t*)((uintptr_t)2 << 44);
+  LayEncBatch(it.data(), n, nullptr, a.data(), &la);
+  LayEncBatch(it.data(), n, base, b.data(), &lb);
+  std::vector<int64_t> v;
+  v.push_back(n); v.push_back((int64_t)la.total_bytes); v.push_back((int64_t)lb.total_bytes); v.push_back((int64_t)lb.head_bytes);
+  for (int k = 0; k <= kNumEncCounterKinds; k++) v.push_back((int64_t)lb.region[k]);
+  for (size_t x : {lb.tables, lb.records_m, lb.mcodes, lb.records_a, lb.acodes, lb.dst_off, lb.body, lb.total_sections, sizeof(EncImage),
+                   kEncModCodeBytes, kEncHfCodeBytes}) v.push_back((int64_t)x);
+  auto fields = [](const EncImage& im) {
+    std::vector<const void*> f;
+    for (int c = 0; c < 3; c++) f.push_back(im.xyb[c]);
+    for (int c = 0; c < 3; c++) f.push_back(im.pad[c]);
+    f.push_back(im.alpha_px);
+    for (int c = 0; c < 3; c++) f.push_back(im.lfq[c]);
+    f.push_back(im.rawq); f.push_back(im.act); f.push_back(im.strat);
+    for (int c = 0; c < 3; c++) f.push_back(im.qs[c]);
+    for (int c = 0; c < 3; c++) f.push_back(im.nz[c]);
+    for (int c = 0; c < 3; c++) f.push_back(im.nzc[c]);
+    for (int c = 0; c < 3; c++) f.push_back(im.last[c]);
+    f.push_back(im.tok_lf); f.push_back(im.tok_meta); f.push_back(im.tok_ac); f.push_back(im.tok_alpha);
+    f.push_back(im.n_ac); f.push_back(im.n_meta); f.push_back(im.hist_mod); f.push_back(im.hist_ac);
+    for (int c = 0; c < 4; c++) f.push_back(im.ll_plane[c]);
+    f.push_back(im.tok_ll); f.push_back(im.sec_bytes); f.push_back(im.stream_state); f.push_back(im.sec_bits);
+    return f;
+  };
+  for (int i = 0; i < n; i++) {
+    const EncBatchSlot& sl = lb.slots[(size_t)i];
+    v.push_back((int64_t)sl.begin); v.push_back((int64_t)sl.end); v.push_back((int64_t)sl.src); v.push_back((int64_t)sl.surface);
+    v.push_back(EncNumSections(b[i]));
+    const std::vector<const void*> fa = fields(a[i]), fb = fields(b[i]);
+    const size_t at = v.size();
+    v.push_back(0);
+    for (size_t k = 0; k < fb.size(); k++) {
+      if (!fb[k]) continue;
+      v.push_back((int64_t)k); v.push_back((int64_t)(uintptr_t)fa[k]); v.push_back((int64_t)((uintptr_t)fb[k] - (uintptr_t)base));
+      v[at]++;
+    }
+  }
+  if (out) memcpy(out, v.data(), std::min(capacity, v.size()) * sizeof(int64_t));
+  return v.size();
 }
