@@ -145,6 +145,7 @@ struct JxlHipDecoder {
   // alpha groups of the lane path whose rows are all gradient rows keep their residuals as int16 between the two alpha phases while
   // |residual| <= this (a group with a larger one is decoded again as int32: same output either way); 0: int32 for all
   int alpha_narrow_limit = 32767;
+  int alpha_sample_limit = 255;   // largest sample the one-pass alpha form keeps (lower: ordinary files reach its give-up path)
   bool no_direct = false, mod_lanes64 = false;   // launch shapes of the vector loops for small launches too (parity tests: same output either way)
   bool overlap = true;
   // reduced-size decode: 1 = full size; 8 = every image of the next batches leaves at ceil(w / 8) x ceil(h / 8), one pixel
@@ -607,7 +608,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
 #endif
   Mark("hf_start", s_hf, 1);
-  // the narrow alpha residuals belong to the lane path (several sections per wavefront); one-section launches keep the scalar row loop
+  // alpha in one pass belongs to the lane path (several sections per wavefront); one-section launches keep the scalar row loop and two passes
   const int alpha_narrow = plan.direct_alpha ? 0 : alpha_narrow_limit;
   // Reduced-size decode: the HF tokens are read only to find what follows them in a pass-group section, i.e. for frames with alpha
   // (their pass tasks are the only ones listed); stages that do not run leave no entry in the stage times.
@@ -618,7 +619,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // necessarily; the main stream carries nothing but the pixel stages
   if (any_alpha && !(skip_stages & 4))
     LaunchAlphaAns(d_imgs, B.alpha_tasks, nalpha_t, plan.alpha_stride, plan.alpha.Bytes(), plan.direct_alpha, plan.lean_mod,
-                   alpha_narrow, s_hf);
+                   alpha_narrow, alpha_sample_limit, s_hf);
   if (!ds || any_alpha) Mark("alpha_ans", s_hf, 1);
   if (debug_taps && !ds) {   // the quantised coefficients as dense planes (every frame has its own planes in this mode)
     taps.assign(n, Tap());
@@ -631,7 +632,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   // while the HF stream was the longest it was the other way round - knob JXLHIP_ALPHA_FINISH_ON_PIX)
   const bool finish_on_hf = s_hf == stream || debug_taps || !Knob("JXLHIP_ALPHA_FINISH_ON_PIX");
   if (finish_on_hf) {
-    if (any_alpha && !(skip_stages & 4)) LaunchAlphaFinish(d_imgs, n, max_groups, alpha_narrow > 0, s_hf);
+    if (any_alpha && !(skip_stages & 4)) LaunchAlphaFinish(d_imgs, n, max_groups, s_hf);
     if (!ds || any_alpha) Mark("alpha_finish", s_hf, 1);
   }
   if (s_hf != stream) {
@@ -640,7 +641,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
   Mark("main_start", stream, 2);
   if (!finish_on_hf) {
-    if (any_alpha && !(skip_stages & 4)) LaunchAlphaFinish(d_imgs, n, max_groups, alpha_narrow > 0, stream);
+    if (any_alpha && !(skip_stages & 4)) LaunchAlphaFinish(d_imgs, n, max_groups, stream);
     Mark("alpha_finish", stream, 2);
   }
   // experiment knob: the pixel stages behind the HF chain on ITS stream (no overlap between a batch's pixels and the next batch's HF decode)
@@ -928,7 +929,8 @@ int32_t jxlhip_set_option(JxlHipDecoder* dec, const char* name, int32_t value) {
   if (!strcmp(name, "band_rows")) { if (value < 0) return 0; dec->band_rows = value; return 1; }
   if (!strcmp(name, "no_direct")) { dec->no_direct = value != 0; return 1; }
   if (!strcmp(name, "alpha_narrow_limit")) { if (value < 0 || value > 32767) return 0; dec->alpha_narrow_limit = value; return 1; }
-  // the alpha path's counters of the last finished batch: groups left as int16 residuals / groups decoded a second time (-1: not finished)
+  if (!strcmp(name, "alpha_sample_limit")) { if (value < 0 || value > 255) return 0; dec->alpha_sample_limit = value; return 1; }
+  // the alpha path's counters of the last finished batch: groups finished in one pass / groups decoded a second time (-1: not finished)
   if (!strcmp(name, "query_alpha_narrow_groups") || !strcmp(name, "query_alpha_redo_groups")) {
     JxlHipDecoder::Slot& S = dec->Last();
     if (S.pending || !S.h_status) return -1;

@@ -62,18 +62,18 @@ enum ChanKind : int32_t {
   kChanFinal = 0,   // samples are final
   kChanResid = 1,   // residuals stored in place; the row predictors (Zero / W / N / Gradient) are still to be applied
   kChanConst = 2,   // every sample equals `value`; nothing was stored
-  // alpha groups of the lane path only (alpha_ans_kernel):
-  kChanResid16 = 3, // gradient residuals stored as int16: row r in the first 2 * gw bytes of its (unchanged, 4 * w bytes apart) int32 row
-  kChanRedo = 4,    // a residual did not fit the narrow form: nothing usable was stored, the redo launch decodes the group again (kChanResid)
+  // alpha groups of the lane path only (alpha_ans_kernel; 3 was the int16 residual form, which is gone):
+  kChanRedo = 4,    // the one-pass form gave the group up (a residual or a sample out of range): nothing usable was stored, the redo
+                    // launch decodes the group again (kChanResid)
 };
 // DevImage::status words (16 per image, zeroed for every batch, copied to the host behind it): 0 error bits, 1 listed tiles,
 // 3..7 last failing section + 1 per stage, and the alpha path's counters:
-constexpr int kStatusAlphaNarrow = 8;   // groups that phase A left as kChanResid16
+constexpr int kStatusAlphaNarrow = 8;   // groups that phase A finished in one pass (kChanFinal, u8 samples in the alpha plane)
 constexpr int kStatusAlphaRedo = 9;     // groups that phase A left as kChanRedo (the redo launch leaves at once where this is 0)
 struct ChanDesc {
   int32_t kind;
   int32_t value;
-  int32_t pad0, pad1;   // pad0: phase A writes 0; alpha_finish_gradient_kernel sets 1 on the groups it finished
+  int32_t pad0, pad1;   // pad0: phase A writes 0, or 1 on an alpha group it finished in one pass; alpha_finish_gradient_kernel sets 1 on the groups it finished
 };
 
 // One coded channel of a Modular frame (sizes after Squeeze; shifts tell which sections code it).

@@ -675,17 +675,24 @@ __device__ __forceinline__ ChanDesc FinalChan() {
 }
 
 struct AlphaNarrow {
-  uint32_t limit;       // largest |residual| the narrow form may hold; 0: this group keeps the int32 form
-  uint32_t* counters;   // the image's status words (kStatusAlphaNarrow / kStatusAlphaRedo)
-  bool redo;            // out: a residual did not fit, the group is marked kChanRedo and the stream was left half read
+  uint32_t limit;         // largest |residual| the one-pass form takes; 0: this group keeps the int32 form and two passes
+  uint32_t sample_limit;  // largest finished sample it takes (255 but for the option alpha_sample_limit)
+  uint32_t* counters;     // the image's status words (kStatusAlphaNarrow / kStatusAlphaRedo)
+  JXL_LDS uint32_t* rows; // the lane's previous row, packed u8 (AlphaRowsLds): dword j at rows[j * slots]
+  uint32_t slots;
+  JXL_GLB uint8_t* out;   // the group's first sample in the frame's u8 alpha plane; rows `stride` samples apart, as in the int32 plane
+  bool redo;              // out: the group was given up, it is marked kChanRedo and the stream was left half read
 };
 typedef uint32_t __attribute__((ext_vector_type(4))) U4v;
 
 // Phase A of one channel on one lane.  Writes residuals (kChanResid), final samples (kChanFinal) or nothing (kChanConst).
-// An alpha group whose rows all end in a gradient leaf leaves its residuals as int16 instead (kChanResid16, `nar`): every lane of a
-// store instruction hits a cache line of its own, so a sample stored alone is a write request of its own; eight residuals gathered
-// in registers leave as one 16-byte store, an eighth of the requests and half the bytes, and phase B reads half the bytes back.
-// The residual does not depend on the sample before it on these rows, so the range check sits beside the token chain, not on it.
+// An alpha group whose rows all end in a gradient leaf is finished here, in one pass (`nar`): the lane produces the group's rows top
+// to bottom, so West is its previous sample and North / North-West are the previous row, which it keeps as packed u8 in LDS.  The
+// prediction depends on the decoded residual, the ANS chain does not depend on the prediction: it lengthens no dependency, but a lone
+// wavefront issues in order, so its nine vector instructions per token still add to the loop (1.7 ms of 12.3 per 384 4K frames).
+// Sixteen samples leave as one 16-byte store to the u8 alpha plane (every lane of a store instruction hits a cache line of its own, so
+// a sample stored alone would be a write request of its own).  The u8 row is exact while every sample lies in 0 .. 255 - the two-pass
+// form predicts from unclamped samples and clamps when it packs - so a sample outside gives the group up, like a residual too large.
 // kGeneric = false: the per-sample path (ModularChannel: weighted predictor, any tree) is not compiled in.  The LF and alpha kernels
 // carry both forms: the generic path alone raises their register allocation by half (lf_ans 156 -> 203 VGPRs, alpha_ans 96 -> 135)
 // whether or not a stream ever takes it, and these wavefronts sit on their registers for tens of milliseconds while the pixel
@@ -724,8 +731,8 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
     return;
   }
   JXL_GLB int32_t* const out = G(out_generic);
-  // the narrow form: exactly the groups alpha_finish_gradient_kernel takes (the caller has checked the frame: AlphaGroupStatic), on the
-  // lane path, and no row of one-symbol tokens
+  // the one-pass form: exactly the groups alpha_finish_gradient_kernel would take (the caller has checked the frame: AlphaGroupStatic),
+  // on the lane path, and no row of one-symbol tokens
   bool narrow = false;
   if (nar && nar->limit) {
     narrow = needs_n && !tab.direct && (w & 15) == 0;
@@ -773,27 +780,56 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
       }
     }
     uint64_t entry = AnsPrefetch<kLds>(state, abase, tab.log_alpha);
-    if (narrow) {   // w is a multiple of kTopUpEvery = 16: two 16-byte stores per top-up period
-      static_assert(kTopUpEvery == 16, "the narrow rows store two vectors of eight residuals per top-up period");
-      JXL_GLB U4v* const row16 = (JXL_GLB U4v*)row;
+    if (narrow) {   // w is a multiple of kTopUpEvery = 16: one 16-byte store per top-up period
+      static_assert(kTopUpEvery == 16, "the one-pass rows take four dwords of the row above and store one vector of sixteen samples per top-up period");
+      JXL_LDS uint32_t* const above = nar->rows;
+      const uint32_t rs = nar->slots;
+      JXL_GLB uint8_t* const row8 = nar->out + (size_t)y * stride;
       const uint32_t lim = nar->limit;
-      uint32_t top = 0;   // max of residual + limit as unsigned: above 2 * limit when some |residual| > limit
+      const bool top_row = y == 0;
+      uint32_t top = 0;    // max of residual + limit as unsigned: above 2 * limit when some |residual| > limit
+      uint32_t vtop = 0;   // max of the finished samples as unsigned: above the sample limit when one lies outside 0 .. limit
+      int32_t Wv = 0, nw_carry = 0;
       for (int x0 = 0; x0 < w; x0 += kTopUpEvery) {
+        uint32_t nd[4] = {0u, 0u, 0u, 0u};   // North of columns x0 .. x0 + 15, requested ahead of the sixteen tokens
+        if (!top_row) {
+#pragma unroll
+          for (int i = 0; i < 4; i++) nd[i] = above[__umul24((uint32_t)(x0 >> 2) + i, rs)];
+        }
         b.TopUp();
-        uint32_t pk[kTopUpEvery / 2];
+        uint32_t pk[4];
+        int32_t n_prev = nw_carry;   // North-West of column x0: the last North of the period before
 #pragma unroll
         for (int k = 0; k < kTopUpEvery; k++) {
           const uint32_t sym = AnsSymPf<kLds>(b, state, abase, tab.log_alpha, entry);
-          const uint32_t val = LeafResidual(HybridTail(b, cfg, sym), mul, off);
-          top = max(top, val + lim);
-          if (k & 1) pk[k >> 1] |= val << 16;
-          else pk[k >> 1] = val & 0xFFFFu;
+          const uint32_t res = LeafResidual(HybridTail(b, cfg, sym), mul, off);
+          top = max(top, res + lim);
+          const int32_t N = (int32_t)((nd[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+          if (k == 0 && x0 == 0) {   // first column: West = North = North-West = the sample above (0 in the top row)
+            Wv = N; n_prev = N;
+          }
+          // (samples of 0 .. 255: the median form.  Behind a sample outside that range the group is given up whatever follows it.
+          // Top row: North = North-West = West, of which the clamped gradient is West - and so is it of North = North-West = 0,
+          // which is what nd holds there: no case of its own)
+          const int32_t guess = ClampedGradientSmall(Wv, N, n_prev);
+          const uint32_t val = res + (uint32_t)guess;
+          vtop = max(vtop, val);
+          Wv = (int32_t)val;
+          n_prev = N;
+          // (no mask: a sample that does not fit its byte gives the group up, and what was stored of it is overwritten)
+          if (k & 3) pk[k >> 2] |= val << (8 * (k & 3));
+          else pk[k >> 2] = val;
+          // the maxima and the packed word are kept up token by token: left alone, the compiler holds all sixteen residuals and samples
+          // until the end of the period, a third more registers
+          asm volatile("" : "+v"(top), "+v"(vtop), "+v"(pk[k >> 2]));
         }
-        row16[x0 >> 3] = U4v{pk[0], pk[1], pk[2], pk[3]};
-        row16[(x0 >> 3) + 1] = U4v{pk[4], pk[5], pk[6], pk[7]};
-        if (top > 2 * lim) break;
+        nw_carry = n_prev;
+#pragma unroll
+        for (int i = 0; i < 4; i++) above[__umul24((uint32_t)(x0 >> 2) + i, rs)] = pk[i];
+        *(JXL_GLB U4v*)(row8 + x0) = U4v{pk[0], pk[1], pk[2], pk[3]};
+        if (top > 2 * lim || vtop > nar->sample_limit) break;
       }
-      if (top > 2 * lim) {   // a legal stream, only not one for this form: the redo launch decodes the group again, as int32
+      if (top > 2 * lim || vtop > nar->sample_limit) {   // a legal stream, only not one for this form: the redo launch decodes the group again, as int32
         d.kind = kChanRedo;
         *desc = d;
         atomicAdd(nar->counters + kStatusAlphaRedo, 1u);
@@ -815,7 +851,8 @@ __device__ __forceinline__ void DecodeChannelLane(LaneBits& b, uint32_t& state, 
     }
     first_prev = first;
   }
-  d.kind = narrow ? kChanResid16 : (needs_n ? kChanResid : kChanFinal);
+  d.kind = (narrow || !needs_n) ? kChanFinal : kChanResid;
+  d.pad0 = narrow ? 1 : 0;   // one pass: the samples are in the u8 plane, alpha_finish_kernel leaves the group alone
   *desc = d;
   if (narrow) atomicAdd(nar->counters + kStatusAlphaNarrow, 1u);
 }
@@ -1840,13 +1877,16 @@ __global__ __launch_bounds__(512) void hf_decode_kernel(const DevImage* imgs, co
 
 // ------------------------------------------------------------------ alpha (Modular stream after the HF tokens), phase A
 // One lane per pass-group section; a workgroup (one wavefront) holds sections of ONE image.
-// narrow_limit: groups that alpha_finish_gradient_kernel takes leave int16 residuals (kChanResid16) while every |residual| is at most
-// this; 0: int32 residuals for all.  A stream may code any residual: a lane that meets a larger one marks its group kChanRedo and
-// stops, and the same kernel launched once more behind this one (redo = 1) decodes those groups alone, as int32 (kChanResid).  Its
-// workgroups leave before they stage a table where the image counted no such group.
+// narrow_limit: groups that alpha_finish_gradient_kernel would take are finished here in one pass (DecodeChannelLane: the gradient on the
+// lane, u8 samples straight to the alpha plane) while every |residual| is at most this and every sample lies in 0 .. sample_limit;
+// 0: int32 residuals for all, finished by the second pass.  A stream may code any residual: a lane that meets one outside marks its
+// group kChanRedo and stops, and the same kernel launched once more behind this one (redo = 1) decodes those groups alone, as int32
+// (kChanResid).  Its workgroups leave before they stage a table where the image counted no such group.
+// LDS: bit windows | tree + code (SlotsLds; in global memory when !kLds) | the lanes' previous rows (AlphaRowsLds; not in the
+// one-section scalar launches, which pass no narrow limit)
 template <bool kLds, bool kGeneric = true>
 __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, const SectionTask* tasks, int lane_stride, int scalar_rows, int narrow_limit,
-                                                       int redo) {
+                                                       int sample_limit, int redo) {
   JXL_SERIAL_PRIO();
   extern __shared__ __align__(16) uint8_t smem[];
   const SectionTask task = tasks[blockIdx.x];
@@ -1880,7 +1920,10 @@ __global__ __launch_bounds__(64) void alpha_ans_kernel(const DevImage* imgs, con
     const int sid = 1 + 3 * im.nlf + kNumQuantTables + g;
     // (the frame's side of what AlphaGroupStatic asks; the group's side is DecodeChannelLane's)
     const bool frame_ok = !redo && !im.is_modular && im.out_bits == 8 && im.alpha_bits == 8 && !im.alpha_exp && (im.w & 3) == 0;
-    AlphaNarrow nar = {frame_ok ? (uint32_t)narrow_limit : 0u, im.status, false};
+    const size_t tables_end = kLds ? ModTablesLds(SlotsLds(slots).tables, (size_t)im.tree_size, ShapeOf(im.mcode)).end : SlotsLds(slots).tables;
+    AlphaNarrow nar = {frame_ok ? (uint32_t)narrow_limit : 0u, (uint32_t)sample_limit, im.status,
+                       (JXL_LDS uint32_t*)((JXL_LDS uint8_t*)smem + AlphaRowsLds(tables_end, slots).rows) + lane, (uint32_t)slots,
+                       G(im.alpha) + (size_t)y0 * im.w + x0, false};
     DecodeChannelLane<kLds, false, kGeneric>(b, state, mt.tab, mt.tree, 0, sid, gw, gh, im.alpha32 + (size_t)y0 * im.w + x0, im.w, desc,
                             im.wp_grp ? im.wp_grp + (size_t)g * im.wp_grp_ints : nullptr, nullptr, nullptr, &nar);
     if (nar.redo) return;   // (stopped in mid-stream: nothing to check yet)
@@ -1989,19 +2032,6 @@ struct AlphaLines {
     *(JXL_GLB U4v*)(out + (size_t)r * stride + q * 16) = U4v{pk[0], pk[1], pk[2], pk[3]};
   }
 };
-// the same for groups whose residuals phase A left as int16 (kChanResid16): a line of 16 columns is 32 bytes, widened in registers
-struct AlphaLines16 : AlphaLines {
-  __device__ __forceinline__ void load(int r, int q, bool act, I4v* v) const {
-    const int rc = act ? r : 0, qc = act ? q : 0;
-    const JXL_GLB I4v* p = (const JXL_GLB I4v*)(plane + (size_t)(mine ? rc : 0) * stride + qc * 8);   // (row pitch as for int32)
-    const I4v lo = p[0], hi = p[1];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int32_t a = k < 2 ? lo[2 * k] : hi[2 * k - 4], c = k < 2 ? lo[2 * k + 1] : hi[2 * k - 3];
-      v[k] = I4v{(int32_t)(int16_t)a, a >> 16, (int32_t)(int16_t)c, c >> 16};
-    }
-  }
-};
 // whether rows [row0, row0 + step * k) ... of the group's alpha channel all end in a gradient leaf; called by `nlanes` lanes (lane index
 // `li`) that must then combine their answers
 __device__ __forceinline__ bool AlphaRowsAreGradient(const I4* tree, int sid, int gh, int li, int nlanes) {
@@ -2009,7 +2039,7 @@ __device__ __forceinline__ bool AlphaRowsAreGradient(const I4* tree, int sid, in
   for (int r = li; r < gh; r += nlanes) { bool u = false; ok = ok && LeafPredictor(RowNode(tree, 0, sid, r, &u)) == 5; }
   return ok;
 }
-__device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int* gw, int* gh, int* sid, ChanDesc* d, int32_t kind = kChanResid) {
+__device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int* gw, int* gh, int* sid, ChanDesc* d) {
   // (a Modular frame has no alpha_desc, no group grid of this kind: nothing of it may be touched)
   if (!im.has_alpha || im.is_modular || g < 0 || g >= im.ng || im.out_bits != 8 || im.alpha_bits != 8 || im.alpha_exp || (im.w & 3) != 0) return false;
   const int gx = g % im.xg, gy = g / im.xg;
@@ -2017,11 +2047,9 @@ __device__ __forceinline__ bool AlphaGroupStatic(const DevImage& im, int g, int*
   *gw = min(kGroupDim, im.w - gx * kGroupDim); *gh = min(kGroupDim, im.h - gy * kGroupDim);
   *sid = im.alpha_in_global ? 0 : 1 + 3 * im.nlf + kNumQuantTables + g;
   *d = im.alpha_desc[g];
-  return d->kind == kind && (*gw & 15) == 0;
+  return d->kind == kChanResid && (*gw & 15) == 0;
 }
-// kNarrow: the launch behind a phase A that wrote int16 residuals takes those groups (kChanResid16) and no other: what phase A left
-// as int32 there (groups decoded again, rows of one-symbol tokens) is alpha_finish_kernel's.
-template <bool kNarrow>
+// (Groups that phase A finished in one pass are kChanFinal: a wavefront whose four groups are all of that kind leaves at the ballot.)
 __global__ __launch_bounds__(64) void alpha_finish_gradient_kernel(const DevImage* __restrict__ imgs) {
   const DevImage& im = imgs[blockIdx.y];
   const int lane = threadIdx.x, sub = lane >> 4, li = lane & 15;
@@ -2029,7 +2057,7 @@ __global__ __launch_bounds__(64) void alpha_finish_gradient_kernel(const DevImag
   int gw = 0, gh = 0, sid = 0;
   ChanDesc d;
   d.kind = kChanFinal;
-  bool mine = AlphaGroupStatic(im, g, &gw, &gh, &sid, &d, kNarrow ? kChanResid16 : kChanResid);
+  bool mine = AlphaGroupStatic(im, g, &gw, &gh, &sid, &d);
   if (mine) mine = AlphaRowsAreGradient((const I4*)im.tree, sid, gh, li, 16);
   {  // all sixteen lanes of the group must agree
     const uint64_t bal = __ballot(mine);
@@ -2039,7 +2067,7 @@ __global__ __launch_bounds__(64) void alpha_finish_gradient_kernel(const DevImag
   const int gx = mine ? g % im.xg : 0, gy = mine ? g / im.xg : 0;
   const int x0 = gx * kGroupDim, y0 = gy * kGroupDim;
   const int nq = mine ? gw >> 4 : 0, rows = mine ? gh : 0;
-  typename std::conditional<kNarrow, AlphaLines16, AlphaLines>::type mem;
+  AlphaLines mem;
   mem.plane = G(im.alpha32) + (size_t)y0 * im.w + x0; mem.out = G(im.alpha) + (size_t)y0 * im.w + x0; mem.stride = im.w; mem.mine = mine;
   // uniform loop bound: the longest of the wavefront's groups
   int steps = rows + 15;
@@ -2062,8 +2090,8 @@ __global__ __launch_bounds__(64, 3) void alpha_finish_kernel(const DevImage* __r
   const int gw = min(kGroupDim, im.w - x0), gh = min(kGroupDim, im.h - y0);
   int32_t* plane = im.alpha32 + (size_t)y0 * im.w + x0;
   const int sid = im.alpha_in_global ? 0 : 1 + 3 * im.nlf + kNumQuantTables + g;
-  if (d.pad0 == 1) return;   // finished by alpha_finish_gradient_kernel (phase A writes pad0 = 0)
-  if (d.kind == kChanResid16 || d.kind == kChanRedo) {   // never reached (the narrow pass takes every such group, the redo launch leaves none): not read as int32
+  if (d.pad0 == 1) return;   // finished by alpha_finish_gradient_kernel, or by phase A in one pass (it writes pad0 = 0 on every other group)
+  if (d.kind == kChanRedo) {   // never reached (the redo launch leaves no such group): not read as int32
     if (lane == 0) SetError(im, kErrBitstream, 4, g);
     return;
   }
@@ -2474,18 +2502,21 @@ void LaunchHfDecode(const DevImage* imgs, const SectionTask* tasks, int nwg, int
 }
 
 void LaunchAlphaAns(const DevImage* imgs, const SectionTask* tasks, int nwg, int lane_stride, size_t lds_bytes, int scalar_rows, bool lean, int narrow_limit,
-                    hipStream_t s) {
+                    int sample_limit, hipStream_t s) {
   if (nwg <= 0) return;
-  // narrow_limit > 0 (lane path only, see AlphaNarrowLaunch): a second launch behind the first decodes the groups it gave up on
+  // narrow_limit > 0 (lane path only): a second launch behind the first decodes the groups it gave up on
+  // (lds_bytes holds the lanes' row area behind the tables, entropy_plan.cc; with the tables in global memory it lies behind the windows)
+  const int slots = 64 / lane_stride;
+  const size_t lds_global = narrow_limit > 0 ? AlphaRowsLds(SlotsLds(slots).tables, slots).end : SlotsLds(slots).tables;
   for (int redo = 0; redo <= (narrow_limit > 0 ? 1 : 0); redo++) {
     if (lds_bytes && lean) {
       RaiseLds((const void*)alpha_ans_kernel<true, false>, lds_bytes);
-      hipLaunchKernelGGL((alpha_ans_kernel<true, false>), dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows, narrow_limit, redo);
+      hipLaunchKernelGGL((alpha_ans_kernel<true, false>), dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows, narrow_limit, sample_limit, redo);
     } else if (lds_bytes) {
       RaiseLds((const void*)alpha_ans_kernel<true>, lds_bytes);
-      hipLaunchKernelGGL(alpha_ans_kernel<true>, dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows, narrow_limit, redo);
+      hipLaunchKernelGGL(alpha_ans_kernel<true>, dim3(nwg), dim3(64), lds_bytes, s, imgs, tasks, lane_stride, scalar_rows, narrow_limit, sample_limit, redo);
     } else {
-      hipLaunchKernelGGL(alpha_ans_kernel<false>, dim3(nwg), dim3(64), SlotsLds(64 / lane_stride).tables, s, imgs, tasks, lane_stride, 0, narrow_limit, redo);
+      hipLaunchKernelGGL(alpha_ans_kernel<false>, dim3(nwg), dim3(64), lds_global, s, imgs, tasks, lane_stride, 0, narrow_limit, sample_limit, redo);
     }
   }
 }
@@ -2548,11 +2579,10 @@ void LaunchModularOut(const DevImage* imgs, int nimg, size_t max_pixels, hipStre
   hipLaunchKernelGGL(modular_out_kernel, dim3((unsigned)b, nimg), dim3(256), 0, s, imgs);
 }
 
-void LaunchAlphaFinish(const DevImage* imgs, int nimg, int max_groups, bool narrow, hipStream_t s) {
+void LaunchAlphaFinish(const DevImage* imgs, int nimg, int max_groups, hipStream_t s) {
   if (nimg <= 0 || max_groups <= 0) return;
-  // narrow: phase A ran with a narrow limit (LaunchAlphaAns), the gradient groups hold int16 residuals
-  if (narrow) hipLaunchKernelGGL(alpha_finish_gradient_kernel<true>, dim3((max_groups + 3) / 4, nimg), dim3(64), 0, s, imgs);
-  else hipLaunchKernelGGL(alpha_finish_gradient_kernel<false>, dim3((max_groups + 3) / 4, nimg), dim3(64), 0, s, imgs);
+  // what phase A left as int32 residuals: gradient groups (register pipeline), then everything else
+  hipLaunchKernelGGL(alpha_finish_gradient_kernel, dim3((max_groups + 3) / 4, nimg), dim3(64), 0, s, imgs);
   hipLaunchKernelGGL(alpha_finish_kernel, dim3(max_groups, nimg), dim3(64), 0, s, imgs);
 }
 

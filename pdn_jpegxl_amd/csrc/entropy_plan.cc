@@ -197,7 +197,8 @@ EntropyPlan PlanEntropy(const std::vector<ParsedFrame>& frames, const std::vecto
       continue;
     }
     P.lf.lds = std::max(P.lf.lds, SlotsLdsBytes(lf_per_wave, f.tree.size(), mshape));
-    P.alpha.lds = std::max(P.alpha.lds, SlotsLdsBytes(per_alpha_wg, f.tree.size(), mshape));
+    // (the lane path finishes alpha groups in one pass: every lane keeps its group's previous row behind the tables)
+    P.alpha.lds = std::max(P.alpha.lds, SlotsLdsBytes(per_alpha_wg, f.tree.size(), mshape) + (P.direct_alpha ? 0 : AlphaRowsLdsBytes(per_alpha_wg)));
     for (uint32_t g = r.lf0; g < r.lf1; g++) P.lf_finish_tasks.push_back(SectionTask{i, (int32_t)g, 1, 0});
     for (uint32_t g = r.lf0; g < r.lf1; g += lf_per_wave)
       P.lf_ans_tasks.push_back(SectionTask{i, (int32_t)g, (int32_t)std::min<uint32_t>((uint32_t)lf_per_wave, r.lf1 - g), 0});

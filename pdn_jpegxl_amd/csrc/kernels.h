@@ -13,9 +13,9 @@ void LaunchLfFinish(const DevImage* imgs, const SectionTask* tasks, int ntasks, 
 void LaunchHfBlockList(const DevImage* imgs, int nimg, int max_groups, hipStream_t s);
 void LaunchHfDecode(const DevImage* imgs, const SectionTask* tasks, int nwg, int threads, int lane_stride, size_t lds_bytes, size_t lane_bytes,
                     hipStream_t s);
-void LaunchAlphaAns(const DevImage* imgs, const SectionTask* tasks, int nwg, int lane_stride, size_t lds_bytes, int scalar_rows, bool lean, int narrow_limit,
+void LaunchAlphaAns(const DevImage* imgs, const SectionTask* tasks, int nwg, int lane_stride, size_t lds_bytes, int scalar_rows, bool lean, int narrow_limit, int sample_limit,
                     hipStream_t s);
-void LaunchAlphaFinish(const DevImage* imgs, int nimg, int max_groups, bool narrow, hipStream_t s);
+void LaunchAlphaFinish(const DevImage* imgs, int nimg, int max_groups, hipStream_t s);
 // Modular (lossless) frames: per-section ANS phase + predictor phase; inverse transforms (kind 0 RCT, 1 / 2 horizontal / vertical
 // unsqueeze of planes a (average), b (residual) into c); clamp + interleave
 // lanes: sections per workgroup; rb_width > 0: previous-row buffers (and, with wp_lds, the weighted-predictor state) of the generic

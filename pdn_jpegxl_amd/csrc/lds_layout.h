@@ -72,6 +72,20 @@ struct SlotsLds {
 };
 JXL_LAYOUT size_t SlotsLdsBytes(int slots, size_t tree_nodes, const CodeShape& s) { return SlotsLds(slots).tables + ModTablesLdsBytes(tree_nodes, s); }
 
+// ---- alpha_ans_kernel, launches that finish groups in one pass (the lane path): the previous row of every lane's group as packed u8,
+// behind the launch's tables (behind the bit windows when the tables stay in global memory).  Dword j of lane `slot` lies at
+// rows[j * slots + slot], the bank-per-lane layout of the bit windows.
+struct AlphaRowsLds {
+  size_t rows, end;
+  JXL_LAYOUT AlphaRowsLds(size_t tables_end, int slots) {
+    rows = LdsRoundUp(tables_end, 4);
+    end = rows + (size_t)slots * kGroupDim;
+  }
+};
+// (no allowance for the round-up: the tables' allowances, kTreeAllowance and kCodeAllowance, pay for nothing behind bit windows)
+JXL_LAYOUT size_t AlphaRowsLdsBytes(int slots) { return (size_t)slots * kGroupDim; }
+static_assert(kTreeAllowance + kCodeAllowance >= 4, "the row area's round-up is paid for by the tables' allowances");
+
 // ---- modular_ans_kernel: bit windows | previous-row buffers | weighted-predictor state | grid (uniform shape only) | tree + code
 // uniform: the one-section-per-wavefront shape of modular_uniform.h (three rows and the leaf grid instead of one row per lane)
 JXL_LAYOUT bool ModularUniform(int lanes, int rb_width) { return lanes == 1 && rb_width > 0; }

@@ -119,6 +119,15 @@ __host__ __device__ __forceinline__ int32_t ClampedGradient32(int32_t W, int32_t
   const int32_t mn = W < N ? W : N, mx = W < N ? N : W;
   return NW >= mx ? mn : (NW <= mn ? mx : (int32_t)((uint32_t)W + (uint32_t)N - (uint32_t)NW));
 }
+// Predictor 5 as the median of W, N and W + N - NW (the clamp of the sum to [min(W, N), max(W, N)]): three dependent operations where
+// the device has a median instruction.  Equal to ClampedGradient32 wherever the sum does not overflow; meant for small samples (the
+// u8 rows of the one-pass alpha decode), where it cannot.
+__host__ __device__ __forceinline__ int32_t ClampedGradientSmall(int32_t W, int32_t N, int32_t NW) {
+  const int32_t s = (int32_t)((uint32_t)W + ((uint32_t)N - (uint32_t)NW));
+  const int32_t mn = W < N ? W : N, mx = W < N ? N : W;
+  const int32_t lo = mx < s ? mx : s;   // min(max(W, N), s)
+  return mn > lo ? mn : lo;             // max(min(W, N), min(max(W, N), s)): the median of the three
+}
 // Predictors 0, 1, 2 and 5 (the ones a row-static channel may use) without a branch, low 32 bits.
 __host__ __device__ __forceinline__ uint32_t RowGuess(uint32_t pred, int32_t W, int32_t N, int32_t NW) {
   const uint32_t g = (uint32_t)ClampedGradient32(W, N, NW);

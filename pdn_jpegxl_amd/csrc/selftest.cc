@@ -367,6 +367,7 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_lossless_file(uint32_t w, ui
 //   2 lf / alpha    in: slots, nodes, shape                          out: windows, tree, alias, cfg, cmap, end | SlotsLdsBytes, lanes only
 //   3 Modular       in: lanes, rb_width, wp_lds, uniform, nodes, shape   out: windows, rows, wp, grid, tree, alias, cfg, cmap, end | ModularLdsBytes, lanes only
 //   4 HF            in: sections, shape                              out: ring, descq, nzcol, alias, cfg, cmap, nnz, end | tables + lanes, lanes only, slots
+//   6 alpha rows    in: slots, nodes, shape                          out: tables' end, rows, end | SlotsLdsBytes + AlphaRowsLdsBytes, behind the windows alone: rows, end
 //   5 constants     out: kLdsMax, kRingWords, kHfRingWords, kNzColBytes, kNnzCtxBytes, kWpStateInts, kUniRows, kUniGridBytes, sizeof(DevTreeNode)
 extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_lds_layout(int32_t kind, const int64_t* in, int64_t* out) {
   int k = 0;
@@ -396,6 +397,12 @@ extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_lds_layout(int32_t kind, co
     const CodeLds c(l.tables, shape(1));
     put(l.ring); put(l.descq); put(l.nzcol); put_code(c); put(c.end); put(HfTablesEnd(l.tables, shape(1)));
     put(HfTablesBytes(shape(1)) + HfLaneBytes(nslots)); put(HfLaneBytes(nslots)); put((size_t)nslots);
+  } else if (kind == 6) {
+    const SlotsLds l((int)in[0]);
+    const ModTablesLds t(l.tables, (size_t)in[1], shape(2));
+    const AlphaRowsLds r(t.end, (int)in[0]), g(l.tables, (int)in[0]);
+    put(t.end); put(r.rows); put(r.end); put(SlotsLdsBytes((int)in[0], (size_t)in[1], shape(2)) + AlphaRowsLdsBytes((int)in[0]));
+    put(g.rows); put(g.end);
   } else if (kind == 5) {
     put(kLdsMax); put(kRingWords); put(kHfRingWords); put(kNzColBytes); put(kNnzCtxBytes); put(kWpStateInts); put(kUniRows); put(kUniGridBytes);
     put(sizeof(DevTreeNode));
@@ -675,6 +682,15 @@ extern "C" JXLFILETYPEIO_API void jxlhip_selftest_modular_predict(int32_t n, con
     gradient32[i] = ClampedGradient32(h[0], h[1], h[2]);
     const uint32_t ids[4] = {0, 1, 2, 5};
     for (int k = 0; k < 4; k++) row_guess[4 * (size_t)i + k] = RowGuess(ids[k], h[0], h[1], h[2]);
+  }
+}
+
+// Per (W, N, NW): ClampedGradientSmall and ClampedGradient32
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_gradient_small(int32_t n, const int32_t* wnnw, int32_t* small, int32_t* gradient32) {
+  for (int i = 0; i < n; i++) {
+    const int32_t* h = wnnw + 3 * (size_t)i;
+    small[i] = ClampedGradientSmall(h[0], h[1], h[2]);
+    gradient32[i] = ClampedGradient32(h[0], h[1], h[2]);
   }
 }
 
