@@ -15,6 +15,10 @@
  *
  * Part 3 (jxlhip_save_pixels) is SaveImage for every sample type LoadImage hands out: 8- to 16-bit integers, binary16 and binary32,
  * Gray | GrayA | RGB | RGBA, in any of the colour encodings the host knows by name.
+ *
+ * Part 4 (jxlhip_encode_batch) encodes many device-resident images in one call.
+ *
+ * Part 5 (jxlhip_animation_*) decodes every displayed image of an animated file into device memory, in file order.
  */
 #ifndef JXLFILETYPEIO_H_
 #define JXLFILETYPEIO_H_
@@ -310,9 +314,74 @@ JXLFILETYPEIO_API int32_t jxlhip_encoder_result(JxlHipEncoder* enc, int32_t i, c
  * allocate ("host: ... allocation") appear only in a call that had to grow a buffer. */
 JXLFILETYPEIO_API int32_t jxlhip_encoder_stage_times(JxlHipEncoder* enc, const char** names, float* ms, int32_t capacity);
 
+/* =====================================================================================================
+ * Part 5: animations - every displayed image of a file, decoded to device memory (not in the reference, whose LoadImage
+ * keeps the first displayed image; LoadImage and jxlhip_decode_batch still do exactly that).
+ *
+ * Displayed image j is the canvas after the j-th frame, in file order, that ends the file or has a duration.  Frames
+ * without a duration between them are layers: they blend onto the canvas and may be saved to the four reference slots.
+ * Those slots are the state between two displayed images, so decoding is sequential by design: random access is
+ * jxlhip_animation_rewind followed by skipping (jxlhip_animation_next into a buffer that is thrown away).
+ * A file without an animation header is accepted: a single frame or a layered still has one displayed image, the one
+ * LoadImage delivers.  Files whose frames carry patches or are reference-only frames are refused by name at open
+ * ("animations with patches are not supported"), and so is everything LoadImage refuses of a layered file, with the same
+ * words and the number of the codestream frame.  There is no limit on the number of frames.
+ * ===================================================================================================== */
+typedef struct JxlHipAnimation JxlHipAnimation;
+
+typedef struct JxlHipAnimationInfo {
+  int32_t width, height;         /* as displayed (orientation applied), like jxlhip_peek */
+  int32_t num_channels, has_alpha;
+  int32_t bytes_per_sample;      /* 1, 2 or 4 */
+  int32_t float_samples;         /* 1: binary16 / binary32 samples */
+  int32_t bits_per_sample;       /* of the colour channels, as coded */
+  int32_t have_animation;        /* 0: no animation header; the four fields below are 0 */
+  uint32_t tps_numerator, tps_denominator;   /* ticks per second = numerator / denominator */
+  uint32_t num_loops;            /* 0: endless */
+  int32_t have_timecodes;
+  int32_t num_displayed;         /* displayed images in the file */
+  int32_t num_codestream_frames; /* frames in the file, layers included */
+  uint64_t image_bytes;          /* one displayed image: width * height * num_channels * bytes_per_sample, tight rows */
+} JxlHipAnimationInfo;
+
+typedef struct JxlHipAnimationFrame {
+  uint32_t duration;             /* ticks the image is shown for (0 for the only image of a still) */
+  uint32_t timecode;             /* as written (have_timecodes), else 0 */
+  int32_t first_codestream_frame, num_codestream_frames;   /* the frames consumed since the previous displayed image */
+  int32_t name_length;           /* bytes of `name`, without the NUL */
+  char name[1076];               /* the name of the frame that completes the image, NUL-terminated */
+} JxlHipAnimationFrame;
+
+/* Parses the whole file on the host (the bytes are copied: `data` may be freed after the call), then creates a decoder on
+ * `device` (< 0: the current one) and uploads the codestream once.  info may be NULL.  Returns NULL on failure, message in err. */
+JXLFILETYPEIO_API JxlHipAnimation* jxlhip_animation_open(int32_t device, const uint8_t* data, size_t size, JxlHipAnimationInfo* info,
+                                                         ErrorInfo* err);
+JXLFILETYPEIO_API void jxlhip_animation_close(JxlHipAnimation* anim);
+/* Displayed image j (0 .. num_displayed - 1).  Returns 1, or 0 for an index outside the file. */
+JXLFILETYPEIO_API int32_t jxlhip_animation_frame(JxlHipAnimation* anim, int32_t j, JxlHipAnimationFrame* out);
+/* Writes the next `count` displayed images (fewer at the end of the file; 0 there), tightly packed, image_bytes each, into
+ * the device buffer dev_out of `capacity` bytes; *written is how many.  Synchronous.  The frames are decoded in chunks of
+ * consecutive codestream frames - at most 64, and at most 16 GiB of scratch unless one frame needs more - so the scratch
+ * does not grow with the length of the file.  After a failure (the message names the codestream frame) the position and
+ * the reference slots are those in front of the chunk that failed (a chunk stores its slots to a second set of buffers, which
+ * becomes the state only when the chunk has succeeded): images in front of the damaged frame can still be asked for. */
+JXLFILETYPEIO_API DecoderStatus jxlhip_animation_next(JxlHipAnimation* anim, int32_t count, void* dev_out, size_t capacity,
+                                                      int32_t* written, ErrorInfo* err);
+/* Back to the first displayed image. */
+JXLFILETYPEIO_API void jxlhip_animation_rewind(JxlHipAnimation* anim);
+/* "chunk_frames" (0: chunks by the limits above, the default; n >= 1: at most n frames per chunk - same output, for tests);
+ * "lane_stride", "no_direct", "mod_lanes64", "no_stream_pairs" and "no_lf_pipeline" go to the animation's decoder as
+ * jxlhip_set_option takes them (same output).  Every other name is refused: neither a band nor a reduced size is offered
+ * here.  Returns 1 if the option was set. */
+JXLFILETYPEIO_API int32_t jxlhip_animation_set_option(JxlHipAnimation* anim, const char* name, int32_t value);
+/* The decoder the animation runs on, owned by it: for jxlhip_stage_times / jxlhip_stage_totals (measurement). */
+JXLFILETYPEIO_API JxlHipDecoder* jxlhip_animation_decoder(JxlHipAnimation* anim);
+
 #ifdef __cplusplus
 }
 static_assert(sizeof(JxlHipPixels) == 40, "JxlHipPixels layout");
+static_assert(sizeof(JxlHipAnimationInfo) == 64, "JxlHipAnimationInfo layout");
+static_assert(sizeof(JxlHipAnimationFrame) == 1096, "JxlHipAnimationFrame layout");
 static_assert(sizeof(BitmapData) == 24, "BitmapData layout");
 static_assert(sizeof(EncoderOptions) == 12, "EncoderOptions layout");
 static_assert(sizeof(EncoderImageMetadata) == 48, "EncoderImageMetadata layout");

@@ -76,11 +76,24 @@ class JxlHipPixels(C.Structure):
                 ("num_channels", C.c_int32), ("sample_type", C.c_int32), ("bits_per_sample", C.c_int32), ("colour", C.c_int32)]
 
 
+class AnimationInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("num_channels", C.c_int32), ("has_alpha", C.c_int32),
+                ("bytes_per_sample", C.c_int32), ("float_samples", C.c_int32), ("bits_per_sample", C.c_int32), ("have_animation", C.c_int32),
+                ("tps_numerator", C.c_uint32), ("tps_denominator", C.c_uint32), ("num_loops", C.c_uint32), ("have_timecodes", C.c_int32),
+                ("num_displayed", C.c_int32), ("num_codestream_frames", C.c_int32), ("image_bytes", C.c_uint64)]
+
+
+class AnimationFrame(C.Structure):
+    _fields_ = [("duration", C.c_uint32), ("timecode", C.c_uint32), ("first_codestream_frame", C.c_int32),
+                ("num_codestream_frames", C.c_int32), ("name_length", C.c_int32), ("name", C.c_char * 1076)]
+
+
 EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jxlhip_decoder_create", "jxlhip_decoder_destroy", "jxlhip_peek",
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
            "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
-           "jxlhip_encoder_result", "jxlhip_encoder_stage_times"]
+           "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
+           "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder"]
 
 _lib = None
 
@@ -176,6 +189,20 @@ def lib(build_if_missing=True):
     L.jxlhip_encoder_result.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.jxlhip_encoder_stage_times.restype = C.c_int32
     L.jxlhip_encoder_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]
+    L.jxlhip_animation_open.restype = C.c_void_p
+    L.jxlhip_animation_open.argtypes = [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(AnimationInfo), C.POINTER(ErrorInfo)]
+    L.jxlhip_animation_close.restype = None
+    L.jxlhip_animation_close.argtypes = [C.c_void_p]
+    L.jxlhip_animation_frame.restype = C.c_int32
+    L.jxlhip_animation_frame.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AnimationFrame)]
+    L.jxlhip_animation_next.restype = C.c_int32
+    L.jxlhip_animation_next.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
+    L.jxlhip_animation_rewind.restype = None
+    L.jxlhip_animation_rewind.argtypes = [C.c_void_p]
+    L.jxlhip_animation_set_option.restype = C.c_int32
+    L.jxlhip_animation_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.jxlhip_animation_decoder.restype = C.c_void_p
+    L.jxlhip_animation_decoder.argtypes = [C.c_void_p]
     L.jxlhip_parse_check.restype = C.c_int32
     L.jxlhip_parse_check.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_static_table.restype = C.c_size_t
@@ -647,3 +674,97 @@ class Encoder:
         ms = (C.c_float * 48)()
         k = self._L.jxlhip_encoder_stage_times(self._h, names, ms, 48)
         return {names[i].decode(): ms[i] for i in range(k)}
+
+
+class Animation:
+    """Every displayed image of a file, in file order, decoded to device memory (jxlhip_animation_*).  A context manager:
+
+        with api.Animation(data) as a:
+            a.info.num_displayed, a.frames[0].duration
+            t = a.next(4)          # torch tensor [n, h, w, c] on the GPU, n <= 4 (0 at the end)
+            a.rewind()
+            every = a.read_all()   # numpy [num_displayed, h, w, c]
+
+    Decoding is sequential (the state between two images is the reference slots): random access is rewind() and skipping.  A file
+    without an animation header has one displayed image, the one load_image delivers.  Raises FormatError where the file is refused."""
+
+    def __init__(self, data, device=-1):
+        self._h = None
+        self._L = lib()
+        self.info = AnimationInfo()
+        self._device, self._pos = device, 0
+        err = ErrorInfo()
+        self._h = self._L.jxlhip_animation_open(device, data, len(data), C.byref(self.info), C.byref(err))
+        if not self._h:
+            raise FormatError("DecodeError", err.errorMessage.decode("ascii", "replace"))
+        self.frames = []
+        for j in range(self.info.num_displayed):
+            fr = AnimationFrame()
+            self._L.jxlhip_animation_frame(self._h, j, C.byref(fr))
+            fr.name_bytes = fr.name[:fr.name_length] if fr.name_length else b""
+            self.frames.append(fr)
+        i = self.info
+        if i.float_samples:
+            self.dtype = np.float16 if i.bytes_per_sample == 2 else np.float32
+        else:
+            self.dtype = np.uint16 if i.bytes_per_sample == 2 else np.uint8
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._h:
+            self._L.jxlhip_animation_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def set_option(self, name, value):
+        """"chunk_frames": 0 (chunks by the decoder's limits) or n >= 1 (at most n codestream frames per chunk; same output), and the
+        decoder's "lane_stride", "no_direct", "mod_lanes64", "no_stream_pairs", "no_lf_pipeline".  Returns 1 when the option was set,
+        0 for any other name."""
+        return self._L.jxlhip_animation_set_option(self._h, name.encode(), int(value))
+
+    def rewind(self):
+        self._L.jxlhip_animation_rewind(self._h)
+        self._pos = 0
+
+    def next(self, count=1):
+        """The next `count` displayed images as a torch tensor [n, h, w, c] on the device (n < count at the end of the file, 0 behind
+        it).  16-bit integer samples arrive as torch.int16 holding the same bits (read_all() hands them out as numpy uint16)."""
+        import torch
+        i = self.info
+        tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.float16: torch.float16, np.float32: torch.float32}[self.dtype]
+        want = max(0, min(count, i.num_displayed - self._pos))   # (nothing is allocated for images behind the end of the file)
+        dev = torch.device("cuda", self._device) if self._device >= 0 else torch.device("cuda")
+        out = torch.empty((want, i.height, i.width, i.num_channels), dtype=tdt, device=dev)
+        torch.cuda.synchronize()
+        n = C.c_int32(0)
+        err = ErrorInfo()
+        st = self._L.jxlhip_animation_next(self._h, want, out.data_ptr() if want else None, out.numel() * out.element_size(), C.byref(n), C.byref(err))
+        self.last_error = err.errorMessage.decode("ascii", "replace")
+        if st != 0:
+            raise FormatError(DECODER_STATUS[st] if 0 <= st < len(DECODER_STATUS) else str(st), self.last_error)
+        self._pos += n.value
+        return out[:n.value]
+
+    def read_all(self):
+        """Rewinds and returns every displayed image as one numpy array [num_displayed, h, w, c] of the file's sample type."""
+        self.rewind()
+        t = self.next(self.info.num_displayed)
+        a = t.cpu().numpy()
+        return a.view(np.uint16) if self.dtype == np.uint16 else a
+
+    def decoder_stage_totals(self, reset=False):
+        """({stage: cumulative ms}, chunks) of the animation's decoder over every chunk since the last reset (HIP events), as
+        Decoder.stage_totals: a call of next() runs one batch per chunk."""
+        L = self._L
+        names = (C.c_char_p * 16)()
+        ms = (C.c_float * 16)()
+        nb = C.c_int32()
+        k = L.jxlhip_stage_totals(L.jxlhip_animation_decoder(self._h), names, ms, 16, C.byref(nb), 1 if reset else 0)
+        return {names[i].decode(): ms[i] for i in range(k)}, nb.value

@@ -493,6 +493,10 @@ void BuildBatch(const BatchInput& in, BatchRegions& R, BatchOutput& out) {
         ci.first = comps[k].first; ci.count = comps[k].count;
         ci.raw = top.layers->raw ? 1 : 0;
         ci.out = comps[k].out;
+        ci.live_in = top.layers->live_in; ci.live_out = top.layers->live_out;
+        ci.slots_in = top.layers->slots_in; ci.slots_out = top.layers->slots_out;
+        for (int s = 0; s < 4; s++) ci.slot_plane[s] = top.layers->slot_plane[s];
+        ci.out_stride = top.layers->out_stride;
       }
     });
     out.comp_frames = blob.Fill<ComposeFrame>((size_t)n, [&](ComposeFrame* cframes) {
@@ -512,8 +516,12 @@ void BuildBatch(const BatchInput& in, BatchRegions& R, BatchOutput& out) {
           cf.source[0] = (int32_t)bc.source; cf.source[1] = (int32_t)ba.source;
           cf.clamp[0] = (int32_t)bc.clamp; cf.clamp[1] = (int32_t)ba.clamp;
           cf.save = c.save[j];
+          cf.show = top.layers->show.empty() ? (j == c.count - 1 ? 0 : -1) : top.layers->show[j];
           // a reference-only frame is read by patches only: an empty crop and no save leave the canvas and the slots as they are
-          if (f.frame_type == 2) { cf.w = cf.h = 0; cf.save = -1; }
+          if (f.frame_type == 2) { cf.w = cf.h = 0; cf.save = -1; cf.show = -1; }
+          // a frame that was refused after the file was expanded (its LF pre-pass failed) has no samples: an empty crop, so that the
+          // launch reads nothing of it (the file fails through the frame's status)
+          if (!decoded(c.first + j)) { cf.px = nullptr; cf.w = cf.h = 0; }
         }
       }
     });

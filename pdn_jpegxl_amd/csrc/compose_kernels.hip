@@ -5,6 +5,10 @@
 // One lane per canvas pixel.  The four reference slots of the pixel live in registers (4 slots x 4 channels), so no canvas-sized slot
 // buffers exist: every frame is read once, one 16-byte load per pixel for four channels, and the canvas is written once.  The frame descriptors are uniform across
 // a workgroup (scalar loads).  Un-premultiply, rounding to the output type and the orientation are fused into the store.
+//
+// Animations (every displayed image of a file, decoded in chunks of frames) run through the same loop: a frame that
+// completes a displayed image stores the canvas as it stands, and the slots a later chunk still reads are loaded at entry from one
+// buffer and stored at exit to another (ComposeImage::live_in / live_out, slots_in / slots_out).  A still has one displayed image, on its last frame, and no slot traffic.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "dev_types.h"
@@ -18,7 +22,7 @@ __device__ __forceinline__ float Clamp01(float v) { return fminf(fmaxf(v, 0.f), 
 
 // The four slots of a pixel as four named register quads, read and written through per-component selects: an array indexed by the
 // (uniform) slot number went to scratch memory (72-80 B per lane), even behind unrolled compares (the compiler folds them back into an
-// index); with selects the kernel has no scratch and 59 VGPRs.
+// index); with selects the kernel has no scratch (57 VGPRs with the slot loads and stores of chunked animations, 51 before them).
 struct Slots { float4 s0, s1, s2, s3; };
 __device__ __forceinline__ float4 Sel(bool c, float4 a, float4 b) {
   return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
@@ -85,18 +89,90 @@ __device__ __forceinline__ float BlendSample(int mode, bool is_alpha, bool premu
   }
 }
 
+// One displayed image leaves: un-premultiply (as modular_out_kernel), round to the output type, store at the oriented position.  The
+// frame loop calls this after every frame that completes a displayed image (a still: its last frame), with that image's buffer.
+__device__ __forceinline__ void StoreDisplayed(const ComposeImage& im, uint8_t* out, const float (&canvas)[4], int x, int y, int ai) {
+  const int w = im.w, h = im.h, nch = im.nch;
+  float res[4] = {canvas[0], canvas[1], canvas[2], canvas[3]};
+  if (im.premul && ai >= 0 && !im.raw) {
+    const float unmul = 1.0f / fmaxf(1.0f / 67108864.0f, Lane(make_float4(res[0], res[1], res[2], res[3]), ai));
+#pragma unroll
+    for (int c = 0; c < 4; c++) if (c < ai) res[c] *= unmul;
+  }
+  int ox = x, oy = y, ow = w;
+  switch (im.orientation) {
+    case 2: ox = w - 1 - x; break;
+    case 3: ox = w - 1 - x; oy = h - 1 - y; break;
+    case 4: oy = h - 1 - y; break;
+    case 5: ox = y; oy = x; ow = h; break;
+    case 6: ox = h - 1 - y; oy = x; ow = h; break;
+    case 7: ox = h - 1 - y; oy = w - 1 - x; ow = h; break;
+    case 8: ox = y; oy = w - 1 - x; ow = h; break;
+    default: break;
+  }
+  const size_t o = (size_t)oy * ow + ox;
+  if (im.raw) {
+    if (im.out_bits == 8 && nch == 4) {
+      uint32_t px = 0;
+#pragma unroll
+      for (int c = 0; c < 4; c++) px |= __float_as_uint(res[c]) << (8 * c);
+      ((uint32_t*)out)[o] = px;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; c++)
+        if (c < nch) StoreOutSample(out, o * nch + c, __float_as_uint(res[c]), im.out_bits);
+    }
+    return;
+  }
+  // rounding half up like modular_out_kernel (not v_cvt_pk_u8_f32, which rounds ties to even): a layered file whose frames replace
+  // decodes to the same bytes as its frames would alone
+  if (im.out_bits == 8 && nch == 4) {   // the common layout: one 4-byte store
+    uint32_t px = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) px |= FloatToOutBits(res[c], 8, 0) << (8 * c);
+    ((uint32_t*)out)[o] = px;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+      if (c < nch) StoreOutSample(out, o * nch + c, FloatToOutBits(res[c], im.out_bits, im.out_float), im.out_bits);
+  }
+}
+
+// A slot of pixel p in the slot buffers of a chunked animation: nch floats (one 16-byte access for four channels)
+__device__ __forceinline__ float4 LoadSlot(const float* slots, size_t plane, int s, size_t p, int nch) {
+  const float* q = slots + ((size_t)s * plane + p) * nch;
+  if (nch == 4) return *(const float4*)q;
+  if (nch == 3) return make_float4(q[0], q[1], q[2], 0.f);
+  if (nch == 2) { const float2 v = *(const float2*)q; return make_float4(v.x, v.y, 0.f, 0.f); }
+  return make_float4(q[0], 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ void StoreSlot(float* slots, size_t plane, int s, size_t p, int nch, float4 v) {
+  float* q = slots + ((size_t)s * plane + p) * nch;
+  if (nch == 4) *(float4*)q = v;
+  else if (nch == 3) { q[0] = v.x; q[1] = v.y; q[2] = v.z; }
+  else if (nch == 2) *(float2*)q = make_float2(v.x, v.y);
+  else q[0] = v.x;
+}
+
 __global__ void compose_kernel(const ComposeImage* __restrict__ imgs, const ComposeFrame* __restrict__ frames) {
   const ComposeImage& im = imgs[blockIdx.y];
   const int w = im.w, h = im.h, nch = im.nch;
   const int ai = im.has_alpha ? nch - 1 : -1;
+  const size_t plane = (size_t)w * h;
   // a workgroup per 256-pixel row segment, one pixel per lane: the segment's row and column come from one uniform (scalar) division per
   // workgroup, none per pixel, and a wavefront's crop tests are on one row segment
   const int xseg = (w + (int)blockDim.x - 1) / (int)blockDim.x;
   for (int t = blockIdx.x; t < xseg * h; t += gridDim.x) {
     const int y = t / xseg, x = (t - y * xseg) * (int)blockDim.x + (int)threadIdx.x;
     if (x >= w) continue;
+    const size_t p = (size_t)y * w + x;
     Slots sl;
     sl.s0 = sl.s1 = sl.s2 = sl.s3 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // a later chunk of an animation: the slots some frame from here on reads, as the chunk before left them (uniform tests)
+    if (im.live_in & 1) sl.s0 = LoadSlot(im.slots_in, plane, im.slot_plane[0], p, nch);
+    if (im.live_in & 2) sl.s1 = LoadSlot(im.slots_in, plane, im.slot_plane[1], p, nch);
+    if (im.live_in & 4) sl.s2 = LoadSlot(im.slots_in, plane, im.slot_plane[2], p, nch);
+    if (im.live_in & 8) sl.s3 = LoadSlot(im.slots_in, plane, im.slot_plane[3], p, nch);
     float res[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < im.count; k++) {
       const ComposeFrame& fr = frames[im.first + k];
@@ -121,50 +197,12 @@ __global__ void compose_kernel(const ComposeImage* __restrict__ imgs, const Comp
         for (int c = 0; c < 4; c++) res[c] = c == ai ? old_a[c] : old_c[c];
       }
       if (fr.save >= 0) WriteSlot(sl, fr.save, make_float4(res[0], res[1], res[2], res[3]));
+      if (fr.show >= 0) StoreDisplayed(im, im.out + (size_t)fr.show * im.out_stride, res, x, y, ai);
     }
-    // the displayed image: un-premultiply (as modular_out_kernel), round to the output type, store at the oriented position
-    if (im.premul && ai >= 0 && !im.raw) {
-      const float unmul = 1.0f / fmaxf(1.0f / 67108864.0f, Lane(make_float4(res[0], res[1], res[2], res[3]), ai));
-#pragma unroll
-      for (int c = 0; c < 4; c++) if (c < ai) res[c] *= unmul;
-    }
-    int ox = x, oy = y, ow = w;
-    switch (im.orientation) {
-      case 2: ox = w - 1 - x; break;
-      case 3: ox = w - 1 - x; oy = h - 1 - y; break;
-      case 4: oy = h - 1 - y; break;
-      case 5: ox = y; oy = x; ow = h; break;
-      case 6: ox = h - 1 - y; oy = x; ow = h; break;
-      case 7: ox = h - 1 - y; oy = w - 1 - x; ow = h; break;
-      case 8: ox = y; oy = w - 1 - x; ow = h; break;
-      default: break;
-    }
-    const size_t o = (size_t)oy * ow + ox;
-    if (im.raw) {
-      if (im.out_bits == 8 && nch == 4) {
-        uint32_t px = 0;
-#pragma unroll
-        for (int c = 0; c < 4; c++) px |= __float_as_uint(res[c]) << (8 * c);
-        ((uint32_t*)im.out)[o] = px;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-          if (c < nch) StoreOutSample(im.out, o * nch + c, __float_as_uint(res[c]), im.out_bits);
-      }
-      continue;
-    }
-    // rounding half up like modular_out_kernel (not v_cvt_pk_u8_f32, which rounds ties to even): a layered file whose frames replace
-    // decodes to the same bytes as its frames would alone
-    if (im.out_bits == 8 && nch == 4) {   // the common layout: one 4-byte store
-      uint32_t px = 0;
-#pragma unroll
-      for (int c = 0; c < 4; c++) px |= FloatToOutBits(res[c], 8, 0) << (8 * c);
-      ((uint32_t*)im.out)[o] = px;
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; c++)
-        if (c < nch) StoreOutSample(im.out, o * nch + c, FloatToOutBits(res[c], im.out_bits, im.out_float), im.out_bits);
-    }
+    if (im.live_out & 1) StoreSlot(im.slots_out, plane, im.slot_plane[0], p, nch, sl.s0);
+    if (im.live_out & 2) StoreSlot(im.slots_out, plane, im.slot_plane[1], p, nch, sl.s1);
+    if (im.live_out & 4) StoreSlot(im.slots_out, plane, im.slot_plane[2], p, nch, sl.s2);
+    if (im.live_out & 8) StoreSlot(im.slots_out, plane, im.slot_plane[3], p, nch, sl.s3);
   }
 }
 

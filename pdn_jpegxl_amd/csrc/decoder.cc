@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "animation.h"
 #include "batch_layout.h"
 #include "entropy_plan.h"
 #include "host_parse.h"
@@ -151,6 +152,7 @@ struct JxlHipDecoder {
   // reduced-size decode: 1 = full size; 8 = every image of the next batches leaves at ceil(w / 8) x ceil(h / 8), one pixel
   // per 8x8 cell (VarDCT: the LF image; Modular: cell means of the full decode)
   int downscale = 1;
+  bool single_slot = false;   // every batch in workspace slot 0 (an animation's chunks are synchronous: one workspace, not three)
 
   explicit JxlHipDecoder(int dev);
   ~JxlHipDecoder();
@@ -159,8 +161,10 @@ struct JxlHipDecoder {
   void Mark(const char* name, hipStream_t s, int chain);
   void WaitSlot(Slot& S);
   Slot& Last() { return slots[last]; }
+  // preparsed (a chunk of an animation, JxlHipAnimation::RunChunk): the parse of the call's one file - a single frame, or a layered file
+  // whose Layers carry the chunk's frames; it is moved from, and no host bytes are read.
   void Decode(int32_t n_, const uint8_t* const* host_data, const size_t* sizes, const uint8_t* const* dev_data,
-              uint8_t* const* dev_out, hipStream_t stream, bool sync, DecoderStatus* statuses, ErrorInfo* err);
+              uint8_t* const* dev_out, hipStream_t stream, bool sync, DecoderStatus* statuses, ErrorInfo* err, ParsedFrame* preparsed = nullptr);
   DecoderStatus Finish(DecoderStatus* statuses, ErrorInfo* err);
   void CopyPlaneTap(int stage);
   void PrepassSingle(ParsedFrame& f, const uint8_t* dev_file);
@@ -367,7 +371,7 @@ EntropyPlanOptions JxlHipDecoder::PlanOptions() const {
 }
 
 void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const size_t* sizes, const uint8_t* const* dev_data,
-                           uint8_t* const* dev_out, hipStream_t stream, bool sync, DecoderStatus* statuses, ErrorInfo* err) {
+                           uint8_t* const* dev_out, hipStream_t stream, bool sync, DecoderStatus* statuses, ErrorInfo* err, ParsedFrame* preparsed) {
   HIP_OK(hipSetDevice(device));
   if (!stream) stream = own_stream;
   Slot& S = slots[cur];
@@ -391,7 +395,9 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   parse_status.assign(n, DecoderStatus_Ok);
   parse_msg.assign(n, "");
   // ---- 1. host parse (threaded across images)
-  {
+  if (preparsed) {
+    frames[0] = std::move(*preparsed);
+  } else {
     int nt = std::min<int>(n, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
     std::vector<std::thread> th;
     std::atomic<int> next(0);
@@ -704,7 +710,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   last_stream = stream;
   S.pending = true;
   last = cur;
-  cur = (cur + 1) % kSlots;
+  cur = single_slot ? cur : (cur + 1) % kSlots;
   if (sync) {
     DecoderStatus st = Finish(statuses, err);
     (void)st;
@@ -1106,6 +1112,193 @@ DecoderStatus LoadImage(DecoderCallbacks* cb, const uint8_t* data, size_t size, 
 }
 
 // SaveImage lives in encoder.cc.
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------- animations: every displayed image of a file, in file order
+// The state between two displayed images is the four reference slots, so decoding is sequential.  Frames are decoded in chunks
+// (animation.h): each chunk is one JxlHipDecoder::Decode of a layered file made of the chunk's frames, whose compose launch stores every
+// displayed image it passes and carries the live slots from and to the slot buffers.
+struct JxlHipAnimation {
+  std::vector<uint8_t> file;      // the caller's bytes (the parse points into them)
+  Animation anim;
+  AnimPlan plan;
+  ParsedFrame top;                // what every chunk's file looks like from outside: the image header on the canvas
+  std::unique_ptr<JxlHipDecoder> dec;
+  uint8_t* d_cs = nullptr;        // the codestream, uploaded once
+  // The slots that are alive at some cut of the file, one canvas-sized plane of nch floats per pixel each (slot_plane), twice: a chunk
+  // loads from d_slots[cur_slots] and stores to the other, and the two swap when the chunk has succeeded - after a failure the state
+  // in front of the chunk is intact.  Null when no cut has a live slot.
+  float* d_slots[2] = {nullptr, nullptr};
+  int slot_plane[4] = {0, 0, 0, 0};
+  int cur_slots = 0;
+  int next_frame = 0, next_shown = 0;
+  int chunk_frames = 0;
+  size_t image_bytes = 0;
+  ~JxlHipAnimation() {
+    if (dec) (void)hipSetDevice(dec->device);
+    if (d_cs) (void)hipFree(d_cs);
+    for (float* p : d_slots) if (p) (void)hipFree(p);
+  }
+  DecoderStatus RunChunk(const AnimChunk& c, uint8_t* out, ErrorInfo* err);
+};
+
+DecoderStatus JxlHipAnimation::RunChunk(const AnimChunk& c, uint8_t* out, ErrorInfo* err) {
+  if (anim.single) {   // one single-frame image: the ordinary decode, straight into the caller's buffer
+    ParsedFrame one = anim.frames[0];
+    const uint8_t* host = nullptr;
+    const size_t size = 0;
+    const uint8_t* dev = d_cs;
+    DecoderStatus st = DecoderStatus_Ok;
+    ErrorInfo detail;
+    detail.errorMessage[0] = 0;
+    dec->Decode(1, &host, &size, &dev, &out, nullptr, true, &st, &detail, &one);
+    if (st != DecoderStatus_Ok) SetErr(err, "animation, codestream frame 0: %s", detail.errorMessage);
+    return st;
+  }
+  ParsedFrame file = top;
+  auto lay = std::make_shared<Layers>();
+  lay->canvas_w = top.xsize; lay->canvas_h = top.ysize;
+  lay->raw = anim.raw;
+  lay->frames.assign(anim.frames.begin() + c.first, anim.frames.begin() + c.first + c.count);
+  lay->save.assign(anim.save.begin() + c.first, anim.save.begin() + c.first + c.count);
+  for (int k = 0; k < c.count; k++) lay->show.push_back(anim.show[c.first + k] >= 0 ? anim.show[c.first + k] - c.first_shown : -1);
+  lay->live_in = c.live_in; lay->live_out = c.live_out;
+  lay->slots_in = d_slots[cur_slots]; lay->slots_out = d_slots[cur_slots ^ 1];
+  for (int s = 0; s < 4; s++) lay->slot_plane[s] = slot_plane[s];
+  lay->out_stride = image_bytes;
+  file.layers = lay;
+  const uint8_t* host = nullptr;
+  const size_t size = 0;
+  const uint8_t* dev = d_cs;
+  DecoderStatus st = DecoderStatus_Ok;
+  ErrorInfo detail;
+  detail.errorMessage[0] = 0;
+  dec->Decode(1, &host, &size, &dev, &out, nullptr, true, &st, &detail, &file);
+  if (st == DecoderStatus_Ok) cur_slots ^= 1;   // what the chunk stored is the state now
+  if (st != DecoderStatus_Ok) {
+    // the chunk's images are its frames: the first one that failed names the codestream frame
+    JxlHipDecoder::Slot& S = dec->Last();
+    int bad = 0;
+    for (int i = 0; i < S.n; i++)
+      if (S.parse_status[i] != DecoderStatus_Ok || S.h_status[(size_t)i * 16]) { bad = i; break; }
+    SetErr(err, "animation, codestream frame %d: %s", c.first + bad, detail.errorMessage);
+  }
+  return st;
+}
+
+extern "C" {
+
+JxlHipAnimation* jxlhip_animation_open(int32_t device, const uint8_t* data, size_t size, JxlHipAnimationInfo* info, ErrorInfo* err) {
+  if (!data) { SetErr(err, "null file"); return nullptr; }
+  try {
+    // everything the parser refuses is refused here, before any HIP call
+    std::unique_ptr<JxlHipAnimation> a(new JxlHipAnimation());
+    a->file.assign(data, data + size);
+    ParseAnimation(a->file.data(), a->file.size(), false, a->anim);
+    a->plan = PlanAnimation(a->anim);
+    ParsedFrame& head = a->anim.head;
+    {
+      auto cs_copy = std::move(head.cs_copy);
+      auto owned = std::move(head.owned_boxes);
+      a->top = head;
+      head.cs_copy = std::move(cs_copy);
+      head.owned_boxes = std::move(owned);
+    }
+    for (auto& fr : a->anim.frames) { fr.cs_file_offset = 0; fr.cs_contiguous = true; }   // d_cs holds the codestream itself
+    const size_t nch = OutSamplesPerPixel(head);
+    a->image_bytes = (size_t)head.xsize * head.ysize * nch * OutBytesPerSample(head);
+    int live = 0, nslots = 0;
+    for (int m : a->plan.live_after) live |= m;
+    for (int s = 0; s < 4; s++) if (live >> s & 1) a->slot_plane[s] = nslots++;
+    a->dec.reset(new JxlHipDecoder(device));
+    a->dec->single_slot = true;
+    HIP_OK(hipMalloc(&a->d_cs, head.cs_size + 16));
+    HIP_OK(hipMemcpy(a->d_cs, head.cs, head.cs_size, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(a->d_cs + head.cs_size, 0, 16));
+    for (float*& p : a->d_slots) if (nslots) HIP_OK(hipMalloc(&p, (size_t)nslots * head.xsize * head.ysize * nch * sizeof(float)));
+    if (info) {
+      memset(info, 0, sizeof(*info));
+      info->width = head.orientation >= 5 ? head.ysize : head.xsize; info->height = head.orientation >= 5 ? head.xsize : head.ysize;
+      info->has_alpha = head.alpha_index >= 0;
+      info->num_channels = (int32_t)nch;
+      info->bytes_per_sample = (int32_t)OutBytesPerSample(head);
+      info->float_samples = head.exp_bits ? 1 : 0;
+      info->bits_per_sample = (int32_t)head.bits;
+      info->have_animation = head.have_animation;
+      info->tps_numerator = head.tps_numerator; info->tps_denominator = head.tps_denominator; info->num_loops = head.num_loops;
+      info->have_timecodes = head.have_timecodes;
+      info->num_displayed = (int32_t)a->anim.completes.size();
+      info->num_codestream_frames = (int32_t)a->anim.frames.size();
+      info->image_bytes = a->image_bytes;
+    }
+    return a.release();
+  } catch (const std::exception& e) {
+    SetErr(err, "%s", e.what());
+    return nullptr;
+  }
+}
+
+void jxlhip_animation_close(JxlHipAnimation* a) { delete a; }
+
+JxlHipDecoder* jxlhip_animation_decoder(JxlHipAnimation* a) { return a ? a->dec.get() : nullptr; }
+
+int32_t jxlhip_animation_frame(JxlHipAnimation* a, int32_t j, JxlHipAnimationFrame* out) {
+  if (!a || !out || j < 0 || j >= (int32_t)a->anim.completes.size()) return 0;
+  const int k = a->anim.completes[j];
+  const ParsedFrame& fr = a->anim.frames[k];
+  memset(out, 0, sizeof(*out));
+  out->duration = fr.duration; out->timecode = fr.timecode;
+  out->first_codestream_frame = j > 0 ? a->anim.completes[j - 1] + 1 : 0;
+  out->num_codestream_frames = k + 1 - out->first_codestream_frame;
+  out->name_length = (int32_t)std::min(fr.name.size(), sizeof(out->name) - 1);
+  memcpy(out->name, fr.name.data(), (size_t)out->name_length);
+  return 1;
+}
+
+DecoderStatus jxlhip_animation_next(JxlHipAnimation* a, int32_t count, void* dev_out, size_t capacity, int32_t* written, ErrorInfo* err) {
+  if (written) *written = 0;
+  if (!a || (count > 0 && !dev_out)) return DecoderStatus_NullParameter;
+  try {
+    const int total = (int)a->anim.completes.size();
+    const int n = std::max(0, std::min(count, total - a->next_shown));
+    if ((size_t)n > capacity / std::max<size_t>(1, a->image_bytes)) {
+      SetErr(err, "the buffer holds %zu bytes, %d displayed images need %zu", capacity, n, (size_t)n * a->image_bytes);
+      return DecoderStatus_InvalidParameter;
+    }
+    const int last = a->next_shown + n - 1;
+    int done = 0;
+    while (a->next_shown <= last) {
+      const AnimChunk c = NextChunk(a->anim, a->plan, a->next_frame, last, a->chunk_frames, kAnimChunkScratch);
+      const DecoderStatus st = a->RunChunk(c, (uint8_t*)dev_out + (size_t)done * a->image_bytes, err);
+      if (st != DecoderStatus_Ok) return st;   // the position stays in front of the chunk
+      a->next_frame += c.count;
+      a->next_shown += c.shown;
+      done += c.shown;
+      if (written) *written = done;
+    }
+    return DecoderStatus_Ok;
+  } catch (const std::bad_alloc&) {
+    return DecoderStatus_OutOfMemory;
+  } catch (const std::exception& e) {
+    SetErr(err, "%s", e.what());
+    return DecoderStatus_DecodeError;
+  }
+}
+
+void jxlhip_animation_rewind(JxlHipAnimation* a) {
+  if (a) a->next_frame = a->next_shown = 0;   // (the first chunk loads no slot: nothing of the old state is read)
+}
+
+int32_t jxlhip_animation_set_option(JxlHipAnimation* a, const char* name, int32_t value) {
+  if (!a || !name) return 0;
+  if (!strcmp(name, "chunk_frames")) { if (value < 0) return 0; a->chunk_frames = value; return 1; }
+  // of the decoder's options, those that choose between launch shapes with the same output; neither a band nor a reduced size is
+  // offered here, and nothing that changes the layout the chunk plan measured (debug_taps)
+  for (const char* ok : {"lane_stride", "no_direct", "mod_lanes64", "no_stream_pairs", "no_lf_pipeline"})
+    if (!strcmp(name, ok)) return jxlhip_set_option(a->dec.get(), name, value);
+  return 0;
+}
 
 }  // extern "C"
 

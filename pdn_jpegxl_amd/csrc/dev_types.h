@@ -247,14 +247,24 @@ struct ComposeFrame {
   int32_t source[2];        // reference slot each of them blends onto (an empty slot reads as 0)
   int32_t clamp[2];         // clamp the blending alpha (and, for mul, the new sample) to [0, 1]
   int32_t save;             // slot the blended canvas is saved to, -1: none
-  int32_t pad;
+  int32_t show;             // the displayed image of this launch that the canvas after this frame is (stored at out + show * out_stride), -1: none
 };
 struct ComposeImage {
   int32_t w, h, nch, has_alpha;                 // canvas; nch = colour channels + alpha, alpha last
   int32_t premul, orientation, out_bits, out_float;
-  int32_t first, count;                         // frames [first, first + count) of the frame table, the last one is displayed
+  int32_t first, count;                         // frames [first, first + count) of the frame table; a still: the last one is displayed (show 0)
   int32_t raw, pad0;                            // raw: every frame replaces every channel; frames hold output-type samples (px as bytes)
-  uint8_t* out;                                 // the displayed image, oriented, interleaved samples of the output type
+  // Animations decoded in chunks of frames: the reference slots that a later chunk reads travel through memory.  Slot s
+  // of pixel p is the nch floats at slots[(slot_plane[s] * w * h + p) * nch] (raw images: bit patterns, as in registers; only the slots
+  // that are alive at some cut of the file have a plane).  Bit s of live_in: the lane loads slot s at entry (the others start as 0); of
+  // live_out: it stores slot s at exit.  Stills: both 0, no buffer.  slots_in and slots_out are two buffers: a chunk that fails leaves
+  // the state it started from as it was (decoder.cc swaps them after a chunk that succeeded).
+  int32_t live_in, live_out;
+  int32_t slot_plane[4];
+  uint64_t out_stride;                          // bytes from one displayed image of this launch to the next in `out`
+  const float* slots_in;
+  float* slots_out;
+  uint8_t* out;                                 // the displayed image(s), oriented, interleaved samples of the output type
 };
 
 // Patches (patch_kernels.hip): a frame's f32 samples updated in place from rectangles of reference-only frames (atlases), before the

@@ -476,9 +476,9 @@ void ReadImageHeader(Bits& r, ParsedFrame& f) {
       if (r.b()) Fail("preview frames are not supported");
       f.have_animation = r.b();
       if (f.have_animation) {
-        r.U32(V(100), V(1000), B(10, 1), B(30, 1));
-        r.U32(V(1), V(1001), B(8, 1), B(10, 1));
-        r.U32(V(0), B(3), B(16), B(32));
+        f.tps_numerator = r.U32(V(100), V(1000), B(10, 1), B(30, 1));
+        f.tps_denominator = r.U32(V(1), V(1001), B(8, 1), B(10, 1));
+        f.num_loops = r.U32(V(0), B(3), B(16), B(32));
         f.have_timecodes = r.b();
       }
     }
@@ -610,7 +610,7 @@ void ReadFrameHeader(Bits& r, ParsedFrame& f) {
     bool full = !have_crop || (x0 <= 0 && y0 <= 0 && x0 + (int64_t)cw >= f.xsize && y0 + (int64_t)ch >= f.ysize);
     if (normal) {
       for (auto& b : f.blend) ReadBlending(r, f.ec.size(), !full, &b);
-      if (f.have_animation) { duration = r.U32(V(0), V(1), B(8), B(32)); if (f.have_timecodes) r.u(32); }
+      if (f.have_animation) { duration = r.U32(V(0), V(1), B(8), B(32)); if (f.have_timecodes) f.timecode = r.u(32); }
       f.is_last = r.b();
     } else f.is_last = false;
     if (f.frame_type != 1 && !f.is_last) save_ref = r.u(2);
@@ -1667,7 +1667,9 @@ void ParseFrameBody(ParsedFrame& f) {
   }
 }
 
-void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame& f) {
+// Container, signature, image header and ICC profile into f; `image` becomes the image header alone (without the container's buffers,
+// which stay with f): where every frame of a layered image or an animation starts from.  Returns the bit position of the first frame.
+size_t ReadFileHead(const uint8_t* data, size_t size, ParsedFrame& f, ParsedFrame& image) {
   f = ParsedFrame();
   SplitContainer(data, size, f);
   if (!(f.cs_size >= 2 && f.cs[0] == 0xFF && f.cs[1] == 0x0A)) Fail("invalid codestream signature", stInvalidSignature);
@@ -1676,16 +1678,19 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
   ReadImageHeader(r, f);
   if (f.color.want_icc) ReadIcc(r, f);
   r.Align();
-  const size_t frame_base = r.pos();
-  // the image header alone (without the container's buffers, which stay with f): where every frame of a layered image starts from
+  auto cs_copy = std::move(f.cs_copy);
+  auto owned = std::move(f.owned_boxes);
+  image = f;
+  f.cs_copy = std::move(cs_copy);
+  f.owned_boxes = std::move(owned);
+  return r.pos();
+}
+
+void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame& f) {
   ParsedFrame image;
-  {
-    auto cs_copy = std::move(f.cs_copy);
-    auto owned = std::move(f.owned_boxes);
-    image = f;
-    f.cs_copy = std::move(cs_copy);
-    f.owned_boxes = std::move(owned);
-  }
+  const size_t frame_base = ReadFileHead(data, size, f, image);
+  Bits r(f.cs, f.cs_size);
+  r.Skip(frame_base);
   ReadFrameHeader(r, f);
   ReadToc(r, f, frame_base);
   if (IsSingleFrameImage(f)) {
@@ -1788,6 +1793,83 @@ void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame&
         Fail("reference-only frames are not supported yet (layered image, frame " + std::to_string(k) + "): no patch reads it");
   }
   f.layers = std::move(layers);
+}
+
+// Which reference slots a regular frame reads (bit s): the source of a channel group is read by a blend mode other than kReplace, and
+// outside a crop that does not cover the canvas.  The channel groups are the colour channels and the alpha channel.
+int SlotsRead(const ParsedFrame& fr, uint32_t canvas_w, uint32_t canvas_h) {
+  const bool partial = fr.have_crop && !(fr.crop_x0 <= 0 && fr.crop_y0 <= 0 && fr.crop_x0 + (int64_t)fr.xsize >= canvas_w &&
+                                         fr.crop_y0 + (int64_t)fr.ysize >= canvas_h);
+  const BlendInfo& bc = fr.blend[0];
+  const BlendInfo& ba = fr.alpha_index >= 0 ? fr.blend[1 + fr.alpha_index] : bc;
+  int m = 0;
+  if (bc.mode != 0 || partial) m |= 1 << (bc.source & 3);
+  if (ba.mode != 0 || partial) m |= 1 << (ba.source & 3);
+  return m;
+}
+
+// The walk of an animation: every frame from the first to the one with is_last, under ParseFile's rules for a frame of a layered image
+// (CheckLayerFrame, the save rule, the noise seeds), with no cap on their number.
+void ParseAnimation(const uint8_t* data, size_t size, bool headers_only, Animation& a) {
+  a = Animation();
+  ParsedFrame image;
+  const size_t frame_base = ReadFileHead(data, size, a.head, image);
+  uint64_t pos = frame_base / 8;
+  const int slot_frame[4] = {-1, -1, -1, -1};   // (no reference-only frame is ever in a slot here: they are refused below)
+  uint32_t visible_index = 0, nonvisible_index = 0;
+  for (;;) {
+    a.frames.push_back(image);
+    ParsedFrame& fr = a.frames.back();
+    const size_t k = a.frames.size() - 1;
+    fr.is_layer = true;
+    Bits rr(a.head.cs, a.head.cs_size);
+    rr.Skip((size_t)pos * 8);
+    ReadFrameHeader(rr, fr);
+    ReadToc(rr, fr, (size_t)pos * 8);
+    const std::string at = "frame " + std::to_string(k) + ")";
+    if ((fr.flags & 2) || fr.frame_type == 2) Fail("animations with patches are not supported (animation, " + at);
+    // a file that is one single-frame image (what LoadImage decodes without compositing) is accepted as that: one displayed image
+    // through the single-frame path, CMYK included; every other frame is a frame of a layered image
+    a.single = k == 0 && fr.is_last && IsSingleFrameImage(fr);
+    try {
+      if (a.single) CheckSingleFrame(fr);
+      else CheckLayerFrame(fr, k, slot_frame, a.frames);
+    } catch (const ParseError& e) {
+      throw ParseError(e.status, std::string(e.what()) + " (animation, " + at);
+    }
+    if (a.single) fr.is_layer = false;
+    fr.noise_seed[0] = visible_index; fr.noise_seed[1] = nonvisible_index;
+    const bool shown = fr.is_last || (fr.have_animation && fr.duration > 0);
+    if (fr.is_last || fr.duration > 0) { visible_index++; nonvisible_index = 0; }
+    else nonvisible_index++;
+    const bool can_ref = !fr.is_last && (fr.duration == 0 || fr.save_ref != 0);
+    a.save.push_back(can_ref ? (int)fr.save_ref : -1);
+    a.show.push_back(shown ? (int)a.completes.size() : -1);
+    if (shown) a.completes.push_back((int)k);
+    if (fr.is_last) break;
+    pos = fr.frame_end;
+    REQUIRE(pos < a.head.cs_size, "the codestream ends before the last frame");
+  }
+  // raw / f32 once over the whole file, by ParseFile's rule: only files whose frames all replace every channel stay a selection of
+  // output-type samples
+  a.raw = true;
+  for (auto& fr : a.frames) a.raw = a.raw && ReplacesAll(fr);
+  for (size_t k = 0; k < a.frames.size(); k++) {
+    ParsedFrame& fr = a.frames[k];
+    fr.layer_f32 = !a.raw;
+    if (fr.encoding == 0 && !a.raw)
+      Fail("lossy (XYB) frames are supported only in layered images whose frames all replace (layered image, frame " + std::to_string(k) + ")");
+  }
+  a.head.xsize = image.xsize; a.head.ysize = image.ysize;
+  FrameGeometry(a.head);
+  if (!headers_only)
+    for (size_t k = 0; k < a.frames.size(); k++) {
+      try {
+        ParseFrameBody(a.frames[k]);
+      } catch (const ParseError& e) {
+        throw ParseError(e.status, std::string(e.what()) + " (animation, frame " + std::to_string(k) + ")");
+      }
+    }
 }
 
 uint64_t ParseHfGlobalAt(ParsedFrame& f, uint64_t bit_pos) {

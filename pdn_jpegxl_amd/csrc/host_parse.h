@@ -92,6 +92,7 @@ struct ParsedFrame {
   std::vector<uint8_t> icc;       // the embedded ICC profile (want_icc), decoded
   float intensity_target = 255.f;
   bool have_animation = false, have_timecodes = false;
+  uint32_t tps_numerator = 0, tps_denominator = 0, num_loops = 0;   // the animation header (have_animation): ticks per second, 0 loops = endless
   float opsin_inv[9], opsin_bias[3], qbias[4];
   int alpha_index = -1, black_index = -1;
   int ncolor = 3;
@@ -105,6 +106,7 @@ struct ParsedFrame {
   bool have_crop = false, do_ycbcr = false, save_before_ct = false;
   int32_t crop_x0 = 0, crop_y0 = 0;
   uint32_t upsampling = 1, duration = 0, save_ref = 0;
+  uint32_t timecode = 0;            // have_timecodes: the frame's SMPTE timecode, as written
   std::vector<BlendInfo> blend;     // [0] colour channels, [1 + k] extra channel k
   uint64_t frame_end = 0;           // byte offset in cs right after the frame's last section (the next frame header starts here)
   bool is_layer = false;            // one frame of a layered image: decoded to scratch, then composited (decoder.cc)
@@ -192,10 +194,37 @@ struct Layers {
   std::vector<int> save;
   bool raw = false;   // every frame replaces every channel: frames are decoded in the output type and the compositor selects
   bool patches = false;   // some frame applies patches from reference-only (type 2) frames: decoder.cc runs patch_kernel
+  // A chunk of an animation (decoder.cc builds these from an Animation; a still leaves them as they are): show[k] is the displayed image
+  // of the chunk that frame k completes (-1: none; empty: a still, whose last frame is image 0), the images are out_stride bytes
+  // apart, and the slots in live_in / live_out (bit s) are loaded from slots_in / stored to slots_out, slot s in plane slot_plane[s]
+  // (ComposeImage, dev_types.h).
+  std::vector<int> show;
+  int live_in = 0, live_out = 0;
+  int slot_plane[4] = {0, 0, 0, 0};
+  const float* slots_in = nullptr;
+  float* slots_out = nullptr;
+  uint64_t out_stride = 0;
 };
 
 // Throws ParseError.  headers_only: stop after the frame header + TOC (jxlhip_peek / pass 1 of LoadImage).
 void ParseFile(const uint8_t* data, size_t size, bool headers_only, ParsedFrame& out);
+
+// Every frame of a file, for the sequential decode of all its displayed images (jxlhip_animation_*).  Displayed
+// image j is the canvas after the j-th frame, in file order, that is is_last or has a duration (in a file with an animation header).
+// A file without one has exactly one displayed image.  `data` must outlive the object: the frames point into it.
+struct Animation {
+  ParsedFrame head;                // container and image header: the canvas (xsize / ysize), orientation, sample type, animation header
+  std::vector<ParsedFrame> frames; // file order, each parsed on its own (xsize / ysize = its crop), the last one is is_last
+  std::vector<int> save;           // slot frame k is saved to after blending (-1: none), by the save rule of layered images
+  std::vector<int> show;           // the displayed image frame k completes (-1: none)
+  std::vector<int> completes;      // displayed image j -> its frame
+  bool raw = false;                // every frame of the file replaces every channel (decided once for the file, as for a layered image)
+  bool single = false;             // the file is one single-frame image (ParseFile's rule): decoded as that, not composited
+};
+// Throws ParseError; a refusal names the frame.  Frames with the patches flag and reference-only frames are refused.
+void ParseAnimation(const uint8_t* data, size_t size, bool headers_only, Animation& out);
+// Bit s: the frame reads reference slot s (as the source of a channel group that blends, or outside a crop smaller than the canvas).
+int SlotsRead(const ParsedFrame& fr, uint32_t canvas_w, uint32_t canvas_h);
 // Single-section frames: parses HfGlobal at `bit_pos` (where the GPU finished the LF group); returns the bit position after it.
 uint64_t ParseHfGlobalAt(ParsedFrame& f, uint64_t bit_pos);
 

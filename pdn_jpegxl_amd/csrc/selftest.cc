@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "animation.h"
 #include "dev_util.h"
 #include "enc_types.h"
 #include "batch_layout.h"
@@ -823,4 +824,64 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_enc_batch_layout(int32_t n, 
   }
   if (out) memcpy(out, v.data(), std::min(capacity, v.size()) * sizeof(int64_t));
   return v.size();
+}
+
+// The plan of an animation decode, without a GPU (host_parse.h: ParseAnimation, animation.h).  counts[0 .. ncounts): the `count` of
+// successive jxlhip_animation_next calls (<= 0: all that is left).  scratch_budget: bytes of scratch a chunk may take (<= 0: the
+// decoder's kAnimChunkScratch).  out, as numbers (returns how many; 0: refused - *status and err say
+// why - or they do not fit `capacity`):
+//   frames, displayed images, have_animation, tps_numerator, tps_denominator, num_loops, have_timecodes, raw, canvas width, canvas height, is the file one
+//   single-frame image;
+//   per frame: displayed image it completes (-1), duration, timecode, save slot (-1), mask of the slots it reads, source and mode of the
+//   colour channels, source and mode of the alpha channel, is its crop smaller than the canvas, its scratch bytes, the slots alive
+//   behind it, the length of its name and the name's bytes;
+//   chunks, then per chunk: the call it belongs to, first frame, frames, first displayed image, displayed images, live_in, live_out.
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_animation_plan(const uint8_t* data, size_t size, int32_t chunk_frames, int64_t scratch_budget,
+                                                                   const int32_t* counts, int32_t ncounts, int64_t* out, size_t capacity, int32_t* status, ErrorInfo* err) {
+  if (status) *status = DecoderStatus_Ok;
+  try {
+    Animation a;
+    ParseAnimation(data, size, false, a);
+    const AnimPlan p = PlanAnimation(a);
+    std::vector<int64_t> v;
+    auto put = [&](int64_t x) { v.push_back(x); };
+    const ParsedFrame& h = a.head;
+    for (int64_t x : {(int64_t)a.frames.size(), (int64_t)a.completes.size(), (int64_t)h.have_animation, (int64_t)h.tps_numerator, (int64_t)h.tps_denominator,
+                      (int64_t)h.num_loops, (int64_t)h.have_timecodes, (int64_t)a.raw, (int64_t)h.xsize, (int64_t)h.ysize, (int64_t)a.single})
+      put(x);
+    for (size_t k = 0; k < a.frames.size(); k++) {
+      const ParsedFrame& f = a.frames[k];
+      const BlendInfo& bc = f.blend[0];
+      const BlendInfo& ba = f.alpha_index >= 0 ? f.blend[1 + f.alpha_index] : bc;
+      const bool partial = f.have_crop && !(f.crop_x0 <= 0 && f.crop_y0 <= 0 && f.crop_x0 + (int64_t)f.xsize >= h.xsize && f.crop_y0 + (int64_t)f.ysize >= h.ysize);
+      for (int64_t x : {(int64_t)a.show[k], (int64_t)f.duration, (int64_t)f.timecode, (int64_t)a.save[k], (int64_t)SlotsRead(f, h.xsize, h.ysize), (int64_t)bc.source,
+                        (int64_t)bc.mode, (int64_t)ba.source, (int64_t)ba.mode, (int64_t)partial, (int64_t)p.scratch[k], (int64_t)p.live_after[k], (int64_t)f.name.size()})
+        put(x);
+      for (char c : f.name) put((uint8_t)c);
+    }
+    const size_t nchunks_at = v.size();
+    put(0);
+    int next_frame = 0, next_shown = 0, nchunks = 0;
+    const int total = (int)a.completes.size();
+    for (int call = 0; call < ncounts; call++) {
+      const int n = counts[call] <= 0 ? total - next_shown : std::min(counts[call], total - next_shown);
+      const int last = next_shown + n - 1;
+      while (next_shown <= last) {
+        const AnimChunk c = NextChunk(a, p, next_frame, last, chunk_frames, scratch_budget > 0 ? (size_t)scratch_budget : kAnimChunkScratch);
+        for (int64_t x : {(int64_t)call, (int64_t)c.first, (int64_t)c.count, (int64_t)c.first_shown, (int64_t)c.shown, (int64_t)c.live_in, (int64_t)c.live_out}) put(x);
+        next_frame += c.count; next_shown += c.shown; nchunks++;
+      }
+    }
+    v[nchunks_at] = nchunks;
+    if (v.size() > capacity) return 0;
+    memcpy(out, v.data(), v.size() * sizeof(int64_t));
+    return v.size();
+  } catch (const ParseError& e) {
+    if (status) *status = e.status;
+    SetEncErr(err, e.what());
+  } catch (const std::exception& e) {
+    if (status) *status = DecoderStatus_DecodeError;
+    SetEncErr(err, e.what());
+  }
+  return 0;
 }
