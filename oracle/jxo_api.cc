@@ -93,7 +93,7 @@ void jxo_last_encode_token_counts(uint64_t out[4]) { GetLastEncodeTokenCounts(ou
 static thread_local std::vector<uint8_t> g_next_icc;
 static thread_local bool g_next_cmyk = false;
 static thread_local int g_next_frames = 1;
-static thread_local uint32_t g_next_flags = 0;   // 1: explicit (custom) dequantisation tables; 2: prefix codes; 4: LZ77; 8 / 16: two / three passes; 32: custom coefficient orders; 64: block contexts from LF / quant-field thresholds; 128: palette; 256: some DCT8 blocks labelled AFV (refusal tests); 512: alpha signalled as premultiplied
+static thread_local uint32_t g_next_flags = 0;   // 1: explicit (custom) dequantisation tables; 2: prefix codes; 4: LZ77; 8 / 16: two / three passes; 32: custom coefficient orders; 64: block contexts from LF / quant-field thresholds; 128: palette; 256: some DCT8 blocks labelled AFV (refusal tests); 512: alpha signalled as premultiplied; 1024: wide codes (jxo_entropy.cc: entropy test mode 4)
 void jxo_set_next_flags(uint32_t flags) { g_next_flags = flags; }
 // Side information of the next lossy frame (jxo_codec.h: SideInfo, a plain struct of 32-bit fields that ctypes mirrors)
 static thread_local SideInfo g_next_side;
@@ -157,7 +157,7 @@ JxoBytes* jxo_encode(const uint8_t* px, uint32_t w, uint32_t h, int32_t nch, con
     const uint32_t g_next_flags_entropy = g_next_flags;
     g_next_flags = 0;
     JxoBytes* b = new JxoBytes();
-    SetEntropyTestMode(((g_next_flags_entropy >> 1) & 3));
+    SetEntropyTestMode(((g_next_flags_entropy >> 1) & 3) | ((g_next_flags_entropy & 1024) ? 4 : 0));
     try {
       b->b = EncodeJxl(px, w, h, nch, p, exif, exif_size, xmp, xmp_size);
     } catch (...) { SetEntropyTestMode(0); delete b; throw; }

@@ -573,7 +573,8 @@ static double MergeCost(const RawHist& a, const RawHist& b) {
   return e - a.entropy - b.entropy;
 }
 
-// ---- test modes: prefix codes and LZ77
+// ---- test modes: 1 prefix codes, 2 LZ77, 4 wide codes (plain ANS codes with log_alpha 8 and up to 255 clusters: the used contexts
+// stay apart while they fit; tokens, contexts and everything else about the stream are unchanged)
 static uint32_t g_entropy_test_mode = 0;
 void SetEntropyTestMode(uint32_t mode) { g_entropy_test_mode = mode; }
 static std::mutex g_dm_mutex;
@@ -726,6 +727,7 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
   EntropyCode& code = out.code;
   const bool use_prefix = opt.use_prefix || (opt.top_level && (g_entropy_test_mode & 1));
   const bool lz77 = opt.lz77 || (opt.top_level && (g_entropy_test_mode & 2));
+  const bool wide = opt.top_level && !use_prefix && (g_entropy_test_mode & 4);
   out.num_contexts = num_contexts;
   const size_t data_contexts = num_contexts;
   if (lz77) num_contexts++;   // the distance context
@@ -754,7 +756,7 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
   std::vector<size_t> used;
   for (size_t i = 0; i < num_contexts; i++)
     if (hist[i].total) used.push_back(i);
-  size_t maxc = opt.force_single_cluster ? 1 : (size_t)std::max(1, std::min(opt.max_clusters, 255));
+  size_t maxc = opt.force_single_cluster ? 1 : (size_t)std::max(1, std::min(wide ? 255 : opt.max_clusters, 255));
   if (used.size() <= maxc) {
     for (size_t k = 0; k < used.size(); k++) {
       code.ctx_map[used[k]] = (uint8_t)k;
@@ -802,7 +804,7 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
   code.lz77 = lz77;
   code.lz_min_symbol = kLzMinSymbol; code.lz_min_length = kLzMinLength; code.lz_len_cfg = HybridUintConfig(4, 2, 0);
   code.use_prefix = use_prefix;
-  code.log_alpha = use_prefix ? 15 : std::max(5, CeilLog2(max_token + 1));
+  code.log_alpha = use_prefix ? 15 : wide ? 8 : std::max(5, CeilLog2(max_token + 1));
   JXO_CHECK(use_prefix || code.log_alpha <= 8, "log_alpha");
   code.cfg.assign(code.num_hist, opt.cfg);
   JXO_CHECK(opt.cfg.split_exponent <= code.log_alpha, "uint config vs alphabet");

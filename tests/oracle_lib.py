@@ -142,13 +142,15 @@ class OracleError(RuntimeError):
 def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, seed=1, epf_iters=-1, gaborish=True,
            container=True, adaptive_lf_smoothing=True, lossless_predictor=6, lossless_squeeze=False, num_threads=8, exif=None,
            xmp=None, lossless_tree=0, bits=8, orientation=1, float_samples=0, colour=0, icc=None, cmyk=False, animation_frames=1, custom_quant_tables=False, prefix_codes=False, lz77=False, num_passes=1, custom_orders=False, lf_contexts=False, palette=False, mislabel_afv=False,
-           premultiplied_alpha=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None):
+           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None):
     """px: uint8 array (h, w, nch) with nch in 1..4 (Gray, GrayA, RGB, RGBA); with bits > 8 (up to 16) a uint16 array whose
     samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes.
     side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters).
     tree / alpha_tree / lf_tree: an explicit MA tree for a lossless frame / for the alpha channel / for each LF channel of a lossy frame:
     a list of nodes (property or -1, split value, child for property > split value, other child, predictor, offset, multiplier), node 0
-    the root, children after their parent (oracle/jxo_codec.h: EncodeParams::tree)."""
+    the root, children after their parent (oracle/jxo_codec.h: EncodeParams::tree).
+    wide_codes: the frame's plain ANS codes are written with log_alpha 8 and up to 255 clusters (used contexts are not merged while they
+    fit); tokens, contexts and quantised data are those of the same call without it."""
     L = lib()
     if float_samples:
         px = np.ascontiguousarray(px, dtype=np.float16 if float_samples == 16 else np.float32)
@@ -159,10 +161,10 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
     h, w, nch = px.shape
     p = EncodeParams(distance, int(lossless), 7, strategy_mode, fixed_strategy, seed, epf_iters, int(gaborish), int(container),
                      int(adaptive_lf_smoothing), lossless_predictor, int(lossless_squeeze), lossless_tree, num_threads, bits, orientation, float_samples, colour)
-    if custom_quant_tables or prefix_codes or lz77 or num_passes > 1 or custom_orders or lf_contexts or palette or mislabel_afv or premultiplied_alpha:
+    if custom_quant_tables or prefix_codes or lz77 or num_passes > 1 or custom_orders or lf_contexts or palette or mislabel_afv or premultiplied_alpha or wide_codes:
         L.jxo_set_next_flags.argtypes = [C.c_uint32]
         L.jxo_set_next_flags((1 if custom_quant_tables else 0) | (2 if prefix_codes else 0) | (4 if lz77 else 0) | {1: 0, 2: 8, 3: 16}[num_passes] | (32 if custom_orders else 0) | (64 if lf_contexts else 0) | (128 if palette else 0) |
-                             (256 if mislabel_afv else 0) | (512 if premultiplied_alpha else 0))
+                             (256 if mislabel_afv else 0) | (512 if premultiplied_alpha else 0) | (1024 if wide_codes else 0))
     if side_info:
         L.jxo_set_next_side_info.argtypes = [C.POINTER(SideInfo)]
         L.jxo_side_info_size.restype = C.c_size_t

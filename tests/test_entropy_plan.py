@@ -193,10 +193,11 @@ def check_plan(P, band=(0, 0), downscale=1):
     assert not P["direct_lf"] or (P["global_direct"] and P["lf_per_wave"] == 1)
     assert not P["direct_alpha"] or (P["global_direct"] and P["per_alpha_wg"] == 1)
     assert not P["direct_mod"] or (P["global_direct"] and P["mod_lanes"] == 1)
-    # a launch asks for no more LDS than the limit, or keeps its tables in global memory (of the streams of this file only the LZ77
-    # one has tables that large, and only for the HF launch: the other launches' global-table branches are checked as "not taken")
+    # a launch asks for no more LDS than the limit, or keeps its tables in global memory - and only then: the plan has no other reason
+    # to leave LDS.  The `streams` below reach that form in the HF launch alone (LZ77); `global_streams` take every launch there, and
+    # check_global_launches states what those launches are handed
     for k in ("lf", "hf", "alpha", "mod"):
-        assert P["lds_" + k] <= c["lds_max"] or P[k + "_global"], k
+        assert P[k + "_global"] == int(P["lds_" + k] > c["lds_max"]), k
     # image records: the batch's frames, then the later passes of the progressive ones
     rec_of = {}
     extra = 0
@@ -394,3 +395,92 @@ def test_frames_that_failed_to_parse_contribute_nothing(streams):
     assert [f["decoded"] for f in P["frames"]] == [1, 0, 0, 1, 0]
     check_plan(P)
     assert {t[0] for name in TABLES for t in P[name]} == {0, 3}
+
+
+# ---------------------------------------------------------------- launches whose tables stay in global memory
+def big_tree(prop, n, preds):
+    """n thresholds around zero on one property, the leaves' predictors cycling through `preds`: 2 n + 1 nodes of 16 bytes."""
+    import ma_tree_util as M
+    leaf = M.Leaves(preds)
+    return M.flatten(M.buckets(prop, list(range(-(n // 2), n - n // 2)), [leaf() for _ in range(n + 1)]))
+
+
+@pytest.fixture(scope="module")
+def global_streams(oracle):
+    """Files one of whose launches cannot hold its tables in LDS: trees of 4 901 .. 10 417 nodes, or codes written with log_alpha 8 and
+    up to 255 clusters (oracle.encode(wide_codes=True): 2 KB of alias table per cluster).  tests/test_gpu_global_tables.py decodes them."""
+    def img(w, h, seed, nch=4):
+        return np.ascontiguousarray(synth(w, h, seed)[..., :nch])
+    S = {}
+    S["160x130 lossless, tree 4901"] = oracle.encode(img(160, 130, 1, 3), lossless=True, tree=big_tree(10, 2450, [5, 4, 7]))
+    S["257x200 lossless, tree 9601 weighted"] = oracle.encode(img(257, 200, 5, 3), lossless=True, tree=big_tree(15, 4800, [6, 5, 4, 7]))
+    S["257x200 lossless, tree 9601 row-static"] = oracle.encode(img(257, 200, 4, 3), lossless=True, tree=big_tree(2, 4800, [0, 1, 2, 5]))
+    noise = np.random.default_rng(131).integers(0, 256, (66, 65, 4), dtype=np.uint8)
+    S["65x66 lossless, wide code"] = oracle.encode(noise, lossless=True, tree=big_tree(10, 128, [5, 4, 7, 1]), wide_codes=True)
+    S["264x264 rgba, alpha + LF trees"] = oracle.encode(img(264, 264, 40 + 264), alpha_tree=big_tree(10, 2000, [5, 4, 7]), lf_tree=big_tree(9, 400, [5, 4, 7, 1]))
+    S["256x256 rgba, row-static trees"] = oracle.encode(img(256, 256, 40 + 256), alpha_tree=big_tree(2, 2000, [5, 1, 2, 0]), lf_tree=big_tree(2, 400, [5, 1, 2, 0]))
+    S["520x264 rgba, LF tree"] = oracle.encode(img(520, 264, 40 + 520), lf_tree=big_tree(9, 1600, [5, 4, 7, 1]))
+    S["520x300 rgba, wide code"] = oracle.encode(img(520, 300, 3), strategy_mode=2, wide_codes=True)
+    S["520x300 rgba, wide code, 2 passes"] = oracle.encode(img(520, 300, 5), strategy_mode=2, num_passes=2, wide_codes=True)
+    return S
+
+
+def check_global_launches(P, want):
+    """The launches named in `want`, and no others, keep their tables in global memory.  Such a launch is handed the lanes' bytes alone
+    (the Launch* wrappers of entropy_kernels.hip ask the layouts for them): what the layouts report for the launch's shape must be what
+    the lanes need by the arithmetic written out here, for every frame of the launch, and within the limit."""
+    c = constants()
+    ring = c["ring_words"] * 4
+    assert {k for k in ("lf", "hf", "alpha", "mod") if P[k + "_global"]} == set(want)
+    for f in P["frames"]:
+        if not f["decoded"]:
+            continue
+        if f["encoding"] == 1 and P["mod_global"]:
+            lanes, rb, wp = P["mod_lanes"], P["mod_rb"], P["mod_wp_lds"]
+            handed = layout(3, lanes, rb, wp, 0, f["tree_nodes"], *f["mcode"])[10]   # (never the uniform shape)
+            assert handed == 64 * ring + lanes * rb * 4 + (lanes * c["wp_ints"] * (rb + 2) * 4 if wp else 0) and handed <= c["lds_max"]
+        if f["encoding"] == 0 and P["lf_global"]:
+            assert layout(2, P["lf_per_wave"], f["tree_nodes"], *f["mcode"])[7] == P["lf_per_wave"] * ring <= c["lds_max"]
+        if f["encoding"] == 0 and P["alpha_global"] and f["has_alpha"]:
+            slots = P["per_alpha_wg"]
+            rows, end = layout(6, slots, f["tree_nodes"], *f["mcode"])[4:6]   # the one-pass rows straight behind the bit windows
+            assert (rows, end) == (slots * ring, slots * ring + slots * 256) and end <= c["lds_max"]
+            assert layout(2, slots, f["tree_nodes"], *f["mcode"])[7] == slots * ring   # launches without the one-pass rows
+    if P["hf_global"]:
+        lanes = [layout(4, count, 1, 8, 1, 0)[9] for _, _, count in P["pass"]]   # (the lanes' bytes do not depend on the code)
+        assert P["lds_hf_lanes"] == max(lanes) <= c["lds_max"]
+        assert all(b == (count + 3) // 4 * 4 * (c["hf_ring_words"] * 4 + c["hf_ring_words"] * 2 + c["nzcol"]) for b, (_, _, count) in zip(lanes, P["pass"]))
+
+
+GLOBAL_WANT = {"160x130 lossless, tree 4901": ["mod"], "257x200 lossless, tree 9601 weighted": ["mod"], "257x200 lossless, tree 9601 row-static": ["mod"],
+               "65x66 lossless, wide code": ["mod"], "264x264 rgba, alpha + LF trees": ["lf", "alpha"], "256x256 rgba, row-static trees": ["lf", "alpha"],
+               "520x264 rgba, LF tree": ["lf", "alpha"], "520x300 rgba, wide code": ["hf"], "520x300 rgba, wide code, 2 passes": ["hf"]}
+
+
+@pytest.mark.parametrize("opts", VARIANTS, ids=lambda o: ",".join("%s=%s" % kv for kv in o.items()) or "defaults")
+def test_plan_of_streams_whose_tables_do_not_fit_lds(streams, global_streams, opts):
+    assert set(GLOBAL_WANT) == set(global_streams)
+    ds = opts.get("downscale", 1)
+    for name, data in global_streams.items():
+        P = plan_of([data], **opts)
+        assert all(f["decoded"] for f in P["frames"]), name
+        check_plan(P, downscale=ds)
+        # (a reduced-size decode of an opaque frame launches no HF decoder: nothing to keep anywhere)
+        want = [k for k in GLOBAL_WANT[name] if not (k == "hf" and ds == 8 and not P["frames"][0]["hf"])]
+        check_global_launches(P, want)
+    by = {k: plan_of([v])["frames"][0] for k, v in global_streams.items()}
+    assert by["160x130 lossless, tree 4901"]["tree_nodes"] == 4901 and by["160x130 lossless, tree 4901"]["single"]
+    assert by["257x200 lossless, tree 9601 weighted"]["tree_uses_wp"] and by["257x200 lossless, tree 9601 row-static"]["tree_row_static"]
+    assert by["65x66 lossless, wide code"]["mcode"][:2] == (129, 8) and by["65x66 lossless, wide code"]["tree_nodes"] == 257
+    assert by["264x264 rgba, alpha + LF trees"]["tree_nodes"] == 2 * 4001 + 3 * 801 + 12 and by["256x256 rgba, row-static trees"]["single"]
+    assert by["520x300 rgba, wide code"]["acodes"] == [(255, 8, 7425, 0)] and by["520x300 rgba, wide code, 2 passes"]["acodes"] == [(255, 8, 7425, 0)] * 2
+    # one such frame takes the whole launch with it: every ordinary stream of this file in one batch with all of them
+    files = list(streams.values()) + list(global_streams.values())
+    P = plan_of(files, **opts)
+    check_plan(P, downscale=ds)
+    check_global_launches(P, ["lf", "hf", "alpha", "mod"])
+    # ... and the ordinary streams with one of them at a time
+    for name in ("160x130 lossless, tree 4901", "520x264 rgba, LF tree", "520x300 rgba, wide code"):
+        P = plan_of(list(streams.values()) + [global_streams[name]], **opts)
+        check_plan(P, downscale=ds)
+        check_global_launches(P, sorted(set(GLOBAL_WANT[name]) | {"hf"}))   # (hf: the LZ77 stream of `streams`)

@@ -238,6 +238,63 @@ def test_stream_coding_variants_decode_to_the_same_pixels(oracle, opts):
         assert (a == b).all()
 
 
+WIDE_LOSSY = [dict(), dict(num_passes=2), dict(custom_orders=True), dict(lf_contexts=True), dict(lz77=True), dict(distance=0.1, strategy_mode=1)]
+
+
+@pytest.mark.parametrize("opts", WIDE_LOSSY, ids=lambda o: ",".join("%s=%s" % kv for kv in o.items()) or "plain")
+def test_wide_codes_change_the_coding_of_a_lossy_frame_only(oracle, opts):
+    """wide_codes: plain ANS codes with log_alpha 8 and up to 255 clusters.  The oracle reads the file back to the same quantised
+    data, block layout and pixels as the file written without it; the product's parser sees the width and the cluster count."""
+    from test_entropy_plan import plan_of
+    img = synth(530, 300, 41)
+    if "distance" in opts:   # full blocks of non-zeros
+        img = np.random.default_rng(1).integers(0, 256, img.shape, dtype=np.uint8)
+    opts = dict(dict(strategy_mode=2, seed=3), **opts)
+    def token_counts():   # of the last frame this thread wrote
+        import ctypes as C
+        out = (C.c_uint64 * 4)()
+        oracle.lib().jxo_last_encode_token_counts(out)
+        return list(out)
+    wide = oracle.encode(img, wide_codes=True, **opts)
+    tokens_wide = token_counts()
+    plain = oracle.encode(img, **opts)
+    assert wide != plain and tokens_wide == token_counts() and sum(tokens_wide) > 0
+    a, b = oracle.decode(wide, want_dump=True), oracle.decode(plain, want_dump=True)
+    assert (a.pixels == b.pixels).all()
+    for name in ("qcoef", "lf_quant"):
+        assert all(np.array_equal(x, y) for x, y in zip(a.planes[name], b.planes[name])), name
+    for name in ("strategy", "raw_quant", "sharpness", "ytox", "ytob", "alpha"):
+        assert np.array_equal(a.planes[name], b.planes[name]), name
+    fw, fp = plan_of([wide])["frames"][0], plan_of([plain])["frames"][0]
+    for cw, cp in zip(fw["acodes"] + [fw["mcode"]], fp["acodes"] + [fp["mcode"]]):
+        assert cw[1] == 8 and cw[3] == 0 and (cp[1] < 8 or "lz77" in opts)   # log_alpha (the LZ77 symbols need 8 themselves); plain ANS
+        assert cw[0] >= cp[0] and cw[2] == cp[2]              # no fewer clusters over the same contexts
+    assert all(96 < c[0] <= 255 for c in fw["acodes"])        # beyond the writer's own limit of 96 clusters
+
+
+@pytest.mark.parametrize("size", [(2, 3), (63, 5), (65, 66), (300, 280)])
+@pytest.mark.parametrize("tree", ["default", "129 leaves", "264 leaves"])
+def test_wide_codes_lossless_round_trip(oracle, size, tree):
+    """Used contexts stay apart while they fit 255 clusters (129 leaves) and are clustered down to 255 where they do not (a leaf per
+    channel and row of 65 x 66 RGBA)."""
+    import ma_tree_util as M
+    from test_entropy_plan import plan_of
+    w, h = size
+    img = np.random.default_rng(w * h).integers(0, 256, (h, w, 4), dtype=np.uint8)
+    nodes = None
+    if tree == "129 leaves":
+        leaf = M.Leaves([5, 4, 7, 1])
+        nodes = M.flatten(M.buckets(10, [3 * (k - 64) for k in range(128)], [leaf() for _ in range(129)]))
+    elif tree == "264 leaves":
+        nodes = M.flatten(M.buckets(0, [0, 1, 2], [M.buckets(2, list(range(65)), [M.L((0, 1, 2, 5)[(c + y) % 4]) for y in range(66)]) for c in range(4)]))
+    wide, plain = oracle.encode(img, lossless=True, tree=nodes, wide_codes=True), oracle.encode(img, lossless=True, tree=nodes)
+    assert (oracle.decode(wide).pixels == img).all() and (oracle.decode(plain).pixels == img).all()
+    cw, cp = plan_of([wide])["frames"][0]["mcode"], plan_of([plain])["frames"][0]["mcode"]
+    assert cw[1] == 8 and cp[1] < 8 and cw[2] == cp[2] and cp[0] <= cw[0] <= 255
+    if size == (65, 66) and tree != "default":
+        assert cw[0] == {"129 leaves": 129, "264 leaves": 255}[tree] and cp[0] == 64
+
+
 @pytest.mark.parametrize("nch", [1, 2, 3, 4])
 def test_palette_round_trip(oracle, nch):
     rng = np.random.default_rng(nch)
