@@ -386,7 +386,9 @@ struct VarDctEncoder {
       ytox[0] = -128; ytob[0] = 127;
       if (ytox.size() > 1) { ytox[1] = 127; ytob[1] = -128; }
     }
-    // Y of one varblock: quantised values and what the decoder makes of them (its quant biases included)
+    // Y of one varblock: quantised values and what the decoder makes of them (its quant biases included).  Quantised HF values are
+    // clamped to +-32767 ("Quantiser"): Y before it is dequantised, so chroma from luma uses what a decoder sees.
+    const float kMaxQuantHf = 32767.0f;
     auto quant_y = [&](int s, size_t cell, const float* coef_y, std::vector<int32_t>* q, float* yd) {
       const size_t size = (size_t)kCoveredX[s] * kCoveredY[s] * 64;
       const float dqs = inv_gs / raw_quant[cell];
@@ -395,7 +397,7 @@ struct VarDctEncoder {
       for (size_t k = 0; k < size; k++) {
         float v = coef_y[k] / (dqs * wq[k]);
         float a = std::fabs(v);
-        int32_t qi = a < 0.6f ? 0 : (int32_t)std::lrint(v);
+        int32_t qi = a < 0.6f ? 0 : (int32_t)std::lrint(std::max(-kMaxQuantHf, std::min(kMaxQuantHf, v)));
         if (q) (*q)[k] = qi;
         float adj = qi == 0 ? 0 : (std::abs(qi) == 1 ? (qi > 0 ? m.quant_bias[1] : -m.quant_bias[1]) : qi - m.quant_bias[3] / qi);
         yd[k] = adj * dqs * wq[k];
@@ -478,7 +480,7 @@ struct VarDctEncoder {
             float target = coef[c][k] - cfl[c] * yd[k];
             float v = target / (dqs[c] * wq[k]);
             float a = std::fabs(v);
-            q[k] = a < 0.6f ? 0 : (int32_t)std::lrint(v);
+            q[k] = a < 0.6f ? 0 : (int32_t)std::lrint(std::max(-kMaxQuantHf, std::min(kMaxQuantHf, v)));
           }
         }
       }

@@ -17,6 +17,7 @@ constexpr uint32_t kAcContexts = 495 * 15;    // one preset, default block-conte
 constexpr uint32_t kLfTokCap = 3 * 65536;     // tokens per LF group: LF coefficients
 constexpr uint32_t kMetaTokCap = 2 * 65536;   // ... and the two rows of the block info (strategies, quant field)
 constexpr uint32_t kAcTokCap = 3 * 65 * 1024; // tokens per group: 1 + 64 per (block, channel)
+constexpr int32_t kMaxQuantHf = 32767;        // largest |quantised HF value| written: hf_decode_kernel keeps each value as an int16
 // Capacities and the sample depth (jxlhip_save_pixels takes up to 16-bit integers and binary16 / binary32 samples).  The token COUNTS
 // do not depend on the depth: one token per sample, a group is at most 256 x 256 samples per channel.  What grows with the depth is
 // the value a token carries, and with it the bits a token takes in its section:

@@ -428,7 +428,9 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
         const float w = im.dq[e_qtable[s]][(size_t)c * R * C + p];
         const float target = c == 2 ? coef - s_yd[y * P + x] : coef;
         const float v = target / (dqs * w);
-        qi = fabsf(v) < 0.6f ? 0 : (int32_t)rintf(v);
+        // clamped to what a decoder's int16 entry holds (float input far above 1.0 at a small distance gets there); Y's clamped value is
+        // the one dequantised below, so B's chroma from luma uses what the decoder will see
+        qi = fabsf(v) < 0.6f ? 0 : (int32_t)rintf(fminf(fmaxf(v, -(float)kMaxQuantHf), (float)kMaxQuantHf));
         if (c == 1) {
           const float adj = qi == 0 ? 0.f : (abs(qi) == 1 ? (qi > 0 ? im.qbias1 : -im.qbias1) : (float)qi - im.qbias3 / (float)qi);
           s_yd[y * P + x] = adj * dqs * w;
