@@ -66,6 +66,15 @@ size_t jxo_image_plane(const JxoImage* im, const char* name, int c, const void**
   return 0;
 }
 
+// Coded channels of a Modular frame decoded with want_dump (StageDump::mod_coded): their number, then channel i with its size
+int32_t jxo_image_mod_coded_count(const JxoImage* im) { return (int32_t)im->r.dump.mod_coded.size(); }
+const int32_t* jxo_image_mod_coded(const JxoImage* im, int32_t i, int32_t* w, int32_t* h) {
+  const StageDump& d = im->r.dump;
+  if (i < 0 || (size_t)i >= d.mod_coded.size()) { *w = *h = 0; return nullptr; }
+  *w = d.mod_coded_w[i]; *h = d.mod_coded_h[i];
+  return d.mod_coded[i].data();
+}
+
 struct JxoEncodeParams {
   float distance;
   int32_t lossless;
@@ -103,6 +112,13 @@ size_t jxo_side_info_size() { return sizeof(SideInfo); }
 static thread_local std::vector<int32_t> g_next_tree[3];
 void jxo_set_next_tree(const int32_t* nodes, size_t n, int role) {
   if (role >= 0 && role < 3) g_next_tree[role].assign(nodes, nodes + 7 * n);
+}
+// Explicit transform list of the next (lossless) jxo_encode call (EncodeParams::transforms); n = 0 is a list too: no transform at all
+static thread_local std::vector<int32_t> g_next_transforms;
+static thread_local bool g_next_have_transforms = false;
+void jxo_set_next_transforms(const int32_t* data, size_t n) {
+  g_next_transforms.assign(data, data + n);
+  g_next_have_transforms = true;
 }
 void jxo_set_next_animation(int frames) { g_next_frames = frames; }
 void jxo_set_next_icc(const uint8_t* icc, size_t size, int cmyk) {
@@ -154,6 +170,8 @@ JxoBytes* jxo_encode(const uint8_t* px, uint32_t w, uint32_t h, int32_t nch, con
     p.num_passes = (g_next_flags & 16) ? 3 : ((g_next_flags & 8) ? 2 : 1);
     p.side = g_next_side; g_next_side = SideInfo();
     for (int r = 0; r < 3; r++) { p.tree[r].swap(g_next_tree[r]); g_next_tree[r].clear(); }
+    p.transforms.swap(g_next_transforms); g_next_transforms.clear();
+    p.have_transforms = g_next_have_transforms; g_next_have_transforms = false;
     const uint32_t g_next_flags_entropy = g_next_flags;
     g_next_flags = 0;
     JxoBytes* b = new JxoBytes();

@@ -23,6 +23,9 @@ struct StageDump {
   std::vector<float> xyb_idct[3];          // after IDCT, wp*hp (cropped to frame size: w*h)
   std::vector<float> xyb_filtered[3];      // after Gaborish + EPF, w*h
   std::vector<int32_t> alpha;              // decoded alpha (w*h) if present
+  // Modular frames: the frame-level channel list as coded (before the inverse transforms), zero-size channels included
+  std::vector<std::vector<int32_t>> mod_coded;
+  std::vector<int32_t> mod_coded_w, mod_coded_h;
 };
 
 struct DecodeResult {
@@ -91,6 +94,15 @@ struct EncodeParams {
   // [0]: the whole tree of a lossless frame; [1]: what a lossy frame's alpha channel is coded with (in place of both alpha leaves of the
   // frame's tree); [2]: what each of the three LF channels is coded with (in place of their leaves, below the tree's channel splits)
   std::vector<int32_t> tree[3];
+  // Explicit transform list of a lossless frame (parity-test coverage; have_transforms false: the writer's own choice).  Applied forward in
+  // order and written to the GlobalModular header in that order.  Flat ints, one entry after the other:
+  //   0, begin_c, rct_type                                   an RCT
+  //   1, begin_c, num_c                                      a Palette (channel indices as MetaApplyTransforms counts them)
+  //   2, n, n x (horizontal, in_place, begin_c, num_c)       a Squeeze; n = 0: the default parameters, written as a count of 0
+  //   3, id, then the header fields of that transform id     REFUSAL TESTS ONLY, last entry only: written as given, nothing is done to
+  //      (0: begin_c, rct_type; 1: begin_c, num_c, nb_colors, nb_deltas, predictor; 2: n, n x 4)   the channels and nothing is checked
+  bool have_transforms = false;
+  std::vector<int32_t> transforms;
   float distance = 1.0f;
   bool lossless = false;
   int effort = 7;

@@ -625,6 +625,12 @@ void DecodeJxl(const uint8_t* data, size_t size, const DecodeOptions& opt, Decod
         d.ReadPassGroup(sr, g, pass);
       });
   }
+  if (dump && f.encoding == 1)
+    for (const Channel& ch : d.full.ch) {
+      dump->mod_coded.push_back(ch.d);
+      dump->mod_coded_w.push_back(ch.w);
+      dump->mod_coded_h.push_back(ch.h);
+    }
   UndoTransforms(d.full);
 
   // ------------------------------------------------------------- colour pipeline

@@ -791,6 +791,67 @@ struct VarDctEncoder {
 };
 
 // ------------------------------------------------------------------ lossless Modular
+// EncodeParams::transforms: applies the list forward to `img` and fills `header` with what goes into the stream (a default Squeeze as a
+// count of 0; a declared entry as given).  Every applied entry is checked the way MetaApplyTransforms will check it.
+void ApplyTransformList(ModularImage& img, const std::vector<int32_t>& list, std::vector<Transform>& header) {
+  size_t i = 0;
+  auto next = [&]() -> uint32_t {
+    JXO_CHECK(i < list.size(), "transform list: truncated entry");
+    JXO_CHECK(list[i] >= 0, "transform list: negative field");
+    return (uint32_t)list[i++];
+  };
+  auto squeeze_params = [&](std::vector<SqueezeParams>& out) {
+    const uint32_t n = next();
+    for (uint32_t k = 0; k < n; k++) {
+      SqueezeParams s;
+      s.horizontal = next() != 0; s.in_place = next() != 0; s.begin_c = next(); s.num_c = next();
+      out.push_back(s);
+    }
+  };
+  header.clear();
+  while (i < list.size()) {
+    const uint32_t kind = next();
+    if (kind == 0) {
+      const uint32_t begin_c = next(), type = next();
+      JXO_CHECK(type < 42 && (size_t)begin_c + 3 <= img.ch.size(), "transform list: RCT type or channel range");
+      for (int k = 1; k < 3; k++)
+        JXO_CHECK(img.ch[begin_c + k].w == img.ch[begin_c].w && img.ch[begin_c + k].h == img.ch[begin_c].h, "transform list: RCT channel sizes");
+      ForwardRCT(img, begin_c, type);
+      header.push_back(img.transforms.back());
+    } else if (kind == 1) {
+      const uint32_t begin_c = next(), num_c = next();
+      JXO_CHECK(num_c > 0 && (size_t)begin_c + num_c <= img.ch.size() && begin_c >= (uint32_t)img.nb_meta, "transform list: palette channel range");
+      for (uint32_t k = 1; k < num_c; k++)
+        JXO_CHECK(img.ch[begin_c + k].w == img.ch[begin_c].w && img.ch[begin_c + k].h == img.ch[begin_c].h, "transform list: palette channel sizes");
+      JXO_CHECK(ForwardPalette(img, begin_c, num_c, 5376 + 65535), "transform list: more colours than the palette's size field holds");
+      header.push_back(img.transforms.back());
+    } else if (kind == 2) {
+      std::vector<SqueezeParams> sp;
+      squeeze_params(sp);
+      const bool defaults = sp.empty();
+      if (defaults) DefaultSqueezeParams(img, sp);
+      size_t nch = img.ch.size();
+      for (auto& s : sp) {
+        JXO_CHECK(s.num_c > 0 && (size_t)s.begin_c + s.num_c <= nch && s.begin_c >= (uint32_t)img.nb_meta, "transform list: squeeze channel range");
+        nch += s.num_c;
+      }
+      ForwardSqueeze(img, sp);
+      header.push_back(img.transforms.back());
+      if (defaults) header.back().squeezes.clear();
+    } else {
+      JXO_CHECK(kind == 3, "transform list: unknown entry");
+      Transform t;
+      t.id = (int)next();
+      JXO_CHECK(t.id >= 0 && t.id < 3, "transform list: declared transform id");
+      if (t.id == 0) { t.begin_c = next(); t.rct_type = next(); }
+      else if (t.id == 1) { t.begin_c = next(); t.num_c = next(); t.nb_colors = next(); t.nb_deltas = next(); t.predictor = next(); }
+      else squeeze_params(t.squeezes);
+      JXO_CHECK(i == list.size(), "transform list: a declared entry must be the last one");
+      header.push_back(t);
+    }
+  }
+}
+
 std::vector<uint8_t> EncodeLosslessFrame(const ImageMetadata& m, FrameHeader& f, const uint8_t* px, int nch, const EncodeParams& p) {
   f.encoding = 1;
   f.group_size_shift = 1;
@@ -812,14 +873,18 @@ std::vector<uint8_t> EncodeLosslessFrame(const ImageMetadata& m, FrameHeader& f,
   GroupHeader gh_global;
   gh_global.use_global_tree = true;
   bool paletted = false;
-  if (p.palette && !m.exp_bits) paletted = ForwardPalette(full, 0, (uint32_t)nch, 1024);   // colour and alpha together, as one index channel
-  if (!paletted && ncolor == 3 && !m.exp_bits) ForwardRCT(full, 0, 6);   // float samples are coded as bit patterns: no colour transform on those
-  if (p.lossless_squeeze) {
-    std::vector<SqueezeParams> sp;
-    DefaultSqueezeParams(full, sp);
-    ForwardSqueeze(full, sp);
+  if (p.have_transforms) {
+    ApplyTransformList(full, p.transforms, gh_global.transforms);
+  } else {
+    if (p.palette && !m.exp_bits) paletted = ForwardPalette(full, 0, (uint32_t)nch, 1024);   // colour and alpha together, as one index channel
+    if (!paletted && ncolor == 3 && !m.exp_bits) ForwardRCT(full, 0, 6);   // float samples are coded as bit patterns: no colour transform on those
+    if (p.lossless_squeeze) {
+      std::vector<SqueezeParams> sp;
+      DefaultSqueezeParams(full, sp);
+      ForwardSqueeze(full, sp);
+    }
+    gh_global.transforms = full.transforms;
   }
-  gh_global.transforms = full.transforms;
   Tree tree;
   if (p.tree[0].empty()) {
     tree = MakeLosslessTree(p.lossless_predictor, p.lossless_tree);
@@ -945,6 +1010,11 @@ std::vector<uint8_t> EncodeJxl(const uint8_t* px, uint32_t w, uint32_t h, int nc
   JXO_CHECK(p.float_samples == 0 || p.float_samples == 16 || p.float_samples == 32, "float samples are binary16 or binary32");
   m.bits = p.float_samples ? (uint32_t)p.float_samples : (uint32_t)p.bits;
   m.exp_bits = p.float_samples == 32 ? 8 : (p.float_samples == 16 ? 5 : 0);
+  if (p.have_transforms) {
+    JXO_CHECK(p.lossless, "an explicit transform list is for lossless frames only");
+    JXO_CHECK(!p.palette && !p.lossless_squeeze, "an explicit transform list replaces the writer's own: not together with palette or lossless_squeeze");
+    JXO_CHECK(!p.float_samples, "an explicit transform list is not supported on float samples");
+  }
   JXO_CHECK(p.orientation >= 1 && p.orientation <= 8, "orientation must be 1..8");
   m.orientation = (uint32_t)p.orientation;
   if (p.cmyk) {   // "the RGB samples are to be interpreted as CMY" + a black extra channel (+ alpha)

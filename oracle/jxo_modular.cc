@@ -773,8 +773,9 @@ void ModularDecode(BitReader& br, ModularImage& img, GroupHeader* header_out, ui
   size_t nb = img.ch.size(), num_chans = 0, dist_mult = 0, pixels = 0;
   for (size_t i = 0; i < nb; i++) {
     Channel& c = img.ch[i];
-    if (!c.w || !c.h) continue;
+    // the stream stops at the first channel with a side above the limit, an empty one (0 x h: the residuals of a 1-wide channel) included
     if ((int)i >= img.nb_meta && (c.w > max_chan_size || c.h > max_chan_size)) break;
+    if (!c.w || !c.h) continue;
     dist_mult = std::max<size_t>(dist_mult, c.w);
     pixels += (size_t)c.w * c.h;
     num_chans++;
@@ -797,8 +798,8 @@ void ModularDecode(BitReader& br, ModularImage& img, GroupHeader* header_out, ui
   rd.Init(*code, br, (uint32_t)dist_mult);
   for (size_t i = 0; i < nb; i++) {
     Channel& c = img.ch[i];
-    if (!c.w || !c.h) continue;
     if ((int)i >= img.nb_meta && (c.w > max_chan_size || c.h > max_chan_size)) break;
+    if (!c.w || !c.h) continue;
     DecodeChannel(rd, *tree, h.wp, img, (int)i, stream_id);
     JXO_CHECK(!br.overrun, "truncated modular stream");
   }

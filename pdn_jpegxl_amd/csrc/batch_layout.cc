@@ -261,7 +261,14 @@ void BuildBatch(const BatchInput& in, BatchRegions& R, BatchOutput& out) {
       d.mod_ncoded = (int32_t)f.mod_coded.size();
       d.mod_first_group = (int32_t)f.mod_first_group_channel;
       d.mod_desc = ws.Array<ChanDesc>(nsec * f.mod_coded.size());
-      if (f.tree_uses_wp) { d.wp_grp_ints = 10 * ((int64_t)f.group_dim + 2); d.wp_grp = ws.Array<int32_t>(nsec * (size_t)d.wp_grp_ints); }
+      if (f.tree_uses_wp) {
+        // weighted-predictor state per section: as wide as the widest channel a section decodes.  A group's rectangle is at most
+        // group_dim wide; a palette's meta channel (GlobalModular stream) is as wide as its colour count, which may be more
+        int64_t widest = (int64_t)f.group_dim;
+        for (auto& ch : f.mod_coded) if (ch.hshift < 0) widest = std::max<int64_t>(widest, ch.w);
+        d.wp_grp_ints = 10 * (widest + 2);
+        d.wp_grp = ws.Array<int32_t>(nsec * (size_t)d.wp_grp_ints);
+      }
       if (f.mcode.lz77) d.lz_mod = ws.Array<uint32_t>(nsec << 20);
       if (!inline_rct)
         for (auto& op : f.mod_ops) {

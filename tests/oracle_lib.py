@@ -139,10 +139,32 @@ class OracleError(RuntimeError):
     pass
 
 
+def flatten_transforms(transforms):
+    """encode(transforms=...) as the flat ints of oracle/jxo_codec.h: EncodeParams::transforms."""
+    def squeezes(lst):
+        out = [len(lst)]
+        for hor, in_place, begin_c, num_c in lst:
+            out += [int(hor), int(in_place), begin_c, num_c]
+        return out
+    flat = []
+    for t in transforms:
+        if t[0] == "rct":
+            flat += [0, t[1], t[2]]
+        elif t[0] == "palette":
+            flat += [1, t[1], t[2]]
+        elif t[0] == "squeeze":
+            flat += [2] + squeezes(t[1])
+        elif t[0] == "declare":
+            flat += [3, t[1]] + (squeezes(t[2]) if t[1] == 2 else list(t[2:]))
+        else:
+            raise OracleError("transforms: unknown entry %r" % (t,))
+    return flat
+
+
 def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, seed=1, epf_iters=-1, gaborish=True,
            container=True, adaptive_lf_smoothing=True, lossless_predictor=6, lossless_squeeze=False, num_threads=8, exif=None,
            xmp=None, lossless_tree=0, bits=8, orientation=1, float_samples=0, colour=0, icc=None, cmyk=False, animation_frames=1, custom_quant_tables=False, prefix_codes=False, lz77=False, num_passes=1, custom_orders=False, lf_contexts=False, palette=False, mislabel_afv=False,
-           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None):
+           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None, transforms=None):
     """px: uint8 array (h, w, nch) with nch in 1..4 (Gray, GrayA, RGB, RGBA); with bits > 8 (up to 16) a uint16 array whose
     samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes.
     side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters).
@@ -150,7 +172,14 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
     a list of nodes (property or -1, split value, child for property > split value, other child, predictor, offset, multiplier), node 0
     the root, children after their parent (oracle/jxo_codec.h: EncodeParams::tree).
     wide_codes: the frame's plain ANS codes are written with log_alpha 8 and up to 255 clusters (used contexts are not merged while they
-    fit); tokens, contexts and quantised data are those of the same call without it."""
+    fit); tokens, contexts and quantised data are those of the same call without it.
+    transforms: lossless frames only, integer samples: the frame's transform list in place of the writer's own choice (an OracleError
+    together with palette or lossless_squeeze).  Applied forward in order, written to the header in that order; [] is no transform.
+    Entries: ("rct", begin_c, rct_type); ("palette", begin_c, num_c), channel indices those of the channel list at that point, the meta
+    channels of earlier palettes in front; ("squeeze", [(horizontal, in_place, begin_c, num_c), ...]), an empty list being the default
+    parameters (written as a count of 0); and, as the last entry only, ("declare", id, fields...): the header fields of transform `id`
+    (0: begin_c, rct_type; 1: begin_c, num_c, nb_colors, nb_deltas, predictor; 2: a list of squeeze tuples) written as given, with nothing
+    done to the channels and nothing checked (refusal tests)."""
     L = lib()
     if float_samples:
         px = np.ascontiguousarray(px, dtype=np.float16 if float_samples == 16 else np.float32)
@@ -175,6 +204,10 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
             flat = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 7)
             L.jxo_set_next_tree.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
             L.jxo_set_next_tree(flat.ctypes.data, len(flat), role)
+    if transforms is not None:
+        flat = np.ascontiguousarray(flatten_transforms(transforms), dtype=np.int32)
+        L.jxo_set_next_transforms.argtypes = [C.c_void_p, C.c_size_t]
+        L.jxo_set_next_transforms(flat.ctypes.data, len(flat))
     if animation_frames > 1:
         L.jxo_set_next_animation.argtypes = [C.c_int]
         L.jxo_set_next_animation(animation_frames)
@@ -236,6 +269,19 @@ def decode(data, num_threads=8, want_dump=False):
                         buf = (C.c_uint8 * (cnt * es.value)).from_address(ptr.value)
                         out.append(np.frombuffer(buf, dtype=dt).copy())
                 planes[name] = out if chans == 3 else out[0]
+        if want_dump:
+            L.jxo_image_mod_coded_count.argtypes = [C.c_void_p]
+            L.jxo_image_mod_coded.restype = C.POINTER(C.c_int32)
+            L.jxo_image_mod_coded.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            coded = []
+            for i in range(L.jxo_image_mod_coded_count(hnd)):
+                cw, ch = C.c_int32(), C.c_int32()
+                ptr = L.jxo_image_mod_coded(hnd, i, C.byref(cw), C.byref(ch))
+                if cw.value * ch.value:
+                    coded.append(np.ctypeslib.as_array(ptr, shape=(ch.value, cw.value)).copy())
+                else:
+                    coded.append(np.zeros((ch.value, cw.value), np.int32))
+            planes["mod_coded"] = coded   # Modular frames: the coded channel list before the inverse transforms, each (h, w)
         p = C.POINTER(C.c_uint8)()
         n = L.jxo_image_exif(hnd, C.byref(p))
         exif = bytes(C.string_at(p, n)) if n else b""

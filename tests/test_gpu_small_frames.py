@@ -183,9 +183,7 @@ LOSSLESS_MODES = {"gradient-tree": dict(lossless_tree=1, lossless_predictor=5), 
 
 @pytest.mark.parametrize("mode", list(LOSSLESS_MODES))
 def test_lossless_tiny_frames(gpu_decoder, oracle, mode):
-    # (the oracle cannot read back its own squeezed frames 1 column wide and more than 256 rows high: 1 x 2049 works, 1 x 257 ..
-    # 1 x 513 do not; without a checker that size is left out of the squeeze set)
-    sizes = [s for s in LOSSLESS_SIZES if not (mode == "squeeze" and s == (1, 300))]
+    sizes = LOSSLESS_SIZES
     srcs = [image(w, h, 60 + w + 5 * h) for w, h in sizes]
     if mode == "palette":
         srcs = [np.ascontiguousarray(s // 64 * 64) for s in srcs]   # few colours
