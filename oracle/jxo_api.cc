@@ -120,6 +120,51 @@ void jxo_set_next_transforms(const int32_t* data, size_t n) {
   g_next_transforms.assign(data, data + n);
   g_next_have_transforms = true;
 }
+// Code forms of the next jxo_encode call (jxo_entropy.h: EntropyForms), as flat ints in the order read below; the census of that call
+// stays readable (as JSON) until the next call that sets forms.
+static thread_local EntropyForms g_next_forms;
+static thread_local bool g_next_have_forms = false;
+int jxo_set_next_entropy(const int32_t* d, size_t n) {
+  try {
+    size_t p = 0;
+    auto next = [&]() -> int32_t { JXO_CHECK(p < n, "entropy forms: short list"); return d[p++]; };
+    auto cfg = [&]() { const uint32_t s = next(), m = next(), l = next(); return HybridUintConfig(s, m, l); };
+    EntropyForms f;
+    for (int32_t k = next(); k > 0; k--) f.cfgs.push_back(cfg());
+    f.have_lz = next() != 0;
+    f.lz.min_symbol = next(); f.lz.min_length = next(); f.lz.max_len = next();
+    f.lz.len_cfg = cfg();
+    f.lz.custom_distances = next() != 0;
+    for (int32_t k = next(); k > 0; k--) {
+      const int32_t i = next();
+      JXO_CHECK(i >= 0 && i < 120, "entropy forms: special distance index");
+      f.lz.special[i] = true;
+    }
+    f.lz.general = next() != 0; f.lz.general_max = next();
+    f.lz.overshoot = next() != 0; f.lz.zero_start = next() != 0;
+    f.hist = next(); f.hist_shift = next();
+    JXO_CHECK(f.hist >= 0 && f.hist <= 3 && f.hist_shift >= 0 && f.hist_shift <= 13, "entropy forms: histogram form");
+    f.ctx_map_mtf = next() != 0;
+    f.bad_cfg = next() != 0; f.bad = cfg(); f.bad_hist = next();
+    JXO_CHECK(f.lz.max_len >= f.lz.min_length && f.lz.min_length >= 1, "entropy forms: copy lengths");
+    g_next_forms = f;
+    g_next_have_forms = true;
+    return 1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return 0;
+  }
+}
+void jxo_special_distance(int index, int32_t* dx, int32_t* dy) {
+  int x = 0, y = 0;
+  if (index >= 0 && index < 120) SpecialDistance(index, &x, &y);
+  *dx = x; *dy = y;
+}
+size_t jxo_entropy_census(char* dst, size_t capacity) {
+  const std::string s = EntropyCensusJson();
+  for (size_t i = 0; i < s.size() && i < capacity; i++) dst[i] = s[i];
+  return s.size();
+}
 void jxo_set_next_animation(int frames) { g_next_frames = frames; }
 void jxo_set_next_icc(const uint8_t* icc, size_t size, int cmyk) {
   g_next_icc.assign(icc ? icc : nullptr, icc ? icc + size : nullptr);
@@ -176,10 +221,14 @@ JxoBytes* jxo_encode(const uint8_t* px, uint32_t w, uint32_t h, int32_t nch, con
     g_next_flags = 0;
     JxoBytes* b = new JxoBytes();
     SetEntropyTestMode(((g_next_flags_entropy >> 1) & 3) | ((g_next_flags_entropy & 1024) ? 4 : 0));
+    const bool have_forms = g_next_have_forms;
+    g_next_have_forms = false;
+    if (have_forms) SetEntropyForms(&g_next_forms);
     try {
       b->b = EncodeJxl(px, w, h, nch, p, exif, exif_size, xmp, xmp_size);
-    } catch (...) { SetEntropyTestMode(0); delete b; throw; }
+    } catch (...) { SetEntropyTestMode(0); if (have_forms) SetEntropyForms(nullptr); delete b; throw; }
     SetEntropyTestMode(0);
+    if (have_forms) SetEntropyForms(nullptr);
     return b;
   } catch (const std::exception& e) {
     g_err = e.what();

@@ -383,6 +383,8 @@ static const int8_t kSpecialDistances[120][2] = {
     {7, 3},  {-7, 3}, {5, 6},  {-5, 6}, {6, 5},  {-6, 5}, {8, 0},  {4, 7},  {-4, 7}, {7, 4},  {-7, 4}, {8, 1},  {8, 2},  {6, 6},  {-6, 6},
     {8, 3},  {5, 7},  {-5, 7}, {7, 5},  {-7, 5}, {8, 4},  {6, 7},  {-6, 7}, {7, 6},  {-7, 6}, {8, 5},  {7, 7},  {-7, 7}, {8, 6},  {8, 7}};
 
+void SpecialDistance(int index, int* dx, int* dy) { *dx = kSpecialDistances[index][0]; *dy = kSpecialDistances[index][1]; }
+
 void EntropyReader::Init(const EntropyCode& c, BitReader& b, uint32_t dist_mult) {
   code = &c;
   br = &b;
@@ -499,23 +501,41 @@ static std::vector<int32_t> NormalizeCounts(const std::vector<uint32_t>& h) {
   return out;
 }
 
-static void WriteHistogram(BitWriter& bw, const std::vector<int32_t>& counts) {
+// form: 0 full precision; 1 flat (the counts are replaced by the flat ones over the same alphabet); 2 precision `shift` (every count but
+// the omitted one is rounded down to what the field carries, the omitted one takes the rest); 3 runs of >= 5 equal counts through the
+// run-length symbol.  bad: 1 writes the shift field as 14, 2 puts a run-length symbol right after the omitted position (refusal tests).
+struct HistStats { int form = 0; bool simple = false, rle_used = false, rle_to_end = false; };
+static HistStats WriteHistogram(BitWriter& bw, std::vector<int32_t>& counts, int form = 0, int shift = kAnsLogTabSize + 1, int bad = 0) {
+  HistStats st;
   std::vector<int> syms;
   for (size_t i = 0; i < counts.size(); i++)
     if (counts[i]) syms.push_back((int)i);
   if (syms.size() <= 2) {
+    st.simple = true;
     bw.Write(1, 1);
-    if (syms.empty()) { bw.Write(1, 0); WriteVarLenUint8(bw, 0); return; }
+    if (syms.empty()) { bw.Write(1, 0); WriteVarLenUint8(bw, 0); return st; }
     bw.Write(1, syms.size() - 1);
     for (int s : syms) WriteVarLenUint8(bw, s);
     if (syms.size() == 2) bw.Write(kAnsLogTabSize, counts[syms[0]]);
-    return;
+    return st;
   }
   bw.Write(1, 0);  // not simple
+  st.form = form;
+  if (form == 1) {
+    bw.Write(1, 1);
+    const int a = (int)counts.size();
+    WriteVarLenUint8(bw, a - 1);
+    for (int i = 0; i < a; i++) counts[i] = (int32_t)(kAnsTabSize / a) + (i < (int)(kAnsTabSize % a) ? 1 : 0);
+    return st;
+  }
   bw.Write(1, 0);  // not flat
-  const int shift = kAnsLogTabSize + 1;  // full precision
-  bw.Write(3, 7);                        // unary "111" => log = 3
-  bw.Write(3, (shift + 1) - 8);
+  if (form != 2) shift = kAnsLogTabSize + 1;  // full precision
+  {
+    const int field = bad == 1 ? 15 : shift + 1, lg = FloorLog2(field);   // shift + 1 in [1 << lg, 2 << lg), lg in unary (at most 3 ones)
+    for (int i = 0; i < lg; i++) bw.Write(1, 1);
+    if (lg < 3) bw.Write(1, 0);
+    bw.Write(lg, field - (1 << lg));
+  }
   int length = (int)counts.size();
   WriteVarLenUint8(bw, length - 3);
   // encode table for log-count symbols
@@ -537,13 +557,45 @@ static void WriteHistogram(BitWriter& bw, const std::vector<int32_t>& counts) {
     lc[i] = counts[i] ? FloorLog2(counts[i]) + 1 : 0;
     if (lc[i] > omit_log) { omit_log = lc[i]; omit_pos = i; }
   }
-  for (int i = 0; i < length; i++) bw.Write(enc_len[lc[i]], enc_bits[lc[i]]);
+  if (form == 2) {   // rounding down keeps every log-count; the omitted count only grows, so it stays the first of the largest
+    int total = 0;
+    for (int i = 0; i < length; i++) {
+      if (i == omit_pos || lc[i] <= 1) { if (i != omit_pos) total += counts[i]; continue; }
+      const int drop = lc[i] - 1 - PopulationCountPrecision(lc[i] - 1, shift);
+      counts[i] &= ~((1 << drop) - 1);
+      total += counts[i];
+    }
+    counts[omit_pos] = (int32_t)kAnsTabSize - total;
+  }
+  // run[i] > 0: a run-length symbol at i that stands for run[i] counts equal to counts[i - 1] (neither i - 1 nor any of them omitted)
+  std::vector<int> run(length, 0);
+  if (form == 3) {
+    for (int i = 1; i < length;) {
+      int r = 0;
+      if (i - 1 != omit_pos)
+        while (i + r < length && i + r != omit_pos && counts[i + r] == counts[i - 1] && r < 255 + 4) r++;
+      if (r >= 4) { run[i] = r; st.rle_used = true; st.rle_to_end |= i + r == length; i += r + 1; }
+      else i++;
+    }
+  }
+  if (bad == 2 && omit_pos + 5 <= length) run[omit_pos + 1] = 4;
   for (int i = 0; i < length; i++) {
+    if (run[i]) {
+      bw.Write(enc_len[13], enc_bits[13]);
+      WriteVarLenUint8(bw, run[i] - 4);
+      i += run[i] - 1;
+    } else {
+      bw.Write(enc_len[lc[i]], enc_bits[lc[i]]);
+    }
+  }
+  for (int i = 0; i < length; i++) {
+    if (run[i]) { i += run[i] - 1; continue; }
     if (i == omit_pos || lc[i] <= 1) continue;
     int bitcount = PopulationCountPrecision(lc[i] - 1, shift);
-    JXO_CHECK(bitcount == lc[i] - 1, "precision");
-    bw.Write(bitcount, counts[i] - (1 << (lc[i] - 1)));
+    JXO_CHECK(form == 2 || bitcount == lc[i] - 1, "precision");
+    bw.Write(bitcount, (counts[i] - (1 << (lc[i] - 1))) >> (lc[i] - 1 - bitcount));
   }
+  return st;
 }
 
 static double HistEntropyBits(const std::vector<uint32_t>& h, uint64_t total) {
@@ -595,6 +647,81 @@ static uint32_t StreamDistMult(const void* tokens) {
   return it == g_dist_mult.end() ? 0u : it->second;
 }
 
+// ---- code forms on request (EntropyForms) and the census of what was written with them
+static EntropyForms g_forms;
+static bool g_have_forms = false;
+struct Census {   // of one top-level code
+  std::vector<HybridUintConfig> cfgs;
+  uint32_t log_alpha = 0, contexts = 0;
+  bool prefix = false, lz77 = false;
+  uint64_t special[120] = {0};
+  uint64_t general_small[9] = {0};   // plain distances 1 .. 8 ([0]: longer ones)
+  uint64_t general = 0, general_min = 0, general_max = 0, overlapping = 0, clamped = 0, zero_start = 0, longest_copy = 0;
+  uint32_t max_tail_bits = 0, max_dist_tail_bits = 0;
+  uint64_t hist_simple = 0, hist_flat = 0, hist_rle = 0, hist_full = 0, hist_flat_not_pow2 = 0, rle_to_end = 0;
+  std::map<int, uint64_t> hist_shift;
+  uint64_t mtf_maps = 0, mtf_largest = 0;
+  // the first ANS token stream of the code that holds a copy whose length and distance both read extra bits: where those bits start
+  // and where the stream ends, in bits of the section written so far (corruption tests)
+  int64_t first_len_tail_bit = -1, first_dist_tail_bit = -1, first_end_bit = -1;
+  void Add(const Census& o) {   // the counts of one token stream
+    for (int i = 0; i < 120; i++) special[i] += o.special[i];
+    for (int i = 0; i < 9; i++) general_small[i] += o.general_small[i];
+    if (o.general) {
+      general_min = general ? std::min(general_min, o.general_min) : o.general_min;
+      general_max = std::max(general_max, o.general_max);
+      general += o.general;
+    }
+    overlapping += o.overlapping; clamped += o.clamped; zero_start += o.zero_start;
+    longest_copy = std::max(longest_copy, o.longest_copy);
+    max_tail_bits = std::max(max_tail_bits, o.max_tail_bits);
+    max_dist_tail_bits = std::max(max_dist_tail_bits, o.max_dist_tail_bits);
+  }
+};
+static std::vector<Census> g_census;
+static std::mutex g_census_mutex;
+void SetEntropyForms(const EntropyForms* f) {
+  std::lock_guard<std::mutex> lock(g_census_mutex);
+  g_have_forms = f != nullptr;
+  g_forms = f ? *f : EntropyForms();
+  if (f) g_census.clear();
+}
+std::string EntropyCensusJson() {
+  std::lock_guard<std::mutex> lock(g_census_mutex);
+  std::string s = "{\"codes\": [";
+  for (size_t i = 0; i < g_census.size(); i++) {
+    const Census& c = g_census[i];
+    s += std::string(i ? ", " : "") + "{\"prefix\": " + (c.prefix ? "true" : "false") + ", \"lz77\": " + (c.lz77 ? "true" : "false") + ", \"cfgs\": [";
+    for (size_t k = 0; k < c.cfgs.size(); k++)
+      s += std::string(k ? ", " : "") + "[" + std::to_string(c.cfgs[k].split_exponent) + ", " + std::to_string(c.cfgs[k].msb_in_token) + ", " +
+           std::to_string(c.cfgs[k].lsb_in_token) + "]";
+    s += "], \"special\": [";
+    for (int k = 0; k < 120; k++) s += std::string(k ? ", " : "") + std::to_string(c.special[k]);
+    s += "], \"general_small\": [";
+    for (int k = 0; k < 9; k++) s += std::string(k ? ", " : "") + std::to_string(c.general_small[k]);
+    s += "]";
+    auto num = [&](const char* name, uint64_t v) { s += std::string(", \"") + name + "\": " + std::to_string(v); };
+    num("log_alpha", c.log_alpha); num("contexts", c.contexts);
+    num("general", c.general); num("general_min", c.general_min); num("general_max", c.general_max); num("overlapping", c.overlapping);
+    num("clamped", c.clamped); num("zero_start", c.zero_start); num("longest_copy", c.longest_copy); num("max_tail_bits", c.max_tail_bits);
+    num("max_dist_tail_bits", c.max_dist_tail_bits); num("hist_simple", c.hist_simple); num("hist_flat", c.hist_flat);
+    num("hist_flat_not_pow2", c.hist_flat_not_pow2); num("hist_rle", c.hist_rle); num("rle_to_end", c.rle_to_end);
+    num("hist_full", c.hist_full); num("mtf_maps", c.mtf_maps); num("mtf_largest", c.mtf_largest);
+    s += ", \"first_len_tail_bit\": " + std::to_string(c.first_len_tail_bit) + ", \"first_dist_tail_bit\": " + std::to_string(c.first_dist_tail_bit) +
+         ", \"first_end_bit\": " + std::to_string(c.first_end_bit);
+    s += ", \"hist_shift\": {";
+    bool first = true;
+    for (auto& kv : c.hist_shift) { s += std::string(first ? "" : ", ") + "\"" + std::to_string(kv.first) + "\": " + std::to_string(kv.second); first = false; }
+    s += "}}";
+  }
+  return s + "]}";
+}
+
+static bool ValidUintConfig(const HybridUintConfig& c, uint32_t log_alpha) {
+  if (c.split_exponent > log_alpha || c.msb_in_token > c.split_exponent || c.msb_in_token + c.lsb_in_token > c.split_exponent) return false;
+  return c.split_exponent != log_alpha || (c.msb_in_token == 0 && c.lsb_in_token == 0);   // not coded there: read as zeros
+}
+
 namespace {
 const uint32_t kLzMinSymbol = 224, kLzMinLength = 3, kLzMaxLength = 200;
 struct Sym { uint32_t ctx, tok, nb, bits; };
@@ -602,34 +729,92 @@ struct Sym { uint32_t ctx, tok, nb, bits; };
 // Token stream -> emitted symbols.  With LZ77: a run of values equal to the value before it, or a stretch equal to the stretch
 // `dist_mult` symbols back, of at least kLzMinLength symbols becomes (length symbol in the position's context, distance symbol in
 // the extra context).  The window holds decoded VALUES, so matches are on Token::value; contexts of copied positions are never coded.
-void Symbolize(const std::vector<Token>& t, const HybridUintConfig& cfg, bool lz77, uint32_t dist_ctx, uint32_t dist_mult, std::vector<Sym>& out) {
+// `cfg` holds one configuration per cluster and `ctx_map` the cluster of each context (null: cfg[0] everywhere).  With
+// LzForm::custom_distances the finder takes the longest match among the allowed special indices (in index order) and the plain
+// distances (after them); a later candidate must be strictly longer.  `census` (WriteTokens only) counts what was emitted.
+void Symbolize(const std::vector<Token>& t, const std::vector<HybridUintConfig>& cfg, const std::vector<uint8_t>* ctx_map, const LzForm& lz, bool lz77,
+               uint32_t dist_ctx, uint32_t dist_mult, std::vector<Sym>& out, Census* census) {
   out.clear();
   const size_t n = t.size();
+  auto cfg_of = [&](uint32_t ctx) -> const HybridUintConfig& { return ctx_map ? cfg[(*ctx_map)[ctx]] : cfg[0]; };
+  // candidate (distance in values, coded distance value), in the finder's order
+  std::vector<std::pair<uint32_t, uint32_t>> cand;
+  if (lz77 && lz.custom_distances) {
+    if (dist_mult) {
+      for (int k = 0; k < 120; k++)
+        if (lz.special[k]) {
+          const int off = kSpecialDistances[k][0] + (int)dist_mult * kSpecialDistances[k][1];
+          cand.emplace_back(off < 1 ? 1u : (uint32_t)off, (uint32_t)k);
+        }
+      if (lz.general) for (uint32_t d = 1; d <= lz.general_max; d++) cand.emplace_back(d, d + 119);
+    } else {
+      cand.emplace_back(1u, 0u);   // no two-dimensional distances on these streams: one back, then the plain ones
+      if (lz.general) for (uint32_t d = 2; d <= lz.general_max; d++) cand.emplace_back(d, d - 1);
+    }
+  }
   for (size_t i = 0; i < n;) {
-    size_t len = 0;
+    size_t len = 0, dist = 0;
     uint32_t dist_value = 0;
-    if (lz77 && i >= 1) {
+    bool zero_start = false, clamped = false;
+    if (lz77 && i == 0 && lz.zero_start) {
+      size_t l0 = 0;
+      while (l0 < n && l0 < lz.max_len && t[l0].value == 0) l0++;
+      if (l0 >= lz.min_length) { len = l0; dist_value = dist_mult ? 1 : 0; zero_start = true; }
+    } else if (lz77 && i >= 1 && lz.custom_distances) {
+      for (auto& cd : cand) {
+        if (cd.first > i) continue;
+        size_t l = 0;
+        while (i + l < n && l < lz.max_len && t[i + l].value == t[i + l - cd.first].value) l++;
+        if (l > len) { len = l; dist = cd.first; dist_value = cd.second; }
+      }
+      if (len < lz.min_length) len = 0;
+      if (len && lz.overshoot && dist == i) {   // the source is the stream's first value: any distance from here on means the same
+        const uint32_t d = (uint32_t)i + 5;
+        dist_value = dist_mult ? d + 119 : d - 1;
+        clamped = true;
+      }
+    } else if (lz77 && i >= 1) {
       size_t l1 = 0;
-      while (i + l1 < n && l1 < kLzMaxLength && t[i + l1].value == t[i - 1].value) l1++;
+      while (i + l1 < n && l1 < lz.max_len && t[i + l1].value == t[i - 1].value) l1++;
       size_t l2 = 0;
       if (dist_mult > 1 && i >= dist_mult)
-        while (i + l2 < n && l2 < kLzMaxLength && t[i + l2].value == t[i + l2 - dist_mult].value) l2++;
-      if (l2 > l1 && l2 >= kLzMinLength) { len = l2; dist_value = 0; }                        // special distance 0: (dx 0, dy 1) = dist_mult back
-      else if (l1 >= kLzMinLength) { len = l1; dist_value = dist_mult ? 1 : 0; }             // one back: special distance 1 (dx 1, dy 0), or 0 + 1
+        while (i + l2 < n && l2 < lz.max_len && t[i + l2].value == t[i + l2 - dist_mult].value) l2++;
+      if (l2 > l1 && l2 >= lz.min_length) { len = l2; dist_value = 0; dist = dist_mult; }                 // special distance 0: (dx 0, dy 1) = dist_mult back
+      else if (l1 >= lz.min_length) { len = l1; dist_value = dist_mult ? 1 : 0; dist = 1; }              // one back: special distance 1 (dx 1, dy 0), or 0 + 1
     }
     Sym s;
     if (len) {
-      HybridUintConfig(4, 2, 0).Encode((uint32_t)(len - kLzMinLength), &s.tok, &s.nb, &s.bits);
-      s.tok += kLzMinSymbol;
+      lz.len_cfg.Encode((uint32_t)(len - lz.min_length), &s.tok, &s.nb, &s.bits);
+      if (census) census->max_tail_bits = std::max(census->max_tail_bits, s.nb);
+      s.tok += lz.min_symbol;
       s.ctx = t[i].ctx;
       out.push_back(s);
-      cfg.Encode(dist_value, &s.tok, &s.nb, &s.bits);
+      cfg_of(dist_ctx).Encode(dist_value, &s.tok, &s.nb, &s.bits);
       s.ctx = dist_ctx;
       out.push_back(s);
+      if (census) {
+        census->max_tail_bits = std::max(census->max_tail_bits, s.nb);
+        census->max_dist_tail_bits = std::max(census->max_dist_tail_bits, s.nb);
+        census->longest_copy = std::max<uint64_t>(census->longest_copy, len);
+        if (zero_start) census->zero_start++;
+        else {
+          if (clamped) census->clamped++;
+          if (dist < len) census->overlapping++;
+          if (dist_mult && dist_value < 120) census->special[dist_value]++;
+          else {
+            const uint64_t d = dist_mult ? dist_value - 119 : dist_value + 1;
+            census->general_min = census->general ? std::min(census->general_min, d) : d;
+            census->general_max = std::max(census->general_max, d);
+            census->general_small[d <= 8 ? d : 0]++;
+            census->general++;
+          }
+        }
+      }
       i += len;
     } else {
-      cfg.Encode(t[i].value, &s.tok, &s.nb, &s.bits);
-      JXO_CHECK(!lz77 || s.tok < kLzMinSymbol, "literal token collides with the LZ77 symbols");
+      cfg_of(t[i].ctx).Encode(t[i].value, &s.tok, &s.nb, &s.bits);
+      JXO_CHECK(!lz77 || s.tok < lz.min_symbol, "literal token collides with the LZ77 symbols");
+      if (census) census->max_tail_bits = std::max(census->max_tail_bits, s.nb);
       s.ctx = t[i].ctx;
       out.push_back(s);
       i++;
@@ -741,10 +926,18 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
     h.total++;
     max_token = std::max(max_token, tok);
   };
+  EntropyForms forms;
+  if (opt.top_level) {
+    std::lock_guard<std::mutex> lock(g_census_mutex);
+    if (g_have_forms) forms = g_forms;
+  }
+  if (forms.have_lz) out.lz = forms.lz;
+  const LzForm& lzf = out.lz;
   std::vector<Sym> syms;
+  const std::vector<HybridUintConfig> one_cfg(1, opt.cfg);
   for (auto* ts : token_sets) {
     for (const Token& t : *ts) JXO_CHECK(t.ctx < data_contexts, "token context out of range");
-    Symbolize(*ts, opt.cfg, lz77, (uint32_t)data_contexts, StreamDistMult(ts), syms);
+    Symbolize(*ts, one_cfg, nullptr, lzf, lz77, (uint32_t)data_contexts, StreamDistMult(ts), syms, nullptr);
     for (const Sym& sy : syms) count(sy.ctx, sy.tok);
   }
   if (lz77) { count((uint32_t)data_contexts, 0); count((uint32_t)data_contexts, 1); }
@@ -802,17 +995,44 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
   }
   code.num_hist = (uint32_t)clusters.size();
   code.lz77 = lz77;
-  code.lz_min_symbol = kLzMinSymbol; code.lz_min_length = kLzMinLength; code.lz_len_cfg = HybridUintConfig(4, 2, 0);
+  code.lz_min_symbol = lzf.min_symbol; code.lz_min_length = lzf.min_length; code.lz_len_cfg = lzf.len_cfg;
+  JXO_CHECK(!lz77 || ValidUintConfig(lzf.len_cfg, 8), "length configuration is invalid");
   code.use_prefix = use_prefix;
+  code.cfg.assign(code.num_hist, opt.cfg);
+  if (!forms.cfgs.empty()) {
+    // the clusters stand as found on default tokens; every cluster takes its own configuration and its tokens are formed again
+    for (uint32_t k = 0; k < code.num_hist; k++) code.cfg[k] = forms.cfgs[k % forms.cfgs.size()];
+    for (auto& h : hist) h = RawHist();
+    max_token = 0;
+    for (auto* ts : token_sets) {
+      Symbolize(*ts, code.cfg, &code.ctx_map, lzf, lz77, (uint32_t)data_contexts, StreamDistMult(ts), syms, nullptr);
+      for (const Sym& sy : syms) count(sy.ctx, sy.tok);
+    }
+    if (lz77) { count((uint32_t)data_contexts, 0); count((uint32_t)data_contexts, 1); }
+    JXO_CHECK(use_prefix || max_token < 256, "token alphabet exceeds ANS limit");
+    for (auto& c : clusters) c = RawHist();
+    for (size_t i = 0; i < num_contexts; i++) {
+      RawHist& s = clusters[code.ctx_map[i]];
+      if (s.c.size() < hist[i].c.size()) s.c.resize(hist[i].c.size(), 0);
+      for (size_t j = 0; j < hist[i].c.size(); j++) s.c[j] += hist[i].c[j];
+      s.total += hist[i].total;
+    }
+  }
   code.log_alpha = use_prefix ? 15 : wide ? 8 : std::max(5, CeilLog2(max_token + 1));
   JXO_CHECK(use_prefix || code.log_alpha <= 8, "log_alpha");
-  code.cfg.assign(code.num_hist, opt.cfg);
-  JXO_CHECK(opt.cfg.split_exponent <= code.log_alpha, "uint config vs alphabet");
+  for (auto& c : code.cfg) JXO_CHECK(ValidUintConfig(c, code.log_alpha), "uint config vs alphabet");
+  if (opt.top_level && g_have_forms) {
+    std::lock_guard<std::mutex> lock(g_census_mutex);
+    Census cc;
+    cc.cfgs = code.cfg; cc.log_alpha = code.log_alpha; cc.prefix = use_prefix; cc.lz77 = lz77; cc.contexts = (uint32_t)data_contexts;
+    out.census_index = (int)g_census.size();
+    g_census.push_back(cc);
+  }
   // 3. header
   bw.Write(1, lz77 ? 1 : 0);
   if (lz77) {
-    bw.U32(Val(224), Val(512), Val(4096), BitsOff(15, 8), kLzMinSymbol);
-    bw.U32(Val(3), Val(4), BitsOff(2, 5), BitsOff(8, 9), kLzMinLength);
+    bw.U32(Val(224), Val(512), Val(4096), BitsOff(15, 8), code.lz_min_symbol);
+    bw.U32(Val(3), Val(4), BitsOff(2, 5), BitsOff(8, 9), code.lz_min_length);
     WriteUintConfig(bw, code.lz_len_cfg, 8);
   }
   if (num_contexts > 1) {
@@ -826,9 +1046,26 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
       for (auto m : code.ctx_map) bw.Write(bits, m);
     } else {
       bw.Write(1, 0);  // not simple
-      bw.Write(1, 0);  // no MTF
+      bw.Write(1, forms.ctx_map_mtf ? 1 : 0);
       std::vector<Token> mt;
-      for (auto m : code.ctx_map) mt.emplace_back(0, m);
+      if (forms.ctx_map_mtf) {   // each entry as its position in the list of values, most recently used first
+        uint8_t list[256];
+        for (int i = 0; i < 256; i++) list[i] = (uint8_t)i;
+        for (auto m : code.ctx_map) {
+          int idx = 0;
+          while (list[idx] != m) idx++;
+          mt.emplace_back(0, idx);
+          for (; idx; idx--) list[idx] = list[idx - 1];
+          list[0] = m;
+        }
+        std::lock_guard<std::mutex> lock(g_census_mutex);
+        if (out.census_index >= 0) {
+          g_census[out.census_index].mtf_maps++;
+          g_census[out.census_index].mtf_largest = std::max<uint64_t>(g_census[out.census_index].mtf_largest, code.ctx_map.size());
+        }
+      } else {
+        for (auto m : code.ctx_map) mt.emplace_back(0, m);
+      }
       EncOptions mo;
       mo.cfg = HybridUintConfig(4, 2, 0);
       mo.top_level = false;
@@ -840,7 +1077,7 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
   }
   bw.Write(1, use_prefix ? 1 : 0);
   if (!use_prefix) bw.Write(2, code.log_alpha - 5);
-  for (auto& c : code.cfg) WriteUintConfig(bw, c, code.log_alpha);
+  for (uint32_t k = 0; k < code.num_hist; k++) WriteUintConfig(bw, k == 0 && forms.bad_cfg ? forms.bad : code.cfg[k], code.log_alpha);
   if (use_prefix) {
     // alphabet sizes, then the codes
     std::vector<uint32_t> asz(code.num_hist);
@@ -871,7 +1108,16 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
   out.sym_start.resize(code.num_hist);
   for (uint32_t k = 0; k < code.num_hist; k++) {
     std::vector<int32_t> counts = NormalizeCounts(clusters[k].c);
-    WriteHistogram(bw, counts);
+    const HistStats hs = WriteHistogram(bw, counts, forms.hist, forms.hist == 2 ? forms.hist_shift : kAnsLogTabSize + 1, forms.bad_hist);
+    if (out.census_index >= 0) {
+      std::lock_guard<std::mutex> lock(g_census_mutex);
+      Census& g = g_census[out.census_index];
+      if (hs.simple) g.hist_simple++;
+      else if (hs.form == 1) { g.hist_flat++; g.hist_flat_not_pow2 += (counts.size() & (counts.size() - 1)) != 0; }
+      else if (hs.form == 2) g.hist_shift[forms.hist_shift]++;
+      else if (hs.rle_used) { g.hist_rle++; g.rle_to_end += hs.rle_to_end; }
+      else g.hist_full++;
+    }
     if (counts.empty()) counts.assign(1, kAnsTabSize);  // what the decoder reconstructs
     code.counts[k] = counts;
     InitAliasTable(counts, code.log_alpha, code.alias[k]);
@@ -896,7 +1142,14 @@ void BuildAndWriteCode(const std::vector<const std::vector<Token>*>& token_sets,
 void WriteTokens(const std::vector<Token>& tokens, const EncCode& ec, BitWriter& bw) {
   const EntropyCode& code = ec.code;
   std::vector<Sym> syms;
-  Symbolize(tokens, code.cfg[0], code.lz77, (uint32_t)ec.num_contexts, StreamDistMult(&tokens), syms);
+  {
+    Census local;
+    Symbolize(tokens, code.cfg, &code.ctx_map, ec.lz, code.lz77, (uint32_t)ec.num_contexts, StreamDistMult(&tokens), syms, ec.census_index >= 0 ? &local : nullptr);
+    if (ec.census_index >= 0) {
+      std::lock_guard<std::mutex> lock(g_census_mutex);
+      if ((size_t)ec.census_index < g_census.size()) g_census[ec.census_index].Add(local);
+    }
+  }
   const size_t n = syms.size();
   if (code.use_prefix) {
     for (const Sym& sy : syms) {
@@ -925,9 +1178,24 @@ void WriteTokens(const std::vector<Token>& tokens, const EncCode& ec, BitWriter&
     state = ((state / freq) << kAnsLogTabSize) + ec.reverse_map[h][ec.sym_start[h][tok] + state % freq];
   }
   bw.Write(32, state);
+  int64_t len_bit = -1, dist_bit = -1;
+  size_t dist_sym = n;
   for (size_t i = 0; i < n; i++) {
     if (flushed[i]) bw.Write(16, flush_bits[i]);
+    if (code.lz77 && len_bit < 0 && syms[i].ctx != ec.num_contexts && syms[i].tok >= code.lz_min_symbol && syms[i].nb > 0 && i + 1 < n && syms[i + 1].nb > 0) {
+      len_bit = (int64_t)bw.bitpos;
+      dist_sym = i + 1;
+    }
+    if (i == dist_sym) dist_bit = (int64_t)bw.bitpos;
     bw.Write(syms[i].nb, syms[i].bits);
+  }
+  if (ec.census_index >= 0 && len_bit >= 0) {
+    std::lock_guard<std::mutex> lock(g_census_mutex);
+    if ((size_t)ec.census_index < g_census.size() && g_census[ec.census_index].first_len_tail_bit < 0) {
+      g_census[ec.census_index].first_len_tail_bit = len_bit;
+      g_census[ec.census_index].first_dist_tail_bit = dist_bit;
+      g_census[ec.census_index].first_end_bit = (int64_t)bw.bitpos;
+    }
   }
 }
 

@@ -102,12 +102,42 @@ struct Token {
   Token(uint32_t c, uint32_t v) : ctx(c), value(v) {}
 };
 
+// The code forms a test can ask the writer for (tests/oracle_lib.py: encode(entropy=...)).  The defaults are what the writer has
+// always written: one configuration (4, 2, 0), LZ77 copies from one back and `dist_mult` back only, full-precision histograms.
+struct LzForm {
+  uint32_t min_symbol = 224, min_length = 3, max_len = 200;
+  HybridUintConfig len_cfg = HybridUintConfig(4, 2, 0);
+  bool custom_distances = false;   // false: the writer's own finder (one back, dist_mult back)
+  bool special[120] = {false};     // special distance indices the finder may use
+  bool general = false;            // ... and plain distances 1 .. general_max
+  uint32_t general_max = 40;
+  bool overshoot = false;          // a copy whose source is value 0 of the stream is coded with a distance past it
+  bool zero_start = false;         // a stream that begins with zeros begins with a copy
+};
+struct EntropyForms {
+  std::vector<HybridUintConfig> cfgs;   // per cluster index, round-robin; empty: (4, 2, 0) everywhere
+  bool have_lz = false;
+  LzForm lz;
+  int hist = 0;                         // 0 the writer's own, 1 flat, 2 reduced precision (hist_shift), 3 run-length symbol
+  int hist_shift = 13;
+  bool ctx_map_mtf = false;
+  // refusal tests: written into the header of every top-level code as given, the tokens keep their own configuration / histogram
+  bool bad_cfg = false;
+  HybridUintConfig bad;                 // the configuration field of cluster 0
+  int bad_hist = 0;                     // 1: shift field 14; 2: a run-length symbol right after the omitted position
+};
+void SpecialDistance(int index, int* dx, int* dy);   // row `index` (0 .. 119) of the reader's table of special LZ77 distances
+void SetEntropyForms(const EntropyForms* f);   // null: back to the defaults; a set of forms starts a new census
+std::string EntropyCensusJson();                // what the top-level codes written since SetEntropyForms used
+
 struct EncCode {
-  EntropyCode code;                                   // what the decoder will see
+  EntropyCode code;
+  LzForm lz;                                          // how WriteTokens finds its copies (as BuildAndWriteCode did)                                   // what the decoder will see
   std::vector<std::vector<uint16_t>> reverse_map;     // per histogram: [sym_start + offset] -> slot
   std::vector<std::vector<uint32_t>> sym_start;       // per histogram: start index of symbol in reverse_map
   std::vector<std::vector<uint16_t>> pcode;           // prefix codes: per histogram, canonical code of each symbol (MSB first)
   size_t num_contexts = 0;                            // without the LZ77 distance context
+  int census_index = -1;                              // the code's entry in the census (top-level codes written under EntropyForms)
 };
 
 struct EncOptions {

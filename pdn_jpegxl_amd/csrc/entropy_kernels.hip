@@ -336,7 +336,9 @@ __device__ __forceinline__ uint32_t SlowGet(Bits& b, uint32_t& state, const Code
   const DevCode& dc = *t.dc;
   const bool lz = (dc.slow & 2) != 0 && b.lz_win != nullptr;
   if (lz && b.lz_copy) {
-    const uint32_t v = b.lz_win[(b.lz_src++) & b.lz_mask];
+    // (source == destination only in a copy that starts the stream: it hands out zeros, and the window records them)
+    const uint32_t v = b.lz_src == b.lz_done ? 0u : b.lz_win[b.lz_src & b.lz_mask];
+    b.lz_src++;
     b.lz_copy--;
     b.lz_win[(b.lz_done++) & b.lz_mask] = v;
     return v;
@@ -352,10 +354,12 @@ __device__ __forceinline__ uint32_t SlowGet(Bits& b, uint32_t& state, const Code
     else if (dist < 120) { const int o = d_special_dist[dist][0] + (int)b.lz_dm * d_special_dist[dist][1]; dist = o < 1 ? 1u : (uint32_t)o; }
     else dist -= 119;
     dist = min(dist, min(b.lz_done, 1u << 20));
-    if (dist == 0 || b.lz_done > b.lz_mask + 1) { b.slow_err = 1; return 0; }   // nothing to copy from / a stream longer than its window
+    if (b.lz_done > b.lz_mask + 1) { b.slow_err = 1; return 0; }   // a stream longer than its window
+    // dist == 0: nothing decoded yet (the clamp above), so the copy is `len` zeros, written to the window like any other value
     b.lz_src = b.lz_done - dist;
     b.lz_copy = len - 1;
-    const uint32_t v = b.lz_win[(b.lz_src++) & b.lz_mask];
+    const uint32_t v = dist == 0 ? 0u : b.lz_win[b.lz_src & b.lz_mask];
+    b.lz_src++;
     b.lz_win[(b.lz_done++) & b.lz_mask] = v;
     return v;
   }

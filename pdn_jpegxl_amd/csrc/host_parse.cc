@@ -323,6 +323,8 @@ class SymReader {
       else dist -= 119;
       dist = std::min(dist, std::min(done_, 1u << 20));
       src_ = done_ - dist;
+      // dist == 0: a copy that starts the stream (nothing to clamp to) is zeros; Copy() reads each from the slot it then writes
+      if (dist == 0) std::fill(win_.begin(), win_.begin() + std::min<size_t>(copy_, win_.size()), 0u);
       return Copy();
     }
     uint32_t v = Hybrid(c_.cfg[h], tok);

@@ -161,10 +161,100 @@ def flatten_transforms(transforms):
     return flat
 
 
+_DEFAULT_DISTANCES = (0, 1)
+
+
+def flatten_entropy(e):
+    """encode(entropy=...) as the flat ints of oracle/jxo_api.cc: jxo_set_next_entropy.  Keys:
+    cfgs: [(split, msb, lsb), ...], given to each code's clusters by cluster index, round-robin (clusters are found on default tokens);
+    lz: dict(min_symbol, min_length, len_cfg, max_len, distances, general_max, overshoot, zero_start) - implies lz77.  distances is a
+      collection of special indices 0..119 and / or "general" (plain distances 1..general_max, default 40); the finder takes the longest
+      match, ties to the lowest index, special before general.  On streams without a distance multiplier (HF coefficients) the special
+      indices mean "one back".  Without `distances` the writer keeps its own finder (one back, one row back);
+    hist: "flat", ("shift", s) or "rle"; ctx_map_mtf: bool;
+    bad_cfg: (split, msb, lsb) written as cluster 0's configuration whatever the tokens use; bad_hist: "shift14" / "rle_after_omit"
+      (refusal tests: the streams do not decode)."""
+    unknown = set(e) - {"cfgs", "lz", "hist", "ctx_map_mtf", "bad_cfg", "bad_hist"}
+    if unknown:
+        raise OracleError("entropy: unknown keys %s" % sorted(unknown))
+    flat = [len(e.get("cfgs", ()))]
+    for c in e.get("cfgs", ()):
+        flat += [int(v) for v in c]
+    lz = e.get("lz")
+    unknown = set(lz or ()) - {"min_symbol", "min_length", "len_cfg", "max_len", "distances", "general_max", "overshoot", "zero_start"}
+    if unknown:
+        raise OracleError("entropy: unknown lz keys %s" % sorted(unknown))
+    lz = lz or {}
+    dist = lz.get("distances")
+    special = sorted(d for d in (dist if dist is not None else _DEFAULT_DISTANCES) if d != "general")
+    flat += [int(e.get("lz") is not None), lz.get("min_symbol", 224), lz.get("min_length", 3), lz.get("max_len", 200)]
+    flat += list(lz.get("len_cfg", (4, 2, 0)))
+    flat += [int(dist is not None), len(special)] + special
+    flat += [int(dist is not None and "general" in dist), lz.get("general_max", 40), int(lz.get("overshoot", False)), int(lz.get("zero_start", False))]
+    hist = e.get("hist")
+    if hist is None:
+        flat += [0, 13]
+    elif hist == "flat":
+        flat += [1, 13]
+    elif hist == "rle":
+        flat += [3, 13]
+    elif isinstance(hist, tuple) and hist[0] == "shift":
+        flat += [2, int(hist[1])]
+    else:
+        raise OracleError("entropy: unknown histogram form %r" % (hist,))
+    flat += [int(e.get("ctx_map_mtf", False))]
+    flat += [int("bad_cfg" in e)] + list(e.get("bad_cfg", (0, 0, 0))) + [{None: 0, "shift14": 1, "rle_after_omit": 2}[e.get("bad_hist")]]
+    return flat
+
+
+def special_distances():
+    """The oracle reader's table of special LZ77 distances: 120 (dx, dy) pairs by index."""
+    L = lib()
+    L.jxo_special_distance.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    out = []
+    for i in range(120):
+        dx, dy = C.c_int32(), C.c_int32()
+        L.jxo_special_distance(i, C.byref(dx), C.byref(dy))
+        out.append((dx.value, dy.value))
+    return out
+
+
+def entropy_census():
+    """What the last encode(entropy=...) wrote.  "codes": one dict per top-level code in the order written - contexts, log_alpha,
+    prefix, lz77, cfgs (per cluster), special (copies per special index), general (plain-distance copies; general_min / general_max their
+    smallest and largest distance as coded, general_small[d] the count of distance d = 1..8), overlapping (distance < length), clamped,
+    zero_start, longest_copy, max_tail_bits (the most extra bits read for one value), max_dist_tail_bits (for one distance), the
+    histogram forms (hist_simple / hist_flat / hist_flat_not_pow2 / hist_shift {s: n} / hist_rle / rle_to_end / hist_full), mtf_maps and
+    mtf_largest.  The same keys at the top level hold the sums (max_*, longest_copy, general_max, mtf_largest: the largest) over the codes."""
+    import json
+    L = lib()
+    L.jxo_entropy_census.restype = C.c_size_t
+    L.jxo_entropy_census.argtypes = [C.c_char_p, C.c_size_t]
+    n = L.jxo_entropy_census(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    L.jxo_entropy_census(buf, n)
+    cen = json.loads(buf.raw[:n].decode())
+    codes = cen["codes"]
+    for key in ("general", "overlapping", "clamped", "zero_start", "hist_simple", "hist_flat", "hist_flat_not_pow2", "hist_rle", "rle_to_end",
+                "hist_full", "mtf_maps"):
+        cen[key] = sum(c[key] for c in codes)
+    for key in ("longest_copy", "max_tail_bits", "max_dist_tail_bits", "general_max", "mtf_largest"):
+        cen[key] = max([c[key] for c in codes] or [0])
+    cen["general_min"] = min([c["general_min"] for c in codes if c["general"]] or [0])
+    cen["special"] = [sum(c["special"][k] for c in codes) for k in range(120)]
+    cen["general_small"] = [sum(c["general_small"][k] for c in codes) for k in range(9)]
+    cen["hist_shift"] = {}
+    for c in codes:
+        for s, v in c["hist_shift"].items():
+            cen["hist_shift"][int(s)] = cen["hist_shift"].get(int(s), 0) + v
+    cen["cfgs"] = sorted({tuple(g) for c in codes for g in c["cfgs"]})
+    return cen
+
+
 def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, seed=1, epf_iters=-1, gaborish=True,
            container=True, adaptive_lf_smoothing=True, lossless_predictor=6, lossless_squeeze=False, num_threads=8, exif=None,
            xmp=None, lossless_tree=0, bits=8, orientation=1, float_samples=0, colour=0, icc=None, cmyk=False, animation_frames=1, custom_quant_tables=False, prefix_codes=False, lz77=False, num_passes=1, custom_orders=False, lf_contexts=False, palette=False, mislabel_afv=False,
-           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None, transforms=None):
+           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None, transforms=None, entropy=None):
     """px: uint8 array (h, w, nch) with nch in 1..4 (Gray, GrayA, RGB, RGBA); with bits > 8 (up to 16) a uint16 array whose
     samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes.
     side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters).
@@ -179,8 +269,16 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
     channels of earlier palettes in front; ("squeeze", [(horizontal, in_place, begin_c, num_c), ...]), an empty list being the default
     parameters (written as a count of 0); and, as the last entry only, ("declare", id, fields...): the header fields of transform `id`
     (0: begin_c, rct_type; 1: begin_c, num_c, nb_colors, nb_deltas, predictor; 2: a list of squeeze tuples) written as given, with nothing
-    done to the channels and nothing checked (refusal tests)."""
+    done to the channels and nothing checked (refusal tests).
+    entropy: a dict that changes how the frame's top-level codes turn values into symbols and headers (flatten_entropy); tokens' values
+    and contexts and all quantised data are those of the same call without it.  entropy_census() then describes what was written."""
     L = lib()
+    if entropy is not None:
+        lz77 = lz77 or "lz" in entropy
+        flat = np.ascontiguousarray(flatten_entropy(entropy), dtype=np.int32)
+        L.jxo_set_next_entropy.argtypes = [C.c_void_p, C.c_size_t]
+        if not L.jxo_set_next_entropy(flat.ctypes.data, len(flat)):
+            raise OracleError(L.jxo_last_error().decode())
     if float_samples:
         px = np.ascontiguousarray(px, dtype=np.float16 if float_samples == 16 else np.float32)
     else:
