@@ -19,6 +19,8 @@
  * Part 4 (jxlhip_encode_batch) encodes many device-resident images in one call.
  *
  * Part 5 (jxlhip_animation_*) decodes every displayed image of an animated file into device memory, in file order.
+ *
+ * Part 6 (jxlhip_encode_animation) encodes a stack of device-resident frames as one animated file: each frame as what changed.
  */
 #ifndef JXLFILETYPEIO_H_
 #define JXLFILETYPEIO_H_
@@ -377,9 +379,45 @@ JXLFILETYPEIO_API int32_t jxlhip_animation_set_option(JxlHipAnimation* anim, con
 /* The decoder the animation runs on, owned by it: for jxlhip_stage_times / jxlhip_stage_totals (measurement). */
 JXLFILETYPEIO_API JxlHipDecoder* jxlhip_animation_decoder(JxlHipAnimation* anim);
 
+/* =====================================================================================================
+ * Part 6: animation encode - a stack of device-resident frames as ONE animated file (not in the reference).
+ *
+ * Frame 0 is written whole.  Every later frame is written as the bounding box of the samples whose bits differ from its
+ * predecessor's (measured on the GPU, in the caller's memory), replacing that part of the canvas: lossless frames as the
+ * exact box, lossy frames as the box grown outwards to multiples of 8 canvas pixels (clipped to the canvas).  A frame that
+ * equals its predecessor is written as the 1 x 1 rectangle at (0, 0): the file has one displayed image per input frame, and
+ * durations are never merged.  Every frame replaces (colour and alpha), reads and is saved to reference slot 1, and has no
+ * name; there are no timecodes.
+ * ===================================================================================================== */
+typedef struct JxlHipAnimationOptions {
+  uint32_t tps_numerator, tps_denominator;   /* ticks per second = numerator / denominator; numerator 1 .. 2^30, denominator 1 .. 1024 */
+  uint32_t num_loops;                        /* 0: endless */
+  int32_t key_interval;                      /* >= 1: every key_interval-th frame is written whole, like frame 0 (an entry point that
+                                              * needs no earlier frame); <= 0: only frame 0 */
+  int32_t chunk_frames;                      /* >= 1: at most this many frames go through the encoder at a time; <= 0: as many as a
+                                              * workspace of 32 GiB holds, at most 64.  The file's bytes do not depend on it */
+} JxlHipAnimationOptions;
+
+/* Encodes n frames (frames[k].data: DEVICE pointers, as for jxlhip_encode_batch; only read) into one file, read with
+ * jxlhip_encoder_result(enc, 0, ...).  durations[k]: ticks frame k is shown for, >= 1.  `options` holds for every frame.  metadata
+ * may be NULL (Exif and XMP: host pointers, written once).  Synchronous.
+ * The bytes of frame k from its TOC on are those of jxlhip_save_pixels for the frame's rectangle with the same options.
+ * Refused on the host, before any device work, with EncoderStatus_EncodeError and a message: whatever jxlhip_encode_batch refuses
+ * of an image (in the same words, behind "frame k: "), n < 1, frames that differ from frame 0 in size, channels, sample type,
+ * bits or colour, a duration of 0, and ticks per second outside their ranges.  After a failure, refusals included, the encoder
+ * holds no result and stays usable. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                        const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                        const EncoderImageMetadata* metadata, ErrorInfo* err);
+
+/* The rectangles of the last jxlhip_encode_animation that got as far as measuring them: x, y, width, height per frame, up to
+ * `capacity` frames are written to xywh.  Returns the number of frames (0: none). */
+JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_rects(JxlHipEncoder* enc, int32_t* xywh, int32_t capacity);
+
 #ifdef __cplusplus
 }
 static_assert(sizeof(JxlHipPixels) == 40, "JxlHipPixels layout");
+static_assert(sizeof(JxlHipAnimationOptions) == 20, "JxlHipAnimationOptions layout");
 static_assert(sizeof(JxlHipAnimationInfo) == 64, "JxlHipAnimationInfo layout");
 static_assert(sizeof(JxlHipAnimationFrame) == 1096, "JxlHipAnimationFrame layout");
 static_assert(sizeof(BitmapData) == 24, "BitmapData layout");

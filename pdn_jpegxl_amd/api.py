@@ -76,6 +76,11 @@ class JxlHipPixels(C.Structure):
                 ("num_channels", C.c_int32), ("sample_type", C.c_int32), ("bits_per_sample", C.c_int32), ("colour", C.c_int32)]
 
 
+class AnimationOptions(C.Structure):
+    _fields_ = [("tps_numerator", C.c_uint32), ("tps_denominator", C.c_uint32), ("num_loops", C.c_uint32), ("key_interval", C.c_int32),
+                ("chunk_frames", C.c_int32)]
+
+
 class AnimationInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("num_channels", C.c_int32), ("has_alpha", C.c_int32),
                 ("bytes_per_sample", C.c_int32), ("float_samples", C.c_int32), ("bits_per_sample", C.c_int32), ("have_animation", C.c_int32),
@@ -92,7 +97,7 @@ EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jx
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
            "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
-           "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
+           "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_encode_animation", "jxlhip_encoder_animation_rects", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
            "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder"]
 
 _lib = None
@@ -189,6 +194,11 @@ def lib(build_if_missing=True):
     L.jxlhip_encoder_result.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.jxlhip_encoder_stage_times.restype = C.c_int32
     L.jxlhip_encoder_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int32]
+    L.jxlhip_encode_animation.restype = C.c_int32
+    L.jxlhip_encode_animation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(C.c_uint32), C.POINTER(EncoderOptions),
+                                          C.POINTER(AnimationOptions), C.POINTER(EncoderImageMetadata), C.POINTER(ErrorInfo)]
+    L.jxlhip_encoder_animation_rects.restype = C.c_int32
+    L.jxlhip_encoder_animation_rects.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.jxlhip_animation_open.restype = C.c_void_p
     L.jxlhip_animation_open.argtypes = [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(AnimationInfo), C.POINTER(ErrorInfo)]
     L.jxlhip_animation_close.restype = None
@@ -666,6 +676,51 @@ class Encoder:
             p, size = C.c_void_p(), C.c_size_t()
             out.append(C.string_at(p.value, size.value) if self._L.jxlhip_encoder_result(self._h, i, C.byref(p), C.byref(size)) else None)
         return out
+
+    def encode_animation(self, frames, durations, tps=(100, 1), loops=0, key_interval=0, chunk_frames=0, distance=1.0, effort=7,
+                         lossless=False, colour=None, bits=None, exif=None, xmp=None):
+        """jxlhip_encode_animation: the frames as ONE animated file (bytes).  frames: a list of EncodeItem / GPU tensors (h, w[, c]), or
+        one GPU tensor [n, h, w, c]; all of one size, channel count and sample type.  durations: ticks per frame (>= 1), one per frame
+        or one number for all; tps: ticks per second as (numerator, denominator); loops: 0 = endless.  Frame 0 - and with
+        key_interval >= 1 every key_interval-th frame - is written whole, every other frame as the rectangle that changed against its
+        predecessor (lossy: grown to multiples of 8 pixels), a frame that changed nothing as one pixel; last_animation_rects has
+        them.  chunk_frames: frames that go through the encoder at a time (0: by its workspace budget; the bytes do not depend on it).
+        distance, effort, lossless hold for every frame; colour and bits default to those of the first EncodeItem (tensors: "Srgb",
+        8 / 16 bits).  Raises JxlError where the call is refused or fails; the encoder stays usable."""
+        if hasattr(frames, "dim") and not isinstance(frames, (list, tuple)):
+            frames = [frames[k] for k in range(frames.shape[0])]
+        items = [f if isinstance(f, EncodeItem) else EncodeItem.from_tensor(f) for f in frames]
+        n = len(items)
+        if not hasattr(durations, "__len__"):
+            durations = [durations] * n
+        if len(durations) != n:
+            raise ValueError("one duration per frame is expected")
+        px = (JxlHipPixels * max(n, 1))()
+        for i, it in enumerate(items):
+            px[i] = JxlHipPixels(it.ptr, it.width, it.height, it.stride_bytes, it.channels, _SAMPLE_TYPES[it.dtype],
+                                 it.bits if bits is None else int(bits), KNOWN_PROFILE.index(it.colour if colour is None else colour))
+        dur = (C.c_uint32 * max(n, 1))(*[int(d) for d in durations])
+        opt = EncoderOptions(float(distance), int(effort), bool(lossless))
+        ao = AnimationOptions(int(tps[0]), int(tps[1]), int(loops), int(key_interval), int(chunk_frames))
+        bufs = [np.frombuffer(b, np.uint8) if b else None for b in (exif, None, xmp)]
+        md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in bufs), []))
+        err = ErrorInfo()
+        r = self._L.jxlhip_encode_animation(self._h, n, px, dur, C.byref(opt), C.byref(ao), C.byref(md), C.byref(err))
+        self.last_error = err.errorMessage.decode("ascii", "replace")
+        if r != 0:
+            raise JxlError(ENCODER_STATUS[r] if 0 <= r < len(ENCODER_STATUS) else str(r), self.last_error)
+        p, size = C.c_void_p(), C.c_size_t()
+        if not self._L.jxlhip_encoder_result(self._h, 0, C.byref(p), C.byref(size)):
+            raise JxlError("EncodeError", "the encoder holds no result")
+        return C.string_at(p.value, size.value)
+
+    @property
+    def last_animation_rects(self):
+        """[(x, y, width, height)] per frame of the last encode_animation that got as far as measuring what changed."""
+        n = self._L.jxlhip_encoder_animation_rects(self._h, None, 0)
+        buf = (C.c_int32 * (4 * max(n, 1)))()
+        self._L.jxlhip_encoder_animation_rects(self._h, buf, n)
+        return [tuple(buf[4 * k:4 * k + 4]) for k in range(n)]
 
     def stage_times(self):
         """{stage: ms} of the last batch: device time per kernel group (stages on different streams overlap), then the host's stages

@@ -1,0 +1,140 @@
+// HIP kernel (gfx950) of animation encode: what changed between consecutive frames.
+//
+// anim_extents_kernel: for every pair (frame k - 1, frame k) the bounding box of the samples whose BITS differ (+0.0 and -0.0 differ,
+// equal NaN patterns do not, a changed alpha sample counts like any other).  It reads the caller's memory as it lies: any base
+// pointer a sample allows, any row stride, rows of row_bytes bytes - the bytes between the end of a row and the next row are never
+// loaded.  A sample differs when one of its bytes does, so the rows are compared as bytes and the first and the last differing byte
+// of a row give the box; only the final division by the pixel size knows about pixels.
+//
+// One launch, grid = pairs x row blocks (a 2-frame 4K animation is 540 workgroups).  A wavefront takes a row at a time: the bytes in
+// front of the first 16-byte boundary of frame k - 1's row (the head) and behind the last (the tail) go one byte per lane; the middle
+// goes 16 bytes per lane and step: frame k - 1 in aligned 16-byte loads, frame k in 16-byte loads at the same offset, aligned when
+// the two rows are congruent modulo 16 and unaligned otherwise (global loads of gfx950 take any address).  Lanes
+// keep (first byte, last byte, first row, last row) in registers; a wavefront reduces them by shuffles, the workgroup through 64
+// bytes of LDS, and one lane issues at most four atomics (unsigned min for x0 / y0, signed max for x1 / y1) - none when the
+// workgroup saw no difference.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdint>
+#include "enc_animation.h"
+
+namespace jxlhip {
+namespace {
+
+constexpr int kExtThreads = 256, kExtWaves = kExtThreads / 64;
+
+struct ExtAcc {
+  uint64_t lo = ~(uint64_t)0, hi = 0;   // first and last differing byte of a row, over the rows seen
+  int32_t y0 = 0x7FFFFFFF, y1 = -1;     // y1 < 0: no difference seen
+  __device__ __forceinline__ void Mark(uint64_t first, uint64_t last, int32_t y) {
+    lo = first < lo ? first : lo;
+    hi = last > hi ? last : hi;
+    y0 = y < y0 ? y : y0;
+    y1 = y > y1 ? y : y1;
+  }
+};
+
+__device__ __forceinline__ uint32_t FirstByte(uint32_t d) { return (uint32_t)(__ffs((int)d) - 1) >> 3; }   // d != 0
+__device__ __forceinline__ uint32_t LastByte(uint32_t d) { return (31u - (uint32_t)__clz((int)d)) >> 3; }
+
+__device__ __forceinline__ void MarkChunk(const uint4& a, const uint4& b, uint64_t off, int32_t y, ExtAcc& acc) {
+  const uint32_t d0 = a.x ^ b.x, d1 = a.y ^ b.y, d2 = a.z ^ b.z, d3 = a.w ^ b.w;
+  if ((d0 | d1 | d2 | d3) == 0) return;
+  const uint32_t first = d0 ? FirstByte(d0) : (d1 ? 4 + FirstByte(d1) : (d2 ? 8 + FirstByte(d2) : 12 + FirstByte(d3)));
+  const uint32_t last = d3 ? 12 + LastByte(d3) : (d2 ? 8 + LastByte(d2) : (d1 ? 4 + LastByte(d1) : LastByte(d0)));
+  acc.Mark(off + first, off + last, y);
+}
+
+// 16 bytes at p, whatever its alignment (global loads of gfx950 need none: this is one dwordx4 load)
+__device__ __forceinline__ uint4 LoadUnaligned(const uint8_t* p) {
+  uint4 v;
+  __builtin_memcpy(&v, p, 16);
+  return v;
+}
+
+// the middle of a row: chunks [0, nmid) of 16 bytes at a (16-byte aligned) against those at b; `off`: of a within its row
+__device__ __forceinline__ void CompareMiddle(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t nmid, uint64_t off, int lane,
+                                              int32_t y, ExtAcc& acc) {
+#pragma unroll 4
+  for (uint64_t j = (uint64_t)lane; j < nmid; j += 64) {
+    const uint4 va = *reinterpret_cast<const uint4*>(a + 16 * j);
+    const uint4 vb = LoadUnaligned(b + 16 * j);
+    MarkChunk(va, vb, off + 16 * j, y, acc);
+  }
+}
+
+__global__ __launch_bounds__(kExtThreads) void anim_extents_kernel(const AnimFrameSrc* __restrict__ frames, int32_t h, uint64_t row_bytes,
+                                                                    uint32_t pixel_bytes, int32_t rows_per_wg, uint32_t row_blocks,
+                                                                    AnimExtent* __restrict__ out) {
+  const uint32_t pair = blockIdx.x / row_blocks, block = blockIdx.x % row_blocks;
+  const AnimFrameSrc fa = frames[pair], fb = frames[pair + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row0 = (int64_t)block * rows_per_wg;
+  const int32_t row1 = (int32_t)std::min<int64_t>(h, row0 + rows_per_wg);
+  ExtAcc acc;
+  for (int32_t y = (int32_t)row0 + wave; y < row1; y += kExtWaves) {
+    const uint8_t* a = fa.data + (int64_t)y * fa.stride;
+    const uint8_t* b = fb.data + (int64_t)y * fb.stride;
+    // [0, head) and [tail, row_bytes): a byte per lane; [head, tail): 16 bytes per lane and step.  Every load lies inside the row.
+    const uint64_t head = std::min<uint64_t>(row_bytes, (uint64_t)(-(intptr_t)a & 15));
+    const uint64_t nmid = (row_bytes - head) >> 4;
+    const uint64_t tail = head + 16 * nmid;
+    if ((uint64_t)lane < head) {
+      if (a[lane] != b[lane]) acc.Mark((uint64_t)lane, (uint64_t)lane, y);
+    } else if (lane >= 32 && lane < 48 && tail + (uint64_t)(lane - 32) < row_bytes) {
+      const uint64_t o = tail + (uint64_t)(lane - 32);
+      if (a[o] != b[o]) acc.Mark(o, o, y);
+    }
+    CompareMiddle(a + head, b + head, nmid, head, lane, y, acc);
+  }
+  // bytes -> pixels, then lanes -> wavefront -> workgroup -> at most four atomics
+  uint32_t x0 = 0xFFFFFFFFu, y0 = 0xFFFFFFFFu;
+  int32_t x1 = -1, y1 = -1;
+  if (acc.y1 >= 0) {
+    x0 = (uint32_t)(acc.lo / pixel_bytes);
+    x1 = (int32_t)(acc.hi / pixel_bytes);
+    y0 = (uint32_t)acc.y0;
+    y1 = acc.y1;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    x0 = std::min(x0, (uint32_t)__shfl_xor((int)x0, m, 64));
+    y0 = std::min(y0, (uint32_t)__shfl_xor((int)y0, m, 64));
+    x1 = std::max(x1, __shfl_xor(x1, m, 64));
+    y1 = std::max(y1, __shfl_xor(y1, m, 64));
+  }
+  __shared__ int32_t part[kExtWaves][4];
+  if (lane == 0) { part[wave][0] = (int32_t)x0; part[wave][1] = (int32_t)y0; part[wave][2] = x1; part[wave][3] = y1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kExtWaves; w++) {
+      x0 = std::min(x0, (uint32_t)part[w][0]);
+      y0 = std::min(y0, (uint32_t)part[w][1]);
+      x1 = std::max(x1, part[w][2]);
+      y1 = std::max(y1, part[w][3]);
+    }
+    if (y1 >= 0) {
+      AnimExtent* e = out + pair;
+      atomicMin(reinterpret_cast<unsigned int*>(&e->x0), x0);
+      atomicMin(reinterpret_cast<unsigned int*>(&e->y0), y0);
+      atomicMax(&e->x1, x1);
+      atomicMax(&e->y1, y1);
+    }
+  }
+}
+
+}  // namespace
+
+void LaunchAnimExtents(const AnimFrameSrc* frames, int32_t npairs, int32_t h, uint64_t row_bytes, uint32_t pixel_bytes, AnimExtent* out, void* stream) {
+  if (npairs <= 0 || h <= 0) return;
+  // a row per wavefront at least; more rows per workgroup once the grid has some thousand workgroups, and whatever keeps it below 2^30
+  const int64_t rows = (int64_t)npairs * h;
+  int64_t per_wg = std::max<int64_t>(kExtWaves, std::min<int64_t>(64, rows / 4096));
+  per_wg = std::max(per_wg, (rows + (1 << 30) - 1) >> 30);
+  per_wg = std::min<int64_t>((per_wg + kExtWaves - 1) / kExtWaves * kExtWaves, 0x7FFFFFFF / 2);
+  const uint32_t row_blocks = (uint32_t)((h + per_wg - 1) / per_wg);
+  hipLaunchKernelGGL(anim_extents_kernel, dim3((uint32_t)npairs * row_blocks), dim3(kExtThreads), 0, (hipStream_t)stream, frames, h, row_bytes, pixel_bytes,
+                     (int32_t)per_wg, row_blocks, out);
+}
+
+}  // namespace jxlhip

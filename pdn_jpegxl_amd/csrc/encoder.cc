@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/jxlfiletypeio.h"
+#include "enc_animation.h"
 #include "enc_batch_layout.h"
 #include "enc_types.h"
 #include "host_parse.h"
@@ -322,8 +323,11 @@ void BeginImage(const EncSource& src, const EncoderImageMetadata* md, Arena& A, 
   Progress(progress, 5);
 }
 
+// A frame of an animation: its headers speak of `canvas`, it lies at `at`, and no image header is written in front of it.
+struct FrameOnCanvas { EncImageInfo canvas; EncFramePlacement at; };
+
 std::vector<uint8_t> AssembleLossless(const EncImage& im, const EncSource& src, const EncoderImageMetadata* md, BitWriter& lf_global, const uint8_t* packed,
-                                      const uint64_t* off, const uint64_t* sec_bits);
+                                      const uint64_t* off, const uint64_t* sec_bits, const FrameOnCanvas* on = nullptr);
 
 // ANS-codes the groups' tokens (im.tok_ll) with `mcode`, gathers the sections and assembles the codestream behind the finished LfGlobal
 // prefix.  The section buffers are allocated at the first call of a save and reused by the next.
@@ -363,14 +367,16 @@ EncImageInfo DescribeImage(const EncImage& im, const EncSource& src, const Encod
 }
 
 // The codestream of a Modular frame behind its finished LfGlobal prefix.  packed + off[g], sec_bits[g]: the coded section of group g.
+// `on`: the frame alone, as a frame of an animation.
 std::vector<uint8_t> AssembleLossless(const EncImage& im, const EncSource& src, const EncoderImageMetadata* md, BitWriter& lf_global, const uint8_t* packed,
-                                      const uint64_t* off, const uint64_t* sec_bits) {
+                                      const uint64_t* off, const uint64_t* sec_bits, const FrameOnCanvas* on) {
   const bool single = im.ng == 1;
-  const EncImageInfo ii = DescribeImage(im, src, md, false);
+  const EncImageInfo ii = on ? on->canvas : DescribeImage(im, src, md, false);
   EncFrameInfo fi;
   fi.encoding = 1; fi.group_size_shift = 1; fi.gab = false; fi.epf_iters = 0;
+  if (on) fi.at = on->at;
   BitWriter cs;
-  WriteCodestreamHeaders(ii, cs);
+  if (!on) WriteCodestreamHeaders(ii, cs);
   WriteFrameHeader(ii, fi, cs);
   std::vector<std::vector<uint8_t>> sections;
   if (single) {
@@ -892,11 +898,12 @@ void WriteLossyHfGlobal(const EncImage& im, const uint32_t* hist_ac, BitWriter& 
 }
 
 // The codestream of a lossy frame from its finished LfGlobal and HfGlobal and the coded sections: packed + off[s], sec_bits[s] for
-// section s (LF groups, groups, then the global alpha stream of a one-group frame).
+// section s (LF groups, groups, then the global alpha stream of a one-group frame).  frame_only: a frame of an animation (ii: its
+// canvas, fi.at: where it lies), without the image header.
 std::vector<uint8_t> AssembleLossy(const EncImage& im, const EncImageInfo& ii, const EncFrameInfo& fi, BitWriter& lf_global, BitWriter& hf_global,
-                                   const uint8_t* packed, const uint64_t* off, const uint64_t* sec_bits) {
+                                   const uint8_t* packed, const uint64_t* off, const uint64_t* sec_bits, bool frame_only = false) {
   BitWriter cs;
-  WriteCodestreamHeaders(ii, cs);
+  if (!frame_only) WriteCodestreamHeaders(ii, cs);
   WriteFrameHeader(ii, fi, cs);
   auto bytes = [&](int sec) { return std::vector<uint8_t>(packed + off[sec], packed + off[sec] + ((sec_bits[sec] + 7) >> 3)); };
   std::vector<std::vector<uint8_t>> sections;
@@ -1383,6 +1390,7 @@ struct BatchJob {
   BitWriter lf_global, hf_global;
   EncCode mcode, acode;
   size_t first_section = 0;    // of the batch's section list
+  const FrameOnCanvas* on = nullptr;   // a frame of an animation: the result is the frame alone, no image header, no container
 };
 
 }  // namespace
@@ -1397,6 +1405,8 @@ struct JxlHipEncoder {
   PinnedBuffer h_hist, h_packed;
   std::vector<std::vector<uint8_t>> files;   // the results of the last batch
   std::vector<std::pair<const char*, float>> stages;
+  DeviceBuffer anim;                         // animation encode: the frame table and the extents of the pairs
+  std::vector<AnimRect> anim_rects;          // the rectangles of the last animation
 
   explicit JxlHipEncoder(int dev) {
     if (dev >= 0) ENC_HIP(hipSetDevice(dev));
@@ -1617,6 +1627,13 @@ void JxlHipEncoder::Run(std::vector<BatchJob>& jobs) {
     BatchJob& job = jobs[i];
     const uint64_t* o = off.data() + job.first_section;
     const uint64_t* bits = host_bits(ims[i].sec_bits);
+    if (job.on) {
+      EncFrameInfo fi = job.qp.fi;
+      fi.at = job.on->at;
+      files[(size_t)job.index] = job.lossless ? AssembleLossless(ims[i], job.src, &job.md, job.lf_global, h_packed.p, o, bits, job.on)
+                                              : AssembleLossy(ims[i], job.on->canvas, fi, job.lf_global, job.hf_global, h_packed.p, o, bits, true);
+      return;
+    }
     const std::vector<uint8_t> cs = job.lossless ? AssembleLossless(ims[i], job.src, &job.md, job.lf_global, h_packed.p, o, bits)
                                                  : AssembleLossy(ims[i], DescribeImage(ims[i], job.src, &job.md, true), job.qp.fi, job.lf_global, job.hf_global, h_packed.p, o, bits);
     files[(size_t)job.index] = WriteContainer(cs, job.md.exif, job.md.exifSize, job.md.xmp, job.md.xmpSize);
@@ -1638,6 +1655,15 @@ extern "C" JXLFILETYPEIO_API JxlHipEncoder* jxlhip_encoder_create(int32_t device
 }
 
 extern "C" JXLFILETYPEIO_API void jxlhip_encoder_destroy(JxlHipEncoder* enc) { delete enc; }
+
+namespace {
+// What a batch refuses of an image, on the host (jxlhip_encode_batch per image, jxlhip_encode_animation per frame)
+void CheckBatchImage(const JxlHipPixels* px, const EncoderOptions* opt, const EncoderImageMetadata* md, EncSource& src) {
+  CheckPixels(px, opt, md, src);
+  if (opt->effort >= 8)
+    throw EncFail(EncoderStatus_EncodeError, "efforts 8 and 9 (the closed loop and the lossless search) are not available in a batch: use jxlhip_save_pixels");
+}
+}  // namespace
 
 extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
                                                                const EncoderImageMetadata* const* metadata, EncoderStatus* statuses, ErrorInfo* err) {
@@ -1665,9 +1691,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* en
     memset(&job.md, 0, sizeof(job.md));
     if (metadata && metadata[i]) job.md = *metadata[i];
     try {
-      CheckPixels(&images[i], &options[i], &job.md, job.src);
-      if (options[i].effort >= 8)
-        throw EncFail(EncoderStatus_EncodeError, "efforts 8 and 9 (the closed loop and the lossless search) are not available in a batch: use jxlhip_save_pixels");
+      CheckBatchImage(&images[i], &options[i], &job.md, job.src);
       job.lossless = options[i].lossless;
       jobs.push_back(std::move(job));
     } catch (const EncFail& e) {
@@ -1701,6 +1725,192 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* en
   }
   if (caller_device != enc->device) (void)hipSetDevice(caller_device);
   return first;
+}
+
+// =====================================================================================================
+// Part 6 of the C-ABI: animation encode.  The extents kernel says what changed, enc_animation.cc turns that into
+// rectangles, and the rectangles go through Run like the images of a batch - a crop is a pointer offset and a narrower row in Run's
+// copy into tight rows.  Run hands back every frame alone (header, TOC, sections); they follow the image header in one codestream.
+// =====================================================================================================
+namespace {
+
+constexpr int kAnimMaxChunkFrames = 64;                      // frames of one Run unless chunk_frames says otherwise
+constexpr size_t kAnimWorkspaceBudget = (size_t)32 << 30;    // ... and at most this much workspace (32 4K RGBA frames), unless one frame needs more
+
+// Everything behind the host's checks.  src0: what CheckPixels made of frame 0 (the same for every frame).
+void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations, const EncoderOptions& opt,
+                     const JxlHipAnimationOptions& ao, const EncoderImageMetadata& md, const EncSource& src0) {
+  const JxlHipPixels& f0 = frames[0];
+  const int32_t w = (int32_t)f0.width, h = (int32_t)f0.height;
+  const uint32_t pixel_bytes = (uint32_t)(f0.num_channels * src0.sample_bytes());
+  const bool lossless = opt.lossless;
+  hipStream_t s0 = enc->streams[0];
+  StageMarks marks;
+  // ---- 1. what changed between consecutive frames: one launch, one download of 16 bytes per pair
+  std::vector<AnimExtent> ext((size_t)std::max(n - 1, 0));
+  if (n > 1) {
+    const size_t table_bytes = ((size_t)n * sizeof(AnimFrameSrc) + 255) & ~(size_t)255, out_bytes = ext.size() * sizeof(AnimExtent);
+    enc->anim.Reserve(table_bytes + out_bytes, true);
+    std::vector<AnimFrameSrc> table((size_t)n);
+    for (int k = 0; k < n; k++) table[(size_t)k] = AnimFrameSrc{(const uint8_t*)frames[k].data, (int64_t)frames[k].stride_bytes};
+    AnimExtent* d_ext = (AnimExtent*)(enc->anim.p + table_bytes);
+    ENC_HIP(hipMemcpyAsync(enc->anim.p, table.data(), table.size() * sizeof(AnimFrameSrc), hipMemcpyHostToDevice, s0));
+    ENC_HIP(hipMemsetAsync(d_ext, 0xFF, out_bytes, s0));
+    const size_t k_ext = marks.Begin("change extents of every pair of frames (one launch)", s0);
+    LaunchAnimExtents((const AnimFrameSrc*)enc->anim.p, n - 1, h, (uint64_t)f0.width * pixel_bytes, pixel_bytes, d_ext, s0);
+    marks.End(k_ext, s0);
+    ENC_HIP(hipMemcpyAsync(ext.data(), d_ext, out_bytes, hipMemcpyDeviceToHost, s0));
+    ENC_HIP(hipStreamSynchronize(s0));   // (also: `table` was staged)
+    ENC_HIP(hipGetLastError());
+  }
+  // ---- 2. the rectangles and what the headers say
+  EncImageInfo canvas;
+  canvas.xsize = f0.width; canvas.ysize = f0.height;
+  canvas.gray = f0.num_channels < 3; canvas.alpha = !(f0.num_channels & 1); canvas.xyb = !lossless;
+  src0.Describe(canvas);
+  canvas.have_animation = true;
+  canvas.tps_numerator = ao.tps_numerator; canvas.tps_denominator = ao.tps_denominator; canvas.num_loops = ao.num_loops;
+  std::vector<FrameOnCanvas> on((size_t)n);
+  std::vector<JxlHipPixels> crops((size_t)n);
+  enc->anim_rects.resize((size_t)n);
+  for (int k = 0; k < n; k++) {
+    const AnimRect r = AnimFrameRect(k, ao.key_interval, k ? ext[(size_t)k - 1] : AnimExtent{-1, -1, -1, -1}, w, h, lossless);
+    enc->anim_rects[(size_t)k] = r;
+    on[(size_t)k].canvas = canvas;
+    on[(size_t)k].at = AnimPlacement(k, n, r, w, h, durations[k]);
+    JxlHipPixels& c = crops[(size_t)k];
+    c = frames[k];
+    c.data = (const uint8_t*)frames[k].data + (size_t)r.y * frames[k].stride_bytes + (size_t)r.x * pixel_bytes;
+    c.width = (uint32_t)r.w; c.height = (uint32_t)r.h;
+  }
+  // ---- 3. the frames, a chunk at a time
+  enc->files.assign((size_t)n, std::vector<uint8_t>());
+  std::vector<std::pair<const char*, float>> first_stages;
+  marks.Publish(&first_stages);
+  for (int first = 0; first < n;) {
+    int cnt = 0;
+    if (ao.chunk_frames >= 1) {
+      cnt = std::min(ao.chunk_frames, n - first);
+    } else {
+      std::vector<EncBatchItem> items;
+      std::vector<EncImage> ims;
+      EncBatchLayout lay;
+      while (first + cnt < n && cnt < kAnimMaxChunkFrames) {
+        const JxlHipPixels& c = crops[(size_t)(first + cnt)];
+        items.push_back(EncBatchItem{c.width, c.height, c.num_channels, (int32_t)src0.sample_bytes(), lossless ? 1 : 0, 0});
+        ims.resize(items.size());
+        LayEncBatch(items.data(), (int)items.size(), nullptr, ims.data(), &lay);
+        if (cnt > 0 && lay.total_bytes > kAnimWorkspaceBudget) break;
+        cnt++;
+      }
+    }
+    std::vector<BatchJob> jobs((size_t)cnt);
+    for (int j = 0; j < cnt; j++) {
+      BatchJob& job = jobs[(size_t)j];
+      job.index = first + j;
+      job.src = src0;
+      job.src.px = &crops[(size_t)(first + j)];
+      job.opt = opt;
+      job.md = md;
+      job.lossless = lossless;
+      job.on = &on[(size_t)(first + j)];
+    }
+    enc->Run(jobs);
+    first += cnt;
+  }
+  // ---- 4. one codestream: the image header, then every frame; one container
+  BitWriter hdr;
+  WriteCodestreamHeaders(canvas, hdr);
+  const std::vector<uint8_t> head = hdr.Finish();
+  size_t cs_size = head.size();
+  for (auto& f : enc->files) cs_size += f.size();
+  std::vector<uint8_t> file = WriteContainerPrefix(cs_size, md.exif, md.exifSize, md.xmp, md.xmpSize);
+  file.reserve(file.size() + cs_size);   // the frames are copied once
+  file.insert(file.end(), head.begin(), head.end());
+  for (auto& f : enc->files) { file.insert(file.end(), f.begin(), f.end()); std::vector<uint8_t>().swap(f); }
+  enc->files.assign(1, std::vector<uint8_t>());
+  enc->files[0] = std::move(file);
+  enc->stages.insert(enc->stages.begin(), first_stages.begin(), first_stages.end());   // the extents pass, then the last chunk's stages
+}
+
+}  // namespace
+
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                                   const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                                   const EncoderImageMetadata* metadata, ErrorInfo* err) {
+  if (!enc || !options || !animation) return EncoderStatus_NullParameter;
+  enc->files.clear();
+  enc->stages.clear();
+  enc->anim_rects.clear();
+  EncoderImageMetadata md;
+  memset(&md, 0, sizeof(md));
+  if (metadata) md = *metadata;
+  EncSource src0;
+  // the refusals, on the host, before any device work
+  try {
+    auto refuse = [](const std::string& why) { throw EncFail(EncoderStatus_EncodeError, why); };
+    if (n < 1) refuse("an animation needs at least one frame");
+    if (!frames || !durations) throw EncFail(EncoderStatus_NullParameter, "");
+    if (animation->tps_denominator < 1 || animation->tps_denominator > 1024) refuse("the denominator of the ticks per second must be 1..1024");
+    if (animation->tps_numerator < 1 || animation->tps_numerator > (1u << 30)) refuse("the numerator of the ticks per second must be 1..2^30");
+    for (int k = 0; k < n; k++) {
+      const std::string who = "frame " + std::to_string(k) + ": ";
+      EncSource src;
+      src.px = &frames[k];
+      try {
+        CheckBatchImage(&frames[k], options, &md, src);
+      } catch (const EncFail& e) {
+        throw EncFail(e.status, who + e.what());
+      }
+      if (k == 0) src0 = src;
+      const JxlHipPixels &a = frames[0], &b = frames[k];
+      if (a.width != b.width || a.height != b.height) refuse(who + "its size differs from frame 0's");
+      if (a.num_channels != b.num_channels) refuse(who + "its number of channels differs from frame 0's");
+      if (a.sample_type != b.sample_type) refuse(who + "its sample type differs from frame 0's");
+      if (a.bits_per_sample != b.bits_per_sample) refuse(who + "its bits per sample differ from frame 0's");
+      if (a.colour != b.colour) refuse(who + "its colour profile differs from frame 0's");
+      if (durations[k] == 0) refuse(who + "a duration of 0 ticks (every frame is a displayed image and needs one)");
+    }
+  } catch (const EncFail& e) {
+    if (e.status == EncoderStatus_EncodeError) SetEncErr(err, e.what());
+    return e.status;
+  } catch (...) {
+    return EncoderStatus_EncodeError;
+  }
+  EncoderStatus failed = EncoderStatus_Ok;
+  std::string why;
+  int caller_device = enc->device;
+  (void)hipGetDevice(&caller_device);
+  try {
+    if (caller_device != enc->device) ENC_HIP(hipSetDevice(enc->device));
+    EncodeAnimation(enc, n, frames, durations, *options, *animation, md, src0);
+  } catch (const EncFail& e) {
+    failed = e.status; why = e.what();
+  } catch (const std::bad_alloc&) {
+    failed = EncoderStatus_OutOfMemory;
+  } catch (const std::exception& e) {
+    failed = EncoderStatus_EncodeError; why = e.what();
+  } catch (...) {
+    failed = EncoderStatus_EncodeError;   // never throw across the ABI
+  }
+  if (failed != EncoderStatus_Ok) {
+    enc->WaitAll();
+    (void)hipGetLastError();
+    enc->files.clear();
+    if (failed == EncoderStatus_EncodeError) SetEncErr(err, ("the animation: " + why).c_str());
+  }
+  if (caller_device != enc->device) (void)hipSetDevice(caller_device);
+  return failed;
+}
+
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_rects(JxlHipEncoder* enc, int32_t* xywh, int32_t capacity) {
+  if (!enc) return 0;
+  const int32_t n = (int32_t)enc->anim_rects.size();
+  for (int32_t k = 0; xywh && k < n && k < capacity; k++) {
+    const AnimRect& r = enc->anim_rects[(size_t)k];
+    xywh[4 * k] = r.x; xywh[4 * k + 1] = r.y; xywh[4 * k + 2] = r.w; xywh[4 * k + 3] = r.h;
+  }
+  return n;
 }
 
 extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_result(JxlHipEncoder* enc, int32_t i, const uint8_t** data, size_t* size) {

@@ -418,12 +418,19 @@ void WriteCodestreamHeaders(const EncImageInfo& im, BitWriter& bw) {
     else { bw.U32(WV(32), WV(16), WV(24), WB(6, 1), im.bits); bw.Write(4, im.exp_bits - 1); }   // floats: bits, exponent bits - 1
   };
   bw.Bool(false);                                   // not all_default
-  bw.Bool(im.pq_intensity);                         // extra fields: only the tone mapping of PQ needs them
-  if (im.pq_intensity) {
+  const bool extra = im.pq_intensity || im.have_animation;
+  bw.Bool(extra);                                   // extra fields: only the tone mapping of PQ and an animation need them
+  if (extra) {
     bw.Write(3, 0);                                 // orientation 1
     bw.Bool(false);                                 // no intrinsic size
     bw.Bool(false);                                 // no preview
-    bw.Bool(false);                                 // no animation
+    bw.Bool(im.have_animation);
+    if (im.have_animation) {
+      bw.U32(WV(100), WV(1000), WB(10, 1), WB(30, 1), im.tps_numerator);
+      bw.U32(WV(1), WV(1001), WB(8, 1), WB(10, 1), im.tps_denominator);
+      bw.U32(WV(0), WB(3), WB(16), WB(32), im.num_loops);
+      bw.Bool(false);                               // no timecodes
+    }
   }
   bit_depth();
   // modular_16_bit_buffer_sufficient: true up to 12 bits (YCoCg-R and the predictors stay inside an int16 then), false beyond and
@@ -455,6 +462,7 @@ void WriteCodestreamHeaders(const EncImageInfo& im, BitWriter& bw) {
     bw.Enum(im.transfer);                           // transfer function (sRGB)
     bw.Enum(0);                                     // rendering intent perceptual
   }
+  if (extra && !im.pq_intensity) bw.Bool(true);     // default tone mapping
   if (im.pq_intensity) {
     bw.Bool(false);                                 // tone mapping not all_default
     bw.Write(16, 0x70E2);                           // intensity target 10000 (binary16)
@@ -496,10 +504,28 @@ void WriteFrameHeader(const EncImageInfo& im, const EncFrameInfo& f, BitWriter& 
   if (f.encoding == 1) bw.Write(2, f.group_size_shift);
   if (f.encoding == 0 && im.xyb) { bw.Write(3, f.x_qm_scale); bw.Write(3, f.b_qm_scale); }
   bw.U32(WV(1), WV(2), WV(3), WB(3, 4), 1);   // one pass
-  bw.Bool(false);                             // no crop
-  bw.U32(WV(0), WV(1), WV(2), WB(2, 3), 0);   // blend mode: replace
-  for (size_t i = 0; i < nec; i++) bw.U32(WV(0), WV(1), WV(2), WB(2, 3), 0);
-  bw.Bool(true);                              // is_last
+  const EncFramePlacement& at = f.at;
+  bw.Bool(at.have_crop);
+  bool full = true;                           // the frame covers the canvas
+  if (at.have_crop) {
+    const BitWriter::Dist d[4] = {WB(8), WB(11, 256), WB(14, 2304), WB(30, 18688)};
+    bw.U32(d[0], d[1], d[2], d[3], PackSignedW(at.x0));
+    bw.U32(d[0], d[1], d[2], d[3], PackSignedW(at.y0));
+    bw.U32(d[0], d[1], d[2], d[3], at.width);
+    bw.U32(d[0], d[1], d[2], d[3], at.height);
+    full = at.x0 <= 0 && at.y0 <= 0 && (int64_t)at.x0 + at.width >= im.xsize && (int64_t)at.y0 + at.height >= im.ysize;
+  }
+  for (size_t i = 0; i < 1 + nec; i++) {
+    bw.U32(WV(0), WV(1), WV(2), WB(2, 3), 0);   // blend mode: replace
+    if (!full) bw.Write(2, at.source);          // what shows around the crop
+  }
+  if (im.have_animation) bw.U32(WV(0), WV(1), WB(8), WB(32), at.duration);
+  bw.Bool(at.is_last);
+  if (!at.is_last) {
+    bw.Write(2, at.save_as_reference);
+    // a full replace frame that can be referenced says whether it is saved before the colour transform: never
+    if (full && (at.duration == 0 || !im.have_animation || at.save_as_reference != 0)) bw.Bool(false);
+  }
   bw.U32(WV(0), WB(4), WB(5, 16), WB(10, 48), 0);   // no name
   // loop filter
   const bool lf_default = f.gab && f.epf_iters == 2;
@@ -526,14 +552,13 @@ void WriteToc(const std::vector<uint32_t>& sizes, BitWriter& bw) {
   bw.AlignByte();
 }
 
-std::vector<uint8_t> WriteContainer(const std::vector<uint8_t>& cs, const uint8_t* exif, size_t exif_size, const uint8_t* xmp,
-                                    size_t xmp_size) {
+std::vector<uint8_t> WriteContainerPrefix(size_t cs_size, const uint8_t* exif, size_t exif_size, const uint8_t* xmp, size_t xmp_size) {
   static const uint8_t kSig[12] = {0, 0, 0, 0xC, 'J', 'X', 'L', ' ', 0xD, 0xA, 0x87, 0xA};
   static const uint8_t kFtyp[20] = {0, 0, 0, 0x14, 'f', 't', 'y', 'p', 'j', 'x', 'l', ' ', 0, 0, 0, 0, 'j', 'x', 'l', ' '};
   std::vector<uint8_t> out(kSig, kSig + 12);
   out.insert(out.end(), kFtyp, kFtyp + 20);
   auto be32 = [&](uint32_t v) { out.push_back(v >> 24); out.push_back(v >> 16); out.push_back(v >> 8); out.push_back(v); };
-  auto box = [&](const char* type, const uint8_t* p, size_t n) {
+  auto box_header = [&](const char* type, size_t n) {
     if (n + 8 > 0xFFFFFFFFull) {
       be32(1);
       out.insert(out.end(), type, type + 4);
@@ -543,11 +568,17 @@ std::vector<uint8_t> WriteContainer(const std::vector<uint8_t>& cs, const uint8_
       be32((uint32_t)(n + 8));
       out.insert(out.end(), type, type + 4);
     }
-    out.insert(out.end(), p, p + n);
   };
-  if (exif && exif_size) box("Exif", exif, exif_size);
-  if (xmp && xmp_size) box("xml ", xmp, xmp_size);
-  box("jxlc", cs.data(), cs.size());
+  if (exif && exif_size) { box_header("Exif", exif_size); out.insert(out.end(), exif, exif + exif_size); }
+  if (xmp && xmp_size) { box_header("xml ", xmp_size); out.insert(out.end(), xmp, xmp + xmp_size); }
+  box_header("jxlc", cs_size);
+  return out;
+}
+
+std::vector<uint8_t> WriteContainer(const std::vector<uint8_t>& cs, const uint8_t* exif, size_t exif_size, const uint8_t* xmp,
+                                    size_t xmp_size) {
+  std::vector<uint8_t> out = WriteContainerPrefix(cs.size(), exif, exif_size, xmp, xmp_size);
+  out.insert(out.end(), cs.begin(), cs.end());
   return out;
 }
 

@@ -82,6 +82,21 @@ struct EncImageInfo {
   uint32_t primaries = 1;  // the format's enum: 1 sRGB, 9 BT.2100 (= BT.2020), 11 P3; white point D65 always; ignored for gray
   uint32_t transfer = 13;  // the format's enum: 1 BT.709, 8 linear, 13 sRGB, 16 PQ
   bool pq_intensity = false;   // tone mapping: intensity target 10000 (the other fields at their defaults) instead of the default 255
+  // animation header (jxlhip_encode_animation; every other writer keeps have_animation false): ticks per second = tps_numerator /
+  // tps_denominator, num_loops 0 = endless; no timecodes
+  bool have_animation = false;
+  uint32_t tps_numerator = 100, tps_denominator = 1, num_loops = 0;
+};
+// Where a frame lies on the canvas and what becomes of it (the frames of an animation; the defaults are a still's only frame: the
+// whole canvas, the last frame).  Both blending infos (colour, alpha) are kReplace with `source` as their slot.
+struct EncFramePlacement {
+  bool have_crop = false;
+  int32_t x0 = 0, y0 = 0;             // of the crop on the canvas
+  uint32_t width = 0, height = 0;     // of the crop = of the frame
+  uint32_t duration = 0;              // ticks; written only under an animation header
+  bool is_last = true;
+  uint32_t save_as_reference = 0;     // slot 0..3; written for every frame but the last
+  uint32_t source = 0;                // slot a crop smaller than the canvas shows around itself
 };
 struct EncFrameInfo {
   uint32_t encoding = 0;           // 0 VarDCT, 1 Modular
@@ -90,13 +105,17 @@ struct EncFrameInfo {
   bool gab = true;
   uint32_t epf_iters = 1;
   uint64_t flags = 0;
+  EncFramePlacement at;
 };
 void WriteCodestreamHeaders(const EncImageInfo& im, BitWriter& bw);   // signature, SizeHeader, ImageMetadata; byte-aligned at the end
-void WriteFrameHeader(const EncImageInfo& im, const EncFrameInfo& f, BitWriter& bw);
+void WriteFrameHeader(const EncImageInfo& im, const EncFrameInfo& f, BitWriter& bw);   // im: the canvas (a still: the frame itself)
 void WriteToc(const std::vector<uint32_t>& sizes, BitWriter& bw);
 // ISO BMFF container (18181-2): signature, ftyp, Exif, xml, jxlc.  exif already carries its 4-byte TIFF offset prefix.
 std::vector<uint8_t> WriteContainer(const std::vector<uint8_t>& codestream, const uint8_t* exif, size_t exif_size, const uint8_t* xmp,
                                     size_t xmp_size);
+
+// The container up to and including the header of the jxlc box, for a codestream of cs_size bytes that the caller appends itself.
+std::vector<uint8_t> WriteContainerPrefix(size_t cs_size, const uint8_t* exif, size_t exif_size, const uint8_t* xmp, size_t xmp_size);
 
 // exported by host_parse.cc: the decoder's alias-table construction (the encoder inverts exactly this table)
 void BuildAliasTable(const std::vector<int>& counts, uint32_t log_alpha, uint64_t* out);

@@ -10,6 +10,7 @@
 #include "../../include/jxlfiletypeio.h"
 #include "animation.h"
 #include "dev_util.h"
+#include "enc_animation.h"
 #include "enc_types.h"
 #include "batch_layout.h"
 #include "enc_batch_layout.h"
@@ -884,4 +885,50 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_animation_plan(const uint8_t
     SetEncErr(err, e.what());
   }
   return 0;
+}
+
+// ---- animation encode (enc_animation.h, host_write.h): headers and geometry rules, host only
+
+// A bare codestream of the image header and one frame header as the encoder writes them, then the first bit of a TOC (not permuted)
+// and the padding to a byte.  in[0..20]: xsize, ysize, gray, alpha, lossless, have_animation, tps_numerator, tps_denominator,
+// num_loops, have_crop, x0, y0, crop width, crop height, duration, is_last, save_as_reference, source, bits, exp_bits, epf_iters.
+// With have_animation = have_crop = 0, is_last = 1 and the rest of the placement 0 these are the fields' defaults.
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_animation_headers(const int64_t* in, uint8_t* dst, size_t capacity) {
+  try {
+    EncImageInfo ii;
+    ii.xsize = (uint32_t)in[0]; ii.ysize = (uint32_t)in[1]; ii.gray = in[2] != 0; ii.alpha = in[3] != 0; ii.xyb = !in[4];
+    ii.bits = (uint32_t)in[18]; ii.exp_bits = (uint32_t)in[19];
+    if (in[5]) { ii.have_animation = true; ii.tps_numerator = (uint32_t)in[6]; ii.tps_denominator = (uint32_t)in[7]; ii.num_loops = (uint32_t)in[8]; }
+    EncFrameInfo fi;
+    fi.encoding = in[4] ? 1 : 0;
+    fi.gab = !in[4]; fi.epf_iters = in[4] ? 0 : (uint32_t)in[20];
+    fi.at.have_crop = in[9] != 0;
+    fi.at.x0 = (int32_t)in[10]; fi.at.y0 = (int32_t)in[11]; fi.at.width = (uint32_t)in[12]; fi.at.height = (uint32_t)in[13];
+    fi.at.duration = (uint32_t)in[14]; fi.at.is_last = in[15] != 0; fi.at.save_as_reference = (uint32_t)in[16]; fi.at.source = (uint32_t)in[17];
+    BitWriter cs;
+    WriteCodestreamHeaders(ii, cs);
+    WriteFrameHeader(ii, fi, cs);
+    cs.Bool(false);
+    std::vector<uint8_t> bytes = cs.Finish();
+    if (bytes.size() > capacity) return 0;
+    memcpy(dst, bytes.data(), bytes.size());
+    return bytes.size();
+  } catch (...) {
+    return 0;
+  }
+}
+
+// The rectangles and placements of n frames on a w x h canvas.  extents: 4 ints (x0, y0, x1, y1; inclusive; x1 < 0: nothing changed)
+// per pair, n - 1 of them.  out, 9 ints per frame: x, y, width, height, have_crop, duration, is_last, save_as_reference, source.
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_animation_rects(int32_t n, const int32_t* extents, const uint32_t* durations, int32_t w, int32_t h,
+                                                                  int32_t lossless, int32_t key_interval, int32_t* out) {
+  for (int32_t k = 0; k < n; k++) {
+    const AnimExtent e = k ? AnimExtent{extents[4 * (k - 1)], extents[4 * (k - 1) + 1], extents[4 * (k - 1) + 2], extents[4 * (k - 1) + 3]} : AnimExtent{-1, -1, -1, -1};
+    const AnimRect r = AnimFrameRect(k, key_interval, e, w, h, lossless != 0);
+    const EncFramePlacement at = AnimPlacement(k, n, r, w, h, durations[k]);
+    int32_t* o = out + 9 * k;
+    o[0] = r.x; o[1] = r.y; o[2] = r.w; o[3] = r.h;
+    o[4] = at.have_crop; o[5] = (int32_t)at.duration; o[6] = at.is_last; o[7] = (int32_t)at.save_as_reference; o[8] = (int32_t)at.source;
+    if (at.have_crop && (at.x0 != r.x || at.y0 != r.y || (int32_t)at.width != r.w || (int32_t)at.height != r.h)) o[4] = -1;
+  }
 }
