@@ -20,7 +20,8 @@
  *
  * Part 5 (jxlhip_animation_*) decodes every displayed image of an animated file into device memory, in file order.
  *
- * Part 6 (jxlhip_encode_animation) encodes a stack of device-resident frames as one animated file: each frame as what changed.
+ * Part 6 (jxlhip_encode_animation, jxlhip_encode_animation_rects) encodes a stack of device-resident frames as one animated file: each
+ * frame as what changed, in one rectangle or in several.
  */
 #ifndef JXLFILETYPEIO_H_
 #define JXLFILETYPEIO_H_
@@ -414,10 +415,42 @@ JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder* enc, int3
  * `capacity` frames are written to xywh.  Returns the number of frames (0: none). */
 JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_rects(JxlHipEncoder* enc, int32_t* xywh, int32_t capacity);
 
+/* Several rectangles per frame.  A frame that changed in two far-apart places has a bounding box as large as the canvas; with
+ * max_rects >= 2 what changed is measured per 64 x 64-pixel tile instead, and a frame that is no key frame is written as up to
+ * max_rects pairwise disjoint rectangles that together cover every changed pixel: the 8-connected groups of changed tiles, their
+ * boxes (lossy: on the 8-pixel grid) merged where they overlap, then the cheapest pair - the one whose common box adds the fewest
+ * pixels - merged while there are more than max_rects or while that costs at most merge_pixels (DESIGN.md §2 "Animation encode"
+ * states the rule in full).  A frame with m rectangles is m frames of the codestream, each replacing its part of slot 1: the first
+ * m - 1 have duration 0, so that a decoder composes them into the displayed image that the last, with the frame's duration, ends.
+ * The file still has one displayed image per input frame.  chunk_frames and its limits count codestream frames. */
+typedef struct JxlHipAnimationRectOptions {
+  int32_t max_rects;     /* 1: one rectangle per frame, byte for byte jxlhip_encode_animation; 2..16: up to this many */
+  int32_t merge_pixels;  /* two rectangles become one when that codes at most this many pixels more; >= 0 */
+} JxlHipAnimationRectOptions;
+
+/* jxlhip_encode_animation with `rects` (jxlhip_encode_animation is this call with {1, 0}).  Refused in addition, on the host and in
+ * words: max_rects outside 1..16 and a negative merge_pixels. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                              const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                              const JxlHipAnimationRectOptions* rects, const EncoderImageMetadata* metadata,
+                                                              ErrorInfo* err);
+
+/* The codestream frames of the last animation that got as far as measuring: input frame, x, y, width, height per codestream frame, in
+ * file order; up to `capacity` of them are written to kxywh.  Returns their number.  (jxlhip_encoder_animation_rects keeps reporting
+ * one rectangle per input frame: the bounding box of the frame's rectangles, the same value for every max_rects.) */
+JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_frame_rects(JxlHipEncoder* enc, int32_t* kxywh, int32_t capacity);
+
+/* The tile table of pair `pair` (frames pair and pair + 1) of the last animation encoded with max_rects >= 2: one word per 64 x 64 tile,
+ * row-major over ceil(width / 64) x ceil(height / 64) tiles, holding the bytes x0, y0, x1, y1 (lowest first; inclusive, relative to the
+ * tile's origin) of the box of the changed pixels in the tile, 0xFFFFFFFF where none changed.  Up to `capacity` words are written to
+ * dst.  Returns the number of tiles (0: no such pair, or max_rects was 1). */
+JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_tiles(JxlHipEncoder* enc, int32_t pair, uint32_t* dst, int32_t capacity);
+
 #ifdef __cplusplus
 }
 static_assert(sizeof(JxlHipPixels) == 40, "JxlHipPixels layout");
 static_assert(sizeof(JxlHipAnimationOptions) == 20, "JxlHipAnimationOptions layout");
+static_assert(sizeof(JxlHipAnimationRectOptions) == 8, "JxlHipAnimationRectOptions layout");
 static_assert(sizeof(JxlHipAnimationInfo) == 64, "JxlHipAnimationInfo layout");
 static_assert(sizeof(JxlHipAnimationFrame) == 1096, "JxlHipAnimationFrame layout");
 static_assert(sizeof(BitmapData) == 24, "BitmapData layout");

@@ -81,6 +81,10 @@ class AnimationOptions(C.Structure):
                 ("chunk_frames", C.c_int32)]
 
 
+class AnimationRectOptions(C.Structure):
+    _fields_ = [("max_rects", C.c_int32), ("merge_pixels", C.c_int32)]
+
+
 class AnimationInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("num_channels", C.c_int32), ("has_alpha", C.c_int32),
                 ("bytes_per_sample", C.c_int32), ("float_samples", C.c_int32), ("bits_per_sample", C.c_int32), ("have_animation", C.c_int32),
@@ -97,7 +101,8 @@ EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jx
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
            "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
-           "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_encode_animation", "jxlhip_encoder_animation_rects", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
+           "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_encode_animation", "jxlhip_encoder_animation_rects", "jxlhip_encode_animation_rects",
+           "jxlhip_encoder_animation_frame_rects", "jxlhip_encoder_animation_tiles", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
            "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder"]
 
 _lib = None
@@ -199,6 +204,14 @@ def lib(build_if_missing=True):
                                           C.POINTER(AnimationOptions), C.POINTER(EncoderImageMetadata), C.POINTER(ErrorInfo)]
     L.jxlhip_encoder_animation_rects.restype = C.c_int32
     L.jxlhip_encoder_animation_rects.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    L.jxlhip_encode_animation_rects.restype = C.c_int32
+    L.jxlhip_encode_animation_rects.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(C.c_uint32), C.POINTER(EncoderOptions),
+                                                C.POINTER(AnimationOptions), C.POINTER(AnimationRectOptions), C.POINTER(EncoderImageMetadata),
+                                                C.POINTER(ErrorInfo)]
+    L.jxlhip_encoder_animation_frame_rects.restype = C.c_int32
+    L.jxlhip_encoder_animation_frame_rects.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    L.jxlhip_encoder_animation_tiles.restype = C.c_int32
+    L.jxlhip_encoder_animation_tiles.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int32]
     L.jxlhip_animation_open.restype = C.c_void_p
     L.jxlhip_animation_open.argtypes = [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(AnimationInfo), C.POINTER(ErrorInfo)]
     L.jxlhip_animation_close.restype = None
@@ -678,13 +691,17 @@ class Encoder:
         return out
 
     def encode_animation(self, frames, durations, tps=(100, 1), loops=0, key_interval=0, chunk_frames=0, distance=1.0, effort=7,
-                         lossless=False, colour=None, bits=None, exif=None, xmp=None):
-        """jxlhip_encode_animation: the frames as ONE animated file (bytes).  frames: a list of EncodeItem / GPU tensors (h, w[, c]), or
+                         lossless=False, colour=None, bits=None, exif=None, xmp=None, max_rects=1, merge_pixels=4096):
+        """jxlhip_encode_animation_rects: the frames as ONE animated file (bytes).  frames: a list of EncodeItem / GPU tensors (h, w[, c]), or
         one GPU tensor [n, h, w, c]; all of one size, channel count and sample type.  durations: ticks per frame (>= 1), one per frame
         or one number for all; tps: ticks per second as (numerator, denominator); loops: 0 = endless.  Frame 0 - and with
         key_interval >= 1 every key_interval-th frame - is written whole, every other frame as the rectangle that changed against its
         predecessor (lossy: grown to multiples of 8 pixels), a frame that changed nothing as one pixel; last_animation_rects has
-        them.  chunk_frames: frames that go through the encoder at a time (0: by its workspace budget; the bytes do not depend on it).
+        them.  max_rects >= 2 (up to 16): what changed is measured per 64 x 64 tile and such a frame is written as up to max_rects
+        disjoint rectangles - the groups of touching changed tiles, merged while there are too many or while merging two codes at
+        most merge_pixels pixels more - each a frame of the codestream, all but the last without a duration;
+        last_animation_frame_rects has them, last_animation_tiles(pair) the tile map.  max_rects = 1 is jxlhip_encode_animation byte
+        for byte (merge_pixels plays no part).  chunk_frames: codestream frames that go through the encoder at a time (0: by its workspace budget; the bytes do not depend on it).
         distance, effort, lossless hold for every frame; colour and bits default to those of the first EncodeItem (tensors: "Srgb",
         8 / 16 bits).  Raises JxlError where the call is refused or fails; the encoder stays usable."""
         if hasattr(frames, "dim") and not isinstance(frames, (list, tuple)):
@@ -705,7 +722,8 @@ class Encoder:
         bufs = [np.frombuffer(b, np.uint8) if b else None for b in (exif, None, xmp)]
         md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in bufs), []))
         err = ErrorInfo()
-        r = self._L.jxlhip_encode_animation(self._h, n, px, dur, C.byref(opt), C.byref(ao), C.byref(md), C.byref(err))
+        ro = AnimationRectOptions(int(max_rects), int(merge_pixels))
+        r = self._L.jxlhip_encode_animation_rects(self._h, n, px, dur, C.byref(opt), C.byref(ao), C.byref(ro), C.byref(md), C.byref(err))
         self.last_error = err.errorMessage.decode("ascii", "replace")
         if r != 0:
             raise JxlError(ENCODER_STATUS[r] if 0 <= r < len(ENCODER_STATUS) else str(r), self.last_error)
@@ -721,6 +739,28 @@ class Encoder:
         buf = (C.c_int32 * (4 * max(n, 1)))()
         self._L.jxlhip_encoder_animation_rects(self._h, buf, n)
         return [tuple(buf[4 * k:4 * k + 4]) for k in range(n)]
+
+    @property
+    def last_animation_frame_rects(self):
+        """[(input frame, x, y, width, height)] per codestream frame of the last encode_animation, in file order: a frame written as m
+        rectangles appears m times."""
+        n = self._L.jxlhip_encoder_animation_frame_rects(self._h, None, 0)
+        buf = (C.c_int32 * (5 * max(n, 1)))()
+        self._L.jxlhip_encoder_animation_frame_rects(self._h, buf, n)
+        return [tuple(buf[5 * c:5 * c + 5]) for c in range(n)]
+
+    def last_animation_tiles(self, pair):
+        """The tile map of frames `pair` and `pair + 1` of the last encode_animation with max_rects >= 2: a (tiles down, tiles across,
+        4) uint8 array of x0, y0, x1, y1 - the inclusive box, relative to the tile, of the changed pixels in each 64 x 64 tile - with
+        255 everywhere for a tile in which nothing changed.  Raises ValueError where there is no such pair."""
+        n = self._L.jxlhip_encoder_animation_tiles(self._h, int(pair), None, 0)
+        if n == 0:
+            raise ValueError("no tile map for pair %d: the last animation has no such pair or was encoded with max_rects = 1" % pair)
+        buf = np.zeros(n, np.uint32)
+        self._L.jxlhip_encoder_animation_tiles(self._h, int(pair), buf.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+        rects = self.last_animation_rects
+        w, h = rects[0][2], rects[0][3]                       # frame 0 is the canvas
+        return buf.view(np.uint8).reshape((h + 63) // 64, (w + 63) // 64, 4)
 
     def stage_times(self):
         """{stage: ms} of the last batch: device time per kernel group (stages on different streams overlap), then the host's stages

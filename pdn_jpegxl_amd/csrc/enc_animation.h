@@ -1,8 +1,10 @@
 // Animation encode: what a frame of an animation covers and what its header says, decided on the host from the
-// change extents that enc_animation_kernels.hip measures.  Host-only and stated once: the encoder (encoder.cc) and the test library
+// change extents - or, for several rectangles per frame, the tile change map - that enc_animation_kernels.hip measures.  Host-only
+// and stated once: the encoder (encoder.cc) and the test library
 // (selftest.cc) both go through these functions.
 #pragma once
 #include <cstdint>
+#include <vector>
 #include "host_write.h"
 
 namespace jxlhip {
@@ -38,5 +40,41 @@ EncFramePlacement AnimPlacement(int32_t k, int32_t n, const AnimRect& r, int32_t
 // enc_animation_kernels.hip: the extents of the npairs = n - 1 consecutive pairs of `frames` (device array of n) into `out` (device,
 // npairs, every byte 0xFF beforehand), one launch.  Rows are row_bytes bytes of pixel_bytes-byte pixels.
 void LaunchAnimExtents(const AnimFrameSrc* frames, int32_t npairs, int32_t h, uint64_t row_bytes, uint32_t pixel_bytes, AnimExtent* out, void* stream);
+
+// ---- several rectangles per frame (max_rects >= 2): a change map per 64 x 64-pixel tile instead of one box per pair
+
+constexpr int32_t kAnimTile = 64;                    // pixels a tile is wide and high (ragged at the right and bottom edges)
+constexpr uint32_t kAnimTileEmpty = 0xFFFFFFFFu;     // the word of a tile in which nothing differs
+constexpr int32_t kAnimMaxRects = 16;                // the largest max_rects
+constexpr int32_t kAnimMaxComponents = 64;           // more boxes than this after the closure: the frame is its one bounding box
+inline uint32_t AnimTilesAcross(int32_t pixels) { return (uint32_t)(((int64_t)pixels + kAnimTile - 1) / kAnimTile); }
+
+// A tile's word: the bytes x0, y0, x1, y1 (lowest first) of the inclusive box of the pixels of the tile of which some sample differs,
+// relative to the tile's origin, each 0 .. 63; kAnimTileEmpty: none does.
+inline uint32_t AnimTileWord(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) { return x0 | y0 << 8 | x1 << 16 | y1 << 24; }
+
+// What changed over the whole canvas, from the tile table of a pair (AnimTilesAcross(w) x AnimTilesAcross(h) words, row-major): the value
+// anim_extents_kernel leaves for the pair.
+AnimExtent AnimTilesExtent(const uint32_t* tiles, int32_t w, int32_t h);
+
+// The rectangles a frame that is no key frame is written as, from the tile table of its pair: at most max_rects (2 .. kAnimMaxRects),
+// pairwise disjoint, together covering every changed pixel, in (y, x) order.  The rule (DESIGN.md §2 "Animation encode"):
+//  1. no tile is non-empty: the 1 x 1 rectangle at (0, 0);
+//  2. the 8-connected components of the non-empty tiles; a component's box is the union of its tiles' pixel boxes, for lossy grown to
+//     multiples of 8 and clipped to the canvas as AnimFrameRect does;
+//  3. closure: while two boxes share a pixel they are replaced by their bounding box;
+//  4. more than kAnimMaxComponents boxes: the frame is its one bounding box (what max_rects = 1 writes);
+//  5. boxes sorted by (y, x); while there are more than max_rects, or at least two and the cheapest pair costs at most merge_pixels:
+//     the cheapest pair - cost = area(bounding box) - area(A) - area(B), ties to the smallest (index, index) - is replaced by its
+//     bounding box, then the closure again and the order again.
+std::vector<AnimRect> AnimFrameRects(const uint32_t* tiles, int32_t w, int32_t h, bool lossless, int32_t max_rects, int64_t merge_pixels);
+
+// Why a call with these max_rects and merge_pixels is refused, in words; nullptr: it is not.
+const char* AnimRectOptionsRefusal(int32_t max_rects, int32_t merge_pixels);
+
+// enc_animation_kernels.hip: the tile tables of the npairs = n - 1 consecutive pairs of `frames` (device array of n) into `out` (device,
+// npairs x AnimTilesAcross(h) x AnimTilesAcross(w) words; every word is written, nothing need be set beforehand), one launch.  Rows are
+// w pixels of pixel_bytes (1 .. 16) bytes.
+void LaunchAnimTiles(const AnimFrameSrc* frames, int32_t npairs, int32_t w, int32_t h, uint32_t pixel_bytes, uint32_t* out, void* stream);
 
 }  // namespace jxlhip

@@ -1,4 +1,5 @@
-// HIP kernel (gfx950) of animation encode: what changed between consecutive frames.
+// HIP kernels (gfx950) of animation encode: what changed between consecutive frames - as one box per pair
+// (anim_extents_kernel, max_rects = 1) or as a box per pair and 64 x 64 tile (anim_tiles_kernel, further down, max_rects >= 2).
 //
 // anim_extents_kernel: for every pair (frame k - 1, frame k) the bounding box of the samples whose BITS differ (+0.0 and -0.0 differ,
 // equal NaN patterns do not, a changed alpha sample counts like any other).  It reads the caller's memory as it lies: any base
@@ -123,7 +124,130 @@ __global__ __launch_bounds__(kExtThreads) void anim_extents_kernel(const AnimFra
   }
 }
 
+// ---- anim_tiles_kernel: the same measurement per 64 x 64-pixel tile of the canvas, for max_rects >= 2 (enc_animation.h: AnimFrameRects).
+//
+// One launch, grid = pairs x tile rows x column groups.  A workgroup owns one tile row (up to 64 canvas rows) of a group of whole tile
+// columns; a lane owns the 16-byte chunk [16 c, 16 c + 16) of a row, counted from the ROW'S START, and walks down the rows, eight rows
+// of both frames loaded before any is looked at.  A tile is 64 pixel_bytes bytes wide - a multiple of 16 for every pixel size - so tile
+// boundaries are chunk boundaries and a chunk lies in exactly one tile: the lane keeps one (first byte, last byte, first row, last row)
+// in registers, relative to its tile.  A row step of a wavefront is one contiguous 1 KB read per frame, aligned when the caller's rows
+// are.  The chunk that the end of the row cuts is loaded as the LAST 16 bytes of the row and the bytes in front of the chunk are masked
+// off (rows shorter than 16 bytes: a byte at a time, by one thread): no byte outside a row is loaded.  At the end the lanes that saw a
+// difference fold into an LDS table of the band's tiles (four LDS atomics each), and one thread per tile stores the packed word:
+// every word of the table is written, by exactly one workgroup, with a plain store - no global atomics, no memset beforehand.
+constexpr int kTileThreads = 256, kTileRowsInFlight = 8;
+
+struct TileAcc {
+  uint32_t lo = 0xFFFFFFFFu, hi = 0, y0 = 0xFFFFFFFFu, y1 = 0;   // bytes relative to the tile's first, rows to its first; lo > hi: nothing seen
+  __device__ __forceinline__ void Mark(uint32_t first, uint32_t last, uint32_t y) {
+    lo = first < lo ? first : lo;
+    hi = last > hi ? last : hi;
+    y0 = y < y0 ? y : y0;
+    y1 = y > y1 ? y : y1;
+  }
+};
+
+// The 16 bytes a and b were loaded from byte `base` of their tile (base + skip: the chunk's first byte; the `skip` bytes in front of it
+// belong to the chunk before and are ignored).
+__device__ __forceinline__ void MarkTileChunk(const uint4& a, const uint4& b, uint32_t base, uint32_t skip, uint32_t y, TileAcc& acc) {
+  uint32_t d[4] = {a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w};
+  if ((d[0] | d[1] | d[2] | d[3]) == 0) return;
+  if (skip) {
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+      if (4 * i + 4 <= skip) d[i] = 0;
+      else if (4 * i < skip) d[i] &= ~0u << (8 * (skip - 4 * i));
+    }
+    if ((d[0] | d[1] | d[2] | d[3]) == 0) return;
+  }
+  const uint32_t first = d[0] ? FirstByte(d[0]) : (d[1] ? 4 + FirstByte(d[1]) : (d[2] ? 8 + FirstByte(d[2]) : 12 + FirstByte(d[3])));
+  const uint32_t last = d[3] ? 12 + LastByte(d[3]) : (d[2] ? 8 + LastByte(d[2]) : (d[1] ? 4 + LastByte(d[1]) : LastByte(d[0])));
+  acc.Mark(base + first, base + last, y);
+}
+
+__global__ __launch_bounds__(kTileThreads) void anim_tiles_kernel(const AnimFrameSrc* __restrict__ frames, int32_t h, uint64_t row_bytes, uint32_t pixel_bytes,
+                                                                  uint32_t tiles_x, uint32_t tiles_y, uint32_t group_tiles, uint32_t groups,
+                                                                  uint32_t* __restrict__ out) {
+  const uint32_t group = blockIdx.x % groups, ty = (blockIdx.x / groups) % tiles_y, pair = blockIdx.x / groups / tiles_y;
+  const AnimFrameSrc fa = frames[pair], fb = frames[pair + 1];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t tile_chunks = 4 * pixel_bytes;                  // 64 pixel_bytes / 16
+  const uint32_t local = tid / tile_chunks;                      // the lane's tile within the group; >= group_tiles: the lane idles
+  const uint64_t chunk = (uint64_t)group * group_tiles * tile_chunks + tid;
+  const uint32_t rows = (uint32_t)std::min<int64_t>(kAnimTile, (int64_t)h - (int64_t)ty * kAnimTile);
+  __shared__ uint32_t table[kTileThreads / 4][4];                // per tile of the group: first byte, first row (min), last byte, last row (max)
+  if (tid < kTileThreads / 4) { table[tid][0] = 0xFFFFFFFFu; table[tid][1] = 0xFFFFFFFFu; table[tid][2] = 0; table[tid][3] = 0; }
+  __syncthreads();
+  TileAcc acc;
+  const int64_t row0 = (int64_t)ty * kAnimTile;
+  if (row_bytes < 16) {
+    // a row of fewer than 16 bytes (one tile column, at most 15 pixels wide): a byte at a time
+    if (group == 0 && tid == 0) {
+      for (uint32_t y = 0; y < rows; y++) {
+        const uint8_t* a = fa.data + (row0 + y) * fa.stride;
+        const uint8_t* b = fb.data + (row0 + y) * fb.stride;
+        for (uint32_t i = 0; i < (uint32_t)row_bytes; i++)
+          if (a[i] != b[i]) acc.Mark(i, i, y);
+      }
+    }
+  } else if (local < group_tiles && 16 * chunk < row_bytes) {
+    // where the lane loads: its chunk, or - the chunk the row's end cuts - the last 16 bytes of the row, `skip` bytes earlier
+    const uint64_t at = std::min<uint64_t>(16 * chunk, row_bytes - 16);
+    const uint32_t skip = (uint32_t)(16 * chunk - at);
+    const uint32_t base = (tid % tile_chunks) * 16 - skip;       // of the load within the tile (mod 2^32 where skip reaches back; first >= skip mends it)
+    const uint8_t* a = fa.data + row0 * fa.stride + at;
+    const uint8_t* b = fb.data + row0 * fb.stride + at;
+    uint32_t y = 0;
+    for (; y + kTileRowsInFlight <= rows; y += kTileRowsInFlight) {
+      uint4 va[kTileRowsInFlight], vb[kTileRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kTileRowsInFlight; r++) {
+        va[r] = LoadUnaligned(a + (int64_t)r * fa.stride);
+        vb[r] = LoadUnaligned(b + (int64_t)r * fb.stride);
+      }
+#pragma unroll
+      for (int r = 0; r < kTileRowsInFlight; r++) MarkTileChunk(va[r], vb[r], base, skip, y + r, acc);
+      a += (int64_t)kTileRowsInFlight * fa.stride;
+      b += (int64_t)kTileRowsInFlight * fb.stride;
+    }
+    for (; y < rows; y++) {
+      MarkTileChunk(LoadUnaligned(a), LoadUnaligned(b), base, skip, y, acc);
+      a += fa.stride;
+      b += fb.stride;
+    }
+  }
+  if (acc.lo <= acc.hi) {
+    const uint32_t t = row_bytes < 16 ? 0 : local;
+    atomicMin(&table[t][0], acc.lo);
+    atomicMin(&table[t][1], acc.y0);
+    atomicMax(&table[t][2], acc.hi);
+    atomicMax(&table[t][3], acc.y1);
+  }
+  __syncthreads();
+  const uint64_t tx = (uint64_t)group * group_tiles + tid;
+  if (tid < group_tiles && tx < tiles_x) {
+    uint32_t word = kAnimTileEmpty;
+    if (table[tid][0] != 0xFFFFFFFFu) word = table[tid][0] / pixel_bytes | table[tid][1] << 8 | (table[tid][2] / pixel_bytes) << 16 | table[tid][3] << 24;
+    out[((uint64_t)pair * tiles_y + ty) * tiles_x + tx] = word;
+  }
+}
+
 }  // namespace
+
+void LaunchAnimTiles(const AnimFrameSrc* frames, int32_t npairs, int32_t w, int32_t h, uint32_t pixel_bytes, uint32_t* out, void* stream) {
+  if (npairs <= 0 || w <= 0 || h <= 0 || pixel_bytes < 1 || pixel_bytes > 16) return;
+  const uint32_t tiles_x = AnimTilesAcross(w), tiles_y = AnimTilesAcross(h);
+  const uint32_t group_tiles = (kTileThreads / 4) / pixel_bytes;           // whole tiles of 4 pixel_bytes chunks that 256 lanes hold: 64 .. 4
+  const uint32_t groups = (tiles_x + group_tiles - 1) / group_tiles;
+  // one launch, unless the grid would pass 2^30 workgroups: then some pairs at a time
+  const int64_t per_pair = (int64_t)tiles_y * groups;
+  const int32_t pairs_per_launch = (int32_t)std::max<int64_t>(1, std::min<int64_t>(npairs, ((int64_t)1 << 30) / per_pair));
+  for (int32_t p = 0; p < npairs; p += pairs_per_launch) {
+    const int32_t cnt = std::min(pairs_per_launch, npairs - p);
+    hipLaunchKernelGGL(anim_tiles_kernel, dim3((uint32_t)(cnt * per_pair)), dim3(kTileThreads), 0, (hipStream_t)stream, frames + p, h,
+                       (uint64_t)w * pixel_bytes, pixel_bytes, tiles_x, tiles_y, group_tiles, groups, out + (size_t)p * tiles_x * tiles_y);
+  }
+}
 
 void LaunchAnimExtents(const AnimFrameSrc* frames, int32_t npairs, int32_t h, uint64_t row_bytes, uint32_t pixel_bytes, AnimExtent* out, void* stream) {
   if (npairs <= 0 || h <= 0) return;

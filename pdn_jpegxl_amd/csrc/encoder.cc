@@ -1406,7 +1406,11 @@ struct JxlHipEncoder {
   std::vector<std::vector<uint8_t>> files;   // the results of the last batch
   std::vector<std::pair<const char*, float>> stages;
   DeviceBuffer anim;                         // animation encode: the frame table and the extents of the pairs
-  std::vector<AnimRect> anim_rects;          // the rectangles of the last animation
+  std::vector<AnimRect> anim_rects;          // the rectangles of the last animation: per input frame, the bounding box of what it wrote
+  struct AnimPart { int32_t k; AnimRect r; };
+  std::vector<AnimPart> anim_parts;          // ... per codestream frame: the input frame it belongs to and its rectangle
+  std::vector<uint32_t> anim_tiles;          // ... and, with max_rects >= 2, the tile tables of its pairs (anim_tiles_per_pair words each)
+  size_t anim_tiles_per_pair = 0;
 
   explicit JxlHipEncoder(int dev) {
     if (dev >= 0) ENC_HIP(hipSetDevice(dev));
@@ -1728,9 +1732,10 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* en
 }
 
 // =====================================================================================================
-// Part 6 of the C-ABI: animation encode.  The extents kernel says what changed, enc_animation.cc turns that into
-// rectangles, and the rectangles go through Run like the images of a batch - a crop is a pointer offset and a narrower row in Run's
-// copy into tight rows.  Run hands back every frame alone (header, TOC, sections); they follow the image header in one codestream.
+// Part 6 of the C-ABI: animation encode.  The extents kernel - with max_rects >= 2 the tile kernel - says what
+// changed, enc_animation.cc turns that into rectangles, one per frame or several, and the rectangles go through Run like the images
+// of a batch - a crop is a pointer offset and a narrower row in Run's copy into tight rows.  Run hands back every frame alone (header,
+// TOC, sections); they follow the image header in one codestream.
 // =====================================================================================================
 namespace {
 
@@ -1739,63 +1744,93 @@ constexpr size_t kAnimWorkspaceBudget = (size_t)32 << 30;    // ... and at most 
 
 // Everything behind the host's checks.  src0: what CheckPixels made of frame 0 (the same for every frame).
 void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations, const EncoderOptions& opt,
-                     const JxlHipAnimationOptions& ao, const EncoderImageMetadata& md, const EncSource& src0) {
+                     const JxlHipAnimationOptions& ao, const JxlHipAnimationRectOptions& ro, const EncoderImageMetadata& md, const EncSource& src0) {
   const JxlHipPixels& f0 = frames[0];
   const int32_t w = (int32_t)f0.width, h = (int32_t)f0.height;
   const uint32_t pixel_bytes = (uint32_t)(f0.num_channels * src0.sample_bytes());
   const bool lossless = opt.lossless;
+  const bool by_tiles = ro.max_rects >= 2;
   hipStream_t s0 = enc->streams[0];
   StageMarks marks;
-  // ---- 1. what changed between consecutive frames: one launch, one download of 16 bytes per pair
+  // ---- 1. what changed between consecutive frames: one launch and one download - 16 bytes per pair (max_rects = 1: its box), or
+  // 4 bytes per pair and 64 x 64 tile
   std::vector<AnimExtent> ext((size_t)std::max(n - 1, 0));
+  const size_t tiles_per_pair = (size_t)AnimTilesAcross(w) * AnimTilesAcross(h);
   if (n > 1) {
-    const size_t table_bytes = ((size_t)n * sizeof(AnimFrameSrc) + 255) & ~(size_t)255, out_bytes = ext.size() * sizeof(AnimExtent);
+    const size_t table_bytes = ((size_t)n * sizeof(AnimFrameSrc) + 255) & ~(size_t)255;
+    const size_t out_bytes = by_tiles ? ext.size() * tiles_per_pair * sizeof(uint32_t) : ext.size() * sizeof(AnimExtent);
     enc->anim.Reserve(table_bytes + out_bytes, true);
     std::vector<AnimFrameSrc> table((size_t)n);
     for (int k = 0; k < n; k++) table[(size_t)k] = AnimFrameSrc{(const uint8_t*)frames[k].data, (int64_t)frames[k].stride_bytes};
-    AnimExtent* d_ext = (AnimExtent*)(enc->anim.p + table_bytes);
     ENC_HIP(hipMemcpyAsync(enc->anim.p, table.data(), table.size() * sizeof(AnimFrameSrc), hipMemcpyHostToDevice, s0));
-    ENC_HIP(hipMemsetAsync(d_ext, 0xFF, out_bytes, s0));
-    const size_t k_ext = marks.Begin("change extents of every pair of frames (one launch)", s0);
-    LaunchAnimExtents((const AnimFrameSrc*)enc->anim.p, n - 1, h, (uint64_t)f0.width * pixel_bytes, pixel_bytes, d_ext, s0);
-    marks.End(k_ext, s0);
-    ENC_HIP(hipMemcpyAsync(ext.data(), d_ext, out_bytes, hipMemcpyDeviceToHost, s0));
+    if (by_tiles) {
+      uint32_t* d_tiles = (uint32_t*)(enc->anim.p + table_bytes);
+      enc->anim_tiles.resize(ext.size() * tiles_per_pair);
+      enc->anim_tiles_per_pair = tiles_per_pair;
+      const size_t k_tiles = marks.Begin("change tiles of every pair of frames (one launch)", s0);
+      LaunchAnimTiles((const AnimFrameSrc*)enc->anim.p, n - 1, w, h, pixel_bytes, d_tiles, s0);
+      marks.End(k_tiles, s0);
+      ENC_HIP(hipMemcpyAsync(enc->anim_tiles.data(), d_tiles, out_bytes, hipMemcpyDeviceToHost, s0));
+    } else {
+      AnimExtent* d_ext = (AnimExtent*)(enc->anim.p + table_bytes);
+      ENC_HIP(hipMemsetAsync(d_ext, 0xFF, out_bytes, s0));
+      const size_t k_ext = marks.Begin("change extents of every pair of frames (one launch)", s0);
+      LaunchAnimExtents((const AnimFrameSrc*)enc->anim.p, n - 1, h, (uint64_t)f0.width * pixel_bytes, pixel_bytes, d_ext, s0);
+      marks.End(k_ext, s0);
+      ENC_HIP(hipMemcpyAsync(ext.data(), d_ext, out_bytes, hipMemcpyDeviceToHost, s0));
+    }
     ENC_HIP(hipStreamSynchronize(s0));   // (also: `table` was staged)
     ENC_HIP(hipGetLastError());
+    if (by_tiles)
+      for (size_t p = 0; p < ext.size(); p++) ext[p] = AnimTilesExtent(enc->anim_tiles.data() + p * tiles_per_pair, w, h);
   }
-  // ---- 2. the rectangles and what the headers say
+  // ---- 2. the rectangles and what the headers say: a frame with m rectangles is m codestream frames, of which the last carries the
+  // duration (the others have none: the decoder composes them into the next displayed image)
   EncImageInfo canvas;
   canvas.xsize = f0.width; canvas.ysize = f0.height;
   canvas.gray = f0.num_channels < 3; canvas.alpha = !(f0.num_channels & 1); canvas.xyb = !lossless;
   src0.Describe(canvas);
   canvas.have_animation = true;
   canvas.tps_numerator = ao.tps_numerator; canvas.tps_denominator = ao.tps_denominator; canvas.num_loops = ao.num_loops;
-  std::vector<FrameOnCanvas> on((size_t)n);
-  std::vector<JxlHipPixels> crops((size_t)n);
   enc->anim_rects.resize((size_t)n);
+  std::vector<JxlHipEncoder::AnimPart>& parts = enc->anim_parts;
+  std::vector<size_t> last_part((size_t)n);   // of frame k: the codestream frame that carries its duration
   for (int k = 0; k < n; k++) {
-    const AnimRect r = AnimFrameRect(k, ao.key_interval, k ? ext[(size_t)k - 1] : AnimExtent{-1, -1, -1, -1}, w, h, lossless);
-    enc->anim_rects[(size_t)k] = r;
-    on[(size_t)k].canvas = canvas;
-    on[(size_t)k].at = AnimPlacement(k, n, r, w, h, durations[k]);
-    JxlHipPixels& c = crops[(size_t)k];
-    c = frames[k];
-    c.data = (const uint8_t*)frames[k].data + (size_t)r.y * frames[k].stride_bytes + (size_t)r.x * pixel_bytes;
-    c.width = (uint32_t)r.w; c.height = (uint32_t)r.h;
+    enc->anim_rects[(size_t)k] = AnimFrameRect(k, ao.key_interval, k ? ext[(size_t)k - 1] : AnimExtent{-1, -1, -1, -1}, w, h, lossless);
+    if (by_tiles && !AnimIsKeyFrame(k, ao.key_interval)) {
+      for (const AnimRect& r : AnimFrameRects(enc->anim_tiles.data() + (size_t)(k - 1) * tiles_per_pair, w, h, lossless, ro.max_rects, ro.merge_pixels))
+        parts.push_back(JxlHipEncoder::AnimPart{k, r});
+    } else {
+      parts.push_back(JxlHipEncoder::AnimPart{k, enc->anim_rects[(size_t)k]});
+    }
+    last_part[(size_t)k] = parts.size() - 1;
+  }
+  const int total = (int)parts.size();
+  std::vector<FrameOnCanvas> on((size_t)total);
+  std::vector<JxlHipPixels> crops((size_t)total);
+  for (int c = 0; c < total; c++) {
+    const int k = parts[(size_t)c].k;
+    const AnimRect& r = parts[(size_t)c].r;
+    on[(size_t)c].canvas = canvas;
+    on[(size_t)c].at = AnimPlacement(c, total, r, w, h, (size_t)c == last_part[(size_t)k] ? durations[k] : 0);
+    JxlHipPixels& px = crops[(size_t)c];
+    px = frames[k];
+    px.data = (const uint8_t*)frames[k].data + (size_t)r.y * frames[k].stride_bytes + (size_t)r.x * pixel_bytes;
+    px.width = (uint32_t)r.w; px.height = (uint32_t)r.h;
   }
   // ---- 3. the frames, a chunk at a time
-  enc->files.assign((size_t)n, std::vector<uint8_t>());
+  enc->files.assign((size_t)total, std::vector<uint8_t>());
   std::vector<std::pair<const char*, float>> first_stages;
   marks.Publish(&first_stages);
-  for (int first = 0; first < n;) {
+  for (int first = 0; first < total;) {
     int cnt = 0;
     if (ao.chunk_frames >= 1) {
-      cnt = std::min(ao.chunk_frames, n - first);
+      cnt = std::min(ao.chunk_frames, total - first);
     } else {
       std::vector<EncBatchItem> items;
       std::vector<EncImage> ims;
       EncBatchLayout lay;
-      while (first + cnt < n && cnt < kAnimMaxChunkFrames) {
+      while (first + cnt < total && cnt < kAnimMaxChunkFrames) {
         const JxlHipPixels& c = crops[(size_t)(first + cnt)];
         items.push_back(EncBatchItem{c.width, c.height, c.num_channels, (int32_t)src0.sample_bytes(), lossless ? 1 : 0, 0});
         ims.resize(items.size());
@@ -1835,13 +1870,17 @@ void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, 
 
 }  // namespace
 
-extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
-                                                                   const EncoderOptions* options, const JxlHipAnimationOptions* animation,
-                                                                   const EncoderImageMetadata* metadata, ErrorInfo* err) {
-  if (!enc || !options || !animation) return EncoderStatus_NullParameter;
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                                         const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                                         const JxlHipAnimationRectOptions* rects, const EncoderImageMetadata* metadata,
+                                                                         ErrorInfo* err) {
+  if (!enc || !options || !animation || !rects) return EncoderStatus_NullParameter;
   enc->files.clear();
   enc->stages.clear();
   enc->anim_rects.clear();
+  enc->anim_parts.clear();
+  enc->anim_tiles.clear();
+  enc->anim_tiles_per_pair = 0;
   EncoderImageMetadata md;
   memset(&md, 0, sizeof(md));
   if (metadata) md = *metadata;
@@ -1853,6 +1892,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder
     if (!frames || !durations) throw EncFail(EncoderStatus_NullParameter, "");
     if (animation->tps_denominator < 1 || animation->tps_denominator > 1024) refuse("the denominator of the ticks per second must be 1..1024");
     if (animation->tps_numerator < 1 || animation->tps_numerator > (1u << 30)) refuse("the numerator of the ticks per second must be 1..2^30");
+    if (const char* why = AnimRectOptionsRefusal(rects->max_rects, rects->merge_pixels)) refuse(why);
     for (int k = 0; k < n; k++) {
       const std::string who = "frame " + std::to_string(k) + ": ";
       EncSource src;
@@ -1883,7 +1923,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder
   (void)hipGetDevice(&caller_device);
   try {
     if (caller_device != enc->device) ENC_HIP(hipSetDevice(enc->device));
-    EncodeAnimation(enc, n, frames, durations, *options, *animation, md, src0);
+    EncodeAnimation(enc, n, frames, durations, *options, *animation, *rects, md, src0);
   } catch (const EncFail& e) {
     failed = e.status; why = e.what();
   } catch (const std::bad_alloc&) {
@@ -1901,6 +1941,30 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder
   }
   if (caller_device != enc->device) (void)hipSetDevice(caller_device);
   return failed;
+}
+
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                                   const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                                   const EncoderImageMetadata* metadata, ErrorInfo* err) {
+  const JxlHipAnimationRectOptions one = {1, 0};
+  return jxlhip_encode_animation_rects(enc, n, frames, durations, options, animation, &one, metadata, err);
+}
+
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_frame_rects(JxlHipEncoder* enc, int32_t* kxywh, int32_t capacity) {
+  if (!enc) return 0;
+  const int32_t n = (int32_t)enc->anim_parts.size();
+  for (int32_t c = 0; kxywh && c < n && c < capacity; c++) {
+    const JxlHipEncoder::AnimPart& p = enc->anim_parts[(size_t)c];
+    kxywh[5 * c] = p.k; kxywh[5 * c + 1] = p.r.x; kxywh[5 * c + 2] = p.r.y; kxywh[5 * c + 3] = p.r.w; kxywh[5 * c + 4] = p.r.h;
+  }
+  return n;
+}
+
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_tiles(JxlHipEncoder* enc, int32_t pair, uint32_t* dst, int32_t capacity) {
+  if (!enc || pair < 0 || enc->anim_tiles_per_pair == 0 || (size_t)pair >= enc->anim_tiles.size() / enc->anim_tiles_per_pair) return 0;
+  const size_t n = enc->anim_tiles_per_pair;
+  for (size_t t = 0; dst && t < n && t < (size_t)std::max(capacity, 0); t++) dst[t] = enc->anim_tiles[(size_t)pair * n + t];
+  return (int32_t)n;
 }
 
 extern "C" JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_rects(JxlHipEncoder* enc, int32_t* xywh, int32_t capacity) {

@@ -932,3 +932,22 @@ extern "C" JXLFILETYPEIO_API void jxlhip_selftest_animation_rects(int32_t n, con
     if (at.have_crop && (at.x0 != r.x || at.y0 != r.y || (int32_t)at.width != r.w || (int32_t)at.height != r.h)) o[4] = -1;
   }
 }
+
+// AnimFrameRects on the caller's tile table (AnimTilesAcross(w) x AnimTilesAcross(h) words, row-major).  out: x, y, width, height per
+// rectangle, up to `capacity` rectangles; returns how many the rule gives.
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_animation_frame_rects(const uint32_t* tiles, int32_t w, int32_t h, int32_t lossless, int32_t max_rects,
+                                                                           int32_t merge_pixels, int32_t* out, int32_t capacity) {
+  const std::vector<AnimRect> rects = AnimFrameRects(tiles, w, h, lossless != 0, max_rects, merge_pixels);
+  for (size_t i = 0; i < rects.size() && (int32_t)i < capacity; i++) {
+    out[4 * i] = rects[i].x; out[4 * i + 1] = rects[i].y; out[4 * i + 2] = rects[i].w; out[4 * i + 3] = rects[i].h;
+  }
+  return (int32_t)rects.size();
+}
+
+// What jxlhip_encode_animation_rects says of these options before it looks at anything else: 1 and the words in err where it refuses
+// them, 0 where it does not.
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_animation_rect_options(int32_t max_rects, int32_t merge_pixels, ErrorInfo* err) {
+  const char* why = AnimRectOptionsRefusal(max_rects, merge_pixels);
+  if (why) SetEncErr(err, why);
+  return why ? 1 : 0;
+}
