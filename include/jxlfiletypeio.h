@@ -323,8 +323,9 @@ JXLFILETYPEIO_API int32_t jxlhip_encoder_stage_times(JxlHipEncoder* enc, const c
  *
  * Displayed image j is the canvas after the j-th frame, in file order, that ends the file or has a duration.  Frames
  * without a duration between them are layers: they blend onto the canvas and may be saved to the four reference slots.
- * Those slots are the state between two displayed images, so decoding is sequential by design: random access is
- * jxlhip_animation_rewind followed by skipping (jxlhip_animation_next into a buffer that is thrown away).
+ * Those slots are the state between two displayed images, so decoding is sequential from an ENTRY POINT: image 0, or an
+ * image in front of whose first frame no slot is alive (nothing written before it is read from there on).  jxlhip_animation_seek
+ * resumes at the nearest one; an encoder's key frames (jxlhip_encode_animation, key_interval) are entry points.
  * A file without an animation header is accepted: a single frame or a layered still has one displayed image, the one
  * LoadImage delivers.  Files whose frames carry patches or are reference-only frames are refused by name at open
  * ("animations with patches are not supported"), and so is everything LoadImage refuses of a layered file, with the same
@@ -370,8 +371,29 @@ JXLFILETYPEIO_API int32_t jxlhip_animation_frame(JxlHipAnimation* anim, int32_t 
  * becomes the state only when the chunk has succeeded): images in front of the damaged frame can still be asked for. */
 JXLFILETYPEIO_API DecoderStatus jxlhip_animation_next(JxlHipAnimation* anim, int32_t count, void* dev_out, size_t capacity,
                                                       int32_t* written, ErrorInfo* err);
-/* Back to the first displayed image. */
+/* Back to the first displayed image: jxlhip_animation_seek(anim, 0). */
 JXLFILETYPEIO_API void jxlhip_animation_rewind(JxlHipAnimation* anim);
+/* The entry points, ascending displayed indices (image 0 is always one).  Returns how many there are and writes up to
+ * `capacity` of them; displayed NULL or capacity 0: the count only. */
+JXLFILETYPEIO_API int32_t jxlhip_animation_entry_points(JxlHipAnimation* anim, int32_t* displayed, int32_t capacity);
+/* After it jxlhip_animation_next delivers displayed image j (j == num_displayed: the end; anything else outside the file:
+ * InvalidParameter, position unchanged).  j equal to the position does nothing.  Otherwise decoding resumes at the latest
+ * entry point e <= j - unless the decode stands in [e, j] already: a forward seek never goes back.  Nothing is decoded
+ * by the call: the images between the resume point and j are decoded for the reference slots only (none of them is
+ * stored, no buffer is needed for them), in the same chunks as the images asked for next. */
+JXLFILETYPEIO_API DecoderStatus jxlhip_animation_seek(JxlHipAnimation* anim, int32_t j, ErrorInfo* err);
+/* Where the next chunk starts (codestream frame) and which displayed image is delivered next.  Either pointer may be NULL. */
+JXLFILETYPEIO_API void jxlhip_animation_position(JxlHipAnimation* anim, int32_t* next_codestream_frame, int32_t* next_displayed);
+/* Thumbnails: with p the position, displayed images p, p + step, p + 2 step, ... (step >= 1) at 1:8, tightly packed into
+ * dev_out - n = min(count, ceil((num_displayed - p) / step)) of them, *written says how many; the position afterwards is
+ * min(num_displayed, p + n * step).  An image has ceil(width / 8) x ceil(height / 8) pixels, tight rows, the channels and
+ * sample type of the full-size image; a sample is the mean over one 8 x 8 cell of the displayed (oriented) image of the
+ * samples jxlhip_animation_next stores, cell (0, 0) at the top left, partial cells at the right and bottom edge averaging
+ * the pixels that exist: integers (sum + n / 2) / n, binary16 / binary32 the float32 sum divided by n and rounded to the
+ * type.  The images in between are decoded for the reference slots only.  Nothing is ever stored at full size.  A
+ * capacity that is too small: InvalidParameter, with the byte counts.  Combines freely with next, seek and rewind. */
+JXLFILETYPEIO_API DecoderStatus jxlhip_animation_next_reduced(JxlHipAnimation* anim, int32_t count, int32_t step, void* dev_out,
+                                                              size_t capacity, int32_t* written, ErrorInfo* err);
 /* "chunk_frames" (0: chunks by the limits above, the default; n >= 1: at most n frames per chunk - same output, for tests);
  * "lane_stride", "no_direct", "mod_lanes64", "no_stream_pairs" and "no_lf_pipeline" go to the animation's decoder as
  * jxlhip_set_option takes them (same output).  Every other name is refused: neither a band nor a reduced size is offered

@@ -103,7 +103,8 @@ EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jx
            "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
            "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_encode_animation", "jxlhip_encoder_animation_rects", "jxlhip_encode_animation_rects",
            "jxlhip_encoder_animation_frame_rects", "jxlhip_encoder_animation_tiles", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
-           "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder"]
+           "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder", "jxlhip_animation_entry_points",
+           "jxlhip_animation_seek", "jxlhip_animation_position", "jxlhip_animation_next_reduced"]
 
 _lib = None
 
@@ -222,6 +223,14 @@ def lib(build_if_missing=True):
     L.jxlhip_animation_next.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_animation_rewind.restype = None
     L.jxlhip_animation_rewind.argtypes = [C.c_void_p]
+    L.jxlhip_animation_entry_points.restype = C.c_int32
+    L.jxlhip_animation_entry_points.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    L.jxlhip_animation_seek.restype = C.c_int32
+    L.jxlhip_animation_seek.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ErrorInfo)]
+    L.jxlhip_animation_position.restype = None
+    L.jxlhip_animation_position.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.jxlhip_animation_next_reduced.restype = C.c_int32
+    L.jxlhip_animation_next_reduced.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_animation_set_option.restype = C.c_int32
     L.jxlhip_animation_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.jxlhip_animation_decoder.restype = C.c_void_p
@@ -779,9 +788,15 @@ class Animation:
             t = a.next(4)          # torch tensor [n, h, w, c] on the GPU, n <= 4 (0 at the end)
             a.rewind()
             every = a.read_all()   # numpy [num_displayed, h, w, c]
+            a.entry_points         # [0, 8, 16, ...]: the images a decode can start at
+            a.seek(20); a.next(1)  # image 20, decoded from image 16 on; images 16 .. 19 are not stored
+            one = a.frame(20)      # the same
+            a.rewind()
+            small = a.thumbnails(step=4)   # images 0, 4, 8, ... at 1:8, [n, ceil(h / 8), ceil(w / 8), c]
 
-    Decoding is sequential (the state between two images is the reference slots): random access is rewind() and skipping.  A file
-    without an animation header has one displayed image, the one load_image delivers.  Raises FormatError where the file is refused."""
+    Decoding is sequential from an entry point (the state between two images is the reference slots): image 0, and every image in
+    front of which no slot is alive - an encoder's key frames are such.  A file without an animation header has one displayed image,
+    the one load_image delivers.  Raises FormatError where the file is refused."""
 
     def __init__(self, data, device=-1):
         self._h = None
@@ -827,6 +842,73 @@ class Animation:
     def rewind(self):
         self._L.jxlhip_animation_rewind(self._h)
         self._pos = 0
+
+    @property
+    def entry_points(self):
+        """The displayed images at which decoding can start (ascending, 0 first): seek() resumes at the nearest one in front."""
+        n = self._L.jxlhip_animation_entry_points(self._h, None, 0)
+        buf = (C.c_int32 * max(1, n))()
+        self._L.jxlhip_animation_entry_points(self._h, buf, n)
+        return list(buf[:n])
+
+    @property
+    def position(self):
+        """(codestream frame the next chunk starts at, displayed image that next() delivers first)."""
+        f, j = C.c_int32(0), C.c_int32(0)
+        self._L.jxlhip_animation_position(self._h, C.byref(f), C.byref(j))
+        return f.value, j.value
+
+    def seek(self, j):
+        """next() delivers displayed image j after it (j == num_displayed: the end).  Lazy: nothing is decoded by the call, and the images
+        between the entry point and j are never stored.  ValueError for a j outside the file."""
+        err = ErrorInfo()
+        st = self._L.jxlhip_animation_seek(self._h, int(j), C.byref(err))
+        self.last_error = err.errorMessage.decode("ascii", "replace")
+        if st != 0:
+            name = DECODER_STATUS[st] if 0 <= st < len(DECODER_STATUS) else str(st)
+            if name == "InvalidParameter":
+                raise ValueError(self.last_error)
+            raise FormatError(name, self.last_error)
+        self._pos = int(j)
+
+    def frame(self, j):
+        """Displayed image j as a torch tensor [h, w, c] on the device: seek(j), then next(1)[0]."""
+        self.seek(j)
+        t = self.next(1)
+        if t.shape[0] != 1:
+            raise ValueError("displayed image %d: the file has %d" % (j, self.info.num_displayed))
+        return t[0]
+
+    def thumbnails(self, count=None, step=1):
+        """Displayed images p, p + step, ... (p: the position) at 1:8 as a torch tensor [n, rh, rw, c] on the device, (rw, rh) =
+        reduced_size(width, height, 8): each sample the mean of an 8 x 8 cell of what next() stores.  count None: every selected image
+        that is left.  The images in between are decoded, not stored.  16-bit integers arrive as torch.int16 holding the same bits."""
+        import torch
+        i = self.info
+        if step < 1:
+            raise ValueError("step %d: step >= 1" % step)
+        left = max(0, (i.num_displayed - self._pos + step - 1) // step)
+        want = left if count is None else max(0, min(int(count), left))
+        rw, rh = reduced_size(i.width, i.height, 8)
+        tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.float16: torch.float16, np.float32: torch.float32}[self.dtype]
+        dev = torch.device("cuda", self._device) if self._device >= 0 else torch.device("cuda")
+        out = torch.empty((want, rh, rw, i.num_channels), dtype=tdt, device=dev)
+        torch.cuda.synchronize()
+        n = C.c_int32(0)
+        err = ErrorInfo()
+        st = self._L.jxlhip_animation_next_reduced(self._h, want, int(step), out.data_ptr() if want else None, out.numel() * out.element_size(),
+                                                   C.byref(n), C.byref(err))
+        self.last_error = err.errorMessage.decode("ascii", "replace")
+        self._pos = self.position[1]
+        if st != 0:
+            raise FormatError(DECODER_STATUS[st] if 0 <= st < len(DECODER_STATUS) else str(st), self.last_error)
+        return out[:n.value]
+
+    def read_thumbnails(self, step=1):
+        """Rewinds and returns the 1:8 images 0, step, 2 step, ... as one numpy array [n, rh, rw, c] of the file's sample type."""
+        self.rewind()
+        a = self.thumbnails(None, step).cpu().numpy()
+        return a.view(np.uint16) if self.dtype == np.uint16 else a
 
     def next(self, count=1):
         """The next `count` displayed images as a torch tensor [n, h, w, c] on the device (n < count at the end of the file, 0 behind

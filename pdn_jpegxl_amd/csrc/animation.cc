@@ -63,8 +63,10 @@ AnimPlan PlanAnimation(Animation& a) {
   return p;
 }
 
-AnimChunk NextChunk(const Animation& a, const AnimPlan& p, int first, int last_shown, int chunk_frames, size_t scratch_budget) {
+AnimChunk NextChunk(const Animation& a, const AnimPlan& p, int first, int last_shown, int chunk_frames, size_t scratch_budget, int first_stored,
+                    int step) {
   AnimChunk c;
+  c.step = step;
   const int n = (int)a.frames.size();
   const int cap = chunk_frames >= 1 ? std::min(chunk_frames, kMaxLayerFrames) : kMaxLayerFrames;
   c.first = first;
@@ -78,12 +80,50 @@ AnimChunk NextChunk(const Animation& a, const AnimPlan& p, int first, int last_s
     if (a.show[k] >= 0) {
       if (c.first_shown < 0) c.first_shown = a.show[k];
       c.shown++;
+      if (a.show[k] >= first_stored && (a.show[k] - first_stored) % step == 0) {
+        if (c.first_stored < 0) c.first_stored = a.show[k];
+        c.stored++;
+      }
       if (a.show[k] >= last_shown) break;
     }
   }
   if (c.first_shown < 0) c.first_shown = 0;
   c.live_out = p.live_after[first + c.count - 1];
   return c;
+}
+
+std::vector<int> EntryPoints(const Animation& a, const AnimPlan& p) {
+  std::vector<int> e;
+  for (int j = 0; j < (int)a.completes.size(); j++) {
+    const int f = FirstFrame(a, j);
+    if (f == 0 || p.live_after[f - 1] == 0) e.push_back(j);
+  }
+  return e;
+}
+
+int FirstFrame(const Animation& a, int j) {
+  if (j <= 0) return 0;
+  return j >= (int)a.completes.size() ? (int)a.frames.size() : a.completes[j - 1] + 1;
+}
+
+int ImageOfFrame(const Animation& a, int k) {
+  return (int)(std::lower_bound(a.completes.begin(), a.completes.end(), k) - a.completes.begin());
+}
+
+bool SeekCursor(const Animation& a, const std::vector<int>& entry_points, AnimCursor& cur, int j) {
+  if (j < 0 || j > (int)a.completes.size()) return false;
+  if (j == cur.shown) return true;
+  // (image 0 is always an entry point, so there is one at or in front of every j)
+  const int e = *(std::upper_bound(entry_points.begin(), entry_points.end(), j) - 1);
+  const int at = ImageOfFrame(a, cur.frame);
+  if (!(e <= at && at <= j)) cur.frame = FirstFrame(a, e);
+  cur.shown = j;
+  return true;
+}
+
+int SelectedImages(const Animation& a, const AnimCursor& cur, int count, int step) {
+  const int left = (int)a.completes.size() - cur.shown;
+  return std::max(0, std::min(count, (left + step - 1) / step));
 }
 
 }  // namespace jxlhip

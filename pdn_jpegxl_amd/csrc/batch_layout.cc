@@ -486,6 +486,12 @@ void BuildBatch(const BatchInput& in, BatchRegions& R, BatchOutput& out) {
     const std::vector<Composite>& comps = *in.comps;
     for (size_t k = 0; k < comps.size(); k++)   // compose_kernel: 256-pixel row segments
       out.max_segments = std::max(out.max_segments, (int)(*in.files)[k].ysize * (int)(((*in.files)[k].xsize + 255) / 256));
+    for (size_t k = 0; k < comps.size(); k++) {   // compose_reduce_kernel: 8x8 cells of the displayed image (transposing swaps its sides)
+      const ParsedFrame& top = (*in.files)[k];
+      if (!top.layers->reduce) continue;
+      out.compose_reduce = true;
+      out.max_reduce_cells = std::max(out.max_reduce_cells, (int)((top.xsize + 7) / 8) * (int)((top.ysize + 7) / 8));
+    }
     out.comp_imgs = blob.Fill<ComposeImage>(comps.size(), [&](ComposeImage* cimgs) {
       for (size_t k = 0; k < comps.size(); k++) {
         const ParsedFrame& top = (*in.files)[k];
@@ -504,6 +510,7 @@ void BuildBatch(const BatchInput& in, BatchRegions& R, BatchOutput& out) {
         ci.slots_in = top.layers->slots_in; ci.slots_out = top.layers->slots_out;
         for (int s = 0; s < 4; s++) ci.slot_plane[s] = top.layers->slot_plane[s];
         ci.out_stride = top.layers->out_stride;
+        ci.reduce = top.layers->reduce ? 1 : 0;
       }
     });
     out.comp_frames = blob.Fill<ComposeFrame>((size_t)n, [&](ComposeFrame* cframes) {

@@ -116,6 +116,8 @@ struct BatchOutput {
   int stage_mask = 0;   // LDS-tiled loop-filter stage kernels some frame of the batch needs (bit s: filter_tile_kernel<s>)
   int any_fused = 0, any_fused2 = 0;   // 1: fused frames (with a second iteration) of the two-pixels-per-lane kernels, 2: others
   int max_w = 1, max_h = 1, max_tiles = 1, max_groups = 1, max_segments = 1;
+  bool compose_reduce = false;   // the batch's layered images leave at 1:8 (an animation's thumbnails: a batch of one)
+  int max_reduce_cells = 1;
   size_t max_cells = 1, max_ds_cells = 1, max_mod_pixels = 1;   // max_ds_cells: reduced-size decode, over the frames of both kinds
   int pixel_chunk = 1;   // frames that share one set of reconstruction / filter planes are this far apart
   DevImage* d_imgs = nullptr;           // where imgs goes in the blob

@@ -89,16 +89,30 @@ __device__ __forceinline__ float BlendSample(int mode, bool is_alpha, bool premu
   }
 }
 
-// One displayed image leaves: un-premultiply (as modular_out_kernel), round to the output type, store at the oriented position.  The
-// frame loop calls this after every frame that completes a displayed image (a still: its last frame), with that image's buffer.
-__device__ __forceinline__ void StoreDisplayed(const ComposeImage& im, uint8_t* out, const float (&canvas)[4], int x, int y, int ai) {
-  const int w = im.w, h = im.h, nch = im.nch;
-  float res[4] = {canvas[0], canvas[1], canvas[2], canvas[3]};
+// The sample as stored: what a displayed image holds for a pixel, as bit patterns of the output type.  Stated once, in two steps:
+// compose_kernel stores these bits and compose_reduce_kernel averages them.
+// Step 1: un-premultiply (as modular_out_kernel).
+__device__ __forceinline__ void Unpremultiply(const ComposeImage& im, const float (&canvas)[4], int ai, float (&res)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; c++) res[c] = canvas[c];
   if (im.premul && ai >= 0 && !im.raw) {
     const float unmul = 1.0f / fmaxf(1.0f / 67108864.0f, Lane(make_float4(res[0], res[1], res[2], res[3]), ai));
 #pragma unroll
     for (int c = 0; c < 4; c++) if (c < ai) res[c] *= unmul;
   }
+}
+// Step 2: a raw image carries the bits themselves; otherwise rounding half up like modular_out_kernel (not v_cvt_pk_u8_f32, which
+// rounds ties to even): a layered file whose frames replace decodes to the same bytes as its frames would alone.
+__device__ __forceinline__ uint32_t SampleBits(bool raw, float v, int out_bits, int out_float) {
+  return raw ? __float_as_uint(v) : FloatToOutBits(v, out_bits, out_float);
+}
+
+// One displayed image leaves: the samples as stored, at the oriented position.  The frame loop calls this after every frame that
+// completes a displayed image (a still: its last frame), with that image's buffer.
+__device__ __forceinline__ void StoreDisplayed(const ComposeImage& im, uint8_t* out, const float (&canvas)[4], int x, int y, int ai) {
+  const int w = im.w, h = im.h, nch = im.nch;
+  float res[4];
+  Unpremultiply(im, canvas, ai, res);
   int ox = x, oy = y, ow = w;
   switch (im.orientation) {
     case 2: ox = w - 1 - x; break;
@@ -115,26 +129,24 @@ __device__ __forceinline__ void StoreDisplayed(const ComposeImage& im, uint8_t* 
     if (im.out_bits == 8 && nch == 4) {
       uint32_t px = 0;
 #pragma unroll
-      for (int c = 0; c < 4; c++) px |= __float_as_uint(res[c]) << (8 * c);
+      for (int c = 0; c < 4; c++) px |= SampleBits(true, res[c], 8, 0) << (8 * c);
       ((uint32_t*)out)[o] = px;
     } else {
 #pragma unroll
       for (int c = 0; c < 4; c++)
-        if (c < nch) StoreOutSample(out, o * nch + c, __float_as_uint(res[c]), im.out_bits);
+        if (c < nch) StoreOutSample(out, o * nch + c, SampleBits(true, res[c], im.out_bits, im.out_float), im.out_bits);
     }
     return;
   }
-  // rounding half up like modular_out_kernel (not v_cvt_pk_u8_f32, which rounds ties to even): a layered file whose frames replace
-  // decodes to the same bytes as its frames would alone
   if (im.out_bits == 8 && nch == 4) {   // the common layout: one 4-byte store
     uint32_t px = 0;
 #pragma unroll
-    for (int c = 0; c < 4; c++) px |= FloatToOutBits(res[c], 8, 0) << (8 * c);
+    for (int c = 0; c < 4; c++) px |= SampleBits(false, res[c], 8, 0) << (8 * c);
     ((uint32_t*)out)[o] = px;
   } else {
 #pragma unroll
     for (int c = 0; c < 4; c++)
-      if (c < nch) StoreOutSample(out, o * nch + c, FloatToOutBits(res[c], im.out_bits, im.out_float), im.out_bits);
+      if (c < nch) StoreOutSample(out, o * nch + c, SampleBits(false, res[c], im.out_bits, im.out_float), im.out_bits);
   }
 }
 
@@ -154,10 +166,61 @@ __device__ __forceinline__ void StoreSlot(float* slots, size_t plane, int s, siz
   else q[0] = v.x;
 }
 
+// The frame loop of one canvas pixel (x, y): the slots in registers, the slot traffic of a chunked animation, both sample routes and
+// every blend mode.  show(frame, canvas) is called after each frame that completes a displayed image of the launch, in uniform control
+// flow.  A lane that is not `inside` the canvas (compose_reduce_kernel's lanes past the image edge) touches no memory and walks the
+// loop with zeros, so that it reaches every show call with the rest of its wavefront.  The caller hands in what is uniform per image
+// (canvas width, channels, alpha index, pixels of a slot plane): computed once in front of its pixel loop, they stay in scalar registers.
+template <class Show>
+__device__ __forceinline__ void ComposePixel(const ComposeImage& im, const ComposeFrame* __restrict__ frames, int w, int nch, int ai, size_t plane, int x, int y, bool inside, Show&& show) {
+  const size_t p = (size_t)y * w + x;
+  Slots sl;
+  sl.s0 = sl.s1 = sl.s2 = sl.s3 = make_float4(0.f, 0.f, 0.f, 0.f);
+  // a later chunk of an animation: the slots some frame from here on reads, as the chunk before left them (uniform tests)
+  if (inside) {
+    if (im.live_in & 1) sl.s0 = LoadSlot(im.slots_in, plane, im.slot_plane[0], p, nch);
+    if (im.live_in & 2) sl.s1 = LoadSlot(im.slots_in, plane, im.slot_plane[1], p, nch);
+    if (im.live_in & 4) sl.s2 = LoadSlot(im.slots_in, plane, im.slot_plane[2], p, nch);
+    if (im.live_in & 8) sl.s3 = LoadSlot(im.slots_in, plane, im.slot_plane[3], p, nch);
+  }
+  float res[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < im.count; k++) {
+    const ComposeFrame& fr = frames[im.first + k];
+    const float4 oc = ReadSlot(sl, fr.source[0]), oa = ReadSlot(sl, fr.source[1]);
+    const float old_c[4] = {oc.x, oc.y, oc.z, oc.w}, old_a[4] = {oa.x, oa.y, oa.z, oa.w};
+    const int fx = x - fr.x0, fy = y - fr.y0;
+    if (inside && fx >= 0 && fy >= 0 && fx < fr.w && fy < fr.h) {
+      float nw[4];
+      if (im.raw) LoadRaw(fr, nch, im.out_bits, fx, fy, nw);
+      else LoadFrame(fr, nch, fx, fy, nw);
+      const float a = ai >= 0 ? Lane(make_float4(nw[0], nw[1], nw[2], nw[3]), ai) : 1.f;
+      const float ob_c = Lane(oc, ai), ob_a = Lane(oa, ai);
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const bool is_alpha = c == ai;
+        const int g = is_alpha ? 1 : 0;
+        res[c] = c >= nch ? 0.f : BlendSample(fr.mode[g], is_alpha, im.premul != 0, fr.clamp[g] != 0, nw[c], is_alpha ? old_a[c] : old_c[c], a,
+                                               is_alpha ? ob_a : ob_c);
+      }
+    } else {   // outside the crop: the source slot as it is
+#pragma unroll
+      for (int c = 0; c < 4; c++) res[c] = c == ai ? old_a[c] : old_c[c];
+    }
+    if (fr.save >= 0) WriteSlot(sl, fr.save, make_float4(res[0], res[1], res[2], res[3]));
+    if (fr.show >= 0) show(fr, res);
+  }
+  if (inside) {
+    if (im.live_out & 1) StoreSlot(im.slots_out, plane, im.slot_plane[0], p, nch, sl.s0);
+    if (im.live_out & 2) StoreSlot(im.slots_out, plane, im.slot_plane[1], p, nch, sl.s1);
+    if (im.live_out & 4) StoreSlot(im.slots_out, plane, im.slot_plane[2], p, nch, sl.s2);
+    if (im.live_out & 8) StoreSlot(im.slots_out, plane, im.slot_plane[3], p, nch, sl.s3);
+  }
+}
+
 __global__ void compose_kernel(const ComposeImage* __restrict__ imgs, const ComposeFrame* __restrict__ frames) {
   const ComposeImage& im = imgs[blockIdx.y];
   const int w = im.w, h = im.h, nch = im.nch;
-  const int ai = im.has_alpha ? nch - 1 : -1;
+  const int ai = im.has_alpha ? im.nch - 1 : -1;
   const size_t plane = (size_t)w * h;
   // a workgroup per 256-pixel row segment, one pixel per lane: the segment's row and column come from one uniform (scalar) division per
   // workgroup, none per pixel, and a wavefront's crop tests are on one row segment
@@ -165,44 +228,99 @@ __global__ void compose_kernel(const ComposeImage* __restrict__ imgs, const Comp
   for (int t = blockIdx.x; t < xseg * h; t += gridDim.x) {
     const int y = t / xseg, x = (t - y * xseg) * (int)blockDim.x + (int)threadIdx.x;
     if (x >= w) continue;
-    const size_t p = (size_t)y * w + x;
-    Slots sl;
-    sl.s0 = sl.s1 = sl.s2 = sl.s3 = make_float4(0.f, 0.f, 0.f, 0.f);
-    // a later chunk of an animation: the slots some frame from here on reads, as the chunk before left them (uniform tests)
-    if (im.live_in & 1) sl.s0 = LoadSlot(im.slots_in, plane, im.slot_plane[0], p, nch);
-    if (im.live_in & 2) sl.s1 = LoadSlot(im.slots_in, plane, im.slot_plane[1], p, nch);
-    if (im.live_in & 4) sl.s2 = LoadSlot(im.slots_in, plane, im.slot_plane[2], p, nch);
-    if (im.live_in & 8) sl.s3 = LoadSlot(im.slots_in, plane, im.slot_plane[3], p, nch);
-    float res[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < im.count; k++) {
-      const ComposeFrame& fr = frames[im.first + k];
-      const float4 oc = ReadSlot(sl, fr.source[0]), oa = ReadSlot(sl, fr.source[1]);
-      const float old_c[4] = {oc.x, oc.y, oc.z, oc.w}, old_a[4] = {oa.x, oa.y, oa.z, oa.w};
-      const int fx = x - fr.x0, fy = y - fr.y0;
-      if (fx >= 0 && fy >= 0 && fx < fr.w && fy < fr.h) {
-        float nw[4];
-        if (im.raw) LoadRaw(fr, nch, im.out_bits, fx, fy, nw);
-        else LoadFrame(fr, nch, fx, fy, nw);
-        const float a = ai >= 0 ? Lane(make_float4(nw[0], nw[1], nw[2], nw[3]), ai) : 1.f;
-        const float ob_c = Lane(oc, ai), ob_a = Lane(oa, ai);
+    ComposePixel(im, frames, w, nch, ai, plane, x, y, true, [=, &im](const ComposeFrame& fr, const float (&canvas)[4]) {
+      StoreDisplayed(im, im.out + (size_t)fr.show * im.out_stride, canvas, x, y, ai);
+    });
+  }
+}
+
+// The mean of one 8 x 8 cell of a displayed image, one lane per pixel of the cell (lane l at (l & 7, l >> 3)): the samples as stored,
+// summed across the wavefront in butterfly steps (every lane takes part in every step; a lane past the image edge adds nothing), and
+// lane 0 stores the nch (<= 4) means at samples first, first + 1, ... of `out`.  n: the pixels of the cell that exist.  Integer samples: (sum + n / 2) / n in 32 bits; binary16 and
+// binary32: the float32 sum in the butterfly's order, divided by n, rounded to the output type.
+__device__ __forceinline__ void StoreCellMean(const uint32_t (&bits)[4], bool inside, int n, int nch, int out_bits, int out_float, uint8_t* out, size_t first) {
+  const int lane = (int)(threadIdx.x & 63);
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-          const bool is_alpha = c == ai;
-          const int g = is_alpha ? 1 : 0;
-          res[c] = c >= nch ? 0.f : BlendSample(fr.mode[g], is_alpha, im.premul != 0, fr.clamp[g] != 0, nw[c], is_alpha ? old_a[c] : old_c[c], a,
-                                                 is_alpha ? ob_a : ob_c);
-        }
-      } else {   // outside the crop: the source slot as it is
+  for (int c = 0; c < 4; c++) {
+    if (c >= nch) break;
+    uint32_t mean;
+    if (out_float) {
+      float v = 0.f;
+      if (inside) v = out_bits == 32 ? __uint_as_float(bits[c]) : __half2float(__ushort_as_half((unsigned short)bits[c]));
 #pragma unroll
-        for (int c = 0; c < 4; c++) res[c] = c == ai ? old_a[c] : old_c[c];
-      }
-      if (fr.save >= 0) WriteSlot(sl, fr.save, make_float4(res[0], res[1], res[2], res[3]));
-      if (fr.show >= 0) StoreDisplayed(im, im.out + (size_t)fr.show * im.out_stride, res, x, y, ai);
+      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+      mean = FloatToOutBits(v / (float)n, out_bits, 1);
+    } else {
+      uint32_t v = inside ? bits[c] : 0u;
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
+      mean = (v + (uint32_t)n / 2) / (uint32_t)n;
     }
-    if (im.live_out & 1) StoreSlot(im.slots_out, plane, im.slot_plane[0], p, nch, sl.s0);
-    if (im.live_out & 2) StoreSlot(im.slots_out, plane, im.slot_plane[1], p, nch, sl.s1);
-    if (im.live_out & 4) StoreSlot(im.slots_out, plane, im.slot_plane[2], p, nch, sl.s2);
-    if (im.live_out & 8) StoreSlot(im.slots_out, plane, im.slot_plane[3], p, nch, sl.s3);
+    if (lane == 0) StoreOutSample(out, first + c, mean, out_bits);
+  }
+}
+
+// Thumbnails of an animation's displayed images (jxlhip_animation_next_reduced): compose_kernel's frame loop, with one wavefront per
+// 8 x 8 cell of the DISPLAYED image.  The lane's canvas pixel is the inverse of the orientation, so a cell's lanes are an 8 x 8 block
+// of the canvas too (mirrored or transposed), and partial cells lie at the canvas edge the orientation maps to the right / bottom.
+// Slots travel at full resolution; nothing of a displayed image is stored but its cell means, out_stride bytes apart.
+__global__ void compose_reduce_kernel(const ComposeImage* __restrict__ imgs, const ComposeFrame* __restrict__ frames) {
+  const ComposeImage& im = imgs[blockIdx.y];
+  const int w = im.w, h = im.h, nch = im.nch;
+  const int ai = im.has_alpha ? nch - 1 : -1;
+  const size_t plane = (size_t)w * h;
+  const bool transposed = im.orientation >= 5;
+  const int dw = transposed ? h : w, dh = transposed ? w : h;
+  const int cw = (dw + 7) >> 3, ch = (dh + 7) >> 3;
+  const int waves = (int)blockDim.x >> 6, wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  for (int t = (int)blockIdx.x * waves + wave; t < cw * ch; t += (int)gridDim.x * waves) {   // (uniform in a wavefront)
+    const int cy = t / cw, cx = t - cy * cw;
+    const int ox = cx * 8 + (lane & 7), oy = cy * 8 + (lane >> 3);
+    const bool inside = ox < dw && oy < dh;
+    const int n = min(8, dw - cx * 8) * min(8, dh - cy * 8);
+    int x = ox, y = oy;
+    switch (im.orientation) {   // the inverse of StoreDisplayed's mapping
+      case 2: x = w - 1 - ox; break;
+      case 3: x = w - 1 - ox; y = h - 1 - oy; break;
+      case 4: y = h - 1 - oy; break;
+      case 5: x = oy; y = ox; break;
+      case 6: x = oy; y = h - 1 - ox; break;
+      case 7: x = w - 1 - oy; y = h - 1 - ox; break;
+      case 8: x = w - 1 - oy; y = ox; break;
+      default: break;
+    }
+    ComposePixel(im, frames, w, nch, ai, plane, x, y, inside, [&](const ComposeFrame& fr, const float (&canvas)[4]) {
+      const int j = fr.show;
+      float res[4];
+      Unpremultiply(im, canvas, ai, res);
+      uint32_t bits[4];
+#pragma unroll
+      for (int c = 0; c < 4; c++) bits[c] = SampleBits(im.raw != 0, res[c], im.out_bits, im.out_float);
+      StoreCellMean(bits, inside, n, nch, im.out_bits, im.out_float, im.out + (size_t)j * im.out_stride, (size_t)t * nch);
+    });
+  }
+}
+
+// The same cell means of one displayed image that is in memory already (a file that is one single-frame image: the ordinary decode
+// wrote it, oriented, to scratch): dw x dh pixels of nch samples, four channels at a time (a CMYK image with alpha has five).
+__global__ void reduce_displayed_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int dw, int dh, int nch, int out_bits, int out_float) {
+  const int cw = (dw + 7) >> 3, ch = (dh + 7) >> 3;
+  const int waves = (int)blockDim.x >> 6, wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  for (int t = (int)blockIdx.x * waves + wave; t < cw * ch; t += (int)gridDim.x * waves) {
+    const int cy = t / cw, cx = t - cy * cw;
+    const int ox = cx * 8 + (lane & 7), oy = cy * 8 + (lane >> 3);
+    const bool inside = ox < dw && oy < dh;
+    const int n = min(8, dw - cx * 8) * min(8, dh - cy * 8);
+    for (int c0 = 0; c0 < nch; c0 += 4) {   // (uniform)
+      uint32_t bits[4] = {0, 0, 0, 0};
+      if (inside) {
+        const size_t i = ((size_t)oy * dw + ox) * nch + c0;
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+          if (c0 + c < nch) bits[c] = out_bits == 8 ? src[i + c] : (out_bits == 16 ? ((const uint16_t*)src)[i + c] : ((const uint32_t*)src)[i + c]);
+      }
+      StoreCellMean(bits, inside, n, min(4, nch - c0), out_bits, out_float, dst, (size_t)t * nch + c0);
+    }
   }
 }
 
@@ -212,6 +330,18 @@ void LaunchCompose(const ComposeImage* imgs, const ComposeFrame* frames, int nim
   if (nimg <= 0) return;
   const unsigned blocks = (unsigned)std::max(1, std::min(1 << 20, max_segments));
   hipLaunchKernelGGL(compose_kernel, dim3(blocks, nimg), dim3(256), 0, s, imgs, frames);
+}
+
+void LaunchComposeReduce(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_cells, hipStream_t s) {
+  if (nimg <= 0) return;
+  const unsigned blocks = (unsigned)std::max(1, std::min(1 << 20, (max_cells + 3) / 4));   // four wavefronts, a cell each
+  hipLaunchKernelGGL(compose_reduce_kernel, dim3(blocks, nimg), dim3(256), 0, s, imgs, frames);
+}
+
+void LaunchReduceDisplayed(const uint8_t* src, uint8_t* dst, int dw, int dh, int nch, int out_bits, int out_float, hipStream_t s) {
+  const int cells = ((dw + 7) / 8) * ((dh + 7) / 8);
+  const unsigned blocks = (unsigned)std::max(1, std::min(1 << 20, (cells + 3) / 4));
+  hipLaunchKernelGGL(reduce_displayed_kernel, dim3(blocks), dim3(256), 0, s, src, dst, dw, dh, nch, out_bits, out_float);
 }
 
 }  // namespace jxlhip

@@ -696,7 +696,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
     Mark("patches", stream, 2);
   }
   if (!comps.empty()) {
-    LaunchCompose(B.comp_imgs, B.comp_frames, (int)comps.size(), B.max_segments, stream);
+    if (B.compose_reduce) LaunchComposeReduce(B.comp_imgs, B.comp_frames, (int)comps.size(), B.max_reduce_cells, stream);
+    else LaunchCompose(B.comp_imgs, B.comp_frames, (int)comps.size(), B.max_segments, stream);
     Mark("compose", stream, 2);
   }
   for (int i = 0; i < n; i++)
@@ -1116,9 +1117,10 @@ DecoderStatus LoadImage(DecoderCallbacks* cb, const uint8_t* data, size_t size, 
 }  // extern "C"
 
 // ---------------------------------------------------------------------- animations: every displayed image of a file, in file order
-// The state between two displayed images is the four reference slots, so decoding is sequential.  Frames are decoded in chunks
-// (animation.h): each chunk is one JxlHipDecoder::Decode of a layered file made of the chunk's frames, whose compose launch stores every
-// displayed image it passes and carries the live slots from and to the slot buffers.
+// The state between two displayed images is the four reference slots, so decoding is sequential from an entry point (an image with no
+// live slot in front of it; animation.h).  Frames are decoded in chunks: each chunk is one JxlHipDecoder::Decode of a layered file made
+// of the chunk's frames, whose compose launch stores the displayed images the chunk's plan selects - at full size, or at 1:8
+// (compose_reduce_kernel) - and carries the live slots from and to the slot buffers.
 struct JxlHipAnimation {
   std::vector<uint8_t> file;      // the caller's bytes (the parse points into them)
   Animation anim;
@@ -1132,19 +1134,29 @@ struct JxlHipAnimation {
   float* d_slots[2] = {nullptr, nullptr};
   int slot_plane[4] = {0, 0, 0, 0};
   int cur_slots = 0;
-  int next_frame = 0, next_shown = 0;
+  AnimCursor cur;                 // where the next chunk starts and which image is delivered next (a seek only moves this)
+  std::vector<int> entry_points;
   int chunk_frames = 0;
-  size_t image_bytes = 0;
+  size_t image_bytes = 0, reduced_bytes = 0;
+  int disp_w = 0, disp_h = 0, nch = 0, out_bits = 8, out_float = 0;
+  uint8_t* d_single = nullptr;    // a single-frame file's full-size image, for its thumbnail (allocated when first asked for)
   ~JxlHipAnimation() {
     if (dec) (void)hipSetDevice(dec->device);
     if (d_cs) (void)hipFree(d_cs);
+    if (d_single) (void)hipFree(d_single);
     for (float* p : d_slots) if (p) (void)hipFree(p);
   }
-  DecoderStatus RunChunk(const AnimChunk& c, uint8_t* out, ErrorInfo* err);
+  // out: where the chunk's first stored image goes (full size, or 1:8 when reduce); a chunk that stores none writes nothing
+  DecoderStatus RunChunk(const AnimChunk& c, uint8_t* out, bool reduce, ErrorInfo* err);
+  DecoderStatus Deliver(int n, int step, bool reduce, uint8_t* out, int32_t* written, ErrorInfo* err);
 };
 
-DecoderStatus JxlHipAnimation::RunChunk(const AnimChunk& c, uint8_t* out, ErrorInfo* err) {
+DecoderStatus JxlHipAnimation::RunChunk(const AnimChunk& c, uint8_t* out, bool reduce, ErrorInfo* err) {
   if (anim.single) {   // one single-frame image: the ordinary decode, straight into the caller's buffer
+    if (c.stored == 0) return DecoderStatus_Ok;
+    // its thumbnail: the same decode into scratch, then the cell means of what it stored (reduce_displayed_kernel)
+    if (reduce && !d_single) HIP_OK(hipMalloc(&d_single, std::max<size_t>(image_bytes, 16)));
+    uint8_t* full = reduce ? d_single : out;
     ParsedFrame one = anim.frames[0];
     const uint8_t* host = nullptr;
     const size_t size = 0;
@@ -1152,8 +1164,14 @@ DecoderStatus JxlHipAnimation::RunChunk(const AnimChunk& c, uint8_t* out, ErrorI
     DecoderStatus st = DecoderStatus_Ok;
     ErrorInfo detail;
     detail.errorMessage[0] = 0;
-    dec->Decode(1, &host, &size, &dev, &out, nullptr, true, &st, &detail, &one);
+    dec->Decode(1, &host, &size, &dev, &full, nullptr, true, &st, &detail, &one);
     if (st != DecoderStatus_Ok) SetErr(err, "animation, codestream frame 0: %s", detail.errorMessage);
+    if (st == DecoderStatus_Ok && reduce) {
+      // (Decode has waited for its stream; the call returns when the means are stored)
+      LaunchReduceDisplayed(d_single, out, disp_w, disp_h, nch, out_bits, out_float, nullptr);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipStreamSynchronize(nullptr));
+    }
     return st;
   }
   ParsedFrame file = top;
@@ -1162,11 +1180,16 @@ DecoderStatus JxlHipAnimation::RunChunk(const AnimChunk& c, uint8_t* out, ErrorI
   lay->raw = anim.raw;
   lay->frames.assign(anim.frames.begin() + c.first, anim.frames.begin() + c.first + c.count);
   lay->save.assign(anim.save.begin() + c.first, anim.save.begin() + c.first + c.count);
-  for (int k = 0; k < c.count; k++) lay->show.push_back(anim.show[c.first + k] >= 0 ? anim.show[c.first + k] - c.first_shown : -1);
+  for (int k = 0; k < c.count; k++) {   // the images the plan selects, in the order they lie in `out`; every other frame stores nothing
+    const int j = anim.show[c.first + k];
+    const bool stored = j >= 0 && c.first_stored >= 0 && j >= c.first_stored && (j - c.first_stored) % c.step == 0;
+    lay->show.push_back(stored ? (j - c.first_stored) / c.step : -1);
+  }
+  lay->reduce = reduce;
   lay->live_in = c.live_in; lay->live_out = c.live_out;
   lay->slots_in = d_slots[cur_slots]; lay->slots_out = d_slots[cur_slots ^ 1];
   for (int s = 0; s < 4; s++) lay->slot_plane[s] = slot_plane[s];
-  lay->out_stride = image_bytes;
+  lay->out_stride = reduce ? reduced_bytes : image_bytes;
   file.layers = lay;
   const uint8_t* host = nullptr;
   const size_t size = 0;
@@ -1187,6 +1210,25 @@ DecoderStatus JxlHipAnimation::RunChunk(const AnimChunk& c, uint8_t* out, ErrorI
   return st;
 }
 
+// n images, every step-th from the position on, into `out` (image_bytes or reduced_bytes apart): DeliverImages' chunks, each one Decode.
+DecoderStatus JxlHipAnimation::Deliver(int n, int step, bool reduce, uint8_t* out, int32_t* written, ErrorInfo* err) {
+  DecoderStatus st = DecoderStatus_Ok;
+  try {
+    const size_t stride = reduce ? reduced_bytes : image_bytes;
+    DeliverImages(anim, plan, cur, n, step, chunk_frames, kAnimChunkScratch, [&](const AnimChunk& c, int done) {
+      st = RunChunk(c, out + (size_t)done * stride, reduce, err);
+      if (st == DecoderStatus_Ok && written) *written = done + c.stored;
+      return st == DecoderStatus_Ok;   // after a failure the position stays in front of the chunk
+    });
+    return st;
+  } catch (const std::bad_alloc&) {
+    return DecoderStatus_OutOfMemory;
+  } catch (const std::exception& e) {
+    SetErr(err, "%s", e.what());
+    return DecoderStatus_DecodeError;
+  }
+}
+
 extern "C" {
 
 JxlHipAnimation* jxlhip_animation_open(int32_t device, const uint8_t* data, size_t size, JxlHipAnimationInfo* info, ErrorInfo* err) {
@@ -1197,6 +1239,7 @@ JxlHipAnimation* jxlhip_animation_open(int32_t device, const uint8_t* data, size
     a->file.assign(data, data + size);
     ParseAnimation(a->file.data(), a->file.size(), false, a->anim);
     a->plan = PlanAnimation(a->anim);
+    a->entry_points = EntryPoints(a->anim, a->plan);
     ParsedFrame& head = a->anim.head;
     {
       auto cs_copy = std::move(head.cs_copy);
@@ -1208,6 +1251,9 @@ JxlHipAnimation* jxlhip_animation_open(int32_t device, const uint8_t* data, size
     for (auto& fr : a->anim.frames) { fr.cs_file_offset = 0; fr.cs_contiguous = true; }   // d_cs holds the codestream itself
     const size_t nch = OutSamplesPerPixel(head);
     a->image_bytes = (size_t)head.xsize * head.ysize * nch * OutBytesPerSample(head);
+    a->disp_w = (int)(head.orientation >= 5 ? head.ysize : head.xsize); a->disp_h = (int)(head.orientation >= 5 ? head.xsize : head.ysize);
+    a->nch = (int)nch; a->out_bits = 8 * (int)OutBytesPerSample(head); a->out_float = head.exp_bits ? 1 : 0;
+    a->reduced_bytes = (size_t)((a->disp_w + 7) / 8) * ((a->disp_h + 7) / 8) * nch * OutBytesPerSample(head);
     int live = 0, nslots = 0;
     for (int m : a->plan.live_after) live |= m;
     for (int s = 0; s < 4; s++) if (live >> s & 1) a->slot_plane[s] = nslots++;
@@ -1259,35 +1305,54 @@ int32_t jxlhip_animation_frame(JxlHipAnimation* a, int32_t j, JxlHipAnimationFra
 DecoderStatus jxlhip_animation_next(JxlHipAnimation* a, int32_t count, void* dev_out, size_t capacity, int32_t* written, ErrorInfo* err) {
   if (written) *written = 0;
   if (!a || (count > 0 && !dev_out)) return DecoderStatus_NullParameter;
-  try {
-    const int total = (int)a->anim.completes.size();
-    const int n = std::max(0, std::min(count, total - a->next_shown));
-    if ((size_t)n > capacity / std::max<size_t>(1, a->image_bytes)) {
-      SetErr(err, "the buffer holds %zu bytes, %d displayed images need %zu", capacity, n, (size_t)n * a->image_bytes);
-      return DecoderStatus_InvalidParameter;
-    }
-    const int last = a->next_shown + n - 1;
-    int done = 0;
-    while (a->next_shown <= last) {
-      const AnimChunk c = NextChunk(a->anim, a->plan, a->next_frame, last, a->chunk_frames, kAnimChunkScratch);
-      const DecoderStatus st = a->RunChunk(c, (uint8_t*)dev_out + (size_t)done * a->image_bytes, err);
-      if (st != DecoderStatus_Ok) return st;   // the position stays in front of the chunk
-      a->next_frame += c.count;
-      a->next_shown += c.shown;
-      done += c.shown;
-      if (written) *written = done;
-    }
-    return DecoderStatus_Ok;
-  } catch (const std::bad_alloc&) {
-    return DecoderStatus_OutOfMemory;
-  } catch (const std::exception& e) {
-    SetErr(err, "%s", e.what());
-    return DecoderStatus_DecodeError;
+  const int n = SelectedImages(a->anim, a->cur, count, 1);
+  if ((size_t)n > capacity / std::max<size_t>(1, a->image_bytes)) {
+    SetErr(err, "the buffer holds %zu bytes, %d displayed images need %zu", capacity, n, (size_t)n * a->image_bytes);
+    return DecoderStatus_InvalidParameter;
   }
+  return a->Deliver(n, 1, false, (uint8_t*)dev_out, written, err);
+}
+
+DecoderStatus jxlhip_animation_next_reduced(JxlHipAnimation* a, int32_t count, int32_t step, void* dev_out, size_t capacity, int32_t* written,
+                                            ErrorInfo* err) {
+  if (written) *written = 0;
+  if (!a || (count > 0 && !dev_out)) return DecoderStatus_NullParameter;
+  if (step < 1) {
+    SetErr(err, "step %d: every step-th image from the position on, step >= 1", step);
+    return DecoderStatus_InvalidParameter;
+  }
+  const int n = SelectedImages(a->anim, a->cur, count, step);
+  if ((size_t)n > capacity / std::max<size_t>(1, a->reduced_bytes)) {
+    SetErr(err, "the buffer holds %zu bytes, %d displayed images at 1:8 need %zu", capacity, n, (size_t)n * a->reduced_bytes);
+    return DecoderStatus_InvalidParameter;
+  }
+  return a->Deliver(n, step, true, (uint8_t*)dev_out, written, err);
+}
+
+DecoderStatus jxlhip_animation_seek(JxlHipAnimation* a, int32_t j, ErrorInfo* err) {
+  if (!a) return DecoderStatus_NullParameter;
+  if (!SeekCursor(a->anim, a->entry_points, a->cur, j)) {
+    SetErr(err, "seek to displayed image %d: the file has %d (0 .. %d, %d: the end)", j, (int)a->anim.completes.size(), (int)a->anim.completes.size() - 1,
+           (int)a->anim.completes.size());
+    return DecoderStatus_InvalidParameter;
+  }
+  return DecoderStatus_Ok;
+}
+
+int32_t jxlhip_animation_entry_points(JxlHipAnimation* a, int32_t* displayed, int32_t capacity) {
+  if (!a) return 0;
+  if (displayed)
+    for (int32_t i = 0; i < capacity && i < (int32_t)a->entry_points.size(); i++) displayed[i] = a->entry_points[i];
+  return (int32_t)a->entry_points.size();
+}
+
+void jxlhip_animation_position(JxlHipAnimation* a, int32_t* next_codestream_frame, int32_t* next_displayed) {
+  if (next_codestream_frame) *next_codestream_frame = a ? a->cur.frame : 0;
+  if (next_displayed) *next_displayed = a ? a->cur.shown : 0;
 }
 
 void jxlhip_animation_rewind(JxlHipAnimation* a) {
-  if (a) a->next_frame = a->next_shown = 0;   // (the first chunk loads no slot: nothing of the old state is read)
+  if (a) (void)SeekCursor(a->anim, a->entry_points, a->cur, 0);   // (image 0's chunk loads no slot: nothing of the old state is read)
 }
 
 int32_t jxlhip_animation_set_option(JxlHipAnimation* a, const char* name, int32_t value) {

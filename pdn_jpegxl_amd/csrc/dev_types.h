@@ -253,7 +253,8 @@ struct ComposeImage {
   int32_t w, h, nch, has_alpha;                 // canvas; nch = colour channels + alpha, alpha last
   int32_t premul, orientation, out_bits, out_float;
   int32_t first, count;                         // frames [first, first + count) of the frame table; a still: the last one is displayed (show 0)
-  int32_t raw, pad0;                            // raw: every frame replaces every channel; frames hold output-type samples (px as bytes)
+  int32_t raw, reduce;                          // raw: every frame replaces every channel; frames hold output-type samples (px as bytes)
+                                                // reduce: compose_reduce_kernel runs, and `out` holds 1:8 images
   // Animations decoded in chunks of frames: the reference slots that a later chunk reads travel through memory.  Slot s
   // of pixel p is the nch floats at slots[(slot_plane[s] * w * h + p) * nch] (raw images: bit patterns, as in registers; only the slots
   // that are alive at some cut of the file have a plane).  Bit s of live_in: the lane loads slot s at entry (the others start as 0); of

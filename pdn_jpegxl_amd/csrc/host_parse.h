@@ -204,6 +204,7 @@ struct Layers {
   const float* slots_in = nullptr;
   float* slots_out = nullptr;
   uint64_t out_stride = 0;
+  bool reduce = false;   // the displayed images leave at 1:8 (jxlhip_animation_next_reduced): compose_reduce_kernel, out_stride of that size
 };
 
 // Throws ParseError.  headers_only: stop after the frame header + TOC (jxlhip_peek / pass 1 of LoadImage).

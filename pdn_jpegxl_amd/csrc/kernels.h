@@ -55,6 +55,10 @@ void LaunchNoise(const DevImage* imgs, int nimg, int max_groups, int max_w, int 
 
 // compose_kernels.hip: blend the frames of `nimg` layered images (tables in device memory) and write their displayed images
 void LaunchCompose(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_segments, hipStream_t s);
+// The same frame loop with every displayed image stored at 1:8 (compose_reduce_kernel; max_cells: the most 8x8 cells of a displayed image)
+void LaunchComposeReduce(const ComposeImage* imgs, const ComposeFrame* frames, int nimg, int max_cells, hipStream_t s);
+// 8x8 cell means of a displayed image in memory: dw x dh pixels of nch samples -> ceil(dw / 8) x ceil(dh / 8), tight rows
+void LaunchReduceDisplayed(const uint8_t* src, uint8_t* dst, int dw, int dh, int nch, int out_bits, int out_float, hipStream_t s);
 // patch_kernels.hip: apply the patches of every patched frame of the batch in place (one workgroup per tile with positions)
 void LaunchPatches(const PatchFrame* frames, const PatchTile* tiles, int ntiles, const int32_t* list, const PatchPos* pos, const PatchRef* refs,
                    hipStream_t s);

@@ -887,6 +887,66 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_animation_plan(const uint8_t
   return 0;
 }
 
+// Seeking and thumbnails of an animation decode, without a GPU: the host logic of jxlhip_animation_seek / _next / _next_reduced
+// (animation.h: EntryPoints, SeekCursor, DeliverImages) run over a list of operations.  ops: nops triples (kind, a, b) - 0: seek a;
+// 1: next a (a <= 0: all that is left); 2: next_reduced a b (a <= 0: all that is left, b: the step).  chunk_frames, scratch_budget: as
+// jxlhip_selftest_animation_plan.  out, as numbers (returns how many; 0: the file is refused or they do not fit):
+//   entry points, then each of them;
+//   per operation: 1 (0: refused - a seek outside the file, a step < 1; nothing moved), and the position behind it: codestream frame,
+//   displayed image;
+//   chunks, then per chunk: the operation it belongs to, first frame, frames, first displayed image, displayed images, live_in, live_out,
+//   first stored image (-1: none), stored images, step (the chunk stores first stored + i * step).
+extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_animation_seek_plan(const uint8_t* data, size_t size, int32_t chunk_frames, int64_t scratch_budget,
+                                                                        const int32_t* ops, int32_t nops, int64_t* out, size_t capacity, int32_t* status,
+                                                                        ErrorInfo* err) {
+  if (status) *status = DecoderStatus_Ok;
+  try {
+    Animation a;
+    ParseAnimation(data, size, false, a);
+    const AnimPlan p = PlanAnimation(a);
+    const std::vector<int> entries = EntryPoints(a, p);
+    std::vector<int64_t> v, chunks;
+    v.push_back((int64_t)entries.size());
+    for (int e : entries) v.push_back(e);
+    AnimCursor cur;
+    int nchunks = 0;
+    const size_t budget = scratch_budget > 0 ? (size_t)scratch_budget : kAnimChunkScratch;
+    for (int op = 0; op < nops; op++) {
+      const int kind = ops[3 * op], x = ops[3 * op + 1], y = ops[3 * op + 2];
+      bool ok = true;
+      if (kind == 0) {
+        ok = SeekCursor(a, entries, cur, x);
+      } else {
+        const int step = kind == 2 ? y : 1;
+        ok = step >= 1;
+        if (ok) {
+          const int n = SelectedImages(a, cur, x <= 0 ? (int)a.completes.size() : x, step);
+          DeliverImages(a, p, cur, n, step, chunk_frames, budget, [&](const AnimChunk& c, int) {
+            for (int64_t q : {(int64_t)op, (int64_t)c.first, (int64_t)c.count, (int64_t)c.first_shown, (int64_t)c.shown, (int64_t)c.live_in, (int64_t)c.live_out,
+                              (int64_t)c.first_stored, (int64_t)c.stored, (int64_t)c.step})
+              chunks.push_back(q);
+            nchunks++;
+            return true;
+          });
+        }
+      }
+      for (int64_t q : {(int64_t)ok, (int64_t)cur.frame, (int64_t)cur.shown}) v.push_back(q);
+    }
+    v.push_back(nchunks);
+    v.insert(v.end(), chunks.begin(), chunks.end());
+    if (v.size() > capacity) return 0;
+    memcpy(out, v.data(), v.size() * sizeof(int64_t));
+    return v.size();
+  } catch (const ParseError& e) {
+    if (status) *status = e.status;
+    SetEncErr(err, e.what());
+  } catch (const std::exception& e) {
+    if (status) *status = DecoderStatus_DecodeError;
+    SetEncErr(err, e.what());
+  }
+  return 0;
+}
+
 // ---- animation encode (enc_animation.h, host_write.h): headers and geometry rules, host only
 
 // A bare codestream of the image header and one frame header as the encoder writes them, then the first bit of a TOC (not permuted)

@@ -6,7 +6,12 @@ files, alternating in one process, and prints the compositor's bytes (DESIGN.md 
   blend-cut8: the same file with the option "chunk_frames" = 8, so that slot 1 crosses three cuts (what a cut costs).
 Times are HIP events around the synchronous calls (host work included), best and median of `--rounds`; compose_kernel's time is the
 "compose" stage of the animation's decoder summed over the chunks of one pass.  The batch path runs no code this feature changed: it is
-the yardstick.  One JSON line per case; --out also writes them to a file (profiles/animation_bench.json)."""
+the yardstick.  One JSON line per case; --out also writes them to a file (profiles/animation_bench.json).
+
+Two further cases time random access and thumbnails on a file the product's own encoder writes - 4K RGBA lossless, 32 frames, a
+256 x 256 block moving over a background that changes at every key frame, key_interval 8, so the entry points are 0, 8, 16, 24:
+  seek:   seek(j); next(1) against rewind(); next(j + 1), for j = 7, 15, 20 and 31;
+  thumbs: rewind(); thumbnails of all 32 images (and of every fourth) against rewind(); next(32) at full size."""
 import argparse
 import json
 import os
@@ -118,6 +123,67 @@ def run(case, rounds, plan_only, chunk_frames=0):
     return line
 
 
+def keyed_file():
+    """The 32-frame file with key frames, and its entry points."""
+    import torch
+    blocks = [synth(min(256, W), min(256, H), 50 + s) for s in range(4)]
+    bgs = [torch.from_numpy(synth(W, H, 31 + s)).cuda() for s in range((N + 7) // 8)]
+    frames = []
+    for k in range(N):
+        f = bgs[k // 8].clone()
+        b = torch.from_numpy(blocks[k % 4]).cuda()
+        x, y = (97 * k) % max(1, W - b.shape[1]), (41 * k) % max(1, H - b.shape[0])
+        f[y:y + b.shape[0], x:x + b.shape[1]] = b
+        frames.append(f)
+    enc = api.Encoder(0)
+    try:
+        return enc.encode_animation(frames, 1, key_interval=8, lossless=True)
+    finally:
+        enc.close()
+
+
+def run_random_access(mode, rounds):
+    import torch
+    data = keyed_file()
+    line = {"case": "%s: %dx%d RGBA lossless, %d frames from encode_animation(key_interval=8)" % (mode, W, H, N), "file_bytes": len(data), "rounds": rounds}
+    with api.Animation(data) as a:
+        line["entry_points"] = a.entry_points
+        line["codestream_frames"] = a.info.num_codestream_frames
+        buf = torch.empty(N * a.info.image_bytes, dtype=torch.uint8, device="cuda")
+        n, err = api.C.c_int32(0), api.ErrorInfo()
+
+        def full(count, first=0):
+            a.seek(first)
+            st = a._L.jxlhip_animation_next(a._h, count, buf.data_ptr(), buf.numel(), api.C.byref(n), api.C.byref(err))
+            assert st == 0 and n.value == count, err.errorMessage
+
+        def reduced(step):
+            a.rewind()
+            st = a._L.jxlhip_animation_next_reduced(a._h, N, step, buf.data_ptr(), buf.numel(), api.C.byref(n), api.C.byref(err))
+            assert st == 0 and n.value == (N + step - 1) // step, err.errorMessage
+
+        def best_median(fn):
+            fn()   # warms (workspaces grow)
+            t = [timed(fn) for _ in range(rounds)]
+            return round(min(t), 3), round(statistics.median(t), 3)
+        if mode == "seek":
+            for j in [j for j in (7, 15, 20, 31) if j < N]:
+                a.rewind()   # (each timed seek starts from the front of the file, so it jumps to the entry point)
+                line["seek_%d_ms_best_median" % j] = best_median(lambda: (a.rewind(), full(1, j)))
+                line["sequential_to_%d_ms_best_median" % j] = best_median(lambda: full(j + 1))
+        else:
+            line["full_size_next_all_ms_best_median"] = best_median(lambda: full(N))
+            a.decoder_stage_totals(reset=True)
+            line["thumbnails_all_ms_best_median"] = best_median(lambda: reduced(1))
+            totals, chunks = a.decoder_stage_totals()
+            line["thumbnails_compose_ms_per_pass"] = round(totals.get("compose", 0.0) / (rounds + 1), 4)
+            line["thumbnails_every_4th_ms_best_median"] = best_median(lambda: reduced(4))
+            a.decoder_stage_totals(reset=True)
+            full(N)
+            line["full_size_compose_ms_per_pass"] = round(a.decoder_stage_totals()[0].get("compose", 0.0), 4)
+    return line
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("cases", nargs="*", default=["lossless", "lossy", "blend", "blend-cut8"])
@@ -132,7 +198,10 @@ if __name__ == "__main__":
     cases = {"lossless": (frames_lossless, 0), "lossy": (frames_lossy, 0), "blend": (frames_blend, 0), "blend-cut8": (frames_blend, 8)}
     lines = []
     for name in args.cases:
-        lines.append(run(cases[name][0], args.rounds, args.plan_only, cases[name][1]))
+        if name in ("seek", "thumbs"):
+            lines.append(run_random_access(name, args.rounds))
+        else:
+            lines.append(run(cases[name][0], args.rounds, args.plan_only, cases[name][1]))
         print(json.dumps(lines[-1]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
