@@ -165,13 +165,25 @@ JXLFILETYPEIO_API DecoderStatus jxlhip_peek(const uint8_t* data, size_t size, Jx
  * With the option "downscale" = 8 the image is written at ceil(width/8) x ceil(height/8) pixels instead (width, height as
  * jxlhip_peek reports them, i.e. as displayed), tight rows, same channels / sample type / colour encoding / orientation: the
  * buffer must hold ceil(width/8)*ceil(height/8)*num_channels*bytes_per_sample bytes and nothing behind them is written.
- * Work is enqueued on `stream` (a hipStream_t, may be NULL = default stream); the call returns after
- * enqueueing unless `synchronize` is non-zero.  Per-image status is written to statuses[i] on return when
- * synchronizing, otherwise by jxlhip_finish(). */
+ * The call returns after enqueueing unless `synchronize` is non-zero.  What `stream` (a hipStream_t, may be NULL = a stream of the
+ * decoder's own) orders, and what it does not:
+ *  - OUTPUTS are ordered on `stream`: every write to dev_out[i] is enqueued there or joined to it by an event, so work enqueued on
+ *    `stream` after the call sees the finished pixels, and the buffers may still be in use by work enqueued on `stream` before it.
+ *  - INPUT is not: the entropy stages run on streams of the decoder's own, and the LF pre-pass of a frame that fits one group runs
+ *    inside the call; both read dev_data[i] without waiting for `stream`.  Resident input must be COMPLETE when the call is made
+ *    (synchronise whatever produced it first), and stay untouched until the batch has finished.  host_data is read inside the call.
+ *  - Up to three batches are in flight on workspaces of their own; the call blocks the host while the batch three calls back has not
+ *    finished.  Options (jxlhip_set_option) are read at the call and hold for that batch.
+ * Per-file status is written to statuses[i] on return: final when synchronizing; otherwise only what the host found (parse errors,
+ * refusals, the LF pre-pass of one-group frames) - what the device finds is reported by jxlhip_finish(). */
 JXLFILETYPEIO_API DecoderStatus jxlhip_decode_batch(JxlHipDecoder* dec, int32_t n, const uint8_t* const* host_data,
                                                     const size_t* sizes, const uint8_t* const* dev_data, uint8_t* const* dev_out,
                                                     void* stream, int32_t synchronize, DecoderStatus* statuses, ErrorInfo* err);
-/* Waits for the last batch and collects device-side error flags. */
+/* Waits for every batch in flight, oldest first, and collects device-side error flags.  statuses (may be NULL): one entry per file
+ * of the MOST RECENT batch.  Returns that batch's first status that is not Ok, with its message in err.  When that batch is Ok but
+ * an older asynchronous batch failed that nobody has been told of, returns the older batch's status and "an earlier asynchronous
+ * batch failed: " followed by the same text that batch would have reported (the image number counts within its own batch); this
+ * is reported once.  With nothing in flight, or no batch ever decoded, the call returns at once. */
 JXLFILETYPEIO_API DecoderStatus jxlhip_finish(JxlHipDecoder* dec, DecoderStatus* statuses, ErrorInfo* err);
 
 /* Stage taps of the most recent (synchronised) batch, image `index`, for parity tests.  `name` as in

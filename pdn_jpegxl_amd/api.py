@@ -544,6 +544,8 @@ class Decoder:
 
     def __init__(self, device=-1):
         self._h = None
+        self._last_n = self._max_n = 0      # files of the last decode_batch call / of the largest one (finish's status buffer)
+        self.last_error = ""
         self._L = lib()
         err = ErrorInfo()
         self._h = self._L.jxlhip_decoder_create(device, C.byref(err))
@@ -578,18 +580,28 @@ class Decoder:
         st = (C.c_int32 * n)()
         err = ErrorInfo()
         self._keep = (hd, sz, dd, do)
+        self._last_n, self._max_n = n, max(n, self._max_n)   # (finish: a batch that failed to submit leaves the one before it the most recent)
         r = self._L.jxlhip_decode_batch(self._h, n, hd, sz, dd, do, stream, 1 if synchronize else 0, st, C.byref(err))
         self.last_error = err.errorMessage.decode("ascii", "replace")
         if r != 0 and raise_on_error:
             raise FormatError(DECODER_STATUS[r] if 0 <= r < len(DECODER_STATUS) else str(r), self.last_error)
         return list(st)
 
-    def finish(self):
-        """Waits for every asynchronous batch; raises if any of them failed."""
+    def finish(self, raise_on_error=True):
+        """Waits for every asynchronous batch, oldest first.  Returns (status name, per-file statuses of the most recent batch), the
+        message in last_error.  The status is the most recent batch's or, that one being Ok, that of an older batch whose failure has
+        not been reported yet ("an earlier asynchronous batch failed: ...", reported once); with raise_on_error it raises FormatError
+        instead of returning a status that is not Ok.  (The list has one entry per file of the last decode_batch call; after a call
+        that failed before it submitted anything, the batch before it is the most recent one and the list's length is not its.)"""
+        n = self._last_n
+        st = (C.c_int32 * max(self._max_n, 1))()
         err = ErrorInfo()
-        r = self._L.jxlhip_finish(self._h, None, C.byref(err))
-        if r != 0:
-            raise FormatError(DECODER_STATUS[r], err.errorMessage.decode("ascii", "replace"))
+        r = self._L.jxlhip_finish(self._h, st if n else None, C.byref(err))
+        self.last_error = err.errorMessage.decode("ascii", "replace")
+        name = DECODER_STATUS[r] if 0 <= r < len(DECODER_STATUS) else str(r)
+        if r != 0 and raise_on_error:
+            raise FormatError(name, self.last_error)
+        return name, list(st[:n])
 
     def read_plane(self, index, name, channel=0):
         n = self._L.jxlhip_read_plane(self._h, index, name.encode(), channel, None, 0)

@@ -160,6 +160,9 @@ struct JxlHipDecoder {
   void EnsureBlob(size_t bytes);
   void Mark(const char* name, hipStream_t s, int chain);
   void WaitSlot(Slot& S);
+  static DecoderStatus ImageStatus(const Slot& S, int i);
+  static std::string FailureText(const Slot& S, int i);
+  void NoteOlderFailure(Slot& S);
   Slot& Last() { return slots[last]; }
   // preparsed (a chunk of an animation, JxlHipAnimation::RunChunk): the parse of the call's one file - a single frame, or a layered file
   // whose Layers carry the chunk's frames; it is moved from, and no host bytes are read.
@@ -254,6 +257,10 @@ JxlHipDecoder::JxlHipDecoder(int dev) {
 
 JxlHipDecoder::~JxlHipDecoder() {
   (void)hipSetDevice(device);
+  // batches still in flight read and write the slots' memory and record the slots' events: every pending one is waited for by name
+  // (errors ignored: a failed batch is over as well) before anything of its slot goes
+  for (auto& S : slots)
+    if (S.pending && S.done) { (void)hipEventSynchronize(S.done); S.pending = false; }
   (void)hipDeviceSynchronize();
   for (auto& S : slots) {
     for (auto e : S.events) (void)hipEventDestroy(e);
@@ -355,6 +362,36 @@ void JxlHipDecoder::WaitSlot(Slot& S) {
   total_batches++;
 }
 
+// Status of image i of a finished batch: the host's (parse, refusal) or, for an image that went to the device, what its status words say.
+DecoderStatus JxlHipDecoder::ImageStatus(const Slot& S, int i) {
+  const DecoderStatus st = (DecoderStatus)S.parse_status[i];
+  if (st == DecoderStatus_Ok && S.h_status[(size_t)i * 16]) return DecoderStatus_DecodeError;
+  return st;
+}
+
+// What went wrong with image i of a finished batch (ImageStatus != Ok): the host's message, or the device's flags, the caller's file
+// and the failing sections.  One text for the last batch's error and for the sticky error of an older one.
+std::string JxlHipDecoder::FailureText(const Slot& S, int i) {
+  if (S.parse_status[i] != DecoderStatus_Ok) return S.parse_msg[i];
+  const int file = S.file_of.empty() ? i : S.file_of[i];
+  const uint32_t* w = S.h_status + (size_t)i * 16;   // [3..7]: last failing section + 1 of lf_ans / lf_finish / hf_decode / alpha_ans / modular
+  const uint32_t bits = w[0];
+  char buf[256];
+  if (bits & kErrUnsupportedTransform) snprintf(buf, sizeof(buf), "AFV transforms are not supported (image %d, LF group section %u)", file, w[4]);
+  else snprintf(buf, sizeof(buf), "GPU decode failed (flags 0x%x:%s%s%s%s%s; image %d, sections lf %u hf %u alpha %u)", bits, bits & kErrBitstream ? " corrupt-bitstream" : "",
+                bits & kErrUnsupportedHeader ? " unsupported-modular-header" : "", bits & kErrUnsupportedTree ? " unsupported-tree" : "",
+                bits & kErrBlockLayout ? " invalid-varblock-layout" : "", bits & kErrRange ? " value-out-of-range" : "", file, w[3], w[5], w[6]);
+  return buf;
+}
+
+// The first failure of a finished batch that is not the most recent one becomes the sticky error, unless an older one is already kept.
+void JxlHipDecoder::NoteOlderFailure(Slot& S) {
+  for (int i = 0; i < S.n && sticky_status == DecoderStatus_Ok; i++) {
+    const DecoderStatus st = ImageStatus(S, i);
+    if (st != DecoderStatus_Ok) { sticky_status = st; sticky_error = "an earlier asynchronous batch failed: " + FailureText(S, i); }
+  }
+}
+
 // The entropy plan's options: this object's, and the experiment knobs' values.
 EntropyPlanOptions JxlHipDecoder::PlanOptions() const {
   EntropyPlanOptions o;
@@ -379,11 +416,7 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   if (S.pending) {
     // the slot is reused: its previous batch must be complete; remember a failure nobody has looked at yet
     WaitSlot(S);
-    for (int i = 0; i < S.n; i++) {
-      int st = S.parse_status[i];
-      if (st == DecoderStatus_Ok && S.h_status[(size_t)i * 16]) st = DecoderStatus_DecodeError;
-      if (st != DecoderStatus_Ok && sticky_status == DecoderStatus_Ok) { sticky_status = st; sticky_error = "an earlier asynchronous batch failed: " + S.parse_msg[i]; }
-    }
+    NoteOlderFailure(S);
   }
   auto& d_ws = S.d_ws; auto& d_blob = S.d_blob; auto& h_blob = S.h_blob; auto& h_status = S.h_status; auto& h_status_cap = S.h_status_cap;
   auto& n = S.n; auto& frames = S.frames; auto& imgs = S.imgs; auto& parse_status = S.parse_status; auto& parse_msg = S.parse_msg;
@@ -816,11 +849,7 @@ DecoderStatus JxlHipDecoder::Finish(DecoderStatus* statuses, ErrorInfo* err) {
     Slot& O = slots[(last + k) % kSlots];
     if (!O.pending) continue;
     WaitSlot(O);
-    for (int i = 0; i < O.n; i++) {
-      int st = O.parse_status[i];
-      if (st == DecoderStatus_Ok && O.h_status[(size_t)i * 16]) st = DecoderStatus_DecodeError;
-      if (st != DecoderStatus_Ok && sticky_status == DecoderStatus_Ok) { sticky_status = st; sticky_error = "an earlier asynchronous batch failed: " + O.parse_msg[i]; }
-    }
+    NoteOlderFailure(O);
   }
   Slot& S = Last();
   WaitSlot(S);
@@ -829,20 +858,8 @@ DecoderStatus JxlHipDecoder::Finish(DecoderStatus* statuses, ErrorInfo* err) {
   std::vector<DecoderStatus> file_st((size_t)S.nfiles, DecoderStatus_Ok);
   for (int i = 0; i < S.n; i++) {
     const int file = S.file_of.empty() ? i : S.file_of[i];
-    DecoderStatus st = S.parse_status[i];
-    if (st != DecoderStatus_Ok) {
-      if (worst == DecoderStatus_Ok) SetErr(err, "%s", S.parse_msg[i].c_str());
-    } else if (S.h_status[(size_t)i * 16]) {
-      uint32_t bits = S.h_status[(size_t)i * 16];
-      st = DecoderStatus_DecodeError;
-      if (worst == DecoderStatus_Ok) {
-        const uint32_t* w = S.h_status + (size_t)i * 16;   // [3..7]: last failing section + 1 of lf_ans / lf_finish / hf_decode / alpha_ans / modular
-        if (bits & kErrUnsupportedTransform) SetErr(err, "AFV transforms are not supported (image %d, LF group section %u)", file, w[4]);
-        else SetErr(err, "GPU decode failed (flags 0x%x:%s%s%s%s%s; image %d, sections lf %u hf %u alpha %u)", bits, bits & kErrBitstream ? " corrupt-bitstream" : "",
-               bits & kErrUnsupportedHeader ? " unsupported-modular-header" : "", bits & kErrUnsupportedTree ? " unsupported-tree" : "",
-               bits & kErrBlockLayout ? " invalid-varblock-layout" : "", bits & kErrRange ? " value-out-of-range" : "", file, w[3], w[5], w[6]);
-      }
-    }
+    const DecoderStatus st = ImageStatus(S, i);
+    if (st != DecoderStatus_Ok && worst == DecoderStatus_Ok) SetErr(err, "%s", FailureText(S, i).c_str());
     if (st != DecoderStatus_Ok && file_st[file] == DecoderStatus_Ok) file_st[file] = st;
     if (st != DecoderStatus_Ok && worst == DecoderStatus_Ok) worst = st;
   }
