@@ -20,7 +20,7 @@
  *
  * Part 5 (jxlhip_animation_*) decodes every displayed image of an animated file into device memory, in file order.
  *
- * Part 6 (jxlhip_encode_animation, jxlhip_encode_animation_rects) encodes a stack of device-resident frames as one animated file: each
+ * Part 6 (jxlhip_encode_animation, jxlhip_encode_animation_rects, jxlhip_encode_animation_changes) encodes a stack of device-resident frames as one animated file: each
  * frame as what changed, in one rectangle or in several.
  */
 #ifndef JXLFILETYPEIO_H_
@@ -477,14 +477,45 @@ JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_frame_rects(JxlHipEncoder* en
 /* The tile table of pair `pair` (frames pair and pair + 1) of the last animation encoded with max_rects >= 2: one word per 64 x 64 tile,
  * row-major over ceil(width / 64) x ceil(height / 64) tiles, holding the bytes x0, y0, x1, y1 (lowest first; inclusive, relative to the
  * tile's origin) of the box of the changed pixels in the tile, 0xFFFFFFFF where none changed.  Up to `capacity` words are written to
- * dst.  Returns the number of tiles (0: no such pair, or max_rects was 1). */
+ * dst.  Returns the number of tiles (0: no such pair, or max_rects was 1 and there was no tolerance).
+ * With a tolerance > 0 (jxlhip_encode_animation_changes) it is the table of frame pair + 1 against the reference canvas as it stood before
+ * that frame, and there is one for every pair whatever max_rects is, key frames included (a key frame is measured, then written whole). */
 JXLFILETYPEIO_API int32_t jxlhip_encoder_animation_tiles(JxlHipEncoder* enc, int32_t pair, uint32_t* dst, int32_t capacity);
+
+/* A tolerance for "unchanged".  The bits decide above, so one count of sensor noise per sample makes every frame be written whole.
+ * With tolerance > 0 a frame is compared not with its predecessor but with what a decoder SHOWS: the encoder keeps a reference canvas R
+ * on the device (tight rows, the frames' pixel format), which starts as frame 0.  For k = 1 .. n - 1 in order: the tile table of frame k
+ * against R is measured; the rectangles follow from it by the rules above (max_rects = 1: the table's bounding box; a key frame: the
+ * canvas); then R takes frame k's pixels inside each of those rectangles - the 1 x 1 rectangle of a frame in which nothing changed and,
+ * for lossy frames, the rectangles grown to the 8-pixel grid included: the pixels a decoder replaces.  So R is the source of exactly
+ * what is shown, and before coding error no displayed sample is further than the tolerance from its source sample, in any frame (a
+ * tolerance against the predecessor would let a slow fade drift without bound).  The rectangles are still coded from the caller's frame
+ * k; headers, slots, durations and chunking are as above.
+ * The tolerance holds for every sample of every channel, alpha included.  A pixel is changed when one of its samples is:
+ *  - integer samples: changed when |a - b| > floor(tolerance), on the stored values (bits_per_sample plays no part);
+ *  - binary16 / binary32: unchanged when the bit patterns are equal, or when both values are finite and |a - b| <= tolerance, the
+ *    subtraction in binary32 (binary16 widened first); changed otherwise.  So +0 and -0 are unchanged, equal NaN patterns are, and a NaN
+ *    or an infinity against anything else is changed.
+ * tolerance == 0 is jxlhip_encode_animation_rects byte for byte (the bit rule against the predecessor, measured in one launch).
+ * Lossless is allowed together with a tolerance: every coded rectangle is exact and the rest of the canvas is within the tolerance of
+ * its source - the file is no longer a lossless copy of the frames. */
+typedef struct JxlHipAnimationChangeOptions {
+  float tolerance;       /* >= 0 and finite; 0: the bits decide */
+} JxlHipAnimationChangeOptions;
+
+/* jxlhip_encode_animation_rects with `changes` (jxlhip_encode_animation_rects is this call with {0}).  Refused in addition, on the host,
+ * in words and before any device work: a negative, NaN or infinite tolerance. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_changes(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                                const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                                const JxlHipAnimationRectOptions* rects, const JxlHipAnimationChangeOptions* changes,
+                                                                const EncoderImageMetadata* metadata, ErrorInfo* err);
 
 #ifdef __cplusplus
 }
 static_assert(sizeof(JxlHipPixels) == 40, "JxlHipPixels layout");
 static_assert(sizeof(JxlHipAnimationOptions) == 20, "JxlHipAnimationOptions layout");
 static_assert(sizeof(JxlHipAnimationRectOptions) == 8, "JxlHipAnimationRectOptions layout");
+static_assert(sizeof(JxlHipAnimationChangeOptions) == 4, "JxlHipAnimationChangeOptions layout");
 static_assert(sizeof(JxlHipAnimationInfo) == 64, "JxlHipAnimationInfo layout");
 static_assert(sizeof(JxlHipAnimationFrame) == 1096, "JxlHipAnimationFrame layout");
 static_assert(sizeof(BitmapData) == 24, "BitmapData layout");

@@ -85,6 +85,10 @@ class AnimationRectOptions(C.Structure):
     _fields_ = [("max_rects", C.c_int32), ("merge_pixels", C.c_int32)]
 
 
+class AnimationChangeOptions(C.Structure):
+    _fields_ = [("tolerance", C.c_float)]
+
+
 class AnimationInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("num_channels", C.c_int32), ("has_alpha", C.c_int32),
                 ("bytes_per_sample", C.c_int32), ("float_samples", C.c_int32), ("bits_per_sample", C.c_int32), ("have_animation", C.c_int32),
@@ -102,7 +106,7 @@ EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jx
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
            "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
            "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_encode_animation", "jxlhip_encoder_animation_rects", "jxlhip_encode_animation_rects",
-           "jxlhip_encoder_animation_frame_rects", "jxlhip_encoder_animation_tiles", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
+           "jxlhip_encoder_animation_frame_rects", "jxlhip_encoder_animation_tiles", "jxlhip_encode_animation_changes", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
            "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder", "jxlhip_animation_entry_points",
            "jxlhip_animation_seek", "jxlhip_animation_position", "jxlhip_animation_next_reduced"]
 
@@ -209,6 +213,10 @@ def lib(build_if_missing=True):
     L.jxlhip_encode_animation_rects.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(C.c_uint32), C.POINTER(EncoderOptions),
                                                 C.POINTER(AnimationOptions), C.POINTER(AnimationRectOptions), C.POINTER(EncoderImageMetadata),
                                                 C.POINTER(ErrorInfo)]
+    L.jxlhip_encode_animation_changes.restype = C.c_int32
+    L.jxlhip_encode_animation_changes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(C.c_uint32), C.POINTER(EncoderOptions),
+                                                  C.POINTER(AnimationOptions), C.POINTER(AnimationRectOptions), C.POINTER(AnimationChangeOptions),
+                                                  C.POINTER(EncoderImageMetadata), C.POINTER(ErrorInfo)]
     L.jxlhip_encoder_animation_frame_rects.restype = C.c_int32
     L.jxlhip_encoder_animation_frame_rects.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.jxlhip_encoder_animation_tiles.restype = C.c_int32
@@ -712,8 +720,8 @@ class Encoder:
         return out
 
     def encode_animation(self, frames, durations, tps=(100, 1), loops=0, key_interval=0, chunk_frames=0, distance=1.0, effort=7,
-                         lossless=False, colour=None, bits=None, exif=None, xmp=None, max_rects=1, merge_pixels=4096):
-        """jxlhip_encode_animation_rects: the frames as ONE animated file (bytes).  frames: a list of EncodeItem / GPU tensors (h, w[, c]), or
+                         lossless=False, colour=None, bits=None, exif=None, xmp=None, max_rects=1, merge_pixels=4096, tolerance=0.0):
+        """jxlhip_encode_animation_changes: the frames as ONE animated file (bytes).  frames: a list of EncodeItem / GPU tensors (h, w[, c]), or
         one GPU tensor [n, h, w, c]; all of one size, channel count and sample type.  durations: ticks per frame (>= 1), one per frame
         or one number for all; tps: ticks per second as (numerator, denominator); loops: 0 = endless.  Frame 0 - and with
         key_interval >= 1 every key_interval-th frame - is written whole, every other frame as the rectangle that changed against its
@@ -722,7 +730,14 @@ class Encoder:
         disjoint rectangles - the groups of touching changed tiles, merged while there are too many or while merging two codes at
         most merge_pixels pixels more - each a frame of the codestream, all but the last without a duration;
         last_animation_frame_rects has them, last_animation_tiles(pair) the tile map.  max_rects = 1 is jxlhip_encode_animation byte
-        for byte (merge_pixels plays no part).  chunk_frames: codestream frames that go through the encoder at a time (0: by its workspace budget; the bytes do not depend on it).
+        for byte (merge_pixels plays no part).  tolerance > 0: a sample counts as changed only when it moved by more than the tolerance
+        (integers: by more than floor(tolerance); floats: equal bits, or both finite and |a - b| <= tolerance in binary32, are
+        unchanged) - every sample of every channel, alpha included - and a frame is compared not with its predecessor but with a
+        reference canvas on the device that holds the source of what a decoder shows: frame 0, then each written rectangle (the 1 x 1
+        of an unchanged frame and the lossy growth to the 8-pixel grid included) copied in.  So no displayed sample is further than
+        the tolerance from its source, before coding error, in any frame; with lossless=True the coded rectangles are exact and the
+        rest is within the tolerance.  last_animation_tiles(pair) then has a map for every pair whatever max_rects is.  tolerance = 0
+        (the default) is the bit rule against the predecessor, byte for byte the file without the argument.  chunk_frames: codestream frames that go through the encoder at a time (0: by its workspace budget; the bytes do not depend on it).
         distance, effort, lossless hold for every frame; colour and bits default to those of the first EncodeItem (tensors: "Srgb",
         8 / 16 bits).  Raises JxlError where the call is refused or fails; the encoder stays usable."""
         if hasattr(frames, "dim") and not isinstance(frames, (list, tuple)):
@@ -744,7 +759,8 @@ class Encoder:
         md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in bufs), []))
         err = ErrorInfo()
         ro = AnimationRectOptions(int(max_rects), int(merge_pixels))
-        r = self._L.jxlhip_encode_animation_rects(self._h, n, px, dur, C.byref(opt), C.byref(ao), C.byref(ro), C.byref(md), C.byref(err))
+        co = AnimationChangeOptions(float(tolerance))
+        r = self._L.jxlhip_encode_animation_changes(self._h, n, px, dur, C.byref(opt), C.byref(ao), C.byref(ro), C.byref(co), C.byref(md), C.byref(err))
         self.last_error = err.errorMessage.decode("ascii", "replace")
         if r != 0:
             raise JxlError(ENCODER_STATUS[r] if 0 <= r < len(ENCODER_STATUS) else str(r), self.last_error)
@@ -773,10 +789,12 @@ class Encoder:
     def last_animation_tiles(self, pair):
         """The tile map of frames `pair` and `pair + 1` of the last encode_animation with max_rects >= 2: a (tiles down, tiles across,
         4) uint8 array of x0, y0, x1, y1 - the inclusive box, relative to the tile, of the changed pixels in each 64 x 64 tile - with
-        255 everywhere for a tile in which nothing changed.  Raises ValueError where there is no such pair."""
+        255 everywhere for a tile in which nothing changed.  With a tolerance > 0: the map of frame `pair + 1` against the reference
+        canvas as it stood before that frame, for every pair whatever max_rects was, key frames included.  Raises ValueError where
+        there is no such pair."""
         n = self._L.jxlhip_encoder_animation_tiles(self._h, int(pair), None, 0)
         if n == 0:
-            raise ValueError("no tile map for pair %d: the last animation has no such pair or was encoded with max_rects = 1" % pair)
+            raise ValueError("no tile map for pair %d: the last animation has no such pair or was encoded with max_rects = 1 and no tolerance" % pair)
         buf = np.zeros(n, np.uint32)
         self._L.jxlhip_encoder_animation_tiles(self._h, int(pair), buf.ctypes.data_as(C.POINTER(C.c_uint32)), n)
         rects = self.last_animation_rects

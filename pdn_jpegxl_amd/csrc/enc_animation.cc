@@ -76,6 +76,12 @@ const char* AnimRectOptionsRefusal(int32_t max_rects, int32_t merge_pixels) {
   return nullptr;
 }
 
+const char* AnimToleranceRefusal(float tolerance) {
+  if (tolerance != tolerance || tolerance - tolerance != 0.f) return "the tolerance must be a finite number";
+  if (tolerance < 0.f) return "the tolerance must not be negative";
+  return nullptr;
+}
+
 AnimExtent AnimTilesExtent(const uint32_t* tiles, int32_t w, int32_t h) {
   const int32_t nx = (int32_t)AnimTilesAcross(w), ny = (int32_t)AnimTilesAcross(h);
   AnimExtent e{-1, -1, -1, -1};

@@ -1,7 +1,8 @@
 // Animation encode: what a frame of an animation covers and what its header says, decided on the host from the
 // change extents - or, for several rectangles per frame, the tile change map - that enc_animation_kernels.hip measures.  Host-only
 // and stated once: the encoder (encoder.cc) and the test library
-// (selftest.cc) both go through these functions.
+// (selftest.cc) both go through these functions.  (The one rule shared with the device - when a sample counts as changed under a
+// tolerance - is at the end.)
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -76,5 +77,65 @@ const char* AnimRectOptionsRefusal(int32_t max_rects, int32_t merge_pixels);
 // npairs x AnimTilesAcross(h) x AnimTilesAcross(w) words; every word is written, nothing need be set beforehand), one launch.  Rows are
 // w pixels of pixel_bytes (1 .. 16) bytes.
 void LaunchAnimTiles(const AnimFrameSrc* frames, int32_t npairs, int32_t w, int32_t h, uint32_t pixel_bytes, uint32_t* out, void* stream);
+
+// ---- a tolerance for "unchanged" (tolerance > 0): frame k is measured against the reference canvas R - the source of exactly what a
+// decoder shows before frame k: frame 0, then every written rectangle copied in - not against frame k - 1 (DESIGN.md §2 "Animation
+// encode").  The rule of one sample is stated here once, for the kernel, the host and the test library.
+
+enum AnimSample : int32_t { kAnimU8 = 0, kAnimU16 = 1, kAnimF16 = 2, kAnimF32 = 3 };
+inline uint32_t AnimSampleBytes(AnimSample kind) { return kind == kAnimU8 ? 1 : (kind == kAnimF32 ? 4 : 2); }
+
+// Why a call with this tolerance is refused, in words; nullptr: it is not.
+const char* AnimToleranceRefusal(float tolerance);
+
+// What an integer sample may move by: floor(tolerance), at most the range of the widest integer sample.
+__host__ __device__ inline uint32_t AnimIntTolerance(float tolerance) { return tolerance >= 65535.f ? 65535u : (uint32_t)tolerance; }
+
+// Integer samples (the stored values; bits_per_sample plays no part): changed when |a - b| > floor(tolerance).
+__host__ __device__ inline bool AnimIntChanged(uint32_t a, uint32_t b, uint32_t int_tolerance) { return (a > b ? a - b : b - a) > int_tolerance; }
+
+// binary32 samples by their bits: unchanged when the bits are equal, or when both are finite and |a - b| <= tolerance (so +0 and -0
+// are unchanged, equal NaN patterns are, NaN or an infinity against anything else is changed).
+__host__ __device__ inline bool AnimFloatChanged(uint32_t a, uint32_t b, float tolerance) {
+  if (a == b) return false;
+  if ((a & 0x7F800000u) == 0x7F800000u || (b & 0x7F800000u) == 0x7F800000u) return true;
+  float fa, fb;
+  __builtin_memcpy(&fa, &a, 4);
+  __builtin_memcpy(&fb, &b, 4);
+  return !(__builtin_fabsf(fa - fb) <= tolerance);
+}
+
+// binary16 bits widened to binary32 bits (exact)
+__host__ __device__ inline uint32_t AnimHalfBits(uint32_t h) {
+  _Float16 v;
+  const uint16_t b = (uint16_t)h;
+  __builtin_memcpy(&v, &b, 2);
+  const float f = (float)v;
+  uint32_t out;
+  __builtin_memcpy(&out, &f, 4);
+  return out;
+}
+
+// binary16: equal bits are unchanged; otherwise the binary32 rule on the widened values
+__host__ __device__ inline bool AnimHalfChanged(uint32_t a, uint32_t b, float tolerance) {
+  return a != b && AnimFloatChanged(AnimHalfBits(a), AnimHalfBits(b), tolerance);
+}
+
+// One sample (its bits in the low bytes of a and b) of either kind
+__host__ __device__ inline bool AnimSampleChanged(AnimSample kind, uint32_t a, uint32_t b, float tolerance) {
+  if (kind == kAnimF32) return AnimFloatChanged(a, b, tolerance);
+  if (kind == kAnimF16) return AnimHalfChanged(a, b, tolerance);
+  return AnimIntChanged(a, b, AnimIntTolerance(tolerance));
+}
+
+// enc_animation_kernels.hip: the tile table of ONE frame (device rows `frame.stride` bytes apart, any sample-aligned base) against the
+// reference canvas `ref` (device, tight rows of w pixel_bytes bytes) into `out` (device, AnimTilesAcross(h) x AnimTilesAcross(w) words, every
+// word written): the words of LaunchAnimTiles, with "differs" meaning AnimSampleChanged.  pixel_bytes: channels x AnimSampleBytes(kind).
+void LaunchAnimTilesTol(AnimFrameSrc frame, const uint8_t* ref, int32_t w, int32_t h, uint32_t pixel_bytes, AnimSample kind, float tolerance,
+                        uint32_t* out, void* stream);
+
+// enc_animation_kernels.hip: the pixels of `frame` inside the nrects (1 .. kAnimMaxRects) rectangles, each inside the w x h canvas, copied
+// into the reference canvas `ref` (tight rows), one launch.  A key frame: the canvas as the one rectangle.
+void LaunchAnimApplyRects(AnimFrameSrc frame, uint8_t* ref, int32_t w, uint32_t pixel_bytes, const AnimRect* rects, int32_t nrects, void* stream);
 
 }  // namespace jxlhip

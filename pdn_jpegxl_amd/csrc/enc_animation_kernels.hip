@@ -1,5 +1,7 @@
 // HIP kernels (gfx950) of animation encode: what changed between consecutive frames - as one box per pair
-// (anim_extents_kernel, max_rects = 1) or as a box per pair and 64 x 64 tile (anim_tiles_kernel, further down, max_rects >= 2).
+// (anim_extents_kernel, max_rects = 1) or as a box per pair and 64 x 64 tile (anim_tiles_kernel, further down, max_rects >= 2).  With a
+// tolerance for "unchanged", at the end: one frame against the reference canvas per tile (anim_tiles_tol_kernel), and the canvas taking
+// the rectangles that were written (anim_apply_rects_kernel).
 //
 // anim_extents_kernel: for every pair (frame k - 1, frame k) the bounding box of the samples whose BITS differ (+0.0 and -0.0 differ,
 // equal NaN patterns do not, a changed alpha sample counts like any other).  It reads the caller's memory as it lies: any base
@@ -232,7 +234,190 @@ __global__ __launch_bounds__(kTileThreads) void anim_tiles_kernel(const AnimFram
   }
 }
 
+// ---- anim_tiles_tol_kernel: the tile table of ONE frame against the reference canvas R under a tolerance (enc_animation.h:
+// AnimSampleChanged; DESIGN.md §2 "Animation encode").  The skeleton is anim_tiles_kernel's - a workgroup per tile row and group of whole
+// tile columns, a lane per 16-byte chunk counted from the row's start (sample-aligned for 1-, 2- and 4-byte samples whatever the pixel
+// size), eight rows of both operands loaded before any is looked at, the chunk the row's end cuts loaded as the row's last 16 bytes, rows
+// under 16 bytes by one thread, one LDS table, one plain store per tile word - and only "differs" is another thing: instead of a XOR b,
+// a comparator per sample type gives the four dwords in which every byte of a changed sample is 0xFF, and MarkTileChunk takes them from
+// there.  The frame's rows have any stride and any sample-aligned base; R's rows are tight.  No byte outside a row is loaded.
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+
+// Per 16-bit half of a dword: 0xFFFF where |a - b| > tol (tol2: tol in both halves), packed arithmetic throughout
+__device__ __forceinline__ uint32_t Over16(uint32_t a, uint32_t b, uint32_t tol2) {
+  u16x2 va, vb, vt;
+  __builtin_memcpy(&va, &a, 4);
+  __builtin_memcpy(&vb, &b, 4);
+  __builtin_memcpy(&vt, &tol2, 4);
+  const u16x2 d = __builtin_elementwise_max(va, vb) - __builtin_elementwise_min(va, vb);
+  const u16x2 over = __builtin_elementwise_sub_sat(d, vt);           // > 0 where the half moved by more than tol
+  const u16x2 m = (u16x2){0, 0} - __builtin_elementwise_min(over, (u16x2){1, 1});
+  uint32_t out;
+  __builtin_memcpy(&out, &m, 4);
+  return out;
+}
+
+// Per byte of a dword: 0xFF where |a - b| > tol - the even and the odd bytes as two dwords of 16-bit halves
+__device__ __forceinline__ uint32_t Over8(uint32_t a, uint32_t b, uint32_t tol2) {
+  const uint32_t even = Over16(a & 0x00FF00FFu, b & 0x00FF00FFu, tol2) & 0x00FF00FFu;
+  const uint32_t odd = Over16(a >> 8 & 0x00FF00FFu, b >> 8 & 0x00FF00FFu, tol2) & 0x00FF00FFu;
+  return even | odd << 8;
+}
+
+// The dword of "changed" bytes of one dword of samples.  tol: floor(tolerance) in both halves (integers), the tolerance's bits (floats).
+template <int KIND> __device__ __forceinline__ uint32_t ChangedDword(uint32_t a, uint32_t b, uint32_t tol) {
+  if (KIND == kAnimU8) return Over8(a, b, tol);
+  if (KIND == kAnimU16) return Over16(a, b, tol);
+  if (a == b) return 0;
+  const float t = __uint_as_float(tol);
+  if (KIND == kAnimF32) return AnimFloatChanged(a, b, t) ? 0xFFFFFFFFu : 0u;
+  return (AnimHalfChanged(a & 0xFFFFu, b & 0xFFFFu, t) ? 0x0000FFFFu : 0u) | (AnimHalfChanged(a >> 16, b >> 16, t) ? 0xFFFF0000u : 0u);
+}
+
+template <int KIND>
+__device__ __forceinline__ void MarkTileChunkTol(const uint4& a, const uint4& b, uint32_t tol, uint32_t base, uint32_t skip, uint32_t y, TileAcc& acc) {
+  if (((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) == 0) return;   // equal bits are unchanged for every sample type
+  const uint4 d = {ChangedDword<KIND>(a.x, b.x, tol), ChangedDword<KIND>(a.y, b.y, tol), ChangedDword<KIND>(a.z, b.z, tol), ChangedDword<KIND>(a.w, b.w, tol)};
+  MarkTileChunk(d, uint4{0, 0, 0, 0}, base, skip, y, acc);                       // (d ^ 0: the first and last marked byte, `skip` honoured)
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kTileThreads) void anim_tiles_tol_kernel(AnimFrameSrc fa, const uint8_t* __restrict__ ref, int32_t h, uint64_t row_bytes,
+                                                                      uint32_t pixel_bytes, uint32_t tiles_x, uint32_t tiles_y, uint32_t group_tiles,
+                                                                      uint32_t groups, float tolerance, uint32_t* __restrict__ out) {
+  constexpr uint32_t kSampleBytes = KIND == kAnimU8 ? 1 : (KIND == kAnimF32 ? 4 : 2);
+  const uint32_t group = blockIdx.x % groups, ty = blockIdx.x / groups;
+  const AnimFrameSrc fb{ref, (int64_t)row_bytes};
+  const uint32_t int_tol = AnimIntTolerance(tolerance);
+  const uint32_t tol = KIND == kAnimU8 || KIND == kAnimU16 ? int_tol | int_tol << 16 : __float_as_uint(tolerance);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t tile_chunks = 4 * pixel_bytes;                  // 64 pixel_bytes / 16
+  const uint32_t local = tid / tile_chunks;                      // the lane's tile within the group; >= group_tiles: the lane idles
+  const uint64_t chunk = (uint64_t)group * group_tiles * tile_chunks + tid;
+  const uint32_t rows = (uint32_t)std::min<int64_t>(kAnimTile, (int64_t)h - (int64_t)ty * kAnimTile);
+  __shared__ uint32_t table[kTileThreads / 4][4];                // per tile of the group: first byte, first row (min), last byte, last row (max)
+  if (tid < kTileThreads / 4) { table[tid][0] = 0xFFFFFFFFu; table[tid][1] = 0xFFFFFFFFu; table[tid][2] = 0; table[tid][3] = 0; }
+  __syncthreads();
+  TileAcc acc;
+  const int64_t row0 = (int64_t)ty * kAnimTile;
+  if (row_bytes < 16) {
+    // a row of fewer than 16 bytes (one tile column): a sample at a time, by the rule itself
+    if (group == 0 && tid == 0) {
+      for (uint32_t y = 0; y < rows; y++) {
+        const uint8_t* a = fa.data + (row0 + y) * fa.stride;
+        const uint8_t* b = fb.data + (row0 + y) * fb.stride;
+        for (uint32_t i = 0; i < (uint32_t)row_bytes; i += kSampleBytes) {
+          uint32_t sa = 0, sb = 0;
+          __builtin_memcpy(&sa, a + i, kSampleBytes);
+          __builtin_memcpy(&sb, b + i, kSampleBytes);
+          if (AnimSampleChanged((AnimSample)KIND, sa, sb, tolerance)) acc.Mark(i, i + kSampleBytes - 1, y);
+        }
+      }
+    }
+  } else if (local < group_tiles && 16 * chunk < row_bytes) {
+    // where the lane loads: its chunk, or - the chunk the row's end cuts - the last 16 bytes of the row, `skip` bytes earlier (row_bytes
+    // and 16 are multiples of the sample size: so is skip)
+    const uint64_t at = std::min<uint64_t>(16 * chunk, row_bytes - 16);
+    const uint32_t skip = (uint32_t)(16 * chunk - at);
+    const uint32_t base = (tid % tile_chunks) * 16 - skip;       // of the load within the tile (mod 2^32 where skip reaches back; first >= skip mends it)
+    const uint8_t* a = fa.data + row0 * fa.stride + at;
+    const uint8_t* b = fb.data + row0 * fb.stride + at;
+    uint32_t y = 0;
+    for (; y + kTileRowsInFlight <= rows; y += kTileRowsInFlight) {
+      uint4 va[kTileRowsInFlight], vb[kTileRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kTileRowsInFlight; r++) {
+        va[r] = LoadUnaligned(a + (int64_t)r * fa.stride);
+        vb[r] = LoadUnaligned(b + (int64_t)r * fb.stride);
+      }
+#pragma unroll
+      for (int r = 0; r < kTileRowsInFlight; r++) MarkTileChunkTol<KIND>(va[r], vb[r], tol, base, skip, y + r, acc);
+      a += (int64_t)kTileRowsInFlight * fa.stride;
+      b += (int64_t)kTileRowsInFlight * fb.stride;
+    }
+    for (; y < rows; y++) {
+      MarkTileChunkTol<KIND>(LoadUnaligned(a), LoadUnaligned(b), tol, base, skip, y, acc);
+      a += fa.stride;
+      b += fb.stride;
+    }
+  }
+  if (acc.lo <= acc.hi) {
+    const uint32_t t = row_bytes < 16 ? 0 : local;
+    atomicMin(&table[t][0], acc.lo);
+    atomicMin(&table[t][1], acc.y0);
+    atomicMax(&table[t][2], acc.hi);
+    atomicMax(&table[t][3], acc.y1);
+  }
+  __syncthreads();
+  const uint64_t tx = (uint64_t)group * group_tiles + tid;
+  if (tid < group_tiles && tx < tiles_x) {
+    uint32_t word = kAnimTileEmpty;
+    if (table[tid][0] != 0xFFFFFFFFu) word = table[tid][0] / pixel_bytes | table[tid][1] << 8 | (table[tid][2] / pixel_bytes) << 16 | table[tid][3] << 24;
+    out[(uint64_t)ty * tiles_x + tx] = word;
+  }
+}
+
+// ---- anim_apply_rects_kernel: R takes the frame's pixels inside the rectangles that were written - what a decoder replaces.  grid =
+// (row blocks of the highest rectangle, rectangles); a wavefront copies a row of a rectangle at a time: the bytes in front of R's first
+// 16-byte boundary and behind its last go one byte per lane, the middle 16 bytes per lane and step - R stored aligned, the frame loaded
+// at the same offset whatever its alignment.  The rectangles are disjoint and lie inside the canvas: no byte outside them is touched.
+constexpr int kApplyThreads = 256, kApplyWaves = kApplyThreads / 64;
+
+struct AnimRectList { AnimRect r[kAnimMaxRects]; };
+
+__global__ __launch_bounds__(kApplyThreads) void anim_apply_rects_kernel(AnimFrameSrc frame, uint8_t* __restrict__ ref, uint64_t row_bytes, uint32_t pixel_bytes,
+                                                                         AnimRectList rects) {
+  const AnimRect r = rects.r[blockIdx.y];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t y = (int64_t)blockIdx.x * kApplyWaves + wave;      // of the rectangle
+  if (y >= r.h) return;
+  const uint64_t n = (uint64_t)r.w * pixel_bytes, x_off = (uint64_t)r.x * pixel_bytes;
+  const uint8_t* s = frame.data + (r.y + y) * frame.stride + x_off;
+  uint8_t* d = ref + (uint64_t)(r.y + y) * row_bytes + x_off;
+  const uint64_t head = std::min<uint64_t>(n, (uint64_t)(-(intptr_t)d & 15));
+  const uint64_t nmid = (n - head) >> 4;
+  const uint64_t tail = head + 16 * nmid;
+  if ((uint64_t)lane < head) {
+    d[lane] = s[lane];
+  } else if (lane >= 32 && lane < 48 && tail + (uint64_t)(lane - 32) < n) {
+    const uint64_t o = tail + (uint64_t)(lane - 32);
+    d[o] = s[o];
+  }
+#pragma unroll 4
+  for (uint64_t j = (uint64_t)lane; j < nmid; j += 64) *reinterpret_cast<uint4*>(d + head + 16 * j) = LoadUnaligned(s + head + 16 * j);
+}
+
 }  // namespace
+
+void LaunchAnimTilesTol(AnimFrameSrc frame, const uint8_t* ref, int32_t w, int32_t h, uint32_t pixel_bytes, AnimSample kind, float tolerance,
+                        uint32_t* out, void* stream) {
+  if (w <= 0 || h <= 0 || pixel_bytes < 1 || pixel_bytes > 16) return;
+  const uint32_t tiles_x = AnimTilesAcross(w), tiles_y = AnimTilesAcross(h);
+  const uint32_t group_tiles = (kTileThreads / 4) / pixel_bytes;           // as LaunchAnimTiles
+  const uint32_t groups = (tiles_x + group_tiles - 1) / group_tiles;
+  const dim3 grid(tiles_y * groups), block(kTileThreads);                  // (at most 2^24 x 2^20 / 4 tiles of 2^30 pixels: far below 2^31)
+  const uint64_t row_bytes = (uint64_t)w * pixel_bytes;
+  hipStream_t s = (hipStream_t)stream;
+  switch (kind) {
+    case kAnimU8: hipLaunchKernelGGL(anim_tiles_tol_kernel<kAnimU8>, grid, block, 0, s, frame, ref, h, row_bytes, pixel_bytes, tiles_x, tiles_y, group_tiles, groups, tolerance, out); break;
+    case kAnimU16: hipLaunchKernelGGL(anim_tiles_tol_kernel<kAnimU16>, grid, block, 0, s, frame, ref, h, row_bytes, pixel_bytes, tiles_x, tiles_y, group_tiles, groups, tolerance, out); break;
+    case kAnimF16: hipLaunchKernelGGL(anim_tiles_tol_kernel<kAnimF16>, grid, block, 0, s, frame, ref, h, row_bytes, pixel_bytes, tiles_x, tiles_y, group_tiles, groups, tolerance, out); break;
+    case kAnimF32: hipLaunchKernelGGL(anim_tiles_tol_kernel<kAnimF32>, grid, block, 0, s, frame, ref, h, row_bytes, pixel_bytes, tiles_x, tiles_y, group_tiles, groups, tolerance, out); break;
+  }
+}
+
+void LaunchAnimApplyRects(AnimFrameSrc frame, uint8_t* ref, int32_t w, uint32_t pixel_bytes, const AnimRect* rects, int32_t nrects, void* stream) {
+  if (nrects < 1 || nrects > kAnimMaxRects || w <= 0) return;
+  AnimRectList list;
+  int32_t highest = 0;
+  for (int32_t i = 0; i < kAnimMaxRects; i++) {
+    list.r[i] = i < nrects ? rects[i] : AnimRect{0, 0, 0, 0};
+    highest = std::max(highest, list.r[i].h);
+  }
+  if (highest <= 0) return;
+  hipLaunchKernelGGL(anim_apply_rects_kernel, dim3((uint32_t)((highest + kApplyWaves - 1) / kApplyWaves), (uint32_t)nrects), dim3(kApplyThreads), 0,
+                     (hipStream_t)stream, frame, ref, (uint64_t)w * pixel_bytes, pixel_bytes, list);
+}
 
 void LaunchAnimTiles(const AnimFrameSrc* frames, int32_t npairs, int32_t w, int32_t h, uint32_t pixel_bytes, uint32_t* out, void* stream) {
   if (npairs <= 0 || w <= 0 || h <= 0 || pixel_bytes < 1 || pixel_bytes > 16) return;

@@ -1405,11 +1405,12 @@ struct JxlHipEncoder {
   PinnedBuffer h_hist, h_packed;
   std::vector<std::vector<uint8_t>> files;   // the results of the last batch
   std::vector<std::pair<const char*, float>> stages;
-  DeviceBuffer anim;                         // animation encode: the frame table and the extents of the pairs
+  DeviceBuffer anim;                         // animation encode: the frame table and the extents of the pairs; with a tolerance, one
+                                             // frame's tile table and the reference canvas
   std::vector<AnimRect> anim_rects;          // the rectangles of the last animation: per input frame, the bounding box of what it wrote
   struct AnimPart { int32_t k; AnimRect r; };
   std::vector<AnimPart> anim_parts;          // ... per codestream frame: the input frame it belongs to and its rectangle
-  std::vector<uint32_t> anim_tiles;          // ... and, with max_rects >= 2, the tile tables of its pairs (anim_tiles_per_pair words each)
+  std::vector<uint32_t> anim_tiles;          // ... and, with max_rects >= 2 or a tolerance, the tile tables of its pairs (anim_tiles_per_pair words each)
   size_t anim_tiles_per_pair = 0;
 
   explicit JxlHipEncoder(int dev) {
@@ -1735,7 +1736,8 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* en
 // Part 6 of the C-ABI: animation encode.  The extents kernel - with max_rects >= 2 the tile kernel - says what
 // changed, enc_animation.cc turns that into rectangles, one per frame or several, and the rectangles go through Run like the images
 // of a batch - a crop is a pointer offset and a narrower row in Run's copy into tight rows.  Run hands back every frame alone (header,
-// TOC, sections); they follow the image header in one codestream.
+// TOC, sections); they follow the image header in one codestream.  With a tolerance for "unchanged" the measuring is a loop over the
+// frames against a reference canvas instead (EncodeAnimation, step 2); everything behind the rectangles is the same.
 // =====================================================================================================
 namespace {
 
@@ -1744,7 +1746,8 @@ constexpr size_t kAnimWorkspaceBudget = (size_t)32 << 30;    // ... and at most 
 
 // Everything behind the host's checks.  src0: what CheckPixels made of frame 0 (the same for every frame).
 void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations, const EncoderOptions& opt,
-                     const JxlHipAnimationOptions& ao, const JxlHipAnimationRectOptions& ro, const EncoderImageMetadata& md, const EncSource& src0) {
+                     const JxlHipAnimationOptions& ao, const JxlHipAnimationRectOptions& ro, const JxlHipAnimationChangeOptions& co,
+                     const EncoderImageMetadata& md, const EncSource& src0) {
   const JxlHipPixels& f0 = frames[0];
   const int32_t w = (int32_t)f0.width, h = (int32_t)f0.height;
   const uint32_t pixel_bytes = (uint32_t)(f0.num_channels * src0.sample_bytes());
@@ -1753,10 +1756,12 @@ void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, 
   hipStream_t s0 = enc->streams[0];
   StageMarks marks;
   // ---- 1. what changed between consecutive frames: one launch and one download - 16 bytes per pair (max_rects = 1: its box), or
-  // 4 bytes per pair and 64 x 64 tile
+  // 4 bytes per pair and 64 x 64 tile.  With a tolerance (further down) frame k is measured against the reference canvas instead, a
+  // launch per frame, and its rectangles are found before frame k + 1 is measured
   std::vector<AnimExtent> ext((size_t)std::max(n - 1, 0));
   const size_t tiles_per_pair = (size_t)AnimTilesAcross(w) * AnimTilesAcross(h);
-  if (n > 1) {
+  const bool with_tolerance = co.tolerance > 0.f;
+  if (n > 1 && !with_tolerance) {
     const size_t table_bytes = ((size_t)n * sizeof(AnimFrameSrc) + 255) & ~(size_t)255;
     const size_t out_bytes = by_tiles ? ext.size() * tiles_per_pair * sizeof(uint32_t) : ext.size() * sizeof(AnimExtent);
     enc->anim.Reserve(table_bytes + out_bytes, true);
@@ -1795,7 +1800,8 @@ void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, 
   enc->anim_rects.resize((size_t)n);
   std::vector<JxlHipEncoder::AnimPart>& parts = enc->anim_parts;
   std::vector<size_t> last_part((size_t)n);   // of frame k: the codestream frame that carries its duration
-  for (int k = 0; k < n; k++) {
+  // the rectangles of frame k, from ext[k - 1] and the tile table of its pair
+  auto place = [&](int k) {
     enc->anim_rects[(size_t)k] = AnimFrameRect(k, ao.key_interval, k ? ext[(size_t)k - 1] : AnimExtent{-1, -1, -1, -1}, w, h, lossless);
     if (by_tiles && !AnimIsKeyFrame(k, ao.key_interval)) {
       for (const AnimRect& r : AnimFrameRects(enc->anim_tiles.data() + (size_t)(k - 1) * tiles_per_pair, w, h, lossless, ro.max_rects, ro.merge_pixels))
@@ -1804,6 +1810,45 @@ void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, 
       parts.push_back(JxlHipEncoder::AnimPart{k, enc->anim_rects[(size_t)k]});
     }
     last_part[(size_t)k] = parts.size() - 1;
+  };
+  if (!with_tolerance) {
+    for (int k = 0; k < n; k++) place(k);
+  } else {
+    // With a tolerance: the reference canvas R holds the source of what a decoder shows - frame 0, then frame k's pixels inside every
+    // rectangle frame k is written as (lossy: the grown ones; the 1 x 1 of an unchanged frame too).  Frame k is measured against R, per
+    // tile whatever max_rects is (max_rects = 1 reduces the table to its box; a key frame is measured too, then R is the frame), the
+    // host turns the table into rectangles, and R takes them before frame k + 1 is measured: a round trip per frame.
+    place(0);
+    if (n > 1) {
+      const AnimSample kind = src0.exp_bits == 8 ? kAnimF32 : (src0.exp_bits ? kAnimF16 : (src0.sample_bytes() == 2 ? kAnimU16 : kAnimU8));
+      const size_t table_bytes = (tiles_per_pair * sizeof(uint32_t) + 255) & ~(size_t)255;
+      const uint64_t row_bytes = (uint64_t)f0.width * pixel_bytes;
+      enc->anim.Reserve(table_bytes + (size_t)(row_bytes * (uint64_t)h), true);
+      uint32_t* d_tiles = (uint32_t*)enc->anim.p;
+      uint8_t* ref = enc->anim.p + table_bytes;
+      enc->anim_tiles.resize(ext.size() * tiles_per_pair);
+      enc->anim_tiles_per_pair = tiles_per_pair;
+      auto src_of = [&](int k) { return AnimFrameSrc{(const uint8_t*)frames[k].data, (int64_t)frames[k].stride_bytes}; };
+      std::vector<AnimRect> rects;
+      const size_t k_loop = marks.Begin("change tiles against the reference canvas (a launch per frame)", s0);
+      LaunchAnimApplyRects(src_of(0), ref, w, pixel_bytes, &enc->anim_rects[0], 1, s0);
+      for (int k = 1; k < n; k++) {
+        uint32_t* tiles = enc->anim_tiles.data() + (size_t)(k - 1) * tiles_per_pair;
+        LaunchAnimTilesTol(src_of(k), ref, w, h, pixel_bytes, kind, co.tolerance, d_tiles, s0);
+        ENC_HIP(hipMemcpyAsync(tiles, d_tiles, tiles_per_pair * sizeof(uint32_t), hipMemcpyDeviceToHost, s0));
+        ENC_HIP(hipStreamSynchronize(s0));
+        ENC_HIP(hipGetLastError());
+        ext[(size_t)k - 1] = AnimTilesExtent(tiles, w, h);
+        const size_t first = parts.size();
+        place(k);
+        rects.clear();
+        for (size_t c = first; c < parts.size(); c++) rects.push_back(parts[c].r);
+        LaunchAnimApplyRects(src_of(k), ref, w, pixel_bytes, rects.data(), (int32_t)rects.size(), s0);
+      }
+      marks.End(k_loop, s0);
+      ENC_HIP(hipStreamSynchronize(s0));
+      ENC_HIP(hipGetLastError());
+    }
   }
   const int total = (int)parts.size();
   std::vector<FrameOnCanvas> on((size_t)total);
@@ -1870,11 +1915,11 @@ void EncodeAnimation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, 
 
 }  // namespace
 
-extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
-                                                                         const EncoderOptions* options, const JxlHipAnimationOptions* animation,
-                                                                         const JxlHipAnimationRectOptions* rects, const EncoderImageMetadata* metadata,
-                                                                         ErrorInfo* err) {
-  if (!enc || !options || !animation || !rects) return EncoderStatus_NullParameter;
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_changes(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                                           const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                                           const JxlHipAnimationRectOptions* rects, const JxlHipAnimationChangeOptions* changes,
+                                                                           const EncoderImageMetadata* metadata, ErrorInfo* err) {
+  if (!enc || !options || !animation || !rects || !changes) return EncoderStatus_NullParameter;
   enc->files.clear();
   enc->stages.clear();
   enc->anim_rects.clear();
@@ -1893,6 +1938,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipE
     if (animation->tps_denominator < 1 || animation->tps_denominator > 1024) refuse("the denominator of the ticks per second must be 1..1024");
     if (animation->tps_numerator < 1 || animation->tps_numerator > (1u << 30)) refuse("the numerator of the ticks per second must be 1..2^30");
     if (const char* why = AnimRectOptionsRefusal(rects->max_rects, rects->merge_pixels)) refuse(why);
+    if (const char* why = AnimToleranceRefusal(changes->tolerance)) refuse(why);
     for (int k = 0; k < n; k++) {
       const std::string who = "frame " + std::to_string(k) + ": ";
       EncSource src;
@@ -1923,7 +1969,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipE
   (void)hipGetDevice(&caller_device);
   try {
     if (caller_device != enc->device) ENC_HIP(hipSetDevice(enc->device));
-    EncodeAnimation(enc, n, frames, durations, *options, *animation, *rects, md, src0);
+    EncodeAnimation(enc, n, frames, durations, *options, *animation, *rects, *changes, md, src0);
   } catch (const EncFail& e) {
     failed = e.status; why = e.what();
   } catch (const std::bad_alloc&) {
@@ -1941,6 +1987,14 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipE
   }
   if (caller_device != enc->device) (void)hipSetDevice(caller_device);
   return failed;
+}
+
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_rects(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,
+                                                                         const EncoderOptions* options, const JxlHipAnimationOptions* animation,
+                                                                         const JxlHipAnimationRectOptions* rects, const EncoderImageMetadata* metadata,
+                                                                         ErrorInfo* err) {
+  const JxlHipAnimationChangeOptions bits = {0.f};
+  return jxlhip_encode_animation_changes(enc, n, frames, durations, options, animation, rects, &bits, metadata, err);
 }
 
 extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* frames, const uint32_t* durations,

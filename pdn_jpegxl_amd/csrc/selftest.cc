@@ -1011,3 +1011,17 @@ extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_animation_rect_options(int3
   if (why) SetEncErr(err, why);
   return why ? 1 : 0;
 }
+
+// What jxlhip_encode_animation_changes says of this tolerance: 1 and the words in err where it refuses it, 0 where it does not.
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_animation_tolerance(float tolerance, ErrorInfo* err) {
+  const char* why = AnimToleranceRefusal(tolerance);
+  if (why) SetEncErr(err, why);
+  return why ? 1 : 0;
+}
+
+// AnimSampleChanged (enc_animation.h) on n pairs of samples, their bits in the low bytes of a[i] and b[i].  kind: 0 u8, 1 u16, 2
+// binary16, 3 binary32.  out[i]: 1 changed, 0 unchanged.
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_animation_sample_changed(int32_t kind, const uint32_t* a, const uint32_t* b, size_t n, float tolerance,
+                                                                           uint8_t* out) {
+  for (size_t i = 0; i < n; i++) out[i] = AnimSampleChanged((AnimSample)kind, a[i], b[i], tolerance) ? 1 : 0;
+}

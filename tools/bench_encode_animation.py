@@ -7,7 +7,11 @@ stills - the path there was before - alternating in one process (DESIGN.md §4.1
            rectangles per frame (max_rects >= 2) are for;
 each lossy (distance 1, effort 7) and lossless.  A case name may end in "@M" (sprite-lossy@4): encode_animation runs with max_rects = M
 (merge_pixels 4096) and the kernel timed is anim_tiles_kernel; "@1,4" alternates both in one process, round by round, and prints a
-line for each.  --frames 2 is the smallest call: one pair.  Times are HIP events around the synchronous calls (host work included), best and
+line for each.  The "noise" cases (noise-lossy@0,4, noise-lossless@0,4) are the sprite stack plus uniform noise of +-2 on every sample,
+new for every frame - what a sensor delivers; there the suffix lists TOLERANCES (encode_animation's tolerance; 0: the bits decide and every
+frame is written whole), which alternate round by round with max_rects = 4: the stage timed is the one-launch anim_tiles_kernel at
+tolerance 0 and, with a tolerance, the whole per-frame loop against the reference canvas (anim_tiles_tol_kernel, the download of the
+table, the synchronise, the host's rule, anim_apply_rects_kernel - HIP events around all of it).  --frames 2 is the smallest call: one pair.  Times are HIP events around the synchronous calls (host work included), best and
 median of `--rounds` after one warm-up round (workspaces grow in it).  The extents kernel's own time is its stage of the encoder's
 stage times (HIP events around the launch); its bytes are the two frames of every pair, read once.  One JSON line per case; --out
 also writes them to a file.  --only-animation runs nothing else (for a kernel trace of a short run)."""
@@ -28,7 +32,9 @@ W, H, N = 3840, 2160, 32
 COPY_RATE = 6.29e12   # float4 copy, bytes per second read + written
 EXTENTS_STAGE = "change extents of every pair of frames (one launch)"
 TILES_STAGE = "change tiles of every pair of frames (one launch)"
+TOLERANCE_STAGE = "change tiles against the reference canvas (a launch per frame)"
 MERGE_PIXELS = 4096
+NOISE, NOISE_MAX_RECTS = 2, 4
 
 
 def frames_sprite():
@@ -60,6 +66,17 @@ def frames_changed():
     return [bg + (37 * k) % 256 for k in range(N)]   # uint8 wraps: every sample differs from its predecessor's by 37
 
 
+def frames_noise():
+    import torch
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    out = []
+    for f in frames_sprite():
+        n = torch.randint(-NOISE, NOISE + 1, f.shape, generator=g, device="cuda", dtype=torch.int16)
+        out.append((f.to(torch.int16) + n).clamp_(0, 255).to(torch.uint8))   # (clamping keeps two frames within 2 * NOISE of each other)
+    return out
+
+
 def timed(fn):
     import torch
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -71,39 +88,47 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
-def run(name, make, lossless, rounds, only_animation, max_rects=(1,)):
-    """One line per entry of max_rects; with several they alternate round by round on one encoder."""
+def run(name, make, lossless, rounds, only_animation, max_rects=(1,), tolerances=None):
+    """One line per entry of max_rects - or, where `tolerances` is given, per tolerance at max_rects = NOISE_MAX_RECTS; with several
+    they alternate round by round on one encoder."""
     frames = make()
     kw = dict(lossless=True) if lossless else dict(distance=1.0, effort=7)
     items = [api.EncodeItem.from_tensor(f, **kw) for f in frames]
     enc = api.Encoder(0)
-    t_anim, t_ext = {m: [] for m in max_rects}, {m: [] for m in max_rects}
+    variants = [(NOISE_MAX_RECTS, float(t)) for t in tolerances] if tolerances else [(m, 0.0) for m in max_rects]
+    t_anim, t_ext = {v: [] for v in variants}, {v: [] for v in variants}
     t_batch = []
     out, rects, parts = {}, {}, {}
+    stage_of = lambda m, tol: TOLERANCE_STAGE if tol > 0 else (EXTENTS_STAGE if m == 1 else TILES_STAGE)
     for r in range(rounds + 1):
-        for m in max_rects:
-            ta = timed(lambda: out.__setitem__(m, enc.encode_animation(items, 1, max_rects=m, merge_pixels=MERGE_PIXELS, **kw)))
-            ext = enc.stage_times().get(EXTENTS_STAGE if m == 1 else TILES_STAGE, 0.0)
-            rects[m], parts[m] = enc.last_animation_rects, enc.last_animation_frame_rects
+        for v in variants:
+            m, tol = v
+            ta = timed(lambda: out.__setitem__(v, enc.encode_animation(items, 1, max_rects=m, merge_pixels=MERGE_PIXELS, tolerance=tol, **kw)))
+            ext = enc.stage_times().get(stage_of(m, tol), 0.0)
+            rects[v], parts[v] = enc.last_animation_rects, enc.last_animation_frame_rects
             if r:
-                t_anim[m].append(ta), t_ext[m].append(ext)
+                t_anim[v].append(ta), t_ext[v].append(ext)
         tb = 0.0 if only_animation else timed(lambda: out.__setitem__("batch", enc.encode_batch(items)))
         if r:
             t_batch.append(tb)
     enc.close()
     ext_bytes = 2 * (N - 1) * W * H * 4
     lines = []
-    for m in max_rects:
-        ext_ms = min(t_ext[m])
+    for v in variants:
+        m, tol = v
+        ext_ms = min(t_ext[v])
         line = {"case": "%s, %dx%d RGBA8, %d frames, %s" % (name, W, H, N, "lossless" if lossless else "lossy d1 e7"),
-                "max_rects": m, "codestream_frames": len(parts[m]),
-                "coded_pixels_share": round(sum(p[3] * p[4] for p in parts[m]) / float(N * W * H), 4),
-                "animation_file_bytes": len(out[m]),
-                "animation_ms_per_frame_best": round(min(t_anim[m]) / N, 3), "animation_ms_per_frame_median": round(statistics.median(t_anim[m]) / N, 3),
-                "kernel": "anim_extents_kernel" if m == 1 else "anim_tiles_kernel",
-                "extents_ms": round(ext_ms, 4), "extents_ms_all_rounds": [round(t, 4) for t in t_ext[m]], "extents_bytes_read": ext_bytes,
+                "max_rects": m, "codestream_frames": len(parts[v]),
+                "coded_pixels_share": round(sum(p[3] * p[4] for p in parts[v]) / float(N * W * H), 4),
+                "animation_file_bytes": len(out[v]),
+                "animation_ms_per_frame_best": round(min(t_anim[v]) / N, 3), "animation_ms_per_frame_median": round(statistics.median(t_anim[v]) / N, 3),
+                "kernel": "anim_tiles_tol_kernel + anim_apply_rects_kernel, a round trip per frame" if tol > 0 else ("anim_extents_kernel" if m == 1 else "anim_tiles_kernel"),
+                "extents_ms": round(ext_ms, 4), "extents_ms_all_rounds": [round(t, 4) for t in t_ext[v]], "extents_bytes_read": ext_bytes,
                 "extents_tb_per_s": round(ext_bytes / (ext_ms * 1e-3) / 1e12, 3) if ext_ms else None,
                 "extents_share_of_copy_rate": round(ext_bytes / (ext_ms * 1e-3) / COPY_RATE, 3) if ext_ms else None, "rounds": rounds}
+        if tolerances:
+            line.update({"tolerance": tol, "noise": NOISE, "coded_pixels_per_frame": round(sum(p[3] * p[4] for p in parts[v]) / float(N), 1),
+                         "extents_ms_per_frame": round(ext_ms / max(1, N - 1), 4)})
         if not only_animation:
             line.update({"batch_of_full_frames_bytes": sum(len(b) for b in out["batch"]),
                          "batch_of_full_frames_ms_per_frame_best": round(min(t_batch) / N, 3),
@@ -123,12 +148,16 @@ if __name__ == "__main__":
     ap.add_argument("--only-animation", action="store_true")
     args = ap.parse_args()
     W, H, N = args.width, args.height, args.frames
-    makers = {"sprite": frames_sprite, "changed": frames_changed, "corner": frames_corner}
+    makers = {"sprite": frames_sprite, "changed": frames_changed, "corner": frames_corner, "noise": frames_noise}
     lines = []
     for case in args.cases:
         case, _, ms = case.partition("@")
         what, mode = case.split("-")
-        for line in run(what, makers[what], mode == "lossless", args.rounds, args.only_animation, tuple(int(m) for m in ms.split(",")) if ms else (1,)):
+        if what == "noise":
+            suffix = dict(tolerances=tuple(float(t) for t in (ms or "0,4").split(",")))
+        else:
+            suffix = dict(max_rects=tuple(int(m) for m in ms.split(",")) if ms else (1,))
+        for line in run(what, makers[what], mode == "lossless", args.rounds, args.only_animation, **suffix):
             lines.append(line)
             print(json.dumps(line), flush=True)
     if args.out:
