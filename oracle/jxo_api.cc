@@ -120,6 +120,14 @@ void jxo_set_next_transforms(const int32_t* data, size_t n) {
   g_next_transforms.assign(data, data + n);
   g_next_have_transforms = true;
 }
+// Varblock layout of the next (lossy) jxo_encode call: kind 0 EncodeParams::varblocks (4 ints per block), 1 ::varblock_sequence (2 ints)
+static thread_local std::vector<int32_t> g_next_varblocks[2];
+static thread_local bool g_next_have_varblocks = false;
+void jxo_set_next_varblocks(const int32_t* data, size_t n, int kind) {
+  if (kind != 0 && kind != 1) return;
+  g_next_varblocks[kind].assign(data, data + n * (kind == 0 ? 4 : 2));
+  if (kind == 0) g_next_have_varblocks = true;
+}
 // Code forms of the next jxo_encode call (jxo_entropy.h: EntropyForms), as flat ints in the order read below; the census of that call
 // stays readable (as JSON) until the next call that sets forms.
 static thread_local EntropyForms g_next_forms;
@@ -217,6 +225,9 @@ JxoBytes* jxo_encode(const uint8_t* px, uint32_t w, uint32_t h, int32_t nch, con
     for (int r = 0; r < 3; r++) { p.tree[r].swap(g_next_tree[r]); g_next_tree[r].clear(); }
     p.transforms.swap(g_next_transforms); g_next_transforms.clear();
     p.have_transforms = g_next_have_transforms; g_next_have_transforms = false;
+    p.varblocks.swap(g_next_varblocks[0]); g_next_varblocks[0].clear();
+    p.have_varblocks = g_next_have_varblocks; g_next_have_varblocks = false;
+    p.varblock_sequence.swap(g_next_varblocks[1]); g_next_varblocks[1].clear();
     const uint32_t g_next_flags_entropy = g_next_flags;
     g_next_flags = 0;
     JxoBytes* b = new JxoBytes();

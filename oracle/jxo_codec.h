@@ -138,6 +138,15 @@ struct EncodeParams {
   bool mislabel_afv = false;    // lossy, REFUSAL TESTS ONLY: some 8x8 DCT blocks are written to the block-metadata stream as AFV0..AFV3 (the
                                 // coefficients stay those of the 8x8 DCT, so the stream is not a meaningful picture): a decoder without AFV must refuse it
   bool premultiplied_alpha = false;   // the alpha channel is signalled as associated; the colour samples handed in are ALREADY premultiplied
+  // lossy: the varblock layout in place of the writer's heuristics (parity-test coverage).  4 ints per block - strategy, bx, by (origin
+  // cell), raw quant (1..256; 0: the writer's own) - anywhere the format allows, aligned to the block's size or not: disjoint, inside
+  // the frame and inside their 32x32-cell group (checked).  Every cell left over becomes DCT8.
+  bool have_varblocks = false;
+  std::vector<int32_t> varblocks;
+  // lossy, one-LF-group frames, REFUSAL TESTS: the strategy and quant rows of the block-metadata channel written exactly as given
+  // (2 ints per block: strategy, raw quant), count = their number.  The rest of the frame is that of the longest prefix the placement
+  // rule accepts, completed with DCT8; a decoder refuses an invalid sequence before it reads the HF sections.
+  std::vector<int32_t> varblock_sequence;
   bool cmyk = false;            // lossless only: nch 4 / 5 = C, M, Y, K [, A] as STORED (0 = full ink); K goes to a black extra channel
 };
 

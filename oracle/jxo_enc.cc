@@ -225,12 +225,57 @@ struct VarDctEncoder {
                                DCT16X32, DCT4X8, DCT8X4, DCT64X64, DCT64X32, DCT32X64, DCT128X128, DCT128X64, DCT64X128,
                                DCT256X256, DCT256X128, DCT128X256};
     const int nall = sizeof(kAll) / sizeof(kAll[0]);
+    // a layout the caller chose: what the format's placement rule allows, which asks for no alignment (fits() above is the writer's
+    // own habit).  Everything after this works per origin cell.
+    std::vector<int32_t> forced_q((size_t)w8 * h8, 0);
+    auto known = [](int s) { return s >= 0 && s < kNumStrategies && !(s >= AFV0 && s <= AFV3); };
+    auto allowed = [&](int bx, int by, int s) {
+      const int cx = kCoveredX[s], cy = kCoveredY[s];
+      if (bx < 0 || by < 0 || bx + cx > w8 || by + cy > h8) return false;
+      if ((bx % 32) + cx > 32 || (by % 32) + cy > 32) return false;
+      for (int iy = 0; iy < cy; iy++)
+        for (int ix = 0; ix < cx; ix++)
+          if (strategy[(size_t)(by + iy) * w8 + bx + ix] != 0xFF) return false;
+      return true;
+    };
+    if (p.have_varblocks) {
+      JXO_CHECK(p.varblocks.size() % 4 == 0, "varblocks: four values per block");
+      for (size_t k = 0; k < p.varblocks.size(); k += 4) {
+        const int s = p.varblocks[k], bx = p.varblocks[k + 1], by = p.varblocks[k + 2], q = p.varblocks[k + 3];
+        JXO_CHECK(known(s), "varblocks: unknown strategy");
+        JXO_CHECK(q >= 0 && q <= 256, "varblocks: raw quant is 1..256");
+        JXO_CHECK(bx >= 0 && by >= 0 && bx + kCoveredX[s] <= w8 && by + kCoveredY[s] <= h8, "varblocks: block outside the frame");
+        JXO_CHECK((bx % 32) + kCoveredX[s] <= 32 && (by % 32) + kCoveredY[s] <= 32, "varblocks: block crosses a group boundary");
+        JXO_CHECK(allowed(bx, by, s), "varblocks: blocks overlap");
+        place(bx, by, s);
+        forced_q[(size_t)by * w8 + bx] = q;
+      }
+    }
+    if (!p.varblock_sequence.empty()) {
+      // the longest prefix of the sequence that the placement rule accepts, each block at the first free cell in raster order
+      JXO_CHECK(p.varblock_sequence.size() % 2 == 0 && !p.have_varblocks, "varblock_sequence: two values per block, no varblocks beside it");
+      JXO_CHECK(f.num_lf_groups == 1, "varblock_sequence: frames of one LF group only");
+      const size_t n = p.varblock_sequence.size() / 2;
+      JXO_CHECK(n <= (size_t)w8 * h8, "varblock_sequence: more blocks than the count field can say");
+      size_t k = 0;
+      for (int by = 0; by < h8 && k < n; by++)
+        for (int bx = 0; bx < w8 && k < n; bx++) {
+          if (strategy[(size_t)by * w8 + bx] != 0xFF) continue;
+          const int s = p.varblock_sequence[2 * k], q = p.varblock_sequence[2 * k + 1];
+          if (!known(s) || q < 1 || q > 256 || !allowed(bx, by, s)) { k = n; break; }
+          place(bx, by, s);
+          forced_q[(size_t)by * w8 + bx] = q;
+          k++;
+        }
+    }
     Rng rng(p.seed);
     for (int by = 0; by < h8; by++)
       for (int bx = 0; bx < w8; bx++) {
         if (strategy[(size_t)by * w8 + bx] != 0xFF) continue;
         int s = DCT8;
-        if (p.strategy_mode == 1) {
+        if (p.have_varblocks || !p.varblock_sequence.empty()) {
+          s = DCT8;
+        } else if (p.strategy_mode == 1) {
           s = DCT8;
         } else if (p.strategy_mode == 3) {
           s = fits(bx, by, p.fixed_strategy) ? p.fixed_strategy : DCT8;
@@ -268,6 +313,7 @@ struct VarDctEncoder {
         double mod = 0.7 + 0.8 / (1.0 + a / 0.012);
         int q = (int)std::lrint(16.0 * mod);
         q = std::max(1, std::min(256, q));
+        if (forced_q[cell]) q = forced_q[cell];
         for (int iy = 0; iy < cy; iy++) for (int ix = 0; ix < cx; ix++) raw_quant[cell + (size_t)iy * w8 + ix] = q;
       }
   }
@@ -517,6 +563,13 @@ struct VarDctEncoder {
           srow.push_back(sw);
           qrow.push_back(raw_quant[cell] - 1);
         }
+      if (!p.varblock_sequence.empty()) {   // the two rows as the caller gave them, valid or not
+        srow.clear(); qrow.clear();
+        for (size_t k = 0; k < p.varblock_sequence.size(); k += 2) {
+          srow.push_back(p.varblock_sequence[k]);
+          qrow.push_back(p.varblock_sequence[k + 1] - 1);
+        }
+      }
       nb_blocks[g] = (uint32_t)srow.size();
       int tw = (int)DivCeil(bw, 8), th = (int)DivCeil(bh, 8);
       ModularImage mi;

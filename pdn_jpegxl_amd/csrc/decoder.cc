@@ -685,6 +685,8 @@ void JxlHipDecoder::Decode(int32_t n_, const uint8_t* const* host_data, const si
   }
   // experiment knob: the pixel stages behind the HF chain on ITS stream (no overlap between a batch's pixels and the next batch's HF decode)
   hipStream_t s_pix = pix_on_hf ? s_hf : stream;
+  // every entropy stage of the batch is behind this point on the pixel stream: what they refused is taken out of the output kernels
+  if (B.any_vardct) LaunchSkipFailedImages(d_imgs, n, s_pix);
   if (ds && B.any_vardct) {
     // the whole pixel stage of a reduced-size decode: no reconstruction, no noise, no filters, and every image in one launch
     if (any_alpha) LaunchAlphaReduce(d_imgs, n, B.max_ds_cells, s_pix);
@@ -961,6 +963,14 @@ int32_t jxlhip_set_option(JxlHipDecoder* dec, const char* name, int32_t value) {
     const int word = name[12] == 'n' ? kStatusAlphaNarrow : kStatusAlphaRedo;
     int64_t sum = 0;
     for (int i = 0; i < S.n; i++) sum += S.h_status[(size_t)i * 16 + word];
+    return (int32_t)std::min<int64_t>(sum, INT32_MAX);
+  }
+  // the 64x64 tiles of the last finished batch that recon_tile_kernel left to the generic reconstruction kernels (-1: not finished)
+  if (!strcmp(name, "query_generic_tiles")) {
+    JxlHipDecoder::Slot& S = dec->Last();
+    if (S.pending || !S.h_status) return -1;
+    int64_t sum = 0;
+    for (int i = 0; i < S.n; i++) sum += S.h_status[(size_t)i * 16 + 1];
     return (int32_t)std::min<int64_t>(sum, INT32_MAX);
   }
   if (!strcmp(name, "no_stream_pairs")) { dec->no_stream_pairs = value != 0; return 1; }

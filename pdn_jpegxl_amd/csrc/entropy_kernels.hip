@@ -1350,7 +1350,10 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
       }
       // both reductions are barriers: the marks of this row are visible to the next, and every thread takes the same exit
       const int n_row = __syncthreads_count(inrow);
-      if (__syncthreads_or(bad || (nfree && !n_row))) { layout_bad = true; break; }   // (free cells left but no block left)
+      // the row's blocks must take all of its free cells: when the sequence ends inside a row - or in the last row, where no row
+      // below is left to find free cells and no block - fewer widths than free cells means uncovered cells (same test in every thread)
+      if (nfree && s_pre[num + (uint32_t)n_row] - s_pre[num] != nfree) bad = true;
+      if (__syncthreads_or(bad)) { layout_bad = true; break; }
       num += (uint32_t)n_row;
     }
   }

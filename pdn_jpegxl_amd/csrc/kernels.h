@@ -63,6 +63,8 @@ void LaunchReduceDisplayed(const uint8_t* src, uint8_t* dst, int dw, int dh, int
 void LaunchPatches(const PatchFrame* frames, const PatchTile* tiles, int ntiles, const int32_t* list, const PatchPos* pos, const PatchRef* refs,
                    hipStream_t s);
 
+// lossy images whose error word is set: their records' output switches are cleared, no kernel writes their buffer (kernels.hip)
+void LaunchSkipFailedImages(DevImage* imgs, int nimg, hipStream_t s);
 // the batch's status words into pinned host memory, by a kernel (kernels.hip)
 void LaunchStatusToHost(const uint32_t* src, uint32_t* dst_pinned, int nwords, hipStream_t s);
 #ifdef JXLHIP_EXPERIMENTS

@@ -68,8 +68,9 @@ __global__ void cell_sigma_kernel(const DevImage* __restrict__ imgs) {
 }
 
 // ------------------------------------------------------------------ generic (any block size) reconstruction
-// These kernels only visit the 64x64 tiles that recon_tile_kernel could not handle (tiles touched by a varblock
-// larger than the tile); the list and its length (status[1]) are written by that kernel.
+// These kernels only visit the 64x64 tiles that recon_tile_kernel could not handle (tiles that hold part of a varblock which leaves
+// the tile - larger than it, or astride its edge - a varblock that does not start on a multiple of its own size, or a special 8x8
+// transform; every tile of a progressive frame); the list and its length (status[1]) are written by that kernel.
 #define FOR_LISTED_TILES(im, tile)                                   \
   const uint32_t n_listed_ = (im).status ? (im).status[1] : 0u;       \
   for (uint32_t li_ = blockIdx.x; li_ < n_listed_; li_ += gridDim.x) \
@@ -223,11 +224,14 @@ __global__ void llf_kernel(const DevImage* __restrict__ imgs, const float* basis
   }
 }
 
-// A 64x64 tile that lies inside ONE varblock of at least 64 points both ways (varblocks are aligned to their size, so it is enough
-// to look at the tile's first cell) takes the matrix-core kernel below; everything else the vector-ALU kernels.
+// A 64x64 tile that lies inside ONE varblock takes the matrix-core kernel below; everything else the vector-ALU kernels.  The format
+// does not align a varblock to its size, so the block of the tile's first cell must be seen to reach the tile's far edges: a tile
+// can hold no more than the last cell of a 64x64 block that starts at cell (1, 1).  (A tile that passes lies inside the frame: the
+// kernel's full-tile stores stay inside the planes.)
 __device__ __forceinline__ bool GemmTile(const DevImage& im, int tx, int ty) {
   const uint32_t info = im.cellinfo[(size_t)ty * 8 * im.w8 + tx * 8];
-  return (info & 0xFF) >= 18 && (info & 0xFF) <= 26 && ((info >> 18) & 7) >= 3 && ((info >> 21) & 7) >= 3;
+  const uint32_t ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
+  return (info & 0xFF) >= 18 && (info & 0xFF) <= 26 && ix + 8 <= (1u << lcx) && iy + 8 <= (1u << lcy);
 }
 
 // Both 1-D IDCT passes of such a tile as 64 x R x 64 matrix products on the matrix cores (v_mfma_f32_16x16x4_f32: exact f32
@@ -508,6 +512,26 @@ void LaunchOrient(const uint8_t* src, uint8_t* dst, int w, int h, int px_bytes, 
   const size_t n = (size_t)w * h;
   const unsigned blocks = (unsigned)std::min<size_t>(8192, (n + 255) / 256);
   hipLaunchKernelGGL(orient_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, src, dst, w, h, px_bytes, orientation);
+}
+
+// ------------------------------------------------------------------ images the entropy stages refused
+// Runs on the pixel stream once every entropy stage of the batch has finished: a lossy image with an error bit set (a varblock
+// layout the placement refused, a damaged section ...) has no planes worth showing, so the switches that the output-writing kernels
+// test first are cleared in its record and the caller's buffer keeps what it held.  (Frames that go through a scratch image -
+// orientations, layers - are copied or composed by later launches that know nothing of this.)
+__global__ void skip_failed_images_kernel(DevImage* imgs, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  DevImage& im = imgs[i];
+  if (im.is_modular || !im.status || !im.status[0]) return;
+  for (int k = 0; k < 5; k++) im.stage_on[k] = 0;
+  im.final_stage = -1;
+  im.fused_gab_epf1 = 0;
+  im.ds = 0;
+}
+void LaunchSkipFailedImages(DevImage* imgs, int nimg, hipStream_t s) {
+  if (nimg <= 0) return;
+  hipLaunchKernelGGL(skip_failed_images_kernel, dim3((nimg + 255) / 256), dim3(256), 0, s, imgs, nimg);
 }
 
 // ------------------------------------------------------------------ status words back to the host

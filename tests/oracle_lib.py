@@ -254,7 +254,8 @@ def entropy_census():
 def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, seed=1, epf_iters=-1, gaborish=True,
            container=True, adaptive_lf_smoothing=True, lossless_predictor=6, lossless_squeeze=False, num_threads=8, exif=None,
            xmp=None, lossless_tree=0, bits=8, orientation=1, float_samples=0, colour=0, icc=None, cmyk=False, animation_frames=1, custom_quant_tables=False, prefix_codes=False, lz77=False, num_passes=1, custom_orders=False, lf_contexts=False, palette=False, mislabel_afv=False,
-           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None, transforms=None, entropy=None):
+           premultiplied_alpha=False, wide_codes=False, side_info=None, tree=None, alpha_tree=None, lf_tree=None, transforms=None, entropy=None,
+           varblocks=None, varblock_sequence=None):
     """px: uint8 array (h, w, nch) with nch in 1..4 (Gray, GrayA, RGB, RGBA); with bits > 8 (up to 16) a uint16 array whose
     samples use the low `bits` bits; with float_samples = 16 / 32 a float16 / float32 array (nominal range [0, 1]).  Returns bytes.
     side_info: dict of make_side_info's keyword arguments (lossy frames: varying maps and custom header parameters).
@@ -271,7 +272,12 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
     (0: begin_c, rct_type; 1: begin_c, num_c, nb_colors, nb_deltas, predictor; 2: a list of squeeze tuples) written as given, with nothing
     done to the channels and nothing checked (refusal tests).
     entropy: a dict that changes how the frame's top-level codes turn values into symbols and headers (flatten_entropy); tokens' values
-    and contexts and all quantised data are those of the same call without it.  entropy_census() then describes what was written."""
+    and contexts and all quantised data are those of the same call without it.  entropy_census() then describes what was written.
+    varblocks: lossy frames: [(strategy, bx, by[, raw_quant]), ...], each block at that origin cell, aligned to its size or not; every
+    cell left over becomes DCT8.  An OracleError when blocks overlap, leave the frame or cross the edge of their 32x32-cell group.
+    varblock_sequence: lossy frames of one LF group, refusal tests: [(strategy, raw_quant), ...] written as the strategy and quant rows
+    of the block-metadata channel exactly as given, with their number as the count; the rest of the frame is that of the longest prefix
+    the placement rule accepts."""
     L = lib()
     if entropy is not None:
         lz77 = lz77 or "lz" in entropy
@@ -306,6 +312,12 @@ def encode(px, distance=1.0, lossless=False, strategy_mode=0, fixed_strategy=0, 
         flat = np.ascontiguousarray(flatten_transforms(transforms), dtype=np.int32)
         L.jxo_set_next_transforms.argtypes = [C.c_void_p, C.c_size_t]
         L.jxo_set_next_transforms(flat.ctypes.data, len(flat))
+    for kind, blocks in enumerate((varblocks, varblock_sequence)):
+        if blocks is not None:
+            rows = [tuple(b) + (0,) * (4 - len(b)) for b in blocks] if kind == 0 else [tuple(b) for b in blocks]
+            flat = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2 if kind else 4)
+            L.jxo_set_next_varblocks.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+            L.jxo_set_next_varblocks(flat.ctypes.data, len(flat), kind)
     if animation_frames > 1:
         L.jxo_set_next_animation.argtypes = [C.c_int]
         L.jxo_set_next_animation(animation_frames)
