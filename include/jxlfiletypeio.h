@@ -294,6 +294,21 @@ JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels* pixels, c
                                                    const EncoderImageMetadata* metadata, IOCallbacks* callbacks, ErrorInfo* errorInfo,
                                                    ProgressProc progressCallback);
 
+/* What a lossy save may do beyond EncoderOptions.  All zero: the file jxlhip_save_pixels writes. */
+typedef struct JxlHipLossyOptions {
+  int32_t chroma_from_luma;    /* 0: the per-tile chroma-from-luma maps are all zero; 1: fitted per 64 x 64 tile on the GPU (a least-squares
+                                * factor of the X and of the B coefficients on the dequantised Y; usually fewer bytes and better pixels) */
+  int32_t reserved[3];         /* must be zero */
+} JxlHipLossyOptions;
+
+/* jxlhip_save_pixels with a JxlHipLossyOptions (jxlhip_save_pixels is this call with all of it zero).  Every effort tier, sample type
+ * and channel count is supported.  A lossless save ignores what the struct asks for: its bytes are those without it.  Refused on the
+ * host, before any device work, with EncoderStatus_EncodeError and a message: chroma_from_luma outside 0..1, a reserved word that is
+ * not zero.  When the fit leaves every map value zero (a flat frame), the file is the one of chroma_from_luma = 0, byte for byte. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels_lossy(const JxlHipPixels* pixels, const EncoderOptions* options, const JxlHipLossyOptions* lossy,
+                                                         const EncoderImageMetadata* metadata, IOCallbacks* callbacks, ErrorInfo* errorInfo,
+                                                         ProgressProc progressCallback);
+
 /* =====================================================================================================
  * Part 4: batch encode of device-resident images (not in the reference).
  * ===================================================================================================== */
@@ -319,6 +334,13 @@ JXLFILETYPEIO_API void jxlhip_encoder_destroy(JxlHipEncoder* enc);
  * jxlhip_last_save_* reporters are not touched. */
 JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
                                                     const EncoderImageMetadata* const* metadata, EncoderStatus* statuses, ErrorInfo* err);
+
+/* jxlhip_encode_batch with a JxlHipLossyOptions per image: lossy[i] belongs to images[i]; lossy may be NULL, meaning all zero
+ * (jxlhip_encode_batch is this call with NULL).  The file of image i is, byte for byte, what jxlhip_save_pixels_lossy writes with
+ * options[i] and lossy[i].  An image whose lossy[i] that call refuses is refused here the same way, in statuses[i]. */
+JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch_lossy(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
+                                                          const JxlHipLossyOptions* lossy, const EncoderImageMetadata* const* metadata,
+                                                          EncoderStatus* statuses, ErrorInfo* err);
 
 /* The file of image i of the last batch: host memory owned by the encoder, valid until the next batch or destroy.  Returns 1, or 0
  * when there is none (an index outside the batch, a refused or failed image). */
@@ -513,6 +535,7 @@ JXLFILETYPEIO_API EncoderStatus jxlhip_encode_animation_changes(JxlHipEncoder* e
 #ifdef __cplusplus
 }
 static_assert(sizeof(JxlHipPixels) == 40, "JxlHipPixels layout");
+static_assert(sizeof(JxlHipLossyOptions) == 16, "JxlHipLossyOptions layout");
 static_assert(sizeof(JxlHipAnimationOptions) == 20, "JxlHipAnimationOptions layout");
 static_assert(sizeof(JxlHipAnimationRectOptions) == 8, "JxlHipAnimationRectOptions layout");
 static_assert(sizeof(JxlHipAnimationChangeOptions) == 4, "JxlHipAnimationChangeOptions layout");

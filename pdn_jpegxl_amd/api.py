@@ -76,6 +76,15 @@ class JxlHipPixels(C.Structure):
                 ("num_channels", C.c_int32), ("sample_type", C.c_int32), ("bits_per_sample", C.c_int32), ("colour", C.c_int32)]
 
 
+class JxlHipLossyOptions(C.Structure):
+    _fields_ = [("chroma_from_luma", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def _lossy_options(cfl):
+    """cfl: False / True (chroma-from-luma maps all zero / fitted per tile), or a JxlHipLossyOptions as it is."""
+    return cfl if isinstance(cfl, JxlHipLossyOptions) else JxlHipLossyOptions(int(cfl))
+
+
 class AnimationOptions(C.Structure):
     _fields_ = [("tps_numerator", C.c_uint32), ("tps_denominator", C.c_uint32), ("num_loops", C.c_uint32), ("key_interval", C.c_int32),
                 ("chunk_frames", C.c_int32)]
@@ -104,7 +113,8 @@ class AnimationFrame(C.Structure):
 EXPORTS = ["GetLibJxlVersion", "LoadImage", "SaveImage", "jxlhip_parse_icc", "jxlhip_decoder_create", "jxlhip_decoder_destroy", "jxlhip_peek",
            "jxlhip_decode_batch", "jxlhip_finish", "jxlhip_read_plane", "jxlhip_set_option", "jxlhip_stage_times", "jxlhip_stage_totals",
            "jxlhip_last_load_stage_times", "jxlhip_last_save_stage_times", "jxlhip_distance_map", "jxlhip_last_save_distances",
-           "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_encoder_create", "jxlhip_encoder_destroy", "jxlhip_encode_batch",
+           "jxlhip_last_save_lossless_info", "jxlhip_save_pixels", "jxlhip_save_pixels_lossy", "jxlhip_encoder_create", "jxlhip_encoder_destroy",
+           "jxlhip_encode_batch", "jxlhip_encode_batch_lossy",
            "jxlhip_encoder_result", "jxlhip_encoder_stage_times", "jxlhip_encode_animation", "jxlhip_encoder_animation_rects", "jxlhip_encode_animation_rects",
            "jxlhip_encoder_animation_frame_rects", "jxlhip_encoder_animation_tiles", "jxlhip_encode_animation_changes", "jxlhip_animation_open", "jxlhip_animation_close", "jxlhip_animation_frame",
            "jxlhip_animation_next", "jxlhip_animation_rewind", "jxlhip_animation_set_option", "jxlhip_animation_decoder", "jxlhip_animation_entry_points",
@@ -193,6 +203,9 @@ def lib(build_if_missing=True):
     L.jxlhip_save_pixels.restype = C.c_int32
     L.jxlhip_save_pixels.argtypes = [C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions), C.POINTER(EncoderImageMetadata),
                                      C.POINTER(IOCallbacks), C.POINTER(ErrorInfo), ProgressFn]
+    L.jxlhip_save_pixels_lossy.restype = C.c_int32
+    L.jxlhip_save_pixels_lossy.argtypes = [C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions), C.POINTER(JxlHipLossyOptions),
+                                           C.POINTER(EncoderImageMetadata), C.POINTER(IOCallbacks), C.POINTER(ErrorInfo), ProgressFn]
     L.jxlhip_encoder_create.restype = C.c_void_p
     L.jxlhip_encoder_create.argtypes = [C.c_int32, C.POINTER(ErrorInfo)]
     L.jxlhip_encoder_destroy.restype = None
@@ -200,6 +213,9 @@ def lib(build_if_missing=True):
     L.jxlhip_encode_batch.restype = C.c_int32
     L.jxlhip_encode_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions),
                                       C.POINTER(C.POINTER(EncoderImageMetadata)), C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
+    L.jxlhip_encode_batch_lossy.restype = C.c_int32
+    L.jxlhip_encode_batch_lossy.argtypes = [C.c_void_p, C.c_int32, C.POINTER(JxlHipPixels), C.POINTER(EncoderOptions), C.POINTER(JxlHipLossyOptions),
+                                            C.POINTER(C.POINTER(EncoderImageMetadata)), C.POINTER(C.c_int32), C.POINTER(ErrorInfo)]
     L.jxlhip_encoder_result.restype = C.c_int32
     L.jxlhip_encoder_result.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.jxlhip_encoder_stage_times.restype = C.c_int32
@@ -385,10 +401,12 @@ def save_image(bgra, distance=1.0, effort=7, lossless=False, exif=None, icc=None
 _SAMPLE_TYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float16): 2, np.dtype(np.float32): 3}
 
 
-def save_pixels(px, distance=1.0, effort=7, lossless=False, colour="Srgb", bits=None, exif=None, xmp=None, progress=None):
-    """jxlhip_save_pixels: px = numpy array (h, w[, c]) of uint8, uint16, float16 or float32, c = 1..4 (Gray | Gray,A | R,G,B |
+def save_pixels(px, distance=1.0, effort=7, lossless=False, colour="Srgb", bits=None, exif=None, xmp=None, progress=None, cfl=False):
+    """jxlhip_save_pixels_lossy: px = numpy array (h, w[, c]) of uint8, uint16, float16 or float32, c = 1..4 (Gray | Gray,A | R,G,B |
     R,G,B,A; rows may be strided).  colour: a KNOWN_PROFILE name, the space the samples are already in.  bits: of integer samples
-    (default 8 for uint8, 16 for uint16; uint16 samples use the low `bits` bits).  Returns the encoded bytes."""
+    (default 8 for uint8, 16 for uint16; uint16 samples use the low `bits` bits).  cfl: True fits the chroma-from-luma maps of a lossy
+    save per tile, False (the file of jxlhip_save_pixels) leaves them zero; a JxlHipLossyOptions is passed as it is; None calls
+    jxlhip_save_pixels, the entry point without the struct.  Returns the encoded bytes."""
     L = lib()
     px = np.asarray(px)
     if px.dtype not in _SAMPLE_TYPES:
@@ -416,7 +434,11 @@ def save_pixels(px, distance=1.0, effort=7, lossless=False, colour="Srgb", bits=
     md = EncoderImageMetadata(*sum(([k.ctypes.data if k is not None else None, len(k) if k is not None else 0] for k in keep), []))
     io = IOCallbacks(WriteFn(write), SeekFn(lambda p: S_OK))
     err = ErrorInfo()
-    st = L.jxlhip_save_pixels(C.byref(desc), C.byref(opt), C.byref(md), C.byref(io), C.byref(err), ProgressFn(progress) if progress else ProgressFn())
+    pf = ProgressFn(progress) if progress else ProgressFn()
+    if cfl is None:
+        st = L.jxlhip_save_pixels(C.byref(desc), C.byref(opt), C.byref(md), C.byref(io), C.byref(err), pf)
+    else:
+        st = L.jxlhip_save_pixels_lossy(C.byref(desc), C.byref(opt), C.byref(_lossy_options(cfl)), C.byref(md), C.byref(io), C.byref(err), pf)
     if st != 0:
         raise JxlError(ENCODER_STATUS[st] if 0 <= st < len(ENCODER_STATUS) else str(st), err.errorMessage.decode("ascii", "replace"))
     return bytes(out)
@@ -639,10 +661,10 @@ class EncodeItem:
 
     ptr: device pointer (int) of interleaved samples, Gray | Gray,A | R,G,B | R,G,B,A; dtype: numpy dtype of a sample (uint8, uint16,
     float16, float32); stride_bytes: bytes from one row to the next (default: tight rows); bits: of integer samples (default 8 / 16).
-    The other arguments are save_pixels' own.  `from_tensor` takes a torch tensor (h, w[, c]) on the GPU, rows may be strided."""
+    The other arguments are save_pixels' own (cfl: True / False or a JxlHipLossyOptions).  `from_tensor` takes a torch tensor (h, w[, c]) on the GPU, rows may be strided."""
 
     def __init__(self, ptr, width, height, channels, dtype, stride_bytes=None, bits=None, colour="Srgb", distance=1.0, effort=7,
-                 lossless=False, exif=None, xmp=None, icc=None, keep=None):
+                 lossless=False, exif=None, xmp=None, icc=None, keep=None, cfl=False):
         dtype = np.dtype(dtype)
         if dtype not in _SAMPLE_TYPES:
             raise ValueError("samples are uint8, uint16, float16 or float32")
@@ -651,6 +673,7 @@ class EncodeItem:
         self.bits = ({1: 8, 2: 16}[dtype.itemsize] if dtype.kind == "u" else 0) if bits is None else int(bits)
         self.colour, self.distance, self.effort, self.lossless = colour, float(distance), int(effort), bool(lossless)
         self.exif, self.xmp, self.icc = exif, xmp, icc
+        self.cfl = cfl
         self.keep = keep   # whatever owns the device memory
 
     @classmethod
@@ -688,10 +711,11 @@ class Encoder:
     def __del__(self):
         self.close()
 
-    def encode_batch(self, items, raise_on_error=True):
+    def encode_batch(self, items, raise_on_error=True, lossy_call=None):
         """items: list of EncodeItem.  Returns one bytes object per image (None for an image that was refused or failed; its status
         name is in last_statuses[i], the first message in last_error).  Synchronous.  With raise_on_error the first status that is not
-        Ok raises JxlError."""
+        Ok raises JxlError.  lossy_call: None - jxlhip_encode_batch_lossy when an item sets cfl, jxlhip_encode_batch otherwise; True -
+        jxlhip_encode_batch_lossy with every item's options; "null" - jxlhip_encode_batch_lossy without options (NULL)."""
         n = len(items)
         px = (JxlHipPixels * max(n, 1))()
         opt = (EncoderOptions * max(n, 1))()
@@ -708,7 +732,13 @@ class Encoder:
                 mds[i] = C.pointer(md)
         st = (C.c_int32 * max(n, 1))()
         err = ErrorInfo()
-        r = self._L.jxlhip_encode_batch(self._h, n, px, opt, mds, st, C.byref(err))
+        if lossy_call is None:
+            lossy_call = any(isinstance(it.cfl, JxlHipLossyOptions) or it.cfl for it in items)
+        if lossy_call:
+            lossy = None if lossy_call == "null" else (JxlHipLossyOptions * max(n, 1))(*[_lossy_options(it.cfl) for it in items])
+            r = self._L.jxlhip_encode_batch_lossy(self._h, n, px, opt, lossy, mds, st, C.byref(err))
+        else:
+            r = self._L.jxlhip_encode_batch(self._h, n, px, opt, mds, st, C.byref(err))
         self.last_error = err.errorMessage.decode("ascii", "replace")
         self.last_statuses = [ENCODER_STATUS[st[i]] if 0 <= st[i] < len(ENCODER_STATUS) else str(st[i]) for i in range(n)]
         if r != 0 and raise_on_error:

@@ -49,6 +49,7 @@ void Pass(const EncBatchItem* items, int n, uint8_t* base, const size_t* start, 
     im.gray = it.nch < 3;
     im.has_alpha = (it.nch & 1) ? 0 : 1;
     im.lossless = it.lossless ? 1 : 0;
+    im.cfl = (!it.lossless && it.cfl) ? 1 : 0;
     sl.begin = Up(c.body);
     sl.src = (size_t)((uintptr_t)c.Get<uint8_t>((size_t)it.w * it.nch * it.sample_bytes * it.h) - (uintptr_t)base);
     sl.surface = it.sample_bytes == 1 ? (size_t)((uintptr_t)c.Get<uint8_t>((size_t)it.w * 4 * it.h) - (uintptr_t)base) : sl.src;

@@ -38,13 +38,19 @@ void LayLossyPlanes(Alloc& a, EncImage& im) {
   im.act = a.template Get<float>(ncell);
   im.strat = a.template Get<uint8_t>(ncell);
   if (im.has_alpha) im.alpha_px = a.template Get<int32_t>(npx);
+  if (im.cfl) {   // fitted chroma-from-luma maps: one value per 64x64 tile (an image without them lays out what it always did)
+    const size_t ntile = (size_t)((im.w8 + 7) / 8) * ((im.h8 + 7) / 8);
+    im.ytox = a.template Get<int8_t>(ntile);
+    im.ytob = a.template Get<int8_t>(ntile);
+  }
 }
 
 // lossy: everything that follows from the quantised data - tokens, counters, histograms, section buffers
 template <class Alloc>
 void LayLossyCoding(Alloc& a, EncImage& im) {
+  im.meta_cap = kMetaTokCap + (im.cfl ? kCflTokCap : 0);
   im.tok_lf = a.template Get<DevToken>((size_t)im.nlf * kLfTokCap);
-  im.tok_meta = a.template Get<DevToken>((size_t)im.nlf * kMetaTokCap);
+  im.tok_meta = a.template Get<DevToken>((size_t)im.nlf * im.meta_cap);
   im.tok_ac = a.template Get<DevToken>((size_t)im.ng * kAcTokCap);
   if (im.has_alpha) im.tok_alpha = a.template Get<DevToken>((size_t)im.ng * kAlphaTokCap);
   im.n_ac = a.template Counter<uint32_t>(kEncCount, im.ng);
@@ -52,7 +58,7 @@ void LayLossyCoding(Alloc& a, EncImage& im) {
   im.hist_mod = a.template Counter<uint32_t>(kEncHist, kNumEncLeaves * kEncSyms);
   im.hist_ac = a.template Counter<uint32_t>(kEncHist, (size_t)kAcContexts * kEncSyms);
   const int nsec = EncNumSections(im);
-  im.sec_cap = ((size_t)std::max(kLfTokCap + kMetaTokCap, kAcTokCap + kAlphaTokCap) * kSecBytesPerTok + 256) & ~(size_t)15;
+  im.sec_cap = ((size_t)std::max(kLfTokCap + im.meta_cap, kAcTokCap + kAlphaTokCap) * kSecBytesPerTok + 256) & ~(size_t)15;
   im.sec_bytes = a.template Get<uint8_t>((size_t)nsec * im.sec_cap);
   im.sec_bits = a.template Counter<uint64_t>(kEncSecBits, nsec);
   im.stream_state = a.template Counter<uint32_t>(kEncCount, EncNumStreamStates(im));
@@ -87,7 +93,8 @@ struct EncBatchItem {
   uint32_t w, h;
   int32_t nch;            // 1..4 interleaved samples per pixel
   int32_t sample_bytes;   // 1, 2 or 4
-  int32_t lossless, pad;
+  int32_t lossless;
+  int32_t cfl;            // lossy: chroma-from-luma maps fitted per tile (JxlHipLossyOptions::chroma_from_luma)
 };
 // where the buffers of one image lie that are no field of its EncImage (offsets from the workspace base)
 struct EncBatchSlot {

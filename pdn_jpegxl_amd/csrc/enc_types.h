@@ -16,6 +16,8 @@ constexpr uint32_t kEncSyms = 128;            // token alphabet of the fixed hyb
 constexpr uint32_t kAcContexts = 495 * 15;    // one preset, default block-context map
 constexpr uint32_t kLfTokCap = 3 * 65536;     // tokens per LF group: LF coefficients
 constexpr uint32_t kMetaTokCap = 2 * 65536;   // ... and the two rows of the block info (strategies, quant field)
+constexpr uint32_t kCflTokCap = 2 * 1024;     // ... and, with fitted chroma-from-luma maps, the two maps of its up to 32 x 32 tiles
+constexpr uint32_t kMetaCflBit = 0x80000000u; // n_meta: set when the stream begins with the tokens of the two maps
 constexpr uint32_t kAcTokCap = 3 * 65 * 1024; // tokens per group: 1 + 64 per (block, channel)
 constexpr int32_t kMaxQuantHf = 32767;        // largest |quantised HF value| written: hf_decode_kernel keeps each value as an int16
 // Capacities and the sample depth (jxlhip_save_pixels takes up to 16-bit integers and binary16 / binary32 samples).  The token COUNTS
@@ -69,6 +71,11 @@ struct EncImage {
   int32_t* alpha_px;        // w*h
   int32_t* lfq[3];          // w8*h8 quantised LF (X, Y, B)
   int32_t* rawq;            // w8*h8 raw quant field (1..256)
+  // chroma-from-luma maps fitted per 64x64 tile (cfl != 0; null otherwise: factor 0 for X and 1 for B everywhere)
+  int8_t* ytox;             // ceil(w8 / 8) * ceil(h8 / 8)
+  int8_t* ytob;
+  int32_t cfl;              // JxlHipLossyOptions::chroma_from_luma
+  uint32_t meta_cap;        // tokens of tok_meta per LF group: kMetaTokCap, + kCflTokCap with fitted maps
   // varblocks: `squares` = 0: 8x8 DCTs only (the fast effort); 1: 8x8 / 16x16 / 32x32; 2: also 64x64 and the rectangular
   // 16x8 ... 64x32 shapes (the default effort)
   int32_t squares, pad1;
@@ -96,11 +103,11 @@ struct EncImage {
   const float* rs;          // [(lcy * 4 + lcx) * 64 + ky * 8 + kx]: scale of coefficient (ky, kx) of the lowest cy x cx
   // tokens
   DevToken* tok_lf;         // [nlf][kLfTokCap]
-  DevToken* tok_meta;       // [nlf][kMetaTokCap]
+  DevToken* tok_meta;       // [nlf][meta_cap]
   DevToken* tok_ac;         // [ng][kAcTokCap]
   DevToken* tok_alpha;      // [ng][kAlphaTokCap]
   uint32_t* n_ac;           // [ng]
-  uint32_t* n_meta;         // [nlf] tokens of the block-info stream
+  uint32_t* n_meta;         // [nlf] tokens of the block-info stream (| kMetaCflBit)
   uint32_t* hist_mod;       // [kNumEncLeaves][kEncSyms]
   uint32_t* hist_ac;        // [kAcContexts][kEncSyms]
   // lossless (Modular) frames: whole-image integer channels, tokens per group

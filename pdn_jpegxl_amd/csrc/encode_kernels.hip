@@ -349,6 +349,12 @@ __global__ void enc_strategy_kernel(EncImage im) {
 // every sample position of the region belongs to exactly one varblock, so both DCT passes run over all 4096 positions at once (a
 // thread's loop length is its varblock's height / width), through LDS.  Then per coefficient: its scan position, quantisation,
 // non-zero statistics; and per cell the quantised LF from the varblock's lowest cy x cx coefficients.
+//
+// kFit: the region is one chroma-from-luma tile, and its two map values are fitted here ("Chroma from luma, fitted"):
+// the least-squares factor of the X (B) coefficients on the dequantised Y over the tile's HF positions, as a step of 1 / 84 above the
+// base 0 (1), rounded and clamped to int8; X and B then code what is left after that factor.  The sums are reduced in a fixed order
+// (a thread's 16 positions, the wavefront by shuffles, the four wavefronts through LDS), so the maps are the same run to run.
+template <bool kFit>
 __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
   constexpr int P = 65;
   __shared__ float s_a[64 * P];    // pixels, later the coefficients of the channel
@@ -357,6 +363,7 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
   __shared__ uint8_t s_strat[64];
   __shared__ uint32_t s_nz[64], s_last[64];
   __shared__ float s_fy[64];       // dequantised LF of Y per cell
+  __shared__ float s_red[kFit ? 8 : 1];   // kFit: the sums of the four wavefronts
   const int rw = (im.w8 + 7) / 8;
   const int bx0 = (blockIdx.x % rw) * 8, by0 = (blockIdx.x / rw) * 8;
   const int tid = threadIdx.x;
@@ -408,11 +415,34 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
       s_a[y * P + x] = acc / (float)C;   // every thread reads s_t and writes its own s_a element: no hazard
     }
     __syncthreads();
+    float fac = 0.f;   // kFit: what of the dequantised Y this channel's coefficients are coded against
+    if constexpr (kFit) {
+      if (c != 1) {
+        // s_yd is 0 at the LLF positions and outside the frame, so the sums run over all 4096 positions
+        float sa = 0.f, sd = 0.f;
+        for (int i = tid; i < 4096; i += 256) {
+          const float yd = s_yd[(i >> 6) * P + (i & 63)];
+          sa += s_a[(i >> 6) * P + (i & 63)] * yd;
+          sd += yd * yd;
+        }
+        for (int o = 32; o; o >>= 1) { sa += __shfl_down(sa, o); sd += __shfl_down(sd, o); }
+        if ((tid & 63) == 0) { s_red[(tid >> 6) * 2] = sa; s_red[(tid >> 6) * 2 + 1] = sd; }
+        __syncthreads();
+        const float a = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]), d = (s_red[1] + s_red[3]) + (s_red[5] + s_red[7]);
+        const float base = c == 2 ? 1.f : 0.f;
+        const float m = d > 0.f ? fminf(fmaxf(rintf((a / d - base) * 84.f), -128.f), 127.f) : 0.f;   // (a NaN sum: -128, a valid value)
+        fac = base + m * (1.0f / 84.0f);
+        if (tid == 0) (c == 0 ? im.ytox : im.ytob)[blockIdx.x] = (int8_t)m;
+      }
+    }
     // quantisation of the HF coefficients
     for (int i = tid; i < 4096; i += 256) {
       const int y = i >> 6, x = i & 63;
       int s, oy, ox;
-      if (!geom(y, x, &s, &oy, &ox)) continue;
+      if (!geom(y, x, &s, &oy, &ox)) {
+        if constexpr (kFit) { if (c == 1) s_yd[y * P + x] = 0.f; }   // outside the frame: no part of the fit
+        continue;
+      }
       const int lcx = e_lcx[s], lcy = e_lcy[s], cx = 1 << lcx, cy = 1 << lcy, R = 8 << lcy, C = 8 << lcx;
       const int ky = y - oy, kx = x - ox;
       // stored layout: the longer side runs along a row (squares: transposed)
@@ -426,7 +456,9 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
       int32_t qi = 0;
       if (!(ky < cy && kx < cx)) {   // the lowest cy x cx coefficients travel with the LF image
         const float w = im.dq[e_qtable[s]][(size_t)c * R * C + p];
-        const float target = c == 2 ? coef - s_yd[y * P + x] : coef;
+        float target;
+        if constexpr (kFit) target = c == 1 ? coef : coef - fac * s_yd[y * P + x];
+        else target = c == 2 ? coef - s_yd[y * P + x] : coef;
         const float v = target / (dqs * w);
         // clamped to what a decoder's int16 entry holds (float input far above 1.0 at a small distance gets there); Y's clamped value is
         // the one dequantised below, so B's chroma from luma uses what the decoder will see
@@ -525,11 +557,14 @@ __global__ __launch_bounds__(256) void enc_lf_tokens_kernel(EncImage im) {
 // Block info of an LF group: its varblocks in raster order of their first cells, row 0 = strategies (Zero predictor), row 1 = quant
 // field - 1 (West predictor; the first entry's West is the sample above it, i.e. the first strategy).  One workgroup per LF group:
 // first cells per 64-cell run (one ballot each), a scan over the runs, then both rows are written in parallel.
+// With fitted chroma-from-luma maps that are not all zero anywhere in the frame, the group's tiles of ytox and then of ytob come first
+// (channels 0 and 1 of the stream, raster order, clamped-gradient predictor); n_meta then carries kMetaCflBit.  All-zero maps write
+// nothing, so that the frame is the one without fitting.
 __global__ __launch_bounds__(1024) void enc_meta_tokens_kernel(EncImage im) {
-  __shared__ uint32_t s_hq[kEncSyms], s_hs[kEncSyms];
+  __shared__ uint32_t s_hq[kEncSyms], s_hs[kEncSyms], s_hc[kEncSyms];
   __shared__ uint32_t s_run[1024 + 1];   // first cells before run r (65536 cells / 64)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < (int)kEncSyms; i += 1024) { s_hq[i] = 0; s_hs[i] = 0; }
+  for (int i = tid; i < (int)kEncSyms; i += 1024) { s_hq[i] = 0; s_hs[i] = 0; s_hc[i] = 0; }
   const int g = blockIdx.x;
   const int gx = g % im.xlf, gy = g / im.xlf;
   const int bx0 = gx * kLfGroupBlocks, by0 = gy * kLfGroupBlocks;
@@ -549,7 +584,30 @@ __global__ __launch_bounds__(1024) void enc_meta_tokens_kernel(EncImage im) {
   }
   __syncthreads();
   const uint32_t count = s_run[nrun];
-  DevToken* out = im.tok_meta + (size_t)g * kMetaTokCap;
+  DevToken* out = im.tok_meta + (size_t)g * im.meta_cap;
+  uint32_t ncfl = 0;
+  if (im.cfl) {
+    const int wt = (im.w8 + 7) / 8, ht = (im.h8 + 7) / 8;
+    int any = 0;
+    for (int i = tid; i < wt * ht; i += 1024) any |= im.ytox[i] | im.ytob[i];
+    if (__syncthreads_or(any)) {
+      const int tx0 = bx0 / 8, ty0 = by0 / 8, tw = (bw + 7) / 8, th = (bh + 7) / 8;
+      ncfl = (uint32_t)(2 * tw * th);
+      for (int i = tid; i < (int)ncfl; i += 1024) {
+        const int8_t* pl = (i < tw * th ? im.ytox : im.ytob) + (size_t)ty0 * wt + tx0;
+        const int r = i % (tw * th), y = r / tw, x = r % tw;
+        const ModularWNNW hd = ModularWNNWAt([&](int sx, int sy) { return (int32_t)pl[(size_t)sy * wt + sx]; }, x, y);
+        DevToken t;
+        t.ctx = kLeafCfl;
+        t.value = PackSigned((int32_t)pl[(size_t)y * wt + x] - ModularPredictWNNW(5, hd.W, hd.N, hd.NW));
+        out[i] = t;
+        uint32_t tok, nb, bits;
+        HybridD(t.value, &tok, &nb, &bits);
+        atomicAdd(&s_hc[tok], 1u);
+      }
+      out += ncfl;
+    }
+  }
   const bool with_strategies = im.squares != 0;   // 8x8 only: the strategy row is a constant channel, no token is written for it
   const uint32_t qbase = with_strategies ? count : 0;
   for (int r = wave; r < nrun; r += 16) {
@@ -584,8 +642,9 @@ __global__ __launch_bounds__(1024) void enc_meta_tokens_kernel(EncImage im) {
     atomicAdd(&s_hq[tok], 1u);
   }
   __syncthreads();
-  if (tid == 0) im.n_meta[g] = qbase + count;
+  if (tid == 0) im.n_meta[g] = (ncfl + qbase + count) | (ncfl ? kMetaCflBit : 0u);
   for (int i = tid; i < (int)kEncSyms; i += 1024) {
+    if (s_hc[i]) atomicAdd(&im.hist_mod[kLeafCfl * kEncSyms + i], s_hc[i]);
     if (s_hq[i]) atomicAdd(&im.hist_mod[kLeafQf * kEncSyms + i], s_hq[i]);
     if (s_hs[i]) atomicAdd(&im.hist_mod[kLeafStrategy * kEncSyms + i], s_hs[i]);
   }
@@ -912,7 +971,7 @@ __device__ __forceinline__ bool LossyStream(const EncImage& im, int st, DevToken
     const int gx = g % im.xlf, gy = g / im.xlf;
     const int bw = min(kLfGroupBlocks, im.w8 - gx * kLfGroupBlocks), bh = min(kLfGroupBlocks, im.h8 - gy * kLfGroupBlocks);
     *modular = true;
-    if (st & 1) { *tok = im.tok_meta + (size_t)g * kMetaTokCap; *n = im.n_meta[g]; }
+    if (st & 1) { *tok = im.tok_meta + (size_t)g * im.meta_cap; *n = im.n_meta[g] & ~kMetaCflBit; }
     else { *tok = im.tok_lf + (size_t)g * kLfTokCap; *n = (uint32_t)(3 * bw * bh); }
     return true;
   }
@@ -975,7 +1034,9 @@ __device__ __forceinline__ void SectionsBody(const EncImage& im, int wg, WaveScr
     w.PutUniform(4, 3);   // modular group header: global tree, default weighted-predictor parameters, no transforms
     LossyStream(im, 2 * g, &tok, &n, &modular);
     ForwardPass(tok, n, im.stream_state[2 * g], w);
-    const uint32_t nblocks = im.squares ? im.n_meta[g] / 2 : im.n_meta[g];
+    const uint32_t nm = im.n_meta[g];
+    const uint32_t nrows = (nm & ~kMetaCflBit) - ((nm & kMetaCflBit) ? (uint32_t)(2 * ((bw + 7) / 8) * ((bh + 7) / 8)) : 0u);   // without the maps
+    const uint32_t nblocks = im.squares ? nrows / 2 : nrows;
     w.PutUniform(CeilLog2E((uint32_t)(bw * bh)), nblocks - 1);   // number of varblocks - 1
     w.PutUniform(4, 3);
     LossyStream(im, 2 * g + 1, &tok, &n, &modular);
@@ -1183,19 +1244,21 @@ void LaunchEncPackBgra(const EncImage& im, const uint8_t* src, int nch, hipStrea
     default: hipLaunchKernelGGL(enc_pack_bgra_kernel<4>, grid, block, 0, s, im, src); break;
   }
 }
+void LaunchEncVarblocks(const EncImage& im, hipStream_t s);
 void LaunchEncFrontEnd(const EncImage& im, hipStream_t s) {
   LaunchEncXyb(im, s);
   hipLaunchKernelGGL(enc_sharpen_pad_kernel, dim3(GridFor((size_t)im.wp * im.hp)), dim3(256), 0, s, im);
   hipLaunchKernelGGL(enc_activity_kernel, dim3(GridFor((size_t)im.w8 * im.h8)), dim3(256), 0, s, im);
   const unsigned regions = (unsigned)(((im.w8 + 7) / 8) * ((im.h8 + 7) / 8));
   hipLaunchKernelGGL(enc_strategy_kernel, dim3(GridFor(regions)), dim3(256), 0, s, im);
-  hipLaunchKernelGGL(enc_varblock_kernel, dim3(regions), dim3(256), 0, s, im);
+  LaunchEncVarblocks(im, s);
 }
 // the pieces of the front end the distance map and the closed loop of efforts 8 and 9 launch on their own: samples -> XYB planes
 // (LaunchEncXyb above); DCTs and quantisation again after the quant field has changed (the kernel rewrites every value it wrote)
 void LaunchEncVarblocks(const EncImage& im, hipStream_t s) {
   const unsigned regions = (unsigned)(((im.w8 + 7) / 8) * ((im.h8 + 7) / 8));
-  hipLaunchKernelGGL(enc_varblock_kernel, dim3(regions), dim3(256), 0, s, im);
+  if (im.cfl) hipLaunchKernelGGL(enc_varblock_kernel<true>, dim3(regions), dim3(256), 0, s, im);
+  else hipLaunchKernelGGL(enc_varblock_kernel<false>, dim3(regions), dim3(256), 0, s, im);
 }
 void LaunchEncTokens(const EncImage& im, hipStream_t s) {
   hipLaunchKernelGGL(enc_lf_tokens_kernel, dim3(64, im.nlf), dim3(256), 0, s, im);

@@ -167,8 +167,9 @@ void Progress(ProgressProc progress, int percent) {
 }  // namespace
 
 // The fixed MA tree of this encoder, in decode (breadth-first) order; leaf order = context ids of EncLeaf.  (Not file-local: the
-// test library's self tests serialise it, csrc/selftest.cc.)
-std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf) {
+// test library's self tests serialise it, csrc/selftest.cc.)  cfl_maps: the frame codes fitted chroma-from-luma maps, so their leaf
+// predicts like the LF channels do instead of being a constant; shape and leaf numbering are the same.
+std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf, bool cfl_maps) {
   auto split = [](int prop, int32_t v) { return EncTreeNode{prop, v, 0, 0, 1}; };
   auto leaf = [](int pred, int32_t offset = 0) { return EncTreeNode{-1, 0, pred, offset, 1}; };
   std::vector<EncTreeNode> t;
@@ -182,7 +183,7 @@ std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf) {
   t.push_back(split(0, 1));                                      // 7: channel 2 = B (11) : 12
   t.push_back(leaf(5));                                          // 8: alpha coded in the global section   (kLeafAlphaGlobal)
   t.push_back(split(2, 0));                                      // 9: row 1 = quant field (13) : row 0 = strategies (14)
-  t.push_back(leaf(0));                                          // 10: chroma-from-luma maps, constant 0   (kLeafCfl)
+  t.push_back(leaf(cfl_maps ? 5 : 0));                           // 10: chroma-from-luma maps: constant 0, fitted: gradient (kLeafCfl)
   t.push_back(leaf(5));                                          // 11: LF of B                            (kLeafLfB)
   t.push_back(split(0, 0));                                      // 12: channel 1 = X (15) : channel 0 = Y (16)
   t.push_back(leaf(1));                                          // 13: quant field row, West predictor    (kLeafQf)
@@ -191,6 +192,7 @@ std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf) {
   t.push_back(leaf(5));                                          // 16: LF of Y                            (kLeafLfY)
   return t;
 }
+std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf) { return MakeEncoderTree(nlf, false); }
 
 namespace {
 
@@ -879,10 +881,15 @@ void WriteLossyLfGlobal(const EncImage& im, const LossyParams& qp, const uint32_
   lf_global.Bool(true);   // default block-context map
   lf_global.Bool(true);   // default LF chroma-from-luma parameters
   lf_global.Bool(true);   // global MA tree
-  WriteTree(MakeEncoderTree((uint32_t)im.nlf), lf_global);
+  // fitted chroma-from-luma maps wrote tokens unless every value of the frame is 0 (enc_meta_tokens_kernel); the frame is then the
+  // one without fitting
+  bool cfl_maps = false;
+  for (uint32_t k = 0; k < kEncSyms; k++) cfl_maps |= hist_mod[kLeafCfl * kEncSyms + k] != 0;
+  WriteTree(MakeEncoderTree((uint32_t)im.nlf, cfl_maps), lf_global);
   {
     std::vector<uint8_t> pinned(kNumEncLeaves, 0);
-    pinned[kLeafSharp] = pinned[kLeafCfl] = 1;   // constant channels: no token is ever written
+    pinned[kLeafSharp] = 1;                      // constant channels: no token is ever written
+    pinned[kLeafCfl] = cfl_maps ? 0 : 1;
     pinned[kLeafStrategy] = im.squares ? 0 : 1;  // ... and so is the strategy row while every block is an 8x8 DCT
     BuildAndWriteCode(hist_mod, kNumEncLeaves, kEncModClusters, pinned, lf_global, mcode);
   }
@@ -930,7 +937,8 @@ std::vector<uint8_t> AssembleLossy(const EncImage& im, const EncImageInfo& ii, c
   return out;
 }
 
-void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderImageMetadata* md, IOCallbacks* io, ProgressProc progress) {
+void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const JxlHipLossyOptions& lossy, const EncoderImageMetadata* md, IOCallbacks* io,
+                 ProgressProc progress) {
   Arena A;
   hipStream_t s = nullptr;
   EncImage im;
@@ -958,6 +966,7 @@ void EncodeLossy(const EncSource& src, const EncoderOptions* opt, const EncoderI
   const EncFrameInfo& fi = qp.fi;
   UploadEncTables(A, im);
   // ---- 3. planes, front end
+  im.cfl = lossy.chroma_from_luma;
   LayLossyPlanes(A, im);
   Progress(progress, 15);
   clk.Lap("allocation");
@@ -1204,7 +1213,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus SaveImage(const BitmapData* bitmap, c
     EncSource src;
     src.bmp = bitmap;
     if (options->lossless) EncodeLossless(src, options, metadata, callbacks, progress);   // :214,325
-    else EncodeLossy(src, options, metadata, callbacks, progress);
+    else EncodeLossy(src, options, JxlHipLossyOptions{}, metadata, callbacks, progress);
     return EncoderStatus_Ok;
   } catch (const EncFail& e) {
     if (e.status == EncoderStatus_EncodeError) SetEncErr(err, e.what());
@@ -1267,22 +1276,32 @@ void CheckPixels(const JxlHipPixels* px, const EncoderOptions* opt, const Encode
   if (opt->lossless && src.exp_bits) refuse("lossless float samples are not supported (save lossy, or as integers)");
 }
 
+// The refusals of a JxlHipLossyOptions, on the host
+void CheckLossyOptions(const JxlHipLossyOptions* lossy) {
+  if (lossy->chroma_from_luma < 0 || lossy->chroma_from_luma > 1)
+    throw EncFail(EncoderStatus_EncodeError, "JxlHipLossyOptions: chroma_from_luma must be 0 (maps all zero) or 1 (fitted per tile)");
+  for (int32_t r : lossy->reserved)
+    if (r) throw EncFail(EncoderStatus_EncodeError, "JxlHipLossyOptions: the reserved words must be zero");
+}
+
 }  // namespace
 
 // Part 3 of the C-ABI: SaveImage for every sample type the decoder hands out.  Everything behind the front end is SaveImage's.
-extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels* pixels, const EncoderOptions* options, const EncoderImageMetadata* metadata,
-                                                              IOCallbacks* callbacks, ErrorInfo* err, ProgressProc progress) {
-  if (!pixels || !options || !callbacks || !metadata) return EncoderStatus_NullParameter;
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels_lossy(const JxlHipPixels* pixels, const EncoderOptions* options, const JxlHipLossyOptions* lossy,
+                                                                    const EncoderImageMetadata* metadata, IOCallbacks* callbacks, ErrorInfo* err,
+                                                                    ProgressProc progress) {
+  if (!pixels || !options || !lossy || !callbacks || !metadata) return EncoderStatus_NullParameter;
   try {
     g_last_dist = LastDistances();
     g_last_lossless = JxlHipLosslessInfo();
     EncSource src;
     src.px = pixels;
     CheckPixels(pixels, options, metadata, src);
+    CheckLossyOptions(lossy);
     if (!callbacks->Write) throw EncFail(EncoderStatus_NullParameter, "");
     Progress(progress, 0);
     if (options->lossless) EncodeLossless(src, options, metadata, callbacks, progress);
-    else EncodeLossy(src, options, metadata, callbacks, progress);
+    else EncodeLossy(src, options, *lossy, metadata, callbacks, progress);
     return EncoderStatus_Ok;
   } catch (const EncFail& e) {
     if (e.status == EncoderStatus_EncodeError) SetEncErr(err, e.what());
@@ -1295,6 +1314,12 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels
   } catch (...) {
     return EncoderStatus_EncodeError;
   }
+}
+
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_save_pixels(const JxlHipPixels* pixels, const EncoderOptions* options, const EncoderImageMetadata* metadata,
+                                                              IOCallbacks* callbacks, ErrorInfo* err, ProgressProc progress) {
+  const JxlHipLossyOptions none = {0, {0, 0, 0}};
+  return jxlhip_save_pixels_lossy(pixels, options, &none, metadata, callbacks, err, progress);
 }
 
 // =====================================================================================================
@@ -1386,6 +1411,7 @@ struct BatchJob {
   EncoderImageMetadata md;
   EncoderOptions opt;
   bool lossless = false;
+  JxlHipLossyOptions lossy = {0, {0, 0, 0}};
   LossyParams qp;
   BitWriter lf_global, hf_global;
   EncCode mcode, acode;
@@ -1464,7 +1490,7 @@ void JxlHipEncoder::Run(std::vector<BatchJob>& jobs) {
   std::vector<EncBatchItem> items((size_t)n);
   for (int i = 0; i < n; i++) {
     const JxlHipPixels& px = *jobs[i].src.px;
-    items[i] = EncBatchItem{px.width, px.height, px.num_channels, (int32_t)jobs[i].src.sample_bytes(), jobs[i].lossless ? 1 : 0, 0};
+    items[i] = EncBatchItem{px.width, px.height, px.num_channels, (int32_t)jobs[i].src.sample_bytes(), jobs[i].lossless ? 1 : 0, jobs[i].lossy.chroma_from_luma};
   }
   std::vector<EncImage> ims((size_t)n);
   EncBatchLayout lay;
@@ -1672,6 +1698,12 @@ void CheckBatchImage(const JxlHipPixels* px, const EncoderOptions* opt, const En
 
 extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
                                                                const EncoderImageMetadata* const* metadata, EncoderStatus* statuses, ErrorInfo* err) {
+  return jxlhip_encode_batch_lossy(enc, n, images, options, nullptr, metadata, statuses, err);
+}
+
+extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch_lossy(JxlHipEncoder* enc, int32_t n, const JxlHipPixels* images, const EncoderOptions* options,
+                                                                     const JxlHipLossyOptions* lossy, const EncoderImageMetadata* const* metadata,
+                                                                     EncoderStatus* statuses, ErrorInfo* err) {
   if (!enc || n < 0 || (n > 0 && (!images || !options || !statuses))) return EncoderStatus_NullParameter;
   enc->files.assign((size_t)n, std::vector<uint8_t>());
   enc->stages.clear();
@@ -1697,6 +1729,7 @@ extern "C" JXLFILETYPEIO_API EncoderStatus jxlhip_encode_batch(JxlHipEncoder* en
     if (metadata && metadata[i]) job.md = *metadata[i];
     try {
       CheckBatchImage(&images[i], &options[i], &job.md, job.src);
+      if (lossy) { CheckLossyOptions(&lossy[i]); job.lossy = lossy[i]; }
       job.lossless = options[i].lossless;
       jobs.push_back(std::move(job));
     } catch (const EncFail& e) {

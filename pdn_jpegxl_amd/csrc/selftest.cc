@@ -774,7 +774,7 @@ extern "C" JXLFILETYPEIO_API void jxlhip_selftest_wp(int32_t w, int32_t h, const
 }
 
 // ---- the workspace of a batch encode (csrc/enc_batch_layout.cc: LayEncBatch), measured and then placed at a made-up base.
-// items: 6 int32 per image (w, h, channels, bytes per sample, lossless, 0).  out (int64 each; returns how many the full answer takes):
+// items: 6 int32 per image (w, h, channels, bytes per sample, lossless, fitted chroma-from-luma maps).  out (int64 each; returns how many the full answer takes):
 //   n; total bytes measured; total bytes placed; head bytes; the four region bounds; tables, records_m, mcodes, records_a, acodes, dst_off,
 //   body; total sections; sizeof(EncImage); kEncModCodeBytes; kEncHfCodeBytes; then per image: begin, end, src, surface, sections, count,
 //   and per non-null buffer pointer of its EncImage (in the order of `fields` below) the field's number, the offset the measuring pass
@@ -782,7 +782,7 @@ extern "C" JXLFILETYPEIO_API void jxlhip_selftest_wp(int32_t w, int32_t h, const
 extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_enc_batch_layout(int32_t n, const int32_t* items, int64_t* out, size_t capacity) {
   std::vector<EncBatchItem> it((size_t)n);
   for (int i = 0; i < n; i++)
-    it[i] = EncBatchItem{(uint32_t)items[6 * i], (uint32_t)items[6 * i + 1], items[6 * i + 2], items[6 * i + 3], items[6 * i + 4], 0};
+    it[i] = EncBatchItem{(uint32_t)items[6 * i], (uint32_t)items[6 * i + 1], items[6 * i + 2], items[6 * i + 3], items[6 * i + 4], items[6 * i + 5]};
   std::vector<EncImage> a((size_t)n), b((size_t)n);
   EncBatchLayout la, lb;
   uint8_t* const base = (uint8_t*)((uintptr_t)2 << 44);
