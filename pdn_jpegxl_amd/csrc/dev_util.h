@@ -34,10 +34,19 @@ __host__ __device__ __forceinline__ size_t OrientedIndex(int o, int x, int y, in
 // (0, 31, 62, 93, 123, 152, 180, 206) and thresholds at 2, 3, 5, 9, 13, 21 and 33, computed in registers so that the batched HF
 // token loop has no table lookup in front of its context-map read.  The CPU suite checks all 64 inputs through
 // jxlhip_selftest_nnz_ctx.
+// The thresholds are the set bits of a 64-bit word (threshold t at bit t - 1), so the thresholds still above nzl are one shift and
+// a bit count, and the eight values sit in a second word in that order: six instructions, where seven comparisons with their adds
+// and the wait states between them were twenty-five - on every step of the batched loop.  nzl above 63 (no valid count gives one: a
+// block's non-zeros per covered cell are at most 63) is taken as 63, so that the shift is defined for every input.
 __host__ __device__ __forceinline__ uint32_t NnzBucketCtx(uint32_t nzl) {
-  const uint32_t b = (nzl >= 2) + (nzl >= 3) + (nzl >= 5) + (nzl >= 9) + (nzl >= 13) + (nzl >= 21) + (nzl >= 33);
-  return (uint32_t)(0xCEB4987B5D3E1F00ull >> (8 * b)) & 0xFFu;
+  const uint32_t above = (uint32_t)__builtin_popcountll(0x100101116ull >> (nzl < 63 ? nzl : 63));
+  return (uint32_t)(0x001F3E5D7B98B4CEull >> (8 * above)) & 0xFFu;
 }
+
+// A non-zero HF coefficient leaves the token loops as the upper half of a 32-bit entry (scan position | value << 16): it must fit
+// int16, and a stream with a wider one is refused (kErrRange).  Stated once for HfTakeCoeff and HfTakeToken (HfScalarRun folds the
+// same bound into one OR per value); the CPU suite checks the bounds through jxlhip_selftest_hf_entry_fits.
+__host__ __device__ __forceinline__ bool HfEntryFits(int32_t v) { return v == (int32_t)(int16_t)v; }
 
 // Position context of an HF coefficient token, for ks = scan position / cells the varblock covers, in [1, 63]: the format's three pieces
 // (ks - 1 below 16, then one context per two positions, from 32 on one per four) as the minimum of three lines, without branches.
@@ -51,12 +60,17 @@ __host__ __device__ __forceinline__ uint32_t HfPosCtx(uint32_t ks) {
 // Context of a block's non-zero-count token.  The prediction: from the counts of the block above and the block to the left (each
 // already divided by the cells its block covers), 32 for the group's first block.  Its bucket: clamped at 64, one context per value below
 // 8 and one per two values from there on (0 .. 36).  The CPU suite checks both through jxlhip_selftest_hf_nnz_predict / _bucket.
+// Both are written as selects and minima: as nested conditions they became three exec-masked regions per block start of the batched
+// HF loop, each with its own mask save and restore.  In the first column the block above stands in for the missing left neighbour
+// ((a + a + 1) >> 1 = a); 4 + p / 2 = (p + 8) >> 1 lies below p from 8 on and reaches 36 at the clamp.
 __host__ __device__ __forceinline__ uint32_t HfNnzPredict(uint32_t bx, uint32_t by, uint32_t above, uint32_t left) {
-  return bx == 0 ? (by == 0 ? 32u : above) : (by == 0 ? left : (above + left + 1) >> 1);
+  const uint32_t beside = bx == 0 ? above : left, edge = bx == 0 ? 32u : left, mean = (above + beside + 1) >> 1;
+  const uint32_t top_row = by == 0 ? ~0u : 0u;
+  return mean ^ ((mean ^ edge) & top_row);   // by == 0 ? edge : mean, kept a blend
 }
 __host__ __device__ __forceinline__ uint32_t HfNnzCountBucket(uint32_t predicted) {
-  const uint32_t p = predicted >= 64 ? 64 : predicted;
-  return p < 8 ? p : 4 + p / 2;
+  const uint32_t half = (predicted + 8) >> 1, lim = predicted < 36 ? predicted : 36;
+  return half < lim ? half : lim;
 }
 
 // Integer sample of `bits` bits -> output sample (8 or 16 bits).  Equal depths pass through clamped; otherwise through a [0, 1]

@@ -1471,13 +1471,53 @@ struct HfProfile {
   __device__ __forceinline__ void ScalarRun(uint64_t t0, uint32_t n) { entries++; scalar += clock64() - t0; tokens += n; }
   __device__ __forceinline__ uint64_t GeneralBegin() { general_n++; return clock64(); }
   __device__ __forceinline__ void GeneralEnd(uint64_t t0) { general += clock64() - t0; }
+  // The batched loop: its steps, and the steps on which AT LEAST ONE lane of the wavefront takes a path (a step pays for the union of
+  // its lanes' paths): a block pop, a non-zero-count token, a non-zero coefficient (an entry store), a hybrid-integer tail, a
+  // renormalisation; fill_cols adds up, over the non-zero-count steps, the columns of the widest lane at such a token (1 to 32: the
+  // column writes HfFillColumns issues on that step).  Counted from the state in front of the token,
+  // through the token rules themselves (AnsStep on a bit source that only records that it was asked).
+  struct ProbeBits {
+    static constexpr bool kScalar = false;
+    bool asked = false;
+    __device__ __forceinline__ uint32_t Read(int) { asked = true; return 0; }
+  };
+  uint32_t b_steps = 0, b_pops = 0, b_nnz = 0, b_coef = 0, b_tails = 0, b_renorms = 0, b_fill_cols = 0;
+  template <class Lane, class State>
+  __device__ __forceinline__ void Step(const Lane& L, const State& t, bool is_nnz, bool pop, uint32_t ctx, uint32_t state) {
+    const uint32_t cl = L.tab.cmap[ctx], le = 12 - L.tab.log_alpha;
+    ProbeBits probe;
+    uint32_t st = state;
+    const uint32_t sym = AnsStep(probe, st, L.tab.alias[(cl << L.tab.log_alpha) | AnsBucket(state, le)], le);
+    const bool tail = sym >= (1u << (L.tab.cfg[cl] & 0xF));
+    b_steps++;
+    b_pops += __any(pop) ? 1 : 0;
+    b_nnz += __any(is_nnz) ? 1 : 0;
+    b_coef += __any(!is_nnz && (tail || sym != 0)) ? 1 : 0;   // (a value past the split is never zero)
+    b_tails += __any(tail) ? 1 : 0;
+    b_renorms += __any(probe.asked) ? 1 : 0;
+    for (uint32_t l = 0; l < 6; l++) b_fill_cols += __any(is_nnz && t.lcx >= l) ? (l ? 1u << (l - 1) : 1u) : 0u;
+  }
+  // (lanes leave the loop one by one and stop counting: the wavefront's figures are those of the lane that stayed longest)
+  __device__ __forceinline__ static uint32_t WaveMax(uint32_t v) {
+    for (int m = 1; m < 64; m <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
+    return v;
+  }
   __device__ __forceinline__ void Print(int g, uint32_t nblk, int per_wave) const {
-    if (per_wave == 1)
+    if (per_wave == 1) {
       printf("[hfprof] g %d total %llu scalar-loop %llu (%llu entries, %llu tokens) period %llu (%llu periods) blocks %u general %llu (%llu iterations)\n", g,
              (unsigned long long)(clock64() - start), (unsigned long long)scalar, (unsigned long long)entries, (unsigned long long)tokens,
              (unsigned long long)period, (unsigned long long)periods, nblk, (unsigned long long)general, (unsigned long long)general_n);
+      return;
+    }
+    const uint32_t steps = WaveMax(b_steps), pops = WaveMax(b_pops), nnz = WaveMax(b_nnz), coef = WaveMax(b_coef), tails = WaveMax(b_tails),
+                   renorms = WaveMax(b_renorms), fill_cols = WaveMax(b_fill_cols);
+    const uint32_t sections = (uint32_t)__popcll(__ballot(1));
+    if ((threadIdx.x & 63) == 0 && steps)
+      printf("[hfstep] workgroups %u wg %u wave %u sections %u cycles %llu steps %u pops %u nnz %u coef %u tails %u renorms %u fill_cols %u\n", gridDim.x,
+             blockIdx.x, threadIdx.x >> 6, sections, (unsigned long long)(clock64() - start), steps, pops, nnz, coef, tails, renorms, fill_cols);
   }
 #else
+  template <class Lane, class State> __device__ __forceinline__ void Step(const Lane&, const State&, bool, bool, uint32_t, uint32_t) {}
   __device__ __forceinline__ uint64_t Now() const { return 0; }
   __device__ __forceinline__ void Period(uint64_t) {}
   __device__ __forceinline__ void ScalarRun(uint64_t, uint32_t) {}
@@ -1570,29 +1610,57 @@ __device__ __forceinline__ uint32_t HfNzPerCell(const HfState& t) { return (t.nz
 // context of the non-zero-count token of slot ci, from the column values above (x = bx) and to the left (x = bx - 1, or 0)
 template <bool kLds>
 __device__ __forceinline__ uint32_t HfNnzCtx(const HfLane<kLds>& L, const HfState& t, int ci, uint32_t above, uint32_t left) {
-  return L.ctx_offset + HfNnzCountBucket(HfNnzPredict(t.bx, t.by, above, left)) * L.nbc + ((t.ctxs >> (5 * ci)) & 31);
+  // (at most 37 buckets times at most 16 block contexts: the full-rate 24-bit product)
+  return L.ctx_offset + __umul24(HfNnzCountBucket(HfNnzPredict(t.bx, t.by, above, left)), L.nbc) + ((t.ctxs >> (5 * ci)) & 31);
 }
 // context of the coefficient token at t.k; nz_ctx: the context offset of HfNzPerCell (NnzBucketCtx, or d_nnz_ctx where a lookup is cheaper)
 __device__ __forceinline__ uint32_t HfCoeffCtx(const HfState& t, uint32_t nz_ctx) {
   return t.histo + (nz_ctx + HfPosCtx(t.k >> t.log2c)) * 2 + t.prev;
 }
+// The columns [bx, bx + (1 << lcx)) of channel c take `fill`.  Written without a loop over the lane's own width: column bx, then 1, 2
+// and 4 more writes while ANY lane of the wavefront is that wide, a narrower lane writing one of its own columns again (ix & (width - 1)).
+// As a per-lane loop the wavefront ran eleven instructions per column of its widest lane - 2.4 columns on the average non-zero-count
+// step of the 4K batch (profiles/hf_step_parent.json).
+template <bool kLds>
+__device__ __forceinline__ void HfFillColumns(const HfLane<kLds>& L, const HfState& t, int c, uint32_t fill) {
+  JXL_LDS uint8_t* const cc = L.col + __umul24(c * 32 + t.bx, L.nslots);
+  const uint32_t last = (1u << t.lcx) - 1;
+  cc[0] = (uint8_t)fill;
+  if (__any(last >= 1)) {
+    cc[__umul24(1u & last, L.nslots)] = (uint8_t)fill;
+    if (__any(last >= 2)) {
+#pragma unroll
+      for (uint32_t ix = 2; ix < 4; ix++) cc[__umul24(ix & last, L.nslots)] = (uint8_t)fill;
+      if (__any(last >= 4)) {
+#pragma unroll
+        for (uint32_t ix = 4; ix < 8; ix++) cc[__umul24(ix & last, L.nslots)] = (uint8_t)fill;
+        // (128 and 256 samples across: 16 and 32 columns, one more write each while any lane still has one)
+        for (uint32_t ix = 8; __any(last >= ix); ix++) cc[__umul24(ix & last, L.nslots)] = (uint8_t)fill;
+      }
+    }
+  }
+}
+// first context of the coefficient tokens of slot t.ci
+template <bool kLds>
+__device__ __forceinline__ uint32_t HfCoeffHisto(const HfLane<kLds>& L, const HfState& t) {
+  return L.ctx_offset + L.nbc * 37 + 458 * ((t.ctxs >> (5 * t.ci)) & 31);
+}
+// `prev` of a channel's first coefficient token, from its non-zero count
+__device__ __forceinline__ uint32_t HfFirstPrev(const HfState& t, uint32_t nzeros) { return nzeros > t.size / 16 ? 0 : 1; }
 // A non-zero count u arrives: bound check (false: the stream is corrupt, nothing recorded), the columns the block covers, the
 // (first entry, count) record, and on to the channel's coefficients - or, with none, to the next channel.
 template <bool kLds>
 __device__ __forceinline__ bool HfTakeNnz(const HfLane<kLds>& L, HfState& t, uint32_t u) {
   t.nzeros = u;
   if (t.nzeros + t.covered > t.size) return false;
-  const uint32_t fill = HfNzPerCell(t);
   const int c = HfChannel(t.ci);
-  JXL_LDS uint8_t* const cc = L.col + __umul24(c * 32 + t.bx, L.nslots);
-  for (uint32_t ix = 0; ix < (1u << t.lcx); ix++) cc[__umul24(ix, L.nslots)] = (uint8_t)fill;
+  HfFillColumns(L, t, c, HfNzPerCell(t));
   U2 rec;
   rec.x = t.epos; rec.y = t.nzeros;
   L.cblk[(size_t)c * L.ncells + t.cell] = rec;
   if (t.nzeros) {
-    const uint32_t block_ctx = (t.ctxs >> (5 * t.ci)) & 31;
-    t.histo = L.ctx_offset + L.nbc * 37 + 458 * block_ctx;
-    t.prev = t.nzeros > t.size / 16 ? 0 : 1;
+    t.histo = HfCoeffHisto(L, t);
+    t.prev = HfFirstPrev(t, t.nzeros);
     t.k = t.covered;
     t.want_nz = false;
   } else {
@@ -1607,7 +1675,7 @@ template <bool kLds>
 __device__ __forceinline__ bool HfTakeCoeff(const HfLane<kLds>& L, HfState& t, uint32_t u, uint32_t& err) {
   if (u) {
     const int32_t v = UnpackSigned(u);
-    if (v != (int32_t)(int16_t)v) err |= kErrRange;
+    if (!HfEntryFits(v)) err |= kErrRange;
     L.ent[t.epos++] = t.k | (uint32_t)v << 16;
     t.prev = 1;
     if (--t.nzeros == 0) { t.want_nz = true; t.ci++; }
@@ -1615,6 +1683,39 @@ __device__ __forceinline__ bool HfTakeCoeff(const HfLane<kLds>& L, HfState& t, u
     t.prev = 0;
   }
   return !(++t.k >= t.size && t.nzeros != 0);
+}
+// HfTakeNnz and HfTakeCoeff in one, for a loop whose wavefront holds lanes at both kinds of token on most steps: the two then run
+// one after the other, each under its own exec mask, and every value they both set is merged from two masked copies.  Here what both
+// set - nzeros, k, prev, the step to the next slot - is one select per value, and only the writes (columns and record; the entry) sit
+// under a mask.  The lane is at a non-zero count exactly while the channel owes no non-zeros (t.nzeros == 0: `is_nnz`, which this form
+// uses in place of t.want_nz).  fv: the fill of slot t.ci goes to fv[t.ci] (the caller's copy of what the columns now hold).
+// false: the stream is corrupt (as in the two above; the lane must stop).
+template <bool kLds>
+__device__ __forceinline__ bool HfTakeToken(const HfLane<kLds>& L, HfState& t, bool is_nnz, uint32_t u, uint32_t& err, uint32_t& fv0, uint32_t& fv1,
+                                            uint32_t& fv2) {
+  const bool entry = !is_nnz && u != 0;   // a non-zero coefficient
+  const int32_t v = UnpackSigned(u);
+  err |= entry && !HfEntryFits(v) ? (uint32_t)kErrRange : 0u;
+  if (entry) L.ent[t.epos] = t.k | (uint32_t)v << 16;
+  const uint32_t owed = is_nnz ? u : t.nzeros - (entry ? 1u : 0u);
+  const bool room = u + t.covered <= t.size;               // a count: the block has that many positions
+  const bool ran_out = t.k + 1 >= t.size && owed != 0;     // a coefficient: the last position is taken and non-zeros are still owed
+  if (is_nnz && room) {
+    const uint32_t fill = (u + t.covered - 1) >> t.log2c;   // HfNzPerCell of the new count
+    const int c = HfChannel(t.ci);
+    HfFillColumns(L, t, c, fill);
+    fv0 = t.ci == 0 ? fill : fv0; fv1 = t.ci == 1 ? fill : fv1; fv2 = t.ci == 2 ? fill : fv2;
+    U2 rec;
+    rec.x = t.epos; rec.y = u;
+    L.cblk[(size_t)c * L.ncells + t.cell] = rec;
+    t.histo = HfCoeffHisto(L, t);
+  }
+  t.epos += entry ? 1u : 0u;
+  t.prev = is_nnz ? HfFirstPrev(t, u) : (entry ? 1u : 0u);
+  t.k = is_nnz ? t.covered : t.k + 1;
+  t.nzeros = owed;
+  t.ci += owed == 0 ? 1 : 0;   // a count of zero, or the channel's last non-zero (a zero coefficient leaves owed != 0)
+  return is_nnz ? room : !ran_out;
 }
 
 // ---- loop 1: several sections per wavefront, plain ANS.
@@ -1630,11 +1731,19 @@ __device__ __forceinline__ void HfBatchedLoop(const HfLane<kLds>& L, HfBits& b, 
   uint32_t d_next = 0, d_after = 0;                  // descriptors of blocks bi and bi + 1 (valid from the first pop on)
   uint32_t up0 = 0, up1 = 0, up2 = 0, lf0 = 0, lf1 = 0, lf2 = 0;   // col[] above (x = bx) / left (x = bx - 1) of block bi, as read
   uint32_t pbx = 0, pcx = 0, fv0 = 0, fv1 = 0, fv2 = 0;           // the previous block's columns [pbx, pbx + pcx) and its fills
-  while (!err) {
+  // The loop has ONE exit, tested at its end, and no lane mask carried from step to step but that one: a lane is done after an error
+  // or when its last block is finished.  (With `break` inside the masked regions of the two token kinds, and want_nz carried as a lane
+  // mask, the loop's own bookkeeping was some thirty scalar mask instructions on every step - of about 200 instructions a step issues,
+  // 82 scalar: profiles/hf_step_parent.json.)
+  // (A group without blocks - only a refused layout leaves one - skips the loop and with it the one top-up the old form ran before its
+  // first pop broke out.  Nothing has been consumed then, and SectionEndOk reads the state, the general reader's error flag and the
+  // bits consumed, none of which a top-up touches.)
+  bool done = err != 0 || L.nblk == 0;
+  while (!done) {
     if ((it & (kHfTop - 1)) == 0) HfPeriod(L, b, q, pf);
-    // One straight-line step per token for both token kinds: the wavefront almost always holds a lane that starts a block and one
-    // that reads a non-zero count, so what used to be their own code paths (descriptor read -> col[] reads -> context map) headed
-    // nearly every step.  Now the loop-carried chain is context map -> alias entry (+ cfg beside it) -> state.
+    // One straight-line step per token for both token kinds.  On the 4K batch a lane of the wavefront starts a block on 11 % of the
+    // steps and reads a non-zero count on 28 %: their former code paths (descriptor read -> col[] reads -> context map) are off the
+    // loop-carried chain, which is context map -> alias entry (+ cfg beside it) -> state.
     auto colv = [&](uint32_t c, uint32_t x) { return (uint32_t)L.col[__umul24(c * 32 + x, nslots)]; };
     auto look_ahead = [&]() {   // col[] around block bi (descriptor d_next), read before the current block's fills land
       const uint32_t x = d_next & 31, xl = x ? x - 1 : 0;
@@ -1642,8 +1751,9 @@ __device__ __forceinline__ void HfBatchedLoop(const HfLane<kLds>& L, HfBits& b, 
       up1 = colv(0, x); lf1 = colv(0, xl);
       up2 = colv(2, x); lf2 = colv(2, xl);
     };
-    if (t.want_nz && t.ci >= 3) {
-      if (q.bi >= L.nblk) break;
+    const bool is_nnz = t.nzeros == 0;   // the lane is at a non-zero count (see HfTakeToken)
+    const bool pop = is_nnz && t.ci >= 3;   // (with a block left: the lane would be done otherwise)
+    if (pop) {
       if (q.bi == 0) {   // first block of the section: nothing read ahead yet, and no previous block to patch from
         d_next = L.dq[0];
         d_after = L.dq[__umul24(1u & kHfDqMask, nslots)];
@@ -1653,9 +1763,14 @@ __device__ __forceinline__ void HfBatchedLoop(const HfLane<kLds>& L, HfBits& b, 
       HfUnpackBlock(t, d_next, L.w8);
       const uint32_t xl = t.bx ? t.bx - 1 : 0;
       const bool up_prev = t.bx - pbx < pcx, lf_prev = xl - pbx < pcx;   // columns the previous block filled after the reads
-      nz_ctx0 = HfNnzCtx(L, t, 0, up_prev ? fv0 : up0, lf_prev ? fv0 : lf0);
-      nz_ctx1 = HfNnzCtx(L, t, 1, up_prev ? fv1 : up1, lf_prev ? fv1 : lf1);
-      nz_ctx2 = HfNnzCtx(L, t, 2, up_prev ? fv2 : up2, lf_prev ? fv2 : lf2);
+      // The six neighbour values are formed HERE, whichever of them the prediction of this block's position uses: left to the compiler
+      // each select sinks into a branch on bx / by of its own (three masked regions with mask save and restore per pop).
+      uint32_t a0 = up_prev ? fv0 : up0, l0 = lf_prev ? fv0 : lf0, a1 = up_prev ? fv1 : up1, l1 = lf_prev ? fv1 : lf1;
+      uint32_t a2 = up_prev ? fv2 : up2, l2 = lf_prev ? fv2 : lf2;
+      asm volatile("" : "+v"(a0), "+v"(l0), "+v"(a1), "+v"(l1), "+v"(a2), "+v"(l2));
+      nz_ctx0 = HfNnzCtx(L, t, 0, a0, l0);
+      nz_ctx1 = HfNnzCtx(L, t, 1, a1, l1);
+      nz_ctx2 = HfNnzCtx(L, t, 2, a2, l2);
       pbx = t.bx; pcx = 1u << t.lcx;
       q.bi++;
       // block bi is at most two ahead of the last pop of a period, so its descriptor and the next one are already queued
@@ -1667,18 +1782,15 @@ __device__ __forceinline__ void HfBatchedLoop(const HfLane<kLds>& L, HfBits& b, 
       d_after = L.dq[__umul24((q.bi + 1) & kHfDqMask, nslots)];
     }
     const uint32_t nzc = t.ci == 0 ? nz_ctx0 : (t.ci == 1 ? nz_ctx1 : nz_ctx2);
-    const uint32_t u = AnsGet(b, state, L.tab, t.want_nz ? nzc : HfCoeffCtx(t, NnzBucketCtx(HfNzPerCell(t))));
+    const uint32_t ctx = is_nnz ? nzc : HfCoeffCtx(t, NnzBucketCtx(HfNzPerCell(t)));
+    pf.Step(L, t, is_nnz, pop, ctx, state);
+    const uint32_t u = AnsGet(b, state, L.tab, ctx);
     it++;
-    if (t.want_nz) {
-      const int ci = t.ci;
-      if (!HfTakeNnz(L, t, u)) { err |= kErrBitstream; break; }
-      const uint32_t fill = HfNzPerCell(t);   // what the block's columns now hold
-      fv0 = ci == 0 ? fill : fv0; fv1 = ci == 1 ? fill : fv1; fv2 = ci == 2 ? fill : fv2;
-    } else if (!HfTakeCoeff(L, t, u, err)) {
-      err |= kErrBitstream;
-      break;
-    }
+    const bool ok = HfTakeToken(L, t, is_nnz, u, err, fv0, fv1, fv2);
+    err |= ok ? 0u : (uint32_t)kErrBitstream;
+    done = err != 0 || (t.nzeros == 0 && t.ci >= 3 && q.bi >= L.nblk);
   }
+  t.want_nz = t.nzeros == 0;
 }
 
 // ---- loop 2: one section per wavefront (single frames, small batches), plain ANS: one run of coefficient tokens.

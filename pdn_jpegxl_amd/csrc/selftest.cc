@@ -213,6 +213,8 @@ extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_hf_nnz_predict(uint32_t bx
   return HfNnzPredict(bx, by, above, left);
 }
 extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_hf_nnz_bucket(uint32_t predicted) { return HfNnzCountBucket(predicted); }
+// whether the coefficient of token value u (signed values packed as UnpackSigned unpacks them) fits an entry
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_hf_entry_fits(uint32_t u) { return HfEntryFits(UnpackSigned(u)) ? 1 : 0; }
 
 // An entropy-coded stream of n (context, value) tokens over num_ctx contexts, as the encoder writes its host-side streams (code header
 // by BuildAndWriteCode, tokens by WriteTokensHost): the CPU and GPU tests write patch dictionaries with it.  Writes the bytes into dst
