@@ -10,7 +10,7 @@ LIBNAME = "libJpegXLFileTypeIO_X64.so"
 TEST_LIBNAME = "libjxlhip_selftest.so"   # the product's objects + csrc/selftest.cc: writer self tests for the CPU suite, never shipped
 TEST_SOURCES = ["selftest.cc"]
 SOURCES = ["kernels.hip", "entropy_kernels.hip", "tile_kernels.hip", "encode_kernels.hip", "enc_animation_kernels.hip", "lossless_kernels.hip", "distance_kernels.hip", "compose_kernels.hip", "patch_kernels.hip", "noise_kernels.hip", "downscale_kernels.hip", "host_parse.cc", "host_write.cc", "icc.cc", "entropy_plan.cc", "batch_layout.cc", "animation.cc", "enc_batch_layout.cc", "enc_animation.cc", "decoder.cc", "encoder.cc"]
-HEADERS = ["dev_types.h", "dev_util.h", "modular_rules.h", "modular_uniform.h", "enc_types.h", "enc_batch_layout.h", "enc_animation.h", "enc_dev.h", "kernels.h", "lds_layout.h", "entropy_plan.h", "batch_layout.h", "animation.h", "host_parse.h", "host_write.h", "icc.h", os.path.join("..", "..", "include", "jxlfiletypeio.h")]
+HEADERS = ["dev_types.h", "dev_util.h", "modular_rules.h", "varblock_rules.h", "modular_uniform.h", "enc_types.h", "enc_batch_layout.h", "enc_animation.h", "enc_dev.h", "kernels.h", "lds_layout.h", "entropy_plan.h", "batch_layout.h", "animation.h", "host_parse.h", "host_write.h", "icc.h", os.path.join("..", "..", "include", "jxlfiletypeio.h")]
 
 
 def lib_path():

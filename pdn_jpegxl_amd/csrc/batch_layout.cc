@@ -1,5 +1,6 @@
 // The layout of a decode batch (batch_layout.h): every buffer is sized, typed and assigned in one statement of BuildBatch.
 #include "batch_layout.h"
+#include "varblock_rules.h"
 #include <cmath>
 #include "../../include/jxlfiletypeio.h"
 
@@ -7,7 +8,7 @@ namespace jxlhip {
 
 // Order bucket of a quant table (every strategy of a quant table shares one bucket).
 static int OrderBucketOfQuantTable(int q) {
-  for (int s = 0; s < kNumStrategies; s++) if (kStrategyQuantTable[s] == q) return kStrategyOrderBucket[s];
+  for (int s = 0; s < kNumStrategies; s++) if ((int)StrategyQuantTable(s) == q) return (int)StrategyOrderBucket(s);
   return 0;
 }
 

@@ -145,7 +145,7 @@ struct DevImage {
   float* lf_final[3];       // what LLF reads (lf_tmp when smoothing is on)
   uint8_t* lf_extra;        // per LF group: extra_precision
   int32_t* lfq[3];          // quantised LF (X,Y,B)
-  uint32_t* cellinfo;       // per 8x8 cell: strategy | ix << 8 | iy << 13 | log2cx << 18 | log2cy << 21 | valid << 31
+  uint32_t* cellinfo;       // per 8x8 cell: the info word of varblock_rules.h (CellInfoPack and its accessors)
   uint16_t* rawq;           // per cell
   uint8_t* sharp;           // per cell
   int8_t* ytox;             // per 64x64 tile

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "dev_util.h"
 #include "enc_types.h"
+#include "varblock_rules.h"
 
 namespace jxlhip {
 namespace {
@@ -124,10 +125,6 @@ __global__ __launch_bounds__(256) void dist_cell_kernel(DistMap dm) {
   }
 }
 
-// cells covered across / down (log2) by strategy code, as encode_kernels.hip
-__device__ const uint8_t d_lcx[27] = {0, 0, 0, 0, 1, 2, 0, 1, 0, 2, 1, 2, 0, 0, 0, 0, 0, 0, 3, 2, 3, 4, 3, 4, 5, 4, 5};
-__device__ const uint8_t d_lcy[27] = {0, 0, 0, 0, 1, 2, 1, 0, 2, 0, 2, 1, 0, 0, 0, 0, 0, 0, 3, 3, 2, 4, 4, 3, 5, 5, 4};
-
 // One thread per cell; the thread of a varblock's first cell takes the maximum of its cells' distances and writes the corrected quant
 // field to every cell it covers (no other thread writes them).
 __global__ void dist_correct_kernel(EncImage im, const float* __restrict__ cell, const int32_t* __restrict__ q0, float tau, float p_up,
@@ -137,7 +134,7 @@ __global__ void dist_correct_kernel(EncImage im, const float* __restrict__ cell,
   if (i >= ncell || !(tau > 0.f)) return;
   const uint32_t st = im.strat[i];
   if (!(st & 0x80)) return;
-  const int cx = 1 << d_lcx[st & 0x7F], cy = 1 << d_lcy[st & 0x7F];
+  const int cx = 1 << StrategyLog2Cx(st & 0x7F), cy = 1 << StrategyLog2Cy(st & 0x7F);
   float tv = 0.f;
   for (int y = 0; y < cy; y++)
     for (int x = 0; x < cx; x++) tv = fmaxf(tv, cell[i + y * im.w8 + x]);

@@ -18,6 +18,7 @@
 #include "enc_dev.h"
 #include "enc_types.h"
 #include "kernels.h"
+#include "varblock_rules.h"
 
 namespace jxlhip {
 
@@ -289,12 +290,6 @@ __global__ void enc_activity_kernel(EncImage im) {
   }
 }
 
-// Strategy tables (the shapes this encoder uses): cells covered across / down (log2), order bucket, quantisation table.
-__device__ const uint8_t e_lcx[27] = {0, 0, 0, 0, 1, 2, 0, 1, 0, 2, 1, 2, 0, 0, 0, 0, 0, 0, 3, 2, 3, 4, 3, 4, 5, 4, 5};
-__device__ const uint8_t e_lcy[27] = {0, 0, 0, 0, 1, 2, 1, 0, 2, 0, 2, 1, 0, 0, 0, 0, 0, 0, 3, 3, 2, 4, 4, 3, 5, 5, 4};
-__device__ const uint8_t e_bucket[27] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-__device__ const uint8_t e_qtable[27] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-
 // One thread per aligned 64x64 region (8 x 8 cells).  The choice is the raster-greedy one: cells in raster order, at every free cell the
 // largest shape of the list that is aligned to its own size there, lies inside the frame, covers only free cells and whose cells' maximum
 // activity stays under the shape's threshold.  Shapes of at most 64 points aligned to their size never leave their aligned 64x64
@@ -315,7 +310,7 @@ __global__ void enc_strategy_kernel(EncImage im) {
           for (int t = 0; t < 9; t++) {
             const int cand = kShape[t];
             if (im.squares == 1 && cand != 5 && cand != 4) continue;
-            const int cx = 1 << e_lcx[cand], cy = 1 << e_lcy[cand];
+            const int cx = 1 << StrategyLog2Cx(cand), cy = 1 << StrategyLog2Cy(cand);
             if ((ix & (cx - 1)) || (iy & (cy - 1)) || bx0 + ix + cx > im.w8 || by0 + iy + cy > im.h8) continue;
             const uint64_t rowm = ((1ull << cx) - 1) << ix;
             uint64_t m = 0;
@@ -326,7 +321,7 @@ __global__ void enc_strategy_kernel(EncImage im) {
               for (int x = 0; x < cx; x++) mx = fmaxf(mx, im.act[(size_t)(by0 + iy + y) * im.w8 + bx0 + ix + x]);
             if (mx < kThr[t]) { s = cand; break; }
           }
-        const int cx = 1 << e_lcx[s], cy = 1 << e_lcy[s];
+        const int cx = 1 << StrategyLog2Cx(s), cy = 1 << StrategyLog2Cy(s);
         double a = 0;
         for (int y = 0; y < cy; y++)
           for (int x = 0; x < cx; x++) a += im.act[(size_t)(by0 + iy + y) * im.w8 + bx0 + ix + x];
@@ -378,12 +373,12 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
     if (st == 0xFF) return false;
     const int sc = (int)(st & 0x7F);
     *s = sc;
-    *oy = y & ~((8 << e_lcy[sc]) - 1);
-    *ox = x & ~((8 << e_lcx[sc]) - 1);
+    *oy = y & ~((8 << StrategyLog2Cy(sc)) - 1);
+    *ox = x & ~((8 << StrategyLog2Cx(sc)) - 1);
     return true;
   };
   for (int ci = 0; ci < 3; ci++) {
-    const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+    const int c = ChannelOfTeam(ci);
     if (tid < 64) { s_nz[tid] = 0; s_last[tid] = 0; }
     for (int i = tid; i < 4096; i += 256) {
       const int y = i >> 6, x = i & 63;
@@ -396,7 +391,7 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
       const int y = i >> 6, x = i & 63;
       int s, oy, ox;
       if (!geom(y, x, &s, &oy, &ox)) continue;
-      const int lr = e_lcy[s], R = 8 << lr, ky = y - oy;
+      const int lr = StrategyLog2Cy(s), R = 8 << lr, ky = y - oy;
       const float* b = im.basis_div[lr] + ky * R;
       float acc = 0.f;
       for (int k = 0; k < R; k++) acc += b[k] * s_a[(oy + k) * P + x];
@@ -408,7 +403,7 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
       const int y = i >> 6, x = i & 63;
       int s, oy, ox;
       if (!geom(y, x, &s, &oy, &ox)) continue;
-      const int lc = e_lcx[s], C = 8 << lc, kx = x - ox;
+      const int lc = StrategyLog2Cx(s), C = 8 << lc, kx = x - ox;
       const float* b = im.basis[lc] + kx * C;
       float acc = 0.f;
       for (int k = 0; k < C; k++) acc += s_t[y * P + ox + k] * b[k];
@@ -443,19 +438,18 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
         if constexpr (kFit) { if (c == 1) s_yd[y * P + x] = 0.f; }   // outside the frame: no part of the fit
         continue;
       }
-      const int lcx = e_lcx[s], lcy = e_lcy[s], cx = 1 << lcx, cy = 1 << lcy, R = 8 << lcy, C = 8 << lcx;
+      const int lcx = StrategyLog2Cx(s), lcy = StrategyLog2Cy(s), cx = 1 << lcx, R = 8 << lcy, C = 8 << lcx;
       const int ky = y - oy, kx = x - ox;
-      // stored layout: the longer side runs along a row (squares: transposed)
-      const uint32_t p = R >= C ? (uint32_t)(kx * R + ky) : (uint32_t)(ky * C + kx);
-      const uint32_t k = im.scan_of[e_bucket[s]][p];
+      const uint32_t p = StoredIndex((uint32_t)ky, (uint32_t)kx, StoredLog2Pitch(lcx, lcy), R >= C);   // (R >= C: StoredTransposed of a plain DCT, from the lengths at hand - the log2 form costs this kernel a VGPR)
+      const uint32_t k = im.scan_of[StrategyOrderBucket(s)][p];
       const int fcell = (oy >> 3) * 8 + (ox >> 3);         // first cell of the varblock, within the region
       const size_t first = (size_t)(by0 + (oy >> 3)) * im.w8 + bx0 + (ox >> 3);
       const float scale = im.inv_gs / (float)im.rawq[first];
       const float dqs = c == 1 ? scale : (c == 0 ? scale * im.x_dm : scale * im.b_dm);
       const float coef = s_a[y * P + x];
       int32_t qi = 0;
-      if (!(ky < cy && kx < cx)) {   // the lowest cy x cx coefficients travel with the LF image
-        const float w = im.dq[e_qtable[s]][(size_t)c * R * C + p];
+      if (!IsLlfPosition(ky, kx, lcx, lcy)) {   // the lowest cy x cx coefficients travel with the LF image
+        const float w = im.dq[StrategyQuantTable(s)][(size_t)c * R * C + p];
         float target;
         if constexpr (kFit) target = c == 1 ? coef : coef - fac * s_yd[y * P + x];
         else target = c == 2 ? coef - s_yd[y * P + x] : coef;
@@ -464,8 +458,7 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
         // the one dequantised below, so B's chroma from luma uses what the decoder will see
         qi = fabsf(v) < 0.6f ? 0 : (int32_t)rintf(fminf(fmaxf(v, -(float)kMaxQuantHf), (float)kMaxQuantHf));
         if (c == 1) {
-          const float adj = qi == 0 ? 0.f : (abs(qi) == 1 ? (qi > 0 ? im.qbias1 : -im.qbias1) : (float)qi - im.qbias3 / (float)qi);
-          s_yd[y * P + x] = adj * dqs * w;
+          s_yd[y * P + x] = DequantBias(qi, im.qbias1, im.qbias3, ExactQuotient()) * dqs * w;
         }
       } else if (c == 1) {
         s_yd[y * P + x] = 0.f;
@@ -484,7 +477,7 @@ __global__ __launch_bounds__(256) void enc_varblock_kernel(EncImage im) {
       if (st != 0xFF) {
         int s, oy, ox;
         geom(iy * 8, ix * 8, &s, &oy, &ox);
-        const int lcx = e_lcx[s], lcy = e_lcy[s], cx = 1 << lcx, cy = 1 << lcy;
+        const int lcx = StrategyLog2Cx(s), lcy = StrategyLog2Cy(s), cx = 1 << lcx, cy = 1 << lcy;
         const int fcell = (oy >> 3) * 8 + (ox >> 3), py = iy - (oy >> 3), px = ix - (ox >> 3);
         const size_t cell = (size_t)(by0 + iy) * im.w8 + bx0 + ix;
         // IDCT of the cy x cx lowest coefficients, undoing the resampling scale: horizontal then vertical
@@ -695,11 +688,11 @@ __global__ __launch_bounds__(256) void enc_ac_tokens_kernel(EncImage im) {
   for (int e = tid; e < 3072; e += 256) {
     uint32_t cnt = 0;
     if (e < nent) {
-      const int blk = e / 3, ci = e % 3, c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+      const int blk = e / 3, ci = e % 3, c = ChannelOfTeam(ci);
       const size_t cell = (size_t)(by0 + blk / bw) * im.w8 + bx0 + blk % bw;
       const uint32_t st = im.strat[cell];
       if (st & 0x80) {
-        const uint32_t covered = 1u << (e_lcx[st & 0x7F] + e_lcy[st & 0x7F]);
+        const uint32_t covered = 1u << (StrategyLog2Cx(st & 0x7F) + StrategyLog2Cy(st & 0x7F));
         cnt = 1u + (im.nzc[c][cell] ? (uint32_t)im.last[c][cell] + 1u - covered : 0u);
       }
     }
@@ -722,12 +715,12 @@ __global__ __launch_bounds__(256) void enc_ac_tokens_kernel(EncImage im) {
   for (int k = 0; k < 12; k++) {
     const int e = tid * 12 + k;
     if (e >= nent) break;
-    const int blk = e / 3, ci = e % 3, c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+    const int blk = e / 3, ci = e % 3, c = ChannelOfTeam(ci);
     const int bx = blk % bw, by = blk / bw;
     const size_t cell = (size_t)(by0 + by) * im.w8 + bx0 + bx;
     const uint32_t st = im.strat[cell];
     if (!(st & 0x80)) continue;
-    const uint32_t sc = st & 0x7F, lcx = e_lcx[sc], cc = 1u << lcx, log2c = lcx + e_lcy[sc], covered = 1u << log2c, size = covered << 6;
+    const uint32_t sc = st & 0x7F, lcx = StrategyLog2Cx(sc), cc = 1u << lcx, log2c = lcx + StrategyLog2Cy(sc), covered = 1u << log2c, size = covered << 6;
     const uint8_t* nzp = im.nz[c];
     const uint32_t nzeros0 = im.nzc[c][cell];
     uint32_t predicted;
@@ -736,7 +729,7 @@ __global__ __launch_bounds__(256) void enc_ac_tokens_kernel(EncImage im) {
     else predicted = ((uint32_t)nzp[cell - im.w8] + nzp[cell - 1] + 1) >> 1;
     // default block-context map by order bucket: one row for Y, one shared by X and B
     const uint8_t kCtxY[13] = {0, 1, 2, 2, 3, 3, 4, 5, 6, 6, 6, 6, 6}, kCtxXB[13] = {7, 8, 9, 9, 10, 11, 12, 13, 14, 14, 14, 14, 14};
-    const uint32_t block_ctx = c == 1 ? kCtxY[e_bucket[sc]] : kCtxXB[e_bucket[sc]];
+    const uint32_t block_ctx = c == 1 ? kCtxY[StrategyOrderBucket(sc)] : kCtxXB[StrategyOrderBucket(sc)];
     uint32_t nzc = predicted >= 64 ? 64 : predicted;
     nzc = nzc < 8 ? nzc : 4 + nzc / 2;
     DevToken t;

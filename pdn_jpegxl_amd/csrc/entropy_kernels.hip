@@ -20,14 +20,12 @@
 #include "kernels.h"
 #include "lds_layout.h"
 #include "modular_rules.h"
+#include "varblock_rules.h"
 
 namespace jxlhip {
 
 namespace {
 
-__device__ const uint8_t d_order_bucket[kNumStrategies] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-__device__ const uint8_t d_log2cx[kNumStrategies] = {0, 0, 0, 0, 1, 2, 0, 1, 0, 2, 1, 2, 0, 0, 0, 0, 0, 0, 3, 2, 3, 4, 3, 4, 5, 4, 5};
-__device__ const uint8_t d_log2cy[kNumStrategies] = {0, 0, 0, 0, 1, 2, 1, 0, 2, 0, 2, 1, 0, 0, 0, 0, 0, 0, 3, 3, 2, 4, 4, 3, 5, 5, 4};
 __device__ const uint8_t d_nnz_ctx[64] = {0,   0,   31,  62,  62,  93,  93,  93,  93,  123, 123, 123, 123, 152, 152, 152, 152, 152, 152, 152, 152, 180,
                                           180, 180, 180, 180, 180, 180, 180, 180, 180, 180, 180, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206,
                                           206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206, 206};
@@ -1270,12 +1268,12 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
     uint32_t sum = 0;
     for (uint32_t i = i0; i < i1; i++) {
       const int es = s_info[i], eq = 1 + s_info[count + i];
-      const bool ok = es >= 0 && es < kNumStrategies && eq >= 1 && eq <= 256;
+      const bool ok = StrategyValid(es) && eq >= 1 && eq <= 256;
       if (!ok) err |= kErrBlockLayout;
       // AFV0..AFV3: the strategy ids are only known here (the block-metadata stream is decoded on the GPU), so this is where the
       // frame is refused; the group keeps no varblock (s_count = 0 below), nothing downstream reconstructs it
-      if (es >= 14 && es <= 17) err |= kErrUnsupportedTransform | kErrBlockLayout;
-      sum += ok ? 1u << d_log2cx[es] : 1u;
+      if (StrategyIsAfv(es)) err |= kErrUnsupportedTransform | kErrBlockLayout;
+      sum += ok ? 1u << StrategyLog2Cx(es) : 1u;
     }
     s_part[tid] = sum;
     __syncthreads();
@@ -1289,7 +1287,7 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
     for (uint32_t i = i0; i < i1; i++) {
       const int es = s_info[i];
       s_pre[i] = base;
-      base += (es >= 0 && es < kNumStrategies) ? 1u << d_log2cx[es] : 1u;
+      base += StrategyValid(es) ? 1u << StrategyLog2Cx(es) : 1u;
     }
     if (err & kErrBlockLayout) atomicOr(&s_flag, 1u);
   }
@@ -1321,7 +1319,7 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
         if (j < count) { off = s_pre[j] - s_pre[num]; inrow = off < nfree; }
         if (inrow) {
           const int es = s_info[j];
-          const int lcx = d_log2cx[es], lcy = d_log2cy[es], cx = 1 << lcx, cy = 1 << lcy;
+          const int lcx = StrategyLog2Cx(es), lcy = StrategyLog2Cy(es), cx = 1 << lcx, cy = 1 << lcy;
           // rank-select: the word that holds free cell number `off`, then the position of that set bit
           int wi = 0;
           uint32_t before = 0;
@@ -1366,12 +1364,12 @@ __global__ __launch_bounds__(256) void lf_finish_kernel(const DevImage* __restri
   for (uint32_t i = tid; i < placed; i += 256) {
     const int x = s_pos[i] & 0xFF, y = s_pos[i] >> 8;
     const int s = s_info[i], q = 1 + s_info[count + i];
-    const int lcx = d_log2cx[s], lcy = d_log2cy[s], cx = 1 << lcx, cy = 1 << lcy;
+    const int lcx = StrategyLog2Cx(s), lcy = StrategyLog2Cy(s), cx = 1 << lcx, cy = 1 << lcy;
     const size_t cell = (size_t)(by0 + y) * im.w8 + bx0 + x;
     for (int iy = 0; iy < cy; iy++)
       for (int ix = 0; ix < cx; ix++) {
         const size_t cc = cell + (size_t)iy * im.w8 + ix;
-        im.cellinfo[cc] = (uint32_t)s | ix << 8 | iy << 13 | lcx << 18 | lcy << 21 | 1u << 31;
+        im.cellinfo[cc] = CellInfoPack(s, ix, iy, lcx, lcy);
         im.rawq[cc] = (uint16_t)q;
       }
   }
@@ -1401,13 +1399,13 @@ __global__ __launch_bounds__(64) void hf_blocklist_kernel(const DevImage* __rest
     uint32_t info = 0;
     if (bx < bw && by < bh) {
       info = im.cellinfo[(size_t)(by0 + by) * im.w8 + bx0 + bx];
-      first = (info & 0x8003FF00u) == 0x80000000u;
+      first = CellIsOrigin(info);
     }
     const uint64_t m = __ballot(first);
     if (first) {
       const uint32_t pos = total + (uint32_t)__popcll(m & (((uint64_t)1 << lane) - 1));
-      const uint32_t s = info & 0xFF, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
-      const uint32_t ord = d_order_bucket[s];
+      const uint32_t lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
+      const uint32_t ord = StrategyOrderBucket(CellStrategy(info));
       const uint32_t rq = im.rawq[(size_t)(by0 + by) * im.w8 + bx0 + bx];
       uint32_t qf_idx = 0;
       for (int i = 0; i < n_qf; i++) qf_idx += rq > im.qf_thr[i];
@@ -1422,7 +1420,7 @@ __global__ __launch_bounds__(64) void hf_blocklist_kernel(const DevImage* __rest
       }
       uint32_t ctxs = 0;
       for (int ci = 0; ci < 3; ci++) {
-        const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
+        const int c = ChannelOfTeam(ci);
         const uint32_t cprime = c < 2 ? (c ^ 1) : 2;
         ctxs |= ((uint32_t)im.block_ctx_map[((cprime * kNumOrders + ord) * (n_qf + 1) + qf_idx) * im.num_lf_ctx + lf_idx] & 31u) << (5 * ci);
       }
@@ -1593,7 +1591,7 @@ __device__ __forceinline__ void HfPeriod(const HfLane<kLds>& L, HfBits& b, HfQue
 }
 
 // ---- the format's rules, each stated once
-// channel of coding slot ci (Y, X, B)
+// channel of coding slot ci (Y, X, B): hf_decode_kernel's own copy of ChannelOfTeam (varblock_rules.h); the two agree
 __device__ __forceinline__ int HfChannel(int ci) { return ci == 0 ? 1 : (ci == 1 ? 0 : 2); }
 // a varblock starts: descriptor -> block state (the word hf_blocklist_kernel wrote)
 __device__ __forceinline__ void HfUnpackBlock(HfState& t, uint32_t d, uint32_t w8) {

@@ -2,6 +2,7 @@
 // reference reaches it via libjxl (Decoder/JxlDecoder.cpp:454 JxlDecoderProcessInput).
 #include "host_parse.h"
 #include "icc.h"
+#include "varblock_rules.h"
 #include "../../include/jxlfiletypeio.h"
 #include <algorithm>
 #include <array>
@@ -1064,8 +1065,16 @@ struct QEnc {
   BandParams dct, afv44;
 };
 
-const int kReqS[kNumQuantTables] = {1, 1, 1, 1, 2, 4, 1, 1, 2, 1, 1, 8, 4, 16, 8, 32, 16};   // short side in blocks
-const int kReqL[kNumQuantTables] = {1, 1, 1, 1, 2, 4, 2, 4, 4, 1, 1, 8, 8, 16, 16, 32, 32};  // long side
+// Log2 of the short and the long side, in cells, of the blocks that quant table q serves (every strategy of a table has the same two).
+static void QuantTableSides(int q, int* log2_short, int* log2_long) {
+  for (int s = 0; s < kNumStrategies; s++) {
+    if ((int)StrategyQuantTable(s) != q) continue;
+    *log2_short = std::min(StrategyLog2Cx(s), StrategyLog2Cy(s));
+    *log2_long = std::max(StrategyLog2Cx(s), StrategyLog2Cy(s));
+    return;
+  }
+  Fail("no strategy uses this quant table");
+}
 
 QEnc Library(int q) {
   QEnc e;
@@ -1149,7 +1158,9 @@ QEnc Library(int q) {
 }
 
 void WeightsFor(int q, const QEnc& e, std::vector<float>& table) {
-  int rows = 8 * kReqS[q], cols = 8 * kReqL[q];
+  int ls, ll;
+  QuantTableSides(q, &ls, &ll);
+  int rows = 8 << ls, cols = 8 << ll;
   size_t n = (size_t)rows * cols;
   std::vector<float> w(3 * n, 0.f);
   if (e.mode != 6) REQUIRE(n == 64, "8x8-only quant encoding used for a larger table");
@@ -1275,7 +1286,7 @@ void ReadHfGlobal(Bits& r, ParsedFrame& f, std::vector<float> custom_dq[kNumQuan
         if (!(used >> o & 1)) continue;
         const std::vector<uint16_t>& nat = st.natural_order[o];
         int s = kBucketStrategy[o];
-        size_t llf = (size_t)kCoveredX[s] * kCoveredY[s];
+        size_t llf = (size_t)1 << (StrategyLog2Cx(s) + StrategyLog2Cy(s));
         for (int ch = 0; ch < 3; ch++) {
           std::vector<uint32_t> perm;
           ReadPermutation(sr, llf, nat.size(), perm);
@@ -1544,11 +1555,6 @@ bool ReadBackTree(const uint8_t* bytes, size_t nbytes, std::vector<DevTreeNode>*
   }
 }
 
-const uint8_t kCoveredX[kNumStrategies] = {1, 1, 1, 1, 2, 4, 1, 2, 1, 4, 2, 4, 1, 1, 1, 1, 1, 1, 8, 4, 8, 16, 8, 16, 32, 16, 32};
-const uint8_t kCoveredY[kNumStrategies] = {1, 1, 1, 1, 2, 4, 2, 1, 4, 1, 4, 2, 1, 1, 1, 1, 1, 1, 8, 8, 4, 16, 16, 8, 32, 32, 16};
-const uint8_t kStrategyOrderBucket[kNumStrategies] = {0, 1, 1, 1, 2, 3, 4, 4, 5, 5, 6, 6, 1, 1, 1, 1, 1, 1, 7, 8, 8, 9, 10, 10, 11, 12, 12};
-const uint8_t kStrategyQuantTable[kNumStrategies] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-
 const StaticTables& GetStaticTables() {
   static StaticTables t;
   static std::once_flag once;
@@ -1557,7 +1563,7 @@ const StaticTables& GetStaticTables() {
     // restricted to every (long/short)-th row
     for (int o = 0; o < kNumOrders; o++) {
       int s = kBucketStrategy[o];
-      size_t L = std::max(kCoveredX[s], kCoveredY[s]), S = std::min(kCoveredX[s], kCoveredY[s]);
+      size_t L = (size_t)1 << std::max(StrategyLog2Cx(s), StrategyLog2Cy(s)), S = (size_t)1 << std::min(StrategyLog2Cx(s), StrategyLog2Cy(s));
       size_t ratio = L / S, rshift = CeilLog2(ratio), N = L * 8;
       std::vector<uint16_t>& ord = t.natural_order[o];
       ord.assign(L * S * 64, 0);

@@ -238,9 +238,4 @@ struct StaticTables {
 };
 const StaticTables& GetStaticTables();
 
-extern const uint8_t kCoveredX[kNumStrategies];
-extern const uint8_t kCoveredY[kNumStrategies];
-extern const uint8_t kStrategyOrderBucket[kNumStrategies];
-extern const uint8_t kStrategyQuantTable[kNumStrategies];
-
 }  // namespace jxlhip

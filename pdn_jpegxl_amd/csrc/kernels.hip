@@ -8,11 +8,9 @@
 #include <algorithm>
 #include "dev_types.h"
 #include "kernels.h"
+#include "varblock_rules.h"
 
 namespace jxlhip {
-
-__constant__ uint8_t c_quant_table[kNumStrategies] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-__device__ __forceinline__ bool IsSpecial(uint32_t s) { return (s >= 1 && s <= 3) || (s >= 12 && s <= 17); }
 
 // ------------------------------------------------------------------ LF pixel stages
 __global__ void lf_dequant_kernel(const DevImage* __restrict__ imgs) {
@@ -113,11 +111,11 @@ __global__ void expand_scatter_kernel(const DevImage* __restrict__ imgs, int all
       const int bx = tx * 8 + (cell & 7), by = ty * 8 + (cell >> 3);
       if (bx >= im.w8 || by >= im.h8) continue;
       const uint32_t info = im.cellinfo[(size_t)by * im.w8 + bx];
-      if (!(info >> 31) || (info & 0x3FF00u)) continue;   // not the origin cell of a varblock
-      const uint32_t s = info & 0xFF, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
-      const uint32_t q = c_quant_table[s], nq = im.dq_n[q];
-      const uint32_t lng = 3 + max(lcx, lcy);
-      const bool transposed = !IsSpecial(s) && lcy >= lcx;
+      if (!CellIsOrigin(info)) continue;
+      const uint32_t s = CellStrategy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
+      const uint32_t q = StrategyQuantTable(s), nq = im.dq_n[q];
+      const uint32_t lng = StoredLog2Pitch(lcx, lcy);
+      const bool transposed = StoredTransposed(StrategyIsSpecial(s), lcx, lcy);
       int32_t* plane = im.coef[c] + (size_t)by * 8 * im.wp + (size_t)bx * 8;
       // every pass of a progressive frame adds its share (value << shift); each has its own lists, orders and scan lists
       for (const DevImage* ps = &im; ps; ps = ps->next_pass) {
@@ -131,8 +129,8 @@ __global__ void expand_scatter_kernel(const DevImage* __restrict__ imgs, int all
           const uint32_t ent = entries[blk.x + i], k = ent & 0xFFFFu;
           if (k >= nq) continue;
           const uint32_t p = scan[k].x;
-          const uint32_t r = p >> lng, cc = p & ((1u << lng) - 1);
-          const uint32_t ky = transposed ? cc : r, kx = transposed ? r : cc;
+          uint32_t ky, kx;
+          StoredToKyKx(p, lng, transposed, &ky, &kx);
           if (ky < (8u << lcy) && kx < (8u << lcx)) {
             const int32_t v = ((int32_t)ent >> 16) * (1 << shift);
             if (accumulate) atomicAdd(&plane[(size_t)ky * im.wp + kx], v);   // lanes of different passes may meet at one position
@@ -155,14 +153,11 @@ __global__ void dequant_kernel(const DevImage* __restrict__ imgs) {
       const int bx = x >> 3, by = y >> 3;
       const size_t cell = (size_t)by * im.w8 + bx;
       const uint32_t info = im.cellinfo[cell];
-      const uint32_t s = info & 0xFF, ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
+      const uint32_t s = CellStrategy(info), ix = CellIx(info), iy = CellIy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
       const int kx = (x & 7) + 8 * ix, ky = (y & 7) + 8 * iy;
       const int obx = bx - (int)ix, oby = by - (int)iy;   // varblock origin cell
-      const bool special = IsSpecial(s);
-      const uint32_t lng_log2 = 3 + max(lcx, lcy);
-      const bool transposed = !special && lcy >= lcx;
-      const uint32_t idx = transposed ? ((uint32_t)kx << lng_log2) + ky : ((uint32_t)ky << lng_log2) + kx;
-      const uint32_t q = c_quant_table[s];
+      const uint32_t idx = StoredIndex((uint32_t)ky, (uint32_t)kx, StoredLog2Pitch(lcx, lcy), StoredTransposed(StrategyIsSpecial(s), lcx, lcy));
+      const uint32_t q = StrategyQuantTable(s);
       const float* wt = im.dq[q];
       const uint32_t nq = im.dq_n[q];
       const size_t ocell = (size_t)oby * im.w8 + obx;
@@ -173,13 +168,8 @@ __global__ void dequant_kernel(const DevImage* __restrict__ imgs) {
       float out[3];
 #pragma unroll
       for (int ci = 0; ci < 3; ci++) {
-        const int c = ci == 0 ? 1 : (ci == 1 ? 0 : 2);
-        const int32_t v = im.coef[c][i];
-        float a;
-        if (v == 0) a = 0.f;
-        else if (v == 1) a = im.qbias[c];
-        else if (v == -1) a = -im.qbias[c];
-        else a = (float)v - im.qbias[3] / (float)v;
+        const int c = ChannelOfTeam(ci);
+        const float a = DequantBias(im.coef[c][i], im.qbias[c], im.qbias[3], ExactQuotient());
         const float dqs = c == 0 ? scale * im.x_dm : (c == 1 ? scale : scale * im.b_dm);
         float d = a * dqs * wt[(size_t)c * nq + idx];
         if (c == 0) d += cfx * out[1];
@@ -202,12 +192,11 @@ __global__ void llf_kernel(const DevImage* __restrict__ imgs, const float* basis
       const int bx = tx * 8 + (e & 7), by = ty * 8 + (e >> 3);
       if (bx >= im.w8 || by >= im.h8) continue;
       const uint32_t info = im.cellinfo[(size_t)by * im.w8 + bx];
-      const uint32_t ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
+      const uint32_t ix = CellIx(info), iy = CellIy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
       const int cx = 1 << lcx, cy = 1 << lcy;
       const int obx = bx - (int)ix, oby = by - (int)iy;
-      // basis_small holds, for c = 1,2,4,...,32 at offset (c*c-1)/3, the c x c scaled DCT basis B[k*c+n]
-      const float* Bx = basis_small + (cx * cx - 1) / 3;
-      const float* By = basis_small + (cy * cy - 1) / 3;
+      const float* Bx = basis_small + BasisSmallOffset(cx);   // the c x c scaled DCT basis B[k * c + n]
+      const float* By = basis_small + BasisSmallOffset(cy);
       const float sc = llf_scale[lcy * 32 + iy] * llf_scale[lcx * 32 + ix] / (float)(cx * cy);
       const size_t dst = (size_t)(oby * 8 + (int)iy) * im.wp + obx * 8 + (int)ix;
       for (int c = 0; c < 3; c++) {
@@ -230,8 +219,8 @@ __global__ void llf_kernel(const DevImage* __restrict__ imgs, const float* basis
 // kernel's full-tile stores stay inside the planes.)
 __device__ __forceinline__ bool GemmTile(const DevImage& im, int tx, int ty) {
   const uint32_t info = im.cellinfo[(size_t)ty * 8 * im.w8 + tx * 8];
-  const uint32_t ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
-  return (info & 0xFF) >= 18 && (info & 0xFF) <= 26 && ix + 8 <= (1u << lcx) && iy + 8 <= (1u << lcy);
+  const uint32_t s = CellStrategy(info), ix = CellIx(info), iy = CellIy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
+  return s >= 18 && s <= 26 && ix + 8 <= (1u << lcx) && iy + 8 <= (1u << lcy);
 }
 
 // Both 1-D IDCT passes of such a tile as 64 x R x 64 matrix products on the matrix cores (v_mfma_f32_16x16x4_f32: exact f32
@@ -249,10 +238,10 @@ __global__ __launch_bounds__(256) void idct_gemm_kernel(const DevImage* __restri
     const int tx = tile % im.wt, ty = tile / im.wt;
     if (!GemmTile(im, tx, ty)) continue;
     const uint32_t info = im.cellinfo[(size_t)ty * 8 * im.w8 + tx * 8];
-    const int ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
+    const int ix = CellIx(info), iy = CellIy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
     const int K = pass == 0 ? 8 << lcy : 8 << lcx;           // length of the transform along the contracted dimension
     const int off = pass == 0 ? iy * 8 : ix * 8;              // the tile's first output row / column inside the varblock
-    const float* B = basis_all + ((size_t)K * K - 64) / 3;   // B[k * K + n]
+    const float* B = basis_all + BasisAllOffset(K);   // B[k * K + n]
     const size_t y0 = (size_t)ty * 64, x0 = (size_t)tx * 64;
     for (int c = 0; c < 3; c++) {
       const float* in = pass == 0 ? (const float*)im.coef[c] : im.tmp[c];
@@ -308,12 +297,10 @@ __global__ void idct_v_kernel(const DevImage* __restrict__ imgs, const float* ba
       const int x = tx * 64 + (e & 63), by = ty * 8 + (e >> 6);
       if (x >= im.wp || by >= im.h8) continue;
       const uint32_t info = im.cellinfo[(size_t)by * im.w8 + (x >> 3)];
-      const uint32_t s = info & 0xFF;
-      if (IsSpecial(s)) continue;
-      const uint32_t iy = (info >> 13) & 31, lcy = (info >> 21) & 7;
+      if (StrategyIsSpecial(CellStrategy(info))) continue;
+      const uint32_t iy = CellIy(info), lcy = CellLog2Cy(info);
       const int R = 8 << lcy;
-      // basis_all holds, for N = 8,...,256 at offset (N*N-64)/3, the scaled basis B[k*N+n]
-      const float* B = basis_all + ((size_t)R * R - 64) / 3 + iy * 8;
+      const float* B = basis_all + BasisAllOffset(R) + iy * 8;   // the scaled basis B[k * N + n]
       const size_t src = (size_t)(by - (int)iy) * 8 * im.wp + x;
       const size_t dst = (size_t)by * 8 * im.wp + x;
       for (int c = 0; c < 3; c++) {
@@ -343,11 +330,10 @@ __global__ void idct_h_kernel(const DevImage* __restrict__ imgs, const float* ba
       const int bx = tx * 8 + (e >> 6), y = ty * 64 + (e & 63);
       if (bx >= im.w8 || y >= im.hp) continue;
       const uint32_t info = im.cellinfo[(size_t)(y >> 3) * im.w8 + bx];
-      const uint32_t s = info & 0xFF;
-      if (IsSpecial(s)) continue;
-      const uint32_t ix = (info >> 8) & 31, lcx = (info >> 18) & 7;
+      if (StrategyIsSpecial(CellStrategy(info))) continue;
+      const uint32_t ix = CellIx(info), lcx = CellLog2Cx(info);
       const int C = 8 << lcx;
-      const float* B = basis_all + ((size_t)C * C - 64) / 3 + ix * 8;
+      const float* B = basis_all + BasisAllOffset(C) + ix * 8;
       const size_t src = (size_t)y * im.wp + (size_t)(bx - (int)ix) * 8;
       const size_t dst = (size_t)y * im.wp + (size_t)bx * 8;
       for (int c = 0; c < 3; c++) {
@@ -380,14 +366,14 @@ __device__ __forceinline__ void Idct1(const float* B, int n, const float* in, in
 __global__ void idct_special_kernel(const DevImage* __restrict__ imgs, const float* basis_all, const float* basis_small) {
   const DevImage& im = imgs[blockIdx.y];
   const float* B8 = basis_all;                 // N = 8
-  const float* B4 = basis_small + (16 - 1) / 3;  // c = 4
+  const float* B4 = basis_small + BasisSmallOffset(4);
   FOR_LISTED_TILES(im, tile)
   for (int e = threadIdx.x; e < 192; e += blockDim.x) {
     const int c = e / 64;
     const int bx = (tile % im.wt) * 8 + (e & 7), by = (tile / im.wt) * 8 + ((e >> 3) & 7);
     if (bx >= im.w8 || by >= im.h8) continue;
-    const uint32_t s = im.cellinfo[(size_t)by * im.w8 + bx] & 0xFF;
-    if (!IsSpecial(s)) continue;
+    const uint32_t s = CellStrategy(im.cellinfo[(size_t)by * im.w8 + bx]);
+    if (!StrategyIsSpecial(s)) continue;
     const size_t base = (size_t)by * 8 * im.wp + (size_t)bx * 8;
     const float* src = (const float*)im.coef[c] + base;
     float* dst = im.xyb[c] + base;

@@ -1,7 +1,7 @@
-// Dynamic LDS of the four serial entropy kernels (entropy_kernels.hip), written once for both sides: the kernels carve their
-// `extern __shared__` block through these descriptions, and the host (entropy_plan.cc, the Launch* wrappers) asks the same
-// descriptions how many bytes a launch needs.  A layout is a plain struct of byte offsets computed from the numbers that determine it;
-// `end` / `tables` is the first byte behind it.  Nothing here touches memory.
+// Dynamic LDS of the four serial entropy kernels (entropy_kernels.hip) and of recon_tile_kernel (tile_kernels.hip), written once for
+// both sides: the kernels carve their `extern __shared__` block through these descriptions, and the host (entropy_plan.cc, the
+// Launch* wrappers) asks the same descriptions how many bytes a launch needs.  A layout is a plain struct of byte offsets computed
+// from the numbers that determine it; `end` / `tables` is the first byte behind it.  Nothing here touches memory.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -120,5 +120,34 @@ JXL_LAYOUT size_t HfTablesEnd(size_t off, const CodeShape& s) { return CodeLds(o
 JXL_LAYOUT size_t HfTablesBytes(const CodeShape& s) { return CodeLdsBytes(s) + kNnzCtxBytes + kHfTailAllowance; }
 // what the lane-stride heuristic takes for a workgroup's LDS: the tables (without the tail allowance) and four lanes
 JXL_LAYOUT size_t HfEstimateBytes(const CodeShape& s) { return CodeLdsBytes(s) + kNnzCtxBytes + HfLaneBytes(kHfEstimateLanes); }
+
+// ---- recon_tile_kernel (tile_kernels.hip): three coefficient tiles | the 8- and 16-point bases | per-cell tables | matrix-core tables
+// The same for every launch.  csc holds pointers (8-byte aligned), the three basis tables are read in 16-byte pieces.
+constexpr int kReconTileSide = 64;    // a tile is 64 x 64 samples, 8 x 8 cells
+constexpr int kReconTilePitch = 65;   // floats per tile row in LDS (conflict-free column walks)
+constexpr int kReconTileFloats = kReconTileSide * kReconTilePitch;
+struct ReconTileLds {
+  size_t cfc3;     // 3 tiles of f32: coefficients -> columns done -> pixels; team order Y, X, B
+  size_t B816;     // 320 f32: IDCT bases of the two common sizes (N = 8 at 0, N = 16 at 64)
+  size_t cscale;   // 64 f32, per cell: inv_global_scale / raw quant of its varblock
+  size_t ci;       // 64 u32: cell info
+  size_t cmeta;    // 64 u32: log2 of the stored pitch | transposed << 4
+  size_t cnq;      // 64 u32: entries per channel of the cell's dequantisation table
+  size_t cpre;     // 3 x 64 u32: exclusive prefix of the entry counts per team ...
+  size_t cstart;   // 3 x 64 u32: ... and where each origin cell's entries start in the group's list
+  size_t ctot;     // 4 u32: totals per team; [3]: the tile holds a 64-point varblock
+  size_t csc;      // 64 pointers: scan list of the cell's quant table
+  size_t t32_lo;   // 128 float4: k-contiguous 32-point basis, first / second four k-steps of lane (n, q) = [n * 4 + q]
+  size_t t32_hi;   // 128 float4
+  size_t t64;      // 4 x 256 float4: the 64-point basis, quarter j of lane (n, q) = [j * 256 + n * 4 + q]
+  size_t end;
+  JXL_LAYOUT constexpr ReconTileLds()
+      : cfc3(0), B816(cfc3 + 3 * (size_t)kReconTileFloats * 4), cscale(B816 + 320 * 4), ci(cscale + 64 * 4), cmeta(ci + 64 * 4), cnq(cmeta + 64 * 4),
+        cpre(cnq + 64 * 4), cstart(cpre + 3 * 64 * 4), ctot(cstart + 3 * 64 * 4), csc(ctot + 4 * 4), t32_lo(csc + 64 * 8), t32_hi(t32_lo + 128 * 16),
+        t64(t32_hi + 128 * 16), end(t64 + 4 * 256 * 16) {}
+};
+static_assert(ReconTileLds().csc % 8 == 0 && ReconTileLds().t32_lo % 16 == 0 && ReconTileLds().t32_hi % 16 == 0 && ReconTileLds().t64 % 16 == 0,
+              "the pointers and the 16-byte pieces are aligned");
+static_assert(ReconTileLds().end == 74768, "three tiles, the small bases, the per-cell tables and 20 KB of matrix-core tables");
 
 }  // namespace jxlhip

@@ -19,6 +19,7 @@
 #include "host_write.h"
 #include "icc.h"
 #include "modular_rules.h"
+#include "varblock_rules.h"
 
 namespace jxlhip {
 std::vector<EncTreeNode> MakeEncoderTree(uint32_t nlf);
@@ -660,6 +661,55 @@ extern "C" JXLFILETYPEIO_API size_t jxlhip_selftest_batch_layout(int32_t n, cons
   if (v.size() > capacity) return 0;
   memcpy(out, v.data(), v.size() * sizeof(int64_t));
   return v.size();
+}
+
+// ---- the varblock rules (csrc/varblock_rules.h) and recon_tile_kernel's LDS layout, as the kernels and the host call them;
+// tests/test_varblock_rules.py holds each against a statement written out in Python.
+// Per strategy id, six numbers: valid, log2 cx, log2 cy, order bucket, quant table, special | afv << 1 (ids outside the tables: valid alone).
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_varblock_strategy(int32_t s, int32_t* out) {
+  for (int k = 0; k < 6; k++) out[k] = 0;
+  out[0] = StrategyValid(s) ? 1 : 0;
+  if (!out[0]) return;
+  out[1] = StrategyLog2Cx(s); out[2] = StrategyLog2Cy(s); out[3] = (int32_t)StrategyOrderBucket(s); out[4] = (int32_t)StrategyQuantTable(s);
+  out[5] = (StrategyIsSpecial(s) ? 1 : 0) | (StrategyIsAfv(s) ? 2 : 0);
+}
+extern "C" JXLFILETYPEIO_API uint32_t jxlhip_selftest_varblock_cell_pack(uint32_t s, uint32_t ix, uint32_t iy, uint32_t lcx, uint32_t lcy) {
+  return CellInfoPack(s, ix, iy, lcx, lcy);
+}
+// strategy, ix, iy, log2 cx, log2 cy, valid, origin
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_varblock_cell_unpack(uint32_t info, uint32_t* out) {
+  out[0] = CellStrategy(info); out[1] = CellIx(info); out[2] = CellIy(info); out[3] = CellLog2Cx(info); out[4] = CellLog2Cy(info);
+  out[5] = CellValid(info) ? 1 : 0; out[6] = CellIsOrigin(info) ? 1 : 0;
+}
+// The stored layout of a block of 8 << lcy rows and 8 << lcx columns, row-major over (ky, kx): StoredIndex, what StoredToKyKx makes of
+// that index (ky << 16 | kx) and IsLlfPosition.  meta: log2 of the pitch, transposed.
+extern "C" JXLFILETYPEIO_API void jxlhip_selftest_varblock_stored(int32_t special, uint32_t lcx, uint32_t lcy, uint32_t* meta, uint32_t* index,
+                                                                  uint32_t* back, uint8_t* llf) {
+  const uint32_t lng = StoredLog2Pitch(lcx, lcy);
+  const bool transposed = StoredTransposed(special != 0, lcx, lcy);
+  meta[0] = lng; meta[1] = transposed ? 1 : 0;
+  const uint32_t R = 8u << lcy, C = 8u << lcx;
+  for (uint32_t ky = 0; ky < R; ky++)
+    for (uint32_t kx = 0; kx < C; kx++) {
+      const uint32_t p = StoredIndex(ky, kx, lng, transposed);
+      uint32_t by, bx;
+      StoredToKyKx(p, lng, transposed, &by, &bx);
+      index[ky * C + kx] = p; back[ky * C + kx] = by << 16 | bx; llf[ky * C + kx] = IsLlfPosition(ky, kx, lcx, lcy) ? 1 : 0;
+    }
+}
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_varblock_basis_offset(int32_t small, int32_t n) { return small ? BasisSmallOffset(n) : BasisAllOffset(n); }
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_varblock_channel_of_team(int32_t i) { return ChannelOfTeam(i); }
+// form 0: the quotient by division; 1: through a reciprocal (1.0f / f on the host)
+extern "C" JXLFILETYPEIO_API float jxlhip_selftest_varblock_dequant_bias(int32_t v, float qb, float qb3, int32_t form) {
+  if (form == 0) return DequantBias(v, qb, qb3, ExactQuotient());
+  return DequantBias(v, qb, qb3, [](float a, float f) { return a * (1.0f / f); });
+}
+// recon_tile_kernel's LDS (lds_layout.h): the offsets in layout order, then `end`; returns how many numbers
+extern "C" JXLFILETYPEIO_API int32_t jxlhip_selftest_varblock_recon_lds(int64_t* out) {
+  const ReconTileLds l;
+  const size_t v[14] = {l.cfc3, l.B816, l.cscale, l.ci, l.cmeta, l.cnq, l.cpre, l.cstart, l.ctot, l.csc, l.t32_lo, l.t32_hi, l.t64, l.end};
+  for (int k = 0; k < 14; k++) out[k] = (int64_t)v[k];
+  return 14;
 }
 
 // ---- the Modular sample rules (csrc/modular_rules.h), as the kernels and the host encoder call them; tests/test_modular_rules.py

@@ -22,6 +22,8 @@
 #include "dev_types.h"
 #include "dev_util.h"
 #include "kernels.h"
+#include "lds_layout.h"
+#include "varblock_rules.h"
 
 namespace jxlhip {
 
@@ -38,12 +40,9 @@ namespace jxlhip {
 
 namespace {
 
-constexpr int kTS = 64;       // tile side
-constexpr int kLP = 65;       // LDS pitch (conflict-free column walks)
+constexpr int kTS = kReconTileSide;    // tile side
+constexpr int kLP = kReconTilePitch;   // LDS pitch (conflict-free column walks)
 
-__device__ const uint8_t t_quant_table[kNumStrategies] = {0, 1, 2, 3, 4, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 10, 10, 11, 12, 12, 13, 14, 14, 15, 16, 16};
-
-__device__ __forceinline__ bool Special(uint32_t s) { return (s >= 1 && s <= 3) || (s >= 12 && s <= 17); }
 typedef float __attribute__((ext_vector_type(4))) F4;
 // a 16x16 sub-block (2x2 cells at even cell coordinates) goes to the matrix cores, per pass, when the varblocks of its cells are at
 // least 16 points long in the pass's direction, of one length and at one offset (MfmaRows / MfmaCols below)
@@ -100,10 +99,12 @@ __device__ __forceinline__ F4 MfmaChain64L(const float4* t64, int pair, const fl
 // need not be the same varblock (16x8 blocks side by side, a 32x16 beside a 32x32 ...).  With the one-varblock test alone, every
 // rectangular block of 8 points in the other direction fell back to the vector-ALU loops (a fifth of this content's cells).
 __device__ __forceinline__ bool MfmaRows(uint32_t tl, uint32_t tr) {   // vertical pass: rows >= 16, same length and row offset
-  return (tl >> 31) && (tr >> 31) && ((tl >> 21) & 7) >= 1 && ((tl >> 21) & 7) == ((tr >> 21) & 7) && ((tl >> 13) & 31) == ((tr >> 13) & 31);
+  const uint32_t ll = CellLog2Cy(tl), lr = CellLog2Cy(tr), ol = CellIy(tl), orr = CellIy(tr);
+  return CellValid(tl) && CellValid(tr) && ll >= 1 && ll == lr && ol == orr;
 }
 __device__ __forceinline__ bool MfmaCols(uint32_t tl, uint32_t bl) {   // horizontal pass: columns >= 16, same length and column offset
-  return (tl >> 31) && (bl >> 31) && ((tl >> 18) & 7) >= 1 && ((tl >> 18) & 7) == ((bl >> 18) & 7) && ((tl >> 8) & 31) == ((bl >> 8) & 31);
+  const uint32_t lt = CellLog2Cx(tl), lb = CellLog2Cx(bl), ot = CellIx(tl), ob = CellIx(bl);
+  return CellValid(tl) && CellValid(bl) && lt >= 1 && lt == lb && ot == ob;
 }
 
 // v^(1/2.4) through the hardware log2 / exp2 (v_log_f32, v_exp_f32: about 1 ulp each, i.e. < 1e-3 of an 8-bit step after the
@@ -282,38 +283,337 @@ __device__ __forceinline__ void WritePixel(const DevImage& im, int x, int y, flo
     a1[4] += v1 * b1.x; a1[5] += v1 * b1.y; a1[6] += v1 * b1.z; a1[7] += v1 * b1.w;                \
   }
 
-// One workgroup per (64x64 tile, channel): dequantisation (+ chroma from luma), LF -> LLF, both IDCT passes in LDS.  Tiles that hold
-// part of a varblock larger than the tile, or a special 8x8 transform, are appended to a per-image list for the generic kernels.
-// The phases are organised around what the profile of the first version showed (two thirds of the wave time parked at its ten
-// barriers / on memory; that version took 118 ms per batch of 384 frames, this one 55):
-//   * one 64x65 tile: both IDCT passes run IN PLACE.  The vertical pass gives wavefront w the column stripe [16w, 16w+16)
-//     (everything a stripe's outputs depend on lies in the same columns), the horizontal pass gives it the row band
-//     [16w, 16w+16); a wavefront fetches all its operands before it stores, so no workgroup barrier is needed inside a
-//     pass, and the copy-out of a row band needs only that wavefront.  LDS 19 KB -> 6 workgroups per CU (VGPR-bound).
-//   * LLF is computed by wavefront 0 with lane shuffles (no LDS staging, no barriers) while the others dequantise; the
-//     dequantisation skips the LLF positions instead of being overwritten after a barrier.
-//   * dequantisation: one thread = four consecutive coefficients of a row (one 16-byte load per plane and per weight
-//     table), per-cell constants (table pointer with the block offset folded in, scale, index shift) prepared once.
-//   * 1 / v through v_rcp_f32 (1 ulp; the term is a bias correction <= 0.15 / |v|).
-__device__ __forceinline__ float DequantBias(int32_t v, float qb, float qb3) {
-  if (v == 0) return 0.f;
-  if (v == 1) return qb;
-  if (v == -1) return -qb;
-  const float f = (float)v;
-  return f - qb3 * __builtin_amdgcn_rcpf(f);
-}
-typedef int __attribute__((ext_vector_type(4))) I4v;
+constexpr int kTileF = kReconTileFloats;   // floats of one channel's tile
 
-// The scatter: every entry of the tile's (block, channel) lists is one non-zero quantised coefficient; its scan position k selects
-// {stored index, weight} from the per-table scan list, the stored index gives the coefficient's place in the varblock.  The lists of
-// the three channels are walked as ONE range [0, T_y + T_x + T_b) by all 768 threads (a 4K frame has about 270 luma and 30 + 30
-// chroma entries per tile: one trip).  An entry's cell comes from a binary search over the exclusive prefix of its channel's
-// per-cell entry counts (only origin cells have entries).  A luma entry is also what chroma from luma adds to X and B - the IDCT is
-// linear and the tile is inside one 64x64 chroma-from-luma tile - so it is added three times (dequantised once) instead of the X
-// and B workgroups of the previous version walking and dequantising the luma list again.  Adds into the zeroed tiles with
-// ds_add_f32: a position receives at most one own addend and one luma addend, two addends commute, so the sums do not depend on
-// the order the lanes arrive in.
-constexpr int kTileF = kTS * kLP;   // floats of one channel's tile
+// The workgroup's LDS, carved as ReconTileLds (lds_layout.h) describes it; the fields are named and explained there.  Every phase makes
+// its own view (the addresses are constants).
+extern __shared__ __align__(16) uint8_t recon_lds[];
+// Who a thread is among the workgroup's 12 wavefronts: team = wave / 4 owns channel Y, X, B, tw is the wavefront's place in its team.
+// (Every phase derives it from threadIdx itself, so that the compiler sees the ranges there.)
+struct ReconLane {
+  int tid, lane, team, tw;
+  __device__ __forceinline__ ReconLane() : tid(threadIdx.x), lane(tid & 63), team(tid >> 8), tw((tid >> 6) & 3) {}
+};
+struct ReconTile {
+  float *cfc3, *B816, *cscale;
+  uint32_t *ci, *cmeta, *cnq, *cpre, *cstart, *ctot;
+  const U32x2** csc;
+  float4 *t32_lo, *t32_hi, *t64;
+  __device__ __forceinline__ ReconTile() {
+    constexpr ReconTileLds L;
+    uint8_t* const smem = recon_lds;
+    cfc3 = (float*)(smem + L.cfc3); B816 = (float*)(smem + L.B816); cscale = (float*)(smem + L.cscale);
+    ci = (uint32_t*)(smem + L.ci); cmeta = (uint32_t*)(smem + L.cmeta); cnq = (uint32_t*)(smem + L.cnq);
+    cpre = (uint32_t*)(smem + L.cpre); cstart = (uint32_t*)(smem + L.cstart); ctot = (uint32_t*)(smem + L.ctot);
+    csc = (const U32x2**)(smem + L.csc);
+    t32_lo = (float4*)(smem + L.t32_lo); t32_hi = (float4*)(smem + L.t32_hi); t64 = (float4*)(smem + L.t64);
+  }
+};
+
+// Per-cell set-up, by wavefront 0 (lane = cell of the tile): owns ci, cscale, cmeta, cnq, csc, the entry-list prefixes cpre / cstart of
+// the three teams and ctot.  Returns whether this lane's cell makes the tile one for the generic kernels.
+__device__ __forceinline__ int ReconCellSetup(const DevImage& im, int tx, int ty) {
+  const ReconTile T;
+  const int tid = threadIdx.x;
+  int bad = 0;
+  const int cx = tx * 8 + (tid & 7), cy = ty * 8 + (tid >> 3);
+  const bool inside = cx < im.w8 && cy < im.h8;
+  const size_t cell_g = (size_t)min(cy, im.h8 - 1) * im.w8 + min(cx, im.w8 - 1);
+  const size_t ncells = (size_t)im.w8 * im.h8;
+  const uint32_t info_g = im.cellinfo[cell_g];
+  const uint32_t rq_g = im.rawq[cell_g];
+  U32x2 blk[3];
+  blk[0] = im.cblk[ncells + cell_g]; blk[1] = im.cblk[cell_g]; blk[2] = im.cblk[2 * ncells + cell_g];   // team order: Y, X, B
+  const uint32_t info = inside ? info_g : 0u;
+  const uint32_t rqv = inside ? rq_g : 1u;
+  const int ix = CellIx(info), iy = CellIy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
+  if (inside) {
+    if (!CellValid(info)) bad = 1;
+    else {
+      const int ox = (tid & 7) - ix, oy = (tid >> 3) - iy;
+      // blocks larger than the tile, the rare special 8x8 transforms, and blocks that do not start on a multiple of their own size
+      // (every encoder aligns them, the format's placement rule does not; the matrix-core sub-blocks below rely on it) are left
+      // to the generic kernels
+      bad = ox < 0 || oy < 0 || ox + (1 << lcx) > 8 || oy + (1 << lcy) > 8 || StrategyIsSpecial(CellStrategy(info)) ||
+            (ox & ((1 << lcx) - 1)) != 0 || (oy & ((1 << lcy) - 1)) != 0;
+    }
+  }
+  const bool valid = CellValid(info) && !bad;
+  const int has64 = valid && (lcx == 3 || lcy == 3);
+  {  // (wavefront 0 is the only writer of the per-cell tables; the flag travels with them through the barrier behind the set-up)
+    const uint64_t any = __ballot(has64);
+    if (tid == 0) T.ctot[3] = any != 0;
+  }
+  const uint32_t q = StrategyQuantTable(valid ? CellStrategy(info) : 0);
+  const uint32_t rq_origin = (uint32_t)__shfl((int)rqv, valid ? tid - iy * 8 - ix : tid);
+  T.ci[tid] = info;
+  T.cscale[tid] = im.inv_global_scale / (float)rq_origin;
+  T.cmeta[tid] = StoredLog2Pitch(lcx, lcy) | (StoredTransposed(false, lcx, lcy) ? 16u : 0u);   // (no special transform gets this far)
+  T.cnq[tid] = im.dq_n[q];
+  T.csc[tid] = im.scan[q];
+  // entry lists of the varblocks that start in this tile; a list a failed section left unwritten is treated as empty
+  const bool origin = valid && ix == 0 && iy == 0;
+  uint32_t cnt[3], sum[3];
+#pragma unroll
+  for (int t = 0; t < 3; t++) {
+    cnt[t] = origin ? blk[t].y : 0u;
+    if (cnt[t] > 65536u || blk[t].x > kGroupEntriesCap - cnt[t]) cnt[t] = 0;
+    sum[t] = cnt[t];   // inclusive scans over the wavefront
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+      const uint32_t a = (uint32_t)__shfl_up((int)sum[t], d);
+      if (tid >= d) sum[t] += a;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 3; t++) {
+    T.cpre[t * 64 + tid] = sum[t] - cnt[t];
+    T.cstart[t * 64 + tid] = blk[t].x;
+    if (tid == 63) T.ctot[t] = sum[t];
+  }
+  return bad;
+}
+
+// LLF, by the first wavefront of each team (lane = cell): the lowest cx * cy coefficients of every varblock are the scaled 2-D DCT of
+// its LF samples, formed with lane shuffles and added into the team's tile `cfc` while the other wavefronts scatter.
+__device__ __forceinline__ void ReconLlf(const DevImage& im, int tx, int ty, const float* basis_small, const float* llf_scale) {
+  const ReconTile T;
+  const ReconLane me;
+  const int lane = me.lane, c = ChannelOfTeam(me.team);
+  float* const cfc = T.cfc3 + me.team * kTileF;
+  const int cxg = tx * 8 + (lane & 7), cyg = ty * 8 + (lane >> 3);
+  const bool inside = cxg < im.w8 && cyg < im.h8;
+  const float lf_g = im.lf_final[c][(size_t)min(cyg, im.h8 - 1) * im.w8 + min(cxg, im.w8 - 1)];
+  const float lfv = inside ? lf_g : 0.f;
+  const uint32_t info = T.ci[lane];
+  const bool valid = CellValid(info);
+  const int ix = CellIx(info), iy = CellIy(info), lcx = CellLog2Cx(info), lcy = CellLog2Cy(info);
+  const int cx = 1 << lcx, cy = 1 << lcy;
+  const int ox = (lane & 7) - ix, oy = (lane >> 3) - iy;
+  const float* Bx = basis_small + BasisSmallOffset(cx) + ix * cx;
+  const float* By = basis_small + BasisSmallOffset(cy) + iy * cy;
+  float bx[8], byv[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { bx[k] = (valid && k < cx) ? Bx[k] : 0.f; byv[k] = (valid && k < cy) ? By[k] : 0.f; }
+  const float sc = valid ? llf_scale[lcy * 32 + iy] * llf_scale[lcx * 32 + ix] / (float)(cx * cy) : 0.f;
+  float row = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const float v = __shfl(lfv, (lane - ix + k) & 63);
+    if (valid && k < cx) row += v * bx[k];
+  }
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const float v = __shfl(row, ((oy + k) * 8 + (lane & 7)) & 63);
+    if (valid && k < cy) acc += v * byv[k];
+  }
+  // (an add like the entries': a custom coefficient order may send an entry to an LLF position, and sums do not depend on who comes first)
+  if (valid) atomicAdd(&cfc[(oy * 8 + iy) * kLP + ox * 8 + ix], acc * sc);
+}
+
+// 1 / v through v_rcp_f32 (1 ulp; the term is a bias correction <= 0.15 / |v|)
+struct RcpQuotient {
+  __device__ __forceinline__ float operator()(float a, float f) const { return a * __builtin_amdgcn_rcpf(f); }
+};
+
+// The entry scatter, by all 768 threads: every entry of the tile's (block, channel) lists is one non-zero quantised coefficient; its
+// scan position k selects {stored index, weight} from the per-table scan list, the stored index gives the coefficient's place in the
+// varblock.  The lists of the three channels are walked as ONE range [0, T_y + T_x + T_b) (a 4K frame has about 270 luma and 30 + 30
+// chroma entries per tile: one trip).  An entry's cell comes from a binary search over the exclusive prefix of its channel's per-cell
+// entry counts (only origin cells have entries).  A luma entry is also what chroma from luma adds to X and B - the IDCT is linear and
+// the tile is inside one 64x64 chroma-from-luma tile - so it is added three times (dequantised once).  Adds into the zeroed tiles with
+// ds_add_f32: a position receives at most one own addend and one luma addend, two addends commute, so the sums do not depend on the
+// order the lanes arrive in.
+__device__ __forceinline__ void ReconScatter(const DevImage& im, int tx, int ty) {
+  const ReconTile T;
+  const int tid = threadIdx.x;
+  const size_t tile_cfl = (size_t)ty * im.wt + tx;
+  const float cfl_x = im.base_x + (float)im.ytox[tile_cfl] * im.inv_color_factor;
+  const float cfl_b = im.base_b + (float)im.ytob[tile_cfl] * im.inv_color_factor;
+  // the tile's group (four tiles per group side)
+  const uint32_t* entries = im.centries + (size_t)((ty >> 2) * im.xg + (tx >> 2) - im.centries_g0) * kGroupEntriesCap;
+  const uint32_t t0 = T.ctot[0], t01 = t0 + T.ctot[1], total = t01 + T.ctot[2];
+  const float qb3 = im.qbias[3];
+  for (uint32_t e = (uint32_t)tid; e < total; e += 768) {
+    const uint32_t t = (e >= t0) + (e >= t01);                     // team of this entry: 0 Y, 1 X, 2 B
+    const uint32_t el = e - (t == 0 ? 0u : (t == 1 ? t0 : t01));
+    const uint32_t* pre = T.cpre + t * 64;
+    uint32_t j = 0;
+#pragma unroll
+    for (int step = 32; step; step >>= 1) if (pre[j + step] <= el) j += step;
+    const uint32_t ent = entries[T.cstart[t * 64 + j] + (el - pre[j])];
+    const uint32_t k = ent & 0xFFFFu, nq = T.cnq[j];
+    if (k >= nq) continue;   // a list that a failed section left half-written must not index past the table
+    const int chan = ChannelOfTeam(t);
+    const U32x2 se = T.csc[j][(size_t)chan * nq + k];
+    const uint32_t meta = T.cmeta[j];
+    uint32_t ky, kx;
+    StoredToKyKx(se.x, meta & 15, meta & 16, &ky, &kx);
+    if (ky >= 64 || kx >= 64) continue;
+    const int32_t v = (int32_t)ent >> 16;
+    const float dm = t == 0 ? 1.0f : (t == 1 ? im.x_dm : im.b_dm);
+    const float o = DequantBias(v, im.qbias[chan], qb3, RcpQuotient()) * (T.cscale[j] * dm) * __uint_as_float(se.y);
+    const uint32_t at = ((j >> 3) * 8 + ky) * kLP + (j & 7) * 8 + kx;
+    atomicAdd(&T.cfc3[t * kTileF + at], o);
+    if (t == 0) {   // chroma from luma: X += cfl_x * Y, B += cfl_b * Y on the dequantised luma coefficient
+      if (cfl_x != 0.f) atomicAdd(&T.cfc3[kTileF + at], o * cfl_x);
+      if (cfl_b != 0.f) atomicAdd(&T.cfc3[2 * kTileF + at], o * cfl_b);
+    }
+  }
+}
+
+// The two 1-D IDCT passes over a team's tile, in place, each of the team's four wavefronts on its own share: the vertical pass gives
+// wavefront tw the column stripe [16 tw, 16 tw + 16) (everything a stripe's outputs depend on lies in the same columns), the
+// horizontal pass the row band [16 tw, 16 tw + 16).  A wavefront fetches all its operands before it stores, so a pass needs no
+// workgroup barrier inside.  The matrix cores take every 16x16 sub-block whose two cells across the pass agree (MfmaRows / MfmaCols):
+// vertical Basis_R^T (16 x R) * coefficients (R x 16), horizontal rows (16 x C) * Basis_C (C x 16), by v_mfma_f32_16x16x4_f32 (exact
+// f32, the same k-ordered fma chain as the vector path).  Lane l feeds A[l & 15][l >> 4] and B[l >> 4][l & 15], owns
+// D[4 * (l >> 4) + r][l & 15].  The vector ALUs take the rest: one lane = two adjacent lines x one 8-sample cell.
+// (Mirror images kept as two functions: merged into one template the kernel compiled to 8 - 10 % more instructions and two more VGPRs.)
+__device__ __forceinline__ void ReconVerticalPass(const float* Bl) {
+  const ReconTile T;
+  const ReconLane me;
+  const int lane = me.lane, tw = me.tw;
+  float* const cfc = T.cfc3 + me.team * kTileF;   // this team's tile
+  const uint32_t* ci = T.ci;
+  float* B816 = T.B816;
+  const int l16 = lane & 15, lq = lane >> 4;
+  F4 acc[4];
+  bool m[4];
+  const int x0 = tw * 16;
+#pragma unroll
+  for (int rb = 0; rb < 4; rb++) {
+    const uint32_t inf = ci[rb * 16 + tw * 2];
+    m[rb] = MfmaRows(inf, ci[rb * 16 + tw * 2 + 1]);   // wave-uniform
+    if (m[rb]) {
+      const int iy = CellIy(inf), lcy = CellLog2Cy(inf), R = 8 << lcy;
+      const float* cp = cfc + ((rb * 2 - iy) * 8 + lq) * kLP + x0 + l16;
+      if (R == 16) acc[rb] = MfmaChain<16>(B816 + 64 + lq * 16 + iy * 8 + l16, 64, cp, 4 * kLP);
+      else if (R == 32) acc[rb] = MfmaChain32L<true>(T.t32_lo, T.t32_hi, (iy * 8 + l16) * 4 + lq, cp, 4 * kLP);
+      else acc[rb] = MfmaChain64L<true>(T.t64, (iy * 8 + l16) * 4 + lq, cp, 4 * kLP);
+    }
+  }
+  // the rest on the vector ALUs.  One lane = two adjacent columns x one 8-row cell: every basis fetch feeds 16 FMAs.
+  const int x = x0 + (lane & 7) * 2, cr = lane >> 3;
+  const uint32_t info = ci[cr * 8 + (x >> 3)];
+  const bool valu = CellValid(info) && !MfmaRows(ci[(cr >> 1) * 16 + (x >> 4) * 2], ci[(cr >> 1) * 16 + (x >> 4) * 2 + 1]);
+  float a0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (valu) {
+    const int iy = CellIy(info), lcy = CellLog2Cy(info);
+    const int R = 8 << lcy;
+    const float* in = cfc + (cr - iy) * 8 * kLP + x;
+    if (R == 8) {            // the common sizes read their basis from LDS: no global load inside the pass
+#pragma unroll 2
+      for (int k = 0; k < 8; k++) { const float v0 = in[k * kLP], v1 = in[k * kLP + 1]; JXL_IDCT_STEP(B816 + k * 8, v0, v1) }
+    } else if (R == 16) {
+      const float* B = B816 + 64 + iy * 8;
+#pragma unroll 2
+      for (int k = 0; k < 16; k++) { const float v0 = in[k * kLP], v1 = in[k * kLP + 1]; JXL_IDCT_STEP(B + k * 16, v0, v1) }
+    } else {
+      const float* B = Bl + BasisAllOffset(R) + iy * 8;
+      for (int k = 0; k < R; k++) { const float v0 = in[k * kLP], v1 = in[k * kLP + 1]; JXL_IDCT_STEP(B + k * R, v0, v1) }
+    }
+  }
+  // every operand of this stripe is in registers: store
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int rb = 0; rb < 4; rb++)
+    if (m[rb]) {
+      float* o = cfc + (rb * 16 + 4 * lq) * kLP + x0 + l16;
+      o[0] = acc[rb].x; o[kLP] = acc[rb].y; o[2 * kLP] = acc[rb].z; o[3 * kLP] = acc[rb].w;
+    }
+  if (valu) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) { cfc[(cr * 8 + j) * kLP + x] = a0[j]; cfc[(cr * 8 + j) * kLP + x + 1] = a1[j]; }
+  }
+}
+
+__device__ __forceinline__ void ReconHorizontalPass(const float* Bl) {
+  const ReconTile T;
+  const ReconLane me;
+  const int lane = me.lane, tw = me.tw;
+  float* const cfc = T.cfc3 + me.team * kTileF;   // this team's tile
+  const uint32_t* ci = T.ci;
+  float* B816 = T.B816;
+  const int l16 = lane & 15, lq = lane >> 4;
+  F4 acc[4];
+  bool m[4];
+  const int y0 = tw * 16;
+#pragma unroll
+  for (int cs = 0; cs < 4; cs++) {
+    const uint32_t inf = ci[tw * 16 + cs * 2];
+    m[cs] = MfmaCols(inf, ci[tw * 16 + 8 + cs * 2]);
+    if (m[cs]) {
+      const int ix = CellIx(inf), lcx = CellLog2Cx(inf), C = 8 << lcx;
+      const float* ap = cfc + (y0 + l16) * kLP + (cs * 2 - ix) * 8 + lq;
+      if (C == 16) acc[cs] = MfmaChain<16>(ap, 4, B816 + 64 + lq * 16 + ix * 8 + l16, 64);
+      else if (C == 32) acc[cs] = MfmaChain32L<false>(T.t32_lo, T.t32_hi, (ix * 8 + l16) * 4 + lq, ap, 4);
+      else acc[cs] = MfmaChain64L<false>(T.t64, (ix * 8 + l16) * 4 + lq, ap, 4);
+    }
+  }
+  // the rest: two adjacent rows per lane
+  const int y = y0 + (lane & 7) * 2, cc = lane >> 3;
+  const uint32_t info = ci[(y >> 3) * 8 + cc];
+  const bool valu = CellValid(info) && !MfmaCols(ci[(y >> 4) * 16 + (cc >> 1) * 2], ci[(y >> 4) * 16 + 8 + (cc >> 1) * 2]);
+  float a0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (valu) {
+    const int ix = CellIx(info), lcx = CellLog2Cx(info);
+    const int C = 8 << lcx;
+    const float* in = cfc + y * kLP + (cc - ix) * 8;
+    if (C == 8) {
+#pragma unroll 2
+      for (int k = 0; k < 8; k++) { const float v0 = in[k], v1 = in[k + kLP]; JXL_IDCT_STEP(B816 + k * 8, v0, v1) }
+    } else if (C == 16) {
+      const float* B = B816 + 64 + ix * 8;
+#pragma unroll 2
+      for (int k = 0; k < 16; k++) { const float v0 = in[k], v1 = in[k + kLP]; JXL_IDCT_STEP(B + k * 16, v0, v1) }
+    } else {
+      const float* B = Bl + BasisAllOffset(C) + ix * 8;
+      for (int k = 0; k < C; k++) { const float v0 = in[k], v1 = in[k + kLP]; JXL_IDCT_STEP(B + k * C, v0, v1) }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int cs = 0; cs < 4; cs++)
+    if (m[cs]) {
+      float* o = cfc + (y0 + 4 * lq) * kLP + cs * 16 + l16;
+      o[0] = acc[cs].x; o[kLP] = acc[cs].y; o[2 * kLP] = acc[cs].z; o[3 * kLP] = acc[cs].w;
+    }
+  if (valu) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) { cfc[y * kLP + cc * 8 + j] = a0[j]; cfc[(y + 1) * kLP + cc * 8 + j] = a1[j]; }
+  }
+}
+
+// Copy-out of the row band the horizontal pass left in this wavefront's hands (no other wavefront wrote it: a wavefront fence is
+// enough), 16 bytes per lane, clipped to the padded frame.
+__device__ __forceinline__ void ReconCopyOut(const DevImage& im, int tx, int ty) {
+  const ReconTile T;
+  const ReconLane me;
+  const int lane = me.lane, tw = me.tw, c = ChannelOfTeam(me.team);
+  const float* const cfc = T.cfc3 + me.team * kTileF;
+  const int wp = im.wp, hp = im.hp;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const int l16 = lane & 15, lq = lane >> 4;
+  float* dst = im.xyb[c];
+  const int x4 = l16 * 4;
+  const int gx = tx * kTS + x4;
+#pragma unroll
+  for (int it = 0; it < 4; it++) {
+    const int yl = tw * 16 + lq + 4 * it;
+    const int gy = ty * kTS + yl;
+    const float* r = cfc + yl * kLP + x4;
+    const float4 o = make_float4(r[0], r[1], r[2], r[3]);
+    if (gx < wp && gy < hp) *(float4*)(dst + (size_t)gy * wp + gx) = o;
+  }
+}
 
 // One workgroup per 64x64 tile, all three channels (12 wavefronts: team t = wave / 4 owns channel Y, X, B; inside a team the four
 // wavefronts split the tile as the one-channel version did): dequantisation with chroma from luma, LF -> LLF, both IDCT passes in
@@ -326,307 +626,50 @@ constexpr int kTileF = kTS * kLP;   // floats of one channel's tile
 //   * the per-cell set-up (cell info, scale, table pointers, entry-list prefixes of the three channels) is done once per tile by
 //     wavefront 0; LLF of channel t is computed by the first wavefront of team t with lane shuffles while the others scatter.
 //   * 1 / v through v_rcp_f32 (1 ulp; the term is a bias correction <= 0.15 / |v|).
-__global__ __launch_bounds__(768, 6) void recon_tile_kernel(const DevImage* __restrict__ imgs, const float* basis_all, const float* basis_small,
+// The 7 of the launch bound is a register cap, not residency: 74 768 bytes of LDS let two workgroups onto a CU, six wavefronts per
+// SIMD, whatever the registers.  It keeps the allocator at the 72 VGPRs this kernel compiled to as one body (under a bound of 6 the
+// same code cut into phase functions takes 74).  A change that needs up to 80 VGPRs can go back to 6 at no cost in residency.
+__global__ __launch_bounds__(768, 7) void recon_tile_kernel(const DevImage* __restrict__ imgs, const float* basis_all, const float* basis_small,
                                                              const float* llf_scale, const float* basis_mfma) {
   JXL_PIXEL_PRIO();
-  extern __shared__ __align__(16) uint8_t smem_raw[];
-  float* cfc3 = (float*)smem_raw;                      // 3 * kTileF   coefficients -> columns done -> pixels; team order Y, X, B
-  float* B816 = cfc3 + 3 * kTileF;                     // 320  IDCT bases of the two common sizes (N = 8 at 0, N = 16 at 64)
-  float* cscale = B816 + 320;                          // 64   per cell: inv_global_scale / raw quant of its varblock
-  uint32_t* ci = (uint32_t*)(cscale + 64);             // 64   cell info
-  uint32_t* cmeta = ci + 64;                           // 64   log2 of the table pitch | transposed << 4
-  uint32_t* cnq = cmeta + 64;                          // 64   entries per channel of the cell's dequant table
-  uint32_t* cpre = cnq + 64;                           // 3 x 64   exclusive prefix of the entry counts per team ...
-  uint32_t* cstart = cpre + 3 * 64;                    // 3 x 64   ... and where each origin cell's entries start in the group's list
-  uint32_t* ctot = cstart + 3 * 64;                    // 4    totals per team
-  const U32x2** csc = (const U32x2**)(ctot + 4);       // 64   scan list of the cell's quant table
-  float4* t32_lo = (float4*)(csc + 64);                // 128  k-contiguous 32-point basis, first / second four k-steps of lane (n, q) = [n * 4 + q]
-  float4* t32_hi = t32_lo + 128;                       // 128
-  float4* t64 = t32_hi + 128;                          // 4 x 256  the 64-point basis, quarter j of lane (n, q) = [j * 256 + n * 4 + q]
+  const ReconTile T;
   const DevImage& im = imgs[blockIdx.y];
   const int tile = blockIdx.x;
   if (tile >= im.wt * im.ht) return;
   const int tid = threadIdx.x;
   const int tx = tile % im.wt, ty = tile / im.wt;
   if (ty < im.dec_gy0 * 4 || ty >= im.dec_gy1 * 4) return;   // outside the decoded band (4 tile rows per group row)
-  const int wave = tid >> 6, lane = tid & 63, team = wave >> 2, tw = wave & 3;
-  const int c = team == 0 ? 1 : (team == 1 ? 0 : 2);          // channel of this wavefront's team
-  const int wp = im.wp, hp = im.hp;
   // the tiles start as zeros: only non-zero coefficients exist in the entry lists
   {
-    float4* z = (float4*)cfc3;
+    float4* z = (float4*)T.cfc3;
     for (int i = tid; i < 3 * kTileF / 4; i += 768) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  int bad = 0, has64 = 0;
+  // wavefront 0 prepares the cells, the next ones stage the 8- / 16-point bases and the 32-point matrix-core table
+  int bad = 0;
   if (tid < 64) {
-    const int cx = tx * 8 + (tid & 7), cy = ty * 8 + (tid >> 3);
-    const bool inside = cx < im.w8 && cy < im.h8;
-    const size_t cell_g = (size_t)min(cy, im.h8 - 1) * im.w8 + min(cx, im.w8 - 1);
-    const size_t ncells = (size_t)im.w8 * im.h8;
-    const uint32_t info_g = im.cellinfo[cell_g];
-    const uint32_t rq_g = im.rawq[cell_g];
-    U32x2 blk[3];
-    blk[0] = im.cblk[ncells + cell_g]; blk[1] = im.cblk[cell_g]; blk[2] = im.cblk[2 * ncells + cell_g];   // team order: Y, X, B
-    const uint32_t info = inside ? info_g : 0u;
-    const uint32_t rqv = inside ? rq_g : 1u;
-    const int ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
-    if (inside) {
-      if (!(info >> 31)) bad = 1;
-      else {
-        const int ox = (tid & 7) - ix, oy = (tid >> 3) - iy;
-        // blocks larger than the tile, the rare special 8x8 transforms, and blocks that do not start on a multiple of their own size
-        // (every encoder aligns them, the format's placement rule does not; the matrix-core sub-blocks below rely on it) are left
-        // to the generic kernels
-        bad = ox < 0 || oy < 0 || ox + (1 << lcx) > 8 || oy + (1 << lcy) > 8 || Special(info & 0xFF) ||
-              (ox & ((1 << lcx) - 1)) != 0 || (oy & ((1 << lcy) - 1)) != 0;
-      }
-    }
-    const bool valid = (info >> 31) && !bad;
-    has64 = valid && (lcx == 3 || lcy == 3);
-    {  // (wavefront 0 is the only writer of the per-cell tables; the flag travels with them through the barrier below)
-      const uint64_t any = __ballot(has64);
-      if (tid == 0) ctot[3] = any != 0;
-    }
-    const uint32_t q = t_quant_table[valid ? (info & 0xFF) : 0];
-    const uint32_t rq_origin = (uint32_t)__shfl((int)rqv, valid ? tid - iy * 8 - ix : tid);
-    const uint32_t lng = 3 + max(lcx, lcy);
-    const bool transposed = lcy >= lcx;   // the stored layout of a varblock has its longer side horizontal (squares: transposed too)
-    ci[tid] = info;
-    cscale[tid] = im.inv_global_scale / (float)rq_origin;
-    cmeta[tid] = lng | (transposed ? 16u : 0u);
-    cnq[tid] = im.dq_n[q];
-    csc[tid] = im.scan[q];
-    // entry lists of the varblocks that start in this tile; a list a failed section left unwritten is treated as empty
-    const bool origin = valid && ix == 0 && iy == 0;
-    uint32_t cnt[3], sum[3];
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-      cnt[t] = origin ? blk[t].y : 0u;
-      if (cnt[t] > 65536u || blk[t].x > kGroupEntriesCap - cnt[t]) cnt[t] = 0;
-      sum[t] = cnt[t];   // inclusive scans over the wavefront
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-      for (int t = 0; t < 3; t++) {
-        const uint32_t a = (uint32_t)__shfl_up((int)sum[t], d);
-        if (tid >= d) sum[t] += a;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-      cpre[t * 64 + tid] = sum[t] - cnt[t];
-      cstart[t * 64 + tid] = blk[t].x;
-      if (tid == 63) ctot[t] = sum[t];
-    }
+    bad = ReconCellSetup(im, tx, ty);
   } else if (tid < 64 + 320) {
-    B816[tid - 64] = basis_all[tid - 64];   // basis_all holds N = 8 at offset 0 and N = 16 at offset 64
+    T.B816[tid - 64] = basis_all[tid - 64];   // basis_all holds N = 8 at offset 0 and N = 16 at offset 64
   } else if (tid < 64 + 320 + 256) {
     const int i = tid - (64 + 320);         // 16-byte piece i of the 32-point table: run (n, q) = i >> 1, half i & 1
     const float4 v = ((const float4*)basis_mfma)[i];
-    if (i & 1) t32_hi[i >> 1] = v; else t32_lo[i >> 1] = v;
+    if (i & 1) T.t32_hi[i >> 1] = v; else T.t32_lo[i >> 1] = v;
   }
   if (im.num_passes > 1) bad = 1;   // progressive frames: the passes' entries are summed as integers first (expand kernels, generic path)
   if (__syncthreads_or(bad)) {
     if (tid == 0) im.tile_list[atomicAdd(&im.status[1], 1u)] = (uint32_t)tile;
     return;
   }
-  if (ctot[3]) {   // the tile holds a 64-point varblock: stage that table (16 KB; the barrier before the passes covers it)
-    for (int i = tid; i < 1024; i += 768) t64[(i & 3) * 256 + (i >> 2)] = ((const float4*)(basis_mfma + 1024))[i];
+  if (T.ctot[3]) {   // the tile holds a 64-point varblock: stage that table (16 KB; the barrier before the passes covers it)
+    for (int i = tid; i < 1024; i += 768) T.t64[(i & 3) * 256 + (i >> 2)] = ((const float4*)(basis_mfma + 1024))[i];
   }
-  const float* const Bl = basis_all;
-  float* const cfc = cfc3 + team * kTileF;   // this team's tile
-  // ---- LLF (first wavefront of each team): lowest cx*cy coefficients of every varblock = scaled 2-D DCT of its LF samples, by lane shuffles
-  if (tw == 0) {
-    const int cxg = tx * 8 + (lane & 7), cyg = ty * 8 + (lane >> 3);
-    const bool inside = cxg < im.w8 && cyg < im.h8;
-    const float lf_g = im.lf_final[c][(size_t)min(cyg, im.h8 - 1) * im.w8 + min(cxg, im.w8 - 1)];
-    const float lfv = inside ? lf_g : 0.f;
-    const uint32_t info = ci[lane];
-    const bool valid = info >> 31;
-    const int ix = (info >> 8) & 31, iy = (info >> 13) & 31, lcx = (info >> 18) & 7, lcy = (info >> 21) & 7;
-    const int cx = 1 << lcx, cy = 1 << lcy;
-    const int ox = (lane & 7) - ix, oy = (lane >> 3) - iy;
-    const float* Bx = basis_small + (cx * cx - 1) / 3 + ix * cx;
-    const float* By = basis_small + (cy * cy - 1) / 3 + iy * cy;
-    float bx[8], byv[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) { bx[k] = (valid && k < cx) ? Bx[k] : 0.f; byv[k] = (valid && k < cy) ? By[k] : 0.f; }
-    const float sc = valid ? llf_scale[lcy * 32 + iy] * llf_scale[lcx * 32 + ix] / (float)(cx * cy) : 0.f;
-    float row = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const float v = __shfl(lfv, (lane - ix + k) & 63);
-      if (valid && k < cx) row += v * bx[k];
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const float v = __shfl(row, ((oy + k) * 8 + (lane & 7)) & 63);
-      if (valid && k < cy) acc += v * byv[k];
-    }
-    // (an add like the entries': a custom coefficient order may send an entry to an LLF position, and sums do not depend on who comes first)
-    if (valid) atomicAdd(&cfc[(oy * 8 + iy) * kLP + ox * 8 + ix], acc * sc);
-  }
-  // ---- dequantisation (+ chroma from luma) of the non-zero coefficients, scattered to their places
-  {
-    const size_t tile_cfl = (size_t)ty * im.wt + tx;
-    const float cfl_x = im.base_x + (float)im.ytox[tile_cfl] * im.inv_color_factor;
-    const float cfl_b = im.base_b + (float)im.ytob[tile_cfl] * im.inv_color_factor;
-    // the tile's group (four tiles per group side)
-    const uint32_t* entries = im.centries + (size_t)((ty >> 2) * im.xg + (tx >> 2) - im.centries_g0) * kGroupEntriesCap;
-    const uint32_t t0 = ctot[0], t01 = t0 + ctot[1], total = t01 + ctot[2];
-    const float qb3 = im.qbias[3];
-    for (uint32_t e = (uint32_t)tid; e < total; e += 768) {
-      const uint32_t t = (e >= t0) + (e >= t01);                     // team of this entry: 0 Y, 1 X, 2 B
-      const uint32_t el = e - (t == 0 ? 0u : (t == 1 ? t0 : t01));
-      const uint32_t* pre = cpre + t * 64;
-      uint32_t j = 0;
-#pragma unroll
-      for (int step = 32; step; step >>= 1) if (pre[j + step] <= el) j += step;
-      const uint32_t ent = entries[cstart[t * 64 + j] + (el - pre[j])];
-      const uint32_t k = ent & 0xFFFFu, nq = cnq[j];
-      if (k >= nq) continue;   // a list that a failed section left half-written must not index past the table
-      const int chan = t == 0 ? 1 : (t == 1 ? 0 : 2);
-      const U32x2 se = csc[j][(size_t)chan * nq + k];
-      const uint32_t meta = cmeta[j];
-      const uint32_t lng = meta & 15, p = se.x;
-      const uint32_t r = p >> lng, cc = p & ((1u << lng) - 1);
-      const uint32_t ky = (meta & 16) ? cc : r, kx = (meta & 16) ? r : cc;
-      if (ky >= 64 || kx >= 64) continue;
-      const int32_t v = (int32_t)ent >> 16;
-      const float dm = t == 0 ? 1.0f : (t == 1 ? im.x_dm : im.b_dm);
-      const float o = DequantBias(v, im.qbias[chan], qb3) * (cscale[j] * dm) * __uint_as_float(se.y);
-      const uint32_t at = ((j >> 3) * 8 + ky) * kLP + (j & 7) * 8 + kx;
-      atomicAdd(&cfc3[t * kTileF + at], o);
-      if (t == 0) {   // chroma from luma: X += cfl_x * Y, B += cfl_b * Y on the dequantised luma coefficient
-        if (cfl_x != 0.f) atomicAdd(&cfc3[kTileF + at], o * cfl_x);
-        if (cfl_b != 0.f) atomicAdd(&cfc3[2 * kTileF + at], o * cfl_b);
-      }
-    }
-  }
+  if (ReconLane().tw == 0) ReconLlf(im, tx, ty, basis_small, llf_scale);
+  ReconScatter(im, tx, ty);
   __syncthreads();
-  const int l16 = tid & 15, lq = lane >> 4;
-  // ---- vertical pass, in place: wavefront = column stripe.  Matrix cores for every 16x16 sub-block that lies inside a varblock
-  // of at least 16 points both ways: Basis_R^T (16 x R) * coefficients (R x 16) by v_mfma_f32_16x16x4_f32 (exact f32, the same
-  // k-ordered fma chain as the VALU path).  Lane l feeds A[l & 15][l >> 4] and B[l >> 4][l & 15], owns D[4 * (l >> 4) + r][l & 15].
-  {
-    F4 acc[4];
-    bool m[4];
-    const int x0 = tw * 16;
-#pragma unroll
-    for (int rb = 0; rb < 4; rb++) {
-      const uint32_t inf = ci[rb * 16 + tw * 2];
-      m[rb] = MfmaRows(inf, ci[rb * 16 + tw * 2 + 1]);   // wave-uniform
-      if (m[rb]) {
-        const int iy = (inf >> 13) & 31, lcy = (inf >> 21) & 7, R = 8 << lcy;
-        const float* cp = cfc + ((rb * 2 - iy) * 8 + lq) * kLP + x0 + l16;
-        if (R == 16) acc[rb] = MfmaChain<16>(B816 + 64 + lq * 16 + iy * 8 + l16, 64, cp, 4 * kLP);
-        else if (R == 32) acc[rb] = MfmaChain32L<true>(t32_lo, t32_hi, (iy * 8 + l16) * 4 + lq, cp, 4 * kLP);
-        else acc[rb] = MfmaChain64L<true>(t64, (iy * 8 + l16) * 4 + lq, cp, 4 * kLP);
-      }
-    }
-    // the rest on the vector ALUs.  One lane = two adjacent columns x one 8-row cell: every basis fetch feeds 16 FMAs.
-    const int x = x0 + (lane & 7) * 2, cr = lane >> 3;
-    const uint32_t info = ci[cr * 8 + (x >> 3)];
-    const bool valu = (info >> 31) && !MfmaRows(ci[(cr >> 1) * 16 + (x >> 4) * 2], ci[(cr >> 1) * 16 + (x >> 4) * 2 + 1]);
-    float a0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (valu) {
-      const int iy = (info >> 13) & 31, lcy = (info >> 21) & 7;
-      const int R = 8 << lcy;
-      const float* in = cfc + (cr - iy) * 8 * kLP + x;
-      if (R == 8) {            // the common sizes read their basis from LDS: no global load inside the pass
-#pragma unroll 2
-        for (int k = 0; k < 8; k++) { const float v0 = in[k * kLP], v1 = in[k * kLP + 1]; JXL_IDCT_STEP(B816 + k * 8, v0, v1) }
-      } else if (R == 16) {
-        const float* B = B816 + 64 + iy * 8;
-#pragma unroll 2
-        for (int k = 0; k < 16; k++) { const float v0 = in[k * kLP], v1 = in[k * kLP + 1]; JXL_IDCT_STEP(B + k * 16, v0, v1) }
-      } else {
-        const float* B = Bl + (R * R - 64) / 3 + iy * 8;
-        for (int k = 0; k < R; k++) { const float v0 = in[k * kLP], v1 = in[k * kLP + 1]; JXL_IDCT_STEP(B + k * R, v0, v1) }
-      }
-    }
-    // every operand of this stripe is in registers: store
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int rb = 0; rb < 4; rb++)
-      if (m[rb]) {
-        float* o = cfc + (rb * 16 + 4 * lq) * kLP + x0 + l16;
-        o[0] = acc[rb].x; o[kLP] = acc[rb].y; o[2 * kLP] = acc[rb].z; o[3 * kLP] = acc[rb].w;
-      }
-    if (valu) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) { cfc[(cr * 8 + j) * kLP + x] = a0[j]; cfc[(cr * 8 + j) * kLP + x + 1] = a1[j]; }
-    }
-  }
+  ReconVerticalPass(basis_all);
   __syncthreads();
-  // ---- horizontal pass, in place: wavefront = row band: rows (16 x C) * Basis_C (C x 16)
-  {
-    F4 acc[4];
-    bool m[4];
-    const int y0 = tw * 16;
-#pragma unroll
-    for (int cs = 0; cs < 4; cs++) {
-      const uint32_t inf = ci[tw * 16 + cs * 2];
-      m[cs] = MfmaCols(inf, ci[tw * 16 + 8 + cs * 2]);
-      if (m[cs]) {
-        const int ix = (inf >> 8) & 31, lcx = (inf >> 18) & 7, C = 8 << lcx;
-        const float* ap = cfc + (y0 + l16) * kLP + (cs * 2 - ix) * 8 + lq;
-        if (C == 16) acc[cs] = MfmaChain<16>(ap, 4, B816 + 64 + lq * 16 + ix * 8 + l16, 64);
-        else if (C == 32) acc[cs] = MfmaChain32L<false>(t32_lo, t32_hi, (ix * 8 + l16) * 4 + lq, ap, 4);
-        else acc[cs] = MfmaChain64L<false>(t64, (ix * 8 + l16) * 4 + lq, ap, 4);
-      }
-    }
-    // the rest: two adjacent rows per lane
-    const int y = y0 + (lane & 7) * 2, cc = lane >> 3;
-    const uint32_t info = ci[(y >> 3) * 8 + cc];
-    const bool valu = (info >> 31) && !MfmaCols(ci[(y >> 4) * 16 + (cc >> 1) * 2], ci[(y >> 4) * 16 + 8 + (cc >> 1) * 2]);
-    float a0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (valu) {
-      const int ix = (info >> 8) & 31, lcx = (info >> 18) & 7;
-      const int C = 8 << lcx;
-      const float* in = cfc + y * kLP + (cc - ix) * 8;
-      if (C == 8) {
-#pragma unroll 2
-        for (int k = 0; k < 8; k++) { const float v0 = in[k], v1 = in[k + kLP]; JXL_IDCT_STEP(B816 + k * 8, v0, v1) }
-      } else if (C == 16) {
-        const float* B = B816 + 64 + ix * 8;
-#pragma unroll 2
-        for (int k = 0; k < 16; k++) { const float v0 = in[k], v1 = in[k + kLP]; JXL_IDCT_STEP(B + k * 16, v0, v1) }
-      } else {
-        const float* B = Bl + (C * C - 64) / 3 + ix * 8;
-        for (int k = 0; k < C; k++) { const float v0 = in[k], v1 = in[k + kLP]; JXL_IDCT_STEP(B + k * C, v0, v1) }
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int cs = 0; cs < 4; cs++)
-      if (m[cs]) {
-        float* o = cfc + (y0 + 4 * lq) * kLP + cs * 16 + l16;
-        o[0] = acc[cs].x; o[kLP] = acc[cs].y; o[2 * kLP] = acc[cs].z; o[3 * kLP] = acc[cs].w;
-      }
-    if (valu) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) { cfc[y * kLP + cc * 8 + j] = a0[j]; cfc[(y + 1) * kLP + cc * 8 + j] = a1[j]; }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // ---- copy-out of this wavefront's row band: 16 bytes per lane
-    float* dst = im.xyb[c];
-    const int x4 = l16 * 4;
-    const int gx = tx * kTS + x4;
-#pragma unroll
-    for (int it = 0; it < 4; it++) {
-      const int yl = y0 + lq + 4 * it;
-      const int gy = ty * kTS + yl;
-      const float* r = cfc + yl * kLP + x4;
-      const float4 o = make_float4(r[0], r[1], r[2], r[3]);
-      if (gx < wp && gy < hp) *(float4*)(dst + (size_t)gy * wp + gx) = o;
-    }
-  }
+  ReconHorizontalPass(basis_all);
+  ReconCopyOut(im, tx, ty);
 }
 
 // ------------------------------------------------------------------ LDS-tiled loop filters
@@ -1418,8 +1461,7 @@ void LaunchLfOutput(const DevImage* imgs, int nimg, size_t max_cells, hipStream_
 
 void LaunchReconTiles(const DevImage* imgs, int nimg, int max_tiles, const float* basis_all, const float* basis_small,
                       const float* llf_scale, const float* basis_mfma, hipStream_t s) {
-  // three tiles, B816, four per-cell words + 2 x 3 prefix words per cell, totals, per-cell scan-list pointers
-  const size_t lds = (size_t)(3 * kTileF + 320 + 64 * 4 + 64 * 6 + 4 + 128 + 1024 + 4096) * 4;   // + the 32- and 64-point matrix-core tables
+  const size_t lds = ReconTileLds().end;
   static bool raised = false;
   if (!raised) { (void)hipFuncSetAttribute((const void*)recon_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); raised = true; }
   hipLaunchKernelGGL(recon_tile_kernel, dim3(max_tiles, nimg), dim3(768), lds, s, imgs, basis_all, basis_small, llf_scale, basis_mfma);
